@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- pss-bam per-read hot path on MI355X: aligned reads/s (whole job) + HBM roofline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--scaling strong|weak]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--scaling strong|weak] [--dump-outputs DIR]
 
 One "step" = one complete pass of the hot path over the synthetic record stream: every
 alignment record of every rank's shard decoded, filtered and tallied, counters reduced to
@@ -30,6 +30,11 @@ Rank 0 prints ONE JSON line (contract in the task statement) with these extra ob
                on a bounded prefix of the same stream (1 core: the reference has no threads)
   e2e          (N=1) bin/pss-bam on a generated level-1 BGZF BAM + FASTA of the named shape:
                wall seconds, reads/s, per-stage seconds, tables checked against the resident tally
+
+--dump-outputs DIR writes, after the timed steps, the tables the last timed step handed back (what
+Engine.finish() returns: fwd, rev, k5 and k3 when fragkon is fused in, stats; rank 0's reduced
+block for N > 1) as DIR/<name>.npy in float64.  The workload is a function of the arguments
+alone, so two builds run with the same arguments can be compared table for table.
 """
 from __future__ import annotations
 
@@ -134,6 +139,8 @@ def parse_args(argv=None):
     ap.add_argument("--e2e-reads", type=int, default=None,
                     help="reads of the file-to-tables leg (N=1; default: the configuration's count, bounded by free disk)")
     ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the tables of the last timed step as DIR/<name>.npy (float64)")
     return ap.parse_args(argv)
 
 
@@ -227,6 +234,35 @@ def traffic_entry(config: str, unsorted: bool, klen, region_len: int, reads_per_
         except (KeyError, TypeError):
             continue
     return None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: Path, counters, lay: dict, stat_names: list[str]) -> None:
+    """the counter block of one step -> DIR/{fwd,rev[,k5,k3],stats}.npy, float64 (exact below 2^53)"""
+    import numpy as np
+    rows, bins = lay["rows"], lay["bins"]
+    tables = {}
+    if rows:
+        tables["fwd"] = counters[lay["fwd"]:lay["fwd"] + rows * 16].reshape(rows, 16)
+        tables["rev"] = counters[lay["rev"]:lay["rev"] + rows * 16].reshape(rows, 16)
+    if bins:
+        tables["k5"] = counters[lay["k5"]:lay["k5"] + bins]
+        tables["k3"] = counters[lay["k3"]:lay["k3"] + bins]
+    tables["stats"] = counters[lay["stats"]:lay["stats"] + len(stat_names)]
+    n_words = sum(t.size for t in tables.values())
+    if n_words * 8 > DUMP_LIMIT_BYTES:
+        # only a --region-len far beyond every configuration's gets here: a fixed, seeded sample of
+        # the rows of both end tables, their row numbers beside them
+        budget = ((DUMP_LIMIT_BYTES - 4096) // 8 - (n_words - 2 * rows * 16)) // 33   # 4 KB for the .npy headers
+        pick = np.sort(np.random.default_rng(0).choice(rows, size=budget, replace=False))
+        tables["fwd"], tables["rev"], tables["rows"] = tables["fwd"][pick], tables["rev"][pick], pick
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, t in tables.items():
+        if t.size and int(t.max()) >= 1 << 53:
+            raise SystemExit(f"--dump-outputs: {name} holds a count float64 cannot carry exactly")
+        np.save(out_dir / f"{name}.npy", t.astype(np.float64))
 
 
 def main():
@@ -363,6 +399,8 @@ def main():
         f"on device in {len(wl.blocks)} blocks, {time.time() - t0:.1f}s")
     m = measure(wl, args.steps, args.warmup)
     stats = {nm: int(m["counters"][lay["stats"] + i]) for i, nm in enumerate(pkg.ST_NAMES)}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), m["counters"], lay, pkg.ST_NAMES)
 
     # algorithmic bytes: record incl. its length word + one u32 index entry +
     # 2*(N+2) reference bytes per read (+ 2k when the k-mer tally is fused in)
@@ -773,7 +811,7 @@ def cpu_baseline(pkg, synth, eng, cfg, cd, region_len, klen, n_sample, names, cp
     parity = (f"bit-exact vs {kind} on the {n_sample}-read CPU sample" if ok
               else f"MISMATCH vs {kind} on the CPU sample")
     out = {"value": value, "unit": "reads/s", "cores": 1, "kind": kind, "sample": sample}
-    if cpu_cores > 1 and have_ref:
+    if cpu_cores > 1:
         try:   # bounded: <= 500 k reads per process, so the default run stays within minutes
             out["all_cores"] = cpu_all_cores(pkg, synth, scfg, region_len, names, tmp, o, cpu_cores,
                                              min(500_000, max(100_000, n_sample // 4), max(1, int(scfg.n_reads) // cpu_cores)))
@@ -788,7 +826,9 @@ def cpu_all_cores(pkg, synth, scfg, region_len, names, tmp, o, procs, per_shard)
     sorted stream, tables summed (tallies are additive) and checked against the engine's tables
     for the same reads.  Load time (every process parses the FASTA) is measured by the same
     number of concurrent processes on an empty SAM and subtracted.  `cores` in the result is what
-    the processes could actually use: min(process count, cgroup CPU quota)."""
+    the processes could actually use: min(process count, cgroup CPU quota).  Without a reference
+    build (oracle/_ref) the CPU restatement takes its place, one thread per shard (ctypes releases
+    the GIL), each loading the FASTA itself, as cpu_baseline does for the one-core figure."""
     import numpy as np
     import pssbam_testlib as tl
     from concurrent.futures import ThreadPoolExecutor
@@ -803,13 +843,27 @@ def cpu_all_cores(pkg, synth, scfg, region_len, names, tmp, o, procs, per_shard)
     with ThreadPoolExecutor(min(threads, 32)) as ex:   # the writers release the GIL
         list(ex.map(lambda k: synth.sam_host(scfg, k * per_shard, per_shard, tmp / f"shard{k}.sam"), range(procs)))
 
-    variant = os.environ.get("PSSBAM_REF_VARIANT", "pss-bam.O2")
+    if tl.have_ref():
+        variant = os.environ.get("PSSBAM_REF_VARIANT", "pss-bam.O2")
+        kind, what = "reference", f"oracle/_ref/{variant} processes"
+
+        def run(sam, prefix):
+            return tl.run_ref_pss(fa, sam, prefix, o, variant=variant, timeout=3000)[:2]
+    else:
+        orc = tl.Oracle()
+        kind, what = "port", "oracle/liboracle.so (CPU restatement) threads"
+
+        def run(sam, prefix):
+            g = orc.load_genome(fa)
+            try:
+                return orc.pss(g, sam, o)[:2]
+            finally:
+                orc.free_genome(g)
 
     def wave(inputs, tag):
         t = time.perf_counter()
         with ThreadPoolExecutor(procs) as ex:
-            res = list(ex.map(lambda kv: tl.run_ref_pss(fa, kv[1], tmp / f"{tag}{kv[0]}", o, variant=variant,
-                                                        timeout=3000)[:2], enumerate(inputs)))
+            res = list(ex.map(lambda kv: run(kv[1], tmp / f"{tag}{kv[0]}"), enumerate(inputs)))
         return time.perf_counter() - t, res
 
     t_load, _ = wave([empty] * procs, "l")
@@ -827,9 +881,9 @@ def cpu_all_cores(pkg, synth, scfg, region_len, names, tmp, o, procs, per_shard)
     e2.close()
     ok = bool(np.array_equal(got.fwd, fwd) and np.array_equal(got.rev, rev))
     eff = effective_cpus()
-    return {"value": total / max(t_full - t_load, 1e-9), "unit": "reads/s", "cores": min(float(procs), eff),
+    return {"value": total / max(t_full - t_load, 1e-9), "unit": "reads/s", "cores": min(float(procs), eff), "kind": kind,
             "processes": procs, "host_cpus_effective": eff, "host_cpus_logical": os.cpu_count(),
-            "sample": f"{procs} concurrent oracle/_ref/{variant} processes x {per_shard} reads each (consecutive shards of "
+            "sample": f"{procs} concurrent {what} x {per_shard} reads each (consecutive shards of "
                       f"the sorted stream, FASTA of contigs 0..{last_contig}) on {eff:g} effective CPUs (cgroup cpu.max); "
                       f"wall {t_full:.1f}s minus {t_load:.1f}s for the same {procs} processes on an empty SAM",
             "parity_check": "summed tables bit-exact vs the engine" if ok else "MISMATCH vs the engine"}

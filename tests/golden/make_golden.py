@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Regenerates tests/golden/* by running the UNMODIFIED reference (oracle/_ref, built by
-oracle/Makefile from /root/reference) on small synthetic inputs made by
+oracle/Makefile from the reference sources) on small synthetic inputs made by
 tests/pssbam_testlib.py.  Only data is written here: inputs (FASTA, SAM, and the BAM
-encoding of the same records) and the reference's outputs for them.
+encoding of the same records) and the reference's outputs for them; for the larger fuzz
+sets of test_oracle_vs_ref.py only the outputs (fuzz_ref.npz: report texts, sparse k-mer
+tables, and a digest of the inputs each was made from), since the tests regenerate those
+inputs from their seeds.
 
-    python tests/golden/make_golden.py        # needs oracle/_ref (i.e. /root/reference)
+    python tests/golden/make_golden.py        # needs oracle/_ref (i.e. the reference sources)
 
 The committed fixtures were produced by exactly this script.
 """
@@ -16,9 +19,56 @@ from pathlib import Path
 HERE = Path(__file__).resolve().parent
 sys.path.insert(0, str(HERE.parent))
 
+import pssbam_testlib as tl  # noqa: E402
 from pssbam_testlib import (FkOpts, PssOpts, build_oracle, fuzz_dataset, have_ref, ref_safe,  # noqa: E402
                             run_ref_fragkon, run_ref_gkc, run_ref_pss, write_bam, write_fasta, write_sam)
 import numpy as np  # noqa: E402
+
+
+def fuzz_vectors(work: Path) -> dict:
+    """the reference's outputs on the fuzz sets of test_oracle_vs_ref.py, generated in `work`"""
+    import os
+    out = {}
+    text = lambda s: np.frombuffer(s.encode(), dtype=np.uint8)  # noqa: E731
+    cwd = os.getcwd()
+    try:
+        for seed in range(tl.FUZZ_SEEDS):
+            d = work / f"pss{seed}"
+            d.mkdir()
+            os.chdir(d)
+            fa, sam, opts = tl.pss_fuzz_case(seed)
+            for trial, o in enumerate(opts):
+                key = f"pss_{seed}_{trial}"
+                _, _, ct, rt, _ = run_ref_pss(Path(fa), Path(sam), Path(f"ref{trial}"), o)
+                out[key + "_counts"], out[key + "_rates"] = text(ct), text(rt)
+                out[key + "_inputs"] = np.array(tl.inputs_digest([fa, sam], o))
+        for seed in range(tl.FUZZ_SEEDS):
+            d = work / f"fk{seed}"
+            d.mkdir()
+            os.chdir(d)
+            fa, trials = tl.fk_fuzz_case(seed)
+            for trial, (o, sam) in enumerate(trials):
+                key = f"fk_{seed}_{trial}"
+                k5, k3, _, _ = run_ref_fragkon(Path(fa), Path(sam), o)
+                out[key + "_idx"], out[key + "_k5"], out[key + "_k3"] = tl.sparse(k5, k3)
+                out[key + "_inputs"] = np.array(tl.inputs_digest([fa, sam], o))
+        d = work / "gz"
+        d.mkdir()
+        os.chdir(d)
+        fa, fagz, sam, o = tl.gz_fuzz_case()
+        out["gz_counts"] = text(run_ref_pss(Path(fa), Path(sam), Path("p0"), o)[2])
+        out["gz_counts_O2"] = text(run_ref_pss(Path(fagz), Path(sam), Path("p1"), o, variant="pss-bam.O2")[2])
+        out["gz_inputs"] = np.array(tl.inputs_digest([fa, sam], o))
+        for k in tl.GKC_KS:
+            d = work / f"gkc{k}"
+            d.mkdir()
+            os.chdir(d)
+            fa = tl.gkc_fuzz_case(k)
+            out[f"gkc_{k}_idx"], out[f"gkc_{k}_counts"] = tl.sparse(run_ref_gkc(Path(fa), k)[0])
+            out[f"gkc_{k}_inputs"] = np.array(tl.inputs_digest([fa]))
+    finally:
+        os.chdir(cwd)
+    return out
 
 
 def main():
@@ -92,6 +142,12 @@ def main():
 
     (HERE / "manifest.json").write_text(json.dumps(manifest, indent=1) + "\n")
     print(f"wrote {len(manifest['cases'])} golden cases to {HERE}")
+
+    import tempfile
+    with tempfile.TemporaryDirectory(prefix="pssbam_golden_") as work:
+        vec = fuzz_vectors(Path(work))
+    np.savez_compressed(tl.FUZZ_REF, **vec)
+    print(f"wrote {len(vec)} fuzz-set arrays to {tl.FUZZ_REF}")
 
 
 if __name__ == "__main__":

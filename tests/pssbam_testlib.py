@@ -754,3 +754,79 @@ def raw_records(refs: list[tuple[str, int]], recs: list[Rec]) -> np.ndarray:
 def loaded_contigs(contigs: list[tuple[str, str]]) -> list[tuple[str, np.ndarray]]:
     """FASTA text form -> the in-memory form init_genome produces (upper case bytes)"""
     return [(cid, np.frombuffer(seq.upper().encode(), dtype=np.uint8).copy()) for cid, seq in contigs]
+
+
+# ----------------------------------------------------------------------------------
+# the fuzz sets of test_oracle_vs_ref.py and the reference's stored outputs for them
+# (tests/golden/fuzz_ref.npz, written by tests/golden/make_golden.py from oracle/_ref)
+# ----------------------------------------------------------------------------------
+
+FUZZ_REF = ROOT / "tests" / "golden" / "fuzz_ref.npz"
+FUZZ_SEEDS = 12
+GKC_KS = (1, 3, 4, 7, 9)
+
+# Every case writes its inputs into the current directory under relative names: the pss-bam
+# reports echo the -F/-B/-o strings, so the stored report text only matches under the same names.
+
+
+def pss_fuzz_case(seed: int, n: int = 1500) -> tuple[str, str, list[PssOpts]]:
+    """-> (fasta, sam, the options of the three trials)"""
+    contigs, refs, recs = fuzz_dataset(seed, n)
+    fa, sam = f"g{seed}.fa", f"a{seed}.sam"
+    write_fasta(Path(fa), contigs, width=int(np.random.default_rng(seed).choice([50, 60, 61, 80])))
+    write_sam(Path(sam), refs, ref_safe(recs))
+    rng = np.random.default_rng(1000 + seed)
+    return fa, sam, [PssOpts() if trial == 0 else random_pss_opts(rng) for trial in range(3)]
+
+
+def fk_fuzz_case(seed: int) -> tuple[str, list[tuple[FkOpts, str]]]:
+    """-> (fasta, [(options, sam)] of the three trials)"""
+    contigs, refs, recs = fuzz_dataset(100 + seed, 1500)
+    rng = np.random.default_rng(2000 + seed)
+    write_fasta(Path("g.fa"), contigs)
+    trials = []
+    for trial in range(3):
+        o = FkOpts(klen=4) if trial == 0 else random_fk_opts(rng)
+        sam = f"a{trial}.sam"
+        # precondition P4 (oracle/pss_oracle.c): starts < k/2 are undefined in the reference
+        write_sam(Path(sam), refs, ref_safe(recs, o.klen))
+        trials.append((o, sam))
+    return "g.fa", trials
+
+
+def gz_fuzz_case() -> tuple[str, str, str, PssOpts]:
+    """-> (fasta, the same fasta gzipped, sam, options)"""
+    contigs, refs, recs = fuzz_dataset(5, 800)
+    write_fasta(Path("g.fa"), contigs)
+    write_fasta(Path("g.fa.gz"), contigs, gz=True)
+    write_sam(Path("a.sam"), refs, ref_safe(recs))
+    return "g.fa", "g.fa.gz", "a.sam", PssOpts(region_len=8)
+
+
+def gkc_fuzz_case(k: int) -> str:
+    contigs, _, _ = fuzz_dataset(40 + k, 10, contig_lens=(30000, 4000, 600, 50))
+    write_fasta(Path("g.fa"), contigs)
+    return "g.fa"
+
+
+def inputs_digest(files: list[str], opts=None) -> str:
+    """sha256 over input files and options: stored beside each output, so a change in the
+    generators above shows up as stale fixtures instead of as a restatement mismatch"""
+    import hashlib
+    h = hashlib.sha256()
+    for f in files:
+        h.update(Path(f).read_bytes())
+    h.update(repr(opts).encode())
+    return h.hexdigest()
+
+
+def sparse(*tables: np.ndarray) -> tuple[np.ndarray, ...]:
+    """equal-length tables -> (indices where any is non-zero, each table's values there)"""
+    idx = np.flatnonzero(np.any(np.stack(tables), axis=0)).astype(np.uint32)
+    return (idx,) + tuple(t[idx] for t in tables)
+
+
+def dense(n: int, idx: np.ndarray, vals: np.ndarray) -> np.ndarray:
+    out = np.zeros(n, dtype=np.uint32)
+    out[idx] = vals
+    return out

@@ -1,46 +1,32 @@
 """Drop-in boundary, from the reference's side: the UNMODIFIED reference `main`s
-(/root/reference/pss-bam.c:650-805, fragkon.c:253-386, genome-kmer-count.c:23-66) are compiled
-against THIS repo's include/{fasta-genome-io,sam-parse,kmer}.h and linked with libpssbam_host.so
-instead of the reference's own fasta-genome-io.c / sam-parse.c / kmer.c, then run on the golden
-inputs: their output must be the golden files byte for byte.
+(pss-bam.c:650-805, fragkon.c:253-386, genome-kmer-count.c:23-66) compiled against THIS repo's
+include/{fasta-genome-io,sam-parse,kmer}.h and linked with libpssbam_host.so instead of the
+reference's own fasta-genome-io.c / sam-parse.c / kmer.c, then run on the golden inputs: their
+output must be the golden files byte for byte.
 
-The reference source never enters the repository: it is piped to gcc on stdin from where it lies
-(`gcc -x c -`, run in an empty directory so the quote-includes resolve through -Iinclude).
-Skipped where /root/reference is absent (the GPU box)."""
+The binaries are oracle/_ref/on_ours/*, made by build() through oracle/Makefile where the
+reference sources are present; the reference source never enters the repository, and this
+module reads nothing outside it.  Skipped where build() had no reference sources to compile."""
 import json
-import os
 import subprocess
 from pathlib import Path
 
 import pytest
 
-import __graft_entry__ as ge
 import pssbam_testlib as tl
 
-REF = Path("/root/reference")
-ROOT = Path(__file__).resolve().parent.parent
 GOLD = Path(__file__).resolve().parent / "golden"
 MANIFEST = json.loads((GOLD / "manifest.json").read_text())
+MAINS = tl.REF_DIR / "on_ours"
+TOOLS = ("pss-bam", "fragkon", "genome-kmer-count")
 
-pytestmark = pytest.mark.skipif(not (REF / "pss-bam.c").exists(), reason="/root/reference not present")
+pytestmark = pytest.mark.skipif(not all((MAINS / t).exists() for t in TOOLS),
+                                reason="oracle/_ref/on_ours not built (no reference sources at build time)")
 
 
 @pytest.fixture(scope="module")
-def ref_mains(tmp_path_factory):
-    ge.build()
-    pkg = ge.load_pkg()
-    out = tmp_path_factory.mktemp("ref_mains")
-    build_dir = tmp_path_factory.mktemp("empty_cwd")   # no header here: "x.h" falls through to -I
-    exes = {}
-    for tool in ("pss-bam", "fragkon", "genome-kmer-count"):
-        exe = out / tool
-        with open(REF / f"{tool}.c", "rb") as src:
-            pr = subprocess.run(["gcc", "-w", "-O1", "-x", "c", "-", f"-I{ROOT / 'include'}", "-o", str(exe),
-                                 f"-L{pkg.PKG_DIR}", "-lpssbam_host", f"-Wl,-rpath,{pkg.PKG_DIR}", "-lz"],
-                                stdin=src, cwd=build_dir, capture_output=True, text=True)
-        assert pr.returncode == 0, f"{tool}.c does not build against include/: {pr.stderr[-3000:]}"
-        exes[tool] = exe
-    return exes
+def ref_mains():
+    return {t: MAINS / t for t in TOOLS}
 
 
 def _stage(ds, tmp_path):
