@@ -33,6 +33,7 @@ extern "C" {
 
 #define PSSBAM_ABI_VERSION 1
 #define PSSBAM_MAX_KLEN 15     /* 4^15 64-bit bins per k-mer table = 8.6 GB of device memory */
+#define PSSBAM_MAX_READ_GROUPS 4096  /* pssbam_engine_set_read_groups */
 
 /* error codes */
 #define PSSBAM_OK 0
@@ -179,8 +180,26 @@ int pssbam_engine_finish(pssbam_engine *e, unsigned long *fwd, unsigned long *re
                          uint64_t *k3, uint64_t stats[PSSBAM_ST_N]);
 int pssbam_engine_reset(pssbam_engine *e);
 
+/* Read groups (pss-bam -G): one set of substitution tables per @RG ID in a single pass over the records,
+ * instead of one `-R <ID>` run per library.  ids[0..n-1] are the header's IDs in order, n in
+ * 1..PSSBAM_MAX_READ_GROUPS; an ID given twice keeps its first index.  A record belongs to ID g when its FIRST
+ * RG:Z aux field equals ids[g] byte for byte -- exactly the records `-R ids[g]` keeps -- and to the unassigned
+ * bucket otherwise (no RG:Z, or a value no ID matches).  Legal after create (or reset) and before the first
+ * tally launch; with pssbam_engine_feed_open that is any time before set_references.  PSSBAM_EINVAL with
+ * cfg.read_group or PSSBAM_TALLY_KMER set, PSSBAM_ESTATE once records have been tallied or the counter block
+ * has been bound.  The table survives pssbam_engine_reset.  pssbam_engine_finish keeps returning the totals
+ * over every record. */
+int pssbam_engine_set_read_groups(pssbam_engine *e, int32_t n, const char *const *ids);
+/* Drains the engine like pssbam_engine_finish and copies one group's two tables ((region_len+2)*16 each, any
+ * pointer may be NULL): group -1 is the unassigned bucket, 0..n-1 the IDs in the order given. */
+int pssbam_engine_finish_groups(pssbam_engine *e, int32_t group, unsigned long *fwd, unsigned long *rev);
+
 /* The device-resident counter block [fwd | rev | k5 | k3 | stats] as one array of
- * n_u64 64-bit words, for a caller-side RCCL reduce across GPUs (sum, uint64). */
+ * n_u64 64-bit words, for a caller-side RCCL reduce across GPUs (sum, uint64).  With read groups it is
+ * [fwd | rev | stats | fwd_0 | rev_0 | ... | fwd_n-1 | rev_n-1]: the leading fwd | rev are the unassigned
+ * bucket, group g's pair ((region_len+2)*16 words each) starts at 2*(region_len+2)*16 + PSSBAM_ST_N +
+ * g*2*(region_len+2)*16 (the k-mer tables are empty: read groups exclude PSSBAM_TALLY_KMER).  The block is
+ * still summed across GPUs as one u64 array. */
 int pssbam_engine_counters_device(pssbam_engine *e, void **d_counters, size_t *n_u64);
 
 /* Makes the engine accumulate into caller-owned device memory (n_u64 words, as reported

@@ -40,7 +40,9 @@ HIP_SYMBOLS = [
     "pssbam_bgzf_inflate_device", "pssbam_bgzf_inflate_host", "pssbam_engine_submit_bgzf", "pssbam_engine_wait_bgzf_copied",
     "pssbam_engine_feed_status", "pssbam_engine_feed_break", "pssbam_engine_feed_handoff", "pssbam_feed_reserve", "pssbam_engine_hint_records",
     "pssbam_engine_set_genome_async", "pssbam_engine_genome_wait", "pssbam_engine_feed_open", "pssbam_feed_release",
+    "pssbam_engine_set_read_groups", "pssbam_engine_finish_groups",
 ]
+MAX_READ_GROUPS = 4096
 EBUSY = -7
 
 
@@ -100,6 +102,8 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_sync.argtypes = [C.c_void_p]
     L.pssbam_engine_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_reset.argtypes = [C.c_void_p]
+    L.pssbam_engine_set_read_groups.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p)]
+    L.pssbam_engine_finish_groups.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.pssbam_engine_counters_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.pssbam_engine_bind_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.pssbam_engine_genome_kmer_count.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -166,10 +170,11 @@ class Tables:
 class Engine:
     """One engine = one GPU, one stream.  Options mirror the two reference CLIs:
     `pss` = dict(region_len, min_read_len, max_read_len, min_mq, up_ctx, down_ctx, merged_only),
-    `kmer` = dict(klen, min_mq, min_read_len, max_read_len, merged_only)."""
+    `kmer` = dict(klen, min_mq, min_read_len, max_read_len, merged_only).
+    `read_groups` = @RG IDs (pss-bam -G): one set of substitution tables per ID, see set_read_groups."""
 
     def __init__(self, pss: dict | None = None, kmer: dict | None = None, read_group: str | None = None,
-                 kernel: int = KERNEL_AUTO, device: int = -1):
+                 kernel: int = KERNEL_AUTO, device: int = -1, read_groups: list[str] | None = None):
         L = hip_lib()
         cfg = _Config()
         cfg.abi_version = 1
@@ -197,6 +202,28 @@ class Engine:
         _chk(L.pssbam_engine_create(C.byref(cfg), C.byref(h)))
         self._h = h
         self._L = L
+        self.read_groups: list[str] = []
+        if read_groups is not None:
+            self.set_read_groups(read_groups)
+
+    def set_read_groups(self, ids: list[str]):
+        """pss-bam -G: tallies every record into the tables of the ID its first RG:Z value equals (the unassigned
+        bucket otherwise).  Before the first tally (after feed_open: before set_references)."""
+        raw = [i.encode() if isinstance(i, str) else bytes(i) for i in ids]
+        arr = (C.c_char_p * max(len(raw), 1))(*raw)
+        _chk(self._L.pssbam_engine_set_read_groups(self._h, len(raw), arr))
+        self.read_groups = [i.decode() if isinstance(i, bytes) else i for i in ids]
+
+    def finish_groups(self) -> dict:
+        """{ID: Tables, ..., None: Tables of the unassigned bucket} (fwd / rev only; drains like finish)"""
+        out = {}
+        for g, key in [(-1, None)] + list(enumerate(self.read_groups)):
+            fwd = np.zeros((self.region_len + 2, 16), dtype=np.uint64)
+            rev = np.zeros_like(fwd)
+            _chk(self._L.pssbam_engine_finish_groups(self._h, g, fwd.ctypes.data, rev.ctypes.data))
+            if key not in out:   # a repeated ID: its first index holds the counts
+                out[key] = Tables(fwd, rev, None, None, {})
+        return out
 
     def close(self):
         if getattr(self, "_h", None):
@@ -371,8 +398,14 @@ class Engine:
         """u64-word offsets of the sections of the counter block"""
         rows = (self.region_len + 2) if self.has_pss else 0
         nb = 4 ** self.klen if self.has_kmer else 0
-        return {"fwd": 0, "rev": rows * 16, "k5": 2 * rows * 16, "k3": 2 * rows * 16 + nb,
-                "stats": 2 * rows * 16 + 2 * nb, "rows": rows, "bins": nb}
+        lay = {"fwd": 0, "rev": rows * 16, "k5": 2 * rows * 16, "k3": 2 * rows * 16 + nb,
+               "stats": 2 * rows * 16 + 2 * nb, "rows": rows, "bins": nb}
+        # read groups: plane 0 (the unassigned bucket) is fwd / rev above; group g's [fwd | rev] pair follows the stats
+        base = lay["stats"] + ST_N
+        lay["groups"] = [{"id": g, "fwd": base + k * 2 * rows * 16, "rev": base + k * 2 * rows * 16 + rows * 16}
+                         for k, g in enumerate(self.read_groups)]
+        lay["n_u64"] = base + len(self.read_groups) * 2 * rows * 16
+        return lay
 
     def genome_kmer_count(self, klen: int) -> np.ndarray:
         out = np.zeros(4 ** klen, dtype=np.uint64)

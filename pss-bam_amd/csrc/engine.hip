@@ -195,6 +195,12 @@ struct pssbam_engine {
     bool have_refs = false;
     // -R
     uint8_t *d_rg = nullptr;
+    // -G (pssbam_engine_set_read_groups): plane 1 + g of the counter block holds ID g
+    std::vector<std::string> groups;
+    uint8_t *d_grp_ids = nullptr;
+    uint32_t *d_grp_offs = nullptr, *d_grp_hash = nullptr;
+    uint32_t grp_hash_mask = 0, off_groups = 0, plane_words = 0;
+    bool tallied = false;   // a tally launch since create / reset
     // counters
     unsigned long long *d_counters = nullptr;      // block in use (own or caller-bound)
     unsigned long long *d_counters_own = nullptr;  // the engine's own allocation
@@ -242,6 +248,7 @@ struct pssbam_engine {
     uint64_t kernel_launches = 0;
     // tuning overrides (environment, for experiments)
     int env_tile_reads = 0, env_grid_mult = 0, env_simple_blocks = 0, env_grid_wgs = 0, env_pieces = 0;
+    int env_group_slots = 0;   // PSSBAM_GROUP_SLOTS: at most this many planes per -G launch (tests: plane passes with few groups)
     bool warned_ablate = false;
     bool compact_plan_once = false;   // tally_compact: header decode + filters once per read, plan through LDS (PSSBAM_COMPACT_PLAN_ONCE)
     uint32_t prep_lds[32] = {0};    // prep_kernel's memo, by kernel variant
@@ -360,6 +367,8 @@ extern "C" int pssbam_engine_create(const pssbam_config *cfg, pssbam_engine **ou
     e->off_k3 = (uint32_t)(e->off_k5 + e->n_bins);
     e->off_stats = (uint32_t)(e->off_k3 + e->n_bins);
     e->n_counters = (size_t)e->off_stats + PSSBAM_ST_N;
+    e->plane_words = 2u * e->rows * 16u;
+    e->off_groups = (uint32_t)e->n_counters;
     HIP_TRY(hipMalloc(&e->d_counters_own, e->n_counters * sizeof(unsigned long long)));
     e->d_counters = e->d_counters_own;
     HIP_TRY(hipMemsetAsync(e->d_counters, 0, e->n_counters * sizeof(unsigned long long), e->stream));
@@ -382,6 +391,7 @@ extern "C" int pssbam_engine_create(const pssbam_config *cfg, pssbam_engine **ou
     e->env_simple_blocks = env_int("PSSBAM_SIMPLE_BLOCKS");
     e->env_grid_wgs = env_int("PSSBAM_GRID_WGS");
     e->env_pieces = env_int("PSSBAM_PIECES");
+    e->env_group_slots = env_int("PSSBAM_GROUP_SLOTS");
     if (getenv("PSSBAM_COMPACT")) e->use_compact = env_int("PSSBAM_COMPACT") != 0;
     if (getenv("PSSBAM_COMPACT_PLAN_ONCE")) e->compact_plan_once = env_int("PSSBAM_COMPACT_PLAN_ONCE") != 0;
     if (tstat)
@@ -443,6 +453,9 @@ extern "C" void pssbam_engine_destroy(pssbam_engine *e) {
     if (e->d_ref_info) (void)hipFree(e->d_ref_info);
     if (e->h_ref_info) (void)hipHostFree(e->h_ref_info);
     if (e->d_rg) (void)hipFree(e->d_rg);
+    if (e->d_grp_ids) (void)hipFree(e->d_grp_ids);
+    if (e->d_grp_offs) (void)hipFree(e->d_grp_offs);
+    if (e->d_grp_hash) (void)hipFree(e->d_grp_hash);
     if (e->d_counters_own) (void)hipFree(e->d_counters_own);
     if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
     if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
@@ -725,6 +738,9 @@ static uint64_t sample_prefix_need(const uint8_t *bytes, uint64_t nbytes, bool w
     return need_max;
 }
 
+// -R and -G walk the aux fields, which sit behind QUAL: the tiled kernels stage whole records
+static bool whole_records(const pssbam_engine *e) { return e->has_rg || !e->groups.empty(); }
+
 static uint32_t pieces_for(uint64_t need_max) {
     uint64_t pieces = (need_max + 15 + 15) / 16;  // + worst-case misalignment of the record start
     // records sit pieces*16 bytes apart in LDS: an even piece count puts every record start of a
@@ -740,6 +756,7 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                         uint32_t n_records, const uint8_t *host_sample, uint64_t host_sample_bytes,
                         const uint32_t *d_n_recs = nullptr, uint64_t sample_off = 0, const uint32_t *host_offsets = nullptr) {
     if (!n_records) return PSSBAM_OK;
+    e->tallied = true;
     const pssbam_config &c = e->cfg;
     TallyParams P{};
     P.recs = d_recs;
@@ -779,6 +796,19 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
     P.off_k5 = e->off_k5;
     P.off_k3 = e->off_k3;
     P.off_stats = e->off_stats;
+    const bool grouped = !e->groups.empty();
+    GroupParams G{};
+    if (grouped) {
+        G.ids = e->d_grp_ids;
+        G.id_offs = e->d_grp_offs;
+        G.hash = e->d_grp_hash;
+        G.hash_mask = e->grp_hash_mask;
+        G.n_groups = (uint32_t)e->groups.size();
+        G.plane0 = 0;
+        G.n_slots = G.n_groups + 1u;
+        G.plane_words = e->plane_words;
+        G.off_groups = e->off_groups;
+    }
 
     int kernel = c.kernel;
     if (d_n_recs && kernel == PSSBAM_KERNEL_SIMPLE) return fail(PSSBAM_EINVAL, "device-indexed blocks need the tiled kernels");
@@ -801,7 +831,8 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         const bool lds_tab = do_pss && tab_bytes <= 60u * 1024u;
         uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n_records + 255) / 256, (uint64_t)e->n_cu * 8);
         if (e->env_simple_blocks > 0) blocks = (uint32_t)e->env_simple_blocks;
-        if (lds_tab) hipLaunchKernelGGL(tally_simple<true>, dim3(blocks), dim3(256), tab_bytes, e->stream, P);
+        if (grouped) hipLaunchKernelGGL(tally_simple_grouped, dim3(blocks), dim3(256), 0, e->stream, P, G);
+        else if (lds_tab) hipLaunchKernelGGL(tally_simple<true>, dim3(blocks), dim3(256), tab_bytes, e->stream, P);
         else hipLaunchKernelGGL(tally_simple<false>, dim3(blocks), dim3(256), 0, e->stream, P);
     } else {
         // how much of each record goes through LDS: sampled from the block itself (host copy at
@@ -813,11 +844,11 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
             // three regions of the block (start, middle, end: 1400 records each), found through the
             // caller's offset index -- a block whose later records are longer than its first ones must
             // not silently fall onto the one-lane path (stats.slow_path)
-            uint64_t need = sample_prefix_need(host_sample, host_sample_bytes, e->has_rg, 1400);
+            uint64_t need = sample_prefix_need(host_sample, host_sample_bytes, whole_records(e), 1400);
             if (host_offsets && n_records > 4200u) {
                 const uint32_t mid = host_offsets[n_records / 2], late = host_offsets[n_records - 1400u];
-                need = std::max(need, sample_prefix_need(host_sample + mid, host_sample_bytes - mid, e->has_rg, 1400));
-                need = std::max(need, sample_prefix_need(host_sample + late, host_sample_bytes - late, e->has_rg, 1400));
+                need = std::max(need, sample_prefix_need(host_sample + mid, host_sample_bytes - mid, whole_records(e), 1400));
+                need = std::max(need, sample_prefix_need(host_sample + late, host_sample_bytes - late, whole_records(e), 1400));
             }
             pieces = pieces_for(need);
         } else {
@@ -826,7 +857,7 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                 std::vector<uint8_t> head((size_t)std::min<uint64_t>(nbytes - sample_off, 1024 * 1024));
                 HIP_TRY(hipMemcpyAsync(head.data(), d_recs + sample_off, head.size(), hipMemcpyDeviceToHost, e->stream));
                 HIP_TRY(hipStreamSynchronize(e->stream));
-                uint64_t need = sample_prefix_need(head.data(), head.size(), e->has_rg);
+                uint64_t need = sample_prefix_need(head.data(), head.size(), whole_records(e));
                 if (!d_n_recs && n_records > 8192u) {   // device-resident block with a known count: its middle and end too
                     uint32_t at[2] = {0, 0};
                     HIP_TRY(hipMemcpyAsync(&at[0], d_offs + n_records / 2, 4, hipMemcpyDeviceToHost, e->stream));
@@ -837,7 +868,7 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                         head.resize((size_t)std::min<uint64_t>(nbytes - at[k], 512 * 1024));
                         HIP_TRY(hipMemcpyAsync(head.data(), d_recs + at[k], head.size(), hipMemcpyDeviceToHost, e->stream));
                         HIP_TRY(hipStreamSynchronize(e->stream));
-                        need = std::max(need, sample_prefix_need(head.data(), head.size(), e->has_rg, 2048));
+                        need = std::max(need, sample_prefix_need(head.data(), head.size(), whole_records(e), 2048));
                     }
                 }
                 e->dev_pieces = pieces_for(need);
@@ -902,6 +933,44 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                                (uint32_t)(LK ? 1 : 0));                                            \
         }                                                                                          \
     } while (0)
+        if (grouped) {
+            // -G: every (32-row pass, plane pass) pair is one launch over the block.  A plane pass holds as
+            // many planes as fit the LDS beside the staging buffer (8 planes = 32 KiB always do: one pass for
+            // up to 7 groups); more groups take more passes, each re-reading the records.
+            const uint32_t n_planes = G.n_groups + 1u;
+            const uint32_t stage_bytes = tiled_lds_bytes(T, pieces);
+            const uint32_t fit = stage_bytes + 2u * GROUP_PLANE_WORDS * 4u <= GROUPED_LDS_BUDGET
+                                     ? (GROUPED_LDS_BUDGET - stage_bytes) / (GROUP_PLANE_WORDS * 4u) - 1u : 1u;
+            uint32_t per_pass = std::min(n_planes, fit);
+            if (e->env_group_slots > 0) per_pass = std::min(per_pass, (uint32_t)e->env_group_slots);
+            for (uint32_t pass = 0; pass < n_passes && rc == PSSBAM_OK; pass++) {
+                P.row_base = pass * TILED_ROWS;
+                for (uint32_t plane0 = 0; plane0 < n_planes && rc == PSSBAM_OK; plane0 += per_pass) {
+                    G.plane0 = plane0;
+                    G.n_slots = std::min(per_pass, n_planes - plane0);
+                    G.scratch_words = GROUP_SCRATCH_DELTA + G.n_slots * GROUP_PLANE_WORDS;
+                    const uint32_t glds = tiled_grouped_lds_bytes(T, pieces, G.n_slots);
+                    const bool later = pass > 0;
+                    rc = later ? prep_kernel(e, 29, tally_tiled_grouped<true>, glds, &occ) : prep_kernel(e, 28, tally_tiled_grouped<false>, glds, &occ);
+                    if (rc != PSSBAM_OK) break;
+                    uint32_t grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)e->n_cu * occ * mult);
+                    if (e->env_grid_wgs > 0) grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)e->env_grid_wgs);
+                    const size_t need_slots = ((size_t)grid * G.scratch_words + SCRATCH_WORDS - 1) / SCRATCH_WORDS;
+                    if (e->scratch_slots < need_slots) {
+                        HIP_TRY(hipStreamSynchronize(e->stream));
+                        if (e->d_scratch) HIP_TRY(hipFree(e->d_scratch));
+                        e->d_scratch = nullptr;
+                        e->scratch_slots = need_slots;
+                        HIP_TRY(hipMalloc(&e->d_scratch, e->scratch_slots * SCRATCH_WORDS * sizeof(uint32_t)));
+                    }
+                    P.scratch = e->d_scratch;
+                    if (later) hipLaunchKernelGGL(tally_tiled_grouped<true>, dim3(grid), dim3(TILED_THREADS), glds, e->stream, P, G);
+                    else hipLaunchKernelGGL(tally_tiled_grouped<false>, dim3(grid), dim3(TILED_THREADS), glds, e->stream, P, G);
+                    hipLaunchKernelGGL(reduce_partials_grouped, dim3((G.scratch_words * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream,
+                                       P, G, grid);
+                }
+            }
+        } else
         if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg) {
             if (!do_kmer && getenv("PSSBAM_COMPACT_DECODE_TWICE")) {   // diagnostics: what the shared header decode costs
                 rc = prep_kernel(e, 20, tally_compact_decode_twice, lds, &occ);
@@ -922,7 +991,7 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         else { if (kmer_lds) LAUNCH_TILED(false, true, true, false); else LAUNCH_TILED(false, true, false, false); }
         // rows 32.. of a large -r: further passes over the same block, substitution rows only
         // (the status counters and the k-mer tally belong to pass 0)
-        for (uint32_t pass = 1; pass < n_passes && rc == PSSBAM_OK; pass++) {
+        for (uint32_t pass = 1; pass < n_passes && rc == PSSBAM_OK && !grouped; pass++) {
             P.row_base = pass * TILED_ROWS;
             LAUNCH_TILED(true, false, false, true);
         }
@@ -943,7 +1012,7 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
 extern "C" int pssbam_engine_hint_records(pssbam_engine *e, const void *records, uint64_t nbytes) {
     if (!e || (!records && nbytes)) return fail(PSSBAM_EINVAL, "null argument");
     if (nbytes < 36) return PSSBAM_OK;
-    e->dev_pieces = pieces_for(sample_prefix_need((const uint8_t *)records, nbytes, e->has_rg, 1 << 16));
+    e->dev_pieces = pieces_for(sample_prefix_need((const uint8_t *)records, nbytes, whole_records(e), 1 << 16));
     e->dev_pieces_avg = 40;
     return PSSBAM_OK;
 }
@@ -1113,6 +1182,9 @@ extern "C" int pssbam_engine_finish(pssbam_engine *e, unsigned long *fwd, unsign
     HIP_TRY(hipMemcpy(h.data(), e->d_counters, e->n_counters * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     static_assert(sizeof(unsigned long) == 8, "LP64 expected");
     const size_t tab = (size_t)e->rows * 16;
+    // -G: the totals are every plane's sum (plane 0, the unassigned bucket, sits where an ungrouped engine keeps its tables)
+    for (size_t g = 0; g < e->groups.size(); g++)
+        for (size_t i = 0; i < 2 * tab; i++) h[i] += h[e->off_groups + g * e->plane_words + i];
     if (fwd) for (size_t i = 0; i < tab; i++) fwd[i] = (unsigned long)h[i];
     if (rev) for (size_t i = 0; i < tab; i++) rev[i] = (unsigned long)h[e->off_rev + i];
     if (k5) for (uint64_t i = 0; i < e->n_bins; i++) k5[i] = h[e->off_k5 + i];
@@ -1121,9 +1193,82 @@ extern "C" int pssbam_engine_finish(pssbam_engine *e, unsigned long *fwd, unsign
     return PSSBAM_OK;
 }
 
+extern "C" int pssbam_engine_finish_groups(pssbam_engine *e, int32_t group, unsigned long *fwd, unsigned long *rev) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (e->groups.empty()) return fail(PSSBAM_ESTATE, "pssbam_engine_set_read_groups has not been called");
+    if (group < -1 || group >= (int32_t)e->groups.size()) return fail(PSSBAM_EINVAL, "group %d outside -1..%zu", group, e->groups.size() - 1);
+    int rc = pssbam_engine_sync(e);
+    if (rc) return rc;
+    const size_t tab = (size_t)e->rows * 16;
+    const size_t at = group < 0 ? 0 : e->off_groups + (size_t)group * e->plane_words;
+    std::vector<unsigned long long> h(2 * tab);
+    HIP_TRY(hipMemcpy(h.data(), e->d_counters + at, 2 * tab * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (fwd) for (size_t i = 0; i < tab; i++) fwd[i] = (unsigned long)h[i];
+    if (rev) for (size_t i = 0; i < tab; i++) rev[i] = (unsigned long)h[tab + i];
+    return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_set_read_groups(pssbam_engine *e, int32_t n, const char *const *ids) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (n < 1 || n > PSSBAM_MAX_READ_GROUPS || !ids) return fail(PSSBAM_EINVAL, "read group count %d outside 1..%d", n, PSSBAM_MAX_READ_GROUPS);
+    if (e->has_rg) return fail(PSSBAM_EINVAL, "read groups and a -R read group filter exclude each other");
+    if (e->cfg.tally_mask != PSSBAM_TALLY_PSS) return fail(PSSBAM_EINVAL, "read groups split the substitution tables only (no PSSBAM_TALLY_KMER)");
+    for (int32_t i = 0; i < n; i++)
+        if (!ids[i]) return fail(PSSBAM_EINVAL, "read group %d is NULL", i);
+    if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set read groups after create or reset, before the first tally");
+    if (e->d_counters != e->d_counters_own) return fail(PSSBAM_ESTATE, "a caller-bound counter block cannot grow: set read groups before bind_counters");
+    HIP_TRY(hipSetDevice(e->device));
+    // ID table (concatenated) + open-addressing hash over it; a repeated ID keeps its first index
+    std::vector<std::string> groups(ids, ids + n);
+    std::string cat;
+    std::vector<uint32_t> offs(1, 0u);
+    for (const std::string &g : groups) {
+        cat += g;
+        offs.push_back((uint32_t)cat.size());
+    }
+    uint32_t hsize = 16;
+    while (hsize < 2u * (uint32_t)n) hsize <<= 1;
+    std::vector<uint32_t> hash(hsize, 0u);
+    for (int32_t g = 0; g < n; g++) {
+        uint32_t hv = FNV1A_SEED;
+        for (unsigned char ch : groups[g]) hv = fnv1a_step(hv, ch);
+        for (uint32_t k = 0;; k++) {
+            uint32_t &slot = hash[(hv + k) & (hsize - 1)];
+            if (slot == 0u) { slot = (uint32_t)g + 1u; break; }
+            if (groups[slot - 1u] == groups[g]) break;   // duplicate: the first one counts
+        }
+    }
+    // the counter block grows by one [fwd | rev] plane per group; nothing has been counted yet.  The old buffers may still
+    // be named by work queued on the stream (the compressed feed): they are retired, not freed.
+    const size_t n_counters = (size_t)e->off_groups + (size_t)n * e->plane_words;
+    unsigned long long *d_counters = nullptr;
+    uint8_t *d_ids = nullptr;
+    uint32_t *d_offs = nullptr, *d_hash = nullptr;
+    HIP_TRY(hipMalloc(&d_counters, n_counters * sizeof(unsigned long long)));
+    HIP_TRY(hipMalloc(&d_ids, cat.size() + 16));
+    HIP_TRY(hipMalloc(&d_offs, offs.size() * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&d_hash, hash.size() * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(d_ids, cat.data(), cat.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_offs, offs.data(), offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_hash, hash.data(), hash.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(d_counters, 0, n_counters * sizeof(unsigned long long), e->stream));
+    for (void *old : {(void *)e->d_counters_own, (void *)e->d_grp_ids, (void *)e->d_grp_offs, (void *)e->d_grp_hash})
+        if (old) e->retired.push_back(old);
+    e->d_counters = e->d_counters_own = d_counters;
+    e->n_counters = n_counters;
+    e->d_grp_ids = d_ids;
+    e->d_grp_offs = d_offs;
+    e->d_grp_hash = d_hash;
+    e->grp_hash_mask = hsize - 1;
+    e->groups = std::move(groups);
+    e->dev_pieces = 0;   // whole records are staged from now on: resampled at the next launch
+    return PSSBAM_OK;
+}
+
 extern "C" int pssbam_engine_reset(pssbam_engine *e) {
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
     HIP_TRY(hipSetDevice(e->device));
+    e->tallied = false;
     e->feed_fresh = true;   // a compressed stream fed from here on starts a new record chain
     e->feed_skip = 0;
     if (!e->deferred.empty()) {   // inflated ahead of the genome and now given up: the slots go back once their kernels have run

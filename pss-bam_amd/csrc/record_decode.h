@@ -270,6 +270,85 @@ __device__ bool has_read_group(const Src &src, const RecHdr &h, const uint8_t *r
     return false;
 }
 
+// ---- read groups (-G) ------------------------------------------------------------------
+// The grouped kernels' second argument: the @RG ID table and where one launch's planes go.  A
+// plane is one [fwd | rev] pair of (N+2)*16 tables; plane 0 is the unassigned bucket (the
+// counter block's original fwd / rev), plane 1 + g is ID g, at off_groups + g * plane_words.
+struct GroupParams {
+    const uint8_t *ids;        // the IDs back to back
+    const uint32_t *id_offs;   // n_groups + 1 offsets into ids
+    const uint32_t *hash;      // open addressing over FNV-1a of the ID: entry = group + 1, 0 = empty
+    uint32_t hash_mask;        // entries - 1 (a power of two, at least twice n_groups)
+    uint32_t n_groups;
+    uint32_t plane0, n_slots;  // this launch tallies planes plane0 .. plane0 + n_slots - 1
+    uint32_t plane_words;      // 2 * (N+2) * 16
+    uint32_t off_groups;       // first word of plane 1 in the counter block
+    uint32_t scratch_words;    // per-workgroup scratch of the grouped tiled kernel: [deltas 16 | n_slots x 1024]
+};
+constexpr uint32_t GROUP_SCRATCH_DELTA = 16;   // the deltas lead a grouped scratch slot
+constexpr uint32_t GROUP_PLANE_WORDS = 1024;   // one [(cell << 1) | table][32 rows] plane in LDS / scratch
+
+__host__ __device__ __forceinline__ uint32_t fnv1a_step(uint32_t h, uint32_t c) { return (h ^ c) * 16777619u; }
+constexpr uint32_t FNV1A_SEED = 2166136261u;
+
+// Plane of a record: 1 + g when its FIRST RG:Z value equals ID g byte for byte, else 0.  The aux
+// walk and its rules are has_read_group's (a malformed field or an unterminated string ends it
+// with "no RG"), so group g receives exactly the records `-R <ID g>` keeps.
+template <class Src>
+__device__ uint32_t read_group_plane(const Src &src, const RecHdr &h, const GroupParams &G) {
+    uint32_t o = h.aux_off;
+    const uint32_t end = h.rec_len;
+    while (o + 3 <= end) {
+        const uint32_t t0 = src.u8(o), t1 = src.u8(o + 1), ty = src.u8(o + 2);
+        o += 3;
+        uint32_t sz;
+        switch (ty) {
+        case 'A': case 'c': case 'C': sz = 1; break;
+        case 's': case 'S': sz = 2; break;
+        case 'i': case 'I': case 'f': sz = 4; break;
+        case 'Z': case 'H': {
+            const bool is_rg = (t0 == 'R' && t1 == 'G' && ty == 'Z');
+            uint32_t n = 0, hv = FNV1A_SEED;
+            while (o + n < end) {
+                const uint32_t c = src.u8(o + n);
+                if (c == 0) break;
+                if (is_rg) hv = fnv1a_step(hv, c);
+                n++;
+            }
+            if (o + n >= end) return 0u;              // unterminated string
+            if (is_rg) {                               // the first RG tag decides, like bam_aux_get
+                for (uint32_t k = 0; k <= G.hash_mask; k++) {
+                    const uint32_t ent = G.hash[(hv + k) & G.hash_mask];
+                    if (ent == 0u) return 0u;
+                    const uint32_t a = G.id_offs[ent - 1u], b = G.id_offs[ent];
+                    if (b - a != n) continue;
+                    uint32_t i = 0;
+                    while (i < n && G.ids[a + i] == src.u8(o + i)) i++;
+                    if (i == n) return ent;
+                }
+                return 0u;
+            }
+            sz = n + 1;
+            break;
+        }
+        case 'B': {
+            if (o + 5 > end) return 0u;
+            const uint32_t sub = src.u8(o);
+            const uint32_t cnt = src.u32(o + 1);
+            const uint32_t es = (sub == 'c' || sub == 'C') ? 1u : (sub == 's' || sub == 'S') ? 2u : 4u;
+            const uint64_t tot = 5ull + uint64_t(cnt) * es;
+            if (tot > end - o) return 0u;
+            sz = (uint32_t)tot;
+            break;
+        }
+        default: return 0u;
+        }
+        if (sz > end - o) return 0u;
+        o += sz;
+    }
+    return 0u;
+}
+
 // ---- base codes ----------------------------------------------------------------------
 // Device-internal genome encoding: the byte permutation that swaps 'A'<->0, 'C'<->1,
 // 'G'<->2, 'T'<->3 and leaves every other value where it is (applied once at upload,

@@ -36,6 +36,9 @@
 //                 Counters leave LDS once, at kernel end, as plain stores into the workgroup's
 //                 slot of a scratch buffer; reduce_partials sums the slots into the u64 block.
 //
+//  tally_tiled_grouped / tally_simple_grouped (-G): the same kernels with one table plane per read
+//                 group (record -> plane by its first RG:Z value, read_group_plane).
+//
 // Integer/byte work only: no MFMA anywhere (the bound is HBM bandwidth).
 #pragma once
 
@@ -255,6 +258,21 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyP
     return record_events(DO_PSS, DO_KMER, gpl, kfail);
 }
 
+// The same for tally_tiled_grouped (substitution tables only): the record's plane slot of this
+// launch, if it has one, decides where its counts go.
+__device__ __attribute__((noinline)) uint32_t tally_overflow_record_grouped(const TallyParams *kernarg, const GroupParams *gk,
+                                                                            uint32_t o0, uint32_t o1, uint32_t *table) {
+    const TallyParams &P = *kernarg;
+    GlobalBytes gsrc{P.recs + o0};
+    const RecHdr gh = decode_hdr(gsrc, o1 - o0);
+    const Plan gpl = make_plan<true, false>(P, gsrc, gh);
+    if (gpl.pss_fwd || gpl.pss_rev) {
+        const uint32_t slot = read_group_plane(gsrc, gh, *gk) - gk->plane0;
+        if (slot < gk->n_slots) tally_pss_record(P, LdsTableColumnMajor{table + slot * GROUP_PLANE_WORDS, P.row_base}, gsrc, gh, gpl);
+    }
+    return record_events(true, false, gpl, false);
+}
+
 // Reference windows, one per alignment end, each with STATIC byte positions:
 //   left  end (e = 0): 32 bytes from s-2      byte w <-> row w          (0,1 context; 2+i = position i)
 //   right end (e = 1): 32 bytes up to s+L+1   byte w <-> row 31-w       (31 -> row 0, 30 -> row 1, 29-i -> 2+i)
@@ -264,13 +282,18 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyP
 // the count table and the offset buffer never alias the LDS-DMA destination (`stage`) -- without
 // it every LDS access issued while a DMA transfer is in flight is fenced behind vmcnt(0) and
 // the transfer cannot overlap the COLUMNS pass.
-template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS>
+//
+// GROUPED (-G, tally_tiled_grouped): `table` holds gk->n_slots planes of [(cell<<1)|table][row] plus
+// one trash plane behind them; every read's plane slot is resolved in CODES-A (read_group_plane)
+// and kept in grp_lds, and COLUMNS adds the wave's scalar slot offset to each real code.
+template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS, bool GROUPED = false>
 __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const TallyParams *kernarg,
                                                  uint8_t *__restrict__ stage, uint8_t *__restrict__ sheet,
                                                  uint32_t *__restrict__ table,
                                                  uint32_t *__restrict__ toffs,
                                                  uint32_t *__restrict__ lds_kmer,
-                                                 int32_t *__restrict__ lds_delta, uint4 *__restrict__ refs_lds) {
+                                                 int32_t *__restrict__ lds_delta, uint4 *__restrict__ refs_lds,
+                                                 const GroupParams *gk = nullptr, uint32_t *__restrict__ grp_lds = nullptr) {
     const uint32_t T = P.reads_per_tile;   // <= TILED_MAX_T
     const uint32_t n_recs = P.n_recs_dev ? *P.n_recs_dev : P.n_recs;   // device-indexed blocks: the count lives in device memory
     const uint32_t pieces = P.prefix_pieces;  // 16-byte pieces staged per record
@@ -289,7 +312,8 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
     const uint32_t n_live = n_pos > row_base ? min(n_pos - row_base, 32u) : 0u;
 
     // ---- one-time set-up: zero the tables ---------------------------------------------------------
-    for (uint32_t i = tid; i < TABLE_WORDS; i += TILED_THREADS) table[i] = 0u;
+    const uint32_t table_words = GROUPED ? (gk->n_slots + 1u) * GROUP_PLANE_WORDS : TABLE_WORDS;
+    for (uint32_t i = tid; i < table_words; i += TILED_THREADS) table[i] = 0u;
     if (LDS_KMER)
         for (uint32_t i = tid; i < 2u * (1u << (2 * P.K)); i += TILED_THREADS) lds_kmer[i] = 0u;
     if (tid < ST_USED) lds_delta[tid] = 0;
@@ -357,8 +381,8 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         // dead) so the lanes of a wave stay on one path
         LdsBytes src{stage, hdr_ok ? j * pieces * 16u + (o0 & 15u) : 0u};
         const RecHdr h = decode_hdr_lds(src, hdr_ok ? o1 - o0 : 0u);
-        // everything the path reads ends at QUAL[0] (the -R filter walks the aux fields: whole record)
-        const uint32_t needed = P.rg ? o1 - o0 : h.qual_off + 1u;
+        // everything the path reads ends at QUAL[0] (the -R filter and -G walk the aux fields: whole record)
+        const uint32_t needed = (GROUPED || P.rg) ? o1 - o0 : h.qual_off + 1u;
         const bool in_stage = hdr_ok && needed <= avail;
         Plan pl = plan_head<DO_PSS, DO_KMER>(P, src, h, RefsLdsCached{refs_lds, P.ref_info, n_ref_cached, (uint32_t)P.n_ref});
         if (!in_stage) { pl.status = RS_LIVE; pl.live = pl.pss_cand = pl.fk5 = pl.fk3 = false; }
@@ -419,9 +443,17 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
             for (int k = 0; k < 3; k++) kw[k] = kq.v[k];
             ksh = 4u * (uint32_t)(ka & 7ull);
         }
+        if constexpr (GROUPED) {
+            // the read's plane slot for COLUMNS; n_slots = not in this launch (its codes go to the trash plane)
+            if (in_tile && e == 0u) {
+                const uint32_t slot = cand ? read_group_plane(src, h, *gk) - gk->plane0 : gk->n_slots;
+                grp_lds[j] = slot < gk->n_slots ? slot : gk->n_slots;
+            }
+        }
         uint32_t ev_over = 0u;  // events of a record handled by the out-of-line path
         if (in_tile && !in_stage && e == 0u) {
-            ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER>(kernarg, o0, o1, table, lds_kmer);
+            if constexpr (GROUPED) ev_over = tally_overflow_record_grouped(kernarg, gk, o0, o1, table);
+            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER>(kernarg, o0, o1, table, lds_kmer);
             if (pass0) atomicAdd(&lds_delta[ST_SLOW_PATH], 1);
         }
         // First use of the gathered registers happens HERE, before the next tile's DMA is issued:
@@ -574,7 +606,27 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
             const uint32_t wpos = (b & 24u) + 2u * (b & 3u) + ((b >> 2) & 1u);
             const uint32_t row = e ? 31u - wpos : wpos;
             const uint32_t j0 = min(count, wave * 32u), j1 = min(count, j0 + 32u);
-            if (row < n_live) {  // (lanes of dead rows would only ever see CODE_NONE)
+            if (GROUPED && row < n_live) {
+                // real codes (< 32) go to the read's plane slot, the "no count" codes to the trash plane;
+                // the slot is the same for the whole wave (one read per wave-iteration): a scalar offset
+                const uint32_t trash_off = (gk->n_slots - 1u) * GROUP_PLANE_WORDS;
+                uint32_t j = j0;
+                for (; j + 8u <= j1; j += 8u) {
+                    uint32_t c[8], po[8];
+#pragma unroll
+                    for (int u = 0; u < 8; u++) {
+                        c[u] = sheet[(j + u) * 64u + lane];
+                        po[u] = __builtin_amdgcn_readfirstlane(grp_lds[j + u]) * GROUP_PLANE_WORDS;
+                    }
+#pragma unroll
+                    for (int u = 0; u < 8; u++) atomicAdd(&table[(c[u] << 5) + row + (c[u] < 32u ? po[u] : trash_off)], 1u);
+                }
+                for (; j < j1; j++) {
+                    const uint32_t c = sheet[j * 64u + lane];
+                    const uint32_t po = __builtin_amdgcn_readfirstlane(grp_lds[j]) * GROUP_PLANE_WORDS;
+                    atomicAdd(&table[(c << 5) + row + (c < 32u ? po : trash_off)], 1u);
+                }
+            } else if (row < n_live) {  // (lanes of dead rows would only ever see CODE_NONE)
                 uint32_t j = j0;
                 for (; j + 8u <= j1; j += 8u) {
                     uint32_t c[8];
@@ -593,11 +645,18 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
     // reduce_partials() sums the slots afterwards.  (Flushing with global atomics instead had
     // ~1000 workgroups queue on the same few hundred counters at the same moment: 6 % of the
     // kernel's time.)
+    if constexpr (GROUPED) {   // [deltas 16 | n_slots planes]
+        uint32_t *mine = P.scratch + (size_t)blockIdx.x * gk->scratch_words;
+        const uint32_t n_words = gk->n_slots * GROUP_PLANE_WORDS;
+        for (uint32_t i = tid; i < n_words; i += TILED_THREADS) mine[GROUP_SCRATCH_DELTA + i] = table[i];
+        if (tid < 16u) mine[tid] = tid < (uint32_t)ST_USED ? (uint32_t)lds_delta[tid] : 0u;
+    } else {
     uint32_t *mine = P.scratch + (size_t)blockIdx.x * SCRATCH_WORDS;
     for (uint32_t i = tid; i < 32u * 32u; i += TILED_THREADS) mine[i] = DO_PSS ? table[i] : 0u;
     for (uint32_t i = tid; i < 512u; i += TILED_THREADS)
         mine[SCRATCH_KMER + i] = (LDS_KMER && i < 2u * (1u << (2 * P.K))) ? lds_kmer[i] : 0u;
     if (tid < 16u) mine[SCRATCH_DELTA + tid] = tid < (uint32_t)ST_USED ? (uint32_t)lds_delta[tid] : 0u;
+    }
 }
 
 
@@ -1121,6 +1180,91 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P
     // the kernel's single argument, as it lies in the kernarg segment (for the out-of-line path)
     const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
     tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta, refs_lds);
+}
+
+// ---------------------------------------------------------------------------------------
+// -G: one set of substitution tables per read group, in one pass over the records
+// ---------------------------------------------------------------------------------------
+// The grouped kernels take the group table as a second argument; it sits in the kernarg segment
+// right behind TallyParams (HIP lays kernel arguments out in order at their natural alignment).
+constexpr size_t GROUP_KERNARG_OFFSET = (sizeof(TallyParams) + alignof(GroupParams) - 1) & ~(alignof(GroupParams) - 1);
+
+// tally_tiled with every record's counts in its group's plane.  Dynamic LDS: the staging buffer,
+// then (n_slots + 1) planes of 1024 words -- n_slots groups of this launch and the trash plane.
+// Whole records are staged (the RG tag sits behind QUAL).  Substitution tables only.
+template <bool LATER_PASS>
+__global__ void __launch_bounds__(TILED_THREADS) tally_tiled_grouped(const TallyParams P, const GroupParams G) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
+    __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
+    __shared__ uint32_t toffs[2u * (TILED_MAX_T + 4u)];
+    __shared__ uint32_t grp_lds[TILED_MAX_T];
+    __shared__ uint32_t lds_kmer[1];
+    __shared__ int32_t lds_delta[ST_USED];
+    __shared__ uint4 refs_lds[REF_LDS_ENTRIES + 1];
+    const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
+    const GroupParams *gk = (const GroupParams *)((const uint8_t *)kernarg + GROUP_KERNARG_OFFSET);
+    uint32_t *table = (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces));
+    tally_tiled_body<true, false, false, LATER_PASS, true>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta, refs_lds,
+                                                           gk, grp_lds);
+}
+// dynamic LDS a grouped launch may take: the CU's 160 KiB less the kernel's static objects (~10.6 KiB) and some margin
+constexpr uint32_t GROUPED_LDS_BUDGET = 148u * 1024u;
+__host__ __device__ inline uint32_t tiled_grouped_lds_bytes(uint32_t T, uint32_t pieces, uint32_t n_slots) {
+    return tiled_lds_bytes(T, pieces) + (n_slots + 1u) * GROUP_PLANE_WORDS * 4u;
+}
+
+// reduce_partials for tally_tiled_grouped: slot layout [deltas 16 | n_slots planes]; plane slot s
+// of the launch is plane plane0 + s of the counter block.  The status deltas (and the launch's
+// record credit) belong to the launch of rows 0.. and planes 0..
+__global__ void __launch_bounds__(256) reduce_partials_grouped(const TallyParams P, const GroupParams G, uint32_t n_slots) {
+    const uint32_t sw = G.scratch_words;
+    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t i = gid % sw, g = gid / sw;
+    if (g >= REDUCE_GROUPS) return;
+    const uint32_t n_pos = (uint32_t)P.N + 2u;
+    unsigned long long *dst = nullptr;
+    bool is_delta = false;
+    if (i < GROUP_SCRATCH_DELTA) {
+        if (i < (uint32_t)ST_USED && P.row_base == 0u && G.plane0 == 0u) { dst = &P.counters[P.off_stats + i]; is_delta = true; }
+    } else {
+        const uint32_t w = (i - GROUP_SCRATCH_DELTA) & (GROUP_PLANE_WORDS - 1u), plane = G.plane0 + (i - GROUP_SCRATCH_DELTA) / GROUP_PLANE_WORDS;
+        const uint32_t row = P.row_base + (w & 31u), ct = w >> 5, t = ct & 1u, cell = ct >> 1;
+        const uint32_t base = plane ? G.off_groups + (plane - 1u) * G.plane_words : 0u;
+        if (plane <= G.n_groups && row < n_pos) dst = &P.counters[base + (t ? P.off_rev : 0u) + row * 16u + cell];
+    }
+    if (!dst) return;
+    long long sum = 0;
+    const uint32_t *p = P.scratch + i;
+#pragma unroll 8
+    for (uint32_t b = g; b < n_slots; b += REDUCE_GROUPS) {
+        const uint32_t v = p[(size_t)b * sw];
+        sum += is_delta ? (long long)(int32_t)v : (long long)v;
+    }
+    if (is_delta && g == 0u && (i == ST_RECORDS || i == ST_PSS_OK)) sum += P.n_recs_dev ? *P.n_recs_dev : P.n_recs;
+    if (sum) atomicAdd(dst, (unsigned long long)sum);
+}
+
+// tally_simple with every record's counts in its group's plane (global atomics; the cross-check
+// of tally_tiled_grouped).  Substitution tables only.
+__global__ void __launch_bounds__(256) tally_simple_grouped(const TallyParams P, const GroupParams G) {
+    __shared__ int32_t lds_delta[ST_USED];
+    if (threadIdx.x < ST_USED) lds_delta[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < P.n_recs; r += stride) {
+        const uint32_t o0 = P.offs[r], o1 = P.offs[r + 1];
+        GlobalBytes src{P.recs + o0};
+        const RecHdr h = decode_hdr(src, o1 - o0);
+        const Plan pl = make_plan<true, false>(P, src, h);
+        if (pl.pss_fwd || pl.pss_rev) {
+            const uint32_t plane = read_group_plane(src, h, G);
+            unsigned long long *base = P.counters + (plane ? G.off_groups + (plane - 1u) * G.plane_words : 0u);
+            tally_pss_record(P, GlobalTable{base, P.off_rev}, src, h, pl);
+        }
+        book_events(true, false, record_events(true, false, pl, false), lds_delta);
+    }
+    __syncthreads();
+    flush_events(true, false, P, lds_delta);
 }
 
 // genome-kmer-count (genome-kmer-count.c:69-79): every k-mer start of the device genome.  Each

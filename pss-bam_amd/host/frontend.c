@@ -7,6 +7,7 @@
  * reduce at the end.
  */
 #include "frontend.h"
+#include "read_groups.h"
 
 #include <errno.h>
 #include <fcntl.h>
@@ -27,6 +28,7 @@
 #include "sam_reader.h"
 
 int frontend_fast_exit = 0;
+int frontend_group_by_rg = 0;
 
 /* Start-up work that overlaps the caller's FASTA load.  The reference is serial by construction -- load the
  * genome, then loop over the alignments (pss-bam.c:751-783) -- but only the TALLY needs reference bases: a helper
@@ -47,6 +49,8 @@ static struct early_feed {
     char *up, *down, *rg;           /* the strings cfg points at */
     uint64_t fasta_bytes;
     pssbam_engine *eng[64];
+    char **rg_ids;                  /* -G: the BAM header's @RG IDs, set on every engine after create */
+    int n_rg;
     int n_gpus, engines_ok, engines_done, fed, feed_rc, genome_set, failed;
     device_feed_stats dfs;
     char err[600];
@@ -119,7 +123,8 @@ typedef struct {
 static void *engine_make_main(void *arg)
 {
     engine_make_job *j = (engine_make_job *)arg;
-    if (pssbam_engine_create(&j->cfg, j->out) || pssbam_engine_feed_open(*j->out, j->n_ref, EF.fasta_bytes)) {
+    if (pssbam_engine_create(&j->cfg, j->out) || pssbam_engine_feed_open(*j->out, j->n_ref, EF.fasta_bytes) ||
+        (EF.n_rg > 0 && pssbam_engine_set_read_groups(*j->out, EF.n_rg, (const char *const *)EF.rg_ids))) {
         j->rc = 1;
         snprintf(j->err, sizeof j->err, "%s", pssbam_last_error());   /* (the message is this thread's) */
     }
@@ -141,6 +146,7 @@ static void early_feed_main(void)
     pthread_t pin_th;
     const int pin_started = pthread_create(&pin_th, NULL, pin_main, NULL) == 0;
     const bam_header *h = bam_reader_header(early_rd);
+    if (frontend_group_by_rg && (EF.n_rg = pss_parse_read_groups(h->text, h->l_text, &EF.rg_ids)) < 0) EF.n_rg = 0;
     /* one engine per GPU, all created at once: a device's first touch (context, queues, code objects) takes ~0.08 s, and
      * eight of them one after the other would cost more than the whole command does on one GPU */
     engine_make_job job[64];
@@ -380,11 +386,31 @@ int env_gpu_count(void)
 
 void run_result_free(run_result *res)
 {
+    pss_free_read_groups(res->group_ids, res->n_groups);
+    free(res->group_fwd);
+    free(res->group_rev);
     free(res->fwd);
     free(res->rev);
     free(res->k5);
     free(res->k3);
     memset(res, 0, sizeof *res);
+}
+
+/* -G: the @RG IDs of the input's header go to every engine (and into *res); a header without any leaves the engines
+ * ungrouped.  Returns 0 or -1 after a diagnostic. */
+static int send_read_groups(pssbam_engine **eng, int n_gpus, const char *text, size_t len, run_result *res)
+{
+    if ((res->n_groups = pss_parse_read_groups(text, len, &res->group_ids)) < 0) {
+        res->n_groups = 0;
+        fprintf(stderr, "Error: out of memory\n");
+        return -1;
+    }
+    for (int g = 0; g < n_gpus && res->n_groups > 0; g++)
+        if (pssbam_engine_set_read_groups(eng[g], res->n_groups, (const char *const *)res->group_ids)) {
+            fprintf(stderr, "Error: GPU engine %d: %s\n", g, pssbam_last_error());
+            return -1;
+        }
+    return 0;
 }
 
 int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, int n_gpus, run_result *res)
@@ -500,6 +526,12 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
         }
         refs_sent = bam_reader_header(rd)->n_ref;
         dfs = EF.dfs;
+        if (frontend_group_by_rg) { /* the helper set these IDs on its engines */
+            res->n_groups = EF.n_rg;
+            res->group_ids = EF.rg_ids;
+            EF.rg_ids = NULL;
+            EF.n_rg = 0;
+        }
         if (verbose)
             fprintf(stderr, "[pssbam] early feed (helper thread, seconds after start-up began): HIP runtime up %.3f, engines %.3f, genome upload "
                             "enqueued %.3f (took this thread %.3f), references set + put-off tallies launched %.3f (took %.3f), feed drained %.3f\n",
@@ -520,7 +552,11 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
                 fprintf(stderr, "Error: GPU engine %d: %s\n", g, pssbam_last_error());
                 goto done;
             }
+        /* -G on BAM input: the header is known now (SAM text: once its header lines have been read, below) */
+        if (frontend_group_by_rg && rd && send_read_groups(eng, n_gpus, bam_reader_header(rd)->text, bam_reader_header(rd)->l_text, res))
+            goto done;
     }
+    int groups_sent = !frontend_group_by_rg || rd != NULL;
     t_engine = now_s() - t_mark; t_mark = now_s();
     if (device_feed && rd && !adopted) {
         const bam_header *h = bam_reader_header(rd);
@@ -610,6 +646,12 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             fprintf(stderr, "Error: %s: %s\n", aln_path, rd ? bam_reader_error(rd) : sam_reader_error(sd));
             goto done;
         }
+        if (!groups_sent) { /* SAM text: its header lines are in once the first batch (or the end) is */
+            size_t hl = 0;
+            const char *ht = sam_reader_header_text(sd, &hl);
+            if (send_read_groups(eng, n_gpus, ht, hl, res)) goto done;
+            groups_sent = 1;
+        }
         if (n == 0) break;
         n_batches++;
         /* reference names: fixed by the BAM header; for SAM text the table grows as new RNAMEs
@@ -675,6 +717,17 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
     if (pssbam_engine_finish(eng[0], res->fwd, res->rev, res->k5, res->k3, res->stats)) {
         fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
         goto done;
+    }
+    if (res->n_groups > 0) {
+        const size_t cells = (size_t)(cfg->pss.region_len + 2) * 16;
+        res->group_fwd = (unsigned long *)calloc(cells * (size_t)res->n_groups, sizeof(unsigned long));
+        res->group_rev = (unsigned long *)calloc(cells * (size_t)res->n_groups, sizeof(unsigned long));
+        if (!res->group_fwd || !res->group_rev) { fprintf(stderr, "Error: out of memory\n"); goto done; }
+        for (int k = 0; k < res->n_groups; k++)
+            if (pssbam_engine_finish_groups(eng[0], k, res->group_fwd + k * cells, res->group_rev + k * cells)) {
+                fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+                goto done;
+            }
     }
     t_finish = now_s() - t_mark;
     if (verbose) {

@@ -14,7 +14,15 @@ typedef struct run_result {
     uint64_t stats[PSSBAM_ST_N];
     double inflate_s, total_s;
     int n_gpus;
+    /* pss-bam -G (frontend_group_by_rg): the header's @RG IDs and each one's tables, (region_len+2)*16 per group */
+    int n_groups;
+    char **group_ids;
+    unsigned long *group_fwd, *group_rev;
 } run_result;
+
+/* pss-bam -G: every engine gets the input header's @RG IDs (pssbam_engine_set_read_groups) and run_tally()
+ * returns one pair of tables per ID beside the totals.  Set before frontend_warmup_start. */
+extern int frontend_group_by_rg;
 
 /* Streams every alignment of `aln_path` (BGZF BAM, or SAM text plain/gzip) through engines built from `cfg` on
  * n_gpus devices (batches dealt round-robin), sums the counter blocks onto device 0 with

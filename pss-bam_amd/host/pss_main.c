@@ -7,6 +7,9 @@
  *     `samtools view` child and a text parser;
  *   - filtering and tallying of every alignment happen on the GPU(s) (include/pssbam_hip.h);
  *   - PSSBAM_NGPU=<n> in the environment spreads record batches over n GPUs of the node.
+ * Added: -G writes, beside the tables of all reads, one pair of tables per @RG ID of the header
+ * (<prefix>.<ID>.pss.*.txt, the ID file-name encoded: read_groups.h), each the same as `-R <ID>`
+ * would write -- from one pass over the input instead of one run per read group.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -19,6 +22,7 @@
 
 #include "fasta-genome-io.h"
 #include "frontend.h"
+#include "read_groups.h"
 #include "report.h"
 
 int main(int argc, char *argv[])
@@ -26,12 +30,12 @@ int main(int argc, char *argv[])
     const double age_main = frontend_process_age_s();
     frontend_detach_start();   /* the caller gets its prompt back when the reports are written, not when 30 GB of device buffers are gone */
     const double t_main = frontend_now_s();
-    int region_len = 15, min_mq = 0, merged_only = 0, option;
+    int region_len = 15, min_mq = 0, merged_only = 0, by_group = 0, option;
     unsigned long min_read_len = 0, max_read_len = 250000000;
     const char *up_ctx = "ACGT", *down_ctx = "ACGT";
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL, *read_group = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:m")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mG")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -43,6 +47,7 @@ int main(int argc, char *argv[])
         case 'U': up_ctx = optarg; break;
         case 'D': down_ctx = optarg; break;
         case 'm': merged_only = 1; break;
+        case 'G': by_group = 1; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -79,12 +84,16 @@ int main(int argc, char *argv[])
         fprintf(stderr, "-r must not be negative.\n");
         exit(1);
     }
+    if (by_group && read_group) {
+        fprintf(stderr, "-G (tables per read group) and -R (one read group) exclude each other.\n");
+        exit(1);
+    }
 
     /* "Full command" banner: four shapes, as the reference prints them (pss-bam.c:728-749) */
     fprintf(stderr, "Full command: %s -F %s -B %s -o %s -r %d -l %lu -L %lu -q %d", argv[0], fasta_fn, bam_fn,
             out_prefix, region_len, min_read_len, max_read_len, min_mq);
     if (read_group) fprintf(stderr, " -R %s", read_group);
-    fprintf(stderr, " -U %s -D %s%s\n", up_ctx, down_ctx, merged_only ? " -m" : "");
+    fprintf(stderr, " -U %s -D %s%s%s\n", up_ctx, down_ctx, merged_only ? " -m" : "", by_group ? " -G" : "");
 
     pssbam_config cfg;
     memset(&cfg, 0, sizeof cfg);
@@ -101,6 +110,7 @@ int main(int argc, char *argv[])
     cfg.device = 0;
     cfg.kernel = PSSBAM_KERNEL_AUTO;
 
+    frontend_group_by_rg = by_group;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
      * load; only the tally launches wait for the genome (frontend.c) */
@@ -124,6 +134,22 @@ int main(int argc, char *argv[])
     pss_sub_rates(region_len, res.rev, rev_rates);
     pss_write_counts(fasta_fn, bam_fn, out_prefix, region_len, res.fwd, res.rev);
     pss_write_rates(fasta_fn, bam_fn, out_prefix, region_len, fwd_rates, rev_rates);
+    if (by_group && res.n_groups == 0)
+        fprintf(stderr, "Warning: -G: the header of %s has no @RG line; only the tables of all reads were written.\n", bam_fn);
+    for (int k = 0; k < res.n_groups; k++) { /* <prefix>.<ID>: what `-R <ID> -o <prefix>.<ID>` writes */
+        const size_t cells = (size_t)(region_len + 2) * 16;
+        const size_t tag_len = pss_rg_file_tag(res.group_ids[k], NULL, 0);
+        char *gprefix = (char *)malloc(strlen(out_prefix) + tag_len + 2);
+        if (!gprefix) { fprintf(stderr, "Error: out of memory\n"); exit(1); }
+        strcpy(gprefix, out_prefix);
+        strcat(gprefix, ".");
+        pss_rg_file_tag(res.group_ids[k], gprefix + strlen(gprefix), tag_len + 1);
+        pss_sub_rates(region_len, res.group_fwd + k * cells, fwd_rates);
+        pss_sub_rates(region_len, res.group_rev + k * cells, rev_rates);
+        pss_write_counts(fasta_fn, bam_fn, gprefix, region_len, res.group_fwd + k * cells, res.group_rev + k * cells);
+        pss_write_rates(fasta_fn, bam_fn, gprefix, region_len, fwd_rates, rev_rates);
+        free(gprefix);
+    }
 
     if (getenv("PSSBAM_STATS")) {
         static const char *nm[] = {"records", "rg_dropped", "parse_skip", "no_contig", "pss_ok", "pss_filtered"};

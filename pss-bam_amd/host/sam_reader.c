@@ -73,6 +73,8 @@ struct sam_reader {
     char *tbuf;          /* gz path: text slab; [0, tlen) valid, the tail may be a partial line */
     size_t tcap, tlen, tpos;
     int in_header;
+    char *hdr;           /* the header lines read so far (sam_reader_header_text) */
+    size_t hdr_len, hdr_cap;
     char **names;
     int32_t n_names, names_cap;
     uint8_t *buf;
@@ -197,6 +199,11 @@ sam_reader *sam_reader_open(const char *path, size_t batch_bytes, char *err, siz
 int32_t sam_reader_n_ref(const sam_reader *r) { return r->n_names; }
 const char *const *sam_reader_ref_names(const sam_reader *r) { return (const char *const *)r->names; }
 uint64_t sam_reader_lines_skipped(const sam_reader *r) { return r->skipped; }
+const char *sam_reader_header_text(const sam_reader *r, size_t *len)
+{
+    *len = r->hdr_len;
+    return r->hdr;
+}
 const char *sam_reader_error(const sam_reader *r) { return r->err; }
 
 void sam_reader_close(sam_reader *r)
@@ -206,6 +213,7 @@ void sam_reader_close(sam_reader *r)
     if (r->map) munmap((void *)r->map, r->map_len);
     for (int32_t i = 0; i < r->n_names; i++) free(r->names[i]);
     free(r->names);
+    free(r->hdr);
     free(r->buf);
     free(r->offs);
     free(r->tbuf);
@@ -464,6 +472,17 @@ int64_t sam_reader_next(sam_reader *r, const uint8_t **records, const uint32_t *
             memcpy(tmp, a, n);
             tmp[n] = '\0';
             take_header_line(r, tmp);
+            if (r->hdr_len + (size_t)(e - a) + 1 > r->hdr_cap) {
+                size_t nc = r->hdr_cap ? 2 * r->hdr_cap : 4096;
+                while (nc < r->hdr_len + (size_t)(e - a) + 1) nc *= 2;
+                char *t = (char *)realloc(r->hdr, nc);
+                if (!t) { set_err(r, "out of memory"); return -1; }
+                r->hdr = t;
+                r->hdr_cap = nc;
+            }
+            memcpy(r->hdr + r->hdr_len, a, (size_t)(e - a));
+            r->hdr_len += (size_t)(e - a);
+            r->hdr[r->hdr_len] = '\0';
             a = e;
         }
         if (a == b) continue;

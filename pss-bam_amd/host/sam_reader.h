@@ -23,6 +23,8 @@ int32_t sam_reader_n_ref(const sam_reader *r);
 const char *const *sam_reader_ref_names(const sam_reader *r);
 /* next batch of encoded records (same contract as bam_reader_next) */
 int64_t sam_reader_next(sam_reader *r, const uint8_t **records, const uint32_t **offsets, size_t *nbytes);
+/* the leading '@' lines read so far (complete once sam_reader_next has returned records or 0), NULL if none */
+const char *sam_reader_header_text(const sam_reader *r, size_t *len);
 uint64_t sam_reader_lines_skipped(const sam_reader *r); /* lines line2saml would have rejected */
 const char *sam_reader_error(const sam_reader *r);
 void sam_reader_close(sam_reader *r);
