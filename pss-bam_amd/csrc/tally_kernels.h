@@ -219,6 +219,12 @@ static_assert(TILED_MAX_T * 2 == TILED_THREADS, "CODES maps one (read, end) pair
 // before any lane reads `stage`, and nothing else writes `stage`.  (Compiler-counted vmcnt(N)
 // waits for its own loads only get stricter with unseen operations in flight, never weaker:
 // vmcnt retires in order.)
+//
+// The pieces are loaded with the nontemporal policy (`nt`): the record stream is read exactly once
+// per launch and is many times the L2 and MALL, so keeping its lines only evicts the reference
+// windows, which neighbouring reads do re-read (those gathers keep the default policy).  The C3
+// launch is bound by this stream -- switching the whole CODES phase off takes only 3 % off it
+//  -- and `nt` lets it run closer to the chip's plain streaming rate.
 __device__ __forceinline__ void stage_tile_dma(const uint8_t *recs, uint64_t recs_limit, const uint32_t *tile_offs,
                                                uint32_t count, uint32_t pieces, uint8_t *stage, uint32_t tid) {
     const uint32_t n_pieces = count * pieces;
@@ -234,7 +240,7 @@ __device__ __forceinline__ void stage_tile_dma(const uint8_t *recs, uint64_t rec
             const uint8_t *src = recs + a;
             const uint32_t m0v = __builtin_amdgcn_readfirstlane(lds0 + (q0 << 4));
             uint32_t keep;   // m0 is compiler-reserved and cannot be named as a clobber: save and restore it
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
                          : "=&s"(keep) : "v"(src), "s"(m0v) : "memory");
         }
     }
