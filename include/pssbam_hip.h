@@ -34,6 +34,7 @@ extern "C" {
 #define PSSBAM_ABI_VERSION 1
 #define PSSBAM_MAX_KLEN 15     /* 4^15 64-bit bins per k-mer table = 8.6 GB of device memory */
 #define PSSBAM_MAX_READ_GROUPS 4096  /* pssbam_engine_set_read_groups */
+#define PSSBAM_MAX_LENGTH_BINS 64    /* pssbam_engine_set_length_bins: at most 63 edges */
 
 /* error codes */
 #define PSSBAM_OK 0
@@ -191,15 +192,30 @@ int pssbam_engine_reset(pssbam_engine *e);
  * over every record. */
 int pssbam_engine_set_read_groups(pssbam_engine *e, int32_t n, const char *const *ids);
 /* Drains the engine like pssbam_engine_finish and copies one group's two tables ((region_len+2)*16 each, any
- * pointer may be NULL): group -1 is the unassigned bucket, 0..n-1 the IDs in the order given. */
+ * pointer may be NULL): group -1 is the unassigned bucket, 0..n-1 the IDs in the order given.  With length bins
+ * (below) group k is bin k and group -1 is all zeros. */
 int pssbam_engine_finish_groups(pssbam_engine *e, int32_t group, unsigned long *fwd, unsigned long *rev);
+
+/* Length bins (pss-bam -S): one set of substitution tables per fragment-length bin in a single pass over the
+ * records, instead of one `-l <lo> -L <hi>` run per window.  edges[0..n_edges-1], n_edges in
+ * 1..PSSBAM_MAX_LENGTH_BINS-1, must rise strictly with cfg.pss.min_read_len < edges[0] and
+ * edges[n_edges-1] <= cfg.pss.max_read_len.  Bin k is [edges[k-1], edges[k]-1], bin 0 starts at min_read_len and
+ * bin n_edges ends at max_read_len: a record that passes every filter lands in bin #{edges <= its length}, the
+ * length -l / -L compare (|TLEN| for paired reads, else the SEQ length), so bin k holds exactly what
+ * `-l <bin start> -L <bin end>` tallies.  Legal after create (or reset) and before the first tally launch, like
+ * pssbam_engine_set_read_groups, and allowed with cfg.read_group (bins of one read group).  PSSBAM_EINVAL with
+ * PSSBAM_TALLY_KMER, with read groups set or with bad edges, PSSBAM_ESTATE once records have been tallied or the
+ * counter block has been bound.  The bins survive pssbam_engine_reset; pssbam_engine_finish keeps returning the
+ * totals over every bin, pssbam_engine_finish_groups(e, k, ...) returns bin k. */
+int pssbam_engine_set_length_bins(pssbam_engine *e, int32_t n_edges, const uint32_t *edges);
 
 /* The device-resident counter block [fwd | rev | k5 | k3 | stats] as one array of
  * n_u64 64-bit words, for a caller-side RCCL reduce across GPUs (sum, uint64).  With read groups it is
  * [fwd | rev | stats | fwd_0 | rev_0 | ... | fwd_n-1 | rev_n-1]: the leading fwd | rev are the unassigned
  * bucket, group g's pair ((region_len+2)*16 words each) starts at 2*(region_len+2)*16 + PSSBAM_ST_N +
- * g*2*(region_len+2)*16 (the k-mer tables are empty: read groups exclude PSSBAM_TALLY_KMER).  The block is
- * still summed across GPUs as one u64 array. */
+ * g*2*(region_len+2)*16 (the k-mer tables are empty: read groups exclude PSSBAM_TALLY_KMER).  With length bins the
+ * layout is the same with bin k in group k's place, and the leading fwd | rev stay zero.  The block is still
+ * summed across GPUs as one u64 array. */
 int pssbam_engine_counters_device(pssbam_engine *e, void **d_counters, size_t *n_u64);
 
 /* Makes the engine accumulate into caller-owned device memory (n_u64 words, as reported

@@ -40,9 +40,10 @@ HIP_SYMBOLS = [
     "pssbam_bgzf_inflate_device", "pssbam_bgzf_inflate_host", "pssbam_engine_submit_bgzf", "pssbam_engine_wait_bgzf_copied",
     "pssbam_engine_feed_status", "pssbam_engine_feed_break", "pssbam_engine_feed_handoff", "pssbam_feed_reserve", "pssbam_engine_hint_records",
     "pssbam_engine_set_genome_async", "pssbam_engine_genome_wait", "pssbam_engine_feed_open", "pssbam_feed_release",
-    "pssbam_engine_set_read_groups", "pssbam_engine_finish_groups",
+    "pssbam_engine_set_read_groups", "pssbam_engine_finish_groups", "pssbam_engine_set_length_bins",
 ]
 MAX_READ_GROUPS = 4096
+MAX_LENGTH_BINS = 64
 EBUSY = -7
 
 
@@ -104,6 +105,7 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_reset.argtypes = [C.c_void_p]
     L.pssbam_engine_set_read_groups.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p)]
     L.pssbam_engine_finish_groups.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.pssbam_engine_set_length_bins.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)]
     L.pssbam_engine_counters_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.pssbam_engine_bind_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.pssbam_engine_genome_kmer_count.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -171,10 +173,12 @@ class Engine:
     """One engine = one GPU, one stream.  Options mirror the two reference CLIs:
     `pss` = dict(region_len, min_read_len, max_read_len, min_mq, up_ctx, down_ctx, merged_only),
     `kmer` = dict(klen, min_mq, min_read_len, max_read_len, merged_only).
-    `read_groups` = @RG IDs (pss-bam -G): one set of substitution tables per ID, see set_read_groups."""
+    `read_groups` = @RG IDs (pss-bam -G): one set of substitution tables per ID, see set_read_groups.
+    `length_bins` = length bin edges (pss-bam -S): one set of substitution tables per bin, see set_length_bins."""
 
     def __init__(self, pss: dict | None = None, kmer: dict | None = None, read_group: str | None = None,
-                 kernel: int = KERNEL_AUTO, device: int = -1, read_groups: list[str] | None = None):
+                 kernel: int = KERNEL_AUTO, device: int = -1, read_groups: list[str] | None = None,
+                 length_bins: list[int] | None = None):
         L = hip_lib()
         cfg = _Config()
         cfg.abi_version = 1
@@ -187,6 +191,7 @@ class Engine:
                                pss.get("max_read_len", 250000000), pss.get("min_mq", 0), up, dn,
                                int(pss.get("merged_only", False)))
             self.region_len = cfg.pss.region_len
+            self._len_range = (cfg.pss.min_read_len, cfg.pss.max_read_len)
         if kmer is not None:
             cfg.kmer = _KmerOpts(kmer.get("klen", 8), kmer.get("min_mq", 0), kmer.get("min_read_len", 0),
                                  kmer.get("max_read_len", 250000000), int(kmer.get("merged_only", False)))
@@ -203,8 +208,21 @@ class Engine:
         self._h = h
         self._L = L
         self.read_groups: list[str] = []
+        self.length_bins: list[tuple[int, int]] = []
         if read_groups is not None:
             self.set_read_groups(read_groups)
+        if length_bins is not None:
+            self.set_length_bins(length_bins)
+
+    def set_length_bins(self, edges: list[int]):
+        """pss-bam -S: tallies every record into the tables of its length bin [min_read_len, e1-1], [e1, e2-1], ...,
+        [ek, max_read_len] (the length -l / -L compare).  Before the first tally, like set_read_groups."""
+        edges = [int(x) for x in edges]
+        arr = (C.c_uint32 * max(len(edges), 1))(*[x & 0xFFFFFFFF for x in edges])
+        _chk(self._L.pssbam_engine_set_length_bins(self._h, len(edges), arr))
+        lo, hi = self._len_range
+        starts, ends = [lo] + edges, [x - 1 for x in edges] + [hi]
+        self.length_bins = list(zip(starts, ends))
 
     def set_read_groups(self, ids: list[str]):
         """pss-bam -G: tallies every record into the tables of the ID its first RG:Z value equals (the unassigned
@@ -223,6 +241,16 @@ class Engine:
             _chk(self._L.pssbam_engine_finish_groups(self._h, g, fwd.ctypes.data, rev.ctypes.data))
             if key not in out:   # a repeated ID: its first index holds the counts
                 out[key] = Tables(fwd, rev, None, None, {})
+        return out
+
+    def finish_bins(self) -> dict:
+        """{(lo, hi): Tables} per length bin (fwd / rev only; drains like finish)"""
+        out = {}
+        for k, key in enumerate(self.length_bins):
+            fwd = np.zeros((self.region_len + 2, 16), dtype=np.uint64)
+            rev = np.zeros_like(fwd)
+            _chk(self._L.pssbam_engine_finish_groups(self._h, k, fwd.ctypes.data, rev.ctypes.data))
+            out[key] = Tables(fwd, rev, None, None, {})
         return out
 
     def close(self):
@@ -404,7 +432,10 @@ class Engine:
         base = lay["stats"] + ST_N
         lay["groups"] = [{"id": g, "fwd": base + k * 2 * rows * 16, "rev": base + k * 2 * rows * 16 + rows * 16}
                          for k, g in enumerate(self.read_groups)]
-        lay["n_u64"] = base + len(self.read_groups) * 2 * rows * 16
+        # length bins: bin k's pair sits where group k's would (plane 0 stays empty)
+        lay["length_bins"] = [{"bin": b, "fwd": base + k * 2 * rows * 16, "rev": base + k * 2 * rows * 16 + rows * 16}
+                              for k, b in enumerate(self.length_bins)]
+        lay["n_u64"] = base + (len(self.read_groups) + len(self.length_bins)) * 2 * rows * 16
         return lay
 
     def genome_kmer_count(self, klen: int) -> np.ndarray:

@@ -200,6 +200,8 @@ struct pssbam_engine {
     uint8_t *d_grp_ids = nullptr;
     uint32_t *d_grp_offs = nullptr, *d_grp_hash = nullptr;
     uint32_t grp_hash_mask = 0, off_groups = 0, plane_words = 0;
+    // -S (pssbam_engine_set_length_bins): plane 1 + k of the counter block holds length bin k
+    std::vector<uint32_t> len_edges;
     bool tallied = false;   // a tally launch since create / reset
     // counters
     unsigned long long *d_counters = nullptr;      // block in use (own or caller-bound)
@@ -741,6 +743,11 @@ static uint64_t sample_prefix_need(const uint8_t *bytes, uint64_t nbytes, bool w
 // -R and -G walk the aux fields, which sit behind QUAL: the tiled kernels stage whole records
 static bool whole_records(const pssbam_engine *e) { return e->has_rg || !e->groups.empty(); }
 
+// [fwd | rev] planes of the counter block behind the stats: one per read group (-G) or per length bin (-S)
+static uint32_t extra_planes(const pssbam_engine *e) {
+    return (uint32_t)e->groups.size() + (e->len_edges.empty() ? 0u : (uint32_t)e->len_edges.size() + 1u);
+}
+
 static uint32_t pieces_for(uint64_t need_max) {
     uint64_t pieces = (need_max + 15 + 15) / 16;  // + worst-case misalignment of the record start
     // records sit pieces*16 bytes apart in LDS: an even piece count puts every record start of a
@@ -809,6 +816,17 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         G.plane_words = e->plane_words;
         G.off_groups = e->off_groups;
     }
+    const bool binned = !e->len_edges.empty();
+    LenBinParams B{};
+    if (binned) {   // the grouped kernels' plane bookkeeping, with bin k as group k
+        G.n_groups = extra_planes(e);
+        G.plane0 = 0;
+        G.n_slots = G.n_groups + 1u;
+        G.plane_words = e->plane_words;
+        G.off_groups = e->off_groups;
+        B.n_edges = (uint32_t)e->len_edges.size();
+        std::copy(e->len_edges.begin(), e->len_edges.end(), B.edges);
+    }
 
     int kernel = c.kernel;
     if (d_n_recs && kernel == PSSBAM_KERNEL_SIMPLE) return fail(PSSBAM_EINVAL, "device-indexed blocks need the tiled kernels");
@@ -832,6 +850,7 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n_records + 255) / 256, (uint64_t)e->n_cu * 8);
         if (e->env_simple_blocks > 0) blocks = (uint32_t)e->env_simple_blocks;
         if (grouped) hipLaunchKernelGGL(tally_simple_grouped, dim3(blocks), dim3(256), 0, e->stream, P, G);
+        else if (binned) hipLaunchKernelGGL(tally_simple_lenbins, dim3(blocks), dim3(256), 0, e->stream, P, G, B);
         else if (lds_tab) hipLaunchKernelGGL(tally_simple<true>, dim3(blocks), dim3(256), tab_bytes, e->stream, P);
         else hipLaunchKernelGGL(tally_simple<false>, dim3(blocks), dim3(256), 0, e->stream, P);
     } else {
@@ -933,10 +952,11 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                                (uint32_t)(LK ? 1 : 0));                                            \
         }                                                                                          \
     } while (0)
-        if (grouped) {
-            // -G: every (32-row pass, plane pass) pair is one launch over the block.  A plane pass holds as
+        if (grouped || binned) {
+            // -G / -S: every (32-row pass, plane pass) pair is one launch over the block.  A plane pass holds as
             // many planes as fit the LDS beside the staging buffer (8 planes = 32 KiB always do: one pass for
-            // up to 7 groups); more groups take more passes, each re-reading the records.
+            // up to 7 groups or 6 bins -- plane 0 of -S stays empty but keeps its slot); more planes take more
+            // passes, each re-reading the records.
             const uint32_t n_planes = G.n_groups + 1u;
             const uint32_t stage_bytes = tiled_lds_bytes(T, pieces);
             const uint32_t fit = stage_bytes + 2u * GROUP_PLANE_WORDS * 4u <= GROUPED_LDS_BUDGET
@@ -951,7 +971,8 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                     G.scratch_words = GROUP_SCRATCH_DELTA + G.n_slots * GROUP_PLANE_WORDS;
                     const uint32_t glds = tiled_grouped_lds_bytes(T, pieces, G.n_slots);
                     const bool later = pass > 0;
-                    rc = later ? prep_kernel(e, 29, tally_tiled_grouped<true>, glds, &occ) : prep_kernel(e, 28, tally_tiled_grouped<false>, glds, &occ);
+                    if (binned) rc = later ? prep_kernel(e, 31, tally_tiled_lenbins<true>, glds, &occ) : prep_kernel(e, 30, tally_tiled_lenbins<false>, glds, &occ);
+                    else rc = later ? prep_kernel(e, 29, tally_tiled_grouped<true>, glds, &occ) : prep_kernel(e, 28, tally_tiled_grouped<false>, glds, &occ);
                     if (rc != PSSBAM_OK) break;
                     uint32_t grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)e->n_cu * occ * mult);
                     if (e->env_grid_wgs > 0) grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)e->env_grid_wgs);
@@ -964,7 +985,9 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                         HIP_TRY(hipMalloc(&e->d_scratch, e->scratch_slots * SCRATCH_WORDS * sizeof(uint32_t)));
                     }
                     P.scratch = e->d_scratch;
-                    if (later) hipLaunchKernelGGL(tally_tiled_grouped<true>, dim3(grid), dim3(TILED_THREADS), glds, e->stream, P, G);
+                    if (binned && later) hipLaunchKernelGGL(tally_tiled_lenbins<true>, dim3(grid), dim3(TILED_THREADS), glds, e->stream, P, G, B);
+                    else if (binned) hipLaunchKernelGGL(tally_tiled_lenbins<false>, dim3(grid), dim3(TILED_THREADS), glds, e->stream, P, G, B);
+                    else if (later) hipLaunchKernelGGL(tally_tiled_grouped<true>, dim3(grid), dim3(TILED_THREADS), glds, e->stream, P, G);
                     else hipLaunchKernelGGL(tally_tiled_grouped<false>, dim3(grid), dim3(TILED_THREADS), glds, e->stream, P, G);
                     hipLaunchKernelGGL(reduce_partials_grouped, dim3((G.scratch_words * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream,
                                        P, G, grid);
@@ -991,7 +1014,7 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         else { if (kmer_lds) LAUNCH_TILED(false, true, true, false); else LAUNCH_TILED(false, true, false, false); }
         // rows 32.. of a large -r: further passes over the same block, substitution rows only
         // (the status counters and the k-mer tally belong to pass 0)
-        for (uint32_t pass = 1; pass < n_passes && rc == PSSBAM_OK && !grouped; pass++) {
+        for (uint32_t pass = 1; pass < n_passes && rc == PSSBAM_OK && !grouped && !binned; pass++) {
             P.row_base = pass * TILED_ROWS;
             LAUNCH_TILED(true, false, false, true);
         }
@@ -1182,8 +1205,8 @@ extern "C" int pssbam_engine_finish(pssbam_engine *e, unsigned long *fwd, unsign
     HIP_TRY(hipMemcpy(h.data(), e->d_counters, e->n_counters * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     static_assert(sizeof(unsigned long) == 8, "LP64 expected");
     const size_t tab = (size_t)e->rows * 16;
-    // -G: the totals are every plane's sum (plane 0, the unassigned bucket, sits where an ungrouped engine keeps its tables)
-    for (size_t g = 0; g < e->groups.size(); g++)
+    // -G / -S: the totals are every plane's sum (plane 0, the unassigned bucket, sits where an ungrouped engine keeps its tables)
+    for (size_t g = 0; g < extra_planes(e); g++)
         for (size_t i = 0; i < 2 * tab; i++) h[i] += h[e->off_groups + g * e->plane_words + i];
     if (fwd) for (size_t i = 0; i < tab; i++) fwd[i] = (unsigned long)h[i];
     if (rev) for (size_t i = 0; i < tab; i++) rev[i] = (unsigned long)h[e->off_rev + i];
@@ -1195,8 +1218,9 @@ extern "C" int pssbam_engine_finish(pssbam_engine *e, unsigned long *fwd, unsign
 
 extern "C" int pssbam_engine_finish_groups(pssbam_engine *e, int32_t group, unsigned long *fwd, unsigned long *rev) {
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
-    if (e->groups.empty()) return fail(PSSBAM_ESTATE, "pssbam_engine_set_read_groups has not been called");
-    if (group < -1 || group >= (int32_t)e->groups.size()) return fail(PSSBAM_EINVAL, "group %d outside -1..%zu", group, e->groups.size() - 1);
+    const int32_t n_planes = (int32_t)extra_planes(e);
+    if (!n_planes) return fail(PSSBAM_ESTATE, "neither pssbam_engine_set_read_groups nor pssbam_engine_set_length_bins has been called");
+    if (group < -1 || group >= n_planes) return fail(PSSBAM_EINVAL, "group %d outside -1..%d", group, n_planes - 1);
     int rc = pssbam_engine_sync(e);
     if (rc) return rc;
     const size_t tab = (size_t)e->rows * 16;
@@ -1212,6 +1236,7 @@ extern "C" int pssbam_engine_set_read_groups(pssbam_engine *e, int32_t n, const 
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
     if (n < 1 || n > PSSBAM_MAX_READ_GROUPS || !ids) return fail(PSSBAM_EINVAL, "read group count %d outside 1..%d", n, PSSBAM_MAX_READ_GROUPS);
     if (e->has_rg) return fail(PSSBAM_EINVAL, "read groups and a -R read group filter exclude each other");
+    if (!e->len_edges.empty()) return fail(PSSBAM_EINVAL, "read groups and length bins exclude each other");
     if (e->cfg.tally_mask != PSSBAM_TALLY_PSS) return fail(PSSBAM_EINVAL, "read groups split the substitution tables only (no PSSBAM_TALLY_KMER)");
     for (int32_t i = 0; i < n; i++)
         if (!ids[i]) return fail(PSSBAM_EINVAL, "read group %d is NULL", i);
@@ -1262,6 +1287,35 @@ extern "C" int pssbam_engine_set_read_groups(pssbam_engine *e, int32_t n, const 
     e->grp_hash_mask = hsize - 1;
     e->groups = std::move(groups);
     e->dev_pieces = 0;   // whole records are staged from now on: resampled at the next launch
+    return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_set_length_bins(pssbam_engine *e, int32_t n_edges, const uint32_t *edges) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (n_edges < 1 || n_edges > PSSBAM_MAX_LENGTH_BINS - 1 || !edges)
+        return fail(PSSBAM_EINVAL, "length bin edge count %d outside 1..%d", n_edges, PSSBAM_MAX_LENGTH_BINS - 1);
+    if (!e->groups.empty()) return fail(PSSBAM_EINVAL, "length bins and read groups exclude each other");
+    if (e->cfg.tally_mask != PSSBAM_TALLY_PSS) return fail(PSSBAM_EINVAL, "length bins split the substitution tables only (no PSSBAM_TALLY_KMER)");
+    // l < e1 < ... < ek <= L: every bin [l, e1-1], [e1, e2-1], ..., [ek, L] is a non-empty -l / -L window
+    const uint64_t lo = e->cfg.pss.min_read_len, hi = e->cfg.pss.max_read_len;
+    for (int32_t i = 0; i < n_edges; i++) {
+        const uint64_t prev = i ? (uint64_t)edges[i - 1] : lo;
+        if (edges[i] <= prev || edges[i] > hi)
+            return fail(PSSBAM_EINVAL, "length bin edge %d (%u) must lie above %llu and at most at %llu", i, edges[i],
+                        (unsigned long long)prev, (unsigned long long)hi);
+    }
+    if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set length bins after create or reset, before the first tally");
+    if (e->d_counters != e->d_counters_own) return fail(PSSBAM_ESTATE, "a caller-bound counter block cannot grow: set length bins before bind_counters");
+    HIP_TRY(hipSetDevice(e->device));
+    // the counter block grows by one [fwd | rev] plane per bin (as for read groups: old buffers are retired, not freed)
+    const size_t n_counters = (size_t)e->off_groups + (size_t)(n_edges + 1) * e->plane_words;
+    unsigned long long *d_counters = nullptr;
+    HIP_TRY(hipMalloc(&d_counters, n_counters * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(d_counters, 0, n_counters * sizeof(unsigned long long), e->stream));
+    if (e->d_counters_own) e->retired.push_back(e->d_counters_own);
+    e->d_counters = e->d_counters_own = d_counters;
+    e->n_counters = n_counters;
+    e->len_edges.assign(edges, edges + n_edges);
     return PSSBAM_OK;
 }
 

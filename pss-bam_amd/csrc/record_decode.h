@@ -349,6 +349,23 @@ __device__ uint32_t read_group_plane(const Src &src, const RecHdr &h, const Grou
     return 0u;
 }
 
+// ---- length bins (-S) ------------------------------------------------------------------
+// The length-binned kernels' third argument (their second is a GroupParams whose n_groups is the
+// bin count, ids / hash unused).  Bin k is plane 1 + k; plane 0 stays empty.
+constexpr uint32_t MAX_LENGTH_EDGES = 63;   // PSSBAM_MAX_LENGTH_BINS - 1
+struct LenBinParams {
+    uint32_t n_edges;                      // 1..MAX_LENGTH_EDGES, strictly increasing
+    uint32_t edges[MAX_LENGTH_EDGES];      // bin k (k >= 1) starts at edges[k-1]
+};
+
+// Plane of a candidate read of pss length L (Plan::L, what -l / -L compare): 1 + #{edges <= L}.
+// The edges are wave-uniform (kernarg): scalar loads, one compare and add per edge.
+__device__ __forceinline__ uint32_t length_bin_plane(const LenBinParams &B, uint32_t L) {
+    uint32_t k = 1u;
+    for (uint32_t i = 0; i < B.n_edges; i++) k += B.edges[i] <= L ? 1u : 0u;
+    return k;
+}
+
 // ---- base codes ----------------------------------------------------------------------
 // Device-internal genome encoding: the byte permutation that swaps 'A'<->0, 'C'<->1,
 // 'G'<->2, 'T'<->3 and leaves every other value where it is (applied once at upload,

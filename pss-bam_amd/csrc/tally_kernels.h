@@ -39,6 +39,9 @@
 //  tally_tiled_grouped / tally_simple_grouped (-G): the same kernels with one table plane per read
 //                 group (record -> plane by its first RG:Z value, read_group_plane).
 //
+//  tally_tiled_lenbins / tally_simple_lenbins (-S): the same with one plane per fragment-length bin
+//                 (record -> plane by Plan::L, length_bin_plane); prefixes are staged as without planes.
+//
 // Integer/byte work only: no MFMA anywhere (the bound is HBM bandwidth).
 #pragma once
 
@@ -279,6 +282,32 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record_grouped(cons
     return record_events(true, false, gpl, false);
 }
 
+// The same for tally_tiled_lenbins: the plane of the record's length bin.
+__device__ __attribute__((noinline)) uint32_t tally_overflow_record_lenbins(const TallyParams *kernarg, const GroupParams *gk,
+                                                                            const LenBinParams *bk, uint32_t o0, uint32_t o1,
+                                                                            uint32_t *table) {
+    const TallyParams &P = *kernarg;
+    GlobalBytes gsrc{P.recs + o0};
+    const RecHdr gh = decode_hdr(gsrc, o1 - o0);
+    const Plan gpl = make_plan<true, false>(P, gsrc, gh);
+    if (gpl.pss_fwd || gpl.pss_rev) {
+        const uint32_t slot = length_bin_plane(*bk, gpl.L) - gk->plane0;
+        if (slot < gk->n_slots) tally_pss_record(P, LdsTableColumnMajor{table + slot * GROUP_PLANE_WORDS, P.row_base}, gsrc, gh, gpl);
+    }
+    return record_events(true, false, gpl, false);
+}
+
+// What picks a read's table plane in tally_tiled_body: nothing (one plane), its first RG:Z value
+// (-G), or its length bin (-S).
+enum PlaneSel { PLANES_NONE = 0, PLANES_RG, PLANES_LEN };
+
+template <PlaneSel PLANES, class Src>
+__device__ __forceinline__ uint32_t record_plane(const Src &src, const RecHdr &h, const Plan &pl, const GroupParams *gk,
+                                                 const LenBinParams *bk) {
+    if constexpr (PLANES == PLANES_RG) return read_group_plane(src, h, *gk);
+    else return length_bin_plane(*bk, pl.L);
+}
+
 // Reference windows, one per alignment end, each with STATIC byte positions:
 //   left  end (e = 0): 32 bytes from s-2      byte w <-> row w          (0,1 context; 2+i = position i)
 //   right end (e = 1): 32 bytes up to s+L+1   byte w <-> row 31-w       (31 -> row 0, 30 -> row 1, 29-i -> 2+i)
@@ -289,17 +318,20 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record_grouped(cons
 // it every LDS access issued while a DMA transfer is in flight is fenced behind vmcnt(0) and
 // the transfer cannot overlap the COLUMNS pass.
 //
-// GROUPED (-G, tally_tiled_grouped): `table` holds gk->n_slots planes of [(cell<<1)|table][row] plus
-// one trash plane behind them; every read's plane slot is resolved in CODES-A (read_group_plane)
-// and kept in grp_lds, and COLUMNS adds the wave's scalar slot offset to each real code.
-template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS, bool GROUPED = false>
+// PLANES_RG / PLANES_LEN (-G tally_tiled_grouped, -S tally_tiled_lenbins): `table` holds gk->n_slots
+// planes of [(cell<<1)|table][row] plus one trash plane behind them; every read's plane slot is
+// resolved in CODES-A (record_plane: read_group_plane or length_bin_plane) and kept in grp_lds, and
+// COLUMNS adds the wave's scalar slot offset to each real code.
+template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS, PlaneSel PLANES = PLANES_NONE>
 __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const TallyParams *kernarg,
                                                  uint8_t *__restrict__ stage, uint8_t *__restrict__ sheet,
                                                  uint32_t *__restrict__ table,
                                                  uint32_t *__restrict__ toffs,
                                                  uint32_t *__restrict__ lds_kmer,
                                                  int32_t *__restrict__ lds_delta, uint4 *__restrict__ refs_lds,
-                                                 const GroupParams *gk = nullptr, uint32_t *__restrict__ grp_lds = nullptr) {
+                                                 const GroupParams *gk = nullptr, uint32_t *__restrict__ grp_lds = nullptr,
+                                                 const LenBinParams *bk = nullptr) {
+    constexpr bool GROUPED = PLANES != PLANES_NONE;   // one table plane per read group / length bin
     const uint32_t T = P.reads_per_tile;   // <= TILED_MAX_T
     const uint32_t n_recs = P.n_recs_dev ? *P.n_recs_dev : P.n_recs;   // device-indexed blocks: the count lives in device memory
     const uint32_t pieces = P.prefix_pieces;  // 16-byte pieces staged per record
@@ -387,8 +419,9 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         // dead) so the lanes of a wave stay on one path
         LdsBytes src{stage, hdr_ok ? j * pieces * 16u + (o0 & 15u) : 0u};
         const RecHdr h = decode_hdr_lds(src, hdr_ok ? o1 - o0 : 0u);
-        // everything the path reads ends at QUAL[0] (the -R filter and -G walk the aux fields: whole record)
-        const uint32_t needed = (GROUPED || P.rg) ? o1 - o0 : h.qual_off + 1u;
+        // everything the path reads ends at QUAL[0] (the -R filter and -G walk the aux fields: whole record;
+        // a length bin needs nothing behind QUAL[0])
+        const uint32_t needed = (PLANES == PLANES_RG || P.rg) ? o1 - o0 : h.qual_off + 1u;
         const bool in_stage = hdr_ok && needed <= avail;
         Plan pl = plan_head<DO_PSS, DO_KMER>(P, src, h, RefsLdsCached{refs_lds, P.ref_info, n_ref_cached, (uint32_t)P.n_ref});
         if (!in_stage) { pl.status = RS_LIVE; pl.live = pl.pss_cand = pl.fk5 = pl.fk3 = false; }
@@ -452,13 +485,14 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         if constexpr (GROUPED) {
             // the read's plane slot for COLUMNS; n_slots = not in this launch (its codes go to the trash plane)
             if (in_tile && e == 0u) {
-                const uint32_t slot = cand ? read_group_plane(src, h, *gk) - gk->plane0 : gk->n_slots;
+                const uint32_t slot = cand ? record_plane<PLANES>(src, h, pl, gk, bk) - gk->plane0 : gk->n_slots;
                 grp_lds[j] = slot < gk->n_slots ? slot : gk->n_slots;
             }
         }
         uint32_t ev_over = 0u;  // events of a record handled by the out-of-line path
         if (in_tile && !in_stage && e == 0u) {
-            if constexpr (GROUPED) ev_over = tally_overflow_record_grouped(kernarg, gk, o0, o1, table);
+            if constexpr (PLANES == PLANES_RG) ev_over = tally_overflow_record_grouped(kernarg, gk, o0, o1, table);
+            else if constexpr (PLANES == PLANES_LEN) ev_over = tally_overflow_record_lenbins(kernarg, gk, bk, o0, o1, table);
             else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER>(kernarg, o0, o1, table, lds_kmer);
             if (pass0) atomicAdd(&lds_delta[ST_SLOW_PATH], 1);
         }
@@ -1210,7 +1244,7 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled_grouped(const Tally
     const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
     const GroupParams *gk = (const GroupParams *)((const uint8_t *)kernarg + GROUP_KERNARG_OFFSET);
     uint32_t *table = (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces));
-    tally_tiled_body<true, false, false, LATER_PASS, true>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta, refs_lds,
+    tally_tiled_body<true, false, false, LATER_PASS, PLANES_RG>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta, refs_lds,
                                                            gk, grp_lds);
 }
 // dynamic LDS a grouped launch may take: the CU's 160 KiB less the kernel's static objects (~10.6 KiB) and some margin
@@ -1266,6 +1300,56 @@ __global__ void __launch_bounds__(256) tally_simple_grouped(const TallyParams P,
             const uint32_t plane = read_group_plane(src, h, G);
             unsigned long long *base = P.counters + (plane ? G.off_groups + (plane - 1u) * G.plane_words : 0u);
             tally_pss_record(P, GlobalTable{base, P.off_rev}, src, h, pl);
+        }
+        book_events(true, false, record_events(true, false, pl, false), lds_delta);
+    }
+    __syncthreads();
+    flush_events(true, false, P, lds_delta);
+}
+
+// ---------------------------------------------------------------------------------------
+// -S: one set of substitution tables per fragment-length bin, in one pass over the records
+// ---------------------------------------------------------------------------------------
+// Third kernel argument, behind the GroupParams (n_groups = bins; ids / hash unused), which
+// reduce_partials_grouped reads as it does for -G.
+constexpr size_t LENBIN_KERNARG_OFFSET =
+    (GROUP_KERNARG_OFFSET + sizeof(GroupParams) + alignof(LenBinParams) - 1) & ~(alignof(LenBinParams) - 1);
+
+// tally_tiled_grouped with the plane taken from the read's length bin: the LDS layout, plane
+// passes and row passes are the grouped kernel's, but only record prefixes through QUAL[0] are
+// staged (whole records with -R only).  Substitution tables only.
+template <bool LATER_PASS>
+__global__ void __launch_bounds__(TILED_THREADS) tally_tiled_lenbins(const TallyParams P, const GroupParams G, const LenBinParams B) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
+    __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
+    __shared__ uint32_t toffs[2u * (TILED_MAX_T + 4u)];
+    __shared__ uint32_t grp_lds[TILED_MAX_T];
+    __shared__ uint32_t lds_kmer[1];
+    __shared__ int32_t lds_delta[ST_USED];
+    __shared__ uint4 refs_lds[REF_LDS_ENTRIES + 1];
+    const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
+    const GroupParams *gk = (const GroupParams *)((const uint8_t *)kernarg + GROUP_KERNARG_OFFSET);
+    const LenBinParams *bk = (const LenBinParams *)((const uint8_t *)kernarg + LENBIN_KERNARG_OFFSET);
+    uint32_t *table = (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces));
+    tally_tiled_body<true, false, false, LATER_PASS, PLANES_LEN>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta, refs_lds,
+                                                                 gk, grp_lds, bk);
+}
+
+// tally_simple with every record's counts in its length bin's plane (global atomics; the
+// cross-check of tally_tiled_lenbins).  Substitution tables only.
+__global__ void __launch_bounds__(256) tally_simple_lenbins(const TallyParams P, const GroupParams G, const LenBinParams B) {
+    __shared__ int32_t lds_delta[ST_USED];
+    if (threadIdx.x < ST_USED) lds_delta[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < P.n_recs; r += stride) {
+        const uint32_t o0 = P.offs[r], o1 = P.offs[r + 1];
+        GlobalBytes src{P.recs + o0};
+        const RecHdr h = decode_hdr(src, o1 - o0);
+        const Plan pl = make_plan<true, false>(P, src, h);
+        if (pl.pss_fwd || pl.pss_rev) {
+            const uint32_t plane = length_bin_plane(B, pl.L);
+            tally_pss_record(P, GlobalTable{P.counters + G.off_groups + (plane - 1u) * G.plane_words, P.off_rev}, src, h, pl);
         }
         book_events(true, false, record_events(true, false, pl, false), lds_delta);
     }

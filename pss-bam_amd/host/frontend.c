@@ -29,6 +29,8 @@
 
 int frontend_fast_exit = 0;
 int frontend_group_by_rg = 0;
+int frontend_n_length_edges = 0;
+uint32_t frontend_length_edges[PSSBAM_MAX_LENGTH_BINS - 1];
 
 /* Start-up work that overlaps the caller's FASTA load.  The reference is serial by construction -- load the
  * genome, then loop over the alignments (pss-bam.c:751-783) -- but only the TALLY needs reference bases: a helper
@@ -51,6 +53,8 @@ static struct early_feed {
     pssbam_engine *eng[64];
     char **rg_ids;                  /* -G: the BAM header's @RG IDs, set on every engine after create */
     int n_rg;
+    int n_edges;                    /* -S: the length bin edges, set on every engine after create */
+    uint32_t edges[PSSBAM_MAX_LENGTH_BINS - 1];
     int n_gpus, engines_ok, engines_done, fed, feed_rc, genome_set, failed;
     device_feed_stats dfs;
     char err[600];
@@ -124,7 +128,8 @@ static void *engine_make_main(void *arg)
 {
     engine_make_job *j = (engine_make_job *)arg;
     if (pssbam_engine_create(&j->cfg, j->out) || pssbam_engine_feed_open(*j->out, j->n_ref, EF.fasta_bytes) ||
-        (EF.n_rg > 0 && pssbam_engine_set_read_groups(*j->out, EF.n_rg, (const char *const *)EF.rg_ids))) {
+        (EF.n_rg > 0 && pssbam_engine_set_read_groups(*j->out, EF.n_rg, (const char *const *)EF.rg_ids)) ||
+        (EF.n_edges > 0 && pssbam_engine_set_length_bins(*j->out, EF.n_edges, EF.edges))) {
         j->rc = 1;
         snprintf(j->err, sizeof j->err, "%s", pssbam_last_error());   /* (the message is this thread's) */
     }
@@ -248,6 +253,8 @@ void frontend_warmup_start(const pssbam_config *cfg, const char *aln_path, const
         if (early_rd && early_light && cfg && !getenv("PSSBAM_NO_EARLY_FEED")) {
             EF.want = 1;
             EF.cfg = *cfg;
+            EF.n_edges = frontend_n_length_edges;
+            memcpy(EF.edges, frontend_length_edges, sizeof EF.edges);
             EF.cfg.pss.up_ctx = EF.up = dup_or_null(cfg->pss.up_ctx);
             EF.cfg.pss.down_ctx = EF.down = dup_or_null(cfg->pss.down_ctx);
             EF.cfg.read_group = EF.rg = dup_or_null(cfg->read_group);
@@ -260,6 +267,13 @@ void frontend_warmup_start(const pssbam_config *cfg, const char *aln_path, const
 }
 
 static int same_str(const char *a, const char *b) { return (!a && !b) || (a && b && strcmp(a, b) == 0); }
+
+/* the helper's engines carry the length bins that were set when it started */
+static int same_length_bins(void)
+{
+    return EF.n_edges == frontend_n_length_edges &&
+           memcmp(EF.edges, frontend_length_edges, (size_t)frontend_n_length_edges * sizeof *EF.edges) == 0;
+}
 
 static int same_config(const pssbam_config *a, const pssbam_config *b)
 {
@@ -389,6 +403,8 @@ void run_result_free(run_result *res)
     pss_free_read_groups(res->group_ids, res->n_groups);
     free(res->group_fwd);
     free(res->group_rev);
+    free(res->bin_fwd);
+    free(res->bin_rev);
     free(res->fwd);
     free(res->rev);
     free(res->k5);
@@ -441,7 +457,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
     int fed_on_device = 0, adopted = 0, light = 0;
     int device_feed = is_bam && device_feed_enabled() && cfg->kernel != PSSBAM_KERNEL_SIMPLE;
     if (warmup_running) { /* HIP is needed from here on; the helper thread may be feeding already */
-        const int mine = EF.want && is_bam && strcmp(early_path, aln_path) == 0 && same_config(cfg, &EF.cfg) && device_feed;
+        const int mine = EF.want && is_bam && strcmp(early_path, aln_path) == 0 && same_config(cfg, &EF.cfg) && same_length_bins() && device_feed;
         if (EF.want) {
             int upload_ok = 0;
             if (mine) { /* the engines exist a few dozen ms after the runtime is up: normally long before the FASTA is in */
@@ -541,7 +557,8 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             pssbam_config c = *cfg;
             const int have = pssbam_device_count();
             c.device = have > 0 ? g % have : g;
-            if (pssbam_engine_create(&c, &eng[g])) {
+            if (pssbam_engine_create(&c, &eng[g]) ||
+                (frontend_n_length_edges > 0 && pssbam_engine_set_length_bins(eng[g], frontend_n_length_edges, frontend_length_edges))) {
                 fprintf(stderr, "Error: GPU engine %d: %s\n", g, pssbam_last_error());
                 goto done;
             }
@@ -725,6 +742,18 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
         if (!res->group_fwd || !res->group_rev) { fprintf(stderr, "Error: out of memory\n"); goto done; }
         for (int k = 0; k < res->n_groups; k++)
             if (pssbam_engine_finish_groups(eng[0], k, res->group_fwd + k * cells, res->group_rev + k * cells)) {
+                fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+                goto done;
+            }
+    }
+    if (frontend_n_length_edges > 0) {
+        const size_t cells = (size_t)(cfg->pss.region_len + 2) * 16;
+        res->n_bins = frontend_n_length_edges + 1;
+        res->bin_fwd = (unsigned long *)calloc(cells * (size_t)res->n_bins, sizeof(unsigned long));
+        res->bin_rev = (unsigned long *)calloc(cells * (size_t)res->n_bins, sizeof(unsigned long));
+        if (!res->bin_fwd || !res->bin_rev) { fprintf(stderr, "Error: out of memory\n"); goto done; }
+        for (int k = 0; k < res->n_bins; k++)
+            if (pssbam_engine_finish_groups(eng[0], k, res->bin_fwd + k * cells, res->bin_rev + k * cells)) {
                 fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
                 goto done;
             }

@@ -18,11 +18,21 @@ typedef struct run_result {
     int n_groups;
     char **group_ids;
     unsigned long *group_fwd, *group_rev;
+    /* pss-bam -S (frontend_length_edges): each length bin's tables, (region_len+2)*16 per bin, bin k = group k of
+     * the engine */
+    int n_bins;
+    unsigned long *bin_fwd, *bin_rev;
 } run_result;
 
 /* pss-bam -G: every engine gets the input header's @RG IDs (pssbam_engine_set_read_groups) and run_tally()
  * returns one pair of tables per ID beside the totals.  Set before frontend_warmup_start. */
 extern int frontend_group_by_rg;
+
+/* pss-bam -S: the edges of the length bins (frontend_n_length_edges = 0: none); every engine gets them
+ * (pssbam_engine_set_length_bins) and run_tally() returns one pair of tables per bin.  Set before
+ * frontend_warmup_start. */
+extern int frontend_n_length_edges;
+extern uint32_t frontend_length_edges[PSSBAM_MAX_LENGTH_BINS - 1];
 
 /* Streams every alignment of `aln_path` (BGZF BAM, or SAM text plain/gzip) through engines built from `cfg` on
  * n_gpus devices (batches dealt round-robin), sums the counter blocks onto device 0 with

@@ -10,6 +10,9 @@
  * Added: -G writes, beside the tables of all reads, one pair of tables per @RG ID of the header
  * (<prefix>.<ID>.pss.*.txt, the ID file-name encoded: read_groups.h), each the same as `-R <ID>`
  * would write -- from one pass over the input instead of one run per read group.
+ * Added: -S e1,...,ek writes, beside the tables of all reads, one pair of tables per fragment-length bin
+ * [l, e1-1], [e1, e2-1], ..., [ek, L] (<prefix>.len<lo>-<hi>.pss.*.txt), each the same as
+ * `-l <lo> -L <hi> -o <prefix>.len<lo>-<hi>` would write -- again from one pass over the input.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -22,6 +25,7 @@
 
 #include "fasta-genome-io.h"
 #include "frontend.h"
+#include "length_bins.h"
 #include "read_groups.h"
 #include "report.h"
 
@@ -34,8 +38,9 @@ int main(int argc, char *argv[])
     unsigned long min_read_len = 0, max_read_len = 250000000;
     const char *up_ctx = "ACGT", *down_ctx = "ACGT";
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL, *read_group = NULL;
+    const char *len_edges = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mG")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -48,6 +53,7 @@ int main(int argc, char *argv[])
         case 'D': down_ctx = optarg; break;
         case 'm': merged_only = 1; break;
         case 'G': by_group = 1; break;
+        case 'S': len_edges = optarg; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -88,12 +94,27 @@ int main(int argc, char *argv[])
         fprintf(stderr, "-G (tables per read group) and -R (one read group) exclude each other.\n");
         exit(1);
     }
+    uint32_t edges[PSSBAM_MAX_LENGTH_BINS - 1];
+    int n_edges = 0;
+    if (len_edges) {
+        if (by_group) {
+            fprintf(stderr, "-S (tables per length bin) and -G (tables per read group) exclude each other.\n");
+            exit(1);
+        }
+        char err[200];
+        if ((n_edges = pss_parse_length_edges(len_edges, min_read_len, max_read_len, edges, err, sizeof err)) < 0) {
+            fprintf(stderr, "%s\n", err);
+            exit(1);
+        }
+    }
 
     /* "Full command" banner: four shapes, as the reference prints them (pss-bam.c:728-749) */
     fprintf(stderr, "Full command: %s -F %s -B %s -o %s -r %d -l %lu -L %lu -q %d", argv[0], fasta_fn, bam_fn,
             out_prefix, region_len, min_read_len, max_read_len, min_mq);
     if (read_group) fprintf(stderr, " -R %s", read_group);
-    fprintf(stderr, " -U %s -D %s%s%s\n", up_ctx, down_ctx, merged_only ? " -m" : "", by_group ? " -G" : "");
+    fprintf(stderr, " -U %s -D %s%s%s", up_ctx, down_ctx, merged_only ? " -m" : "", by_group ? " -G" : "");
+    if (len_edges) fprintf(stderr, " -S %s", len_edges);
+    fputc('\n', stderr);
 
     pssbam_config cfg;
     memset(&cfg, 0, sizeof cfg);
@@ -111,6 +132,8 @@ int main(int argc, char *argv[])
     cfg.kernel = PSSBAM_KERNEL_AUTO;
 
     frontend_group_by_rg = by_group;
+    frontend_n_length_edges = n_edges;
+    memcpy(frontend_length_edges, edges, (size_t)n_edges * sizeof *edges);
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
      * load; only the tally launches wait for the genome (frontend.c) */
@@ -149,6 +172,22 @@ int main(int argc, char *argv[])
         pss_write_counts(fasta_fn, bam_fn, gprefix, region_len, res.group_fwd + k * cells, res.group_rev + k * cells);
         pss_write_rates(fasta_fn, bam_fn, gprefix, region_len, fwd_rates, rev_rates);
         free(gprefix);
+    }
+    for (int k = 0; k < res.n_bins; k++) { /* <prefix>.len<lo>-<hi>: what `-l <lo> -L <hi> -o <prefix>.len<lo>-<hi>` writes */
+        const size_t cells = (size_t)(region_len + 2) * 16;
+        unsigned long lo, hi;
+        pss_length_bin_bounds(edges, n_edges, k, min_read_len, max_read_len, &lo, &hi);
+        const size_t tag_len = pss_length_bin_tag(lo, hi, NULL, 0);
+        char *bprefix = (char *)malloc(strlen(out_prefix) + tag_len + 2);
+        if (!bprefix) { fprintf(stderr, "Error: out of memory\n"); exit(1); }
+        strcpy(bprefix, out_prefix);
+        strcat(bprefix, ".");
+        pss_length_bin_tag(lo, hi, bprefix + strlen(bprefix), tag_len + 1);
+        pss_sub_rates(region_len, res.bin_fwd + k * cells, fwd_rates);
+        pss_sub_rates(region_len, res.bin_rev + k * cells, rev_rates);
+        pss_write_counts(fasta_fn, bam_fn, bprefix, region_len, res.bin_fwd + k * cells, res.bin_rev + k * cells);
+        pss_write_rates(fasta_fn, bam_fn, bprefix, region_len, fwd_rates, rev_rates);
+        free(bprefix);
     }
 
     if (getenv("PSSBAM_STATS")) {
