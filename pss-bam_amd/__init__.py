@@ -234,23 +234,21 @@ class Engine:
 
     def finish_groups(self) -> dict:
         """{ID: Tables, ..., None: Tables of the unassigned bucket} (fwd / rev only; drains like finish)"""
+        return self._finish_planes([(-1, None)] + list(enumerate(self.read_groups)))
+
+    def finish_bins(self) -> dict:
+        """{(lo, hi): Tables} per length bin (fwd / rev only; drains like finish)"""
+        return self._finish_planes(enumerate(self.length_bins))
+
+    def _finish_planes(self, planes) -> dict:
+        """{key: Tables} for (plane, key) pairs of pssbam_engine_finish_groups; a repeated key keeps its first plane"""
         out = {}
-        for g, key in [(-1, None)] + list(enumerate(self.read_groups)):
+        for g, key in planes:
             fwd = np.zeros((self.region_len + 2, 16), dtype=np.uint64)
             rev = np.zeros_like(fwd)
             _chk(self._L.pssbam_engine_finish_groups(self._h, g, fwd.ctypes.data, rev.ctypes.data))
             if key not in out:   # a repeated ID: its first index holds the counts
                 out[key] = Tables(fwd, rev, None, None, {})
-        return out
-
-    def finish_bins(self) -> dict:
-        """{(lo, hi): Tables} per length bin (fwd / rev only; drains like finish)"""
-        out = {}
-        for k, key in enumerate(self.length_bins):
-            fwd = np.zeros((self.region_len + 2, 16), dtype=np.uint64)
-            rev = np.zeros_like(fwd)
-            _chk(self._L.pssbam_engine_finish_groups(self._h, k, fwd.ctypes.data, rev.ctypes.data))
-            out[key] = Tables(fwd, rev, None, None, {})
         return out
 
     def close(self):

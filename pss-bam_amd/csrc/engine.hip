@@ -153,6 +153,15 @@ void pin_release(const void *p) {
 }
 }  // namespace
 
+// tiled_grid's memo slots: one per kernel instantiation launch_tally launches with dynamic LDS
+enum PrepSlot {
+    PREP_TILED_PSS, PREP_TILED_PSS_LATER, PREP_TILED_PSS_KMER, PREP_TILED_PSS_KMER_LDS, PREP_TILED_KMER, PREP_TILED_KMER_LDS,
+    PREP_COMPACT, PREP_COMPACT_KMER, PREP_COMPACT_KMER_LDS,
+    PREP_COMPACT_ONCE, PREP_COMPACT_ONCE_KMER, PREP_COMPACT_ONCE_KMER_LDS, PREP_COMPACT_DECODE_TWICE,
+    PREP_PLANES_RG, PREP_PLANES_RG_LATER, PREP_PLANES_LEN, PREP_PLANES_LEN_LATER,
+    PREP_N
+};
+
 struct pssbam_engine {
     pssbam_config cfg{};
     std::string up_ctx, down_ctx, rg;
@@ -195,13 +204,14 @@ struct pssbam_engine {
     bool have_refs = false;
     // -R
     uint8_t *d_rg = nullptr;
-    // -G (pssbam_engine_set_read_groups): plane 1 + g of the counter block holds ID g
-    std::vector<std::string> groups;
-    uint8_t *d_grp_ids = nullptr;
+    // -G / -S: n_planes [fwd | rev] planes of the counter block behind the stats (set_planes); plane 1 + g holds
+    // read group g (pssbam_engine_set_read_groups) or length bin g (pssbam_engine_set_length_bins)
+    PlaneSel planes = PLANES_NONE;
+    uint32_t n_planes = 0, off_groups = 0, plane_words = 0;
+    uint8_t *d_grp_ids = nullptr;   // -G: the ID table
     uint32_t *d_grp_offs = nullptr, *d_grp_hash = nullptr;
-    uint32_t grp_hash_mask = 0, off_groups = 0, plane_words = 0;
-    // -S (pssbam_engine_set_length_bins): plane 1 + k of the counter block holds length bin k
-    std::vector<uint32_t> len_edges;
+    uint32_t grp_hash_mask = 0;
+    std::vector<uint32_t> len_edges;   // -S
     bool tallied = false;   // a tally launch since create / reset
     // counters
     unsigned long long *d_counters = nullptr;      // block in use (own or caller-bound)
@@ -253,8 +263,8 @@ struct pssbam_engine {
     int env_group_slots = 0;   // PSSBAM_GROUP_SLOTS: at most this many planes per -G launch (tests: plane passes with few groups)
     bool warned_ablate = false;
     bool compact_plan_once = false;   // tally_compact: header decode + filters once per read, plan through LDS (PSSBAM_COMPACT_PLAN_ONCE)
-    uint32_t prep_lds[32] = {0};    // prep_kernel's memo, by kernel variant
-    int prep_occ[32] = {0};
+    uint32_t prep_lds[PREP_N] = {0};   // tiled_grid's memo, by kernel
+    int prep_occ[PREP_N] = {0};
     bool use_compact = true;        // -r N <= 16: tally_compact (PSSBAM_COMPACT=0 keeps tally_tiled, for A/B runs)
     uint32_t *d_scratch = nullptr;  // per-workgroup partial tables of the tiled kernel
     size_t scratch_slots = 0;
@@ -701,19 +711,58 @@ static int resolve_launch_events(pssbam_engine *e) {
     return PSSBAM_OK;
 }
 
-// dynamic-LDS limit + occupancy of one kernel variant, remembered per (variant, LDS size) so
-// the steady state makes no runtime API calls per launch beyond the launches themselves
+// Grid of one launch of a tiled-family kernel over n_tiles tiles: n_cu x occupancy x PSSBAM_GRID_MULT workgroups
+// (PSSBAM_GRID_WGS: that many), at most one per tile; d_scratch grows to `words` per workgroup.  The kernel's
+// dynamic-LDS limit and occupancy are remembered per (slot, LDS size), so the steady state makes no runtime API calls
+// per launch beyond the launches themselves.
 template <class K>
-static int prep_kernel(pssbam_engine *e, int variant, K kernel, uint32_t lds_bytes, int *occ) {
-    if (e->prep_lds[variant] == lds_bytes && e->prep_occ[variant] > 0) {
-        *occ = e->prep_occ[variant];
-        return PSSBAM_OK;
+static int tiled_grid(pssbam_engine *e, PrepSlot slot, K kernel, uint32_t lds, uint32_t n_tiles, uint32_t words, uint32_t *grid) {
+    if (e->prep_lds[slot] != lds || e->prep_occ[slot] < 1) {
+        int occ = 0;
+        HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, TILED_THREADS, lds));
+        if (occ < 1) return fail(PSSBAM_EHIP, "kernel does not fit a CU with %u bytes of LDS", lds);
+        e->prep_lds[slot] = lds;
+        e->prep_occ[slot] = occ;
     }
-    HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, kernel, TILED_THREADS, lds_bytes));
-    if (*occ < 1) return fail(PSSBAM_EHIP, "kernel does not fit a CU with %u bytes of LDS", lds_bytes);
-    e->prep_lds[variant] = lds_bytes;
-    e->prep_occ[variant] = *occ;
+    const int mult = e->env_grid_mult > 0 ? e->env_grid_mult : 1;
+    *grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)e->n_cu * e->prep_occ[slot] * mult);
+    if (e->env_grid_wgs > 0) *grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)e->env_grid_wgs);
+    const size_t need_slots = ((size_t)*grid * words + SCRATCH_WORDS - 1) / SCRATCH_WORDS;
+    if (e->scratch_slots < need_slots) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        if (e->d_scratch) HIP_TRY(hipFree(e->d_scratch));
+        e->d_scratch = nullptr;
+        e->scratch_slots = need_slots;
+        HIP_TRY(hipMalloc(&e->d_scratch, e->scratch_slots * SCRATCH_WORDS * sizeof(uint32_t)));
+    }
+    return PSSBAM_OK;
+}
+
+// One launch of a kernel with a single table plane (tally_tiled, tally_compact*) and its reduce_partials
+template <class K>
+static int launch_flat(pssbam_engine *e, PrepSlot slot, K kernel, TallyParams &P, uint32_t lds, uint32_t n_tiles, bool lds_kmer) {
+    uint32_t grid = 0;
+    const int rc = tiled_grid(e, slot, kernel, lds, n_tiles, SCRATCH_WORDS, &grid);
+    if (rc != PSSBAM_OK) return rc;
+    P.scratch = e->d_scratch;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(TILED_THREADS), lds, e->stream, P);
+    hipLaunchKernelGGL(reduce_partials, dim3((SCRATCH_WORDS * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream, P, grid,
+                       (uint32_t)(lds_kmer ? 1 : 0));
+    return PSSBAM_OK;
+}
+
+// One (row pass, plane pass) launch of tally_tiled_planes and its reduce_partials_grouped
+template <PlaneSel SEL, bool LATER>
+static int launch_planes(pssbam_engine *e, TallyParams &P, const PlaneParams &G, uint32_t lds, uint32_t n_tiles) {
+    constexpr PrepSlot slot = SEL == PLANES_RG ? (LATER ? PREP_PLANES_RG_LATER : PREP_PLANES_RG)
+                                               : (LATER ? PREP_PLANES_LEN_LATER : PREP_PLANES_LEN);
+    uint32_t grid = 0;
+    const int rc = tiled_grid(e, slot, tally_tiled_planes<SEL, LATER>, lds, n_tiles, G.scratch_words, &grid);
+    if (rc != PSSBAM_OK) return rc;
+    P.scratch = e->d_scratch;
+    hipLaunchKernelGGL((tally_tiled_planes<SEL, LATER>), dim3(grid), dim3(TILED_THREADS), lds, e->stream, P, G);
+    hipLaunchKernelGGL(reduce_partials_grouped, dim3((G.scratch_words * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream, P, G, grid);
     return PSSBAM_OK;
 }
 
@@ -741,11 +790,22 @@ static uint64_t sample_prefix_need(const uint8_t *bytes, uint64_t nbytes, bool w
 }
 
 // -R and -G walk the aux fields, which sit behind QUAL: the tiled kernels stage whole records
-static bool whole_records(const pssbam_engine *e) { return e->has_rg || !e->groups.empty(); }
+static bool whole_records(const pssbam_engine *e) { return e->has_rg || e->planes == PLANES_RG; }
 
-// [fwd | rev] planes of the counter block behind the stats: one per read group (-G) or per length bin (-S)
-static uint32_t extra_planes(const pssbam_engine *e) {
-    return (uint32_t)e->groups.size() + (e->len_edges.empty() ? 0u : (uint32_t)e->len_edges.size() + 1u);
+// The plane kernels' argument for the engine's -G / -S state (plane0, n_slots and scratch_words are per launch)
+static PlaneParams plane_params(const pssbam_engine *e) {
+    PlaneParams G{};
+    G.ids = e->d_grp_ids;
+    G.id_offs = e->d_grp_offs;
+    G.hash = e->d_grp_hash;
+    G.hash_mask = e->grp_hash_mask;
+    G.n_groups = e->n_planes;
+    G.n_slots = e->n_planes + 1u;
+    G.plane_words = e->plane_words;
+    G.off_groups = e->off_groups;
+    G.n_edges = (uint32_t)e->len_edges.size();
+    std::copy(e->len_edges.begin(), e->len_edges.end(), G.edges);
+    return G;
 }
 
 static uint32_t pieces_for(uint64_t need_max) {
@@ -803,30 +863,7 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
     P.off_k5 = e->off_k5;
     P.off_k3 = e->off_k3;
     P.off_stats = e->off_stats;
-    const bool grouped = !e->groups.empty();
-    GroupParams G{};
-    if (grouped) {
-        G.ids = e->d_grp_ids;
-        G.id_offs = e->d_grp_offs;
-        G.hash = e->d_grp_hash;
-        G.hash_mask = e->grp_hash_mask;
-        G.n_groups = (uint32_t)e->groups.size();
-        G.plane0 = 0;
-        G.n_slots = G.n_groups + 1u;
-        G.plane_words = e->plane_words;
-        G.off_groups = e->off_groups;
-    }
-    const bool binned = !e->len_edges.empty();
-    LenBinParams B{};
-    if (binned) {   // the grouped kernels' plane bookkeeping, with bin k as group k
-        G.n_groups = extra_planes(e);
-        G.plane0 = 0;
-        G.n_slots = G.n_groups + 1u;
-        G.plane_words = e->plane_words;
-        G.off_groups = e->off_groups;
-        B.n_edges = (uint32_t)e->len_edges.size();
-        std::copy(e->len_edges.begin(), e->len_edges.end(), B.edges);
-    }
+    PlaneParams G = plane_params(e);
 
     int kernel = c.kernel;
     if (d_n_recs && kernel == PSSBAM_KERNEL_SIMPLE) return fail(PSSBAM_EINVAL, "device-indexed blocks need the tiled kernels");
@@ -849,8 +886,8 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         const bool lds_tab = do_pss && tab_bytes <= 60u * 1024u;
         uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n_records + 255) / 256, (uint64_t)e->n_cu * 8);
         if (e->env_simple_blocks > 0) blocks = (uint32_t)e->env_simple_blocks;
-        if (grouped) hipLaunchKernelGGL(tally_simple_grouped, dim3(blocks), dim3(256), 0, e->stream, P, G);
-        else if (binned) hipLaunchKernelGGL(tally_simple_lenbins, dim3(blocks), dim3(256), 0, e->stream, P, G, B);
+        if (e->planes == PLANES_RG) hipLaunchKernelGGL(tally_simple_planes<PLANES_RG>, dim3(blocks), dim3(256), 0, e->stream, P, G);
+        else if (e->planes == PLANES_LEN) hipLaunchKernelGGL(tally_simple_planes<PLANES_LEN>, dim3(blocks), dim3(256), 0, e->stream, P, G);
         else if (lds_tab) hipLaunchKernelGGL(tally_simple<true>, dim3(blocks), dim3(256), tab_bytes, e->stream, P);
         else hipLaunchKernelGGL(tally_simple<false>, dim3(blocks), dim3(256), 0, e->stream, P);
     } else {
@@ -909,58 +946,19 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         const bool kmer_lds = do_kmer && c.kmer.klen <= KMER_LDS_MAX_K;
         const uint32_t n_tiles = (n_records + T - 1) / T;
         const uint32_t lds = tiled_lds_bytes(T, pieces);
-        int occ = 0, rc = PSSBAM_OK;
-        const int mult = e->env_grid_mult > 0 ? e->env_grid_mult : 1;
-#define LAUNCH_TILED(PSS, KM, LK, LATER)                                                                  \
-    do {                                                                                           \
-        rc = prep_kernel(e, (LATER ? 8 : 0) | (PSS ? 4 : 0) | (KM ? 2 : 0) | (LK ? 1 : 0), tally_tiled<PSS, KM, LK, LATER>, lds, &occ); \
-        if (rc == PSSBAM_OK) {                                                                     \
-            uint32_t grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)e->n_cu * occ * mult); \
-            if (e->env_grid_wgs > 0) grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)e->env_grid_wgs); \
-            if (e->scratch_slots < grid) {                                                         \
-                HIP_TRY(hipStreamSynchronize(e->stream));                                          \
-                if (e->d_scratch) HIP_TRY(hipFree(e->d_scratch));                                  \
-                e->d_scratch = nullptr;                                                            \
-                e->scratch_slots = std::max<size_t>(grid, (size_t)e->n_cu * 8);                    \
-                HIP_TRY(hipMalloc(&e->d_scratch, e->scratch_slots * SCRATCH_WORDS * sizeof(uint32_t))); \
-            }                                                                                      \
-            P.scratch = e->d_scratch;                                                              \
-            hipLaunchKernelGGL((tally_tiled<PSS, KM, LK, LATER>), dim3(grid), dim3(TILED_THREADS), lds, e->stream, P); \
-            hipLaunchKernelGGL(reduce_partials, dim3((SCRATCH_WORDS * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream, P, grid, \
-                               (uint32_t)(LK ? 1 : 0));                                            \
-        }                                                                                          \
-    } while (0)
+        int rc = PSSBAM_OK;
         P.row_base = 0;
-        // -r N <= 16 (2 context rows + 16 positions): the short-window variant, one pass
-#define LAUNCH_COMPACT(KM, LK) do { if (e->compact_plan_once) LAUNCH_COMPACT_(KM, LK, true, 24); else LAUNCH_COMPACT_(KM, LK, false, 16); } while (0)
-#define LAUNCH_COMPACT_(KM, LK, ONCE, VAR)                                                           \
-    do {                                                                                           \
-        rc = prep_kernel(e, VAR | (KM ? 2 : 0) | (LK ? 1 : 0), tally_compact<KM, LK, ONCE>, lds, &occ); \
-        if (rc == PSSBAM_OK) {                                                                     \
-            uint32_t grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)e->n_cu * occ * mult); \
-            if (e->env_grid_wgs > 0) grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)e->env_grid_wgs); \
-            if (e->scratch_slots < grid) {                                                         \
-                HIP_TRY(hipStreamSynchronize(e->stream));                                          \
-                if (e->d_scratch) HIP_TRY(hipFree(e->d_scratch));                                  \
-                e->d_scratch = nullptr;                                                            \
-                e->scratch_slots = std::max<size_t>(grid, (size_t)e->n_cu * 8);                    \
-                HIP_TRY(hipMalloc(&e->d_scratch, e->scratch_slots * SCRATCH_WORDS * sizeof(uint32_t))); \
-            }                                                                                      \
-            P.scratch = e->d_scratch;                                                              \
-            hipLaunchKernelGGL((tally_compact<KM, LK, ONCE>), dim3(grid), dim3(TILED_THREADS), lds, e->stream, P); \
-            hipLaunchKernelGGL(reduce_partials, dim3((SCRATCH_WORDS * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream, P, grid, \
-                               (uint32_t)(LK ? 1 : 0));                                            \
-        }                                                                                          \
-    } while (0)
-        if (grouped || binned) {
+        if (e->planes != PLANES_NONE) {
             // -G / -S: every (32-row pass, plane pass) pair is one launch over the block.  A plane pass holds as
             // many planes as fit the LDS beside the staging buffer (8 planes = 32 KiB always do: one pass for
             // up to 7 groups or 6 bins -- plane 0 of -S stays empty but keeps its slot); more planes take more
             // passes, each re-reading the records.
+            using LaunchPlanes = int (*)(pssbam_engine *, TallyParams &, const PlaneParams &, uint32_t, uint32_t);
+            static constexpr LaunchPlanes launch_pass[2][2] = {{launch_planes<PLANES_RG, false>, launch_planes<PLANES_RG, true>},
+                                                               {launch_planes<PLANES_LEN, false>, launch_planes<PLANES_LEN, true>}};
             const uint32_t n_planes = G.n_groups + 1u;
-            const uint32_t stage_bytes = tiled_lds_bytes(T, pieces);
-            const uint32_t fit = stage_bytes + 2u * GROUP_PLANE_WORDS * 4u <= GROUPED_LDS_BUDGET
-                                     ? (GROUPED_LDS_BUDGET - stage_bytes) / (GROUP_PLANE_WORDS * 4u) - 1u : 1u;
+            const uint32_t fit = lds + 2u * GROUP_PLANE_WORDS * 4u <= GROUPED_LDS_BUDGET
+                                     ? (GROUPED_LDS_BUDGET - lds) / (GROUP_PLANE_WORDS * 4u) - 1u : 1u;
             uint32_t per_pass = std::min(n_planes, fit);
             if (e->env_group_slots > 0) per_pass = std::min(per_pass, (uint32_t)e->env_group_slots);
             for (uint32_t pass = 0; pass < n_passes && rc == PSSBAM_OK; pass++) {
@@ -969,57 +967,37 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                     G.plane0 = plane0;
                     G.n_slots = std::min(per_pass, n_planes - plane0);
                     G.scratch_words = GROUP_SCRATCH_DELTA + G.n_slots * GROUP_PLANE_WORDS;
-                    const uint32_t glds = tiled_grouped_lds_bytes(T, pieces, G.n_slots);
-                    const bool later = pass > 0;
-                    if (binned) rc = later ? prep_kernel(e, 31, tally_tiled_lenbins<true>, glds, &occ) : prep_kernel(e, 30, tally_tiled_lenbins<false>, glds, &occ);
-                    else rc = later ? prep_kernel(e, 29, tally_tiled_grouped<true>, glds, &occ) : prep_kernel(e, 28, tally_tiled_grouped<false>, glds, &occ);
-                    if (rc != PSSBAM_OK) break;
-                    uint32_t grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)e->n_cu * occ * mult);
-                    if (e->env_grid_wgs > 0) grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)e->env_grid_wgs);
-                    const size_t need_slots = ((size_t)grid * G.scratch_words + SCRATCH_WORDS - 1) / SCRATCH_WORDS;
-                    if (e->scratch_slots < need_slots) {
-                        HIP_TRY(hipStreamSynchronize(e->stream));
-                        if (e->d_scratch) HIP_TRY(hipFree(e->d_scratch));
-                        e->d_scratch = nullptr;
-                        e->scratch_slots = need_slots;
-                        HIP_TRY(hipMalloc(&e->d_scratch, e->scratch_slots * SCRATCH_WORDS * sizeof(uint32_t)));
-                    }
-                    P.scratch = e->d_scratch;
-                    if (binned && later) hipLaunchKernelGGL(tally_tiled_lenbins<true>, dim3(grid), dim3(TILED_THREADS), glds, e->stream, P, G, B);
-                    else if (binned) hipLaunchKernelGGL(tally_tiled_lenbins<false>, dim3(grid), dim3(TILED_THREADS), glds, e->stream, P, G, B);
-                    else if (later) hipLaunchKernelGGL(tally_tiled_grouped<true>, dim3(grid), dim3(TILED_THREADS), glds, e->stream, P, G);
-                    else hipLaunchKernelGGL(tally_tiled_grouped<false>, dim3(grid), dim3(TILED_THREADS), glds, e->stream, P, G);
-                    hipLaunchKernelGGL(reduce_partials_grouped, dim3((G.scratch_words * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream,
-                                       P, G, grid);
+                    rc = launch_pass[e->planes == PLANES_LEN][pass > 0](e, P, G, tiled_grouped_lds_bytes(T, pieces, G.n_slots), n_tiles);
                 }
             }
-        } else
-        if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg) {
-            if (!do_kmer && getenv("PSSBAM_COMPACT_DECODE_TWICE")) {   // diagnostics: what the shared header decode costs
-                rc = prep_kernel(e, 20, tally_compact_decode_twice, lds, &occ);
-                if (rc == PSSBAM_OK) {
-                    const uint32_t grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)e->n_cu * occ * mult);
-                    if (e->scratch_slots >= grid) {
-                        P.scratch = e->d_scratch;
-                        hipLaunchKernelGGL(tally_compact_decode_twice, dim3(grid), dim3(TILED_THREADS), lds, e->stream, P);
-                        hipLaunchKernelGGL(reduce_partials, dim3((SCRATCH_WORDS * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream, P, grid, 0u);
-                    } else rc = fail(PSSBAM_ESTATE, "scratch too small for the diagnostic kernel");
-                }
-            } else if (!do_kmer) LAUNCH_COMPACT(false, false);
-            else if (kmer_lds) LAUNCH_COMPACT(true, true);
-            else LAUNCH_COMPACT(true, false);
-        } else
-        if (do_pss && do_kmer) { if (kmer_lds) LAUNCH_TILED(true, true, true, false); else LAUNCH_TILED(true, true, false, false); }
-        else if (do_pss) LAUNCH_TILED(true, false, false, false);
-        else { if (kmer_lds) LAUNCH_TILED(false, true, true, false); else LAUNCH_TILED(false, true, false, false); }
-        // rows 32.. of a large -r: further passes over the same block, substitution rows only
-        // (the status counters and the k-mer tally belong to pass 0)
-        for (uint32_t pass = 1; pass < n_passes && rc == PSSBAM_OK && !grouped && !binned; pass++) {
-            P.row_base = pass * TILED_ROWS;
-            LAUNCH_TILED(true, false, false, true);
+        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg) {
+            // -r N <= 16 (2 context rows + 16 positions): the short-window variant, one pass
+            if (!do_kmer && getenv("PSSBAM_COMPACT_DECODE_TWICE"))   // diagnostics: what the shared header decode costs
+                rc = launch_flat(e, PREP_COMPACT_DECODE_TWICE, tally_compact_decode_twice, P, lds, n_tiles, false);
+            else if (e->compact_plan_once)
+                rc = !do_kmer  ? launch_flat(e, PREP_COMPACT_ONCE, tally_compact<false, false, true>, P, lds, n_tiles, false)
+                     : kmer_lds ? launch_flat(e, PREP_COMPACT_ONCE_KMER_LDS, tally_compact<true, true, true>, P, lds, n_tiles, true)
+                                : launch_flat(e, PREP_COMPACT_ONCE_KMER, tally_compact<true, false, true>, P, lds, n_tiles, false);
+            else
+                rc = !do_kmer  ? launch_flat(e, PREP_COMPACT, tally_compact<false, false, false>, P, lds, n_tiles, false)
+                     : kmer_lds ? launch_flat(e, PREP_COMPACT_KMER_LDS, tally_compact<true, true, false>, P, lds, n_tiles, true)
+                                : launch_flat(e, PREP_COMPACT_KMER, tally_compact<true, false, false>, P, lds, n_tiles, false);
+        } else {
+            if (do_pss && do_kmer)
+                rc = kmer_lds ? launch_flat(e, PREP_TILED_PSS_KMER_LDS, tally_tiled<true, true, true, false>, P, lds, n_tiles, true)
+                              : launch_flat(e, PREP_TILED_PSS_KMER, tally_tiled<true, true, false, false>, P, lds, n_tiles, false);
+            else if (do_pss)
+                rc = launch_flat(e, PREP_TILED_PSS, tally_tiled<true, false, false, false>, P, lds, n_tiles, false);
+            else
+                rc = kmer_lds ? launch_flat(e, PREP_TILED_KMER_LDS, tally_tiled<false, true, true, false>, P, lds, n_tiles, true)
+                              : launch_flat(e, PREP_TILED_KMER, tally_tiled<false, true, false, false>, P, lds, n_tiles, false);
+            // rows 32.. of a large -r: further passes over the same block, substitution rows only
+            // (the status counters and the k-mer tally belong to pass 0)
+            for (uint32_t pass = 1; pass < n_passes && rc == PSSBAM_OK; pass++) {
+                P.row_base = pass * TILED_ROWS;
+                rc = launch_flat(e, PREP_TILED_PSS_LATER, tally_tiled<true, false, false, true>, P, lds, n_tiles, false);
+            }
         }
-#undef LAUNCH_TILED
-#undef LAUNCH_COMPACT
         if (rc != PSSBAM_OK) return rc;
     }
     HIP_TRY(hipGetLastError());
@@ -1206,7 +1184,7 @@ extern "C" int pssbam_engine_finish(pssbam_engine *e, unsigned long *fwd, unsign
     static_assert(sizeof(unsigned long) == 8, "LP64 expected");
     const size_t tab = (size_t)e->rows * 16;
     // -G / -S: the totals are every plane's sum (plane 0, the unassigned bucket, sits where an ungrouped engine keeps its tables)
-    for (size_t g = 0; g < extra_planes(e); g++)
+    for (size_t g = 0; g < e->n_planes; g++)
         for (size_t i = 0; i < 2 * tab; i++) h[i] += h[e->off_groups + g * e->plane_words + i];
     if (fwd) for (size_t i = 0; i < tab; i++) fwd[i] = (unsigned long)h[i];
     if (rev) for (size_t i = 0; i < tab; i++) rev[i] = (unsigned long)h[e->off_rev + i];
@@ -1218,7 +1196,7 @@ extern "C" int pssbam_engine_finish(pssbam_engine *e, unsigned long *fwd, unsign
 
 extern "C" int pssbam_engine_finish_groups(pssbam_engine *e, int32_t group, unsigned long *fwd, unsigned long *rev) {
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
-    const int32_t n_planes = (int32_t)extra_planes(e);
+    const int32_t n_planes = (int32_t)e->n_planes;
     if (!n_planes) return fail(PSSBAM_ESTATE, "neither pssbam_engine_set_read_groups nor pssbam_engine_set_length_bins has been called");
     if (group < -1 || group >= n_planes) return fail(PSSBAM_EINVAL, "group %d outside -1..%d", group, n_planes - 1);
     int rc = pssbam_engine_sync(e);
@@ -1232,17 +1210,33 @@ extern "C" int pssbam_engine_finish_groups(pssbam_engine *e, int32_t group, unsi
     return PSSBAM_OK;
 }
 
+// What set_read_groups and set_length_bins share: the counter block grows to n_planes [fwd | rev] planes behind the stats,
+// zeroed (nothing has been counted yet).  The old block may still be named by work queued on the stream (the compressed
+// feed): it is retired, not freed.  `what` names the caller's planes in the messages.
+static int set_planes(pssbam_engine *e, PlaneSel sel, uint32_t n_planes, const char *what) {
+    if (e->cfg.tally_mask != PSSBAM_TALLY_PSS) return fail(PSSBAM_EINVAL, "%s split the substitution tables only (no PSSBAM_TALLY_KMER)", what);
+    if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set %s after create or reset, before the first tally", what);
+    if (e->d_counters != e->d_counters_own) return fail(PSSBAM_ESTATE, "a caller-bound counter block cannot grow: set %s before bind_counters", what);
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n_counters = (size_t)e->off_groups + (size_t)n_planes * e->plane_words;
+    unsigned long long *d_counters = nullptr;
+    HIP_TRY(hipMalloc(&d_counters, n_counters * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(d_counters, 0, n_counters * sizeof(unsigned long long), e->stream));
+    if (e->d_counters_own) e->retired.push_back(e->d_counters_own);
+    e->d_counters = e->d_counters_own = d_counters;
+    e->n_counters = n_counters;
+    e->planes = sel;
+    e->n_planes = n_planes;
+    return PSSBAM_OK;
+}
+
 extern "C" int pssbam_engine_set_read_groups(pssbam_engine *e, int32_t n, const char *const *ids) {
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
     if (n < 1 || n > PSSBAM_MAX_READ_GROUPS || !ids) return fail(PSSBAM_EINVAL, "read group count %d outside 1..%d", n, PSSBAM_MAX_READ_GROUPS);
     if (e->has_rg) return fail(PSSBAM_EINVAL, "read groups and a -R read group filter exclude each other");
-    if (!e->len_edges.empty()) return fail(PSSBAM_EINVAL, "read groups and length bins exclude each other");
-    if (e->cfg.tally_mask != PSSBAM_TALLY_PSS) return fail(PSSBAM_EINVAL, "read groups split the substitution tables only (no PSSBAM_TALLY_KMER)");
+    if (e->planes == PLANES_LEN) return fail(PSSBAM_EINVAL, "read groups and length bins exclude each other");
     for (int32_t i = 0; i < n; i++)
         if (!ids[i]) return fail(PSSBAM_EINVAL, "read group %d is NULL", i);
-    if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set read groups after create or reset, before the first tally");
-    if (e->d_counters != e->d_counters_own) return fail(PSSBAM_ESTATE, "a caller-bound counter block cannot grow: set read groups before bind_counters");
-    HIP_TRY(hipSetDevice(e->device));
     // ID table (concatenated) + open-addressing hash over it; a repeated ID keeps its first index
     std::vector<std::string> groups(ids, ids + n);
     std::string cat;
@@ -1263,29 +1257,27 @@ extern "C" int pssbam_engine_set_read_groups(pssbam_engine *e, int32_t n, const 
             if (groups[slot - 1u] == groups[g]) break;   // duplicate: the first one counts
         }
     }
-    // the counter block grows by one [fwd | rev] plane per group; nothing has been counted yet.  The old buffers may still
-    // be named by work queued on the stream (the compressed feed): they are retired, not freed.
-    const size_t n_counters = (size_t)e->off_groups + (size_t)n * e->plane_words;
-    unsigned long long *d_counters = nullptr;
+    // on the device before the counter block grows: the engine never sees planes without their ID table.  The old tables
+    // are retired, not freed, like the old counter block.
+    HIP_TRY(hipSetDevice(e->device));
     uint8_t *d_ids = nullptr;
     uint32_t *d_offs = nullptr, *d_hash = nullptr;
-    HIP_TRY(hipMalloc(&d_counters, n_counters * sizeof(unsigned long long)));
     HIP_TRY(hipMalloc(&d_ids, cat.size() + 16));
     HIP_TRY(hipMalloc(&d_offs, offs.size() * sizeof(uint32_t)));
     HIP_TRY(hipMalloc(&d_hash, hash.size() * sizeof(uint32_t)));
     HIP_TRY(hipMemcpy(d_ids, cat.data(), cat.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_offs, offs.data(), offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_hash, hash.data(), hash.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemsetAsync(d_counters, 0, n_counters * sizeof(unsigned long long), e->stream));
-    for (void *old : {(void *)e->d_counters_own, (void *)e->d_grp_ids, (void *)e->d_grp_offs, (void *)e->d_grp_hash})
+    if (const int rc = set_planes(e, PLANES_RG, (uint32_t)n, "read groups")) {
+        for (void *p : {(void *)d_ids, (void *)d_offs, (void *)d_hash}) (void)hipFree(p);
+        return rc;
+    }
+    for (void *old : {(void *)e->d_grp_ids, (void *)e->d_grp_offs, (void *)e->d_grp_hash})
         if (old) e->retired.push_back(old);
-    e->d_counters = e->d_counters_own = d_counters;
-    e->n_counters = n_counters;
     e->d_grp_ids = d_ids;
     e->d_grp_offs = d_offs;
     e->d_grp_hash = d_hash;
     e->grp_hash_mask = hsize - 1;
-    e->groups = std::move(groups);
     e->dev_pieces = 0;   // whole records are staged from now on: resampled at the next launch
     return PSSBAM_OK;
 }
@@ -1294,8 +1286,7 @@ extern "C" int pssbam_engine_set_length_bins(pssbam_engine *e, int32_t n_edges, 
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
     if (n_edges < 1 || n_edges > PSSBAM_MAX_LENGTH_BINS - 1 || !edges)
         return fail(PSSBAM_EINVAL, "length bin edge count %d outside 1..%d", n_edges, PSSBAM_MAX_LENGTH_BINS - 1);
-    if (!e->groups.empty()) return fail(PSSBAM_EINVAL, "length bins and read groups exclude each other");
-    if (e->cfg.tally_mask != PSSBAM_TALLY_PSS) return fail(PSSBAM_EINVAL, "length bins split the substitution tables only (no PSSBAM_TALLY_KMER)");
+    if (e->planes == PLANES_RG) return fail(PSSBAM_EINVAL, "length bins and read groups exclude each other");
     // l < e1 < ... < ek <= L: every bin [l, e1-1], [e1, e2-1], ..., [ek, L] is a non-empty -l / -L window
     const uint64_t lo = e->cfg.pss.min_read_len, hi = e->cfg.pss.max_read_len;
     for (int32_t i = 0; i < n_edges; i++) {
@@ -1304,17 +1295,8 @@ extern "C" int pssbam_engine_set_length_bins(pssbam_engine *e, int32_t n_edges, 
             return fail(PSSBAM_EINVAL, "length bin edge %d (%u) must lie above %llu and at most at %llu", i, edges[i],
                         (unsigned long long)prev, (unsigned long long)hi);
     }
-    if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set length bins after create or reset, before the first tally");
-    if (e->d_counters != e->d_counters_own) return fail(PSSBAM_ESTATE, "a caller-bound counter block cannot grow: set length bins before bind_counters");
-    HIP_TRY(hipSetDevice(e->device));
-    // the counter block grows by one [fwd | rev] plane per bin (as for read groups: old buffers are retired, not freed)
-    const size_t n_counters = (size_t)e->off_groups + (size_t)(n_edges + 1) * e->plane_words;
-    unsigned long long *d_counters = nullptr;
-    HIP_TRY(hipMalloc(&d_counters, n_counters * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(d_counters, 0, n_counters * sizeof(unsigned long long), e->stream));
-    if (e->d_counters_own) e->retired.push_back(e->d_counters_own);
-    e->d_counters = e->d_counters_own = d_counters;
-    e->n_counters = n_counters;
+    const int rc = set_planes(e, PLANES_LEN, (uint32_t)n_edges + 1u, "length bins");
+    if (rc) return rc;
     e->len_edges.assign(edges, edges + n_edges);
     return PSSBAM_OK;
 }

@@ -270,22 +270,27 @@ __device__ bool has_read_group(const Src &src, const RecHdr &h, const uint8_t *r
     return false;
 }
 
-// ---- read groups (-G) ------------------------------------------------------------------
-// The grouped kernels' second argument: the @RG ID table and where one launch's planes go.  A
-// plane is one [fwd | rev] pair of (N+2)*16 tables; plane 0 is the unassigned bucket (the
-// counter block's original fwd / rev), plane 1 + g is ID g, at off_groups + g * plane_words.
-struct GroupParams {
+// ---- table planes (-G, -S) --------------------------------------------------------------
+// The plane kernels' second argument: how a record's plane is picked and where one launch's planes
+// go.  A plane is one [fwd | rev] pair of (N+2)*16 tables; plane 0 is the unassigned bucket (the
+// counter block's original fwd / rev), plane 1 + g is group or bin g, at off_groups + g * plane_words.
+constexpr uint32_t MAX_LENGTH_EDGES = 63;   // PSSBAM_MAX_LENGTH_BINS - 1
+struct PlaneParams {
+    // -G: the @RG ID table
     const uint8_t *ids;        // the IDs back to back
     const uint32_t *id_offs;   // n_groups + 1 offsets into ids
     const uint32_t *hash;      // open addressing over FNV-1a of the ID: entry = group + 1, 0 = empty
     uint32_t hash_mask;        // entries - 1 (a power of two, at least twice n_groups)
-    uint32_t n_groups;
+    uint32_t n_groups;         // planes behind plane 0: read groups, or length bins
     uint32_t plane0, n_slots;  // this launch tallies planes plane0 .. plane0 + n_slots - 1
     uint32_t plane_words;      // 2 * (N+2) * 16
     uint32_t off_groups;       // first word of plane 1 in the counter block
-    uint32_t scratch_words;    // per-workgroup scratch of the grouped tiled kernel: [deltas 16 | n_slots x 1024]
+    uint32_t scratch_words;    // per-workgroup scratch of the tiled plane kernel: [deltas 16 | n_slots x 1024]
+    // -S: the length bin edges
+    uint32_t n_edges;                      // 1..MAX_LENGTH_EDGES, strictly increasing
+    uint32_t edges[MAX_LENGTH_EDGES];      // bin k (k >= 1) starts at edges[k-1]
 };
-constexpr uint32_t GROUP_SCRATCH_DELTA = 16;   // the deltas lead a grouped scratch slot
+constexpr uint32_t GROUP_SCRATCH_DELTA = 16;   // the deltas lead a plane kernel's scratch slot
 constexpr uint32_t GROUP_PLANE_WORDS = 1024;   // one [(cell << 1) | table][32 rows] plane in LDS / scratch
 
 __host__ __device__ __forceinline__ uint32_t fnv1a_step(uint32_t h, uint32_t c) { return (h ^ c) * 16777619u; }
@@ -295,7 +300,7 @@ constexpr uint32_t FNV1A_SEED = 2166136261u;
 // walk and its rules are has_read_group's (a malformed field or an unterminated string ends it
 // with "no RG"), so group g receives exactly the records `-R <ID g>` keeps.
 template <class Src>
-__device__ uint32_t read_group_plane(const Src &src, const RecHdr &h, const GroupParams &G) {
+__device__ uint32_t read_group_plane(const Src &src, const RecHdr &h, const PlaneParams &G) {
     uint32_t o = h.aux_off;
     const uint32_t end = h.rec_len;
     while (o + 3 <= end) {
@@ -349,18 +354,10 @@ __device__ uint32_t read_group_plane(const Src &src, const RecHdr &h, const Grou
     return 0u;
 }
 
-// ---- length bins (-S) ------------------------------------------------------------------
-// The length-binned kernels' third argument (their second is a GroupParams whose n_groups is the
-// bin count, ids / hash unused).  Bin k is plane 1 + k; plane 0 stays empty.
-constexpr uint32_t MAX_LENGTH_EDGES = 63;   // PSSBAM_MAX_LENGTH_BINS - 1
-struct LenBinParams {
-    uint32_t n_edges;                      // 1..MAX_LENGTH_EDGES, strictly increasing
-    uint32_t edges[MAX_LENGTH_EDGES];      // bin k (k >= 1) starts at edges[k-1]
-};
-
+// ---- length bins (-S): bin k is plane 1 + k; plane 0 stays empty ----------------------------
 // Plane of a candidate read of pss length L (Plan::L, what -l / -L compare): 1 + #{edges <= L}.
 // The edges are wave-uniform (kernarg): scalar loads, one compare and add per edge.
-__device__ __forceinline__ uint32_t length_bin_plane(const LenBinParams &B, uint32_t L) {
+__device__ __forceinline__ uint32_t length_bin_plane(const PlaneParams &B, uint32_t L) {
     uint32_t k = 1u;
     for (uint32_t i = 0; i < B.n_edges; i++) k += B.edges[i] <= L ? 1u : 0u;
     return k;

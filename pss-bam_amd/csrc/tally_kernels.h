@@ -36,11 +36,10 @@
 //                 Counters leave LDS once, at kernel end, as plain stores into the workgroup's
 //                 slot of a scratch buffer; reduce_partials sums the slots into the u64 block.
 //
-//  tally_tiled_grouped / tally_simple_grouped (-G): the same kernels with one table plane per read
-//                 group (record -> plane by its first RG:Z value, read_group_plane).
-//
-//  tally_tiled_lenbins / tally_simple_lenbins (-S): the same with one plane per fragment-length bin
-//                 (record -> plane by Plan::L, length_bin_plane); prefixes are staged as without planes.
+//  tally_tiled_planes / tally_simple_planes<PLANES> (-G, -S): the same kernels with one table plane
+//                 per read group (PLANES_RG: record -> plane by its first RG:Z value,
+//                 read_group_plane) or per fragment-length bin (PLANES_LEN: by Plan::L,
+//                 length_bin_plane; prefixes are staged as without planes).
 //
 // Integer/byte work only: no MFMA anywhere (the bound is HBM bandwidth).
 #pragma once
@@ -267,45 +266,30 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyP
     return record_events(DO_PSS, DO_KMER, gpl, kfail);
 }
 
-// The same for tally_tiled_grouped (substitution tables only): the record's plane slot of this
-// launch, if it has one, decides where its counts go.
-__device__ __attribute__((noinline)) uint32_t tally_overflow_record_grouped(const TallyParams *kernarg, const GroupParams *gk,
-                                                                            uint32_t o0, uint32_t o1, uint32_t *table) {
-    const TallyParams &P = *kernarg;
-    GlobalBytes gsrc{P.recs + o0};
-    const RecHdr gh = decode_hdr(gsrc, o1 - o0);
-    const Plan gpl = make_plan<true, false>(P, gsrc, gh);
-    if (gpl.pss_fwd || gpl.pss_rev) {
-        const uint32_t slot = read_group_plane(gsrc, gh, *gk) - gk->plane0;
-        if (slot < gk->n_slots) tally_pss_record(P, LdsTableColumnMajor{table + slot * GROUP_PLANE_WORDS, P.row_base}, gsrc, gh, gpl);
-    }
-    return record_events(true, false, gpl, false);
-}
-
-// The same for tally_tiled_lenbins: the plane of the record's length bin.
-__device__ __attribute__((noinline)) uint32_t tally_overflow_record_lenbins(const TallyParams *kernarg, const GroupParams *gk,
-                                                                            const LenBinParams *bk, uint32_t o0, uint32_t o1,
-                                                                            uint32_t *table) {
-    const TallyParams &P = *kernarg;
-    GlobalBytes gsrc{P.recs + o0};
-    const RecHdr gh = decode_hdr(gsrc, o1 - o0);
-    const Plan gpl = make_plan<true, false>(P, gsrc, gh);
-    if (gpl.pss_fwd || gpl.pss_rev) {
-        const uint32_t slot = length_bin_plane(*bk, gpl.L) - gk->plane0;
-        if (slot < gk->n_slots) tally_pss_record(P, LdsTableColumnMajor{table + slot * GROUP_PLANE_WORDS, P.row_base}, gsrc, gh, gpl);
-    }
-    return record_events(true, false, gpl, false);
-}
-
 // What picks a read's table plane in tally_tiled_body: nothing (one plane), its first RG:Z value
 // (-G), or its length bin (-S).
 enum PlaneSel { PLANES_NONE = 0, PLANES_RG, PLANES_LEN };
 
 template <PlaneSel PLANES, class Src>
-__device__ __forceinline__ uint32_t record_plane(const Src &src, const RecHdr &h, const Plan &pl, const GroupParams *gk,
-                                                 const LenBinParams *bk) {
-    if constexpr (PLANES == PLANES_RG) return read_group_plane(src, h, *gk);
-    else return length_bin_plane(*bk, pl.L);
+__device__ __forceinline__ uint32_t record_plane(const Src &src, const RecHdr &h, const Plan &pl, const PlaneParams &G) {
+    if constexpr (PLANES == PLANES_RG) return read_group_plane(src, h, G);
+    else return length_bin_plane(G, pl.L);
+}
+
+// The same for tally_tiled_planes (substitution tables only): the record's plane slot of this
+// launch, if it has one, decides where its counts go.
+template <PlaneSel PLANES>
+__device__ __attribute__((noinline)) uint32_t tally_overflow_record_planes(const TallyParams *kernarg, const PlaneParams *gk,
+                                                                           uint32_t o0, uint32_t o1, uint32_t *table) {
+    const TallyParams &P = *kernarg;
+    GlobalBytes gsrc{P.recs + o0};
+    const RecHdr gh = decode_hdr(gsrc, o1 - o0);
+    const Plan gpl = make_plan<true, false>(P, gsrc, gh);
+    if (gpl.pss_fwd || gpl.pss_rev) {
+        const uint32_t slot = record_plane<PLANES>(gsrc, gh, gpl, *gk) - gk->plane0;
+        if (slot < gk->n_slots) tally_pss_record(P, LdsTableColumnMajor{table + slot * GROUP_PLANE_WORDS, P.row_base}, gsrc, gh, gpl);
+    }
+    return record_events(true, false, gpl, false);
 }
 
 // Reference windows, one per alignment end, each with STATIC byte positions:
@@ -318,7 +302,7 @@ __device__ __forceinline__ uint32_t record_plane(const Src &src, const RecHdr &h
 // it every LDS access issued while a DMA transfer is in flight is fenced behind vmcnt(0) and
 // the transfer cannot overlap the COLUMNS pass.
 //
-// PLANES_RG / PLANES_LEN (-G tally_tiled_grouped, -S tally_tiled_lenbins): `table` holds gk->n_slots
+// PLANES_RG / PLANES_LEN (-G / -S, tally_tiled_planes): `table` holds gk->n_slots
 // planes of [(cell<<1)|table][row] plus one trash plane behind them; every read's plane slot is
 // resolved in CODES-A (record_plane: read_group_plane or length_bin_plane) and kept in grp_lds, and
 // COLUMNS adds the wave's scalar slot offset to each real code.
@@ -329,8 +313,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
                                                  uint32_t *__restrict__ toffs,
                                                  uint32_t *__restrict__ lds_kmer,
                                                  int32_t *__restrict__ lds_delta, uint4 *__restrict__ refs_lds,
-                                                 const GroupParams *gk = nullptr, uint32_t *__restrict__ grp_lds = nullptr,
-                                                 const LenBinParams *bk = nullptr) {
+                                                 const PlaneParams *gk = nullptr, uint32_t *__restrict__ grp_lds = nullptr) {
     constexpr bool GROUPED = PLANES != PLANES_NONE;   // one table plane per read group / length bin
     const uint32_t T = P.reads_per_tile;   // <= TILED_MAX_T
     const uint32_t n_recs = P.n_recs_dev ? *P.n_recs_dev : P.n_recs;   // device-indexed blocks: the count lives in device memory
@@ -485,14 +468,13 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         if constexpr (GROUPED) {
             // the read's plane slot for COLUMNS; n_slots = not in this launch (its codes go to the trash plane)
             if (in_tile && e == 0u) {
-                const uint32_t slot = cand ? record_plane<PLANES>(src, h, pl, gk, bk) - gk->plane0 : gk->n_slots;
+                const uint32_t slot = cand ? record_plane<PLANES>(src, h, pl, *gk) - gk->plane0 : gk->n_slots;
                 grp_lds[j] = slot < gk->n_slots ? slot : gk->n_slots;
             }
         }
         uint32_t ev_over = 0u;  // events of a record handled by the out-of-line path
         if (in_tile && !in_stage && e == 0u) {
-            if constexpr (PLANES == PLANES_RG) ev_over = tally_overflow_record_grouped(kernarg, gk, o0, o1, table);
-            else if constexpr (PLANES == PLANES_LEN) ev_over = tally_overflow_record_lenbins(kernarg, gk, bk, o0, o1, table);
+            if constexpr (GROUPED) ev_over = tally_overflow_record_planes<PLANES>(kernarg, gk, o0, o1, table);
             else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER>(kernarg, o0, o1, table, lds_kmer);
             if (pass0) atomicAdd(&lds_delta[ST_SLOW_PATH], 1);
         }
@@ -1223,17 +1205,20 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P
 }
 
 // ---------------------------------------------------------------------------------------
-// -G: one set of substitution tables per read group, in one pass over the records
+// -G / -S: one set of substitution tables per read group or per fragment-length bin, in one pass
+// over the records
 // ---------------------------------------------------------------------------------------
-// The grouped kernels take the group table as a second argument; it sits in the kernarg segment
+// The plane kernels take their PlaneParams as a second argument; it sits in the kernarg segment
 // right behind TallyParams (HIP lays kernel arguments out in order at their natural alignment).
-constexpr size_t GROUP_KERNARG_OFFSET = (sizeof(TallyParams) + alignof(GroupParams) - 1) & ~(alignof(GroupParams) - 1);
+constexpr size_t PLANE_KERNARG_OFFSET = (sizeof(TallyParams) + alignof(PlaneParams) - 1) & ~(alignof(PlaneParams) - 1);
 
-// tally_tiled with every record's counts in its group's plane.  Dynamic LDS: the staging buffer,
-// then (n_slots + 1) planes of 1024 words -- n_slots groups of this launch and the trash plane.
-// Whole records are staged (the RG tag sits behind QUAL).  Substitution tables only.
-template <bool LATER_PASS>
-__global__ void __launch_bounds__(TILED_THREADS) tally_tiled_grouped(const TallyParams P, const GroupParams G) {
+// tally_tiled with every record's counts in its plane (PLANES: by read group or by length bin).
+// Dynamic LDS: the staging buffer, then (n_slots + 1) planes of 1024 words -- n_slots planes of
+// this launch and the trash plane.  -G stages whole records (the RG tag sits behind QUAL); -S
+// stages prefixes through QUAL[0] as tally_tiled does (whole records with -R only).  Substitution
+// tables only.
+template <PlaneSel PLANES, bool LATER_PASS>
+__global__ void __launch_bounds__(TILED_THREADS) tally_tiled_planes(const TallyParams P, const PlaneParams G) {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
     __shared__ uint32_t toffs[2u * (TILED_MAX_T + 4u)];
@@ -1242,21 +1227,21 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled_grouped(const Tally
     __shared__ int32_t lds_delta[ST_USED];
     __shared__ uint4 refs_lds[REF_LDS_ENTRIES + 1];
     const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
-    const GroupParams *gk = (const GroupParams *)((const uint8_t *)kernarg + GROUP_KERNARG_OFFSET);
+    const PlaneParams *gk = (const PlaneParams *)((const uint8_t *)kernarg + PLANE_KERNARG_OFFSET);
     uint32_t *table = (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces));
-    tally_tiled_body<true, false, false, LATER_PASS, PLANES_RG>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta, refs_lds,
-                                                           gk, grp_lds);
+    tally_tiled_body<true, false, false, LATER_PASS, PLANES>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta, refs_lds,
+                                                             gk, grp_lds);
 }
-// dynamic LDS a grouped launch may take: the CU's 160 KiB less the kernel's static objects (~10.6 KiB) and some margin
+// dynamic LDS a plane launch may take: the CU's 160 KiB less the kernel's static objects (~10.6 KiB) and some margin
 constexpr uint32_t GROUPED_LDS_BUDGET = 148u * 1024u;
 __host__ __device__ inline uint32_t tiled_grouped_lds_bytes(uint32_t T, uint32_t pieces, uint32_t n_slots) {
     return tiled_lds_bytes(T, pieces) + (n_slots + 1u) * GROUP_PLANE_WORDS * 4u;
 }
 
-// reduce_partials for tally_tiled_grouped: slot layout [deltas 16 | n_slots planes]; plane slot s
+// reduce_partials for tally_tiled_planes: slot layout [deltas 16 | n_slots planes]; plane slot s
 // of the launch is plane plane0 + s of the counter block.  The status deltas (and the launch's
 // record credit) belong to the launch of rows 0.. and planes 0..
-__global__ void __launch_bounds__(256) reduce_partials_grouped(const TallyParams P, const GroupParams G, uint32_t n_slots) {
+__global__ void __launch_bounds__(256) reduce_partials_grouped(const TallyParams P, const PlaneParams G, uint32_t n_slots) {
     const uint32_t sw = G.scratch_words;
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t i = gid % sw, g = gid / sw;
@@ -1284,9 +1269,10 @@ __global__ void __launch_bounds__(256) reduce_partials_grouped(const TallyParams
     if (sum) atomicAdd(dst, (unsigned long long)sum);
 }
 
-// tally_simple with every record's counts in its group's plane (global atomics; the cross-check
-// of tally_tiled_grouped).  Substitution tables only.
-__global__ void __launch_bounds__(256) tally_simple_grouped(const TallyParams P, const GroupParams G) {
+// tally_simple with every record's counts in its plane (global atomics; the cross-check of
+// tally_tiled_planes).  Substitution tables only.
+template <PlaneSel PLANES>
+__global__ void __launch_bounds__(256) tally_simple_planes(const TallyParams P, const PlaneParams G) {
     __shared__ int32_t lds_delta[ST_USED];
     if (threadIdx.x < ST_USED) lds_delta[threadIdx.x] = 0;
     __syncthreads();
@@ -1297,59 +1283,9 @@ __global__ void __launch_bounds__(256) tally_simple_grouped(const TallyParams P,
         const RecHdr h = decode_hdr(src, o1 - o0);
         const Plan pl = make_plan<true, false>(P, src, h);
         if (pl.pss_fwd || pl.pss_rev) {
-            const uint32_t plane = read_group_plane(src, h, G);
+            const uint32_t plane = record_plane<PLANES>(src, h, pl, G);
             unsigned long long *base = P.counters + (plane ? G.off_groups + (plane - 1u) * G.plane_words : 0u);
             tally_pss_record(P, GlobalTable{base, P.off_rev}, src, h, pl);
-        }
-        book_events(true, false, record_events(true, false, pl, false), lds_delta);
-    }
-    __syncthreads();
-    flush_events(true, false, P, lds_delta);
-}
-
-// ---------------------------------------------------------------------------------------
-// -S: one set of substitution tables per fragment-length bin, in one pass over the records
-// ---------------------------------------------------------------------------------------
-// Third kernel argument, behind the GroupParams (n_groups = bins; ids / hash unused), which
-// reduce_partials_grouped reads as it does for -G.
-constexpr size_t LENBIN_KERNARG_OFFSET =
-    (GROUP_KERNARG_OFFSET + sizeof(GroupParams) + alignof(LenBinParams) - 1) & ~(alignof(LenBinParams) - 1);
-
-// tally_tiled_grouped with the plane taken from the read's length bin: the LDS layout, plane
-// passes and row passes are the grouped kernel's, but only record prefixes through QUAL[0] are
-// staged (whole records with -R only).  Substitution tables only.
-template <bool LATER_PASS>
-__global__ void __launch_bounds__(TILED_THREADS) tally_tiled_lenbins(const TallyParams P, const GroupParams G, const LenBinParams B) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
-    __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
-    __shared__ uint32_t toffs[2u * (TILED_MAX_T + 4u)];
-    __shared__ uint32_t grp_lds[TILED_MAX_T];
-    __shared__ uint32_t lds_kmer[1];
-    __shared__ int32_t lds_delta[ST_USED];
-    __shared__ uint4 refs_lds[REF_LDS_ENTRIES + 1];
-    const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
-    const GroupParams *gk = (const GroupParams *)((const uint8_t *)kernarg + GROUP_KERNARG_OFFSET);
-    const LenBinParams *bk = (const LenBinParams *)((const uint8_t *)kernarg + LENBIN_KERNARG_OFFSET);
-    uint32_t *table = (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces));
-    tally_tiled_body<true, false, false, LATER_PASS, PLANES_LEN>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta, refs_lds,
-                                                                 gk, grp_lds, bk);
-}
-
-// tally_simple with every record's counts in its length bin's plane (global atomics; the
-// cross-check of tally_tiled_lenbins).  Substitution tables only.
-__global__ void __launch_bounds__(256) tally_simple_lenbins(const TallyParams P, const GroupParams G, const LenBinParams B) {
-    __shared__ int32_t lds_delta[ST_USED];
-    if (threadIdx.x < ST_USED) lds_delta[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < P.n_recs; r += stride) {
-        const uint32_t o0 = P.offs[r], o1 = P.offs[r + 1];
-        GlobalBytes src{P.recs + o0};
-        const RecHdr h = decode_hdr(src, o1 - o0);
-        const Plan pl = make_plan<true, false>(P, src, h);
-        if (pl.pss_fwd || pl.pss_rev) {
-            const uint32_t plane = length_bin_plane(B, pl.L);
-            tally_pss_record(P, GlobalTable{P.counters + G.off_groups + (plane - 1u) * G.plane_words, P.off_rev}, src, h, pl);
         }
         book_events(true, false, record_events(true, false, pl, false), lds_delta);
     }

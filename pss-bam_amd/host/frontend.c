@@ -400,11 +400,9 @@ int env_gpu_count(void)
 
 void run_result_free(run_result *res)
 {
-    pss_free_read_groups(res->group_ids, res->n_groups);
-    free(res->group_fwd);
-    free(res->group_rev);
-    free(res->bin_fwd);
-    free(res->bin_rev);
+    pss_free_read_groups(res->group_ids, res->group_ids ? res->n_planes : 0);
+    free(res->plane_fwd);
+    free(res->plane_rev);
     free(res->fwd);
     free(res->rev);
     free(res->k5);
@@ -416,13 +414,13 @@ void run_result_free(run_result *res)
  * ungrouped.  Returns 0 or -1 after a diagnostic. */
 static int send_read_groups(pssbam_engine **eng, int n_gpus, const char *text, size_t len, run_result *res)
 {
-    if ((res->n_groups = pss_parse_read_groups(text, len, &res->group_ids)) < 0) {
-        res->n_groups = 0;
+    if ((res->n_planes = pss_parse_read_groups(text, len, &res->group_ids)) < 0) {
+        res->n_planes = 0;
         fprintf(stderr, "Error: out of memory\n");
         return -1;
     }
-    for (int g = 0; g < n_gpus && res->n_groups > 0; g++)
-        if (pssbam_engine_set_read_groups(eng[g], res->n_groups, (const char *const *)res->group_ids)) {
+    for (int g = 0; g < n_gpus && res->n_planes > 0; g++)
+        if (pssbam_engine_set_read_groups(eng[g], res->n_planes, (const char *const *)res->group_ids)) {
             fprintf(stderr, "Error: GPU engine %d: %s\n", g, pssbam_last_error());
             return -1;
         }
@@ -543,7 +541,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
         refs_sent = bam_reader_header(rd)->n_ref;
         dfs = EF.dfs;
         if (frontend_group_by_rg) { /* the helper set these IDs on its engines */
-            res->n_groups = EF.n_rg;
+            res->n_planes = EF.n_rg;
             res->group_ids = EF.rg_ids;
             EF.rg_ids = NULL;
             EF.n_rg = 0;
@@ -735,25 +733,14 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
         fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
         goto done;
     }
-    if (res->n_groups > 0) {
+    if (frontend_n_length_edges > 0) res->n_planes = frontend_n_length_edges + 1; /* -G: set with the IDs */
+    if (res->n_planes > 0) {
         const size_t cells = (size_t)(cfg->pss.region_len + 2) * 16;
-        res->group_fwd = (unsigned long *)calloc(cells * (size_t)res->n_groups, sizeof(unsigned long));
-        res->group_rev = (unsigned long *)calloc(cells * (size_t)res->n_groups, sizeof(unsigned long));
-        if (!res->group_fwd || !res->group_rev) { fprintf(stderr, "Error: out of memory\n"); goto done; }
-        for (int k = 0; k < res->n_groups; k++)
-            if (pssbam_engine_finish_groups(eng[0], k, res->group_fwd + k * cells, res->group_rev + k * cells)) {
-                fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
-                goto done;
-            }
-    }
-    if (frontend_n_length_edges > 0) {
-        const size_t cells = (size_t)(cfg->pss.region_len + 2) * 16;
-        res->n_bins = frontend_n_length_edges + 1;
-        res->bin_fwd = (unsigned long *)calloc(cells * (size_t)res->n_bins, sizeof(unsigned long));
-        res->bin_rev = (unsigned long *)calloc(cells * (size_t)res->n_bins, sizeof(unsigned long));
-        if (!res->bin_fwd || !res->bin_rev) { fprintf(stderr, "Error: out of memory\n"); goto done; }
-        for (int k = 0; k < res->n_bins; k++)
-            if (pssbam_engine_finish_groups(eng[0], k, res->bin_fwd + k * cells, res->bin_rev + k * cells)) {
+        res->plane_fwd = (unsigned long *)calloc(cells * (size_t)res->n_planes, sizeof(unsigned long));
+        res->plane_rev = (unsigned long *)calloc(cells * (size_t)res->n_planes, sizeof(unsigned long));
+        if (!res->plane_fwd || !res->plane_rev) { fprintf(stderr, "Error: out of memory\n"); goto done; }
+        for (int k = 0; k < res->n_planes; k++)
+            if (pssbam_engine_finish_groups(eng[0], k, res->plane_fwd + k * cells, res->plane_rev + k * cells)) {
                 fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
                 goto done;
             }

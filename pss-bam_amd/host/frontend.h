@@ -14,14 +14,11 @@ typedef struct run_result {
     uint64_t stats[PSSBAM_ST_N];
     double inflate_s, total_s;
     int n_gpus;
-    /* pss-bam -G (frontend_group_by_rg): the header's @RG IDs and each one's tables, (region_len+2)*16 per group */
-    int n_groups;
+    /* pss-bam -G / -S: the tables of each plane of the engine, (region_len+2)*16 per plane; plane k is the header's
+     * k-th @RG ID (frontend_group_by_rg, group_ids[k]) or length bin k (frontend_length_edges, group_ids NULL) */
+    int n_planes;
     char **group_ids;
-    unsigned long *group_fwd, *group_rev;
-    /* pss-bam -S (frontend_length_edges): each length bin's tables, (region_len+2)*16 per bin, bin k = group k of
-     * the engine */
-    int n_bins;
-    unsigned long *bin_fwd, *bin_rev;
+    unsigned long *plane_fwd, *plane_rev;
 } run_result;
 
 /* pss-bam -G: every engine gets the input header's @RG IDs (pssbam_engine_set_read_groups) and run_tally()

@@ -157,37 +157,24 @@ int main(int argc, char *argv[])
     pss_sub_rates(region_len, res.rev, rev_rates);
     pss_write_counts(fasta_fn, bam_fn, out_prefix, region_len, res.fwd, res.rev);
     pss_write_rates(fasta_fn, bam_fn, out_prefix, region_len, fwd_rates, rev_rates);
-    if (by_group && res.n_groups == 0)
+    if (by_group && res.n_planes == 0)
         fprintf(stderr, "Warning: -G: the header of %s has no @RG line; only the tables of all reads were written.\n", bam_fn);
-    for (int k = 0; k < res.n_groups; k++) { /* <prefix>.<ID>: what `-R <ID> -o <prefix>.<ID>` writes */
+    /* <prefix>.<tag>: what `-R <ID> -o <prefix>.<ID>` (-G) or `-l <lo> -L <hi> -o <prefix>.len<lo>-<hi>` (-S) writes */
+    for (int k = 0; k < res.n_planes; k++) {
         const size_t cells = (size_t)(region_len + 2) * 16;
-        const size_t tag_len = pss_rg_file_tag(res.group_ids[k], NULL, 0);
-        char *gprefix = (char *)malloc(strlen(out_prefix) + tag_len + 2);
-        if (!gprefix) { fprintf(stderr, "Error: out of memory\n"); exit(1); }
-        strcpy(gprefix, out_prefix);
-        strcat(gprefix, ".");
-        pss_rg_file_tag(res.group_ids[k], gprefix + strlen(gprefix), tag_len + 1);
-        pss_sub_rates(region_len, res.group_fwd + k * cells, fwd_rates);
-        pss_sub_rates(region_len, res.group_rev + k * cells, rev_rates);
-        pss_write_counts(fasta_fn, bam_fn, gprefix, region_len, res.group_fwd + k * cells, res.group_rev + k * cells);
-        pss_write_rates(fasta_fn, bam_fn, gprefix, region_len, fwd_rates, rev_rates);
-        free(gprefix);
-    }
-    for (int k = 0; k < res.n_bins; k++) { /* <prefix>.len<lo>-<hi>: what `-l <lo> -L <hi> -o <prefix>.len<lo>-<hi>` writes */
-        const size_t cells = (size_t)(region_len + 2) * 16;
-        unsigned long lo, hi;
-        pss_length_bin_bounds(edges, n_edges, k, min_read_len, max_read_len, &lo, &hi);
-        const size_t tag_len = pss_length_bin_tag(lo, hi, NULL, 0);
-        char *bprefix = (char *)malloc(strlen(out_prefix) + tag_len + 2);
-        if (!bprefix) { fprintf(stderr, "Error: out of memory\n"); exit(1); }
-        strcpy(bprefix, out_prefix);
-        strcat(bprefix, ".");
-        pss_length_bin_tag(lo, hi, bprefix + strlen(bprefix), tag_len + 1);
-        pss_sub_rates(region_len, res.bin_fwd + k * cells, fwd_rates);
-        pss_sub_rates(region_len, res.bin_rev + k * cells, rev_rates);
-        pss_write_counts(fasta_fn, bam_fn, bprefix, region_len, res.bin_fwd + k * cells, res.bin_rev + k * cells);
-        pss_write_rates(fasta_fn, bam_fn, bprefix, region_len, fwd_rates, rev_rates);
-        free(bprefix);
+        unsigned long lo = 0, hi = 0;
+        if (!by_group) pss_length_bin_bounds(edges, n_edges, k, min_read_len, max_read_len, &lo, &hi);
+        const size_t tag_len = by_group ? pss_rg_file_tag(res.group_ids[k], NULL, 0) : pss_length_bin_tag(lo, hi, NULL, 0);
+        char *pprefix = (char *)malloc(strlen(out_prefix) + tag_len + 2);
+        if (!pprefix) { fprintf(stderr, "Error: out of memory\n"); exit(1); }
+        char *tag = pprefix + sprintf(pprefix, "%s.", out_prefix);
+        if (by_group) pss_rg_file_tag(res.group_ids[k], tag, tag_len + 1);
+        else pss_length_bin_tag(lo, hi, tag, tag_len + 1);
+        pss_sub_rates(region_len, res.plane_fwd + k * cells, fwd_rates);
+        pss_sub_rates(region_len, res.plane_rev + k * cells, rev_rates);
+        pss_write_counts(fasta_fn, bam_fn, pprefix, region_len, res.plane_fwd + k * cells, res.plane_rev + k * cells);
+        pss_write_rates(fasta_fn, bam_fn, pprefix, region_len, fwd_rates, rev_rates);
+        free(pprefix);
     }
 
     if (getenv("PSSBAM_STATS")) {

@@ -104,7 +104,7 @@ def test_tiled_stage_read_group_filter(pkg, oracle, tmp_path, monkeypatch, shape
 @pytest.mark.parametrize("shape", ["default", "one_workgroup", "seven_workgroups", "short_tile_overflow"])
 @pytest.mark.parametrize("region_len", [25, 62])
 def test_tiled_stage_groups(pkg, oracle, tmp_path, monkeypatch, shape, region_len):
-    """-G with 4 groups (tally_tiled_grouped, first and later-row passes)"""
+    """-G with 4 groups (tally_tiled_planes<PLANES_RG>, first and later-row passes)"""
     for k, v in SHAPES[shape].items():
         monkeypatch.setenv(k, v)
     ids = ["lib1", "lib2", "lib3", "lib4"]
