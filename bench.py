@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- pss-bam per-read hot path on MI355X: aligned reads/s (whole job) + HBM roofline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--scaling strong|weak] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--scaling strong|weak] [--dump-outputs DIR] [--full]
 
 One "step" = one complete pass of the hot path over the synthetic record stream: every
 alignment record of every rank's shard decoded, filtered and tallied, counters reduced to
@@ -18,14 +18,19 @@ pss-bam_amd/csrc/synth_model.h.
     under a launcher (the driver's torch.distributed.run) it is a rank.
   * --scaling strong (default): the configuration's reads IN TOTAL; rank r owns the contiguous
     slot range [r*total/N, (r+1)*total/N) of the one sorted stream.  --scaling weak: the
-    configuration's reads PER GPU.  For N > 1 the strong line also carries a `weak_scaling`
-    object measured in the same run.  No data-path collective; one RCCL sum of the ~7 KB
+    configuration's reads PER GPU.  For N > 1 the strong line of a --full run also carries a
+    `weak_scaling` object measured in the same run.  No data-path collective; one RCCL sum of the ~7 KB
     counter block per step.
 
 Rank 0 prints ONE JSON line (contract in the task statement) with these extra objects:
   roofline     algorithmic bytes per launch / mean launch duration of the tally kernel
                (HIP events on the engine's stream, around every launch of the timed steps);
                `frac` against the 8 TB/s spec peak, `frac_of_traffic` from the PMC-measured bytes
+
+A plain run stops there: it sets up, warms up, times the steps, dumps (--dump-outputs) and prints.
+--full adds the measurements that take runs of their own (each `--no-...` switch drops one of them):
+  weak_scaling (N > 1, strong) the same steps over the weak plan's shards, in the same run
+  reduce_ms    (distributed runs) the counter reduce timed alone
   cpu_baseline the UNMODIFIED reference (oracle/_ref, -O2 build) timed on this box's host
                on a bounded prefix of the same stream (1 core: the reference has no threads)
   e2e          (N=1) bin/pss-bam on a generated level-1 BGZF BAM + FASTA of the named shape:
@@ -126,22 +131,28 @@ def parse_args(argv=None):
                     help="read count (total for --scaling strong, per GPU for weak; default: the config's)")
     ap.add_argument("--unsorted", action="store_true", help="shuffled record order (gather stress)")
     ap.add_argument("--kernel", type=int, default=0, help="0 auto, 1 simple, 2 tiled")
-    ap.add_argument("--cpu-sample", type=int, default=2_000_000, help="reads timed on the host reference")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: CPU baseline + parity, file-to-tables, weak-scaling leg, reduce timing")
+    ap.add_argument("--cpu-sample", type=int, default=2_000_000, help="reads timed on the host reference (--full)")
     ap.add_argument("--region-len", type=int, default=None, help="override the configuration's -r N (parity cases / large-N passes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-cores", type=int, default=0,
                     help="processes of the all-cores CPU figure (SURVEY 8d: one reference process per core on disjoint shards); "
                          "0 = the CPUs this job may use (cgroup cpu.max), 1 = skip it")
     ap.add_argument("--scale-genome", type=float, default=1.0)
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and run the counter reduce even with one rank")
-    ap.add_argument("--no-weak-leg", action="store_true", help="N > 1, strong: skip the additional weak-scaling measurement")
-    ap.add_argument("--force-weak-leg", action="store_true", help="run the weak-scaling companion leg even with one rank (test hook)")
+    ap.add_argument("--no-weak-leg", action="store_true", help="--full, N > 1, strong: skip the additional weak-scaling measurement")
+    ap.add_argument("--force-weak-leg", action="store_true",
+                    help="--full: run the weak-scaling companion leg even with one rank (test hook)")
     ap.add_argument("--e2e-reads", type=int, default=None,
-                    help="reads of the file-to-tables leg (N=1; default: the configuration's count, bounded by free disk)")
-    ap.add_argument("--no-e2e", action="store_true")
+                    help="reads of the file-to-tables leg (--full; default: the configuration's count, bounded by free disk)")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without the file-to-tables leg")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the tables of the last timed step as DIR/<name>.npy (float64)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.force_weak_leg and not args.full:
+        ap.error("--force-weak-leg asks for a leg of --full: give --full too")
+    return args
 
 
 def self_launch(args) -> int:
@@ -379,6 +390,10 @@ def main():
             allr = [torch.zeros_like(mine) for _ in range(world)]
             dist.all_gather(allr, mine)
             res["per_rank"] = [[float(x) for x in t.tolist()] for t in allr]
+        else:
+            res["per_rank"] = [[kernel_ms / max(n_launch, 1), float(n_launch), float(wl.n_reads), float(wl.rec_bytes)]]
+        res["reduce_ms"] = None
+        if use_dist and args.full:
             # the collective alone: same tensor, same call, nothing else on the stream
             fence()
             R = 50
@@ -387,9 +402,6 @@ def main():
                 reduce_counters(ctr, 2)
             fence()
             res["reduce_ms"] = (time.perf_counter() - t1) / R * 1e3
-        else:
-            res["per_rank"] = [[kernel_ms / max(n_launch, 1), float(n_launch), float(wl.n_reads), float(wl.rec_bytes)]]
-            res["reduce_ms"] = None
         res["dt"] = dt
         return res
 
@@ -467,8 +479,9 @@ def main():
         out["reduce_ms"] = m["reduce_ms"]
     strong_counters = m["counters"]
 
+    # ---- --full only from here on: the legs below take runs of their own ---------------------------
     # ---- N > 1: the weak-scaling companion measurement, in the same run ------------------------
-    if (world > 1 or args.force_weak_leg) and args.scaling == "strong" and not args.no_weak_leg:
+    if args.full and (world > 1 or args.force_weak_leg) and args.scaling == "strong" and not args.no_weak_leg:
         del wl
         torch.cuda.empty_cache()
         wcfg, wtotal, wslot0, wn = cfg_for("weak")
@@ -481,7 +494,7 @@ def main():
         }
 
     # ---- CPU baseline: the reference itself on this box's host, on a bounded prefix -----------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"], out["parity_check"] = cpu_baseline(pkg, synth, eng, cfg, cd, region_len, klen,
                                                                     min(args.cpu_sample, my_reads), names,
@@ -490,7 +503,7 @@ def main():
             out["cpu_baseline"] = {"value": None, "unit": "reads/s", "cores": 1, "kind": "reference",
                                    "sample": f"failed: {ex!r}"}
     # ---- file-to-tables on the named shape (never `value`) ---------------------------------------
-    if rank == 0 and world == 1 and not args.no_e2e and not klen and not args.unsorted and args.config != "C1":
+    if args.full and rank == 0 and world == 1 and not args.no_e2e and not klen and not args.unsorted and args.config != "C1":
         try:
             del wl
             torch.cuda.empty_cache()
@@ -498,7 +511,7 @@ def main():
         except Exception as ex:
             out["e2e"] = {"error": repr(ex)}
     # ---- N > 1: the command itself over all GPUs of the node (one process, one engine per GPU) ----------
-    if world > 1 and not args.no_e2e and not klen and not args.unsorted and args.config != "C1":
+    if args.full and world > 1 and not args.no_e2e and not klen and not args.unsorted and args.config != "C1":
         flag = Path(tempfile.gettempdir()) / f"pssbam_e2e_done_{os.environ.get('MASTER_PORT', '0')}_{os.getppid()}"
         if rank == 0:
             try:

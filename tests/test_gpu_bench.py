@@ -1,5 +1,6 @@
 """bench.py on the GPU box: the contract line parses, carries the extra objects, and the
-distributed path (RCCL init + the in-place u64 counter reduce) has executed on hardware."""
+distributed path (RCCL init + the in-place u64 counter reduce) has executed on hardware.
+A plain run carries only what the timed steps measure; --full adds the legs of their own."""
 import json
 import os
 import subprocess
@@ -21,8 +22,8 @@ def _run(args, timeout=900):
 
 def test_bench_force_dist_one_rank_rccl():
     """--force-dist: a 1-rank RCCL communicator + dist.reduce of the bound counter tensor every step"""
-    pr = _run(["--force-dist", "--force-weak-leg", "--reads", "2000000", "--steps", "2", "--warmup", "1", "--no-e2e", "--cpu-sample",
-               "200000"])
+    pr = _run(["--full", "--force-dist", "--force-weak-leg", "--reads", "2000000", "--steps", "2", "--warmup", "1", "--no-e2e",
+               "--cpu-sample", "200000"])
     assert pr.returncode == 0, pr.stderr[-3000:]
     line = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")]
     assert len(line) == 1
@@ -41,6 +42,25 @@ def test_bench_force_dist_one_rank_rccl():
     assert d["roofline"]["traffic"] is None or isinstance(d["roofline"]["traffic_stale"], bool)
 
 
+def test_bench_plain_run_leaves_the_extra_legs_to_full(tmp_path):
+    """no --full: the contract line, the roofline of the timed steps and the dumped tables, and none of the legs
+    that take runs of their own"""
+    pr = _run(["--reads", "2000000", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert pr.returncode == 0, pr.stderr[-3000:]
+    line = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")]
+    assert len(line) == 1
+    d = json.loads(line[0])
+    assert d["unit"] == "reads/s" and d["higher_is_better"] is True and d["dtype"] == "u64" and d["value"] > 1e8
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert d["stats_last_step"]["records"] == 2_000_000
+    assert d["roofline"]["bound"] == "hbm" and 0 < d["roofline"]["frac"] < 1.0 and d["roofline"]["launches_timed"] > 0
+    for leg in ("cpu_baseline", "parity_check", "e2e", "weak_scaling", "reduce_ms", "per_rank"):
+        assert leg not in d, leg
+    import numpy as np
+    assert int(np.load(tmp_path / "stats.npy")[0]) == 2_000_000   # records, the first statistic
+    assert np.load(tmp_path / "fwd.npy").sum() + np.load(tmp_path / "rev.npy").sum() > 0
+
+
 def test_bench_bare_multi_gpu_launch_is_decided_before_any_gpu_call():
     import torch
     if torch.cuda.device_count() >= 2:
@@ -51,7 +71,7 @@ def test_bench_bare_multi_gpu_launch_is_decided_before_any_gpu_call():
 
 def test_bench_e2e_leg_small():
     """the file-to-tables leg on a small shape: tables of bin/pss-bam == the resident tally"""
-    pr = _run(["--config", "C2", "--reads", "3000000", "--scale-genome", "0.02", "--steps", "2", "--warmup", "1",
+    pr = _run(["--full", "--config", "C2", "--reads", "3000000", "--scale-genome", "0.02", "--steps", "2", "--warmup", "1",
                "--no-cpu-baseline"])
     assert pr.returncode == 0, pr.stderr[-3000:]
     d = json.loads([ln for ln in pr.stdout.splitlines() if ln.startswith("{")][0])

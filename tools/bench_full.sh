@@ -1,12 +1,14 @@
-# tools/bench_full.sh -- GPU-box helper: the default bench (BASELINE metric config) + rocprofv3 evidence
+# tools/bench_full.sh OUTDIR -- the full bench (BASELINE metric config, every leg) + rocprofv3 evidence, into OUTDIR
 set -e
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out/full
-python3 bench.py > gpurun_out/full/bench.json 2> gpurun_out/full/bench.err || { tail -20 gpurun_out/full/bench.err; exit 1; }
-cat gpurun_out/full/bench.json
-# kernel-trace summary of the same workload (the CPU-baseline leg is a child process without kernels)
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/full/stats -- python3 bench.py --no-cpu-baseline --no-e2e > gpurun_out/full/stats.log 2>&1 || tail -5 gpurun_out/full/stats.log
-tail -2 gpurun_out/full/stats.log
-find gpurun_out/full/stats -name "*kernel_stats.csv" -exec cat {} \;
-PROF_READS=${PROF_READS:-50000000} bash tools/prof1.sh > gpurun_out/full/prof.txt 2>&1 || tail -20 gpurun_out/full/prof.txt
-tail -60 gpurun_out/full/prof.txt
+OUT=${1:?usage: tools/bench_full.sh OUTDIR}
+mkdir -p "$OUT" && OUT=$(cd "$OUT" && pwd)
+export TMPDIR=${TMPDIR:-/tmp}
+cd "$(dirname "$0")/.."
+python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+cat "$OUT/bench.json"
+# kernel-trace summary of the same workload: a plain run, the timed steps and nothing else
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 bench.py > "$OUT/stats.log" 2>&1 || tail -5 "$OUT/stats.log"
+tail -2 "$OUT/stats.log"
+find "$OUT/stats" -name "*kernel_stats.csv" -exec cat {} \;
+PROF_READS=${PROF_READS:-50000000} bash tools/prof1.sh > "$OUT/prof.txt" 2>&1 || tail -20 "$OUT/prof.txt"
+tail -60 "$OUT/prof.txt"
