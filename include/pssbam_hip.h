@@ -35,6 +35,7 @@ extern "C" {
 #define PSSBAM_MAX_KLEN 15     /* 4^15 64-bit bins per k-mer table = 8.6 GB of device memory */
 #define PSSBAM_MAX_READ_GROUPS 4096  /* pssbam_engine_set_read_groups */
 #define PSSBAM_MAX_LENGTH_BINS 64    /* pssbam_engine_set_length_bins: at most 63 edges */
+#define PSSBAM_MAX_CONTIG_SETS 4096  /* pssbam_engine_set_contig_sets */
 
 /* error codes */
 #define PSSBAM_OK 0
@@ -193,7 +194,8 @@ int pssbam_engine_reset(pssbam_engine *e);
 int pssbam_engine_set_read_groups(pssbam_engine *e, int32_t n, const char *const *ids);
 /* Drains the engine like pssbam_engine_finish and copies one group's two tables ((region_len+2)*16 each, any
  * pointer may be NULL): group -1 is the unassigned bucket, 0..n-1 the IDs in the order given.  With length bins
- * (below) group k is bin k and group -1 is all zeros. */
+ * (below) group k is bin k and group -1 is all zeros.  With contig sets (below) group s is set s and group -1
+ * holds the records on contigs no set lists. */
 int pssbam_engine_finish_groups(pssbam_engine *e, int32_t group, unsigned long *fwd, unsigned long *rev);
 
 /* Length bins (pss-bam -S): one set of substitution tables per fragment-length bin in a single pass over the
@@ -209,13 +211,31 @@ int pssbam_engine_finish_groups(pssbam_engine *e, int32_t group, unsigned long *
  * totals over every bin, pssbam_engine_finish_groups(e, k, ...) returns bin k. */
 int pssbam_engine_set_length_bins(pssbam_engine *e, int32_t n_edges, const uint32_t *edges);
 
+/* Contig sets (pss-bam -C): one set of substitution tables per set of reference sequences in a single pass over
+ * the records, instead of one run per set with a FASTA cut down to that set's contigs.  names[0..n_names-1] are
+ * contig names, set_of[i] in 0..n_sets-1 the set of names[i], n_sets in 1..PSSBAM_MAX_CONTIG_SETS; a name given
+ * twice under the same set counts once, under two sets it is PSSBAM_EINVAL.  A record belongs to set s when its
+ * RNAME (the @SQ name of its refID, "*" for refID -1) is listed under s -- exactly the records the reference
+ * tallies with -F holding only s's contigs, since it skips every read whose RNAME find_seq cannot find -- and
+ * to the unassigned bucket otherwise.  The engine keeps the name -> set map and applies it to every reference
+ * table, so the call is legal before and after set_references (a later set_references, e.g. of the SAM-text
+ * reader as new RNAMEs show up, applies it again).  Otherwise legal and illegal as
+ * pssbam_engine_set_read_groups: after create (or reset) and before the first tally launch, allowed with
+ * cfg.read_group; PSSBAM_EINVAL with PSSBAM_TALLY_KMER, with read groups or length bins set, or with bad
+ * arguments, PSSBAM_ESTATE once records have been tallied or the counter block has been bound.  The sets
+ * survive pssbam_engine_reset; pssbam_engine_finish keeps returning the totals over every record,
+ * pssbam_engine_finish_groups(e, s, ...) returns set s. */
+int pssbam_engine_set_contig_sets(pssbam_engine *e, int32_t n_sets, int64_t n_names, const char *const *names,
+                                  const int32_t *set_of);
+
 /* The device-resident counter block [fwd | rev | k5 | k3 | stats] as one array of
  * n_u64 64-bit words, for a caller-side RCCL reduce across GPUs (sum, uint64).  With read groups it is
  * [fwd | rev | stats | fwd_0 | rev_0 | ... | fwd_n-1 | rev_n-1]: the leading fwd | rev are the unassigned
  * bucket, group g's pair ((region_len+2)*16 words each) starts at 2*(region_len+2)*16 + PSSBAM_ST_N +
  * g*2*(region_len+2)*16 (the k-mer tables are empty: read groups exclude PSSBAM_TALLY_KMER).  With length bins the
- * layout is the same with bin k in group k's place, and the leading fwd | rev stay zero.  The block is still
- * summed across GPUs as one u64 array. */
+ * layout is the same with bin k in group k's place, and the leading fwd | rev stay zero.  With contig sets it is
+ * the same with set s in group s's place, the leading fwd | rev the records on unlisted contigs.  The block is
+ * still summed across GPUs as one u64 array. */
 int pssbam_engine_counters_device(pssbam_engine *e, void **d_counters, size_t *n_u64);
 
 /* Makes the engine accumulate into caller-owned device memory (n_u64 words, as reported

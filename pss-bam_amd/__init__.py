@@ -41,9 +41,11 @@ HIP_SYMBOLS = [
     "pssbam_engine_feed_status", "pssbam_engine_feed_break", "pssbam_engine_feed_handoff", "pssbam_feed_reserve", "pssbam_engine_hint_records",
     "pssbam_engine_set_genome_async", "pssbam_engine_genome_wait", "pssbam_engine_feed_open", "pssbam_feed_release",
     "pssbam_engine_set_read_groups", "pssbam_engine_finish_groups", "pssbam_engine_set_length_bins",
+    "pssbam_engine_set_contig_sets",
 ]
 MAX_READ_GROUPS = 4096
 MAX_LENGTH_BINS = 64
+MAX_CONTIG_SETS = 4096
 EBUSY = -7
 
 
@@ -106,6 +108,7 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_set_read_groups.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p)]
     L.pssbam_engine_finish_groups.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_length_bins.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)]
+    L.pssbam_engine_set_contig_sets.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]
     L.pssbam_engine_counters_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.pssbam_engine_bind_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.pssbam_engine_genome_kmer_count.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -174,11 +177,12 @@ class Engine:
     `pss` = dict(region_len, min_read_len, max_read_len, min_mq, up_ctx, down_ctx, merged_only),
     `kmer` = dict(klen, min_mq, min_read_len, max_read_len, merged_only).
     `read_groups` = @RG IDs (pss-bam -G): one set of substitution tables per ID, see set_read_groups.
-    `length_bins` = length bin edges (pss-bam -S): one set of substitution tables per bin, see set_length_bins."""
+    `length_bins` = length bin edges (pss-bam -S): one set of substitution tables per bin, see set_length_bins.
+    `contig_sets` = contig sets (pss-bam -C): one set of substitution tables per label, see set_contig_sets."""
 
     def __init__(self, pss: dict | None = None, kmer: dict | None = None, read_group: str | None = None,
                  kernel: int = KERNEL_AUTO, device: int = -1, read_groups: list[str] | None = None,
-                 length_bins: list[int] | None = None):
+                 length_bins: list[int] | None = None, contig_sets=None):
         L = hip_lib()
         cfg = _Config()
         cfg.abi_version = 1
@@ -209,10 +213,33 @@ class Engine:
         self._L = L
         self.read_groups: list[str] = []
         self.length_bins: list[tuple[int, int]] = []
+        self.contig_sets: list[str] = []
         if read_groups is not None:
             self.set_read_groups(read_groups)
         if length_bins is not None:
             self.set_length_bins(length_bins)
+        if contig_sets is not None:
+            self.set_contig_sets(contig_sets)
+
+    def set_contig_sets(self, sets):
+        """pss-bam -C: tallies every record into the tables of the set that lists its RNAME (the unassigned bucket
+        otherwise).  `sets` = {label: [contig names]} or [(contig name, label)]; labels are numbered in order of
+        first appearance.  Before the first tally, like set_read_groups; before or after set_references."""
+        pairs = [(nm, lab) for lab, nms in sets.items() for nm in nms] if isinstance(sets, dict) else list(sets)
+        labels: list[str] = []
+        index: dict[str, int] = {}
+        for _, lab in pairs:
+            if lab not in index:
+                index[lab] = len(labels)
+                labels.append(lab)
+        names = (C.c_char_p * max(len(pairs), 1))(*[nm.encode() if isinstance(nm, str) else bytes(nm) for nm, _ in pairs])
+        set_of = (C.c_int32 * max(len(pairs), 1))(*[index[lab] for _, lab in pairs])
+        _chk(self._L.pssbam_engine_set_contig_sets(self._h, len(labels), len(pairs), names, set_of))
+        self.contig_sets = labels
+
+    def finish_sets(self) -> dict:
+        """{label: Tables} per contig set, in set order (fwd / rev only; drains like finish)"""
+        return self._finish_planes(enumerate(self.contig_sets))
 
     def set_length_bins(self, edges: list[int]):
         """pss-bam -S: tallies every record into the tables of its length bin [min_read_len, e1-1], [e1, e2-1], ...,
@@ -433,7 +460,9 @@ class Engine:
         # length bins: bin k's pair sits where group k's would (plane 0 stays empty)
         lay["length_bins"] = [{"bin": b, "fwd": base + k * 2 * rows * 16, "rev": base + k * 2 * rows * 16 + rows * 16}
                               for k, b in enumerate(self.length_bins)]
-        lay["n_u64"] = base + (len(self.read_groups) + len(self.length_bins)) * 2 * rows * 16
+        lay["contig_sets"] = [{"label": s, "fwd": base + k * 2 * rows * 16, "rev": base + k * 2 * rows * 16 + rows * 16}
+                              for k, s in enumerate(self.contig_sets)]
+        lay["n_u64"] = base + (len(self.read_groups) + len(self.length_bins) + len(self.contig_sets)) * 2 * rows * 16
         return lay
 
     def genome_kmer_count(self, klen: int) -> np.ndarray:

@@ -18,6 +18,7 @@
 #include <map>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <atomic>
 #include <memory>
 #include <mutex>
@@ -158,7 +159,7 @@ enum PrepSlot {
     PREP_TILED_PSS, PREP_TILED_PSS_LATER, PREP_TILED_PSS_KMER, PREP_TILED_PSS_KMER_LDS, PREP_TILED_KMER, PREP_TILED_KMER_LDS,
     PREP_COMPACT, PREP_COMPACT_KMER, PREP_COMPACT_KMER_LDS,
     PREP_COMPACT_ONCE, PREP_COMPACT_ONCE_KMER, PREP_COMPACT_ONCE_KMER_LDS, PREP_COMPACT_DECODE_TWICE,
-    PREP_PLANES_RG, PREP_PLANES_RG_LATER, PREP_PLANES_LEN, PREP_PLANES_LEN_LATER,
+    PREP_PLANES_RG, PREP_PLANES_RG_LATER, PREP_PLANES_LEN, PREP_PLANES_LEN_LATER, PREP_PLANES_REF, PREP_PLANES_REF_LATER,
     PREP_N
 };
 
@@ -204,14 +205,17 @@ struct pssbam_engine {
     bool have_refs = false;
     // -R
     uint8_t *d_rg = nullptr;
-    // -G / -S: n_planes [fwd | rev] planes of the counter block behind the stats (set_planes); plane 1 + g holds
-    // read group g (pssbam_engine_set_read_groups) or length bin g (pssbam_engine_set_length_bins)
+    // -G / -S / -C: n_planes [fwd | rev] planes of the counter block behind the stats (set_planes); plane 1 + g holds
+    // read group g (pssbam_engine_set_read_groups), length bin g (pssbam_engine_set_length_bins) or contig set g
+    // (pssbam_engine_set_contig_sets)
     PlaneSel planes = PLANES_NONE;
     uint32_t n_planes = 0, off_groups = 0, plane_words = 0;
     uint8_t *d_grp_ids = nullptr;   // -G: the ID table
     uint32_t *d_grp_offs = nullptr, *d_grp_hash = nullptr;
     uint32_t grp_hash_mask = 0;
     std::vector<uint32_t> len_edges;   // -S
+    std::unordered_map<std::string, uint32_t> ctg_plane;   // -C: contig name -> 1 + set, packed into ref_info[].w
+    std::vector<std::string> ref_names;   // the names of the last set_references (-C set after it packs them again)
     bool tallied = false;   // a tally launch since create / reset
     // counters
     unsigned long long *d_counters = nullptr;      // block in use (own or caller-bound)
@@ -638,12 +642,18 @@ extern "C" int pssbam_engine_set_references(pssbam_engine *e, int32_t n_ref, con
     if (!e || n_ref < 0 || (n_ref && !names)) return fail(PSSBAM_EINVAL, "bad argument");
     if (!e->d_genome) return fail(PSSBAM_ESTATE, "set_genome must precede set_references");
     HIP_TRY(hipSetDevice(e->device));
-    // ref_info[i] = {gbase lo, gbase hi, length, found}; entry n_ref answers RNAME "*" (refID -1)
+    // ref_info[i] = {gbase lo, gbase hi, length, found | plane << 1}; entry n_ref answers RNAME "*" (refID -1).
+    // plane = 1 + the -C set that lists the name (0: none); a name the genome lacks stays all zero.
     std::vector<uint4> info((size_t)n_ref + 1, make_uint4(0, 0, 0, 0));
-    auto fill = [&](size_t slot, int32_t contig) {
+    auto fill = [&](size_t slot, int32_t contig, const char *name) {
         if (contig < 0) return;
         const uint64_t gb = e->contig_start[(size_t)contig];
-        info[slot] = make_uint4((uint32_t)gb, (uint32_t)(gb >> 32), e->contig_len[(size_t)contig], 1u);
+        uint32_t plane = 0;
+        if (!e->ctg_plane.empty()) {
+            const auto it = e->ctg_plane.find(name);
+            if (it != e->ctg_plane.end()) plane = it->second;
+        }
+        info[slot] = make_uint4((uint32_t)gb, (uint32_t)(gb >> 32), e->contig_len[(size_t)contig], 1u | plane << 1);
     };
     for (int32_t i = 0; i < n_ref; i++) {
         // bsearch with strcmp over the sorted ids == find_seq (fasta-genome-io.c:202-213)
@@ -651,11 +661,12 @@ extern "C" int pssbam_engine_set_references(pssbam_engine *e, int32_t n_ref, con
         while (lo < hi) {
             const size_t mid = (lo + hi) / 2;
             const int c = strcmp(names[i], e->contig_ids[mid].c_str());
-            if (c == 0) { fill((size_t)i, (int32_t)mid); break; }
+            if (c == 0) { fill((size_t)i, (int32_t)mid, names[i]); break; }
             if (c < 0) hi = mid; else lo = mid + 1;
         }
     }
-    fill((size_t)n_ref, e->star_contig);
+    fill((size_t)n_ref, e->star_contig, "*");
+    e->ref_names.assign(names, names + n_ref);   // for a pssbam_engine_set_contig_sets after this call
     if (e->feed_opened && !e->deferred.empty() && n_ref != e->feed_n_ref)
         return fail(PSSBAM_ESTATE, "pssbam_engine_feed_open announced %d references, set_references brings %d", e->feed_n_ref, n_ref);
     // a table that is being REPLACED (SAM text: the list grows as new RNAMEs show up) may still be read by queued
@@ -755,8 +766,9 @@ static int launch_flat(pssbam_engine *e, PrepSlot slot, K kernel, TallyParams &P
 // One (row pass, plane pass) launch of tally_tiled_planes and its reduce_partials_grouped
 template <PlaneSel SEL, bool LATER>
 static int launch_planes(pssbam_engine *e, TallyParams &P, const PlaneParams &G, uint32_t lds, uint32_t n_tiles) {
-    constexpr PrepSlot slot = SEL == PLANES_RG ? (LATER ? PREP_PLANES_RG_LATER : PREP_PLANES_RG)
-                                               : (LATER ? PREP_PLANES_LEN_LATER : PREP_PLANES_LEN);
+    constexpr PrepSlot slot = SEL == PLANES_RG  ? (LATER ? PREP_PLANES_RG_LATER : PREP_PLANES_RG)
+                            : SEL == PLANES_LEN ? (LATER ? PREP_PLANES_LEN_LATER : PREP_PLANES_LEN)
+                                                : (LATER ? PREP_PLANES_REF_LATER : PREP_PLANES_REF);
     uint32_t grid = 0;
     const int rc = tiled_grid(e, slot, tally_tiled_planes<SEL, LATER>, lds, n_tiles, G.scratch_words, &grid);
     if (rc != PSSBAM_OK) return rc;
@@ -888,6 +900,7 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         if (e->env_simple_blocks > 0) blocks = (uint32_t)e->env_simple_blocks;
         if (e->planes == PLANES_RG) hipLaunchKernelGGL(tally_simple_planes<PLANES_RG>, dim3(blocks), dim3(256), 0, e->stream, P, G);
         else if (e->planes == PLANES_LEN) hipLaunchKernelGGL(tally_simple_planes<PLANES_LEN>, dim3(blocks), dim3(256), 0, e->stream, P, G);
+        else if (e->planes == PLANES_REF) hipLaunchKernelGGL(tally_simple_planes<PLANES_REF>, dim3(blocks), dim3(256), 0, e->stream, P, G);
         else if (lds_tab) hipLaunchKernelGGL(tally_simple<true>, dim3(blocks), dim3(256), tab_bytes, e->stream, P);
         else hipLaunchKernelGGL(tally_simple<false>, dim3(blocks), dim3(256), 0, e->stream, P);
     } else {
@@ -949,13 +962,14 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         int rc = PSSBAM_OK;
         P.row_base = 0;
         if (e->planes != PLANES_NONE) {
-            // -G / -S: every (32-row pass, plane pass) pair is one launch over the block.  A plane pass holds as
-            // many planes as fit the LDS beside the staging buffer (8 planes = 32 KiB always do: one pass for
-            // up to 7 groups or 6 bins -- plane 0 of -S stays empty but keeps its slot); more planes take more
-            // passes, each re-reading the records.
+            // -G / -S / -C: every (32-row pass, plane pass) pair is one launch over the block.  A plane pass holds
+            // as many planes as fit the LDS beside the staging buffer (8 planes = 32 KiB always do: one pass for
+            // up to 7 groups or sets, or 6 bins -- plane 0 of -S stays empty but keeps its slot); more planes take
+            // more passes, each re-reading the records.
             using LaunchPlanes = int (*)(pssbam_engine *, TallyParams &, const PlaneParams &, uint32_t, uint32_t);
-            static constexpr LaunchPlanes launch_pass[2][2] = {{launch_planes<PLANES_RG, false>, launch_planes<PLANES_RG, true>},
-                                                               {launch_planes<PLANES_LEN, false>, launch_planes<PLANES_LEN, true>}};
+            static constexpr LaunchPlanes launch_pass[3][2] = {{launch_planes<PLANES_RG, false>, launch_planes<PLANES_RG, true>},
+                                                               {launch_planes<PLANES_LEN, false>, launch_planes<PLANES_LEN, true>},
+                                                               {launch_planes<PLANES_REF, false>, launch_planes<PLANES_REF, true>}};
             const uint32_t n_planes = G.n_groups + 1u;
             const uint32_t fit = lds + 2u * GROUP_PLANE_WORDS * 4u <= GROUPED_LDS_BUDGET
                                      ? (GROUPED_LDS_BUDGET - lds) / (GROUP_PLANE_WORDS * 4u) - 1u : 1u;
@@ -967,7 +981,7 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                     G.plane0 = plane0;
                     G.n_slots = std::min(per_pass, n_planes - plane0);
                     G.scratch_words = GROUP_SCRATCH_DELTA + G.n_slots * GROUP_PLANE_WORDS;
-                    rc = launch_pass[e->planes == PLANES_LEN][pass > 0](e, P, G, tiled_grouped_lds_bytes(T, pieces, G.n_slots), n_tiles);
+                    rc = launch_pass[e->planes - PLANES_RG][pass > 0](e, P, G, tiled_grouped_lds_bytes(T, pieces, G.n_slots), n_tiles);
                 }
             }
         } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg) {
@@ -1197,7 +1211,7 @@ extern "C" int pssbam_engine_finish(pssbam_engine *e, unsigned long *fwd, unsign
 extern "C" int pssbam_engine_finish_groups(pssbam_engine *e, int32_t group, unsigned long *fwd, unsigned long *rev) {
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
     const int32_t n_planes = (int32_t)e->n_planes;
-    if (!n_planes) return fail(PSSBAM_ESTATE, "neither pssbam_engine_set_read_groups nor pssbam_engine_set_length_bins has been called");
+    if (!n_planes) return fail(PSSBAM_ESTATE, "none of pssbam_engine_set_read_groups / _set_length_bins / _set_contig_sets has been called");
     if (group < -1 || group >= n_planes) return fail(PSSBAM_EINVAL, "group %d outside -1..%d", group, n_planes - 1);
     int rc = pssbam_engine_sync(e);
     if (rc) return rc;
@@ -1235,6 +1249,7 @@ extern "C" int pssbam_engine_set_read_groups(pssbam_engine *e, int32_t n, const 
     if (n < 1 || n > PSSBAM_MAX_READ_GROUPS || !ids) return fail(PSSBAM_EINVAL, "read group count %d outside 1..%d", n, PSSBAM_MAX_READ_GROUPS);
     if (e->has_rg) return fail(PSSBAM_EINVAL, "read groups and a -R read group filter exclude each other");
     if (e->planes == PLANES_LEN) return fail(PSSBAM_EINVAL, "read groups and length bins exclude each other");
+    if (e->planes == PLANES_REF) return fail(PSSBAM_EINVAL, "read groups and contig sets exclude each other");
     for (int32_t i = 0; i < n; i++)
         if (!ids[i]) return fail(PSSBAM_EINVAL, "read group %d is NULL", i);
     // ID table (concatenated) + open-addressing hash over it; a repeated ID keeps its first index
@@ -1287,6 +1302,7 @@ extern "C" int pssbam_engine_set_length_bins(pssbam_engine *e, int32_t n_edges, 
     if (n_edges < 1 || n_edges > PSSBAM_MAX_LENGTH_BINS - 1 || !edges)
         return fail(PSSBAM_EINVAL, "length bin edge count %d outside 1..%d", n_edges, PSSBAM_MAX_LENGTH_BINS - 1);
     if (e->planes == PLANES_RG) return fail(PSSBAM_EINVAL, "length bins and read groups exclude each other");
+    if (e->planes == PLANES_REF) return fail(PSSBAM_EINVAL, "length bins and contig sets exclude each other");
     // l < e1 < ... < ek <= L: every bin [l, e1-1], [e1, e2-1], ..., [ek, L] is a non-empty -l / -L window
     const uint64_t lo = e->cfg.pss.min_read_len, hi = e->cfg.pss.max_read_len;
     for (int32_t i = 0; i < n_edges; i++) {
@@ -1299,6 +1315,35 @@ extern "C" int pssbam_engine_set_length_bins(pssbam_engine *e, int32_t n_edges, 
     if (rc) return rc;
     e->len_edges.assign(edges, edges + n_edges);
     return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_set_contig_sets(pssbam_engine *e, int32_t n_sets, int64_t n_names, const char *const *names,
+                                             const int32_t *set_of) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (n_sets < 1 || n_sets > PSSBAM_MAX_CONTIG_SETS)
+        return fail(PSSBAM_EINVAL, "contig set count %d outside 1..%d", n_sets, PSSBAM_MAX_CONTIG_SETS);
+    if (n_names < 0 || (n_names && (!names || !set_of))) return fail(PSSBAM_EINVAL, "bad contig name list");
+    if (e->planes == PLANES_RG) return fail(PSSBAM_EINVAL, "contig sets and read groups exclude each other");
+    if (e->planes == PLANES_LEN) return fail(PSSBAM_EINVAL, "contig sets and length bins exclude each other");
+    std::unordered_map<std::string, uint32_t> plane;
+    plane.reserve((size_t)n_names);
+    for (int64_t i = 0; i < n_names; i++) {
+        if (!names[i]) return fail(PSSBAM_EINVAL, "contig name %lld is NULL", (long long)i);
+        if (set_of[i] < 0 || set_of[i] >= n_sets)
+            return fail(PSSBAM_EINVAL, "contig %s: set %d outside 0..%d", names[i], set_of[i], n_sets - 1);
+        const auto ins = plane.emplace(names[i], (uint32_t)set_of[i] + 1u);
+        if (!ins.second && ins.first->second != (uint32_t)set_of[i] + 1u)
+            return fail(PSSBAM_EINVAL, "contig %s is given under two sets (%u and %d)", names[i], ins.first->second - 1u, set_of[i]);
+    }
+    const int rc = set_planes(e, PLANES_REF, (uint32_t)n_sets, "contig sets");
+    if (rc) return rc;
+    e->ctg_plane.swap(plane);
+    if (!e->have_refs) return PSSBAM_OK;   // set_references packs the planes into ref_info when it comes
+    // the reference table is there already: built again with the planes (nothing has read it: no tally yet)
+    const std::vector<std::string> refs = e->ref_names;
+    std::vector<const char *> ptrs(refs.size());
+    for (size_t i = 0; i < refs.size(); i++) ptrs[i] = refs[i].c_str();
+    return pssbam_engine_set_references(e, e->n_ref, ptrs.data());
 }
 
 extern "C" int pssbam_engine_reset(pssbam_engine *e) {

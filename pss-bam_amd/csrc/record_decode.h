@@ -39,8 +39,9 @@ struct TallyParams {
     const uint32_t *genome4;
     uint32_t acgt_ctx;            // bit 2v: base v in -U, bit 2v+1: in -D (v = 0..3 for A C G T)
     // BAM refID -> where its contig lies, resolved once per header by find_seq semantics:
-    // ref_info[refID] = {gbase lo, gbase hi, contig length, found ? 1 : 0}; entry n_ref is the
-    // one for RNAME "*" (refID -1; found only if a contig is literally named "*")
+    // ref_info[refID] = {gbase lo, gbase hi, contig length, found ? 1 | plane << 1 : 0}; entry n_ref is
+    // the one for RNAME "*" (refID -1; found only if a contig is literally named "*").  plane = 1 + s
+    // when -C lists the name under set s, else 0 (only ever set on a found entry: .w != 0 stays "found")
     const uint4 *ref_info;
     int32_t n_ref;
     // pss-bam options (pss-bam.c:12-18)
@@ -410,6 +411,7 @@ struct Plan {
     bool pss_cand;           // passed every pss filter that does not look at the genome
     bool pss_fwd, pss_rev;   // which table(s) this read is tallied into (set by plan_finish_pss)
     uint32_t L;              // pss effective length: |TLEN| when paired else strlen(SEQ)
+    uint32_t ref_plane;      // -C: the contig's plane from ref_info[refID].w (read only by PLANES_REF kernels)
     // fragkon
     bool fk5, fk3;           // which k-mer table(s) this read may add to
     uint32_t Lk;             // strlen(SEQ)
@@ -454,6 +456,7 @@ __device__ __forceinline__ Plan plan_head(const TallyParams &P, const Src &src, 
     const bool found = ri.w != 0u && (rid_ok || h.ref_id == -1);
     const uint32_t glen = ri.z;
     pl.gbase = ((uint64_t)ri.y << 32) | ri.x;
+    pl.ref_plane = ri.w >> 1;
     const int32_t contig = found ? 0 : -1;
     pl.status = rg_drop ? RS_RG_DROPPED : parse_skip ? RS_PARSE_SKIP : contig < 0 ? RS_NO_CONTIG : RS_LIVE;
     const bool live = pl.status == RS_LIVE;

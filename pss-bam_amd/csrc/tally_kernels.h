@@ -36,10 +36,11 @@
 //                 Counters leave LDS once, at kernel end, as plain stores into the workgroup's
 //                 slot of a scratch buffer; reduce_partials sums the slots into the u64 block.
 //
-//  tally_tiled_planes / tally_simple_planes<PLANES> (-G, -S): the same kernels with one table plane
+//  tally_tiled_planes / tally_simple_planes<PLANES> (-G, -S, -C): the same kernels with one table plane
 //                 per read group (PLANES_RG: record -> plane by its first RG:Z value,
-//                 read_group_plane) or per fragment-length bin (PLANES_LEN: by Plan::L,
-//                 length_bin_plane; prefixes are staged as without planes).
+//                 read_group_plane), per fragment-length bin (PLANES_LEN: by Plan::L,
+//                 length_bin_plane) or per contig set (PLANES_REF: by Plan::ref_plane, packed into
+//                 the ref_info entry plan_head loads anyway); -S and -C stage prefixes as without planes.
 //
 // Integer/byte work only: no MFMA anywhere (the bound is HBM bandwidth).
 #pragma once
@@ -267,12 +268,13 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyP
 }
 
 // What picks a read's table plane in tally_tiled_body: nothing (one plane), its first RG:Z value
-// (-G), or its length bin (-S).
-enum PlaneSel { PLANES_NONE = 0, PLANES_RG, PLANES_LEN };
+// (-G), its length bin (-S), or its contig's set (-C).
+enum PlaneSel { PLANES_NONE = 0, PLANES_RG, PLANES_LEN, PLANES_REF };
 
 template <PlaneSel PLANES, class Src>
 __device__ __forceinline__ uint32_t record_plane(const Src &src, const RecHdr &h, const Plan &pl, const PlaneParams &G) {
     if constexpr (PLANES == PLANES_RG) return read_group_plane(src, h, G);
+    else if constexpr (PLANES == PLANES_REF) return pl.ref_plane;   // from the ref_info entry plan_head loaded
     else return length_bin_plane(G, pl.L);
 }
 

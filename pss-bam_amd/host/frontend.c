@@ -31,6 +31,13 @@ int frontend_fast_exit = 0;
 int frontend_group_by_rg = 0;
 int frontend_n_length_edges = 0;
 uint32_t frontend_length_edges[PSSBAM_MAX_LENGTH_BINS - 1];
+const frontend_contig_map *frontend_contig_sets = NULL;
+
+/* -C: the map on one engine (0 when there is none) */
+static int send_contig_sets(pssbam_engine *e, const frontend_contig_map *m)
+{
+    return m ? pssbam_engine_set_contig_sets(e, m->n_labels, m->n_names, (const char *const *)m->names, m->set_of) : 0;
+}
 
 /* Start-up work that overlaps the caller's FASTA load.  The reference is serial by construction -- load the
  * genome, then loop over the alignments (pss-bam.c:751-783) -- but only the TALLY needs reference bases: a helper
@@ -55,6 +62,7 @@ static struct early_feed {
     int n_rg;
     int n_edges;                    /* -S: the length bin edges, set on every engine after create */
     uint32_t edges[PSSBAM_MAX_LENGTH_BINS - 1];
+    const frontend_contig_map *sets; /* -C: the map, set on every engine after create */
     int n_gpus, engines_ok, engines_done, fed, feed_rc, genome_set, failed;
     device_feed_stats dfs;
     char err[600];
@@ -129,7 +137,7 @@ static void *engine_make_main(void *arg)
     engine_make_job *j = (engine_make_job *)arg;
     if (pssbam_engine_create(&j->cfg, j->out) || pssbam_engine_feed_open(*j->out, j->n_ref, EF.fasta_bytes) ||
         (EF.n_rg > 0 && pssbam_engine_set_read_groups(*j->out, EF.n_rg, (const char *const *)EF.rg_ids)) ||
-        (EF.n_edges > 0 && pssbam_engine_set_length_bins(*j->out, EF.n_edges, EF.edges))) {
+        (EF.n_edges > 0 && pssbam_engine_set_length_bins(*j->out, EF.n_edges, EF.edges)) || send_contig_sets(*j->out, EF.sets)) {
         j->rc = 1;
         snprintf(j->err, sizeof j->err, "%s", pssbam_last_error());   /* (the message is this thread's) */
     }
@@ -255,6 +263,7 @@ void frontend_warmup_start(const pssbam_config *cfg, const char *aln_path, const
             EF.cfg = *cfg;
             EF.n_edges = frontend_n_length_edges;
             memcpy(EF.edges, frontend_length_edges, sizeof EF.edges);
+            EF.sets = frontend_contig_sets;
             EF.cfg.pss.up_ctx = EF.up = dup_or_null(cfg->pss.up_ctx);
             EF.cfg.pss.down_ctx = EF.down = dup_or_null(cfg->pss.down_ctx);
             EF.cfg.read_group = EF.rg = dup_or_null(cfg->read_group);
@@ -268,10 +277,10 @@ void frontend_warmup_start(const pssbam_config *cfg, const char *aln_path, const
 
 static int same_str(const char *a, const char *b) { return (!a && !b) || (a && b && strcmp(a, b) == 0); }
 
-/* the helper's engines carry the length bins that were set when it started */
+/* the helper's engines carry the length bins and contig sets that were set when it started */
 static int same_length_bins(void)
 {
-    return EF.n_edges == frontend_n_length_edges &&
+    return EF.n_edges == frontend_n_length_edges && EF.sets == frontend_contig_sets &&
            memcmp(EF.edges, frontend_length_edges, (size_t)frontend_n_length_edges * sizeof *EF.edges) == 0;
 }
 
@@ -427,6 +436,46 @@ static int send_read_groups(pssbam_engine **eng, int n_gpus, const char *text, s
     return 0;
 }
 
+static int cmp_str_ptr(const void *a, const void *b) { return strcmp(*(const char *const *)a, *(const char *const *)b); }
+
+/* -C: a label whose contigs cannot receive a read -- none of them is both a reference of the input (or "*", the
+ * RNAME of refID -1) and a contig of the genome -- gets all-zero tables: one warning line each */
+static void warn_unreached_sets(const frontend_contig_map *m, const Genome *genome, int32_t n_ref, const char *const *ref_names,
+                                const char *aln_path)
+{
+    const char **refs = (const char **)malloc(((size_t)n_ref + 1) * sizeof *refs);
+    char *reached = (char *)calloc((size_t)m->n_labels, 1);
+    if (!refs || !reached) {
+        free(refs);
+        free(reached);
+        return;
+    }
+    for (int32_t i = 0; i < n_ref; i++) refs[i] = ref_names[i];
+    qsort(refs, (size_t)n_ref, sizeof *refs, cmp_str_ptr);
+    for (int k = 0; k < m->n_names; k++) {
+        const char *nm = m->names[k];
+        if (reached[m->set_of[k]]) continue;
+        const int in_input = strcmp(nm, "*") == 0 || bsearch(&nm, refs, (size_t)n_ref, sizeof *refs, cmp_str_ptr) != NULL;
+        /* Genome.seqs is sorted by strcmp of the ids (the find_seq order) */
+        size_t lo = 0, hi = genome ? genome->n_seqs : 0;
+        int in_genome = 0;
+        while (in_input && lo < hi && !in_genome) {
+            const size_t mid = (lo + hi) / 2;
+            const int c = strcmp(nm, genome->seqs[mid]->id);
+            if (c == 0) in_genome = 1;
+            else if (c < 0) hi = mid;
+            else lo = mid + 1;
+        }
+        reached[m->set_of[k]] = (char)in_genome;
+    }
+    for (int s = 0; s < m->n_labels; s++)
+        if (!reached[s])
+            fprintf(stderr, "Warning: -C: no contig of label %s is both a reference of %s and in the FASTA; its tables are all zero.\n",
+                    m->labels[s], aln_path);
+    free(refs);
+    free(reached);
+}
+
 int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, int n_gpus, run_result *res)
 {
     pssbam_engine *eng[64] = {0};
@@ -556,7 +605,8 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             const int have = pssbam_device_count();
             c.device = have > 0 ? g % have : g;
             if (pssbam_engine_create(&c, &eng[g]) ||
-                (frontend_n_length_edges > 0 && pssbam_engine_set_length_bins(eng[g], frontend_n_length_edges, frontend_length_edges))) {
+                (frontend_n_length_edges > 0 && pssbam_engine_set_length_bins(eng[g], frontend_n_length_edges, frontend_length_edges)) ||
+                send_contig_sets(eng[g], frontend_contig_sets)) {
                 fprintf(stderr, "Error: GPU engine %d: %s\n", g, pssbam_last_error());
                 goto done;
             }
@@ -734,6 +784,11 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
         goto done;
     }
     if (frontend_n_length_edges > 0) res->n_planes = frontend_n_length_edges + 1; /* -G: set with the IDs */
+    if (frontend_contig_sets) {
+        res->n_planes = frontend_contig_sets->n_labels;
+        warn_unreached_sets(frontend_contig_sets, genome, rd ? bam_reader_header(rd)->n_ref : sam_reader_n_ref(sd),
+                            rd ? (const char *const *)bam_reader_header(rd)->ref_name : sam_reader_ref_names(sd), aln_path);
+    }
     if (res->n_planes > 0) {
         const size_t cells = (size_t)(cfg->pss.region_len + 2) * 16;
         res->plane_fwd = (unsigned long *)calloc(cells * (size_t)res->n_planes, sizeof(unsigned long));

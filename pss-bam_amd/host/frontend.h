@@ -14,8 +14,9 @@ typedef struct run_result {
     uint64_t stats[PSSBAM_ST_N];
     double inflate_s, total_s;
     int n_gpus;
-    /* pss-bam -G / -S: the tables of each plane of the engine, (region_len+2)*16 per plane; plane k is the header's
-     * k-th @RG ID (frontend_group_by_rg, group_ids[k]) or length bin k (frontend_length_edges, group_ids NULL) */
+    /* pss-bam -G / -S / -C: the tables of each plane of the engine, (region_len+2)*16 per plane; plane k is the
+     * header's k-th @RG ID (frontend_group_by_rg, group_ids[k]), length bin k (frontend_length_edges, group_ids
+     * NULL) or the k-th label of frontend_contig_sets (group_ids NULL) */
     int n_planes;
     char **group_ids;
     unsigned long *plane_fwd, *plane_rev;
@@ -30,6 +31,17 @@ extern int frontend_group_by_rg;
  * frontend_warmup_start. */
 extern int frontend_n_length_edges;
 extern uint32_t frontend_length_edges[PSSBAM_MAX_LENGTH_BINS - 1];
+
+/* pss-bam -C: the contig -> set map (contig_sets.h; NULL: none); every engine gets it
+ * (pssbam_engine_set_contig_sets) and run_tally() returns one pair of tables per label, and warns on stderr
+ * about a label none of whose contigs is both in the input's references and in the genome.  Set before
+ * frontend_warmup_start. */
+typedef struct frontend_contig_map {
+    int n_names, n_labels;
+    char **names, **labels;
+    int32_t *set_of;
+} frontend_contig_map;
+extern const frontend_contig_map *frontend_contig_sets;
 
 /* Streams every alignment of `aln_path` (BGZF BAM, or SAM text plain/gzip) through engines built from `cfg` on
  * n_gpus devices (batches dealt round-robin), sums the counter blocks onto device 0 with

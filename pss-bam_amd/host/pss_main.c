@@ -13,6 +13,11 @@
  * Added: -S e1,...,ek writes, beside the tables of all reads, one pair of tables per fragment-length bin
  * [l, e1-1], [e1, e2-1], ..., [ek, L] (<prefix>.len<lo>-<hi>.pss.*.txt), each the same as
  * `-l <lo> -L <hi> -o <prefix>.len<lo>-<hi>` would write -- again from one pass over the input.
+ * Added: -C <map file> writes, beside the tables of all reads, one pair of tables per label of the map
+ * (lines "<contig name>[<blanks><label>]", contig_sets.h; <prefix>.<label>.pss.*.txt, the label file-name
+ * encoded like an -G ID), each the same as a run with -F reduced to the label's contigs would write (the
+ * reference skips every read whose RNAME its FASTA lacks) -- one pass instead of one run per organism, per
+ * mtDNA / nuclear / X / Y split.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -23,6 +28,7 @@
 #include <string.h>
 #include <unistd.h>
 
+#include "contig_sets.h"
 #include "fasta-genome-io.h"
 #include "frontend.h"
 #include "length_bins.h"
@@ -38,9 +44,9 @@ int main(int argc, char *argv[])
     unsigned long min_read_len = 0, max_read_len = 250000000;
     const char *up_ctx = "ACGT", *down_ctx = "ACGT";
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL, *read_group = NULL;
-    const char *len_edges = NULL;
+    const char *len_edges = NULL, *ctg_map = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -54,6 +60,7 @@ int main(int argc, char *argv[])
         case 'm': merged_only = 1; break;
         case 'G': by_group = 1; break;
         case 'S': len_edges = optarg; break;
+        case 'C': ctg_map = optarg; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -107,6 +114,41 @@ int main(int argc, char *argv[])
             exit(1);
         }
     }
+    frontend_contig_map sets;
+    memset(&sets, 0, sizeof sets);
+    if (ctg_map) {
+        if (by_group || len_edges) {
+            fprintf(stderr, "-C (tables per contig set) and %s exclude each other.\n",
+                    by_group ? "-G (tables per read group)" : "-S (tables per length bin)");
+            exit(1);
+        }
+        FILE *mf = fopen(ctg_map, "rb");
+        char *text = NULL;
+        size_t len = 0, cap = 0;
+        int read_ok = mf != NULL;
+        while (read_ok) {
+            if (len == cap) {
+                char *t = (char *)realloc(text, cap = cap ? 2 * cap : 65536);
+                if (!t) { read_ok = 0; break; }
+                text = t;
+            }
+            const size_t got = fread(text + len, 1, cap - len, mf);
+            len += got;
+            if (got == 0) { read_ok = !ferror(mf); break; }
+        }
+        if (mf) fclose(mf);
+        if (!read_ok) {
+            fprintf(stderr, "-C: unable to read the map file %s.\n", ctg_map);
+            exit(1);
+        }
+        char err[600];
+        sets.n_names = pss_parse_contig_sets(text, len, &sets.names, &sets.set_of, &sets.labels, &sets.n_labels, err, sizeof err);
+        free(text);
+        if (sets.n_names < 0) {
+            fprintf(stderr, "%s (%s)\n", err, ctg_map);
+            exit(1);
+        }
+    }
 
     /* "Full command" banner: four shapes, as the reference prints them (pss-bam.c:728-749) */
     fprintf(stderr, "Full command: %s -F %s -B %s -o %s -r %d -l %lu -L %lu -q %d", argv[0], fasta_fn, bam_fn,
@@ -114,6 +156,7 @@ int main(int argc, char *argv[])
     if (read_group) fprintf(stderr, " -R %s", read_group);
     fprintf(stderr, " -U %s -D %s%s%s", up_ctx, down_ctx, merged_only ? " -m" : "", by_group ? " -G" : "");
     if (len_edges) fprintf(stderr, " -S %s", len_edges);
+    if (ctg_map) fprintf(stderr, " -C %s", ctg_map);
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -134,6 +177,7 @@ int main(int argc, char *argv[])
     frontend_group_by_rg = by_group;
     frontend_n_length_edges = n_edges;
     memcpy(frontend_length_edges, edges, (size_t)n_edges * sizeof *edges);
+    if (ctg_map) frontend_contig_sets = &sets;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
      * load; only the tally launches wait for the genome (frontend.c) */
@@ -159,16 +203,18 @@ int main(int argc, char *argv[])
     pss_write_rates(fasta_fn, bam_fn, out_prefix, region_len, fwd_rates, rev_rates);
     if (by_group && res.n_planes == 0)
         fprintf(stderr, "Warning: -G: the header of %s has no @RG line; only the tables of all reads were written.\n", bam_fn);
-    /* <prefix>.<tag>: what `-R <ID> -o <prefix>.<ID>` (-G) or `-l <lo> -L <hi> -o <prefix>.len<lo>-<hi>` (-S) writes */
+    /* <prefix>.<tag>: what `-R <ID> -o <prefix>.<ID>` (-G), `-l <lo> -L <hi> -o <prefix>.len<lo>-<hi>` (-S) or -F
+     * reduced to the label's contigs with `-o <prefix>.<label>` (-C) writes */
     for (int k = 0; k < res.n_planes; k++) {
         const size_t cells = (size_t)(region_len + 2) * 16;
         unsigned long lo = 0, hi = 0;
-        if (!by_group) pss_length_bin_bounds(edges, n_edges, k, min_read_len, max_read_len, &lo, &hi);
-        const size_t tag_len = by_group ? pss_rg_file_tag(res.group_ids[k], NULL, 0) : pss_length_bin_tag(lo, hi, NULL, 0);
+        if (len_edges) pss_length_bin_bounds(edges, n_edges, k, min_read_len, max_read_len, &lo, &hi);
+        const char *id = by_group ? res.group_ids[k] : ctg_map ? sets.labels[k] : NULL;   /* file-name encoded */
+        const size_t tag_len = id ? pss_rg_file_tag(id, NULL, 0) : pss_length_bin_tag(lo, hi, NULL, 0);
         char *pprefix = (char *)malloc(strlen(out_prefix) + tag_len + 2);
         if (!pprefix) { fprintf(stderr, "Error: out of memory\n"); exit(1); }
         char *tag = pprefix + sprintf(pprefix, "%s.", out_prefix);
-        if (by_group) pss_rg_file_tag(res.group_ids[k], tag, tag_len + 1);
+        if (id) pss_rg_file_tag(id, tag, tag_len + 1);
         else pss_length_bin_tag(lo, hi, tag, tag_len + 1);
         pss_sub_rates(region_len, res.plane_fwd + k * cells, fwd_rates);
         pss_sub_rates(region_len, res.plane_rev + k * cells, rev_rates);
@@ -195,6 +241,7 @@ int main(int argc, char *argv[])
     free(fwd_rates);
     free(rev_rates);
     run_result_free(&res);
+    if (ctg_map) pss_free_contig_sets(sets.names, sets.n_names, sets.set_of, sets.labels, sets.n_labels);
     destroy_genome(genome);
     free(fasta_fn);
     free(bam_fn);
