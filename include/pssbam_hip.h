@@ -188,7 +188,7 @@ int pssbam_engine_reset(pssbam_engine *e);
  * RG:Z aux field equals ids[g] byte for byte -- exactly the records `-R ids[g]` keeps -- and to the unassigned
  * bucket otherwise (no RG:Z, or a value no ID matches).  Legal after create (or reset) and before the first
  * tally launch; with pssbam_engine_feed_open that is any time before set_references.  PSSBAM_EINVAL with
- * cfg.read_group or PSSBAM_TALLY_KMER set, PSSBAM_ESTATE once records have been tallied or the counter block
+ * cfg.read_group set or with PSSBAM_TALLY_PSS | PSSBAM_TALLY_KMER together, PSSBAM_ESTATE once records have been tallied or the counter block
  * has been bound.  The table survives pssbam_engine_reset.  pssbam_engine_finish keeps returning the totals
  * over every record. */
 int pssbam_engine_set_read_groups(pssbam_engine *e, int32_t n, const char *const *ids);
@@ -198,6 +198,22 @@ int pssbam_engine_set_read_groups(pssbam_engine *e, int32_t n, const char *const
  * holds the records on contigs no set lists. */
 int pssbam_engine_finish_groups(pssbam_engine *e, int32_t group, unsigned long *fwd, unsigned long *rev);
 
+/* K-mer planes (fragkon -G / -S / -C).  An engine whose tally_mask is PSSBAM_TALLY_KMER alone takes the three
+ * setters as well, one at a time and under the same ordering rules; each plane is then one [k5 | k3] pair of 4^klen
+ * bins instead of a pair of substitution tables.  Read groups and contig sets pick the plane as above.  Length
+ * bins go by the length fragkon's -l / -L compare, the SEQ length for paired reads too (not |TLEN|), and their
+ * edges are checked against cfg.kmer.min_read_len / max_read_len: bin k holds what `fragkon -l <bin start>
+ * -L <bin end>` tallies.  The 5' and the 3' add of one record go to the same plane, each on its own.  The counter
+ * block grows by n planes of 2 * 4^klen words; when that does not fit the device's free memory the setter returns
+ * PSSBAM_ENOMEM.  pssbam_engine_finish keeps returning the totals over every plane and the status counters of the
+ * same engine without planes.  With PSSBAM_TALLY_PSS | PSSBAM_TALLY_KMER together every setter stays PSSBAM_EINVAL.
+ *
+ * Drains the engine like pssbam_engine_finish and copies one plane's two tables (4^klen each, either pointer may
+ * be NULL): group -1 is plane 0 (the unassigned bucket; all zeros with length bins), 0..n-1 as for
+ * pssbam_engine_finish_groups.  PSSBAM_EINVAL on an engine that tallies substitution tables, as
+ * pssbam_engine_finish_groups is on a k-mer engine. */
+int pssbam_engine_finish_kmer_groups(pssbam_engine *e, int32_t group, uint64_t *k5, uint64_t *k3);
+
 /* Length bins (pss-bam -S): one set of substitution tables per fragment-length bin in a single pass over the
  * records, instead of one `-l <lo> -L <hi>` run per window.  edges[0..n_edges-1], n_edges in
  * 1..PSSBAM_MAX_LENGTH_BINS-1, must rise strictly with cfg.pss.min_read_len < edges[0] and
@@ -206,7 +222,7 @@ int pssbam_engine_finish_groups(pssbam_engine *e, int32_t group, unsigned long *
  * length -l / -L compare (|TLEN| for paired reads, else the SEQ length), so bin k holds exactly what
  * `-l <bin start> -L <bin end>` tallies.  Legal after create (or reset) and before the first tally launch, like
  * pssbam_engine_set_read_groups, and allowed with cfg.read_group (bins of one read group).  PSSBAM_EINVAL with
- * PSSBAM_TALLY_KMER, with read groups set or with bad edges, PSSBAM_ESTATE once records have been tallied or the
+ * PSSBAM_TALLY_PSS | PSSBAM_TALLY_KMER together, with read groups set or with bad edges, PSSBAM_ESTATE once records have been tallied or the
  * counter block has been bound.  The bins survive pssbam_engine_reset; pssbam_engine_finish keeps returning the
  * totals over every bin, pssbam_engine_finish_groups(e, k, ...) returns bin k. */
 int pssbam_engine_set_length_bins(pssbam_engine *e, int32_t n_edges, const uint32_t *edges);
@@ -221,7 +237,7 @@ int pssbam_engine_set_length_bins(pssbam_engine *e, int32_t n_edges, const uint3
  * table, so the call is legal before and after set_references (a later set_references, e.g. of the SAM-text
  * reader as new RNAMEs show up, applies it again).  Otherwise legal and illegal as
  * pssbam_engine_set_read_groups: after create (or reset) and before the first tally launch, allowed with
- * cfg.read_group; PSSBAM_EINVAL with PSSBAM_TALLY_KMER, with read groups or length bins set, or with bad
+ * cfg.read_group; PSSBAM_EINVAL with PSSBAM_TALLY_PSS | PSSBAM_TALLY_KMER together, with read groups or length bins set, or with bad
  * arguments, PSSBAM_ESTATE once records have been tallied or the counter block has been bound.  The sets
  * survive pssbam_engine_reset; pssbam_engine_finish keeps returning the totals over every record,
  * pssbam_engine_finish_groups(e, s, ...) returns set s. */
@@ -232,10 +248,12 @@ int pssbam_engine_set_contig_sets(pssbam_engine *e, int32_t n_sets, int64_t n_na
  * n_u64 64-bit words, for a caller-side RCCL reduce across GPUs (sum, uint64).  With read groups it is
  * [fwd | rev | stats | fwd_0 | rev_0 | ... | fwd_n-1 | rev_n-1]: the leading fwd | rev are the unassigned
  * bucket, group g's pair ((region_len+2)*16 words each) starts at 2*(region_len+2)*16 + PSSBAM_ST_N +
- * g*2*(region_len+2)*16 (the k-mer tables are empty: read groups exclude PSSBAM_TALLY_KMER).  With length bins the
+ * g*2*(region_len+2)*16 (a PSSBAM_TALLY_PSS engine has no k-mer tables).  With length bins the
  * layout is the same with bin k in group k's place, and the leading fwd | rev stay zero.  With contig sets it is
- * the same with set s in group s's place, the leading fwd | rev the records on unlisted contigs.  The block is
- * still summed across GPUs as one u64 array. */
+ * the same with set s in group s's place, the leading fwd | rev the records on unlisted contigs.  A k-mer engine
+ * with planes holds [k5 | k3 | stats | k5_0 | k3_0 | ... | k5_n-1 | k3_n-1]: the leading pair is plane 0, plane g's
+ * pair (4^klen words each) starts at 2*4^klen + PSSBAM_ST_N + g*2*4^klen -- offsets that pass 2^32 words at large
+ * klen.  The block is still summed across GPUs as one u64 array. */
 int pssbam_engine_counters_device(pssbam_engine *e, void **d_counters, size_t *n_u64);
 
 /* Makes the engine accumulate into caller-owned device memory (n_u64 words, as reported

@@ -41,7 +41,7 @@ HIP_SYMBOLS = [
     "pssbam_engine_feed_status", "pssbam_engine_feed_break", "pssbam_engine_feed_handoff", "pssbam_feed_reserve", "pssbam_engine_hint_records",
     "pssbam_engine_set_genome_async", "pssbam_engine_genome_wait", "pssbam_engine_feed_open", "pssbam_feed_release",
     "pssbam_engine_set_read_groups", "pssbam_engine_finish_groups", "pssbam_engine_set_length_bins",
-    "pssbam_engine_set_contig_sets",
+    "pssbam_engine_set_contig_sets", "pssbam_engine_finish_kmer_groups",
 ]
 MAX_READ_GROUPS = 4096
 MAX_LENGTH_BINS = 64
@@ -107,6 +107,7 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_reset.argtypes = [C.c_void_p]
     L.pssbam_engine_set_read_groups.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p)]
     L.pssbam_engine_finish_groups.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.pssbam_engine_finish_kmer_groups.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_length_bins.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)]
     L.pssbam_engine_set_contig_sets.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]
     L.pssbam_engine_counters_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
@@ -178,7 +179,9 @@ class Engine:
     `kmer` = dict(klen, min_mq, min_read_len, max_read_len, merged_only).
     `read_groups` = @RG IDs (pss-bam -G): one set of substitution tables per ID, see set_read_groups.
     `length_bins` = length bin edges (pss-bam -S): one set of substitution tables per bin, see set_length_bins.
-    `contig_sets` = contig sets (pss-bam -C): one set of substitution tables per label, see set_contig_sets."""
+    `contig_sets` = contig sets (pss-bam -C): one set of substitution tables per label, see set_contig_sets.
+    With `kmer` alone (no `pss`) the three split the k-mer tables instead (fragkon -G / -S / -C): every plane is a
+    k5 / k3 pair, and the length bins go by the SEQ length and kmer's min_read_len / max_read_len."""
 
     def __init__(self, pss: dict | None = None, kmer: dict | None = None, read_group: str | None = None,
                  kernel: int = KERNEL_AUTO, device: int = -1, read_groups: list[str] | None = None,
@@ -200,6 +203,8 @@ class Engine:
             cfg.kmer = _KmerOpts(kmer.get("klen", 8), kmer.get("min_mq", 0), kmer.get("min_read_len", 0),
                                  kmer.get("max_read_len", 250000000), int(kmer.get("merged_only", False)))
             self.klen = cfg.kmer.klen
+            if pss is None:
+                self._len_range = (cfg.kmer.min_read_len, cfg.kmer.max_read_len)
         self.has_pss, self.has_kmer = pss is not None, kmer is not None
         if read_group is not None:
             rg = read_group.encode()
@@ -238,7 +243,7 @@ class Engine:
         self.contig_sets = labels
 
     def finish_sets(self) -> dict:
-        """{label: Tables} per contig set, in set order (fwd / rev only; drains like finish)"""
+        """{label: Tables} per contig set, in set order (fwd / rev, or k5 / k3 on a k-mer engine; drains like finish)"""
         return self._finish_planes(enumerate(self.contig_sets))
 
     def set_length_bins(self, edges: list[int]):
@@ -260,17 +265,25 @@ class Engine:
         self.read_groups = [i.decode() if isinstance(i, bytes) else i for i in ids]
 
     def finish_groups(self) -> dict:
-        """{ID: Tables, ..., None: Tables of the unassigned bucket} (fwd / rev only; drains like finish)"""
+        """{ID: Tables, ..., None: Tables of the unassigned bucket} (fwd / rev, or k5 / k3 on a k-mer engine; drains
+        like finish)"""
         return self._finish_planes([(-1, None)] + list(enumerate(self.read_groups)))
 
     def finish_bins(self) -> dict:
-        """{(lo, hi): Tables} per length bin (fwd / rev only; drains like finish)"""
+        """{(lo, hi): Tables} per length bin (fwd / rev, or k5 / k3 on a k-mer engine; drains like finish)"""
         return self._finish_planes(enumerate(self.length_bins))
 
     def _finish_planes(self, planes) -> dict:
         """{key: Tables} for (plane, key) pairs of pssbam_engine_finish_groups; a repeated key keeps its first plane"""
         out = {}
         for g, key in planes:
+            if not self.has_pss:   # k-mer planes
+                k5 = np.zeros(4 ** self.klen, dtype=np.uint64)
+                k3 = np.zeros_like(k5)
+                _chk(self._L.pssbam_engine_finish_kmer_groups(self._h, g, k5.ctypes.data, k3.ctypes.data))
+                if key not in out:
+                    out[key] = Tables(None, None, k5, k3, {})
+                continue
             fwd = np.zeros((self.region_len + 2, 16), dtype=np.uint64)
             rev = np.zeros_like(fwd)
             _chk(self._L.pssbam_engine_finish_groups(self._h, g, fwd.ctypes.data, rev.ctypes.data))
@@ -455,6 +468,12 @@ class Engine:
                "stats": 2 * rows * 16 + 2 * nb, "rows": rows, "bins": nb}
         # read groups: plane 0 (the unassigned bucket) is fwd / rev above; group g's [fwd | rev] pair follows the stats
         base = lay["stats"] + ST_N
+        if not self.has_pss:   # k-mer planes: plane 0 is k5 / k3 above; plane k's [k5 | k3] pair follows the stats
+            for name, tag, keys in (("groups", "id", self.read_groups), ("length_bins", "bin", self.length_bins),
+                                    ("contig_sets", "label", self.contig_sets)):
+                lay[name] = [{tag: key, "k5": base + k * 2 * nb, "k3": base + k * 2 * nb + nb} for k, key in enumerate(keys)]
+            lay["n_u64"] = base + (len(self.read_groups) + len(self.length_bins) + len(self.contig_sets)) * 2 * nb
+            return lay
         lay["groups"] = [{"id": g, "fwd": base + k * 2 * rows * 16, "rev": base + k * 2 * rows * 16 + rows * 16}
                          for k, g in enumerate(self.read_groups)]
         # length bins: bin k's pair sits where group k's would (plane 0 stays empty)

@@ -160,6 +160,7 @@ enum PrepSlot {
     PREP_COMPACT, PREP_COMPACT_KMER, PREP_COMPACT_KMER_LDS,
     PREP_COMPACT_ONCE, PREP_COMPACT_ONCE_KMER, PREP_COMPACT_ONCE_KMER_LDS, PREP_COMPACT_DECODE_TWICE,
     PREP_PLANES_RG, PREP_PLANES_RG_LATER, PREP_PLANES_LEN, PREP_PLANES_LEN_LATER, PREP_PLANES_REF, PREP_PLANES_REF_LATER,
+    PREP_KPLANES_RG, PREP_KPLANES_RG_LDS, PREP_KPLANES_LEN, PREP_KPLANES_LEN_LDS, PREP_KPLANES_REF, PREP_KPLANES_REF_LDS,
     PREP_N
 };
 
@@ -210,6 +211,7 @@ struct pssbam_engine {
     // (pssbam_engine_set_contig_sets)
     PlaneSel planes = PLANES_NONE;
     uint32_t n_planes = 0, off_groups = 0, plane_words = 0;
+    uint64_t kplane_words = 0;   // a k-mer engine's plane: one [k5 | k3] pair, 2 * 4^k words (64-bit: 2^31 at k = 15)
     uint8_t *d_grp_ids = nullptr;   // -G: the ID table
     uint32_t *d_grp_offs = nullptr, *d_grp_hash = nullptr;
     uint32_t grp_hash_mask = 0;
@@ -385,6 +387,7 @@ extern "C" int pssbam_engine_create(const pssbam_config *cfg, pssbam_engine **ou
     e->n_counters = (size_t)e->off_stats + PSSBAM_ST_N;
     e->plane_words = 2u * e->rows * 16u;
     e->off_groups = (uint32_t)e->n_counters;
+    e->kplane_words = cfg->tally_mask == PSSBAM_TALLY_KMER ? 2ull * e->n_bins : 0ull;
     HIP_TRY(hipMalloc(&e->d_counters_own, e->n_counters * sizeof(unsigned long long)));
     e->d_counters = e->d_counters_own;
     HIP_TRY(hipMemsetAsync(e->d_counters, 0, e->n_counters * sizeof(unsigned long long), e->stream));
@@ -778,6 +781,22 @@ static int launch_planes(pssbam_engine *e, TallyParams &P, const PlaneParams &G,
     return PSSBAM_OK;
 }
 
+// One plane pass of tally_tiled_kmer_planes and its reduce_partials_kmer_planes
+template <PlaneSel SEL, bool LDS_KMER>
+static int launch_kmer_planes(pssbam_engine *e, TallyParams &P, const PlaneParams &G, uint32_t lds, uint32_t n_tiles) {
+    constexpr PrepSlot slot = SEL == PLANES_RG  ? (LDS_KMER ? PREP_KPLANES_RG_LDS : PREP_KPLANES_RG)
+                            : SEL == PLANES_LEN ? (LDS_KMER ? PREP_KPLANES_LEN_LDS : PREP_KPLANES_LEN)
+                                                : (LDS_KMER ? PREP_KPLANES_REF_LDS : PREP_KPLANES_REF);
+    uint32_t grid = 0;
+    const int rc = tiled_grid(e, slot, tally_tiled_kmer_planes<SEL, LDS_KMER>, lds, n_tiles, G.scratch_words, &grid);
+    if (rc != PSSBAM_OK) return rc;
+    P.scratch = e->d_scratch;
+    hipLaunchKernelGGL((tally_tiled_kmer_planes<SEL, LDS_KMER>), dim3(grid), dim3(TILED_THREADS), lds, e->stream, P, G);
+    hipLaunchKernelGGL(reduce_partials_kmer_planes, dim3((G.scratch_words * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream, P, G, grid,
+                       (uint32_t)(LDS_KMER ? 1 : 0));
+    return PSSBAM_OK;
+}
+
 // How many 16-byte pieces of a record the tiled kernel must stage so that everything the path
 // reads (through QUAL[0]; the whole record when the -R filter walks the aux fields) is in LDS
 // for typical records: sampled from the first records of a block.  Records that need more take
@@ -815,6 +834,8 @@ static PlaneParams plane_params(const pssbam_engine *e) {
     G.n_slots = e->n_planes + 1u;
     G.plane_words = e->plane_words;
     G.off_groups = e->off_groups;
+    G.koff_planes = e->off_groups;
+    G.kplane_words = e->kplane_words;
     G.n_edges = (uint32_t)e->len_edges.size();
     std::copy(e->len_edges.begin(), e->len_edges.end(), G.edges);
     return G;
@@ -898,7 +919,11 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         const bool lds_tab = do_pss && tab_bytes <= 60u * 1024u;
         uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n_records + 255) / 256, (uint64_t)e->n_cu * 8);
         if (e->env_simple_blocks > 0) blocks = (uint32_t)e->env_simple_blocks;
-        if (e->planes == PLANES_RG) hipLaunchKernelGGL(tally_simple_planes<PLANES_RG>, dim3(blocks), dim3(256), 0, e->stream, P, G);
+        if (e->planes != PLANES_NONE && !do_pss) {   // k-mer planes
+            if (e->planes == PLANES_RG) hipLaunchKernelGGL(tally_simple_kmer_planes<PLANES_RG>, dim3(blocks), dim3(256), 0, e->stream, P, G);
+            else if (e->planes == PLANES_LEN) hipLaunchKernelGGL(tally_simple_kmer_planes<PLANES_LEN>, dim3(blocks), dim3(256), 0, e->stream, P, G);
+            else hipLaunchKernelGGL(tally_simple_kmer_planes<PLANES_REF>, dim3(blocks), dim3(256), 0, e->stream, P, G);
+        } else if (e->planes == PLANES_RG) hipLaunchKernelGGL(tally_simple_planes<PLANES_RG>, dim3(blocks), dim3(256), 0, e->stream, P, G);
         else if (e->planes == PLANES_LEN) hipLaunchKernelGGL(tally_simple_planes<PLANES_LEN>, dim3(blocks), dim3(256), 0, e->stream, P, G);
         else if (e->planes == PLANES_REF) hipLaunchKernelGGL(tally_simple_planes<PLANES_REF>, dim3(blocks), dim3(256), 0, e->stream, P, G);
         else if (lds_tab) hipLaunchKernelGGL(tally_simple<true>, dim3(blocks), dim3(256), tab_bytes, e->stream, P);
@@ -961,7 +986,33 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         const uint32_t lds = tiled_lds_bytes(T, pieces);
         int rc = PSSBAM_OK;
         P.row_base = 0;
-        if (e->planes != PLANES_NONE) {
+        if (e->planes != PLANES_NONE && !do_pss) {
+            // k-mer planes.  k <= KMER_LDS_MAX_K: a plane pass holds as many 2 * 4^k-word histograms (plus the trash slot) as
+            // fit the LDS beside the staging buffer -- 2 KiB each at k = 4, so 64 bins and plane 0 are one pass -- and more
+            // planes take more passes, each re-reading the records.  Larger k: global atomics, one pass whatever the count.
+            using LaunchK = int (*)(pssbam_engine *, TallyParams &, const PlaneParams &, uint32_t, uint32_t);
+            static constexpr LaunchK launch_k[3][2] = {{launch_kmer_planes<PLANES_RG, false>, launch_kmer_planes<PLANES_RG, true>},
+                                                       {launch_kmer_planes<PLANES_LEN, false>, launch_kmer_planes<PLANES_LEN, true>},
+                                                       {launch_kmer_planes<PLANES_REF, false>, launch_kmer_planes<PLANES_REF, true>}};
+            const uint32_t n_planes = G.n_groups + 1u;
+            if (kmer_lds) {
+                const uint32_t hist = 2u * (1u << (2 * c.kmer.klen)) * 4u;   // bytes of one plane's histogram
+                const uint32_t fit = lds + 2u * hist <= KMER_PLANES_LDS_BUDGET ? (KMER_PLANES_LDS_BUDGET - lds) / hist - 1u : 1u;
+                uint32_t per_pass = std::min(n_planes, fit);
+                if (e->env_group_slots > 0) per_pass = std::min(per_pass, (uint32_t)e->env_group_slots);
+                for (uint32_t plane0 = 0; plane0 < n_planes && rc == PSSBAM_OK; plane0 += per_pass) {
+                    G.plane0 = plane0;
+                    G.n_slots = std::min(per_pass, n_planes - plane0);
+                    G.scratch_words = GROUP_SCRATCH_DELTA + G.n_slots * (hist / 4u);
+                    rc = launch_k[e->planes - PLANES_RG][1](e, P, G, tiled_kmer_planes_lds_bytes(T, pieces, G.n_slots, c.kmer.klen, true), n_tiles);
+                }
+            } else {
+                G.plane0 = 0;
+                G.n_slots = n_planes;
+                G.scratch_words = GROUP_SCRATCH_DELTA;
+                rc = launch_k[e->planes - PLANES_RG][0](e, P, G, lds, n_tiles);
+            }
+        } else if (e->planes != PLANES_NONE) {
             // -G / -S / -C: every (32-row pass, plane pass) pair is one launch over the block.  A plane pass holds
             // as many planes as fit the LDS beside the staging buffer (8 planes = 32 KiB always do: one pass for
             // up to 7 groups or sets, or 6 bins -- plane 0 of -S stays empty but keeps its slot); more planes take
@@ -1200,6 +1251,9 @@ extern "C" int pssbam_engine_finish(pssbam_engine *e, unsigned long *fwd, unsign
     // -G / -S: the totals are every plane's sum (plane 0, the unassigned bucket, sits where an ungrouped engine keeps its tables)
     for (size_t g = 0; g < e->n_planes; g++)
         for (size_t i = 0; i < 2 * tab; i++) h[i] += h[e->off_groups + g * e->plane_words + i];
+    // k-mer planes: the same for the leading [k5 | k3]
+    for (size_t g = 0; g < e->n_planes && e->kplane_words; g++)
+        for (uint64_t i = 0; i < e->kplane_words; i++) h[e->off_k5 + i] += h[(uint64_t)e->off_groups + g * e->kplane_words + i];
     if (fwd) for (size_t i = 0; i < tab; i++) fwd[i] = (unsigned long)h[i];
     if (rev) for (size_t i = 0; i < tab; i++) rev[i] = (unsigned long)h[e->off_rev + i];
     if (k5) for (uint64_t i = 0; i < e->n_bins; i++) k5[i] = h[e->off_k5 + i];
@@ -1210,6 +1264,7 @@ extern "C" int pssbam_engine_finish(pssbam_engine *e, unsigned long *fwd, unsign
 
 extern "C" int pssbam_engine_finish_groups(pssbam_engine *e, int32_t group, unsigned long *fwd, unsigned long *rev) {
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (e->cfg.tally_mask == PSSBAM_TALLY_KMER) return fail(PSSBAM_EINVAL, "a k-mer engine's planes are read with pssbam_engine_finish_kmer_groups");
     const int32_t n_planes = (int32_t)e->n_planes;
     if (!n_planes) return fail(PSSBAM_ESTATE, "none of pssbam_engine_set_read_groups / _set_length_bins / _set_contig_sets has been called");
     if (group < -1 || group >= n_planes) return fail(PSSBAM_EINVAL, "group %d outside -1..%d", group, n_planes - 1);
@@ -1224,15 +1279,40 @@ extern "C" int pssbam_engine_finish_groups(pssbam_engine *e, int32_t group, unsi
     return PSSBAM_OK;
 }
 
+extern "C" int pssbam_engine_finish_kmer_groups(pssbam_engine *e, int32_t group, uint64_t *k5, uint64_t *k3) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (e->cfg.tally_mask != PSSBAM_TALLY_KMER) return fail(PSSBAM_EINVAL, "only a k-mer engine (PSSBAM_TALLY_KMER alone) has k-mer planes");
+    const int32_t n_planes = (int32_t)e->n_planes;
+    if (!n_planes) return fail(PSSBAM_ESTATE, "none of pssbam_engine_set_read_groups / _set_length_bins / _set_contig_sets has been called");
+    if (group < -1 || group >= n_planes) return fail(PSSBAM_EINVAL, "group %d outside -1..%d", group, n_planes - 1);
+    int rc = pssbam_engine_sync(e);
+    if (rc) return rc;
+    const uint64_t at = group < 0 ? (uint64_t)e->off_k5 : (uint64_t)e->off_groups + (uint64_t)group * e->kplane_words;
+    if (k5) HIP_TRY(hipMemcpy(k5, e->d_counters + at, e->n_bins * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (k3) HIP_TRY(hipMemcpy(k3, e->d_counters + at + e->n_bins, e->n_bins * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return PSSBAM_OK;
+}
+
 // What set_read_groups and set_length_bins share: the counter block grows to n_planes [fwd | rev] planes behind the stats,
 // zeroed (nothing has been counted yet).  The old block may still be named by work queued on the stream (the compressed
 // feed): it is retired, not freed.  `what` names the caller's planes in the messages.
 static int set_planes(pssbam_engine *e, PlaneSel sel, uint32_t n_planes, const char *what) {
-    if (e->cfg.tally_mask != PSSBAM_TALLY_PSS) return fail(PSSBAM_EINVAL, "%s split the substitution tables only (no PSSBAM_TALLY_KMER)", what);
+    const bool kmer = e->cfg.tally_mask == PSSBAM_TALLY_KMER;
+    if (e->cfg.tally_mask != PSSBAM_TALLY_PSS && !kmer)
+        return fail(PSSBAM_EINVAL, "%s split the substitution tables or the k-mer tables, not both (PSSBAM_TALLY_PSS | PSSBAM_TALLY_KMER)", what);
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set %s after create or reset, before the first tally", what);
     if (e->d_counters != e->d_counters_own) return fail(PSSBAM_ESTATE, "a caller-bound counter block cannot grow: set %s before bind_counters", what);
     HIP_TRY(hipSetDevice(e->device));
-    const size_t n_counters = (size_t)e->off_groups + (size_t)n_planes * e->plane_words;
+    // 64-bit throughout: a k-mer plane is 2 * 4^k words (2^31 at k = 15)
+    const uint64_t n_counters = (uint64_t)e->off_groups + (uint64_t)n_planes * (kmer ? e->kplane_words : (uint64_t)e->plane_words);
+    if (kmer) {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        if (n_counters * sizeof(unsigned long long) > (uint64_t)free_b)
+            return fail(PSSBAM_ENOMEM, "k = %d with %u planes (plane 0 and %u %s) needs a counter block of %llu bytes; the device has %llu free",
+                        e->cfg.kmer.klen, n_planes + 1u, n_planes, what, (unsigned long long)(n_counters * sizeof(unsigned long long)),
+                        (unsigned long long)free_b);
+    }
     unsigned long long *d_counters = nullptr;
     HIP_TRY(hipMalloc(&d_counters, n_counters * sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(d_counters, 0, n_counters * sizeof(unsigned long long), e->stream));
@@ -1304,7 +1384,9 @@ extern "C" int pssbam_engine_set_length_bins(pssbam_engine *e, int32_t n_edges, 
     if (e->planes == PLANES_RG) return fail(PSSBAM_EINVAL, "length bins and read groups exclude each other");
     if (e->planes == PLANES_REF) return fail(PSSBAM_EINVAL, "length bins and contig sets exclude each other");
     // l < e1 < ... < ek <= L: every bin [l, e1-1], [e1, e2-1], ..., [ek, L] is a non-empty -l / -L window
-    const uint64_t lo = e->cfg.pss.min_read_len, hi = e->cfg.pss.max_read_len;
+    // (a k-mer engine: the window of fragkon's -l / -L, compared with strlen(SEQ))
+    const bool kmer = e->cfg.tally_mask == PSSBAM_TALLY_KMER;
+    const uint64_t lo = kmer ? e->cfg.kmer.min_read_len : e->cfg.pss.min_read_len, hi = kmer ? e->cfg.kmer.max_read_len : e->cfg.pss.max_read_len;
     for (int32_t i = 0; i < n_edges; i++) {
         const uint64_t prev = i ? (uint64_t)edges[i - 1] : lo;
         if (edges[i] <= prev || edges[i] > hi)

@@ -275,6 +275,7 @@ __device__ bool has_read_group(const Src &src, const RecHdr &h, const uint8_t *r
 // The plane kernels' second argument: how a record's plane is picked and where one launch's planes
 // go.  A plane is one [fwd | rev] pair of (N+2)*16 tables; plane 0 is the unassigned bucket (the
 // counter block's original fwd / rev), plane 1 + g is group or bin g, at off_groups + g * plane_words.
+// On a k-mer engine a plane is one [k5 | k3] pair of 4^k bins each (koff_planes / kplane_words below).
 constexpr uint32_t MAX_LENGTH_EDGES = 63;   // PSSBAM_MAX_LENGTH_BINS - 1
 struct PlaneParams {
     // -G: the @RG ID table
@@ -290,6 +291,9 @@ struct PlaneParams {
     // -S: the length bin edges
     uint32_t n_edges;                      // 1..MAX_LENGTH_EDGES, strictly increasing
     uint32_t edges[MAX_LENGTH_EDGES];      // bin k (k >= 1) starts at edges[k-1]
+    // k-mer planes (a PSSBAM_TALLY_KMER engine): plane p >= 1 is the [k5 | k3] pair of 2 * 4^k words at
+    // koff_planes + (p - 1) * kplane_words, plane 0 the counter block's leading pair.  64-bit: 2 * 4^15 words a plane.
+    uint64_t koff_planes, kplane_words;
 };
 constexpr uint32_t GROUP_SCRATCH_DELTA = 16;   // the deltas lead a plane kernel's scratch slot
 constexpr uint32_t GROUP_PLANE_WORDS = 1024;   // one [(cell << 1) | table][32 rows] plane in LDS / scratch

@@ -41,6 +41,10 @@
 //                 read_group_plane), per fragment-length bin (PLANES_LEN: by Plan::L,
 //                 length_bin_plane) or per contig set (PLANES_REF: by Plan::ref_plane, packed into
 //                 the ref_info entry plan_head loads anyway); -S and -C stage prefixes as without planes.
+//  tally_tiled_kmer_planes / tally_simple_kmer_planes<PLANES> (fragkon -G, -S, -C): the k-mer tally with one
+//                 [k5 | k3] pair of 4^k bins per plane; the length selector reads Plan::Lk (what fragkon's -l / -L
+//                 compare).  k <= KMER_LDS_MAX_K: one 2 * 4^k-word LDS histogram per plane slot of the launch;
+//                 larger k: global 64-bit atomics straight into the plane's bins.
 //
 // Integer/byte work only: no MFMA anywhere (the bound is HBM bandwidth).
 #pragma once
@@ -271,11 +275,61 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyP
 // (-G), its length bin (-S), or its contig's set (-C).
 enum PlaneSel { PLANES_NONE = 0, PLANES_RG, PLANES_LEN, PLANES_REF };
 
-template <PlaneSel PLANES, class Src>
+// KMER: the plane of the k-mer tally -- its length bins go by Plan::Lk (strlen(SEQ), what fragkon's -l / -L compare,
+// for paired reads too), not by Plan::L.
+template <PlaneSel PLANES, bool KMER = false, class Src>
 __device__ __forceinline__ uint32_t record_plane(const Src &src, const RecHdr &h, const Plan &pl, const PlaneParams &G) {
     if constexpr (PLANES == PLANES_RG) return read_group_plane(src, h, G);
     else if constexpr (PLANES == PLANES_REF) return pl.ref_plane;   // from the ref_info entry plan_head loaded
-    else return length_bin_plane(G, pl.L);
+    else return length_bin_plane(G, KMER ? pl.Lk : pl.L);
+}
+
+// ---- k-mer planes --------------------------------------------------------------------------------------------
+// First word of plane `plane`'s [k5 | k3] pair in the counter block.  64-bit: a plane is 2 * 4^k words.
+__device__ __forceinline__ uint64_t kmer_plane_base(const TallyParams &P, const PlaneParams &G, uint32_t plane) {
+    return plane ? G.koff_planes + (uint64_t)(plane - 1u) * G.kplane_words : (uint64_t)P.off_k5;
+}
+// One bin of table `which` (0 = 5', 1 = 3') of plane `plane`: into the plane's slot of the launch's LDS histograms
+// (a plane outside plane0 .. plane0 + n_slots - 1 lands in the trash slot behind them), or straight into the
+// counter block.
+template <bool LDS_KMER>
+__device__ __forceinline__ void kmer_plane_add(const TallyParams &P, const PlaneParams &G, uint32_t plane, uint32_t which,
+                                               uint32_t bin, uint32_t *lds_kmer) {
+    const uint32_t nb = 1u << (2 * P.K);
+    if (LDS_KMER) {
+        const uint32_t slot = min(plane - G.plane0, G.n_slots);   // (plane < plane0 wraps: trash as well)
+        atomicAdd(&lds_kmer[slot * 2u * nb + (which ? nb : 0u) + bin], 1u);
+    } else {
+        atomicAdd(&P.counters[kmer_plane_base(P, G, plane) + (which ? nb : 0u) + bin], 1ull);
+    }
+}
+// tally_kmer_record for a record of plane `plane` (lane-per-read form); true = an attempted add failed
+template <bool LDS_KMER>
+__device__ __forceinline__ bool tally_kmer_record_plane(const TallyParams &P, const PlaneParams &G, const Plan &pl, uint32_t plane,
+                                                        uint32_t *lds_kmer) {
+    const uint8_t *Gn = P.genome + pl.gbase;
+    int64_t w5, w3;
+    kmer_windows(pl, P.K, w5, w3);
+    bool good = true;
+    for (uint32_t which = 0; which < 2u; which++) {   // both attempted, independently (fragkon.c:164-181)
+        if (!(which ? pl.fk3 : pl.fk5)) continue;
+        uint32_t bin;
+        if (kmer_bin(Gn, which ? w3 : w5, P.K, pl.rev, bin)) kmer_plane_add<LDS_KMER>(P, G, plane, which, bin, lds_kmer);
+        else good = false;
+    }
+    return !good;
+}
+// tally_overflow_record for tally_tiled_kmer_planes
+template <PlaneSel PLANES, bool LDS_KMER>
+__device__ __attribute__((noinline)) uint32_t tally_overflow_record_kmer_planes(const TallyParams *kernarg, const PlaneParams *gk,
+                                                                                uint32_t o0, uint32_t o1, uint32_t *lds_kmer) {
+    const TallyParams &P = *kernarg;
+    GlobalBytes gsrc{P.recs + o0};
+    const RecHdr gh = decode_hdr(gsrc, o1 - o0);
+    const Plan gpl = make_plan<false, true>(P, gsrc, gh);
+    bool kfail = false;
+    if (gpl.fk5 || gpl.fk3) kfail = tally_kmer_record_plane<LDS_KMER>(P, *gk, gpl, record_plane<PLANES, true>(gsrc, gh, gpl, *gk), lds_kmer);
+    return record_events(false, true, gpl, kfail);
 }
 
 // The same for tally_tiled_planes (substitution tables only): the record's plane slot of this
@@ -317,6 +371,8 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
                                                  int32_t *__restrict__ lds_delta, uint4 *__restrict__ refs_lds,
                                                  const PlaneParams *gk = nullptr, uint32_t *__restrict__ grp_lds = nullptr) {
     constexpr bool GROUPED = PLANES != PLANES_NONE;   // one table plane per read group / length bin
+    constexpr bool KPLANES = GROUPED && DO_KMER;      // ... of k-mer bins (tally_tiled_kmer_planes: no sheet, no table)
+    static_assert(!KPLANES || !DO_PSS, "planes split either the substitution tables or the k-mer tables");
     const uint32_t T = P.reads_per_tile;   // <= TILED_MAX_T
     const uint32_t n_recs = P.n_recs_dev ? *P.n_recs_dev : P.n_recs;   // device-indexed blocks: the count lives in device memory
     const uint32_t pieces = P.prefix_pieces;  // 16-byte pieces staged per record
@@ -335,10 +391,12 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
     const uint32_t n_live = n_pos > row_base ? min(n_pos - row_base, 32u) : 0u;
 
     // ---- one-time set-up: zero the tables ---------------------------------------------------------
-    const uint32_t table_words = GROUPED ? (gk->n_slots + 1u) * GROUP_PLANE_WORDS : TABLE_WORDS;
+    const uint32_t table_words = KPLANES ? 0u : GROUPED ? (gk->n_slots + 1u) * GROUP_PLANE_WORDS : TABLE_WORDS;
     for (uint32_t i = tid; i < table_words; i += TILED_THREADS) table[i] = 0u;
+    uint32_t kmer_words = 2u * (1u << (2 * P.K));
+    if constexpr (KPLANES) kmer_words *= gk->n_slots + 1u;   // one histogram per plane slot + the trash slot
     if (LDS_KMER)
-        for (uint32_t i = tid; i < 2u * (1u << (2 * P.K)); i += TILED_THREADS) lds_kmer[i] = 0u;
+        for (uint32_t i = tid; i < kmer_words; i += TILED_THREADS) lds_kmer[i] = 0u;
     if (tid < ST_USED) lds_delta[tid] = 0;
     // contig info of the first BAM references (all of them for a human-sized header) + the "*" entry
     const uint32_t n_ref_cached = min((uint32_t)P.n_ref, REF_LDS_ENTRIES);
@@ -467,7 +525,13 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
             for (int k = 0; k < 3; k++) kw[k] = kq.v[k];
             ksh = 4u * (uint32_t)(ka & 7ull);
         }
-        if constexpr (GROUPED) {
+        uint32_t kplane = 0u;   // k-mer planes: the record's plane, resolved by the pair's left-end lane
+        if constexpr (KPLANES) {
+            if (e == 0u && (pl.fk5 || pl.fk3)) kplane = record_plane<PLANES, true>(src, h, pl, *gk);
+            const uint32_t left = (uint32_t)__shfl_xor((int)kplane, 1);   // every lane takes part
+            if (e) kplane = left;
+        }
+        if constexpr (GROUPED && !KPLANES) {
             // the read's plane slot for COLUMNS; n_slots = not in this launch (its codes go to the trash plane)
             if (in_tile && e == 0u) {
                 const uint32_t slot = cand ? record_plane<PLANES>(src, h, pl, *gk) - gk->plane0 : gk->n_slots;
@@ -476,7 +540,8 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         }
         uint32_t ev_over = 0u;  // events of a record handled by the out-of-line path
         if (in_tile && !in_stage && e == 0u) {
-            if constexpr (GROUPED) ev_over = tally_overflow_record_planes<PLANES>(kernarg, gk, o0, o1, table);
+            if constexpr (KPLANES) ev_over = tally_overflow_record_kmer_planes<PLANES, LDS_KMER>(kernarg, gk, o0, o1, lds_kmer);
+            else if constexpr (GROUPED) ev_over = tally_overflow_record_planes<PLANES>(kernarg, gk, o0, o1, table);
             else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER>(kernarg, o0, o1, table, lds_kmer);
             if (pass0) atomicAdd(&lds_delta[ST_SLOW_PATH], 1);
         }
@@ -602,11 +667,12 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
                 }
                 kmer_ok = bad == 0u;
                 if (kmer_ok && !(ablate & 8u)) {
-                    if (LDS_KMER) atomicAdd(&lds_kmer[(kwhich ? (1u << (2 * P.K)) : 0u) + bin], 1u);
+                    if constexpr (KPLANES) kmer_plane_add<LDS_KMER>(P, *gk, kplane, kwhich, bin, lds_kmer);
+                    else if (LDS_KMER) atomicAdd(&lds_kmer[(kwhich ? (1u << (2 * P.K)) : 0u) + bin], 1u);
                     else atomicAdd(&P.counters[(kwhich ? P.off_k3 : P.off_k5) + bin], 1ull);
                 }
             }
-            if (lane_on) {  // code sheet row of read j: bytes [e*32, e*32+32)
+            if (lane_on && !KPLANES) {  // code sheet row of read j: bytes [e*32, e*32+32)
                 uint4 *dst = (uint4 *)(sheet + j * 64u + e * 32u);
                 dst[0] = make_uint4(code_w[0], code_w[1], code_w[2], code_w[3]);
                 dst[1] = make_uint4(code_w[4], code_w[5], code_w[6], code_w[7]);
@@ -669,7 +735,12 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
     // reduce_partials() sums the slots afterwards.  (Flushing with global atomics instead had
     // ~1000 workgroups queue on the same few hundred counters at the same moment: 6 % of the
     // kernel's time.)
-    if constexpr (GROUPED) {   // [deltas 16 | n_slots planes]
+    if constexpr (KPLANES) {   // [deltas 16 | n_slots histograms of 2 * 4^k words (LDS_KMER only)]
+        uint32_t *mine = P.scratch + (size_t)blockIdx.x * gk->scratch_words;
+        const uint32_t n_words = LDS_KMER ? gk->n_slots * 2u * (1u << (2 * P.K)) : 0u;
+        for (uint32_t i = tid; i < n_words; i += TILED_THREADS) mine[GROUP_SCRATCH_DELTA + i] = lds_kmer[i];
+        if (tid < 16u) mine[tid] = tid < (uint32_t)ST_USED ? (uint32_t)lds_delta[tid] : 0u;
+    } else if constexpr (GROUPED) {   // [deltas 16 | n_slots planes]
         uint32_t *mine = P.scratch + (size_t)blockIdx.x * gk->scratch_words;
         const uint32_t n_words = gk->n_slots * GROUP_PLANE_WORDS;
         for (uint32_t i = tid; i < n_words; i += TILED_THREADS) mine[GROUP_SCRATCH_DELTA + i] = table[i];
@@ -1293,6 +1364,82 @@ __global__ void __launch_bounds__(256) tally_simple_planes(const TallyParams P, 
     }
     __syncthreads();
     flush_events(true, false, P, lds_delta);
+}
+
+// ---------------------------------------------------------------------------------------
+// fragkon -G / -S / -C: one [k5 | k3] pair of k-mer tables per plane, in one pass over the records
+// ---------------------------------------------------------------------------------------
+// tally_tiled's k-mer tally with every record's bins in its plane.  Dynamic LDS: the staging buffer, then (LDS_KMER,
+// k <= KMER_LDS_MAX_K) n_slots + 1 histograms of 2 * 4^k words -- the planes of this launch and the trash slot; at
+// k = 4 a plane is 2 KiB, so 64 length bins fit one launch.  Without LDS_KMER the bins go straight into the counter
+// block with 64-bit atomics and one launch serves every plane.  No code sheet and no substitution table: the
+// kernel's static LDS is the offsets, the deltas and the reference cache only.
+template <PlaneSel PLANES, bool LDS_KMER>
+__global__ void __launch_bounds__(TILED_THREADS) tally_tiled_kmer_planes(const TallyParams P, const PlaneParams G) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
+    __shared__ uint32_t toffs[2u * (TILED_MAX_T + 4u)];
+    __shared__ int32_t lds_delta[ST_USED];
+    __shared__ uint4 refs_lds[REF_LDS_ENTRIES + 1];
+    const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
+    const PlaneParams *gk = (const PlaneParams *)((const uint8_t *)kernarg + PLANE_KERNARG_OFFSET);
+    uint32_t *lds_kmer = (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces));
+    tally_tiled_body<false, true, LDS_KMER, false, PLANES>(P, kernarg, stage, nullptr, nullptr, toffs, lds_kmer, lds_delta, refs_lds, gk);
+}
+// dynamic LDS a k-mer plane launch may take: the CU's 160 KiB less the kernel's static objects (~2.1 KiB) and some margin
+constexpr uint32_t KMER_PLANES_LDS_BUDGET = 156u * 1024u;
+__host__ __device__ inline uint32_t tiled_kmer_planes_lds_bytes(uint32_t T, uint32_t pieces, uint32_t n_slots, int K, bool lds_kmer) {
+    return tiled_lds_bytes(T, pieces) + (lds_kmer ? (n_slots + 1u) * 2u * (1u << (2 * K)) * 4u : 0u);
+}
+
+// reduce_partials for tally_tiled_kmer_planes: slot layout [deltas 16 | n_slots histograms of 2 * 4^k words]; histogram
+// s of the launch is plane plane0 + s of the counter block, its words the plane's [k5 | k3] in order.  The status
+// deltas (and the launch's record credit) belong to the launch of planes 0..
+__global__ void __launch_bounds__(256) reduce_partials_kmer_planes(const TallyParams P, const PlaneParams G, uint32_t n_slots,
+                                                                   uint32_t lds_kmer_on) {
+    const uint32_t sw = G.scratch_words;
+    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t i = gid % sw, g = gid / sw;
+    if (g >= REDUCE_GROUPS) return;
+    unsigned long long *dst = nullptr;
+    bool is_delta = false;
+    if (i < GROUP_SCRATCH_DELTA) {
+        if (i < (uint32_t)ST_USED && G.plane0 == 0u) { dst = &P.counters[P.off_stats + i]; is_delta = true; }
+    } else if (lds_kmer_on) {
+        const uint32_t kw = 2u * (1u << (2 * P.K));
+        const uint32_t w = (i - GROUP_SCRATCH_DELTA) % kw, plane = G.plane0 + (i - GROUP_SCRATCH_DELTA) / kw;
+        if (plane <= G.n_groups) dst = &P.counters[kmer_plane_base(P, G, plane) + w];
+    }
+    if (!dst) return;
+    long long sum = 0;
+    const uint32_t *p = P.scratch + i;
+#pragma unroll 8
+    for (uint32_t b = g; b < n_slots; b += REDUCE_GROUPS) {
+        const uint32_t v = p[(size_t)b * sw];
+        sum += is_delta ? (long long)(int32_t)v : (long long)v;
+    }
+    if (is_delta && g == 0u && (i == ST_RECORDS || i == ST_KMER_OK)) sum += P.n_recs_dev ? *P.n_recs_dev : P.n_recs;
+    if (sum) atomicAdd(dst, (unsigned long long)sum);
+}
+
+// tally_simple's k-mer tally with every record's bins in its plane (global atomics; the cross-check of
+// tally_tiled_kmer_planes)
+template <PlaneSel PLANES>
+__global__ void __launch_bounds__(256) tally_simple_kmer_planes(const TallyParams P, const PlaneParams G) {
+    __shared__ int32_t lds_delta[ST_USED];
+    if (threadIdx.x < ST_USED) lds_delta[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < P.n_recs; r += stride) {
+        const uint32_t o0 = P.offs[r], o1 = P.offs[r + 1];
+        GlobalBytes src{P.recs + o0};
+        const RecHdr h = decode_hdr(src, o1 - o0);
+        const Plan pl = make_plan<false, true>(P, src, h);
+        bool kfail = false;
+        if (pl.fk5 || pl.fk3) kfail = tally_kmer_record_plane<false>(P, G, pl, record_plane<PLANES, true>(src, h, pl, G), nullptr);
+        book_events(false, true, record_events(false, true, pl, kfail), lds_delta);
+    }
+    __syncthreads();
+    flush_events(false, true, P, lds_delta);
 }
 
 // genome-kmer-count (genome-kmer-count.c:69-79): every k-mer start of the device genome.  Each

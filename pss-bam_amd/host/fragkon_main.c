@@ -4,6 +4,11 @@
  * Same options, stderr banners and stdout table as the reference front end
  * (/root/reference/fragkon.c:253-386); the k-mer tallies come from the GPU engine's flat
  * 4^k histograms (k <= 15 on the device).  See pss_main.c for what differs underneath.
+ * Added, as in pss-bam: -G, -S e1,...,ek and -C <map file> (at most one of them, with -o <prefix>) write, beside the
+ * table of all reads on stdout, one table per @RG ID, per read-length bin or per label of the map to
+ * <prefix>.<tag>.fragkon.txt (the tags pss-bam uses), each what the same command prints for that plane alone:
+ * on the records `samtools view -r <ID>` keeps, with `-l <lo> -L <hi>`, or with -F cut down to the label's
+ * contigs -- from one pass over the input.  Without these options nothing differs from the reference front end.
  */
 #include <ctype.h>
 #include <stdio.h>
@@ -11,8 +16,11 @@
 #include <string.h>
 #include <unistd.h>
 
+#include "contig_sets.h"
 #include "fasta-genome-io.h"
 #include "frontend.h"
+#include "length_bins.h"
+#include "read_groups.h"
 #include "report.h"
 #include "sam-parse.h"
 
@@ -21,9 +29,11 @@ int main(int argc, char *argv[])
     frontend_detach_start();   /* (frontend.c: the caller does not wait for the teardown) */
     int klen = 8, min_mq = 0, merged_only = 0, option;
     unsigned long min_read_len = 0, max_read_len = 250000000;
-    char *fasta_fn = NULL, *bam_fn = NULL;
+    char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL;
+    int by_group = 0;
+    const char *len_edges = NULL, *ctg_map = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:k:l:L:q:m")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:k:l:L:q:mGS:C:o:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -32,6 +42,10 @@ int main(int argc, char *argv[])
         case 'L': max_read_len = strtoul(optarg, NULL, 10); break;
         case 'q': min_mq = atoi(optarg); break;
         case 'm': merged_only = 1; break;
+        case 'G': by_group = 1; break;
+        case 'S': len_edges = optarg; break;
+        case 'C': ctg_map = optarg; break;
+        case 'o': out_prefix = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
             exit(0);
@@ -59,6 +73,55 @@ int main(int argc, char *argv[])
               stderr);
         exit(1);
     }
+    const int n_selectors = by_group + (len_edges != NULL) + (ctg_map != NULL);
+    if (n_selectors > 1) {
+        fprintf(stderr, "-G (tables per read group), -S (tables per length bin) and -C (tables per contig set) exclude each other.\n");
+        exit(1);
+    }
+    if (n_selectors && !out_prefix) {
+        fprintf(stderr, "-%c needs -o <output filename prefix> for the per-%s tables (<prefix>.<tag>.fragkon.txt).\n",
+                by_group ? 'G' : len_edges ? 'S' : 'C', by_group ? "read-group" : len_edges ? "length-bin" : "contig-set");
+        exit(1);
+    }
+    uint32_t edges[PSSBAM_MAX_LENGTH_BINS - 1];
+    int n_edges = 0;
+    if (len_edges) {
+        char err[200];
+        if ((n_edges = pss_parse_length_edges(len_edges, min_read_len, max_read_len, edges, err, sizeof err)) < 0) {
+            fprintf(stderr, "%s\n", err);
+            exit(1);
+        }
+    }
+    frontend_contig_map sets;
+    memset(&sets, 0, sizeof sets);
+    if (ctg_map) {
+        FILE *mf = fopen(ctg_map, "rb");
+        char *text = NULL;
+        size_t len = 0, cap = 0;
+        int read_ok = mf != NULL;
+        while (read_ok) {
+            if (len == cap) {
+                char *t = (char *)realloc(text, cap = cap ? 2 * cap : 65536);
+                if (!t) { read_ok = 0; break; }
+                text = t;
+            }
+            const size_t got = fread(text + len, 1, cap - len, mf);
+            len += got;
+            if (got == 0) { read_ok = !ferror(mf); break; }
+        }
+        if (mf) fclose(mf);
+        if (!read_ok) {
+            fprintf(stderr, "-C: unable to read the map file %s.\n", ctg_map);
+            exit(1);
+        }
+        char err[600];
+        sets.n_names = pss_parse_contig_sets(text, len, &sets.names, &sets.set_of, &sets.labels, &sets.n_labels, err, sizeof err);
+        free(text);
+        if (sets.n_names < 0) {
+            fprintf(stderr, "%s (%s)\n", err, ctg_map);
+            exit(1);
+        }
+    }
     if (klen < 1 || klen > PSSBAM_MAX_KLEN) {
         fprintf(stderr, "k-mer length %d is outside the range this build tallies on the GPU (1..%d).\n", klen, PSSBAM_MAX_KLEN);
         exit(1);
@@ -84,6 +147,10 @@ int main(int argc, char *argv[])
     cfg.device = 0;
     cfg.kernel = PSSBAM_KERNEL_AUTO;
 
+    frontend_group_by_rg = by_group;
+    frontend_n_length_edges = n_edges;
+    memcpy(frontend_length_edges, edges, (size_t)n_edges * sizeof *edges);
+    if (ctg_map) frontend_contig_sets = &sets;
     /* HIP start-up, engines and the compressed BAM feed overlap the FASTA load (frontend.c) */
     frontend_warmup_start(&cfg, bam_fn, fasta_fn);
     Genome *genome = init_genome(fasta_fn);
@@ -98,6 +165,22 @@ int main(int argc, char *argv[])
     if (run_tally(&cfg, genome, bam_fn, env_gpu_count(), &res)) exit(1);
     fragkon_write_table(stdout, fasta_fn, bam_fn, klen, res.k5, res.k3);
     fflush(stdout);
+    if (by_group && res.n_planes == 0)
+        fprintf(stderr, "Warning: -G: the header of %s has no @RG line; only the table of all reads was written.\n", bam_fn);
+    /* <prefix>.<tag>.fragkon.txt: what the same command prints for the plane's records alone */
+    for (int k = 0; k < res.n_planes; k++) {
+        const size_t bins = (size_t)1 << (2 * klen);
+        unsigned long lo = 0, hi = 0;
+        if (len_edges) pss_length_bin_bounds(edges, n_edges, k, min_read_len, max_read_len, &lo, &hi);
+        const char *id = by_group ? res.group_ids[k] : ctg_map ? sets.labels[k] : NULL;   /* file-name encoded */
+        const size_t tag_len = id ? pss_rg_file_tag(id, NULL, 0) : pss_length_bin_tag(lo, hi, NULL, 0);
+        char *tag = (char *)malloc(tag_len + 1);
+        if (!tag) { fprintf(stderr, "Error: out of memory\n"); exit(1); }
+        if (id) pss_rg_file_tag(id, tag, tag_len + 1);
+        else pss_length_bin_tag(lo, hi, tag, tag_len + 1);
+        if (fragkon_write_plane(fasta_fn, bam_fn, out_prefix, tag, klen, res.plane_k5 + k * bins, res.plane_k3 + k * bins)) exit(1);
+        free(tag);
+    }
     if (getenv("PSSBAM_STATS")) {
         fprintf(stderr, "[pssbam] records=%llu kmer_ok=%llu kmer_filtered=%llu kmer_fail=%llu gpus=%d\n",
                 (unsigned long long)res.stats[PSSBAM_ST_RECORDS], (unsigned long long)res.stats[PSSBAM_ST_KMER_OK],
@@ -110,8 +193,10 @@ int main(int argc, char *argv[])
     }
     run_result_free(&res);
     destroy_genome(genome);
+    if (ctg_map) pss_free_contig_sets(sets.names, sets.n_names, sets.set_of, sets.labels, sets.n_labels);
     free(fasta_fn);
     free(bam_fn);
+    free(out_prefix);
     fprintf(stderr, "Done.\n");
     return 0;
 }

@@ -412,6 +412,8 @@ void run_result_free(run_result *res)
     pss_free_read_groups(res->group_ids, res->group_ids ? res->n_planes : 0);
     free(res->plane_fwd);
     free(res->plane_rev);
+    free(res->plane_k5);
+    free(res->plane_k3);
     free(res->fwd);
     free(res->rev);
     free(res->k5);
@@ -789,7 +791,17 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
         warn_unreached_sets(frontend_contig_sets, genome, rd ? bam_reader_header(rd)->n_ref : sam_reader_n_ref(sd),
                             rd ? (const char *const *)bam_reader_header(rd)->ref_name : sam_reader_ref_names(sd), aln_path);
     }
-    if (res->n_planes > 0) {
+    if (res->n_planes > 0 && cfg->tally_mask == PSSBAM_TALLY_KMER) {
+        const size_t bins = (size_t)1 << (2 * cfg->kmer.klen);
+        res->plane_k5 = (uint64_t *)calloc(bins * (size_t)res->n_planes, sizeof(uint64_t));
+        res->plane_k3 = (uint64_t *)calloc(bins * (size_t)res->n_planes, sizeof(uint64_t));
+        if (!res->plane_k5 || !res->plane_k3) { fprintf(stderr, "Error: out of memory\n"); goto done; }
+        for (int k = 0; k < res->n_planes; k++)
+            if (pssbam_engine_finish_kmer_groups(eng[0], k, res->plane_k5 + k * bins, res->plane_k3 + k * bins)) {
+                fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+                goto done;
+            }
+    } else if (res->n_planes > 0) {
         const size_t cells = (size_t)(cfg->pss.region_len + 2) * 16;
         res->plane_fwd = (unsigned long *)calloc(cells * (size_t)res->n_planes, sizeof(unsigned long));
         res->plane_rev = (unsigned long *)calloc(cells * (size_t)res->n_planes, sizeof(unsigned long));

@@ -20,6 +20,8 @@ typedef struct run_result {
     int n_planes;
     char **group_ids;
     unsigned long *plane_fwd, *plane_rev;
+    /* fragkon -G / -S / -C (a PSSBAM_TALLY_KMER engine): the planes' k-mer tables instead, 4^klen per plane */
+    uint64_t *plane_k5, *plane_k3;
 } run_result;
 
 /* pss-bam -G: every engine gets the input header's @RG IDs (pssbam_engine_set_read_groups) and run_tally()

@@ -123,6 +123,28 @@ int fragkon_write_table(FILE *out, const char *fasta_fn, const char *bam_fn, int
     return 0;
 }
 
+int fragkon_write_plane(const char *fasta_fn, const char *bam_fn, const char *out_prefix, const char *tag, int klen,
+                        const uint64_t *k5, const uint64_t *k3)
+{
+    const size_t cap = strlen(out_prefix) + strlen(tag) + sizeof "..fragkon.txt";
+    char *fn = (char *)malloc(cap);
+    if (!fn) {
+        fprintf(stderr, "Error: out of memory\n");
+        return 1;
+    }
+    snprintf(fn, cap, "%s.%s.fragkon.txt", out_prefix, tag);
+    FILE *fp = fopen(fn, "w");
+    if (!fp) {
+        fprintf(stderr, "ERROR: Cannot write to file %s\n.", fn);
+        free(fn);
+        return 1;
+    }
+    int rc = fragkon_write_table(fp, fasta_fn, bam_fn, klen, k5, k3);
+    if (fclose(fp)) rc = 1;
+    free(fn);
+    return rc;
+}
+
 /* genome-kmer-count's table (/root/reference/genome-kmer-count.c:56-66 prints kmer2count(): an
  * unsigned int that sticks at UINT_MAX, kmer.c:102-104) */
 int gkc_write_table(FILE *out, int klen, const uint64_t *counts)

@@ -14,5 +14,9 @@ int pss_write_rates(const char *fasta_fn, const char *bam_fn, const char *out_pr
 int fragkon_write_table(FILE *out, const char *fasta_fn, const char *bam_fn, int klen, const uint64_t *k5,
                         const uint64_t *k3);
 /* counts: 4^klen 64-bit bins (clamped to UINT_MAX on output) */
+/* fragkon -G / -S / -C: one plane's table as <out_prefix>.<tag>.fragkon.txt in fragkon_write_table's format (the
+ * counts stick at UINT_MAX per plane); `tag` is already file-name encoded.  Returns 0, or 1 after a diagnostic. */
+int fragkon_write_plane(const char *fasta_fn, const char *bam_fn, const char *out_prefix, const char *tag, int klen,
+                        const uint64_t *k5, const uint64_t *k3);
 int gkc_write_table(FILE *out, int klen, const uint64_t *counts);
 #endif
