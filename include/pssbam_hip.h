@@ -36,6 +36,7 @@ extern "C" {
 #define PSSBAM_MAX_READ_GROUPS 4096  /* pssbam_engine_set_read_groups */
 #define PSSBAM_MAX_LENGTH_BINS 64    /* pssbam_engine_set_length_bins: at most 63 edges */
 #define PSSBAM_MAX_CONTIG_SETS 4096  /* pssbam_engine_set_contig_sets */
+#define PSSBAM_MAX_BASE_QUALITY 93   /* pssbam_engine_set_min_base_quality: the largest Phred value SAM text can print */
 
 /* error codes */
 #define PSSBAM_OK 0
@@ -243,6 +244,28 @@ int pssbam_engine_set_length_bins(pssbam_engine *e, int32_t n_edges, const uint3
  * pssbam_engine_finish_groups(e, s, ...) returns set s. */
 int pssbam_engine_set_contig_sets(pssbam_engine *e, int32_t n_sets, int64_t n_names, const char *const *names,
                                   const int32_t *set_of);
+
+/* Minimum base quality (pss-bam -Q): read bases whose quality is below q are left out of the substitution tables,
+ * as the tools that estimate damage from such tables do (a sequencing error at a Q2-Q15 base is no substitution).
+ * q is a Phred value -- the BAM QUAL byte, the SAM character - 33 -- in 0..PSSBAM_MAX_BASE_QUALITY; 0 switches
+ * the mask off and the engine then launches exactly the kernels it launches without this call.  For q > 0
+ * interior position i (0..region_len-1) of an alignment end adds nothing to its table when the QUAL byte of the
+ * read base it pairs with (base i for the left end, base L-1-i for the right end, on either strand) is < q.  That
+ * is what the reference does with a read base that is not A/C/G/T (add_fwd_counts / add_rev_counts skip it), and
+ * nothing else of it looks at the content of SEQ, so
+ *     the tables with minimum base quality q == the tables without it on the same records with every SEQ base
+ *     whose quality is below q replaced by 'N'.
+ * Rows 0 and 1 (the context bases) are reference-only and never masked.  The record filters, -U / -D, the plane a
+ * record falls in and every status counter stay as they are: a read whose window is masked entirely still counts
+ * as PSSBAM_ST_PSS_OK.  Absent qualities (0xFF fill) compare as 255 and mask nothing.  The k-mer tables of a
+ * PSSBAM_TALLY_PSS | PSSBAM_TALLY_KMER engine are unaffected.  The tiled kernels stage whole records for q > 0
+ * (QUAL lies behind SEQ), as they do with cfg.read_group.
+ * Legal after create (or reset) and before the first tally launch; with pssbam_engine_feed_open that is any time
+ * before set_references.  Goes with cfg.read_group and with each of read groups, length bins and contig sets.
+ * PSSBAM_EINVAL for q outside the range or on an engine without PSSBAM_TALLY_PSS, PSSBAM_ESTATE once records have
+ * been tallied.  The value survives pssbam_engine_reset.  The counter block keeps its layout; engines whose blocks
+ * are summed (pssbam_reduce_counters, a caller's RCCL reduce) must all have been given the same q. */
+int pssbam_engine_set_min_base_quality(pssbam_engine *e, int32_t q);
 
 /* The device-resident counter block [fwd | rev | k5 | k3 | stats] as one array of
  * n_u64 64-bit words, for a caller-side RCCL reduce across GPUs (sum, uint64).  With read groups it is

@@ -41,11 +41,12 @@ HIP_SYMBOLS = [
     "pssbam_engine_feed_status", "pssbam_engine_feed_break", "pssbam_engine_feed_handoff", "pssbam_feed_reserve", "pssbam_engine_hint_records",
     "pssbam_engine_set_genome_async", "pssbam_engine_genome_wait", "pssbam_engine_feed_open", "pssbam_feed_release",
     "pssbam_engine_set_read_groups", "pssbam_engine_finish_groups", "pssbam_engine_set_length_bins",
-    "pssbam_engine_set_contig_sets", "pssbam_engine_finish_kmer_groups",
+    "pssbam_engine_set_contig_sets", "pssbam_engine_finish_kmer_groups", "pssbam_engine_set_min_base_quality",
 ]
 MAX_READ_GROUPS = 4096
 MAX_LENGTH_BINS = 64
 MAX_CONTIG_SETS = 4096
+MAX_BASE_QUALITY = 93
 EBUSY = -7
 
 
@@ -110,6 +111,7 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_finish_kmer_groups.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_length_bins.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)]
     L.pssbam_engine_set_contig_sets.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]
+    L.pssbam_engine_set_min_base_quality.argtypes = [C.c_void_p, C.c_int32]
     L.pssbam_engine_counters_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.pssbam_engine_bind_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.pssbam_engine_genome_kmer_count.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -180,12 +182,14 @@ class Engine:
     `read_groups` = @RG IDs (pss-bam -G): one set of substitution tables per ID, see set_read_groups.
     `length_bins` = length bin edges (pss-bam -S): one set of substitution tables per bin, see set_length_bins.
     `contig_sets` = contig sets (pss-bam -C): one set of substitution tables per label, see set_contig_sets.
+    `min_base_qual` = minimum base quality (pss-bam -Q): read bases below it are left out of the substitution tables,
+    see set_min_base_quality; 0 = off.
     With `kmer` alone (no `pss`) the three split the k-mer tables instead (fragkon -G / -S / -C): every plane is a
     k5 / k3 pair, and the length bins go by the SEQ length and kmer's min_read_len / max_read_len."""
 
     def __init__(self, pss: dict | None = None, kmer: dict | None = None, read_group: str | None = None,
                  kernel: int = KERNEL_AUTO, device: int = -1, read_groups: list[str] | None = None,
-                 length_bins: list[int] | None = None, contig_sets=None):
+                 length_bins: list[int] | None = None, contig_sets=None, min_base_qual: int = 0):
         L = hip_lib()
         cfg = _Config()
         cfg.abi_version = 1
@@ -219,12 +223,27 @@ class Engine:
         self.read_groups: list[str] = []
         self.length_bins: list[tuple[int, int]] = []
         self.contig_sets: list[str] = []
+        self._min_base_qual = 0
+        if min_base_qual:
+            self.set_min_base_quality(min_base_qual)
         if read_groups is not None:
             self.set_read_groups(read_groups)
         if length_bins is not None:
             self.set_length_bins(length_bins)
         if contig_sets is not None:
             self.set_contig_sets(contig_sets)
+
+    def set_min_base_quality(self, q: int):
+        """pss-bam -Q: a read base whose Phred quality is below q (0..93, 0 = off) adds nothing to the substitution
+        tables -- the tables equal those of the same records with such bases replaced by N.  Before the first tally
+        (after feed_open: before set_references); survives reset."""
+        _chk(self._L.pssbam_engine_set_min_base_quality(self._h, int(q)))
+        self._min_base_qual = int(q)
+
+    @property
+    def min_base_qual(self) -> int:
+        """the minimum base quality in force (0 = off)"""
+        return self._min_base_qual
 
     def set_contig_sets(self, sets):
         """pss-bam -C: tallies every record into the tables of the set that lists its RNAME (the unassigned bucket

@@ -161,6 +161,9 @@ enum PrepSlot {
     PREP_COMPACT_ONCE, PREP_COMPACT_ONCE_KMER, PREP_COMPACT_ONCE_KMER_LDS, PREP_COMPACT_DECODE_TWICE,
     PREP_PLANES_RG, PREP_PLANES_RG_LATER, PREP_PLANES_LEN, PREP_PLANES_LEN_LATER, PREP_PLANES_REF, PREP_PLANES_REF_LATER,
     PREP_KPLANES_RG, PREP_KPLANES_RG_LDS, PREP_KPLANES_LEN, PREP_KPLANES_LEN_LDS, PREP_KPLANES_REF, PREP_KPLANES_REF_LDS,
+    // -Q (min_bq > 0): the MASKQ instantiations, in the order of their unmasked twins
+    PREP_TILED_PSS_BQ, PREP_TILED_PSS_LATER_BQ, PREP_TILED_PSS_KMER_BQ, PREP_TILED_PSS_KMER_LDS_BQ,
+    PREP_PLANES_RG_BQ, PREP_PLANES_RG_LATER_BQ, PREP_PLANES_LEN_BQ, PREP_PLANES_LEN_LATER_BQ, PREP_PLANES_REF_BQ, PREP_PLANES_REF_LATER_BQ,
     PREP_N
 };
 
@@ -219,6 +222,7 @@ struct pssbam_engine {
     std::unordered_map<std::string, uint32_t> ctg_plane;   // -C: contig name -> 1 + set, packed into ref_info[].w
     std::vector<std::string> ref_names;   // the names of the last set_references (-C set after it packs them again)
     bool tallied = false;   // a tally launch since create / reset
+    uint32_t min_bq = 0;    // -Q: read bases with a QUAL byte below this are left out of the tables (pssbam_engine_set_min_base_quality)
     // counters
     unsigned long long *d_counters = nullptr;      // block in use (own or caller-bound)
     unsigned long long *d_counters_own = nullptr;  // the engine's own allocation
@@ -767,16 +771,17 @@ static int launch_flat(pssbam_engine *e, PrepSlot slot, K kernel, TallyParams &P
 }
 
 // One (row pass, plane pass) launch of tally_tiled_planes and its reduce_partials_grouped
-template <PlaneSel SEL, bool LATER>
+template <PlaneSel SEL, bool LATER, bool MASKQ>
 static int launch_planes(pssbam_engine *e, TallyParams &P, const PlaneParams &G, uint32_t lds, uint32_t n_tiles) {
-    constexpr PrepSlot slot = SEL == PLANES_RG  ? (LATER ? PREP_PLANES_RG_LATER : PREP_PLANES_RG)
-                            : SEL == PLANES_LEN ? (LATER ? PREP_PLANES_LEN_LATER : PREP_PLANES_LEN)
-                                                : (LATER ? PREP_PLANES_REF_LATER : PREP_PLANES_REF);
+    constexpr PrepSlot plain = SEL == PLANES_RG  ? (LATER ? PREP_PLANES_RG_LATER : PREP_PLANES_RG)
+                             : SEL == PLANES_LEN ? (LATER ? PREP_PLANES_LEN_LATER : PREP_PLANES_LEN)
+                                                 : (LATER ? PREP_PLANES_REF_LATER : PREP_PLANES_REF);
+    constexpr PrepSlot slot = MASKQ ? (PrepSlot)(PREP_PLANES_RG_BQ + (plain - PREP_PLANES_RG)) : plain;
     uint32_t grid = 0;
-    const int rc = tiled_grid(e, slot, tally_tiled_planes<SEL, LATER>, lds, n_tiles, G.scratch_words, &grid);
+    const int rc = tiled_grid(e, slot, tally_tiled_planes<SEL, LATER, MASKQ>, lds, n_tiles, G.scratch_words, &grid);
     if (rc != PSSBAM_OK) return rc;
     P.scratch = e->d_scratch;
-    hipLaunchKernelGGL((tally_tiled_planes<SEL, LATER>), dim3(grid), dim3(TILED_THREADS), lds, e->stream, P, G);
+    hipLaunchKernelGGL((tally_tiled_planes<SEL, LATER, MASKQ>), dim3(grid), dim3(TILED_THREADS), lds, e->stream, P, G);
     hipLaunchKernelGGL(reduce_partials_grouped, dim3((G.scratch_words * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream, P, G, grid);
     return PSSBAM_OK;
 }
@@ -820,8 +825,8 @@ static uint64_t sample_prefix_need(const uint8_t *bytes, uint64_t nbytes, bool w
     return need_max;
 }
 
-// -R and -G walk the aux fields, which sit behind QUAL: the tiled kernels stage whole records
-static bool whole_records(const pssbam_engine *e) { return e->has_rg || e->planes == PLANES_RG; }
+// -R and -G walk the aux fields, which sit behind QUAL, and -Q reads QUAL itself: the tiled kernels stage whole records
+static bool whole_records(const pssbam_engine *e) { return e->has_rg || e->planes == PLANES_RG || e->min_bq > 0; }
 
 // The plane kernels' argument for the engine's -G / -S state (plane0, n_slots and scratch_words are per launch)
 static PlaneParams plane_params(const pssbam_engine *e) {
@@ -896,6 +901,8 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
     P.off_k5 = e->off_k5;
     P.off_k3 = e->off_k3;
     P.off_stats = e->off_stats;
+    P.min_bq = do_pss ? e->min_bq : 0u;
+    const bool maskq = P.min_bq > 0;   // -Q: the MASKQ instantiations of the tiled kernels; min_bq == 0 launches what it always did
     PlaneParams G = plane_params(e);
 
     int kernel = c.kernel;
@@ -1018,9 +1025,13 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
             // up to 7 groups or sets, or 6 bins -- plane 0 of -S stays empty but keeps its slot); more planes take
             // more passes, each re-reading the records.
             using LaunchPlanes = int (*)(pssbam_engine *, TallyParams &, const PlaneParams &, uint32_t, uint32_t);
-            static constexpr LaunchPlanes launch_pass[3][2] = {{launch_planes<PLANES_RG, false>, launch_planes<PLANES_RG, true>},
-                                                               {launch_planes<PLANES_LEN, false>, launch_planes<PLANES_LEN, true>},
-                                                               {launch_planes<PLANES_REF, false>, launch_planes<PLANES_REF, true>}};
+            static constexpr LaunchPlanes launch_pass[2][3][2] = {
+                {{launch_planes<PLANES_RG, false, false>, launch_planes<PLANES_RG, true, false>},
+                 {launch_planes<PLANES_LEN, false, false>, launch_planes<PLANES_LEN, true, false>},
+                 {launch_planes<PLANES_REF, false, false>, launch_planes<PLANES_REF, true, false>}},
+                {{launch_planes<PLANES_RG, false, true>, launch_planes<PLANES_RG, true, true>},
+                 {launch_planes<PLANES_LEN, false, true>, launch_planes<PLANES_LEN, true, true>},
+                 {launch_planes<PLANES_REF, false, true>, launch_planes<PLANES_REF, true, true>}}};
             const uint32_t n_planes = G.n_groups + 1u;
             const uint32_t fit = lds + 2u * GROUP_PLANE_WORDS * 4u <= GROUPED_LDS_BUDGET
                                      ? (GROUPED_LDS_BUDGET - lds) / (GROUP_PLANE_WORDS * 4u) - 1u : 1u;
@@ -1032,11 +1043,12 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                     G.plane0 = plane0;
                     G.n_slots = std::min(per_pass, n_planes - plane0);
                     G.scratch_words = GROUP_SCRATCH_DELTA + G.n_slots * GROUP_PLANE_WORDS;
-                    rc = launch_pass[e->planes - PLANES_RG][pass > 0](e, P, G, tiled_grouped_lds_bytes(T, pieces, G.n_slots), n_tiles);
+                    rc = launch_pass[maskq][e->planes - PLANES_RG][pass > 0](e, P, G, tiled_grouped_lds_bytes(T, pieces, G.n_slots), n_tiles);
                 }
             }
-        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg) {
-            // -r N <= 16 (2 context rows + 16 positions): the short-window variant, one pass
+        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq) {
+            // -r N <= 16 (2 context rows + 16 positions): the short-window variant, one pass (it stages prefixes only
+            // and has no QUAL path: -R and -Q go to tally_tiled)
             if (!do_kmer && getenv("PSSBAM_COMPACT_DECODE_TWICE"))   // diagnostics: what the shared header decode costs
                 rc = launch_flat(e, PREP_COMPACT_DECODE_TWICE, tally_compact_decode_twice, P, lds, n_tiles, false);
             else if (e->compact_plan_once)
@@ -1047,6 +1059,17 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                 rc = !do_kmer  ? launch_flat(e, PREP_COMPACT, tally_compact<false, false, false>, P, lds, n_tiles, false)
                      : kmer_lds ? launch_flat(e, PREP_COMPACT_KMER_LDS, tally_compact<true, true, false>, P, lds, n_tiles, true)
                                 : launch_flat(e, PREP_COMPACT_KMER, tally_compact<true, false, false>, P, lds, n_tiles, false);
+        } else if (maskq) {
+            // -Q: tally_tiled with the QUAL fetch and the per-position mask, for every -r (later passes as below)
+            if (do_kmer)
+                rc = kmer_lds ? launch_flat(e, PREP_TILED_PSS_KMER_LDS_BQ, tally_tiled<true, true, true, false, true>, P, lds, n_tiles, true)
+                              : launch_flat(e, PREP_TILED_PSS_KMER_BQ, tally_tiled<true, true, false, false, true>, P, lds, n_tiles, false);
+            else
+                rc = launch_flat(e, PREP_TILED_PSS_BQ, tally_tiled<true, false, false, false, true>, P, lds, n_tiles, false);
+            for (uint32_t pass = 1; pass < n_passes && rc == PSSBAM_OK; pass++) {
+                P.row_base = pass * TILED_ROWS;
+                rc = launch_flat(e, PREP_TILED_PSS_LATER_BQ, tally_tiled<true, false, false, true, true>, P, lds, n_tiles, false);
+            }
         } else {
             if (do_pss && do_kmer)
                 rc = kmer_lds ? launch_flat(e, PREP_TILED_PSS_KMER_LDS, tally_tiled<true, true, true, false>, P, lds, n_tiles, true)
@@ -1374,6 +1397,16 @@ extern "C" int pssbam_engine_set_read_groups(pssbam_engine *e, int32_t n, const 
     e->d_grp_hash = d_hash;
     e->grp_hash_mask = hsize - 1;
     e->dev_pieces = 0;   // whole records are staged from now on: resampled at the next launch
+    return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_set_min_base_quality(pssbam_engine *e, int32_t q) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (q < 0 || q > PSSBAM_MAX_BASE_QUALITY) return fail(PSSBAM_EINVAL, "minimum base quality %d outside 0..%d", q, PSSBAM_MAX_BASE_QUALITY);
+    if (!(e->cfg.tally_mask & PSSBAM_TALLY_PSS)) return fail(PSSBAM_EINVAL, "base qualities mask the substitution tables: the engine needs PSSBAM_TALLY_PSS");
+    if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the minimum base quality after create or reset, before the first tally");
+    if ((e->min_bq > 0) != (q > 0)) e->dev_pieces = 0;   // whole records or prefixes are staged from now on: resampled at the next launch
+    e->min_bq = (uint32_t)q;
     return PSSBAM_OK;
 }
 

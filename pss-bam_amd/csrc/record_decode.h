@@ -69,6 +69,9 @@ struct TallyParams {
     uint32_t xcd_map;             // tiled kernel: XCD-contiguous workgroup -> tile mapping
     uint32_t ablate;              // diagnostics: phases to skip (results are wrong when non-zero)
     uint32_t *scratch;            // tiled kernel: per-workgroup partial tables (SCRATCH_WORDS each)
+    // -Q: a read base whose QUAL byte is below this adds nothing to the substitution tables (0 = off); read only by
+    // the MASKQ instantiations of the tiled kernels and by the lane-per-read kernels
+    uint32_t min_bq;
 };
 
 // stats slots, must match include/pssbam_hip.h.  The kernels count EVENTS only: every launch

@@ -95,15 +95,19 @@ struct GlobalTable {  // straight into the u64 counter block
 // (reference s-2.., read bases 0..) or right end (reference ..s+L+1, read bases ..L-1);
 // `comp` complements both bases (reverse-strand reads), which maps cell c to 15-c.
 // Restates add_ctx_counts + add_fwd_counts / add_rev_counts, pss-bam.c:169-326.
-template <class Src, class Tab>
+// MASKQ (-Q): a position whose read base has a QUAL byte below min_bq adds nothing, as if SEQ held 'N' there
+// (add_fwd_counts / add_rev_counts skip every read base that is not A/C/G/T); the context rows are
+// reference-only and never masked.  min_bq == 0 masks nothing.
+template <bool MASKQ, class Src, class Tab>
 __device__ void tally_end(const Tab &tab, uint32_t table, const Src &src, const RecHdr &h, const uint8_t *G,
-                          int64_t s, uint32_t L, int N, bool left, bool comp) {
+                          int64_t s, uint32_t L, int N, bool left, bool comp, uint32_t min_bq) {
     const uint32_t c0 = ref_code(left ? G[s - 2] : G[s + L + 1]);  // second context base -> row 0
     const uint32_t c1 = ref_code(left ? G[s - 1] : G[s + L]);      // first context base  -> row 1
     if (c0 < 4u) tab.add(table, 0, comp ? 15u - 5u * c0 : 5u * c0);
     if (c1 < 4u) tab.add(table, 1, comp ? 15u - 5u * c1 : 5u * c1);
     for (int i = 0; i < N; i++) {
         const uint32_t ri = left ? (uint32_t)i : L - 1u - (uint32_t)i;
+        if (MASKQ && ri < h.l_seq && src.u8(h.qual_off + ri) < min_bq) continue;   // (absent QUAL is 0xFF: never below)
         const uint32_t rd = nib_code(read_nibble(src, h, ri));
         const uint32_t rf = ref_code(G[s + (int64_t)ri]);
         if (rd < 4u && rf < 4u) {
@@ -113,14 +117,15 @@ __device__ void tally_end(const Tab &tab, uint32_t table, const Src &src, const 
     }
 }
 
-template <class Src, class Tab>
+template <bool MASKQ = false, class Src, class Tab>
 __device__ __forceinline__ void tally_pss_record(const TallyParams &P, const Tab &tab, const Src &src,
                                                  const RecHdr &h, const Plan &pl) {
+    const uint32_t min_bq = MASKQ ? P.min_bq : 0u;
     const uint8_t *G = P.genome + pl.gbase;
     // forward-strand read: fwd table <- left end, rev table <- right end;
     // reverse-strand read: fwd table <- right end complemented, rev table <- left end complemented
-    if (pl.pss_fwd) tally_end(tab, 0u, src, h, G, pl.s, pl.L, P.N, !pl.rev, pl.rev);
-    if (pl.pss_rev) tally_end(tab, 1u, src, h, G, pl.s, pl.L, P.N, pl.rev, pl.rev);
+    if (pl.pss_fwd) tally_end<MASKQ>(tab, 0u, src, h, G, pl.s, pl.L, P.N, !pl.rev, pl.rev, min_bq);
+    if (pl.pss_rev) tally_end<MASKQ>(tab, 1u, src, h, G, pl.s, pl.L, P.N, pl.rev, pl.rev, min_bq);
 }
 
 // one k-mer add (5' when which == 0, 3' when which == 1); false = non-ACGT in the window
@@ -170,8 +175,8 @@ __global__ void __launch_bounds__(256) tally_simple(const TallyParams P) {
         if (!do_pss) pl.pss_fwd = pl.pss_rev = false;
         if (!do_kmer) pl.fk5 = pl.fk3 = false;
         if (pl.pss_fwd || pl.pss_rev) {
-            if (LDS_TABLE) tally_pss_record(P, LdsTableRowMajor{dyn_lds, rows}, src, h, pl);
-            else tally_pss_record(P, GlobalTable{P.counters, P.off_rev}, src, h, pl);
+            if (LDS_TABLE) tally_pss_record<true>(P, LdsTableRowMajor{dyn_lds, rows}, src, h, pl);
+            else tally_pss_record<true>(P, GlobalTable{P.counters, P.off_rev}, src, h, pl);
         }
         bool kfail = false;
         if (pl.fk5 || pl.fk3) kfail = tally_kmer_record<false>(P, pl, nullptr);
@@ -258,14 +263,14 @@ __device__ __forceinline__ void stage_tile_dma(const uint8_t *recs, uint64_t rec
 // nothing.  It reads the kernel arguments through a pointer to the kernarg segment (taken in
 // the kernel): a reference to the kernel's by-value copy would force that whole struct into
 // scratch memory.
-template <bool DO_PSS, bool DO_KMER, bool LDS_KMER>
+template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool MASKQ = false>
 __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyParams *kernarg, uint32_t o0,
                                                                     uint32_t o1, uint32_t *table, uint32_t *lds_kmer) {
     const TallyParams &P = *kernarg;
     GlobalBytes gsrc{P.recs + o0};
     const RecHdr gh = decode_hdr(gsrc, o1 - o0);
     const Plan gpl = make_plan<DO_PSS, DO_KMER>(P, gsrc, gh);
-    if (DO_PSS && (gpl.pss_fwd || gpl.pss_rev)) tally_pss_record(P, LdsTableColumnMajor{table, P.row_base}, gsrc, gh, gpl);
+    if (DO_PSS && (gpl.pss_fwd || gpl.pss_rev)) tally_pss_record<MASKQ>(P, LdsTableColumnMajor{table, P.row_base}, gsrc, gh, gpl);
     bool kfail = false;
     if (DO_KMER && (gpl.fk5 || gpl.fk3)) kfail = tally_kmer_record<LDS_KMER>(P, gpl, lds_kmer);
     return record_events(DO_PSS, DO_KMER, gpl, kfail);
@@ -334,7 +339,7 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record_kmer_planes(
 
 // The same for tally_tiled_planes (substitution tables only): the record's plane slot of this
 // launch, if it has one, decides where its counts go.
-template <PlaneSel PLANES>
+template <PlaneSel PLANES, bool MASKQ = false>
 __device__ __attribute__((noinline)) uint32_t tally_overflow_record_planes(const TallyParams *kernarg, const PlaneParams *gk,
                                                                            uint32_t o0, uint32_t o1, uint32_t *table) {
     const TallyParams &P = *kernarg;
@@ -343,9 +348,17 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record_planes(const
     const Plan gpl = make_plan<true, false>(P, gsrc, gh);
     if (gpl.pss_fwd || gpl.pss_rev) {
         const uint32_t slot = record_plane<PLANES>(gsrc, gh, gpl, *gk) - gk->plane0;
-        if (slot < gk->n_slots) tally_pss_record(P, LdsTableColumnMajor{table + slot * GROUP_PLANE_WORDS, P.row_base}, gsrc, gh, gpl);
+        if (slot < gk->n_slots) tally_pss_record<MASKQ>(P, LdsTableColumnMajor{table + slot * GROUP_PLANE_WORDS, P.row_base}, gsrc, gh, gpl);
     }
     return record_events(true, false, gpl, false);
+}
+
+// -Q: byte mask of one dword of QUAL bytes: 0xFF where the byte is below q (q4 = q in every byte, 1 <= q <= 93), else
+// 0x00.  (x | 0x80) - q cannot borrow from the next byte (q < 0x80) and leaves bit 7 clear exactly when
+// (x & 0x7F) < q; bytes >= 0x80 (the 0xFF fill of absent qualities) are taken out by ~x.
+__device__ __forceinline__ uint32_t base_quality_mask(uint32_t x, uint32_t q4) {
+    const uint32_t lt = ~((x | 0x80808080u) - q4) & ~x & 0x80808080u;
+    return (lt - (lt >> 7)) | lt;   // 0x80 -> 0xFF
 }
 
 // Reference windows, one per alignment end, each with STATIC byte positions:
@@ -362,7 +375,12 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record_planes(const
 // planes of [(cell<<1)|table][row] plus one trash plane behind them; every read's plane slot is
 // resolved in CODES-A (record_plane: read_group_plane or length_bin_plane) and kept in grp_lds, and
 // COLUMNS adds the wave's scalar slot offset to each real code.
-template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS, PlaneSel PLANES = PLANES_NONE>
+//
+// MASKQ (-Q, min_bq > 0): whole records are staged (QUAL lies behind SEQ), CODES-A also fetches the 32 QUAL bytes
+// that line up with the end's window and CODES-B turns them into a 0x00 / 0xFF byte per position that is ORed into
+// the read-side code: a position whose base quality is below P.min_bq lands on a trash code, exactly like a read
+// base that is not A/C/G/T.  The instantiations without MASKQ contain none of it.
+template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS, PlaneSel PLANES = PLANES_NONE, bool MASKQ = false>
 __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const TallyParams *kernarg,
                                                  uint8_t *__restrict__ stage, uint8_t *__restrict__ sheet,
                                                  uint32_t *__restrict__ table,
@@ -373,6 +391,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
     constexpr bool GROUPED = PLANES != PLANES_NONE;   // one table plane per read group / length bin
     constexpr bool KPLANES = GROUPED && DO_KMER;      // ... of k-mer bins (tally_tiled_kmer_planes: no sheet, no table)
     static_assert(!KPLANES || !DO_PSS, "planes split either the substitution tables or the k-mer tables");
+    static_assert(!MASKQ || DO_PSS, "base qualities mask the substitution tables only");
     const uint32_t T = P.reads_per_tile;   // <= TILED_MAX_T
     const uint32_t n_recs = P.n_recs_dev ? *P.n_recs_dev : P.n_recs;   // device-indexed blocks: the count lives in device memory
     const uint32_t pieces = P.prefix_pieces;  // 16-byte pieces staged per record
@@ -463,8 +482,8 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         LdsBytes src{stage, hdr_ok ? j * pieces * 16u + (o0 & 15u) : 0u};
         const RecHdr h = decode_hdr_lds(src, hdr_ok ? o1 - o0 : 0u);
         // everything the path reads ends at QUAL[0] (the -R filter and -G walk the aux fields: whole record;
-        // a length bin needs nothing behind QUAL[0])
-        const uint32_t needed = (PLANES == PLANES_RG || P.rg) ? o1 - o0 : h.qual_off + 1u;
+        // a length bin needs nothing behind QUAL[0]; -Q reads QUAL to its end)
+        const uint32_t needed = (PLANES == PLANES_RG || P.rg) ? o1 - o0 : MASKQ ? h.aux_off : h.qual_off + 1u;
         const bool in_stage = hdr_ok && needed <= avail;
         Plan pl = plan_head<DO_PSS, DO_KMER>(P, src, h, RefsLdsCached{refs_lds, P.ref_info, n_ref_cached, (uint32_t)P.n_ref});
         if (!in_stage) { pl.status = RS_LIVE; pl.live = pl.pss_cand = pl.fk5 = pl.fk3 = false; }
@@ -509,6 +528,24 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
 #pragma unroll
             for (int k = 0; k < 6; k++) rr[k] = qs[k];
         }
+        // -Q: the QUAL bytes of the same read bases, one byte per window position: byte b <-> QUAL[n0 + b] (left,
+        // pass 0: bytes 0,1 are the last SEQ bytes and belong to the context positions, which CODES-B overwrites).
+        // 32 bytes at any alignment = nine aligned dwords; n0 >= -31 and QUAL starts at least 36 bytes into the
+        // record, the clamp keeps the last dword within 36 bytes of the record's end (STAGE_SLACK covers that).
+        uint32_t qq[MASKQ ? 9 : 1];
+        uint32_t qsh = 0u;
+        if constexpr (MASKQ) {
+#pragma unroll
+            for (int k = 0; k < 9; k++) qq[k] = 0u;
+            if (cand) {
+                const int32_t n0q = min(n0, (int32_t)h.l_seq);   // (at or past l_seq nothing is a read base: blanked in CODES-B)
+                const uint32_t qa = src.off + (uint32_t)((int32_t)h.qual_off + n0q);
+                const uint32_t *qp = (const uint32_t *)(stage + (qa & ~3u));
+                qsh = qa & 3u;
+#pragma unroll
+                for (int k = 0; k < 9; k++) qq[k] = qp[k];
+            }
+        }
         // fragkon window of this side of the alignment, fetched now so its latency overlaps the
         // other loads: the left-end lane owns the window at s-k/2.. (5' k-mer of a forward read, 3'
         // of a reverse read), the right-end lane the one at ..s+L+k/2 (fragkon.c:152-181)
@@ -541,8 +578,8 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         uint32_t ev_over = 0u;  // events of a record handled by the out-of-line path
         if (in_tile && !in_stage && e == 0u) {
             if constexpr (KPLANES) ev_over = tally_overflow_record_kmer_planes<PLANES, LDS_KMER>(kernarg, gk, o0, o1, lds_kmer);
-            else if constexpr (GROUPED) ev_over = tally_overflow_record_planes<PLANES>(kernarg, gk, o0, o1, table);
-            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER>(kernarg, o0, o1, table, lds_kmer);
+            else if constexpr (GROUPED) ev_over = tally_overflow_record_planes<PLANES, MASKQ>(kernarg, gk, o0, o1, table);
+            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ>(kernarg, o0, o1, table, lds_kmer);
             if (pass0) atomicAdd(&lds_delta[ST_SLOW_PATH], 1);
         }
         // First use of the gathered registers happens HERE, before the next tile's DMA is issued:
@@ -561,6 +598,10 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         if (DO_KMER) {
 #pragma unroll
             for (int k = 0; k < 2; k++) asm volatile("" : "+v"(kw[k]));
+        }
+        if constexpr (MASKQ) {   // the QUAL bytes are in registers before `stage` is released to the next tile's DMA
+#pragma unroll
+            for (int k = 0; k < 9; k++) asm volatile("" : "+v"(qq[k]));
         }
         __syncthreads();
 
@@ -621,6 +662,20 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
                     // the packed reference is little-endian in nibbles: even positions are the low ones
                     GE[m] = __builtin_amdgcn_perm(0xFFFFFFFFu, 0x00020406u, W[m] & M);
                     GO[m] = __builtin_amdgcn_perm(0xFFFFFFFFu, 0x00020406u, (W[m] >> 4) & M);
+                }
+                if constexpr (MASKQ) {
+                    // QUAL byte of window position 4k + b = byte b of Qb[k]; split into even and odd positions like
+                    // RE / RO and compared four positions at a time.  Done before the two steps below: positions at
+                    // or past l_seq are blanked whatever their mask says, and the context positions are overwritten.
+                    const uint32_t q4 = P.min_bq * 0x01010101u;
+                    uint32_t Qb[8];
+#pragma unroll
+                    for (int k = 0; k < 8; k++) Qb[k] = __builtin_amdgcn_alignbyte(qq[k + 1], qq[k], qsh);
+#pragma unroll
+                    for (int m = 0; m < 4; m++) {
+                        RE[m] |= base_quality_mask(__builtin_amdgcn_perm(Qb[2 * m + 1], Qb[2 * m], 0x06040200u), q4);
+                        RO[m] |= base_quality_mask(__builtin_amdgcn_perm(Qb[2 * m + 1], Qb[2 * m], 0x07050301u), q4);
+                    }
                 }
                 // bases at or beyond l_seq do not exist (precondition P3): blank them.  Rare (reads
                 // shorter than the window), so the whole wave skips it when no lane needs it.
@@ -1263,7 +1318,7 @@ __global__ void __launch_bounds__(256) reduce_partials(const TallyParams P, uint
     if (sum) atomicAdd(dst, (unsigned long long)sum);
 }
 
-template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS = false>
+template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS = false, bool MASKQ = false>
 __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
@@ -1274,7 +1329,8 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P
     __shared__ uint4 refs_lds[REF_LDS_ENTRIES + 1];
     // the kernel's single argument, as it lies in the kernarg segment (for the out-of-line path)
     const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
-    tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta, refs_lds);
+    tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta,
+                                                                             refs_lds);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1290,7 +1346,7 @@ constexpr size_t PLANE_KERNARG_OFFSET = (sizeof(TallyParams) + alignof(PlanePara
 // this launch and the trash plane.  -G stages whole records (the RG tag sits behind QUAL); -S
 // stages prefixes through QUAL[0] as tally_tiled does (whole records with -R only).  Substitution
 // tables only.
-template <PlaneSel PLANES, bool LATER_PASS>
+template <PlaneSel PLANES, bool LATER_PASS, bool MASKQ = false>
 __global__ void __launch_bounds__(TILED_THREADS) tally_tiled_planes(const TallyParams P, const PlaneParams G) {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
@@ -1302,8 +1358,8 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled_planes(const TallyP
     const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
     const PlaneParams *gk = (const PlaneParams *)((const uint8_t *)kernarg + PLANE_KERNARG_OFFSET);
     uint32_t *table = (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces));
-    tally_tiled_body<true, false, false, LATER_PASS, PLANES>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta, refs_lds,
-                                                             gk, grp_lds);
+    tally_tiled_body<true, false, false, LATER_PASS, PLANES, MASKQ>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta, refs_lds,
+                                                                    gk, grp_lds);
 }
 // dynamic LDS a plane launch may take: the CU's 160 KiB less the kernel's static objects (~10.6 KiB) and some margin
 constexpr uint32_t GROUPED_LDS_BUDGET = 148u * 1024u;
@@ -1358,7 +1414,7 @@ __global__ void __launch_bounds__(256) tally_simple_planes(const TallyParams P, 
         if (pl.pss_fwd || pl.pss_rev) {
             const uint32_t plane = record_plane<PLANES>(src, h, pl, G);
             unsigned long long *base = P.counters + (plane ? G.off_groups + (plane - 1u) * G.plane_words : 0u);
-            tally_pss_record(P, GlobalTable{base, P.off_rev}, src, h, pl);
+            tally_pss_record<true>(P, GlobalTable{base, P.off_rev}, src, h, pl);
         }
         book_events(true, false, record_events(true, false, pl, false), lds_delta);
     }

@@ -28,6 +28,10 @@ typedef struct run_result {
  * returns one pair of tables per ID beside the totals.  Set before frontend_warmup_start. */
 extern int frontend_group_by_rg;
 
+/* pss-bam -Q: the minimum base quality (0: off); every engine gets it (pssbam_engine_set_min_base_quality).  Set
+ * before frontend_warmup_start. */
+extern int frontend_min_base_quality;
+
 /* pss-bam -S: the edges of the length bins (frontend_n_length_edges = 0: none); every engine gets them
  * (pssbam_engine_set_length_bins) and run_tally() returns one pair of tables per bin.  Set before
  * frontend_warmup_start. */

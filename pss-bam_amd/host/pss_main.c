@@ -18,6 +18,9 @@
  * encoded like an -G ID), each the same as a run with -F reduced to the label's contigs would write (the
  * reference skips every read whose RNAME its FASTA lacks) -- one pass instead of one run per organism, per
  * mtDNA / nuclear / X / Y split.
+ * Added: -Q <q> leaves every read base whose Phred quality is below q (0..93; 0 = off) out of the tables: they
+ * are the tables this command writes without -Q for the same input with those bases replaced by N.  The context
+ * rows, the filters and the file names stay as they are.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -28,6 +31,7 @@
 #include <string.h>
 #include <unistd.h>
 
+#include "base_quality.h"
 #include "contig_sets.h"
 #include "fasta-genome-io.h"
 #include "frontend.h"
@@ -44,9 +48,9 @@ int main(int argc, char *argv[])
     unsigned long min_read_len = 0, max_read_len = 250000000;
     const char *up_ctx = "ACGT", *down_ctx = "ACGT";
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL, *read_group = NULL;
-    const char *len_edges = NULL, *ctg_map = NULL;
+    const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -61,6 +65,7 @@ int main(int argc, char *argv[])
         case 'G': by_group = 1; break;
         case 'S': len_edges = optarg; break;
         case 'C': ctg_map = optarg; break;
+        case 'Q': min_bq_arg = optarg; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -114,6 +119,14 @@ int main(int argc, char *argv[])
             exit(1);
         }
     }
+    int min_bq = 0;
+    if (min_bq_arg) {
+        char err[200];
+        if ((min_bq = pss_parse_min_base_quality(min_bq_arg, err, sizeof err)) < 0) {
+            fprintf(stderr, "%s\n", err);
+            exit(1);
+        }
+    }
     frontend_contig_map sets;
     memset(&sets, 0, sizeof sets);
     if (ctg_map) {
@@ -157,6 +170,7 @@ int main(int argc, char *argv[])
     fprintf(stderr, " -U %s -D %s%s%s", up_ctx, down_ctx, merged_only ? " -m" : "", by_group ? " -G" : "");
     if (len_edges) fprintf(stderr, " -S %s", len_edges);
     if (ctg_map) fprintf(stderr, " -C %s", ctg_map);
+    if (min_bq_arg) fprintf(stderr, " -Q %d", min_bq);
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -178,6 +192,7 @@ int main(int argc, char *argv[])
     frontend_n_length_edges = n_edges;
     memcpy(frontend_length_edges, edges, (size_t)n_edges * sizeof *edges);
     if (ctg_map) frontend_contig_sets = &sets;
+    frontend_min_base_quality = min_bq;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
      * load; only the tally launches wait for the genome (frontend.c) */
