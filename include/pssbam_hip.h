@@ -37,6 +37,7 @@ extern "C" {
 #define PSSBAM_MAX_LENGTH_BINS 64    /* pssbam_engine_set_length_bins: at most 63 edges */
 #define PSSBAM_MAX_CONTIG_SETS 4096  /* pssbam_engine_set_contig_sets */
 #define PSSBAM_MAX_BASE_QUALITY 93   /* pssbam_engine_set_min_base_quality: the largest Phred value SAM text can print */
+#define PSSBAM_MAX_REGIONS (1 << 26) /* pssbam_engine_set_regions: intervals in one call */
 
 /* error codes */
 #define PSSBAM_OK 0
@@ -266,6 +267,34 @@ int pssbam_engine_set_contig_sets(pssbam_engine *e, int32_t n_sets, int64_t n_na
  * been tallied.  The value survives pssbam_engine_reset.  The counter block keeps its layout; engines whose blocks
  * are summed (pssbam_reduce_counters, a caller's RCCL reduce) must all have been given the same q. */
 int pssbam_engine_set_min_base_quality(pssbam_engine *e, int32_t q);
+
+/* Regions (pss-bam -T, fragkon -T): only records whose alignment overlaps an interval of a BED-style list are
+ * tallied, so that
+ *     the tables with regions == the tables without them on the input reduced to the records that
+ *     `samtools view -L regions.bed` keeps.
+ * A record's alignment is [POS-1, POS-1 + reference length of its CIGAR); only a record whose CIGAR is exactly <L>M
+ * can be tallied by either tool, so for every candidate that is [pos, pos + L).  Interval i is the 0-based half-open
+ * [starts[i], ends[i]) on contig names[name_of[i]], name_of[i] in 0..n_names-1.  A read that ends at a start or
+ * starts at an end does not overlap; one shared base does.  Context bases and k-mer windows outside the alignment
+ * play no part.  Intervals may come in any order and may overlap, nest or touch: the engine sorts them per contig
+ * and merges them.  start > end is PSSBAM_EINVAL, start == end an empty interval that is dropped, an end beyond the
+ * contig is clamped.  A name given twice is the same contig; names are matched to the @SQ name of the record's refID
+ * exactly as pssbam_engine_set_contig_sets matches them, and a name no reference carries has no effect.  A contig
+ * that is not listed, or is left without an interval, tallies nothing.
+ * It is one more record filter: a candidate that meets no region counts as PSSBAM_ST_PSS_FILTERED /
+ * PSSBAM_ST_KMER_FILTERED; RECORDS, RG_DROPPED, PARSE_SKIP and NO_CONTIG stay as without regions.  It picks no plane,
+ * so it goes with cfg.read_group, with each of read groups, length bins and contig sets (every plane is what its
+ * single run gives with the same regions), with a minimum base quality and with both tally masks, alone or together.
+ * n_regions == 0 switches the filter off: the engine then launches exactly the kernels it launches without this
+ * call.  The engine keeps the name -> intervals map and packs the device table whenever set_references or this call
+ * arrives, so the call is legal before and after set_references.  Legal after create (or reset) and before the first
+ * tally launch; with pssbam_engine_feed_open that is any time before set_references.  PSSBAM_ESTATE once records have
+ * been tallied, PSSBAM_ENOMEM when the table does not fit the device.  The regions survive pssbam_engine_reset.  The
+ * counter block keeps its layout; engines whose blocks are summed (pssbam_reduce_counters, a caller's RCCL reduce)
+ * must all have been given the same regions.  $PSSBAM_REGION_GRID_SHIFT (2..20, default 10) sets the bases per word
+ * of the lookup grid (2^shift). */
+int pssbam_engine_set_regions(pssbam_engine *e, int32_t n_names, const char *const *names, int64_t n_regions,
+                              const int32_t *name_of, const uint32_t *starts, const uint32_t *ends);
 
 /* The device-resident counter block [fwd | rev | k5 | k3 | stats] as one array of
  * n_u64 64-bit words, for a caller-side RCCL reduce across GPUs (sum, uint64).  With read groups it is

@@ -42,11 +42,13 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_genome_async", "pssbam_engine_genome_wait", "pssbam_engine_feed_open", "pssbam_feed_release",
     "pssbam_engine_set_read_groups", "pssbam_engine_finish_groups", "pssbam_engine_set_length_bins",
     "pssbam_engine_set_contig_sets", "pssbam_engine_finish_kmer_groups", "pssbam_engine_set_min_base_quality",
+    "pssbam_engine_set_regions",
 ]
 MAX_READ_GROUPS = 4096
 MAX_LENGTH_BINS = 64
 MAX_CONTIG_SETS = 4096
 MAX_BASE_QUALITY = 93
+MAX_REGIONS = 1 << 26
 EBUSY = -7
 
 
@@ -112,6 +114,7 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_set_length_bins.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)]
     L.pssbam_engine_set_contig_sets.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]
     L.pssbam_engine_set_min_base_quality.argtypes = [C.c_void_p, C.c_int32]
+    L.pssbam_engine_set_regions.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_counters_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.pssbam_engine_bind_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.pssbam_engine_genome_kmer_count.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -244,6 +247,22 @@ class Engine:
     def min_base_qual(self) -> int:
         """the minimum base quality in force (0 = off)"""
         return self._min_base_qual
+
+    def set_regions(self, names, name_of, starts, ends):
+        """pss-bam -T / fragkon -T: only records whose alignment overlaps one of the intervals are tallied -- the tables
+        equal those of the input reduced by `samtools view -L`.  Interval i is the 0-based half-open
+        [starts[i], ends[i]) on contig names[name_of[i]] (numpy arrays or sequences; any order, may overlap).  No
+        interval switches the filter off.  Before the first tally (after feed_open: before set_references), before or
+        after set_references; survives reset."""
+        raw = [nm.encode() if isinstance(nm, str) else bytes(nm) for nm in names]
+        arr = (C.c_char_p * max(len(raw), 1))(*raw)
+        name_of = np.ascontiguousarray(name_of, dtype=np.int32)
+        starts = np.ascontiguousarray(starts, dtype=np.uint32)
+        ends = np.ascontiguousarray(ends, dtype=np.uint32)
+        if not (name_of.size == starts.size == ends.size):
+            raise ValueError("name_of, starts and ends must have one entry per interval")
+        _chk(self._L.pssbam_engine_set_regions(self._h, len(raw), arr, name_of.size, name_of.ctypes.data, starts.ctypes.data,
+                                               ends.ctypes.data))
 
     def set_contig_sets(self, sets):
         """pss-bam -C: tallies every record into the tables of the set that lists its RNAME (the unassigned bucket

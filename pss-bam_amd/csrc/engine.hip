@@ -155,7 +155,7 @@ void pin_release(const void *p) {
 }  // namespace
 
 // tiled_grid's memo slots: one per kernel instantiation launch_tally launches with dynamic LDS
-enum PrepSlot {
+enum PrepSlot : int {
     PREP_TILED_PSS, PREP_TILED_PSS_LATER, PREP_TILED_PSS_KMER, PREP_TILED_PSS_KMER_LDS, PREP_TILED_KMER, PREP_TILED_KMER_LDS,
     PREP_COMPACT, PREP_COMPACT_KMER, PREP_COMPACT_KMER_LDS,
     PREP_COMPACT_ONCE, PREP_COMPACT_ONCE_KMER, PREP_COMPACT_ONCE_KMER_LDS, PREP_COMPACT_DECODE_TWICE,
@@ -164,7 +164,7 @@ enum PrepSlot {
     // -Q (min_bq > 0): the MASKQ instantiations, in the order of their unmasked twins
     PREP_TILED_PSS_BQ, PREP_TILED_PSS_LATER_BQ, PREP_TILED_PSS_KMER_BQ, PREP_TILED_PSS_KMER_LDS_BQ,
     PREP_PLANES_RG_BQ, PREP_PLANES_RG_LATER_BQ, PREP_PLANES_LEN_BQ, PREP_PLANES_LEN_LATER_BQ, PREP_PLANES_REF_BQ, PREP_PLANES_REF_LATER_BQ,
-    PREP_N
+    PREP_N   // -T: the REGIONS instantiation of slot s is memo slot PREP_N + s
 };
 
 struct pssbam_engine {
@@ -223,6 +223,15 @@ struct pssbam_engine {
     std::vector<std::string> ref_names;   // the names of the last set_references (-C set after it packs them again)
     bool tallied = false;   // a tally launch since create / reset
     uint32_t min_bq = 0;    // -Q: read bases with a QUAL byte below this are left out of the tables (pssbam_engine_set_min_base_quality)
+    // -T (pssbam_engine_set_regions): contig name -> its merged intervals, kept on the host; the per-refID device table is
+    // packed from it whenever the reference list or the map changes (pack_regions)
+    std::unordered_map<std::string, std::vector<uint2>> regions;
+    bool has_regions = false;
+    uint32_t region_shift = 10;            // a grid word per 2^shift bases ($PSSBAM_REGION_GRID_SHIFT)
+    std::vector<uint4> ref_info_host;      // the last set_references' table: contig length and "found" per refID, for the packing
+    uint4 *d_region_info = nullptr;
+    uint32_t *d_region_grid = nullptr;
+    uint2 *d_region_iv = nullptr;
     // counters
     unsigned long long *d_counters = nullptr;      // block in use (own or caller-bound)
     unsigned long long *d_counters_own = nullptr;  // the engine's own allocation
@@ -273,8 +282,8 @@ struct pssbam_engine {
     int env_group_slots = 0;   // PSSBAM_GROUP_SLOTS: at most this many planes per -G launch (tests: plane passes with few groups)
     bool warned_ablate = false;
     bool compact_plan_once = false;   // tally_compact: header decode + filters once per read, plan through LDS (PSSBAM_COMPACT_PLAN_ONCE)
-    uint32_t prep_lds[PREP_N] = {0};   // tiled_grid's memo, by kernel
-    int prep_occ[PREP_N] = {0};
+    uint32_t prep_lds[2 * PREP_N] = {0};   // tiled_grid's memo, by kernel
+    int prep_occ[2 * PREP_N] = {0};
     bool use_compact = true;        // -r N <= 16: tally_compact (PSSBAM_COMPACT=0 keeps tally_tiled, for A/B runs)
     uint32_t *d_scratch = nullptr;  // per-workgroup partial tables of the tiled kernel
     size_t scratch_slots = 0;
@@ -415,6 +424,7 @@ extern "C" int pssbam_engine_create(const pssbam_config *cfg, pssbam_engine **ou
     e->env_grid_wgs = env_int("PSSBAM_GRID_WGS");
     e->env_pieces = env_int("PSSBAM_PIECES");
     e->env_group_slots = env_int("PSSBAM_GROUP_SLOTS");
+    if (const int g = env_int("PSSBAM_REGION_GRID_SHIFT")) e->region_shift = (uint32_t)std::min(std::max(g, 2), 20);
     if (getenv("PSSBAM_COMPACT")) e->use_compact = env_int("PSSBAM_COMPACT") != 0;
     if (getenv("PSSBAM_COMPACT_PLAN_ONCE")) e->compact_plan_once = env_int("PSSBAM_COMPACT_PLAN_ONCE") != 0;
     if (tstat)
@@ -476,6 +486,8 @@ extern "C" void pssbam_engine_destroy(pssbam_engine *e) {
     if (e->d_ref_info) (void)hipFree(e->d_ref_info);
     if (e->h_ref_info) (void)hipHostFree(e->h_ref_info);
     if (e->d_rg) (void)hipFree(e->d_rg);
+    for (void *q : {(void *)e->d_region_info, (void *)e->d_region_grid, (void *)e->d_region_iv})
+        if (q) (void)hipFree(q);
     if (e->d_grp_ids) (void)hipFree(e->d_grp_ids);
     if (e->d_grp_offs) (void)hipFree(e->d_grp_offs);
     if (e->d_grp_hash) (void)hipFree(e->d_grp_hash);
@@ -645,6 +657,111 @@ extern "C" int pssbam_engine_genome_wait(pssbam_engine *e) {
     return genome_settle(e);
 }
 
+// -T: packs the per-refID region table for the current reference list (ref_names / ref_info_host) on the device:
+// the descriptors, every listed contig's intervals with their ends clamped to the contig, and a grid per contig that
+// has intervals (record_decode.h: TallyParams::region_*).  Plain device memory written by hipMemcpy.  `in_use`: queued
+// kernels may still read the previous table (SAM text: the reference list grows), so the stream is drained first.
+static int pack_regions(pssbam_engine *e, bool in_use) {
+    if (!e->has_regions) return PSSBAM_OK;
+    const size_t n_ent = (size_t)e->n_ref + 1;
+    const uint32_t g = e->region_shift;
+    std::vector<uint4> desc(n_ent, make_uint4(0, 0, 0, 0));
+    // sizes first, in 64 bits
+    uint64_t n_iv = 0, n_grid = 0;
+    std::vector<const std::vector<uint2> *> src(n_ent, nullptr);
+    for (size_t i = 0; i < n_ent; i++) {
+        const uint4 ri = e->ref_info_host[i];
+        if (!ri.w) continue;   // the genome lacks the name: its records are never candidates
+        const auto it = e->regions.find(i < (size_t)e->n_ref ? e->ref_names[i] : std::string("*"));
+        if (it == e->regions.end()) continue;
+        uint64_t cnt = 0;
+        for (const uint2 &v : it->second) cnt += v.x < ri.z ? 1u : 0u;   // (ascending: the ones inside the contig lead)
+        if (!cnt) continue;
+        src[i] = &it->second;
+        desc[i] = make_uint4(0, (uint32_t)cnt, 0, 0);
+        n_iv += cnt;
+        n_grid += ((uint64_t)ri.z >> g) + 2;
+    }
+    if (n_iv >= (1ull << 32) || n_grid >= (1ull << 32)) return fail(PSSBAM_ENOMEM, "the region table has too many intervals or grid words for 32-bit indices");
+    const uint64_t bytes = n_ent * sizeof(uint4) + (n_iv + 1) * sizeof(uint2) + (n_grid + 2) * sizeof(uint32_t);
+    HIP_TRY(hipSetDevice(e->device));
+    if (in_use && e->d_region_info) HIP_TRY(hipStreamSynchronize(e->stream));
+    for (void **q : {(void **)&e->d_region_info, (void **)&e->d_region_grid, (void **)&e->d_region_iv})
+        if (*q) { HIP_TRY(hipFree(*q)); *q = nullptr; }
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (bytes > (uint64_t)free_b)
+        return fail(PSSBAM_ENOMEM, "the region table (%llu intervals, grid shift %u) needs %llu bytes; the device has %llu free",
+                    (unsigned long long)n_iv, g, (unsigned long long)bytes, (unsigned long long)free_b);
+    std::vector<uint2> iv((size_t)n_iv + 1, make_uint2(0, 0));
+    std::vector<uint32_t> grid((size_t)n_grid + 2, 0u);
+    uint64_t at_iv = 0, at_grid = 0;
+    for (size_t i = 0; i < n_ent; i++) {
+        if (!src[i]) continue;
+        const uint32_t len = e->ref_info_host[i].z, cnt = desc[i].y;
+        desc[i].x = (uint32_t)at_iv;
+        desc[i].z = (uint32_t)at_grid;
+        uint2 *out = iv.data() + at_iv;
+        for (uint32_t k = 0; k < cnt; k++) out[k] = make_uint2((*src[i])[k].x, std::min((*src[i])[k].y, len));
+        // grid[b] = first interval whose end lies beyond b << g; one closing word = cnt
+        const uint64_t n_bins = ((uint64_t)len >> g) + 1;
+        uint32_t j = 0;
+        for (uint64_t b = 0; b < n_bins; b++) {
+            while (j < cnt && (uint64_t)out[j].y <= (b << g)) j++;
+            grid[at_grid + b] = j;
+        }
+        grid[at_grid + n_bins] = cnt;
+        at_iv += cnt;
+        at_grid += n_bins + 1;
+    }
+    HIP_TRY(hipMalloc(&e->d_region_info, n_ent * sizeof(uint4)));
+    HIP_TRY(hipMalloc(&e->d_region_iv, iv.size() * sizeof(uint2)));
+    HIP_TRY(hipMalloc(&e->d_region_grid, grid.size() * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(e->d_region_info, desc.data(), n_ent * sizeof(uint4), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_region_iv, iv.data(), iv.size() * sizeof(uint2), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_region_grid, grid.data(), grid.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_set_regions(pssbam_engine *e, int32_t n_names, const char *const *names, int64_t n_regions,
+                                         const int32_t *name_of, const uint32_t *starts, const uint32_t *ends) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (n_names < 0 || n_regions < 0 || n_regions > PSSBAM_MAX_REGIONS) return fail(PSSBAM_EINVAL, "region count outside 0..%d", PSSBAM_MAX_REGIONS);
+    if ((n_names && !names) || (n_regions && (!name_of || !starts || !ends))) return fail(PSSBAM_EINVAL, "null region list");
+    if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the regions after create or reset, before the first tally");
+    std::unordered_map<std::string, std::vector<uint2>> map;
+    for (int32_t k = 0; k < n_names; k++) {
+        if (!names[k]) return fail(PSSBAM_EINVAL, "region contig name %d is NULL", k);
+        if (n_regions) map[names[k]];   // listed, perhaps with nothing: tallies nothing
+    }
+    for (int64_t i = 0; i < n_regions; i++) {
+        if (name_of[i] < 0 || name_of[i] >= n_names) return fail(PSSBAM_EINVAL, "region %lld: contig index %d outside 0..%d", (long long)i, name_of[i], n_names - 1);
+        if (starts[i] > ends[i])
+            return fail(PSSBAM_EINVAL, "region %lld on %s: start %u lies behind end %u", (long long)i, names[name_of[i]], starts[i], ends[i]);
+        if (starts[i] < ends[i]) map[names[name_of[i]]].push_back(make_uint2(starts[i], ends[i]));   // (an empty interval is dropped)
+    }
+    for (auto &kv : map) {   // sorted, then overlapping, nested and touching intervals merged: disjoint, non-adjacent, ascending
+        std::vector<uint2> &v = kv.second;
+        std::sort(v.begin(), v.end(), [](const uint2 &a, const uint2 &b) { return a.x != b.x ? a.x < b.x : a.y < b.y; });
+        size_t n = 0;
+        for (const uint2 &r : v) {
+            if (n && r.x <= v[n - 1].y) v[n - 1].y = std::max(v[n - 1].y, r.y);
+            else v[n++] = r;
+        }
+        v.resize(n);
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    e->regions.swap(map);
+    e->has_regions = n_regions > 0;
+    if (!e->has_regions) {   // switched off: the engine launches what it launches without the call
+        if (e->d_region_info) HIP_TRY(hipStreamSynchronize(e->stream));
+        for (void **q : {(void **)&e->d_region_info, (void **)&e->d_region_grid, (void **)&e->d_region_iv})
+            if (*q) { HIP_TRY(hipFree(*q)); *q = nullptr; }
+        return PSSBAM_OK;
+    }
+    return e->have_refs ? pack_regions(e, true) : PSSBAM_OK;   // (otherwise set_references packs the table when it comes)
+}
+
 extern "C" int pssbam_engine_set_references(pssbam_engine *e, int32_t n_ref, const char *const *names) {
     if (!e || n_ref < 0 || (n_ref && !names)) return fail(PSSBAM_EINVAL, "bad argument");
     if (!e->d_genome) return fail(PSSBAM_ESTATE, "set_genome must precede set_references");
@@ -673,7 +790,7 @@ extern "C" int pssbam_engine_set_references(pssbam_engine *e, int32_t n_ref, con
         }
     }
     fill((size_t)n_ref, e->star_contig, "*");
-    e->ref_names.assign(names, names + n_ref);   // for a pssbam_engine_set_contig_sets after this call
+    e->ref_names.assign(names, names + n_ref);   // for a pssbam_engine_set_contig_sets / _set_regions after this call
     if (e->feed_opened && !e->deferred.empty() && n_ref != e->feed_n_ref)
         return fail(PSSBAM_ESTATE, "pssbam_engine_feed_open announced %d references, set_references brings %d", e->feed_n_ref, n_ref);
     // a table that is being REPLACED (SAM text: the list grows as new RNAMEs show up) may still be read by queued
@@ -696,8 +813,11 @@ extern "C" int pssbam_engine_set_references(pssbam_engine *e, int32_t n_ref, con
     memcpy(e->h_ref_info, info.data(), ((size_t)n_ref + 1) * sizeof(uint4));
     hipLaunchKernelGGL(copy_table_kernel, dim3(1), dim3(256), 0, e->stream, e->d_ref_info, (const uint4 *)e->h_ref_info, (uint32_t)n_ref + 1u);
     HIP_TRY(hipGetLastError());
+    const bool replaced = e->have_refs;
     e->n_ref = n_ref;
     e->have_refs = true;
+    e->ref_info_host.swap(info);
+    if (const int rc = pack_regions(e, replaced)) return rc;   // -T: the region table follows the reference list
     return feed_resume(e);   // super-batches inflated ahead of the genome are tallied now
 }
 
@@ -770,33 +890,43 @@ static int launch_flat(pssbam_engine *e, PrepSlot slot, K kernel, TallyParams &P
     return PSSBAM_OK;
 }
 
+// launch_flat of one tally_tiled instantiation, or of its REGIONS twin when the launch carries a region table (-T)
+template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER, bool MASKQ>
+static int launch_tiled(pssbam_engine *e, PrepSlot slot, TallyParams &P, uint32_t lds, uint32_t n_tiles) {
+    if (P.region_info)
+        return launch_flat(e, (PrepSlot)(slot + PREP_N), tally_tiled<DO_PSS, DO_KMER, LDS_KMER, LATER, MASKQ, true>, P, lds, n_tiles, LDS_KMER);
+    return launch_flat(e, slot, tally_tiled<DO_PSS, DO_KMER, LDS_KMER, LATER, MASKQ, false>, P, lds, n_tiles, LDS_KMER);
+}
+
 // One (row pass, plane pass) launch of tally_tiled_planes and its reduce_partials_grouped
-template <PlaneSel SEL, bool LATER, bool MASKQ>
+template <PlaneSel SEL, bool LATER, bool MASKQ, bool REGIONS>
 static int launch_planes(pssbam_engine *e, TallyParams &P, const PlaneParams &G, uint32_t lds, uint32_t n_tiles) {
     constexpr PrepSlot plain = SEL == PLANES_RG  ? (LATER ? PREP_PLANES_RG_LATER : PREP_PLANES_RG)
                              : SEL == PLANES_LEN ? (LATER ? PREP_PLANES_LEN_LATER : PREP_PLANES_LEN)
                                                  : (LATER ? PREP_PLANES_REF_LATER : PREP_PLANES_REF);
-    constexpr PrepSlot slot = MASKQ ? (PrepSlot)(PREP_PLANES_RG_BQ + (plain - PREP_PLANES_RG)) : plain;
+    constexpr PrepSlot unfiltered = MASKQ ? (PrepSlot)(PREP_PLANES_RG_BQ + (plain - PREP_PLANES_RG)) : plain;
+    constexpr PrepSlot slot = (PrepSlot)(unfiltered + (REGIONS ? PREP_N : 0));
     uint32_t grid = 0;
-    const int rc = tiled_grid(e, slot, tally_tiled_planes<SEL, LATER, MASKQ>, lds, n_tiles, G.scratch_words, &grid);
+    const int rc = tiled_grid(e, slot, tally_tiled_planes<SEL, LATER, MASKQ, REGIONS>, lds, n_tiles, G.scratch_words, &grid);
     if (rc != PSSBAM_OK) return rc;
     P.scratch = e->d_scratch;
-    hipLaunchKernelGGL((tally_tiled_planes<SEL, LATER, MASKQ>), dim3(grid), dim3(TILED_THREADS), lds, e->stream, P, G);
+    hipLaunchKernelGGL((tally_tiled_planes<SEL, LATER, MASKQ, REGIONS>), dim3(grid), dim3(TILED_THREADS), lds, e->stream, P, G);
     hipLaunchKernelGGL(reduce_partials_grouped, dim3((G.scratch_words * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream, P, G, grid);
     return PSSBAM_OK;
 }
 
 // One plane pass of tally_tiled_kmer_planes and its reduce_partials_kmer_planes
-template <PlaneSel SEL, bool LDS_KMER>
+template <PlaneSel SEL, bool LDS_KMER, bool REGIONS>
 static int launch_kmer_planes(pssbam_engine *e, TallyParams &P, const PlaneParams &G, uint32_t lds, uint32_t n_tiles) {
-    constexpr PrepSlot slot = SEL == PLANES_RG  ? (LDS_KMER ? PREP_KPLANES_RG_LDS : PREP_KPLANES_RG)
-                            : SEL == PLANES_LEN ? (LDS_KMER ? PREP_KPLANES_LEN_LDS : PREP_KPLANES_LEN)
-                                                : (LDS_KMER ? PREP_KPLANES_REF_LDS : PREP_KPLANES_REF);
+    constexpr PrepSlot unfiltered = SEL == PLANES_RG  ? (LDS_KMER ? PREP_KPLANES_RG_LDS : PREP_KPLANES_RG)
+                                  : SEL == PLANES_LEN ? (LDS_KMER ? PREP_KPLANES_LEN_LDS : PREP_KPLANES_LEN)
+                                                      : (LDS_KMER ? PREP_KPLANES_REF_LDS : PREP_KPLANES_REF);
+    constexpr PrepSlot slot = (PrepSlot)(unfiltered + (REGIONS ? PREP_N : 0));
     uint32_t grid = 0;
-    const int rc = tiled_grid(e, slot, tally_tiled_kmer_planes<SEL, LDS_KMER>, lds, n_tiles, G.scratch_words, &grid);
+    const int rc = tiled_grid(e, slot, tally_tiled_kmer_planes<SEL, LDS_KMER, REGIONS>, lds, n_tiles, G.scratch_words, &grid);
     if (rc != PSSBAM_OK) return rc;
     P.scratch = e->d_scratch;
-    hipLaunchKernelGGL((tally_tiled_kmer_planes<SEL, LDS_KMER>), dim3(grid), dim3(TILED_THREADS), lds, e->stream, P, G);
+    hipLaunchKernelGGL((tally_tiled_kmer_planes<SEL, LDS_KMER, REGIONS>), dim3(grid), dim3(TILED_THREADS), lds, e->stream, P, G);
     hipLaunchKernelGGL(reduce_partials_kmer_planes, dim3((G.scratch_words * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream, P, G, grid,
                        (uint32_t)(LDS_KMER ? 1 : 0));
     return PSSBAM_OK;
@@ -903,6 +1033,13 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
     P.off_stats = e->off_stats;
     P.min_bq = do_pss ? e->min_bq : 0u;
     const bool maskq = P.min_bq > 0;   // -Q: the MASKQ instantiations of the tiled kernels; min_bq == 0 launches what it always did
+    const bool regions = e->has_regions;   // -T: the REGIONS instantiations; without regions the engine launches what it always did
+    if (regions) {
+        P.region_info = e->d_region_info;
+        P.region_grid = e->d_region_grid;
+        P.region_iv = e->d_region_iv;
+        P.region_shift = e->region_shift;
+    }
     PlaneParams G = plane_params(e);
 
     int kernel = c.kernel;
@@ -998,9 +1135,14 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
             // fit the LDS beside the staging buffer -- 2 KiB each at k = 4, so 64 bins and plane 0 are one pass -- and more
             // planes take more passes, each re-reading the records.  Larger k: global atomics, one pass whatever the count.
             using LaunchK = int (*)(pssbam_engine *, TallyParams &, const PlaneParams &, uint32_t, uint32_t);
-            static constexpr LaunchK launch_k[3][2] = {{launch_kmer_planes<PLANES_RG, false>, launch_kmer_planes<PLANES_RG, true>},
-                                                       {launch_kmer_planes<PLANES_LEN, false>, launch_kmer_planes<PLANES_LEN, true>},
-                                                       {launch_kmer_planes<PLANES_REF, false>, launch_kmer_planes<PLANES_REF, true>}};
+            static constexpr LaunchK launch_kr[2][3][2] = {
+                {{launch_kmer_planes<PLANES_RG, false, false>, launch_kmer_planes<PLANES_RG, true, false>},
+                 {launch_kmer_planes<PLANES_LEN, false, false>, launch_kmer_planes<PLANES_LEN, true, false>},
+                 {launch_kmer_planes<PLANES_REF, false, false>, launch_kmer_planes<PLANES_REF, true, false>}},
+                {{launch_kmer_planes<PLANES_RG, false, true>, launch_kmer_planes<PLANES_RG, true, true>},
+                 {launch_kmer_planes<PLANES_LEN, false, true>, launch_kmer_planes<PLANES_LEN, true, true>},
+                 {launch_kmer_planes<PLANES_REF, false, true>, launch_kmer_planes<PLANES_REF, true, true>}}};
+            const auto &launch_k = launch_kr[regions];
             const uint32_t n_planes = G.n_groups + 1u;
             if (kmer_lds) {
                 const uint32_t hist = 2u * (1u << (2 * c.kmer.klen)) * 4u;   // bytes of one plane's histogram
@@ -1025,13 +1167,20 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
             // up to 7 groups or sets, or 6 bins -- plane 0 of -S stays empty but keeps its slot); more planes take
             // more passes, each re-reading the records.
             using LaunchPlanes = int (*)(pssbam_engine *, TallyParams &, const PlaneParams &, uint32_t, uint32_t);
-            static constexpr LaunchPlanes launch_pass[2][3][2] = {
-                {{launch_planes<PLANES_RG, false, false>, launch_planes<PLANES_RG, true, false>},
-                 {launch_planes<PLANES_LEN, false, false>, launch_planes<PLANES_LEN, true, false>},
-                 {launch_planes<PLANES_REF, false, false>, launch_planes<PLANES_REF, true, false>}},
-                {{launch_planes<PLANES_RG, false, true>, launch_planes<PLANES_RG, true, true>},
-                 {launch_planes<PLANES_LEN, false, true>, launch_planes<PLANES_LEN, true, true>},
-                 {launch_planes<PLANES_REF, false, true>, launch_planes<PLANES_REF, true, true>}}};
+            static constexpr LaunchPlanes launch_pass_r[2][2][3][2] = {
+                {{{launch_planes<PLANES_RG, false, false, false>, launch_planes<PLANES_RG, true, false, false>},
+                  {launch_planes<PLANES_LEN, false, false, false>, launch_planes<PLANES_LEN, true, false, false>},
+                  {launch_planes<PLANES_REF, false, false, false>, launch_planes<PLANES_REF, true, false, false>}},
+                 {{launch_planes<PLANES_RG, false, true, false>, launch_planes<PLANES_RG, true, true, false>},
+                  {launch_planes<PLANES_LEN, false, true, false>, launch_planes<PLANES_LEN, true, true, false>},
+                  {launch_planes<PLANES_REF, false, true, false>, launch_planes<PLANES_REF, true, true, false>}}},
+                {{{launch_planes<PLANES_RG, false, false, true>, launch_planes<PLANES_RG, true, false, true>},
+                  {launch_planes<PLANES_LEN, false, false, true>, launch_planes<PLANES_LEN, true, false, true>},
+                  {launch_planes<PLANES_REF, false, false, true>, launch_planes<PLANES_REF, true, false, true>}},
+                 {{launch_planes<PLANES_RG, false, true, true>, launch_planes<PLANES_RG, true, true, true>},
+                  {launch_planes<PLANES_LEN, false, true, true>, launch_planes<PLANES_LEN, true, true, true>},
+                  {launch_planes<PLANES_REF, false, true, true>, launch_planes<PLANES_REF, true, true, true>}}}};
+            const auto &launch_pass = launch_pass_r[regions];
             const uint32_t n_planes = G.n_groups + 1u;
             const uint32_t fit = lds + 2u * GROUP_PLANE_WORDS * 4u <= GROUPED_LDS_BUDGET
                                      ? (GROUPED_LDS_BUDGET - lds) / (GROUP_PLANE_WORDS * 4u) - 1u : 1u;
@@ -1046,9 +1195,9 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                     rc = launch_pass[maskq][e->planes - PLANES_RG][pass > 0](e, P, G, tiled_grouped_lds_bytes(T, pieces, G.n_slots), n_tiles);
                 }
             }
-        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq) {
+        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions) {
             // -r N <= 16 (2 context rows + 16 positions): the short-window variant, one pass (it stages prefixes only
-            // and has no QUAL path: -R and -Q go to tally_tiled)
+            // and has no QUAL path: -R and -Q go to tally_tiled; so does -T, whose lookup only tally_tiled carries)
             if (!do_kmer && getenv("PSSBAM_COMPACT_DECODE_TWICE"))   // diagnostics: what the shared header decode costs
                 rc = launch_flat(e, PREP_COMPACT_DECODE_TWICE, tally_compact_decode_twice, P, lds, n_tiles, false);
             else if (e->compact_plan_once)
@@ -1062,28 +1211,28 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         } else if (maskq) {
             // -Q: tally_tiled with the QUAL fetch and the per-position mask, for every -r (later passes as below)
             if (do_kmer)
-                rc = kmer_lds ? launch_flat(e, PREP_TILED_PSS_KMER_LDS_BQ, tally_tiled<true, true, true, false, true>, P, lds, n_tiles, true)
-                              : launch_flat(e, PREP_TILED_PSS_KMER_BQ, tally_tiled<true, true, false, false, true>, P, lds, n_tiles, false);
+                rc = kmer_lds ? launch_tiled<true, true, true, false, true>(e, PREP_TILED_PSS_KMER_LDS_BQ, P, lds, n_tiles)
+                              : launch_tiled<true, true, false, false, true>(e, PREP_TILED_PSS_KMER_BQ, P, lds, n_tiles);
             else
-                rc = launch_flat(e, PREP_TILED_PSS_BQ, tally_tiled<true, false, false, false, true>, P, lds, n_tiles, false);
+                rc = launch_tiled<true, false, false, false, true>(e, PREP_TILED_PSS_BQ, P, lds, n_tiles);
             for (uint32_t pass = 1; pass < n_passes && rc == PSSBAM_OK; pass++) {
                 P.row_base = pass * TILED_ROWS;
-                rc = launch_flat(e, PREP_TILED_PSS_LATER_BQ, tally_tiled<true, false, false, true, true>, P, lds, n_tiles, false);
+                rc = launch_tiled<true, false, false, true, true>(e, PREP_TILED_PSS_LATER_BQ, P, lds, n_tiles);
             }
         } else {
             if (do_pss && do_kmer)
-                rc = kmer_lds ? launch_flat(e, PREP_TILED_PSS_KMER_LDS, tally_tiled<true, true, true, false>, P, lds, n_tiles, true)
-                              : launch_flat(e, PREP_TILED_PSS_KMER, tally_tiled<true, true, false, false>, P, lds, n_tiles, false);
+                rc = kmer_lds ? launch_tiled<true, true, true, false, false>(e, PREP_TILED_PSS_KMER_LDS, P, lds, n_tiles)
+                              : launch_tiled<true, true, false, false, false>(e, PREP_TILED_PSS_KMER, P, lds, n_tiles);
             else if (do_pss)
-                rc = launch_flat(e, PREP_TILED_PSS, tally_tiled<true, false, false, false>, P, lds, n_tiles, false);
+                rc = launch_tiled<true, false, false, false, false>(e, PREP_TILED_PSS, P, lds, n_tiles);
             else
-                rc = kmer_lds ? launch_flat(e, PREP_TILED_KMER_LDS, tally_tiled<false, true, true, false>, P, lds, n_tiles, true)
-                              : launch_flat(e, PREP_TILED_KMER, tally_tiled<false, true, false, false>, P, lds, n_tiles, false);
+                rc = kmer_lds ? launch_tiled<false, true, true, false, false>(e, PREP_TILED_KMER_LDS, P, lds, n_tiles)
+                              : launch_tiled<false, true, false, false, false>(e, PREP_TILED_KMER, P, lds, n_tiles);
             // rows 32.. of a large -r: further passes over the same block, substitution rows only
             // (the status counters and the k-mer tally belong to pass 0)
             for (uint32_t pass = 1; pass < n_passes && rc == PSSBAM_OK; pass++) {
                 P.row_base = pass * TILED_ROWS;
-                rc = launch_flat(e, PREP_TILED_PSS_LATER, tally_tiled<true, false, false, true>, P, lds, n_tiles, false);
+                rc = launch_tiled<true, false, false, true, false>(e, PREP_TILED_PSS_LATER, P, lds, n_tiles);
             }
         }
         if (rc != PSSBAM_OK) return rc;

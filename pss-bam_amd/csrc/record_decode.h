@@ -72,6 +72,16 @@ struct TallyParams {
     // -Q: a read base whose QUAL byte is below this adds nothing to the substitution tables (0 = off); read only by
     // the MASKQ instantiations of the tiled kernels and by the lane-per-read kernels
     uint32_t min_bq;
+    // -T: the region filter (NULL region_info = off).  region_info is a sibling of ref_info, indexed the same way (entry
+    // n_ref answers RNAME "*"): {first interval of the contig in region_iv, its interval count, first word of its grid in
+    // region_grid, 0}.  region_iv holds every contig's merged intervals {start, end} -- 0-based, half open, disjoint,
+    // non-adjacent, ascending -- and region_grid one word per 2^region_shift bases of a contig that has intervals: the
+    // index (within the contig) of the first interval whose end lies beyond the bin's first base, and one closing word
+    // = the count.  Read by the REGIONS instantiations of the tiled kernels and by the lane-per-read kernels.
+    const uint4 *region_info;
+    const uint32_t *region_grid;
+    const uint2 *region_iv;
+    uint32_t region_shift;
 };
 
 // stats slots, must match include/pssbam_hip.h.  The kernels count EVENTS only: every launch
@@ -591,10 +601,66 @@ __device__ __forceinline__ void flush_events(bool DO_PSS, bool DO_KMER, const Ta
     }
 }
 
+// ---- -T: does any region of the record's contig meet its alignment? -----------------------------
+// Only candidates are asked about, and a candidate's CIGAR is exactly <len>M (plan_head: `common`, op_len == L for the
+// pss filters and == Lk for fragkon's), so the alignment is [pos, pos + (cigar0 >> 4)) for both tools and no CIGAR walk
+// is needed.  The merged intervals of a contig are disjoint and ascending, hence so are their ends: with j the first
+// interval whose end lies beyond a, [a, b) meets a region iff j exists and start[j] < b.  The grid brackets j: the word
+// of a's bin is a lower bound (its bin starts at or before a), the next word an upper bound (its bin starts behind a).
+struct RegionQuery {
+    uint4 d;           // the contig's region_info entry
+    uint32_t lo, hi;   // j lies in lo..hi
+    uint32_t a, b;
+};
+constexpr uint32_t REGION_SCAN_MAX = 8;   // more intervals than this between the two grid words: binary search
+
+__device__ __forceinline__ uint32_t region_ref_index(const TallyParams &P, const RecHdr &h) {
+    return (uint32_t)h.ref_id < (uint32_t)P.n_ref ? (uint32_t)h.ref_id : (uint32_t)P.n_ref;   // the entry plan_head looked up
+}
+// the two grid words of the query (8 adjacent bytes).  A candidate ends inside its contig (s + L + 2 <= length), so its
+// bin and the one behind it are inside the contig's grid.
+__device__ __forceinline__ void region_grid_load(const TallyParams &P, const RecHdr &h, const uint4 d, RegionQuery &q) {
+    q.d = d;
+    q.a = (uint32_t)h.pos;
+    q.b = q.a + (h.cigar0 >> 4);
+    q.lo = q.hi = 0u;
+    if (d.y) {
+        const uint32_t *g = P.region_grid + d.z + (q.a >> P.region_shift);
+        q.lo = g[0];
+        q.hi = g[1];
+    }
+}
+__device__ __forceinline__ bool region_resolve(const TallyParams &P, const RegionQuery &q) {
+    if (!q.d.y) return false;   // a contig without intervals tallies nothing
+    const uint2 *iv = P.region_iv + q.d.x;
+    uint32_t j = q.lo;
+    if (q.hi - q.lo > REGION_SCAN_MAX) {   // first interval of lo..hi-1 with end > a, else hi
+        uint32_t l = q.lo, r = q.hi;
+        while (l < r) {
+            const uint32_t m = (l + r) >> 1;
+            if (iv[m].y > q.a) r = m; else l = m + 1u;
+        }
+        j = l;
+    } else {
+        while (j < q.hi && iv[j].y <= q.a) j++;
+    }
+    return j < q.d.y && iv[j].x < q.b;
+}
+// the whole lookup for one candidate (lane-per-read kernels)
+__device__ __forceinline__ bool region_hit(const TallyParams &P, const RecHdr &h) {
+    RegionQuery q;
+    region_grid_load(P, h, P.region_info[region_ref_index(P, h)], q);
+    return region_resolve(P, q);
+}
+
 // both steps with the two context bytes fetched from global memory (lane-per-read kernels)
-template <bool DO_PSS, bool DO_KMER, class Src>
+// MAY_HAVE_REGIONS: the -T filter, decided at run time (a NULL table pointer = off).  The one-lane overflow paths of
+// the tiled kernels pass their kernel's REGIONS flag, so the instantiations without it contain none of it.
+template <bool DO_PSS, bool DO_KMER, bool MAY_HAVE_REGIONS = true, class Src>
 __device__ Plan make_plan(const TallyParams &P, const Src &src, const RecHdr &h) {
     Plan pl = plan_head<DO_PSS, DO_KMER>(P, src, h, RefsGlobal{P.ref_info});
+    // a candidate whose alignment meets no region is filtered
+    if (MAY_HAVE_REGIONS && P.region_info && (pl.pss_cand || pl.fk5 || pl.fk3) && !region_hit(P, h)) pl.pss_cand = pl.fk5 = pl.fk3 = false;
     if (DO_PSS) {
         uint32_t l1 = 0, r1 = 0;
         if (pl.pss_cand) {

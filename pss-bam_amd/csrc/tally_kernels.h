@@ -46,6 +46,10 @@
 //                 compare).  k <= KMER_LDS_MAX_K: one 2 * 4^k-word LDS histogram per plane slot of the launch;
 //                 larger k: global 64-bit atomics straight into the plane's bins.
 //
+//  REGIONS twins of the three tiled kernels (-T): every candidate's alignment is looked up in the region table
+//                 (record_decode.h: region_grid_load / region_resolve) in CODES-A; a read that meets no region is
+//                 filtered.  The lane-per-read kernels do the same in make_plan when the table pointer is set.
+//
 // Integer/byte work only: no MFMA anywhere (the bound is HBM bandwidth).
 #pragma once
 
@@ -263,13 +267,13 @@ __device__ __forceinline__ void stage_tile_dma(const uint8_t *recs, uint64_t rec
 // nothing.  It reads the kernel arguments through a pointer to the kernarg segment (taken in
 // the kernel): a reference to the kernel's by-value copy would force that whole struct into
 // scratch memory.
-template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool MASKQ = false>
+template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool MASKQ = false, bool REGIONS = false>
 __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyParams *kernarg, uint32_t o0,
                                                                     uint32_t o1, uint32_t *table, uint32_t *lds_kmer) {
     const TallyParams &P = *kernarg;
     GlobalBytes gsrc{P.recs + o0};
     const RecHdr gh = decode_hdr(gsrc, o1 - o0);
-    const Plan gpl = make_plan<DO_PSS, DO_KMER>(P, gsrc, gh);
+    const Plan gpl = make_plan<DO_PSS, DO_KMER, REGIONS>(P, gsrc, gh);
     if (DO_PSS && (gpl.pss_fwd || gpl.pss_rev)) tally_pss_record<MASKQ>(P, LdsTableColumnMajor{table, P.row_base}, gsrc, gh, gpl);
     bool kfail = false;
     if (DO_KMER && (gpl.fk5 || gpl.fk3)) kfail = tally_kmer_record<LDS_KMER>(P, gpl, lds_kmer);
@@ -325,13 +329,13 @@ __device__ __forceinline__ bool tally_kmer_record_plane(const TallyParams &P, co
     return !good;
 }
 // tally_overflow_record for tally_tiled_kmer_planes
-template <PlaneSel PLANES, bool LDS_KMER>
+template <PlaneSel PLANES, bool LDS_KMER, bool REGIONS = false>
 __device__ __attribute__((noinline)) uint32_t tally_overflow_record_kmer_planes(const TallyParams *kernarg, const PlaneParams *gk,
                                                                                 uint32_t o0, uint32_t o1, uint32_t *lds_kmer) {
     const TallyParams &P = *kernarg;
     GlobalBytes gsrc{P.recs + o0};
     const RecHdr gh = decode_hdr(gsrc, o1 - o0);
-    const Plan gpl = make_plan<false, true>(P, gsrc, gh);
+    const Plan gpl = make_plan<false, true, REGIONS>(P, gsrc, gh);
     bool kfail = false;
     if (gpl.fk5 || gpl.fk3) kfail = tally_kmer_record_plane<LDS_KMER>(P, *gk, gpl, record_plane<PLANES, true>(gsrc, gh, gpl, *gk), lds_kmer);
     return record_events(false, true, gpl, kfail);
@@ -339,13 +343,13 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record_kmer_planes(
 
 // The same for tally_tiled_planes (substitution tables only): the record's plane slot of this
 // launch, if it has one, decides where its counts go.
-template <PlaneSel PLANES, bool MASKQ = false>
+template <PlaneSel PLANES, bool MASKQ = false, bool REGIONS = false>
 __device__ __attribute__((noinline)) uint32_t tally_overflow_record_planes(const TallyParams *kernarg, const PlaneParams *gk,
                                                                            uint32_t o0, uint32_t o1, uint32_t *table) {
     const TallyParams &P = *kernarg;
     GlobalBytes gsrc{P.recs + o0};
     const RecHdr gh = decode_hdr(gsrc, o1 - o0);
-    const Plan gpl = make_plan<true, false>(P, gsrc, gh);
+    const Plan gpl = make_plan<true, false, REGIONS>(P, gsrc, gh);
     if (gpl.pss_fwd || gpl.pss_rev) {
         const uint32_t slot = record_plane<PLANES>(gsrc, gh, gpl, *gk) - gk->plane0;
         if (slot < gk->n_slots) tally_pss_record<MASKQ>(P, LdsTableColumnMajor{table + slot * GROUP_PLANE_WORDS, P.row_base}, gsrc, gh, gpl);
@@ -380,7 +384,15 @@ __device__ __forceinline__ uint32_t base_quality_mask(uint32_t x, uint32_t q4) {
 // that line up with the end's window and CODES-B turns them into a 0x00 / 0xFF byte per position that is ORed into
 // the read-side code: a position whose base quality is below P.min_bq lands on a trash code, exactly like a read
 // base that is not A/C/G/T.  The instantiations without MASKQ contain none of it.
-template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS, PlaneSel PLANES = PLANES_NONE, bool MASKQ = false>
+//
+// REGIONS (-T, P.region_info != NULL): every candidate's alignment is looked up in the region table in CODES-A.  The
+// contig's descriptor is fetched right behind plan_head, the two grid words behind the window gathers -- so the round
+// trips overlap -- and the interval compare is resolved where the gathered registers are first used, in front of the
+// next tile's DMA: a candidate that meets no region stops being one before -U/-D is decided and before the k-mer add.
+// Both lanes of a read's pair ask (same addresses: one request to the memory system).  Only the record's fixed fields
+// are read, so prefixes are staged as without it.  The instantiations without REGIONS contain none of it.
+template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS, PlaneSel PLANES = PLANES_NONE, bool MASKQ = false,
+          bool REGIONS = false>
 __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const TallyParams *kernarg,
                                                  uint8_t *__restrict__ stage, uint8_t *__restrict__ sheet,
                                                  uint32_t *__restrict__ table,
@@ -490,6 +502,12 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         // this end's reference window, issued for every candidate before the -U/-D test so the
         // test costs no extra memory round trip
         const bool cand = DO_PSS && pl.pss_cand;
+        // -T: the contig's region descriptor, first of the lookup's dependent loads
+        const bool rcand = REGIONS && (pl.pss_cand || pl.fk5 || pl.fk3);
+        uint4 rdesc = make_uint4(0u, 0u, 0u, 0u);
+        if constexpr (REGIONS) {
+            if (rcand) rdesc = P.region_info[region_ref_index(P, h)];
+        }
         // 32 window positions = 16 bytes of the 4-bit packed reference (+ up to 7 nibbles of
         // misalignment): five dwords, one dwordx4 + one dword gather
         uint32_t gq[5] = {0u, 0u, 0u, 0u, 0u};
@@ -550,7 +568,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         // other loads: the left-end lane owns the window at s-k/2.. (5' k-mer of a forward read, 3'
         // of a reverse read), the right-end lane the one at ..s+L+k/2 (fragkon.c:152-181)
         const uint32_t kwhich = e ^ (pl.rev ? 1u : 0u);  // 0 = 5' table, 1 = 3' table
-        const bool kmer_try = DO_KMER && (kwhich ? pl.fk3 : pl.fk5) && !(ablate & 16u);
+        bool kmer_try = DO_KMER && (kwhich ? pl.fk3 : pl.fk5) && !(ablate & 16u);
         uint32_t kw[3] = {0u, 0u, 0u};
         uint32_t ksh = 0u;
         if (kmer_try) {
@@ -561,6 +579,11 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
 #pragma unroll
             for (int k = 0; k < 3; k++) kw[k] = kq.v[k];
             ksh = 4u * (uint32_t)(ka & 7ull);
+        }
+        // -T: the two grid words, issued behind the window gathers (the descriptor has had their issue time to arrive)
+        RegionQuery rq{};
+        if constexpr (REGIONS) {
+            if (rcand) region_grid_load(P, h, rdesc, rq);
         }
         uint32_t kplane = 0u;   // k-mer planes: the record's plane, resolved by the pair's left-end lane
         if constexpr (KPLANES) {
@@ -577,9 +600,9 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         }
         uint32_t ev_over = 0u;  // events of a record handled by the out-of-line path
         if (in_tile && !in_stage && e == 0u) {
-            if constexpr (KPLANES) ev_over = tally_overflow_record_kmer_planes<PLANES, LDS_KMER>(kernarg, gk, o0, o1, lds_kmer);
-            else if constexpr (GROUPED) ev_over = tally_overflow_record_planes<PLANES, MASKQ>(kernarg, gk, o0, o1, table);
-            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ>(kernarg, o0, o1, table, lds_kmer);
+            if constexpr (KPLANES) ev_over = tally_overflow_record_kmer_planes<PLANES, LDS_KMER, REGIONS>(kernarg, gk, o0, o1, lds_kmer);
+            else if constexpr (GROUPED) ev_over = tally_overflow_record_planes<PLANES, MASKQ, REGIONS>(kernarg, gk, o0, o1, table);
+            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS>(kernarg, o0, o1, table, lds_kmer);
             if (pass0) atomicAdd(&lds_delta[ST_SLOW_PATH], 1);
         }
         // First use of the gathered registers happens HERE, before the next tile's DMA is issued:
@@ -602,6 +625,15 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         if constexpr (MASKQ) {   // the QUAL bytes are in registers before `stage` is released to the next tile's DMA
 #pragma unroll
             for (int k = 0; k < 9; k++) asm volatile("" : "+v"(qq[k]));
+        }
+        if constexpr (REGIONS) {
+            // -T, resolved here for the same reason: its interval loads must not wait behind the DMA.  A candidate that
+            // meets no region is filtered (PSS_FILTERED / KMER_FILTERED through record_events); its gathered windows
+            // are simply not used.
+            if (rcand && !region_resolve(P, rq)) {
+                pl.pss_cand = pl.fk5 = pl.fk3 = false;
+                kmer_try = false;
+            }
         }
         __syncthreads();
 
@@ -875,7 +907,7 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record_compact(cons
     const TallyParams &P = *kernarg;
     GlobalBytes gsrc{P.recs + o0};
     const RecHdr gh = decode_hdr(gsrc, o1 - o0);
-    const Plan gpl = make_plan<true, DO_KMER>(P, gsrc, gh);
+    const Plan gpl = make_plan<true, DO_KMER, false>(P, gsrc, gh);   // (-T launches never take tally_compact)
     if (gpl.pss_fwd || gpl.pss_rev) tally_pss_record(P, LdsTableCompact{table, ctx}, gsrc, gh, gpl);
     bool kfail = false;
     if (DO_KMER && (gpl.fk5 || gpl.fk3)) kfail = tally_kmer_record<LDS_KMER>(P, gpl, lds_kmer);
@@ -1318,7 +1350,7 @@ __global__ void __launch_bounds__(256) reduce_partials(const TallyParams P, uint
     if (sum) atomicAdd(dst, (unsigned long long)sum);
 }
 
-template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS = false, bool MASKQ = false>
+template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS = false, bool MASKQ = false, bool REGIONS = false>
 __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
@@ -1329,8 +1361,8 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P
     __shared__ uint4 refs_lds[REF_LDS_ENTRIES + 1];
     // the kernel's single argument, as it lies in the kernarg segment (for the out-of-line path)
     const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
-    tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta,
-                                                                             refs_lds);
+    tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
+                                                                                      lds_delta, refs_lds);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1346,7 +1378,7 @@ constexpr size_t PLANE_KERNARG_OFFSET = (sizeof(TallyParams) + alignof(PlanePara
 // this launch and the trash plane.  -G stages whole records (the RG tag sits behind QUAL); -S
 // stages prefixes through QUAL[0] as tally_tiled does (whole records with -R only).  Substitution
 // tables only.
-template <PlaneSel PLANES, bool LATER_PASS, bool MASKQ = false>
+template <PlaneSel PLANES, bool LATER_PASS, bool MASKQ = false, bool REGIONS = false>
 __global__ void __launch_bounds__(TILED_THREADS) tally_tiled_planes(const TallyParams P, const PlaneParams G) {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
@@ -1358,8 +1390,8 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled_planes(const TallyP
     const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
     const PlaneParams *gk = (const PlaneParams *)((const uint8_t *)kernarg + PLANE_KERNARG_OFFSET);
     uint32_t *table = (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces));
-    tally_tiled_body<true, false, false, LATER_PASS, PLANES, MASKQ>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta, refs_lds,
-                                                                    gk, grp_lds);
+    tally_tiled_body<true, false, false, LATER_PASS, PLANES, MASKQ, REGIONS>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta,
+                                                                             refs_lds, gk, grp_lds);
 }
 // dynamic LDS a plane launch may take: the CU's 160 KiB less the kernel's static objects (~10.6 KiB) and some margin
 constexpr uint32_t GROUPED_LDS_BUDGET = 148u * 1024u;
@@ -1430,7 +1462,7 @@ __global__ void __launch_bounds__(256) tally_simple_planes(const TallyParams P, 
 // k = 4 a plane is 2 KiB, so 64 length bins fit one launch.  Without LDS_KMER the bins go straight into the counter
 // block with 64-bit atomics and one launch serves every plane.  No code sheet and no substitution table: the
 // kernel's static LDS is the offsets, the deltas and the reference cache only.
-template <PlaneSel PLANES, bool LDS_KMER>
+template <PlaneSel PLANES, bool LDS_KMER, bool REGIONS = false>
 __global__ void __launch_bounds__(TILED_THREADS) tally_tiled_kmer_planes(const TallyParams P, const PlaneParams G) {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     __shared__ uint32_t toffs[2u * (TILED_MAX_T + 4u)];
@@ -1439,7 +1471,8 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled_kmer_planes(const T
     const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
     const PlaneParams *gk = (const PlaneParams *)((const uint8_t *)kernarg + PLANE_KERNARG_OFFSET);
     uint32_t *lds_kmer = (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces));
-    tally_tiled_body<false, true, LDS_KMER, false, PLANES>(P, kernarg, stage, nullptr, nullptr, toffs, lds_kmer, lds_delta, refs_lds, gk);
+    tally_tiled_body<false, true, LDS_KMER, false, PLANES, false, REGIONS>(P, kernarg, stage, nullptr, nullptr, toffs, lds_kmer, lds_delta,
+                                                                           refs_lds, gk);
 }
 // dynamic LDS a k-mer plane launch may take: the CU's 160 KiB less the kernel's static objects (~2.1 KiB) and some margin
 constexpr uint32_t KMER_PLANES_LDS_BUDGET = 156u * 1024u;

@@ -9,6 +9,8 @@
  * <prefix>.<tag>.fragkon.txt (the tags pss-bam uses), each what the same command prints for that plane alone:
  * on the records `samtools view -r <ID>` keeps, with `-l <lo> -L <hi>`, or with -F cut down to the label's
  * contigs -- from one pass over the input.  Without these options nothing differs from the reference front end.
+ * Added: -T <bed> tallies only the reads whose alignment overlaps an interval of the BED file, as in pss-bam: every
+ * table is what this command gives without -T for the input reduced by `samtools view -L <bed>`.
  */
 #include <ctype.h>
 #include <stdio.h>
@@ -21,6 +23,7 @@
 #include "frontend.h"
 #include "length_bins.h"
 #include "read_groups.h"
+#include "regions.h"
 #include "report.h"
 #include "sam-parse.h"
 
@@ -31,9 +34,9 @@ int main(int argc, char *argv[])
     unsigned long min_read_len = 0, max_read_len = 250000000;
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL;
     int by_group = 0;
-    const char *len_edges = NULL, *ctg_map = NULL;
+    const char *len_edges = NULL, *ctg_map = NULL, *bed_fn = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:k:l:L:q:mGS:C:o:")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:k:l:L:q:mGS:C:o:T:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -45,6 +48,7 @@ int main(int argc, char *argv[])
         case 'G': by_group = 1; break;
         case 'S': len_edges = optarg; break;
         case 'C': ctg_map = optarg; break;
+        case 'T': bed_fn = optarg; break;
         case 'o': out_prefix = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -89,6 +93,15 @@ int main(int argc, char *argv[])
         char err[200];
         if ((n_edges = pss_parse_length_edges(len_edges, min_read_len, max_read_len, edges, err, sizeof err)) < 0) {
             fprintf(stderr, "%s\n", err);
+            exit(1);
+        }
+    }
+    pss_regions bed;
+    memset(&bed, 0, sizeof bed);
+    if (bed_fn) {
+        char err[300];
+        if (pss_read_bed(bed_fn, &bed, err, sizeof err)) {
+            fprintf(stderr, "%s (%s)\n", err, bed_fn);
             exit(1);
         }
     }
@@ -151,6 +164,7 @@ int main(int argc, char *argv[])
     frontend_n_length_edges = n_edges;
     memcpy(frontend_length_edges, edges, (size_t)n_edges * sizeof *edges);
     if (ctg_map) frontend_contig_sets = &sets;
+    if (bed_fn) frontend_regions = &bed;
     /* HIP start-up, engines and the compressed BAM feed overlap the FASTA load (frontend.c) */
     frontend_warmup_start(&cfg, bam_fn, fasta_fn);
     Genome *genome = init_genome(fasta_fn);

@@ -31,6 +31,7 @@ int frontend_fast_exit = 0;
 int frontend_group_by_rg = 0;
 int frontend_n_length_edges = 0;
 int frontend_min_base_quality = 0;
+const pss_regions *frontend_regions = NULL;
 uint32_t frontend_length_edges[PSSBAM_MAX_LENGTH_BINS - 1];
 const frontend_contig_map *frontend_contig_sets = NULL;
 
@@ -38,6 +39,11 @@ const frontend_contig_map *frontend_contig_sets = NULL;
 static int send_contig_sets(pssbam_engine *e, const frontend_contig_map *m)
 {
     return m ? pssbam_engine_set_contig_sets(e, m->n_labels, m->n_names, (const char *const *)m->names, m->set_of) : 0;
+}
+
+static int send_regions(pssbam_engine *e, const pss_regions *r)
+{
+    return r ? pssbam_engine_set_regions(e, r->n_names, (const char *const *)r->names, r->n, r->name_of, r->starts, r->ends) : 0;
 }
 
 /* Start-up work that overlaps the caller's FASTA load.  The reference is serial by construction -- load the
@@ -62,6 +68,7 @@ static struct early_feed {
     char **rg_ids;                  /* -G: the BAM header's @RG IDs, set on every engine after create */
     int n_rg;
     int min_bq;                     /* -Q: the minimum base quality, set on every engine after create */
+    const pss_regions *regions;     /* -T: the intervals, set on every engine after create */
     int n_edges;                    /* -S: the length bin edges, set on every engine after create */
     uint32_t edges[PSSBAM_MAX_LENGTH_BINS - 1];
     const frontend_contig_map *sets; /* -C: the map, set on every engine after create */
@@ -138,7 +145,7 @@ static void *engine_make_main(void *arg)
 {
     engine_make_job *j = (engine_make_job *)arg;
     if (pssbam_engine_create(&j->cfg, j->out) || pssbam_engine_feed_open(*j->out, j->n_ref, EF.fasta_bytes) ||
-        (EF.min_bq > 0 && pssbam_engine_set_min_base_quality(*j->out, EF.min_bq)) ||
+        (EF.min_bq > 0 && pssbam_engine_set_min_base_quality(*j->out, EF.min_bq)) || send_regions(*j->out, EF.regions) ||
         (EF.n_rg > 0 && pssbam_engine_set_read_groups(*j->out, EF.n_rg, (const char *const *)EF.rg_ids)) ||
         (EF.n_edges > 0 && pssbam_engine_set_length_bins(*j->out, EF.n_edges, EF.edges)) || send_contig_sets(*j->out, EF.sets)) {
         j->rc = 1;
@@ -266,6 +273,7 @@ void frontend_warmup_start(const pssbam_config *cfg, const char *aln_path, const
             EF.cfg = *cfg;
             EF.n_edges = frontend_n_length_edges;
             EF.min_bq = frontend_min_base_quality;
+            EF.regions = frontend_regions;
             memcpy(EF.edges, frontend_length_edges, sizeof EF.edges);
             EF.sets = frontend_contig_sets;
             EF.cfg.pss.up_ctx = EF.up = dup_or_null(cfg->pss.up_ctx);
@@ -281,10 +289,11 @@ void frontend_warmup_start(const pssbam_config *cfg, const char *aln_path, const
 
 static int same_str(const char *a, const char *b) { return (!a && !b) || (a && b && strcmp(a, b) == 0); }
 
-/* the helper's engines carry the length bins, contig sets and minimum base quality that were set when it started */
+/* the helper's engines carry the length bins, contig sets, minimum base quality and regions that were set when it started */
 static int same_length_bins(void)
 {
     return EF.n_edges == frontend_n_length_edges && EF.sets == frontend_contig_sets && EF.min_bq == frontend_min_base_quality &&
+           EF.regions == frontend_regions &&
            memcmp(EF.edges, frontend_length_edges, (size_t)frontend_n_length_edges * sizeof *EF.edges) == 0;
 }
 
@@ -612,6 +621,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             c.device = have > 0 ? g % have : g;
             if (pssbam_engine_create(&c, &eng[g]) ||
                 (frontend_min_base_quality > 0 && pssbam_engine_set_min_base_quality(eng[g], frontend_min_base_quality)) ||
+                send_regions(eng[g], frontend_regions) ||
                 (frontend_n_length_edges > 0 && pssbam_engine_set_length_bins(eng[g], frontend_n_length_edges, frontend_length_edges)) ||
                 send_contig_sets(eng[g], frontend_contig_sets)) {
                 fprintf(stderr, "Error: GPU engine %d: %s\n", g, pssbam_last_error());

@@ -7,6 +7,7 @@
 
 #include "fasta-genome-io.h"
 #include "pssbam_hip.h"
+#include "regions.h"
 
 typedef struct run_result {
     unsigned long *fwd, *rev; /* (region_len+2)*16 each, or NULL */
@@ -31,6 +32,10 @@ extern int frontend_group_by_rg;
 /* pss-bam -Q: the minimum base quality (0: off); every engine gets it (pssbam_engine_set_min_base_quality).  Set
  * before frontend_warmup_start. */
 extern int frontend_min_base_quality;
+
+/* -T: the intervals of the BED file (regions.h; NULL: none); every engine gets them (pssbam_engine_set_regions), on
+ * every input path -- the filter lives in the engine.  Set before frontend_warmup_start. */
+extern const pss_regions *frontend_regions;
 
 /* pss-bam -S: the edges of the length bins (frontend_n_length_edges = 0: none); every engine gets them
  * (pssbam_engine_set_length_bins) and run_tally() returns one pair of tables per bin.  Set before

@@ -21,6 +21,9 @@
  * Added: -Q <q> leaves every read base whose Phred quality is below q (0..93; 0 = off) out of the tables: they
  * are the tables this command writes without -Q for the same input with those bases replaced by N.  The context
  * rows, the filters and the file names stay as they are.
+ * Added: -T <bed> tallies only the reads whose alignment overlaps an interval of the BED file (plain text; contig,
+ * 0-based start, end): every file written holds what this command writes without -T for the input reduced by
+ * `samtools view -L <bed>`.  The file names stay as they are.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -37,6 +40,7 @@
 #include "frontend.h"
 #include "length_bins.h"
 #include "read_groups.h"
+#include "regions.h"
 #include "report.h"
 
 int main(int argc, char *argv[])
@@ -48,9 +52,9 @@ int main(int argc, char *argv[])
     unsigned long min_read_len = 0, max_read_len = 250000000;
     const char *up_ctx = "ACGT", *down_ctx = "ACGT";
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL, *read_group = NULL;
-    const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL;
+    const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL, *bed_fn = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -66,6 +70,7 @@ int main(int argc, char *argv[])
         case 'S': len_edges = optarg; break;
         case 'C': ctg_map = optarg; break;
         case 'Q': min_bq_arg = optarg; break;
+        case 'T': bed_fn = optarg; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -124,6 +129,15 @@ int main(int argc, char *argv[])
         char err[200];
         if ((min_bq = pss_parse_min_base_quality(min_bq_arg, err, sizeof err)) < 0) {
             fprintf(stderr, "%s\n", err);
+            exit(1);
+        }
+    }
+    pss_regions bed;
+    memset(&bed, 0, sizeof bed);
+    if (bed_fn) {
+        char err[300];
+        if (pss_read_bed(bed_fn, &bed, err, sizeof err)) {
+            fprintf(stderr, "%s (%s)\n", err, bed_fn);
             exit(1);
         }
     }
@@ -193,6 +207,7 @@ int main(int argc, char *argv[])
     memcpy(frontend_length_edges, edges, (size_t)n_edges * sizeof *edges);
     if (ctg_map) frontend_contig_sets = &sets;
     frontend_min_base_quality = min_bq;
+    if (bed_fn) frontend_regions = &bed;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
      * load; only the tally launches wait for the genome (frontend.c) */
