@@ -36,6 +36,7 @@ extern "C" {
 #define PSSBAM_MAX_READ_GROUPS 4096  /* pssbam_engine_set_read_groups */
 #define PSSBAM_MAX_LENGTH_BINS 64    /* pssbam_engine_set_length_bins: at most 63 edges */
 #define PSSBAM_MAX_CONTIG_SETS 4096  /* pssbam_engine_set_contig_sets */
+#define PSSBAM_MAX_HIST_LENGTH 65535 /* pssbam_engine_set_length_histogram: the largest limit (lengths above it share one row) */
 #define PSSBAM_MAX_BASE_QUALITY 93   /* pssbam_engine_set_min_base_quality: the largest Phred value SAM text can print */
 #define PSSBAM_MAX_REGIONS (1 << 26) /* pssbam_engine_set_regions: intervals in one call */
 
@@ -296,6 +297,32 @@ int pssbam_engine_set_min_base_quality(pssbam_engine *e, int32_t q);
 int pssbam_engine_set_regions(pssbam_engine *e, int32_t n_names, const char *const *names, int64_t n_regions,
                               const int32_t *name_of, const uint32_t *starts, const uint32_t *ends);
 
+/* Fragment-length histogram (pss-bam -H) of the reads that are added to the substitution tables, counted in the
+ * tally kernel itself from the registers that hold a read's length and fate: no second pass, no extra bytes read.
+ * With limit max_len = M (1..PSSBAM_MAX_HIST_LENGTH; 0 switches the histogram off and the engine then launches
+ * exactly the kernels it launches without this call) the engine keeps two arrays of M + 2 counters, hf and hr.  For
+ * every record let L be the length -l / -L compare -- |TLEN| of a paired read, else the length of the SEQ text -- and
+ * b = min(L, M + 1): hf[b] += 1 when the record is added to the forward table, hr[b] += 1 when it is added to the
+ * reverse table.  An unpaired read that passes counts in both, a paired one in one; row M + 1 collects every longer
+ * read.  Every filter that decides "added" shapes the histogram as it shapes the tables (flags, the <L>M CIGAR rule,
+ * -q, -l / -L, -m, -U / -D, the contig-edge test, cfg.read_group, regions); a minimum base quality masks bases, not
+ * reads, and changes nothing.  So with OK(x..y) = PSSBAM_ST_PSS_OK of the same options run with -l x -L y (cut to the
+ * run's own -l / -L): on unpaired records hf[l] == hr[l] == OK(l..l); on any input hf[l] + hr[l] ==
+ * 2 * OK_unpaired(l..l) + OK_paired(l..l).  The tables, the status counters and the k-mer tables of a
+ * PSSBAM_TALLY_PSS | PSSBAM_TALLY_KMER engine stay bit-identical.
+ * Legal after create (or reset) and before the first tally launch; with pssbam_engine_feed_open that is any time
+ * before set_references.  Goes with cfg.read_group, a minimum base quality, regions and both tally masks together.
+ * PSSBAM_EINVAL for max_len outside the range, on an engine without PSSBAM_TALLY_PSS, and with read groups, length
+ * bins or contig sets set (those setters return PSSBAM_EINVAL once the histogram is on: one histogram per plane is
+ * not kept); PSSBAM_ESTATE once records have been tallied or the counter block has been bound (the block grows, see
+ * pssbam_engine_counters_device).  The setting survives pssbam_engine_reset; engines whose blocks are summed must all
+ * have been given the same limit. */
+int pssbam_engine_set_length_histogram(pssbam_engine *e, int32_t max_len);
+
+/* Drains the engine like pssbam_engine_finish and copies the two arrays, max_len + 2 words each; either pointer may
+ * be NULL.  PSSBAM_EINVAL when the histogram is off. */
+int pssbam_engine_finish_length_histogram(pssbam_engine *e, uint64_t *fwd, uint64_t *rev);
+
 /* The device-resident counter block [fwd | rev | k5 | k3 | stats] as one array of
  * n_u64 64-bit words, for a caller-side RCCL reduce across GPUs (sum, uint64).  With read groups it is
  * [fwd | rev | stats | fwd_0 | rev_0 | ... | fwd_n-1 | rev_n-1]: the leading fwd | rev are the unassigned
@@ -305,7 +332,10 @@ int pssbam_engine_set_regions(pssbam_engine *e, int32_t n_names, const char *con
  * the same with set s in group s's place, the leading fwd | rev the records on unlisted contigs.  A k-mer engine
  * with planes holds [k5 | k3 | stats | k5_0 | k3_0 | ... | k5_n-1 | k3_n-1]: the leading pair is plane 0, plane g's
  * pair (4^klen words each) starts at 2*4^klen + PSSBAM_ST_N + g*2*4^klen -- offsets that pass 2^32 words at large
- * klen.  The block is still summed across GPUs as one u64 array. */
+ * klen.  The block is still summed across GPUs as one u64 array.
+ * With a length histogram of limit M (pssbam_engine_set_length_histogram; never together with planes) the two
+ * arrays are appended: [fwd | rev | k5 | k3 | stats | hf | hr], hf at 2*(region_len+2)*16 + 2*4^klen + PSSBAM_ST_N
+ * (no k-mer term on a PSSBAM_TALLY_PSS engine), hr M + 2 words behind it, n_u64 larger by 2*(M+2). */
 int pssbam_engine_counters_device(pssbam_engine *e, void **d_counters, size_t *n_u64);
 
 /* Makes the engine accumulate into caller-owned device memory (n_u64 words, as reported

@@ -42,12 +42,13 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_genome_async", "pssbam_engine_genome_wait", "pssbam_engine_feed_open", "pssbam_feed_release",
     "pssbam_engine_set_read_groups", "pssbam_engine_finish_groups", "pssbam_engine_set_length_bins",
     "pssbam_engine_set_contig_sets", "pssbam_engine_finish_kmer_groups", "pssbam_engine_set_min_base_quality",
-    "pssbam_engine_set_regions",
+    "pssbam_engine_set_regions", "pssbam_engine_set_length_histogram", "pssbam_engine_finish_length_histogram",
 ]
 MAX_READ_GROUPS = 4096
 MAX_LENGTH_BINS = 64
 MAX_CONTIG_SETS = 4096
 MAX_BASE_QUALITY = 93
+MAX_HIST_LENGTH = 65535
 MAX_REGIONS = 1 << 26
 EBUSY = -7
 
@@ -114,6 +115,8 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_set_length_bins.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)]
     L.pssbam_engine_set_contig_sets.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]
     L.pssbam_engine_set_min_base_quality.argtypes = [C.c_void_p, C.c_int32]
+    L.pssbam_engine_set_length_histogram.argtypes = [C.c_void_p, C.c_int32]
+    L.pssbam_engine_finish_length_histogram.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_regions.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_counters_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.pssbam_engine_bind_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -187,12 +190,15 @@ class Engine:
     `contig_sets` = contig sets (pss-bam -C): one set of substitution tables per label, see set_contig_sets.
     `min_base_qual` = minimum base quality (pss-bam -Q): read bases below it are left out of the substitution tables,
     see set_min_base_quality; 0 = off.
+    `length_hist` = limit of the fragment-length histogram (pss-bam -H) of the reads added to the substitution tables,
+    see set_length_histogram; 0 = off.
     With `kmer` alone (no `pss`) the three split the k-mer tables instead (fragkon -G / -S / -C): every plane is a
     k5 / k3 pair, and the length bins go by the SEQ length and kmer's min_read_len / max_read_len."""
 
     def __init__(self, pss: dict | None = None, kmer: dict | None = None, read_group: str | None = None,
                  kernel: int = KERNEL_AUTO, device: int = -1, read_groups: list[str] | None = None,
-                 length_bins: list[int] | None = None, contig_sets=None, min_base_qual: int = 0):
+                 length_bins: list[int] | None = None, contig_sets=None, min_base_qual: int = 0,
+                 length_hist: int = 0):
         L = hip_lib()
         cfg = _Config()
         cfg.abi_version = 1
@@ -227,8 +233,11 @@ class Engine:
         self.length_bins: list[tuple[int, int]] = []
         self.contig_sets: list[str] = []
         self._min_base_qual = 0
+        self._length_hist = 0
         if min_base_qual:
             self.set_min_base_quality(min_base_qual)
+        if length_hist:
+            self.set_length_histogram(length_hist)
         if read_groups is not None:
             self.set_read_groups(read_groups)
         if length_bins is not None:
@@ -247,6 +256,27 @@ class Engine:
     def min_base_qual(self) -> int:
         """the minimum base quality in force (0 = off)"""
         return self._min_base_qual
+
+    def set_length_histogram(self, max_len: int):
+        """pss-bam -H: counts the length (the one -l / -L compare) of every read that is added to the forward / reverse
+        table, in the tally kernel itself; lengths above max_len (1..65535, 0 = off) share one last row.  Not with read
+        groups, length bins or contig sets.  Before the first tally (after feed_open: before set_references) and before
+        bind_counters: the counter block grows by 2 * (max_len + 2) words.  Survives reset."""
+        _chk(self._L.pssbam_engine_set_length_histogram(self._h, int(max_len)))
+        self._length_hist = int(max_len)
+
+    @property
+    def length_hist(self) -> int:
+        """the limit of the length histogram in force (0 = off)"""
+        return self._length_hist
+
+    def finish_length_hist(self) -> tuple[np.ndarray, np.ndarray]:
+        """(fwd, rev): u64 arrays of max_len + 2 rows -- row l = reads of length l added to that table, the last row
+        every longer read (drains like finish)"""
+        fwd = np.zeros(self._length_hist + 2, dtype=np.uint64)
+        rev = np.zeros_like(fwd)
+        _chk(self._L.pssbam_engine_finish_length_histogram(self._h, fwd.ctypes.data, rev.ctypes.data))
+        return fwd, rev
 
     def set_regions(self, names, name_of, starts, ends):
         """pss-bam -T / fragkon -T: only records whose alignment overlaps one of the intervals are tallied -- the tables
@@ -520,6 +550,9 @@ class Engine:
         lay["contig_sets"] = [{"label": s, "fwd": base + k * 2 * rows * 16, "rev": base + k * 2 * rows * 16 + rows * 16}
                               for k, s in enumerate(self.contig_sets)]
         lay["n_u64"] = base + (len(self.read_groups) + len(self.length_bins) + len(self.contig_sets)) * 2 * rows * 16
+        if self._length_hist:   # the length histogram (never together with planes): hf | hr behind the stats
+            lay["hist_fwd"], lay["hist_rev"] = base, base + self._length_hist + 2
+            lay["n_u64"] = base + 2 * (self._length_hist + 2)
         return lay
 
     def genome_kmer_count(self, klen: int) -> np.ndarray:

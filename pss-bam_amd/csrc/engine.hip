@@ -164,6 +164,8 @@ enum PrepSlot : int {
     // -Q (min_bq > 0): the MASKQ instantiations, in the order of their unmasked twins
     PREP_TILED_PSS_BQ, PREP_TILED_PSS_LATER_BQ, PREP_TILED_PSS_KMER_BQ, PREP_TILED_PSS_KMER_LDS_BQ,
     PREP_PLANES_RG_BQ, PREP_PLANES_RG_LATER_BQ, PREP_PLANES_LEN_BQ, PREP_PLANES_LEN_LATER_BQ, PREP_PLANES_REF_BQ, PREP_PLANES_REF_LATER_BQ,
+    // -H (hist_max > 0): the HIST instantiations of pass 0, without and with -Q
+    PREP_TILED_PSS_H, PREP_TILED_PSS_KMER_H, PREP_TILED_PSS_KMER_LDS_H, PREP_TILED_PSS_H_BQ, PREP_TILED_PSS_KMER_H_BQ, PREP_TILED_PSS_KMER_LDS_H_BQ,
     PREP_N   // -T: the REGIONS instantiation of slot s is memo slot PREP_N + s
 };
 
@@ -223,6 +225,9 @@ struct pssbam_engine {
     std::vector<std::string> ref_names;   // the names of the last set_references (-C set after it packs them again)
     bool tallied = false;   // a tally launch since create / reset
     uint32_t min_bq = 0;    // -Q: read bases with a QUAL byte below this are left out of the tables (pssbam_engine_set_min_base_quality)
+    // -H (pssbam_engine_set_length_histogram): hf | hr, hist_max + 2 words each, at off_hist = the end of the block as it is without them
+    uint32_t hist_max = 0, off_hist = 0;
+    int env_hist_lds_bins = -1;   // PSSBAM_HIST_LDS_BINS: at most this many bins of each array in LDS (tests: the global-atomic path with short reads)
     // -T (pssbam_engine_set_regions): contig name -> its merged intervals, kept on the host; the per-refID device table is
     // packed from it whenever the reference list or the map changes (pack_regions)
     std::unordered_map<std::string, std::vector<uint2>> regions;
@@ -424,6 +429,7 @@ extern "C" int pssbam_engine_create(const pssbam_config *cfg, pssbam_engine **ou
     e->env_grid_wgs = env_int("PSSBAM_GRID_WGS");
     e->env_pieces = env_int("PSSBAM_PIECES");
     e->env_group_slots = env_int("PSSBAM_GROUP_SLOTS");
+    if (getenv("PSSBAM_HIST_LDS_BINS")) e->env_hist_lds_bins = std::max(env_int("PSSBAM_HIST_LDS_BINS"), 0);
     if (const int g = env_int("PSSBAM_REGION_GRID_SHIFT")) e->region_shift = (uint32_t)std::min(std::max(g, 2), 20);
     if (getenv("PSSBAM_COMPACT")) e->use_compact = env_int("PSSBAM_COMPACT") != 0;
     if (getenv("PSSBAM_COMPACT_PLAN_ONCE")) e->compact_plan_once = env_int("PSSBAM_COMPACT_PLAN_ONCE") != 0;
@@ -891,11 +897,20 @@ static int launch_flat(pssbam_engine *e, PrepSlot slot, K kernel, TallyParams &P
 }
 
 // launch_flat of one tally_tiled instantiation, or of its REGIONS twin when the launch carries a region table (-T)
-template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER, bool MASKQ>
+template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER, bool MASKQ, bool HIST = false>
 static int launch_tiled(pssbam_engine *e, PrepSlot slot, TallyParams &P, uint32_t lds, uint32_t n_tiles) {
     if (P.region_info)
-        return launch_flat(e, (PrepSlot)(slot + PREP_N), tally_tiled<DO_PSS, DO_KMER, LDS_KMER, LATER, MASKQ, true>, P, lds, n_tiles, LDS_KMER);
-    return launch_flat(e, slot, tally_tiled<DO_PSS, DO_KMER, LDS_KMER, LATER, MASKQ, false>, P, lds, n_tiles, LDS_KMER);
+        return launch_flat(e, (PrepSlot)(slot + PREP_N), tally_tiled<DO_PSS, DO_KMER, LDS_KMER, LATER, MASKQ, true, HIST>, P, lds, n_tiles, LDS_KMER);
+    return launch_flat(e, slot, tally_tiled<DO_PSS, DO_KMER, LDS_KMER, LATER, MASKQ, false, HIST>, P, lds, n_tiles, LDS_KMER);
+}
+
+// Pass 0 of a launch with the length histogram (-H): the HIST instantiation for the launch's tallies and -Q state
+template <bool MASKQ>
+static int launch_tiled_hist(pssbam_engine *e, TallyParams &P, bool do_kmer, bool kmer_lds, uint32_t lds, uint32_t n_tiles) {
+    constexpr int bq = MASKQ ? PREP_TILED_PSS_H_BQ - PREP_TILED_PSS_H : 0;
+    if (!do_kmer) return launch_tiled<true, false, false, false, MASKQ, true>(e, (PrepSlot)(PREP_TILED_PSS_H + bq), P, lds, n_tiles);
+    return kmer_lds ? launch_tiled<true, true, true, false, MASKQ, true>(e, (PrepSlot)(PREP_TILED_PSS_KMER_LDS_H + bq), P, lds, n_tiles)
+                    : launch_tiled<true, true, false, false, MASKQ, true>(e, (PrepSlot)(PREP_TILED_PSS_KMER_H + bq), P, lds, n_tiles);
 }
 
 // One (row pass, plane pass) launch of tally_tiled_planes and its reduce_partials_grouped
@@ -1034,6 +1049,11 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
     P.min_bq = do_pss ? e->min_bq : 0u;
     const bool maskq = P.min_bq > 0;   // -Q: the MASKQ instantiations of the tiled kernels; min_bq == 0 launches what it always did
     const bool regions = e->has_regions;   // -T: the REGIONS instantiations; without regions the engine launches what it always did
+    const bool hist = do_pss && e->hist_max > 0;   // -H: the HIST instantiations; without a histogram the engine launches what it always did
+    if (hist) {
+        P.hist_max = e->hist_max;
+        P.off_hist = e->off_hist;
+    }
     if (regions) {
         P.region_info = e->d_region_info;
         P.region_grid = e->d_region_grid;
@@ -1195,9 +1215,9 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                     rc = launch_pass[maskq][e->planes - PLANES_RG][pass > 0](e, P, G, tiled_grouped_lds_bytes(T, pieces, G.n_slots), n_tiles);
                 }
             }
-        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions) {
+        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions && !hist) {
             // -r N <= 16 (2 context rows + 16 positions): the short-window variant, one pass (it stages prefixes only
-            // and has no QUAL path: -R and -Q go to tally_tiled; so does -T, whose lookup only tally_tiled carries)
+            // and has no QUAL path: -R and -Q go to tally_tiled; so do -T and -H, whose arms only tally_tiled carries)
             if (!do_kmer && getenv("PSSBAM_COMPACT_DECODE_TWICE"))   // diagnostics: what the shared header decode costs
                 rc = launch_flat(e, PREP_COMPACT_DECODE_TWICE, tally_compact_decode_twice, P, lds, n_tiles, false);
             else if (e->compact_plan_once)
@@ -1208,6 +1228,18 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                 rc = !do_kmer  ? launch_flat(e, PREP_COMPACT, tally_compact<false, false, false>, P, lds, n_tiles, false)
                      : kmer_lds ? launch_flat(e, PREP_COMPACT_KMER_LDS, tally_compact<true, true, false>, P, lds, n_tiles, true)
                                 : launch_flat(e, PREP_COMPACT_KMER, tally_compact<true, false, false>, P, lds, n_tiles, false);
+        } else if (hist) {
+            // -H: pass 0 is the HIST instantiation of tally_tiled, with the LDS part of the two arrays behind the staging
+            // buffer (at most HIST_LDS_MAX_BINS bins each: 8 KiB); the later passes of a large -r count nothing again
+            P.hist_lds_bins = std::min(e->hist_max + 2u, HIST_LDS_MAX_BINS);
+            if (e->env_hist_lds_bins >= 0) P.hist_lds_bins = std::min(P.hist_lds_bins, (uint32_t)e->env_hist_lds_bins);
+            const uint32_t lds_h = lds + hist_lds_bytes(P.hist_lds_bins);
+            rc = maskq ? launch_tiled_hist<true>(e, P, do_kmer, kmer_lds, lds_h, n_tiles) : launch_tiled_hist<false>(e, P, do_kmer, kmer_lds, lds_h, n_tiles);
+            for (uint32_t pass = 1; pass < n_passes && rc == PSSBAM_OK; pass++) {
+                P.row_base = pass * TILED_ROWS;
+                rc = maskq ? launch_tiled<true, false, false, true, true>(e, PREP_TILED_PSS_LATER_BQ, P, lds, n_tiles)
+                           : launch_tiled<true, false, false, true, false>(e, PREP_TILED_PSS_LATER, P, lds, n_tiles);
+            }
         } else if (maskq) {
             // -Q: tally_tiled with the QUAL fetch and the per-position mask, for every -r (later passes as below)
             if (do_kmer)
@@ -1469,6 +1501,7 @@ extern "C" int pssbam_engine_finish_kmer_groups(pssbam_engine *e, int32_t group,
 // zeroed (nothing has been counted yet).  The old block may still be named by work queued on the stream (the compressed
 // feed): it is retired, not freed.  `what` names the caller's planes in the messages.
 static int set_planes(pssbam_engine *e, PlaneSel sel, uint32_t n_planes, const char *what) {
+    if (e->hist_max) return fail(PSSBAM_EINVAL, "%s and the length histogram exclude each other", what);
     const bool kmer = e->cfg.tally_mask == PSSBAM_TALLY_KMER;
     if (e->cfg.tally_mask != PSSBAM_TALLY_PSS && !kmer)
         return fail(PSSBAM_EINVAL, "%s split the substitution tables or the k-mer tables, not both (PSSBAM_TALLY_PSS | PSSBAM_TALLY_KMER)", what);
@@ -1556,6 +1589,42 @@ extern "C" int pssbam_engine_set_min_base_quality(pssbam_engine *e, int32_t q) {
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the minimum base quality after create or reset, before the first tally");
     if ((e->min_bq > 0) != (q > 0)) e->dev_pieces = 0;   // whole records or prefixes are staged from now on: resampled at the next launch
     e->min_bq = (uint32_t)q;
+    return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_set_length_histogram(pssbam_engine *e, int32_t max_len) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (max_len < 0 || max_len > PSSBAM_MAX_HIST_LENGTH) return fail(PSSBAM_EINVAL, "length histogram limit %d outside 0..%d", max_len, PSSBAM_MAX_HIST_LENGTH);
+    if (!(e->cfg.tally_mask & PSSBAM_TALLY_PSS))
+        return fail(PSSBAM_EINVAL, "the length histogram counts the reads added to the substitution tables: the engine needs PSSBAM_TALLY_PSS");
+    if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the length histogram and read groups / length bins / contig sets exclude each other");
+    if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the length histogram after create or reset, before the first tally");
+    if (e->d_counters != e->d_counters_own) return fail(PSSBAM_ESTATE, "a caller-bound counter block cannot grow: set the length histogram before bind_counters");
+    if ((uint32_t)max_len == e->hist_max) return PSSBAM_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    // the block grows (or shrinks back) behind everything it holds without the histogram; zeroed: nothing has been counted
+    // yet.  The old block may still be named by work queued on the stream: retired, not freed (set_planes).
+    const uint64_t n_counters = (uint64_t)e->off_groups + (max_len ? 2ull * ((uint64_t)max_len + 2ull) : 0ull);
+    if (n_counters > 0xFFFFFFFFull) return fail(PSSBAM_EINVAL, "the counter block would pass 2^32 words");
+    unsigned long long *d_counters = nullptr;
+    HIP_TRY(hipMalloc(&d_counters, n_counters * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(d_counters, 0, n_counters * sizeof(unsigned long long), e->stream));
+    if (e->d_counters_own) e->retired.push_back(e->d_counters_own);
+    e->d_counters = e->d_counters_own = d_counters;
+    e->n_counters = n_counters;
+    e->hist_max = (uint32_t)max_len;
+    e->off_hist = e->off_groups;
+    return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_finish_length_histogram(pssbam_engine *e, uint64_t *fwd, uint64_t *rev) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (!e->hist_max) return fail(PSSBAM_EINVAL, "pssbam_engine_set_length_histogram has not been called");
+    const int rc = pssbam_engine_sync(e);
+    if (rc) return rc;
+    const size_t n = (size_t)e->hist_max + 2;
+    if (fwd) HIP_TRY(hipMemcpy(fwd, e->d_counters + e->off_hist, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (rev) HIP_TRY(hipMemcpy(rev, e->d_counters + e->off_hist + n, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return PSSBAM_OK;
 }
 

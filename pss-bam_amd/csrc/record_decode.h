@@ -82,6 +82,12 @@ struct TallyParams {
     const uint32_t *region_grid;
     const uint2 *region_iv;
     uint32_t region_shift;
+    // -H: the fragment-length histogram (hist_max = 0: off).  Two arrays of hist_max + 2 u64 counters in the counter
+    // block, hf at off_hist and hr right behind it; a read of pss length L (Plan::L) counts in bin min(L, hist_max + 1)
+    // of hf when it is added to the forward table and of hr when it is added to the reverse table.  The HIST
+    // instantiations of tally_tiled keep the first hist_lds_bins bins of each array in LDS (0: none, every bin goes
+    // straight to the counter block); the lane-per-read kernels read hist_max and off_hist only.
+    uint32_t hist_max, off_hist, hist_lds_bins;
 };
 
 // stats slots, must match include/pssbam_hip.h.  The kernels count EVENTS only: every launch

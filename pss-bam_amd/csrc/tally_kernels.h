@@ -50,6 +50,11 @@
 //                 (record_decode.h: region_grid_load / region_resolve) in CODES-A; a read that meets no region is
 //                 filtered.  The lane-per-read kernels do the same in make_plan when the table pointer is set.
 //
+//  HIST arm of tally_tiled (-H, pass 0 only): the fragment-length histogram of the reads that were added to the
+//                 tables, from the registers that hold the decision anyway (Plan::L, pss_fwd / pss_rev).  Equal
+//                 lengths are merged inside the wave first, the first HIST_LDS_MAX_BINS bins of each array live in
+//                 LDS behind the staging buffer and leave it once, at kernel end (hist_wave_add below).
+//
 // Integer/byte work only: no MFMA anywhere (the bound is HBM bandwidth).
 #pragma once
 
@@ -156,6 +161,58 @@ __device__ __forceinline__ bool tally_kmer_record(const TallyParams &P, const Pl
 }
 
 // ---------------------------------------------------------------------------------------
+// -H: fragment-length histogram of the reads added to the forward / reverse table
+// ---------------------------------------------------------------------------------------
+// hf / hr of the counter block hold hist_max + 2 bins each (bin hist_max + 1 = "longer").  The tiled kernel keeps bins
+// 0 .. hist_lds_bins - 1 of both arrays as u32 words in LDS, [hf | hr]; hist_lds_bins = min(hist_max + 2,
+// HIST_LDS_MAX_BINS), i.e. at most 8 KiB, which every limit up to 1022 fits whole.  Bins beyond that (a limit above
+// 1022 AND a read that long) go to the counter block with 64-bit atomics, merged inside the wave first.
+constexpr uint32_t HIST_LDS_MAX_BINS = 1024;
+__host__ __device__ inline uint32_t hist_lds_bytes(uint32_t lds_bins) { return 2u * lds_bins * 4u; }
+
+// n reads of bin b into hf (fwd) and / or hr (rev)
+__device__ __forceinline__ void hist_add(const TallyParams &P, uint32_t *hist_lds, uint32_t b, bool fwd, bool rev, uint32_t n) {
+    if (b < P.hist_lds_bins) {
+        if (fwd) atomicAdd(&hist_lds[b], n);
+        if (rev) atomicAdd(&hist_lds[P.hist_lds_bins + b], n);
+    } else {
+        if (fwd) atomicAdd(&P.counters[P.off_hist + b], (unsigned long long)n);
+        if (rev) atomicAdd(&P.counters[P.off_hist + P.hist_max + 2u + b], (unsigned long long)n);
+    }
+}
+__device__ __forceinline__ uint32_t hist_bin(const TallyParams &P, uint32_t L) { return min(L, P.hist_max + 1u); }
+
+// The whole wave's reads of one tile (called from uniform control flow; `on` = this lane holds a read that was added
+// to a table).  A modern library puts every read of the wave in ONE bin and an ancient-DNA library in a few dozen, so
+// lanes are merged by value before anything is added: the lanes that hold the first pending lane's (bin, fwd, rev)
+// are counted with one ballot and their leader adds the count once.  Two such rounds take the modes of the
+// distribution; what is left after them is spread thin, and for a bin that lives in LDS a lane's own add is then
+// cheaper than another round (an LDS atomic whose lanes meet on a word costs a cycle per lane, nothing more).  Bins
+// that live in the counter block are merged to the end: a wave sends at most one global atomic per distinct bin.
+__device__ __forceinline__ void hist_wave_add(const TallyParams &P, uint32_t *hist_lds, bool on, uint32_t L, bool fwd, bool rev) {
+    const uint32_t b = hist_bin(P, L);
+    const uint32_t key = (b << 2) | (fwd ? 2u : 0u) | (rev ? 1u : 0u);
+    const uint32_t lane = threadIdx.x & 63u;
+    bool pending = on && (fwd || rev);
+    for (uint32_t round = 0; __any(pending); round++) {
+        if (pending) {
+            if (round >= 2u && b < P.hist_lds_bins) {
+                hist_add(P, hist_lds, b, fwd, rev, 1u);
+                pending = false;
+            } else {
+                const uint32_t v = __builtin_amdgcn_readfirstlane(key);   // (of the lanes still in this branch)
+                const bool same = key == v;
+                const unsigned long long m = __ballot(same);
+                if (same) {
+                    pending = false;
+                    if (lane == (uint32_t)__ffsll((long long)m) - 1u) hist_add(P, hist_lds, b, fwd, rev, (uint32_t)__popcll(m));
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // tally_simple
 // ---------------------------------------------------------------------------------------
 // dynamic LDS: [2*(N+2)*16 u32 table, if LDS_TABLE]
@@ -181,6 +238,8 @@ __global__ void __launch_bounds__(256) tally_simple(const TallyParams P) {
         if (pl.pss_fwd || pl.pss_rev) {
             if (LDS_TABLE) tally_pss_record<true>(P, LdsTableRowMajor{dyn_lds, rows}, src, h, pl);
             else tally_pss_record<true>(P, GlobalTable{P.counters, P.off_rev}, src, h, pl);
+            // -H: straight into the counter block (hist_lds_bins is 0 in this kernel's launches)
+            if (P.hist_max) hist_add(P, nullptr, hist_bin(P, pl.L), pl.pss_fwd, pl.pss_rev, 1u);
         }
         bool kfail = false;
         if (pl.fk5 || pl.fk3) kfail = tally_kmer_record<false>(P, pl, nullptr);
@@ -267,14 +326,18 @@ __device__ __forceinline__ void stage_tile_dma(const uint8_t *recs, uint64_t rec
 // nothing.  It reads the kernel arguments through a pointer to the kernarg segment (taken in
 // the kernel): a reference to the kernel's by-value copy would force that whole struct into
 // scratch memory.
-template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool MASKQ = false, bool REGIONS = false>
+template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool MASKQ = false, bool REGIONS = false, bool HIST = false>
 __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyParams *kernarg, uint32_t o0,
-                                                                    uint32_t o1, uint32_t *table, uint32_t *lds_kmer) {
+                                                                    uint32_t o1, uint32_t *table, uint32_t *lds_kmer,
+                                                                    uint32_t *hist_lds = nullptr) {
     const TallyParams &P = *kernarg;
     GlobalBytes gsrc{P.recs + o0};
     const RecHdr gh = decode_hdr(gsrc, o1 - o0);
     const Plan gpl = make_plan<DO_PSS, DO_KMER, REGIONS>(P, gsrc, gh);
     if (DO_PSS && (gpl.pss_fwd || gpl.pss_rev)) tally_pss_record<MASKQ>(P, LdsTableColumnMajor{table, P.row_base}, gsrc, gh, gpl);
+    if constexpr (HIST) {   // (the HIST instantiation is a pass-0 one: counted once)
+        if (gpl.pss_fwd || gpl.pss_rev) hist_add(P, hist_lds, hist_bin(P, gpl.L), gpl.pss_fwd, gpl.pss_rev, 1u);
+    }
     bool kfail = false;
     if (DO_KMER && (gpl.fk5 || gpl.fk3)) kfail = tally_kmer_record<LDS_KMER>(P, gpl, lds_kmer);
     return record_events(DO_PSS, DO_KMER, gpl, kfail);
@@ -391,16 +454,23 @@ __device__ __forceinline__ uint32_t base_quality_mask(uint32_t x, uint32_t q4) {
 // next tile's DMA: a candidate that meets no region stops being one before -U/-D is decided and before the k-mer add.
 // Both lanes of a read's pair ask (same addresses: one request to the memory system).  Only the record's fixed fields
 // are read, so prefixes are staged as without it.  The instantiations without REGIONS contain none of it.
+//
+// HIST (-H, P.hist_max > 0; pass 0, one plane): behind CODES-B, where pss_fwd / pss_rev are decided, the left-end lane
+// of every read that is added to a table counts its length (hist_wave_add); `hist_lds` holds the LDS part of the two
+// arrays and is added to the counter block when the workgroup is done, one 64-bit atomic per non-zero bin.  Nothing is
+// read that the kernel does not read anyway.  The instantiations without HIST contain none of it.
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS, PlaneSel PLANES = PLANES_NONE, bool MASKQ = false,
-          bool REGIONS = false>
+          bool REGIONS = false, bool HIST = false>
 __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const TallyParams *kernarg,
                                                  uint8_t *__restrict__ stage, uint8_t *__restrict__ sheet,
                                                  uint32_t *__restrict__ table,
                                                  uint32_t *__restrict__ toffs,
                                                  uint32_t *__restrict__ lds_kmer,
                                                  int32_t *__restrict__ lds_delta, uint4 *__restrict__ refs_lds,
-                                                 const PlaneParams *gk = nullptr, uint32_t *__restrict__ grp_lds = nullptr) {
+                                                 const PlaneParams *gk = nullptr, uint32_t *__restrict__ grp_lds = nullptr,
+                                                 uint32_t *__restrict__ hist_lds = nullptr) {
     constexpr bool GROUPED = PLANES != PLANES_NONE;   // one table plane per read group / length bin
+    static_assert(!HIST || (DO_PSS && !LATER_PASS && PLANES == PLANES_NONE), "the length histogram belongs to pass 0 of the one-plane substitution tally");
     constexpr bool KPLANES = GROUPED && DO_KMER;      // ... of k-mer bins (tally_tiled_kmer_planes: no sheet, no table)
     static_assert(!KPLANES || !DO_PSS, "planes split either the substitution tables or the k-mer tables");
     static_assert(!MASKQ || DO_PSS, "base qualities mask the substitution tables only");
@@ -429,6 +499,8 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
     if (LDS_KMER)
         for (uint32_t i = tid; i < kmer_words; i += TILED_THREADS) lds_kmer[i] = 0u;
     if (tid < ST_USED) lds_delta[tid] = 0;
+    if constexpr (HIST)
+        for (uint32_t i = tid; i < 2u * P.hist_lds_bins; i += TILED_THREADS) hist_lds[i] = 0u;
     // contig info of the first BAM references (all of them for a human-sized header) + the "*" entry
     const uint32_t n_ref_cached = min((uint32_t)P.n_ref, REF_LDS_ENTRIES);
     if (tid < n_ref_cached) refs_lds[tid] = P.ref_info[tid];
@@ -602,7 +674,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         if (in_tile && !in_stage && e == 0u) {
             if constexpr (KPLANES) ev_over = tally_overflow_record_kmer_planes<PLANES, LDS_KMER, REGIONS>(kernarg, gk, o0, o1, lds_kmer);
             else if constexpr (GROUPED) ev_over = tally_overflow_record_planes<PLANES, MASKQ, REGIONS>(kernarg, gk, o0, o1, table);
-            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS>(kernarg, o0, o1, table, lds_kmer);
+            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS, HIST>(kernarg, o0, o1, table, lds_kmer, hist_lds);
             if (pass0) atomicAdd(&lds_delta[ST_SLOW_PATH], 1);
         }
         // First use of the gathered registers happens HERE, before the next tile's DMA is issued:
@@ -772,6 +844,9 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
                 kfail = (bad | bad_other) != 0;
             }
             if (e == 0u && pass0) book_events(DO_PSS, DO_KMER, in_stage ? record_events(DO_PSS, DO_KMER, pl, kfail) : ev_over, lds_delta);
+            // -H: both lanes of a pair hold the same decision; the left-end lane counts the read (a record that took
+            // the out-of-line path counted itself there and is no candidate here)
+            if constexpr (HIST) hist_wave_add(P, hist_lds, e == 0u, pl.L, pl.pss_fwd, pl.pss_rev);
         }
         // (no barrier: wave w wrote the sheet rows of reads 32w .. 32w+31 -- j = tid >> 1 -- and its
         //  COLUMNS pass below reads exactly those rows)
@@ -838,6 +913,14 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
     for (uint32_t i = tid; i < 512u; i += TILED_THREADS)
         mine[SCRATCH_KMER + i] = (LDS_KMER && i < 2u * (1u << (2 * P.K))) ? lds_kmer[i] : 0u;
     if (tid < 16u) mine[SCRATCH_DELTA + tid] = tid < (uint32_t)ST_USED ? (uint32_t)lds_delta[tid] : 0u;
+    }
+    if constexpr (HIST) {
+        // the LDS part of hf / hr: a handful of bins are non-zero (one, for a library of equal lengths), so the
+        // workgroup adds those to the counter block itself -- no scratch slot, no words for reduce_partials to walk
+        for (uint32_t i = tid; i < 2u * P.hist_lds_bins; i += TILED_THREADS) {
+            const uint32_t v = hist_lds[i];
+            if (v) atomicAdd(&P.counters[P.off_hist + (i < P.hist_lds_bins ? i : P.hist_max + 2u + (i - P.hist_lds_bins))], (unsigned long long)v);
+        }
     }
 }
 
@@ -1350,7 +1433,8 @@ __global__ void __launch_bounds__(256) reduce_partials(const TallyParams P, uint
     if (sum) atomicAdd(dst, (unsigned long long)sum);
 }
 
-template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS = false, bool MASKQ = false, bool REGIONS = false>
+// HIST: dynamic LDS is the staging buffer and, behind it, the 2 * P.hist_lds_bins words of the length histogram
+template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS = false, bool MASKQ = false, bool REGIONS = false, bool HIST = false>
 __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
@@ -1361,8 +1445,9 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P
     __shared__ uint4 refs_lds[REF_LDS_ENTRIES + 1];
     // the kernel's single argument, as it lies in the kernarg segment (for the out-of-line path)
     const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
-    tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
-                                                                                      lds_delta, refs_lds);
+    uint32_t *hist_lds = HIST ? (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces)) : nullptr;
+    tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
+                                                                                            lds_delta, refs_lds, nullptr, nullptr, hist_lds);
 }
 
 // ---------------------------------------------------------------------------------------

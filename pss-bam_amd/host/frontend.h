@@ -23,6 +23,10 @@ typedef struct run_result {
     unsigned long *plane_fwd, *plane_rev;
     /* fragkon -G / -S / -C (a PSSBAM_TALLY_KMER engine): the planes' k-mer tables instead, 4^klen per plane */
     uint64_t *plane_k5, *plane_k3;
+    /* pss-bam -H (frontend_length_hist): the fragment-length histogram of the reads added to the forward / reverse
+     * table, hist_max + 2 rows each (row hist_max + 1: every longer read), or NULL */
+    int hist_max;
+    uint64_t *hist_fwd, *hist_rev;
 } run_result;
 
 /* pss-bam -G: every engine gets the input header's @RG IDs (pssbam_engine_set_read_groups) and run_tally()
@@ -32,6 +36,10 @@ extern int frontend_group_by_rg;
 /* pss-bam -Q: the minimum base quality (0: off); every engine gets it (pssbam_engine_set_min_base_quality).  Set
  * before frontend_warmup_start. */
 extern int frontend_min_base_quality;
+
+/* pss-bam -H: the limit of the fragment-length histogram (0: off); every engine gets it
+ * (pssbam_engine_set_length_histogram) and run_tally() returns the two arrays.  Set before frontend_warmup_start. */
+extern int frontend_length_hist;
 
 /* -T: the intervals of the BED file (regions.h; NULL: none); every engine gets them (pssbam_engine_set_regions), on
  * every input path -- the filter lives in the engine.  Set before frontend_warmup_start. */

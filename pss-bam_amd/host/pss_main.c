@@ -24,6 +24,9 @@
  * Added: -T <bed> tallies only the reads whose alignment overlaps an interval of the BED file (plain text; contig,
  * 0-based start, end): every file written holds what this command writes without -T for the input reduced by
  * `samtools view -L <bed>`.  The file names stay as they are.
+ * Added: -H <max> also writes <prefix>.pss.lengths.txt, the fragment-length histogram (the length -l / -L compare,
+ * 0..max and one row for everything longer) of the reads that were added to the forward / reverse table, from the
+ * same pass; the other files stay as they are.  Not with -G, -S or -C.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -39,6 +42,7 @@
 #include "fasta-genome-io.h"
 #include "frontend.h"
 #include "length_bins.h"
+#include "length_hist.h"
 #include "read_groups.h"
 #include "regions.h"
 #include "report.h"
@@ -52,9 +56,9 @@ int main(int argc, char *argv[])
     unsigned long min_read_len = 0, max_read_len = 250000000;
     const char *up_ctx = "ACGT", *down_ctx = "ACGT";
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL, *read_group = NULL;
-    const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL, *bed_fn = NULL;
+    const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL, *bed_fn = NULL, *hist_arg = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -71,6 +75,7 @@ int main(int argc, char *argv[])
         case 'C': ctg_map = optarg; break;
         case 'Q': min_bq_arg = optarg; break;
         case 'T': bed_fn = optarg; break;
+        case 'H': hist_arg = optarg; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -132,6 +137,19 @@ int main(int argc, char *argv[])
             exit(1);
         }
     }
+    int hist_max = 0;
+    if (hist_arg) {
+        if (by_group || len_edges || ctg_map) {
+            fprintf(stderr, "-H (fragment-length histogram) and %s exclude each other.\n",
+                    by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)" : "-C (tables per contig set)");
+            exit(1);
+        }
+        char err[200];
+        if ((hist_max = pss_parse_length_hist(hist_arg, err, sizeof err)) < 0) {
+            fprintf(stderr, "%s\n", err);
+            exit(1);
+        }
+    }
     pss_regions bed;
     memset(&bed, 0, sizeof bed);
     if (bed_fn) {
@@ -185,6 +203,7 @@ int main(int argc, char *argv[])
     if (len_edges) fprintf(stderr, " -S %s", len_edges);
     if (ctg_map) fprintf(stderr, " -C %s", ctg_map);
     if (min_bq_arg) fprintf(stderr, " -Q %d", min_bq);
+    if (hist_arg) fprintf(stderr, " -H %d", hist_max);
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -207,6 +226,7 @@ int main(int argc, char *argv[])
     memcpy(frontend_length_edges, edges, (size_t)n_edges * sizeof *edges);
     if (ctg_map) frontend_contig_sets = &sets;
     frontend_min_base_quality = min_bq;
+    frontend_length_hist = hist_max;
     if (bed_fn) frontend_regions = &bed;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
@@ -231,6 +251,7 @@ int main(int argc, char *argv[])
     pss_sub_rates(region_len, res.rev, rev_rates);
     pss_write_counts(fasta_fn, bam_fn, out_prefix, region_len, res.fwd, res.rev);
     pss_write_rates(fasta_fn, bam_fn, out_prefix, region_len, fwd_rates, rev_rates);
+    if (res.hist_fwd && pss_write_lengths(fasta_fn, bam_fn, out_prefix, res.hist_max, res.hist_fwd, res.hist_rev)) exit(1);
     if (by_group && res.n_planes == 0)
         fprintf(stderr, "Warning: -G: the header of %s has no @RG line; only the tables of all reads were written.\n", bam_fn);
     /* <prefix>.<tag>: what `-R <ID> -o <prefix>.<ID>` (-G), `-l <lo> -L <hi> -o <prefix>.len<lo>-<hi>` (-S) or -F

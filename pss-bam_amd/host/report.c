@@ -104,6 +104,25 @@ int pss_write_rates(const char *fasta_fn, const char *bam_fn, const char *out_pr
     return 0;
 }
 
+int pss_write_lengths(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int max_len, const uint64_t *fwd,
+                      const uint64_t *rev)
+{
+    char fn[FN_BUF + 1];
+    FILE *fp;
+    snprintf(fn, sizeof fn, "%s.pss.lengths.txt", out_prefix);
+    fp = fopen(fn, "w");
+    if (!fp) {
+        fprintf(stderr, "ERROR: Cannot write to file %s\n.", fn);
+        return 1;
+    }
+    fprintf(fp, "# fragment lengths of the reads added to the forward / reverse table\n# FASTA: %s\n# BAM: %s\n", fasta_fn, bam_fn);
+    fputs("length\tfwd\trev\n", fp);
+    for (int len = 0; len <= max_len; len++)
+        fprintf(fp, "%d\t%llu\t%llu\n", len, (unsigned long long)fwd[len], (unsigned long long)rev[len]);
+    fprintf(fp, ">%d\t%llu\t%llu\n", max_len, (unsigned long long)fwd[max_len + 1], (unsigned long long)rev[max_len + 1]);
+    return fclose(fp) ? 1 : 0;
+}
+
 int fragkon_write_table(FILE *out, const char *fasta_fn, const char *bam_fn, int klen, const uint64_t *k5,
                         const uint64_t *k3)
 {

@@ -10,6 +10,11 @@ int pss_write_counts(const char *fasta_fn, const char *bam_fn, const char *out_p
                      const unsigned long *fwd, const unsigned long *rev);
 int pss_write_rates(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int region_len,
                     const double *fwd_rates, const double *rev_rates);
+/* pss-bam -H: <out_prefix>.pss.lengths.txt -- three '#' lines, the column names, then one tab-separated line
+ * "<length> <fwd> <rev>" per length 0..max_len (zero rows included) and a last one labelled "><max_len>" for every
+ * longer read; fwd / rev hold max_len + 2 counts.  Returns 0, or 1 after a diagnostic. */
+int pss_write_lengths(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int max_len, const uint64_t *fwd,
+                      const uint64_t *rev);
 /* k5 / k3: 4^klen 64-bit bins (clamped to UINT_MAX on output) */
 int fragkon_write_table(FILE *out, const char *fasta_fn, const char *bam_fn, int klen, const uint64_t *k5,
                         const uint64_t *k3);
