@@ -39,6 +39,8 @@ extern "C" {
 #define PSSBAM_MAX_HIST_LENGTH 65535 /* pssbam_engine_set_length_histogram: the largest limit (lengths above it share one row) */
 #define PSSBAM_MAX_BASE_QUALITY 93   /* pssbam_engine_set_min_base_quality: the largest Phred value SAM text can print */
 #define PSSBAM_MAX_REGIONS (1 << 26) /* pssbam_engine_set_regions: intervals in one call */
+#define PSSBAM_SITE_NONE 0           /* pssbam_engine_set_site_context: off */
+#define PSSBAM_SITE_CPG 1            /* ... the reference position lies in a CpG dinucleotide */
 
 /* error codes */
 #define PSSBAM_OK 0
@@ -323,6 +325,33 @@ int pssbam_engine_set_length_histogram(pssbam_engine *e, int32_t max_len);
  * be NULL.  PSSBAM_EINVAL when the histogram is off. */
 int pssbam_engine_finish_length_histogram(pssbam_engine *e, uint64_t *fwd, uint64_t *rev);
 
+/* Site context (pss-bam -X cpg): a second pair of substitution tables, IN, over the interior positions whose REFERENCE
+ * position lies in a given context, from the same pass as the ordinary tables T.  With g the contig's bases after the
+ * case folding the engine applies anyway, position p is in CpG context (PSSBAM_SITE_CPG) when
+ *     (g[p] == 'C' && g[p+1] == 'G') || (g[p] == 'G' && g[p-1] == 'C');
+ * a neighbour outside the contig counts as "no" (every position a tallied read touches has both inside).  The set is
+ * its own reverse complement and is evaluated in genome orientation for reads of both strands.  Interior position i
+ * of an alignment end adds to IN exactly when it adds to T and the reference position it pairs with -- POS-1+i for the
+ * left end, POS-1+L-1-i for the right end, on either strand -- is in context.  Rows 0 and 1 (the context bases) are
+ * reference-only and never masked: IN returns T's.  Nothing of the reference looks at the content of SEQ except
+ * add_fwd_counts / add_rev_counts, which skip a read base that is not A/C/G/T, so
+ *     IN == the tables of the same records with SEQ base k set to 'N' wherever contig position POS-1+k is NOT in
+ *     context, and T - IN on rows 2+ (rows 0/1 as T) == the same with the complementary mask.
+ * T, every status counter and the record filters are bit-identical to the engine without the setting; a base masked
+ * by a minimum base quality is missing from T and from IN alike.  PSSBAM_SITE_NONE switches it off: the engine then
+ * launches exactly the kernels it launches without this call.
+ * Legal after create (or reset) and before the first tally launch; with pssbam_engine_feed_open that is any time
+ * before set_references.  Goes with cfg.read_group, a minimum base quality and regions.  PSSBAM_EINVAL for an unknown
+ * mode, on an engine with PSSBAM_TALLY_KMER in its mask, and with read groups, length bins, contig sets or a length
+ * histogram set (those setters return PSSBAM_EINVAL once site context is on); PSSBAM_ESTATE once records have been
+ * tallied or the counter block has been bound (the block grows, see pssbam_engine_counters_device).  The setting
+ * survives pssbam_engine_reset; engines whose blocks are summed must all have been given the same mode. */
+int pssbam_engine_set_site_context(pssbam_engine *e, int32_t mode);
+
+/* Drains the engine like pssbam_engine_finish and copies IN's two tables, (region_len+2)*16 words each with rows 0/1
+ * filled from T; either pointer may be NULL.  PSSBAM_EINVAL when the setting is off. */
+int pssbam_engine_finish_site_context(pssbam_engine *e, unsigned long *fwd_in, unsigned long *rev_in);
+
 /* The device-resident counter block [fwd | rev | k5 | k3 | stats] as one array of
  * n_u64 64-bit words, for a caller-side RCCL reduce across GPUs (sum, uint64).  With read groups it is
  * [fwd | rev | stats | fwd_0 | rev_0 | ... | fwd_n-1 | rev_n-1]: the leading fwd | rev are the unassigned
@@ -335,7 +364,12 @@ int pssbam_engine_finish_length_histogram(pssbam_engine *e, uint64_t *fwd, uint6
  * klen.  The block is still summed across GPUs as one u64 array.
  * With a length histogram of limit M (pssbam_engine_set_length_histogram; never together with planes) the two
  * arrays are appended: [fwd | rev | k5 | k3 | stats | hf | hr], hf at 2*(region_len+2)*16 + 2*4^klen + PSSBAM_ST_N
- * (no k-mer term on a PSSBAM_TALLY_PSS engine), hr M + 2 words behind it, n_u64 larger by 2*(M+2). */
+ * (no k-mer term on a PSSBAM_TALLY_PSS engine), hr M + 2 words behind it, n_u64 larger by 2*(M+2).
+ * With site context (pssbam_engine_set_site_context; a PSSBAM_TALLY_PSS engine without planes or histogram) the
+ * in-context pair is appended: [fwd | rev | stats | fwd_in | rev_in], fwd_in at 2*(region_len+2)*16 + PSSBAM_ST_N (the
+ * old n_u64), rev_in (region_len+2)*16 words behind it, n_u64 larger by 2*(region_len+2)*16.  Rows 0 and 1 of the
+ * pair stay zero on the device (pssbam_engine_finish_site_context fills them from fwd | rev), so the block still sums
+ * across engines as one u64 array. */
 int pssbam_engine_counters_device(pssbam_engine *e, void **d_counters, size_t *n_u64);
 
 /* Makes the engine accumulate into caller-owned device memory (n_u64 words, as reported

@@ -43,6 +43,7 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_read_groups", "pssbam_engine_finish_groups", "pssbam_engine_set_length_bins",
     "pssbam_engine_set_contig_sets", "pssbam_engine_finish_kmer_groups", "pssbam_engine_set_min_base_quality",
     "pssbam_engine_set_regions", "pssbam_engine_set_length_histogram", "pssbam_engine_finish_length_histogram",
+    "pssbam_engine_set_site_context", "pssbam_engine_finish_site_context",
 ]
 MAX_READ_GROUPS = 4096
 MAX_LENGTH_BINS = 64
@@ -50,6 +51,8 @@ MAX_CONTIG_SETS = 4096
 MAX_BASE_QUALITY = 93
 MAX_HIST_LENGTH = 65535
 MAX_REGIONS = 1 << 26
+SITE_NONE, SITE_CPG = 0, 1
+SITE_MODES = {None: SITE_NONE, "none": SITE_NONE, "cpg": SITE_CPG}
 EBUSY = -7
 
 
@@ -117,6 +120,8 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_set_min_base_quality.argtypes = [C.c_void_p, C.c_int32]
     L.pssbam_engine_set_length_histogram.argtypes = [C.c_void_p, C.c_int32]
     L.pssbam_engine_finish_length_histogram.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pssbam_engine_set_site_context.argtypes = [C.c_void_p, C.c_int32]
+    L.pssbam_engine_finish_site_context.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_regions.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_counters_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.pssbam_engine_bind_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -192,13 +197,15 @@ class Engine:
     see set_min_base_quality; 0 = off.
     `length_hist` = limit of the fragment-length histogram (pss-bam -H) of the reads added to the substitution tables,
     see set_length_histogram; 0 = off.
+    `site_context` = "cpg" (pss-bam -X cpg): a second pair of tables over the positions whose reference site is in CpG
+    context, see set_site_context; None = off.
     With `kmer` alone (no `pss`) the three split the k-mer tables instead (fragkon -G / -S / -C): every plane is a
     k5 / k3 pair, and the length bins go by the SEQ length and kmer's min_read_len / max_read_len."""
 
     def __init__(self, pss: dict | None = None, kmer: dict | None = None, read_group: str | None = None,
                  kernel: int = KERNEL_AUTO, device: int = -1, read_groups: list[str] | None = None,
                  length_bins: list[int] | None = None, contig_sets=None, min_base_qual: int = 0,
-                 length_hist: int = 0):
+                 length_hist: int = 0, site_context: str | None = None):
         L = hip_lib()
         cfg = _Config()
         cfg.abi_version = 1
@@ -234,10 +241,13 @@ class Engine:
         self.contig_sets: list[str] = []
         self._min_base_qual = 0
         self._length_hist = 0
+        self._site_context = SITE_NONE
         if min_base_qual:
             self.set_min_base_quality(min_base_qual)
         if length_hist:
             self.set_length_histogram(length_hist)
+        if site_context is not None:
+            self.set_site_context(site_context)
         if read_groups is not None:
             self.set_read_groups(read_groups)
         if length_bins is not None:
@@ -276,6 +286,32 @@ class Engine:
         fwd = np.zeros(self._length_hist + 2, dtype=np.uint64)
         rev = np.zeros_like(fwd)
         _chk(self._L.pssbam_engine_finish_length_histogram(self._h, fwd.ctypes.data, rev.ctypes.data))
+        return fwd, rev
+
+    def set_site_context(self, mode):
+        """pss-bam -X: "cpg" (or SITE_CPG) keeps a second pair of tables, IN, over the interior positions whose reference
+        position is in CpG context -- the tables of the same records with every other read base replaced by N; None /
+        "none" switches it off.  Not with kmer, read groups, length bins, contig sets or the length histogram.  Before
+        the first tally (after feed_open: before set_references) and before bind_counters: the counter block grows by
+        2 * (region_len + 2) * 16 words.  Survives reset."""
+        if isinstance(mode, str) or mode is None:
+            if mode not in SITE_MODES:
+                raise ValueError(f"unknown site context {mode!r}")
+            mode = SITE_MODES[mode]
+        _chk(self._L.pssbam_engine_set_site_context(self._h, int(mode)))
+        self._site_context = int(mode)
+
+    @property
+    def site_context(self) -> str | None:
+        """the site context in force ("cpg" or None)"""
+        return "cpg" if self._site_context == SITE_CPG else None
+
+    def finish_site_context(self) -> tuple[np.ndarray, np.ndarray]:
+        """(fwd_in, rev_in): the in-context tables, (region_len + 2, 16) u64 each, rows 0 / 1 as in finish() (drains
+        like finish); the out-of-context tables are finish() minus these on rows 2+"""
+        fwd = np.zeros((self.region_len + 2, 16), dtype=np.uint64)
+        rev = np.zeros_like(fwd)
+        _chk(self._L.pssbam_engine_finish_site_context(self._h, fwd.ctypes.data, rev.ctypes.data))
         return fwd, rev
 
     def set_regions(self, names, name_of, starts, ends):
@@ -553,6 +589,9 @@ class Engine:
         if self._length_hist:   # the length histogram (never together with planes): hf | hr behind the stats
             lay["hist_fwd"], lay["hist_rev"] = base, base + self._length_hist + 2
             lay["n_u64"] = base + 2 * (self._length_hist + 2)
+        if self._site_context:   # site context (never together with planes or the histogram): fwd_in | rev_in behind the stats
+            lay["site_fwd"], lay["site_rev"] = base, base + rows * 16
+            lay["n_u64"] = base + 2 * rows * 16
         return lay
 
     def genome_kmer_count(self, klen: int) -> np.ndarray:

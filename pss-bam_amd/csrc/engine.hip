@@ -166,6 +166,8 @@ enum PrepSlot : int {
     PREP_PLANES_RG_BQ, PREP_PLANES_RG_LATER_BQ, PREP_PLANES_LEN_BQ, PREP_PLANES_LEN_LATER_BQ, PREP_PLANES_REF_BQ, PREP_PLANES_REF_LATER_BQ,
     // -H (hist_max > 0): the HIST instantiations of pass 0, without and with -Q
     PREP_TILED_PSS_H, PREP_TILED_PSS_KMER_H, PREP_TILED_PSS_KMER_LDS_H, PREP_TILED_PSS_H_BQ, PREP_TILED_PSS_KMER_H_BQ, PREP_TILED_PSS_KMER_LDS_H_BQ,
+    // -X (site_mode != 0): the SITE instantiations, without and with -Q
+    PREP_TILED_SITE, PREP_TILED_SITE_LATER, PREP_TILED_SITE_BQ, PREP_TILED_SITE_LATER_BQ,
     PREP_N   // -T: the REGIONS instantiation of slot s is memo slot PREP_N + s
 };
 
@@ -227,6 +229,8 @@ struct pssbam_engine {
     uint32_t min_bq = 0;    // -Q: read bases with a QUAL byte below this are left out of the tables (pssbam_engine_set_min_base_quality)
     // -H (pssbam_engine_set_length_histogram): hf | hr, hist_max + 2 words each, at off_hist = the end of the block as it is without them
     uint32_t hist_max = 0, off_hist = 0;
+    // -X (pssbam_engine_set_site_context): fwd_in | rev_in, rows * 16 words each, at off_site = the end of the block as it is without them
+    uint32_t site_mode = 0, off_site = 0;
     int env_hist_lds_bins = -1;   // PSSBAM_HIST_LDS_BINS: at most this many bins of each array in LDS (tests: the global-atomic path with short reads)
     // -T (pssbam_engine_set_regions): contig name -> its merged intervals, kept on the host; the per-refID device table is
     // packed from it whenever the reference list or the map changes (pack_regions)
@@ -884,14 +888,16 @@ static int tiled_grid(pssbam_engine *e, PrepSlot slot, K kernel, uint32_t lds, u
 }
 
 // One launch of a kernel with a single table plane (tally_tiled, tally_compact*) and its reduce_partials
-template <class K>
+// (SITE: the larger scratch slot of the -X instantiations and the reduce that walks it)
+template <bool SITE = false, class K>
 static int launch_flat(pssbam_engine *e, PrepSlot slot, K kernel, TallyParams &P, uint32_t lds, uint32_t n_tiles, bool lds_kmer) {
+    constexpr uint32_t words = SITE ? SITE_SCRATCH_WORDS : SCRATCH_WORDS;
     uint32_t grid = 0;
-    const int rc = tiled_grid(e, slot, kernel, lds, n_tiles, SCRATCH_WORDS, &grid);
+    const int rc = tiled_grid(e, slot, kernel, lds, n_tiles, words, &grid);
     if (rc != PSSBAM_OK) return rc;
     P.scratch = e->d_scratch;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(TILED_THREADS), lds, e->stream, P);
-    hipLaunchKernelGGL(reduce_partials, dim3((SCRATCH_WORDS * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream, P, grid,
+    hipLaunchKernelGGL(reduce_partials<SITE>, dim3((words * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream, P, grid,
                        (uint32_t)(lds_kmer ? 1 : 0));
     return PSSBAM_OK;
 }
@@ -902,6 +908,15 @@ static int launch_tiled(pssbam_engine *e, PrepSlot slot, TallyParams &P, uint32_
     if (P.region_info)
         return launch_flat(e, (PrepSlot)(slot + PREP_N), tally_tiled<DO_PSS, DO_KMER, LDS_KMER, LATER, MASKQ, true, HIST>, P, lds, n_tiles, LDS_KMER);
     return launch_flat(e, slot, tally_tiled<DO_PSS, DO_KMER, LDS_KMER, LATER, MASKQ, false, HIST>, P, lds, n_tiles, LDS_KMER);
+}
+
+// One row pass of a launch with site context (-X): the SITE instantiation for the pass and the launch's -Q and -T state
+template <bool LATER, bool MASKQ>
+static int launch_tiled_site(pssbam_engine *e, TallyParams &P, uint32_t lds, uint32_t n_tiles) {
+    constexpr PrepSlot slot = MASKQ ? (LATER ? PREP_TILED_SITE_LATER_BQ : PREP_TILED_SITE_BQ) : (LATER ? PREP_TILED_SITE_LATER : PREP_TILED_SITE);
+    if (P.region_info)
+        return launch_flat<true>(e, (PrepSlot)(slot + PREP_N), tally_tiled<true, false, false, LATER, MASKQ, true, false, true>, P, lds, n_tiles, false);
+    return launch_flat<true>(e, slot, tally_tiled<true, false, false, LATER, MASKQ, false, false, true>, P, lds, n_tiles, false);
 }
 
 // Pass 0 of a launch with the length histogram (-H): the HIST instantiation for the launch's tallies and -Q state
@@ -1054,6 +1069,8 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         P.hist_max = e->hist_max;
         P.off_hist = e->off_hist;
     }
+    const bool site = do_pss && e->site_mode != PSSBAM_SITE_NONE;   // -X: the SITE instantiations; without it the engine launches what it always did
+    if (site) P.off_site = e->off_site;
     if (regions) {
         P.region_info = e->d_region_info;
         P.region_grid = e->d_region_grid;
@@ -1215,9 +1232,16 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                     rc = launch_pass[maskq][e->planes - PLANES_RG][pass > 0](e, P, G, tiled_grouped_lds_bytes(T, pieces, G.n_slots), n_tiles);
                 }
             }
+        } else if (site) {
+            // -X: tally_tiled with the neighbour compare and the in-context table, for every -r (tally_compact has no such arm)
+            rc = maskq ? launch_tiled_site<false, true>(e, P, lds, n_tiles) : launch_tiled_site<false, false>(e, P, lds, n_tiles);
+            for (uint32_t pass = 1; pass < n_passes && rc == PSSBAM_OK; pass++) {
+                P.row_base = pass * TILED_ROWS;
+                rc = maskq ? launch_tiled_site<true, true>(e, P, lds, n_tiles) : launch_tiled_site<true, false>(e, P, lds, n_tiles);
+            }
         } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions && !hist) {
             // -r N <= 16 (2 context rows + 16 positions): the short-window variant, one pass (it stages prefixes only
-            // and has no QUAL path: -R and -Q go to tally_tiled; so do -T and -H, whose arms only tally_tiled carries)
+            // and has no QUAL path: -R and -Q go to tally_tiled; so do -T, -H and -X, whose arms only tally_tiled carries)
             if (!do_kmer && getenv("PSSBAM_COMPACT_DECODE_TWICE"))   // diagnostics: what the shared header decode costs
                 rc = launch_flat(e, PREP_COMPACT_DECODE_TWICE, tally_compact_decode_twice, P, lds, n_tiles, false);
             else if (e->compact_plan_once)
@@ -1502,6 +1526,7 @@ extern "C" int pssbam_engine_finish_kmer_groups(pssbam_engine *e, int32_t group,
 // feed): it is retired, not freed.  `what` names the caller's planes in the messages.
 static int set_planes(pssbam_engine *e, PlaneSel sel, uint32_t n_planes, const char *what) {
     if (e->hist_max) return fail(PSSBAM_EINVAL, "%s and the length histogram exclude each other", what);
+    if (e->site_mode) return fail(PSSBAM_EINVAL, "%s and site context exclude each other", what);
     const bool kmer = e->cfg.tally_mask == PSSBAM_TALLY_KMER;
     if (e->cfg.tally_mask != PSSBAM_TALLY_PSS && !kmer)
         return fail(PSSBAM_EINVAL, "%s split the substitution tables or the k-mer tables, not both (PSSBAM_TALLY_PSS | PSSBAM_TALLY_KMER)", what);
@@ -1598,6 +1623,7 @@ extern "C" int pssbam_engine_set_length_histogram(pssbam_engine *e, int32_t max_
     if (!(e->cfg.tally_mask & PSSBAM_TALLY_PSS))
         return fail(PSSBAM_EINVAL, "the length histogram counts the reads added to the substitution tables: the engine needs PSSBAM_TALLY_PSS");
     if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the length histogram and read groups / length bins / contig sets exclude each other");
+    if (e->site_mode) return fail(PSSBAM_EINVAL, "the length histogram and site context exclude each other");
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the length histogram after create or reset, before the first tally");
     if (e->d_counters != e->d_counters_own) return fail(PSSBAM_ESTATE, "a caller-bound counter block cannot grow: set the length histogram before bind_counters");
     if ((uint32_t)max_len == e->hist_max) return PSSBAM_OK;
@@ -1625,6 +1651,48 @@ extern "C" int pssbam_engine_finish_length_histogram(pssbam_engine *e, uint64_t 
     const size_t n = (size_t)e->hist_max + 2;
     if (fwd) HIP_TRY(hipMemcpy(fwd, e->d_counters + e->off_hist, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     if (rev) HIP_TRY(hipMemcpy(rev, e->d_counters + e->off_hist + n, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_set_site_context(pssbam_engine *e, int32_t mode) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (mode != PSSBAM_SITE_NONE && mode != PSSBAM_SITE_CPG) return fail(PSSBAM_EINVAL, "unknown site context %d", mode);
+    if (e->cfg.tally_mask != PSSBAM_TALLY_PSS)
+        return fail(PSSBAM_EINVAL, "site context splits the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
+    if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "site context and read groups / length bins / contig sets exclude each other");
+    if (e->hist_max) return fail(PSSBAM_EINVAL, "site context and the length histogram exclude each other");
+    if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the site context after create or reset, before the first tally");
+    if (e->d_counters != e->d_counters_own) return fail(PSSBAM_ESTATE, "a caller-bound counter block cannot grow: set the site context before bind_counters");
+    if ((uint32_t)mode == e->site_mode) return PSSBAM_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    // the block grows (or shrinks back) behind everything it holds without the pair; zeroed: nothing has been counted yet.
+    // The old block may still be named by work queued on the stream: retired, not freed (set_planes).
+    const uint64_t n_counters = (uint64_t)e->off_groups + (mode ? 2ull * e->rows * 16ull : 0ull);
+    if (n_counters > 0xFFFFFFFFull) return fail(PSSBAM_EINVAL, "the counter block would pass 2^32 words");
+    unsigned long long *d_counters = nullptr;
+    HIP_TRY(hipMalloc(&d_counters, n_counters * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(d_counters, 0, n_counters * sizeof(unsigned long long), e->stream));
+    if (e->d_counters_own) e->retired.push_back(e->d_counters_own);
+    e->d_counters = e->d_counters_own = d_counters;
+    e->n_counters = n_counters;
+    e->site_mode = (uint32_t)mode;
+    e->off_site = mode ? e->off_groups : 0u;
+    return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_finish_site_context(pssbam_engine *e, unsigned long *fwd_in, unsigned long *rev_in) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (!e->site_mode) return fail(PSSBAM_EINVAL, "pssbam_engine_set_site_context has not been called");
+    const int rc = pssbam_engine_sync(e);
+    if (rc) return rc;
+    std::vector<unsigned long long> h(e->n_counters);
+    HIP_TRY(hipMemcpy(h.data(), e->d_counters, e->n_counters * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    const size_t tab = (size_t)e->rows * 16;
+    // rows 0 and 1 (the context bases) are never masked: they stay zero on the device and are T's here
+    for (size_t i = 0; i < tab; i++) {
+        if (fwd_in) fwd_in[i] = (unsigned long)(i < 32 ? h[i] : h[e->off_site + i]);
+        if (rev_in) rev_in[i] = (unsigned long)(i < 32 ? h[e->off_rev + i] : h[e->off_site + tab + i]);
+    }
     return PSSBAM_OK;
 }
 

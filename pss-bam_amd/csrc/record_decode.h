@@ -88,6 +88,10 @@ struct TallyParams {
     // instantiations of tally_tiled keep the first hist_lds_bins bins of each array in LDS (0: none, every bin goes
     // straight to the counter block); the lane-per-read kernels read hist_max and off_hist only.
     uint32_t hist_max, off_hist, hist_lds_bins;
+    // -X: site context (off_site = 0: off).  [fwd_in | rev_in], (N + 2) * 16 u64 counters each, in the counter block at
+    // off_site: the adds of the interior positions whose reference position is in CpG context.  Read by the SITE
+    // instantiations of tally_tiled, their reduce_partials and tally_simple.
+    uint32_t off_site;
 };
 
 // stats slots, must match include/pssbam_hip.h.  The kernels count EVENTS only: every launch

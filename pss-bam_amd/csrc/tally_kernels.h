@@ -72,6 +72,10 @@ constexpr uint32_t CODE_NONE = 32;     // sheet byte meaning "no count"; every c
 constexpr uint32_t TABLE_WORDS = 64 * 32;  // codes 0..31 = (cell << 1) | table, 32..63 = trash bin
 // per-workgroup partial results of tally_tiled in global scratch: [table 1024 | k-mer bins 512 | stat deltas 16]
 constexpr uint32_t SCRATCH_KMER = 1024, SCRATCH_DELTA = 1536, SCRATCH_WORDS = 1552;
+// -X (SITE): the in-context table behind a slot: [(read base << 2) | (reference G ? 2 : 0) | table][row], 16 x 32 words --
+// an in-context cell always has reference base C or G (in table coordinates too: complementing swaps the two)
+constexpr uint32_t SITE_WORDS = 16 * 32, SITE_SCRATCH_WORDS = SCRATCH_WORDS + SITE_WORDS;
+constexpr uint32_t CODE_SITE = 64;     // sheet bit "the reference position is in context" (SITE instantiations only)
 constexpr uint32_t REF_LDS_ENTRIES = 64;   // BAM references whose contig info is cached in LDS (+1 for "*")
 
 // ---------------------------------------------------------------------------------------
@@ -100,6 +104,34 @@ struct GlobalTable {  // straight into the u64 counter block
     }
 };
 
+// -X: where the lane-per-read form adds an in-context position a second time (NoSite: nowhere, the option is off)
+struct NoSite {
+    __device__ __forceinline__ void add(uint32_t, uint32_t, uint32_t) const {}
+};
+__device__ __forceinline__ uint32_t site_half_code(uint32_t table, uint32_t cell) {   // cell = 4 * read + reference, reference C or G
+    return ((cell >> 2) << 2) | (cell & 2u) | table;
+}
+struct LdsSiteColumnMajor {  // the tiled kernel's [half code][32 rows] table of the rows row_base .. +31
+    uint32_t *t;
+    uint32_t row_base;
+    __device__ __forceinline__ void add(uint32_t table, uint32_t row, uint32_t cell) const {
+        const uint32_t r = row - row_base;
+        if (r < 32u) atomicAdd(&t[(site_half_code(table, cell) << 5) + r], 1u);
+    }
+};
+struct GlobalSite {  // straight into the [fwd_in | rev_in] pair of the counter block
+    unsigned long long *c;
+    uint32_t off_rev;
+    __device__ __forceinline__ void add(uint32_t table, uint32_t row, uint32_t cell) const {
+        atomicAdd(&c[(table ? off_rev : 0u) + row * 16u + cell], 1ull);
+    }
+};
+// CpG context of contig position p from the stored genome bytes (C = 1, G = 2; anything else, padding included, is "no")
+__device__ __forceinline__ bool site_in_cpg(const uint8_t *G, int64_t p) {
+    const uint32_t b = G[p];
+    return (b == 1u && G[p + 1] == 2u) || (b == 2u && G[p - 1] == 1u);
+}
+
 // One end of one read into one table.  `left` selects the alignment's left end
 // (reference s-2.., read bases 0..) or right end (reference ..s+L+1, read bases ..L-1);
 // `comp` complements both bases (reverse-strand reads), which maps cell c to 15-c.
@@ -107,8 +139,10 @@ struct GlobalTable {  // straight into the u64 counter block
 // MASKQ (-Q): a position whose read base has a QUAL byte below min_bq adds nothing, as if SEQ held 'N' there
 // (add_fwd_counts / add_rev_counts skip every read base that is not A/C/G/T); the context rows are
 // reference-only and never masked.  min_bq == 0 masks nothing.
-template <bool MASKQ, class Src, class Tab>
-__device__ void tally_end(const Tab &tab, uint32_t table, const Src &src, const RecHdr &h, const uint8_t *G,
+// SITE (-X cpg): a position that is counted and whose reference position is in CpG context is added to `site` as well
+// (genome orientation for both strands: the set is its own reverse complement); the context rows never are.
+template <bool MASKQ, bool SITE, class Src, class Tab, class Site>
+__device__ void tally_end(const Tab &tab, const Site &site, uint32_t table, const Src &src, const RecHdr &h, const uint8_t *G,
                           int64_t s, uint32_t L, int N, bool left, bool comp, uint32_t min_bq) {
     const uint32_t c0 = ref_code(left ? G[s - 2] : G[s + L + 1]);  // second context base -> row 0
     const uint32_t c1 = ref_code(left ? G[s - 1] : G[s + L]);      // first context base  -> row 1
@@ -122,19 +156,27 @@ __device__ void tally_end(const Tab &tab, uint32_t table, const Src &src, const 
         if (rd < 4u && rf < 4u) {
             const uint32_t cell = 4u * rd + rf;
             tab.add(table, (uint32_t)i + 2u, comp ? 15u - cell : cell);
+            if constexpr (SITE) {
+                if (site_in_cpg(G, s + (int64_t)ri)) site.add(table, (uint32_t)i + 2u, comp ? 15u - cell : cell);
+            }
         }
     }
 }
 
-template <bool MASKQ = false, class Src, class Tab>
-__device__ __forceinline__ void tally_pss_record(const TallyParams &P, const Tab &tab, const Src &src,
+template <bool MASKQ = false, bool SITE = false, class Src, class Tab, class Site>
+__device__ __forceinline__ void tally_pss_record(const TallyParams &P, const Tab &tab, const Site &site, const Src &src,
                                                  const RecHdr &h, const Plan &pl) {
     const uint32_t min_bq = MASKQ ? P.min_bq : 0u;
     const uint8_t *G = P.genome + pl.gbase;
     // forward-strand read: fwd table <- left end, rev table <- right end;
     // reverse-strand read: fwd table <- right end complemented, rev table <- left end complemented
-    if (pl.pss_fwd) tally_end<MASKQ>(tab, 0u, src, h, G, pl.s, pl.L, P.N, !pl.rev, pl.rev, min_bq);
-    if (pl.pss_rev) tally_end<MASKQ>(tab, 1u, src, h, G, pl.s, pl.L, P.N, pl.rev, pl.rev, min_bq);
+    if (pl.pss_fwd) tally_end<MASKQ, SITE>(tab, site, 0u, src, h, G, pl.s, pl.L, P.N, !pl.rev, pl.rev, min_bq);
+    if (pl.pss_rev) tally_end<MASKQ, SITE>(tab, site, 1u, src, h, G, pl.s, pl.L, P.N, pl.rev, pl.rev, min_bq);
+}
+template <bool MASKQ = false, class Src, class Tab>
+__device__ __forceinline__ void tally_pss_record(const TallyParams &P, const Tab &tab, const Src &src,
+                                                 const RecHdr &h, const Plan &pl) {
+    tally_pss_record<MASKQ, false>(P, tab, NoSite{}, src, h, pl);
 }
 
 // one k-mer add (5' when which == 0, 3' when which == 1); false = non-ACGT in the window
@@ -236,7 +278,11 @@ __global__ void __launch_bounds__(256) tally_simple(const TallyParams P) {
         if (!do_pss) pl.pss_fwd = pl.pss_rev = false;
         if (!do_kmer) pl.fk5 = pl.fk3 = false;
         if (pl.pss_fwd || pl.pss_rev) {
-            if (LDS_TABLE) tally_pss_record<true>(P, LdsTableRowMajor{dyn_lds, rows}, src, h, pl);
+            if (P.off_site) {   // -X: the in-context pair takes its adds straight in the counter block
+                const GlobalSite site{P.counters + P.off_site, rows * 16u};
+                if (LDS_TABLE) tally_pss_record<true, true>(P, LdsTableRowMajor{dyn_lds, rows}, site, src, h, pl);
+                else tally_pss_record<true, true>(P, GlobalTable{P.counters, P.off_rev}, site, src, h, pl);
+            } else if (LDS_TABLE) tally_pss_record<true>(P, LdsTableRowMajor{dyn_lds, rows}, src, h, pl);
             else tally_pss_record<true>(P, GlobalTable{P.counters, P.off_rev}, src, h, pl);
             // -H: straight into the counter block (hist_lds_bins is 0 in this kernel's launches)
             if (P.hist_max) hist_add(P, nullptr, hist_bin(P, pl.L), pl.pss_fwd, pl.pss_rev, 1u);
@@ -326,15 +372,18 @@ __device__ __forceinline__ void stage_tile_dma(const uint8_t *recs, uint64_t rec
 // nothing.  It reads the kernel arguments through a pointer to the kernarg segment (taken in
 // the kernel): a reference to the kernel's by-value copy would force that whole struct into
 // scratch memory.
-template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool MASKQ = false, bool REGIONS = false, bool HIST = false>
+template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool MASKQ = false, bool REGIONS = false, bool HIST = false, bool SITE = false>
 __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyParams *kernarg, uint32_t o0,
                                                                     uint32_t o1, uint32_t *table, uint32_t *lds_kmer,
-                                                                    uint32_t *hist_lds = nullptr) {
+                                                                    uint32_t *hist_lds = nullptr, uint32_t *site_lds = nullptr) {
     const TallyParams &P = *kernarg;
     GlobalBytes gsrc{P.recs + o0};
     const RecHdr gh = decode_hdr(gsrc, o1 - o0);
     const Plan gpl = make_plan<DO_PSS, DO_KMER, REGIONS>(P, gsrc, gh);
-    if (DO_PSS && (gpl.pss_fwd || gpl.pss_rev)) tally_pss_record<MASKQ>(P, LdsTableColumnMajor{table, P.row_base}, gsrc, gh, gpl);
+    if constexpr (SITE) {
+        if (gpl.pss_fwd || gpl.pss_rev)
+            tally_pss_record<MASKQ, true>(P, LdsTableColumnMajor{table, P.row_base}, LdsSiteColumnMajor{site_lds, P.row_base}, gsrc, gh, gpl);
+    } else if (DO_PSS && (gpl.pss_fwd || gpl.pss_rev)) tally_pss_record<MASKQ>(P, LdsTableColumnMajor{table, P.row_base}, gsrc, gh, gpl);
     if constexpr (HIST) {   // (the HIST instantiation is a pass-0 one: counted once)
         if (gpl.pss_fwd || gpl.pss_rev) hist_add(P, hist_lds, hist_bin(P, gpl.L), gpl.pss_fwd, gpl.pss_rev, 1u);
     }
@@ -459,8 +508,16 @@ __device__ __forceinline__ uint32_t base_quality_mask(uint32_t x, uint32_t q4) {
 // of every read that is added to a table counts its length (hist_wave_add); `hist_lds` holds the LDS part of the two
 // arrays and is added to the counter block when the workgroup is done, one 64-bit atomic per non-zero bin.  Nothing is
 // read that the kernel does not read anyway.  The instantiations without HIST contain none of it.
+//
+// SITE (-X cpg, P.off_site != 0; one plane, substitution tables only): CODES-B compares the window's reference codes with
+// their one-base neighbours -- GE / GO against each other shifted by a byte -- and sets CODE_SITE in the sheet byte of
+// every interior position whose reference position is in CpG context; COLUMNS adds such a position a second time, into
+// the 2 KiB in-context table `site_lds` (SITE_WORDS).  The neighbour beyond either edge of the window (one nibble each)
+// comes with the window gather in CODES-A: the one behind it lies in the fifth gathered dword already, the one in
+// front of it is one more dword load of a line the gather touches anyway.  The instantiations without SITE contain
+// none of it.
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS, PlaneSel PLANES = PLANES_NONE, bool MASKQ = false,
-          bool REGIONS = false, bool HIST = false>
+          bool REGIONS = false, bool HIST = false, bool SITE = false>
 __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const TallyParams *kernarg,
                                                  uint8_t *__restrict__ stage, uint8_t *__restrict__ sheet,
                                                  uint32_t *__restrict__ table,
@@ -468,8 +525,9 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
                                                  uint32_t *__restrict__ lds_kmer,
                                                  int32_t *__restrict__ lds_delta, uint4 *__restrict__ refs_lds,
                                                  const PlaneParams *gk = nullptr, uint32_t *__restrict__ grp_lds = nullptr,
-                                                 uint32_t *__restrict__ hist_lds = nullptr) {
+                                                 uint32_t *__restrict__ hist_lds = nullptr, uint32_t *__restrict__ site_lds = nullptr) {
     constexpr bool GROUPED = PLANES != PLANES_NONE;   // one table plane per read group / length bin
+    static_assert(!SITE || (DO_PSS && !DO_KMER && PLANES == PLANES_NONE && !HIST), "site context belongs to the one-plane substitution tally without the length histogram");
     static_assert(!HIST || (DO_PSS && !LATER_PASS && PLANES == PLANES_NONE), "the length histogram belongs to pass 0 of the one-plane substitution tally");
     constexpr bool KPLANES = GROUPED && DO_KMER;      // ... of k-mer bins (tally_tiled_kmer_planes: no sheet, no table)
     static_assert(!KPLANES || !DO_PSS, "planes split either the substitution tables or the k-mer tables");
@@ -501,6 +559,8 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
     if (tid < ST_USED) lds_delta[tid] = 0;
     if constexpr (HIST)
         for (uint32_t i = tid; i < 2u * P.hist_lds_bins; i += TILED_THREADS) hist_lds[i] = 0u;
+    if constexpr (SITE)
+        for (uint32_t i = tid; i < SITE_WORDS; i += TILED_THREADS) site_lds[i] = 0u;
     // contig info of the first BAM references (all of them for a human-sized header) + the "*" entry
     const uint32_t n_ref_cached = min((uint32_t)P.n_ref, REF_LDS_ENTRIES);
     if (tid < n_ref_cached) refs_lds[tid] = P.ref_info[tid];
@@ -584,6 +644,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         // misalignment): five dwords, one dwordx4 + one dword gather
         uint32_t gq[5] = {0u, 0u, 0u, 0u, 0u};
         uint32_t gsh = 0u;
+        uint32_t nb_front = 4u, nb_behind = 4u;   // SITE: the reference nibbles next to the window, positions -1 and 32 of it
         if (cand) {
             const uint64_t ga = pl.gbase + (uint64_t)pl.s + (e ? (uint64_t)pl.L - 30ull - row_base : (uint64_t)row_base - 2ull);
             const uint32_t *pg = P.genome4 + (ga >> 3);
@@ -592,6 +653,8 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
 #pragma unroll
                 for (int k = 0; k < 4; k++) gq[k] = q0.v[k];
                 gq[4] = pg[4];
+                // (a candidate's window starts at most 31 bases in front of its contig: inside the padding between contigs)
+                if constexpr (SITE) nb_front = P.genome4[(ga - 1ull) >> 3] >> (4u * (uint32_t)((ga - 1ull) & 7ull));
             }
             gsh = 4u * (uint32_t)(ga & 7ull);
         }
@@ -674,7 +737,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         if (in_tile && !in_stage && e == 0u) {
             if constexpr (KPLANES) ev_over = tally_overflow_record_kmer_planes<PLANES, LDS_KMER, REGIONS>(kernarg, gk, o0, o1, lds_kmer);
             else if constexpr (GROUPED) ev_over = tally_overflow_record_planes<PLANES, MASKQ, REGIONS>(kernarg, gk, o0, o1, table);
-            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS, HIST>(kernarg, o0, o1, table, lds_kmer, hist_lds);
+            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS, HIST, SITE>(kernarg, o0, o1, table, lds_kmer, hist_lds, site_lds);
             if (pass0) atomicAdd(&lds_delta[ST_SLOW_PATH], 1);
         }
         // First use of the gathered registers happens HERE, before the next tile's DMA is issued:
@@ -690,6 +753,12 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
 #pragma unroll
         for (int m = 0; m < 4; m++) asm volatile("" : "+v"(W[m]));
         asm volatile("" : "+v"(cx));
+        if constexpr (SITE) {   // window position 32 = nibble (ga & 7) of the fifth dword
+            nb_front &= 15u;
+            nb_behind = (gq[4] >> gsh) & 15u;
+            asm volatile("" : "+v"(nb_front));
+            asm volatile("" : "+v"(nb_behind));
+        }
         if (DO_KMER) {
 #pragma unroll
             for (int k = 0; k < 2; k++) asm volatile("" : "+v"(kw[k]));
@@ -810,6 +879,36 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
                     code_w[2 * m] = ((RE[m] | GE[m] | tsel4) ^ sx) & 0x3F3F3F3Fu;
                     code_w[2 * m + 1] = ((RO[m] | GO[m] | tsel4) ^ sx) & 0x3F3F3F3Fu;
                 }
+                if constexpr (SITE) {
+                    // Reference codes are A 6, C 4, G 2, T 0, other 0xFF: bits 1-2 alone tell C (10) and G (01) from the
+                    // rest (11, 00).  c? / g? carry 0x02 in the bytes that hold a C / a G.  Both windows run in genome
+                    // order, so the next base of an even position is the same byte of the odd word, the next base of an
+                    // odd position the following byte of the even word, and the previous bases mirror that; the bytes
+                    // beyond the window's edges come from nb_front / nb_behind.  In context: C followed by G, or G
+                    // preceded by C.
+                    const uint32_t B = 0x02020202u;
+                    uint32_t cE[4], gE[5], cO[5], gO[4];   // cO[0] / gE[4]: the words in front of / behind the window
+                    cO[0] = nb_front == 1u ? 0x02000000u : 0u;
+                    gE[4] = nb_behind == 2u ? 0x00000002u : 0u;
+#pragma unroll
+                    for (int m = 0; m < 4; m++) {
+                        const uint32_t yE = GE[m] & 0x06060606u, yO = GO[m] & 0x06060606u;
+                        cE[m] = (yE >> 1) & ~yE & B;
+                        gE[m] = yE & ~(yE >> 1) & B;
+                        cO[m + 1] = (yO >> 1) & ~yO & B;
+                        gO[m] = yO & ~(yO >> 1) & B;
+                    }
+                    // the context positions (rows 0, 1) are reference-only: never in the in-context table
+                    const uint32_t ml = (e || !pass0) ? 0u : 0x000000FFu, mr = (e && pass0) ? 0xFF000000u : 0u;
+#pragma unroll
+                    for (int m = 0; m < 4; m++) {
+                        const uint32_t keep = ~((m == 0 ? ml : 0u) | (m == 3 ? mr : 0u));
+                        const uint32_t inE = (cE[m] & gO[m]) | (gE[m] & __builtin_amdgcn_alignbyte(cO[m + 1], cO[m], 3));
+                        const uint32_t inO = (cO[m + 1] & __builtin_amdgcn_alignbyte(gE[m + 1], gE[m], 1)) | (gO[m] & cE[m]);
+                        code_w[2 * m] |= (inE << 5) & keep;       // 0x02 -> CODE_SITE
+                        code_w[2 * m + 1] |= (inO << 5) & keep;
+                    }
+                }
             }
             bool kmer_ok = true;
             if (kmer_try) {
@@ -878,6 +977,22 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
                     const uint32_t po = __builtin_amdgcn_readfirstlane(grp_lds[j]) * GROUP_PLANE_WORDS;
                     atomicAdd(&table[(c << 5) + row + (c < 32u ? po : trash_off)], 1u);
                 }
+            } else if (SITE && row < n_live) {
+                // a real code (< 32) with CODE_SITE set counts a second time, in the in-context table: its half code is
+                // the code without the reference base's low bit
+                auto add = [&](uint32_t c) {
+                    atomicAdd(&table[((c & 63u) << 5) + row], 1u);
+                    if ((c & (CODE_SITE | CODE_NONE)) == CODE_SITE) atomicAdd(&site_lds[((((c >> 1) & 14u) | (c & 1u)) << 5) + row], 1u);
+                };
+                uint32_t j = j0;
+                for (; j + 8u <= j1; j += 8u) {
+                    uint32_t c[8];
+#pragma unroll
+                    for (int u = 0; u < 8; u++) c[u] = sheet[(j + u) * 64u + lane];
+#pragma unroll
+                    for (int u = 0; u < 8; u++) add(c[u]);
+                }
+                for (; j < j1; j++) add(sheet[j * 64u + lane]);
             } else if (row < n_live) {  // (lanes of dead rows would only ever see CODE_NONE)
                 uint32_t j = j0;
                 for (; j + 8u <= j1; j += 8u) {
@@ -908,7 +1023,9 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         for (uint32_t i = tid; i < n_words; i += TILED_THREADS) mine[GROUP_SCRATCH_DELTA + i] = table[i];
         if (tid < 16u) mine[tid] = tid < (uint32_t)ST_USED ? (uint32_t)lds_delta[tid] : 0u;
     } else {
-    uint32_t *mine = P.scratch + (size_t)blockIdx.x * SCRATCH_WORDS;
+    uint32_t *mine = P.scratch + (size_t)blockIdx.x * (SITE ? SITE_SCRATCH_WORDS : SCRATCH_WORDS);
+    if constexpr (SITE)   // [table | k-mer bins | deltas | in-context table]
+        for (uint32_t i = tid; i < SITE_WORDS; i += TILED_THREADS) mine[SCRATCH_WORDS + i] = site_lds[i];
     for (uint32_t i = tid; i < 32u * 32u; i += TILED_THREADS) mine[i] = DO_PSS ? table[i] : 0u;
     for (uint32_t i = tid; i < 512u; i += TILED_THREADS)
         mine[SCRATCH_KMER + i] = (LDS_KMER && i < 2u * (1u << (2 * P.K))) ? lds_kmer[i] : 0u;
@@ -1398,10 +1515,14 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_compact_decode_twice(cons
 // Sums the per-workgroup partials of one tally_tiled launch into the u64 counter block.
 // Thread (word w, group g) adds up slots g, g+REDUCE_GROUPS, ... of word w (loads coalesce across
 // w) and contributes one atomic; launched on the same stream right behind the tally kernel.
+// SITE: the slots of a SITE launch, SITE_SCRATCH_WORDS apart; word SCRATCH_WORDS + (half code << 5 | row) goes to
+// the [fwd_in | rev_in] pair at P.off_site (rows 0 and 1 of the pair are never written).
 constexpr uint32_t REDUCE_GROUPS = 32;
+template <bool SITE = false>
 __global__ void __launch_bounds__(256) reduce_partials(const TallyParams P, uint32_t n_slots, uint32_t lds_kmer_on) {
+    constexpr uint32_t SLOT_WORDS = SITE ? SITE_SCRATCH_WORDS : SCRATCH_WORDS;
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t i = gid % SCRATCH_WORDS, g = gid / SCRATCH_WORDS;
+    const uint32_t i = gid % SLOT_WORDS, g = gid / SLOT_WORDS;
     if (g >= REDUCE_GROUPS) return;
     const bool do_pss = (P.tally_mask & 1u) != 0, do_kmer = (P.tally_mask & 2u) != 0;
     const uint32_t n_pos = (uint32_t)P.N + 2u;
@@ -1413,6 +1534,10 @@ __global__ void __launch_bounds__(256) reduce_partials(const TallyParams P, uint
     } else if (i < SCRATCH_DELTA) {
         const uint32_t k = i - SCRATCH_KMER, nb = do_kmer ? 1u << (2 * P.K) : 0u;
         if (lds_kmer_on && k < 2u * nb) dst = &P.counters[k < nb ? P.off_k5 + k : P.off_k3 + (k - nb)];
+    } else if (SITE && i >= SCRATCH_WORDS) {
+        const uint32_t k = i - SCRATCH_WORDS, row = P.row_base + (k & 31u), hc = k >> 5;
+        const uint32_t cell = ((hc >> 2) << 2) | ((hc & 2u) ? 2u : 1u);
+        if (row >= 2u && row < n_pos) dst = &P.counters[P.off_site + ((hc & 1u) ? n_pos * 16u : 0u) + row * 16u + cell];
     } else {
         const uint32_t k = i - SCRATCH_DELTA;  // status counters belong to pass 0
         if (k < (uint32_t)ST_USED && P.row_base == 0u) { dst = &P.counters[P.off_stats + k]; is_delta = true; }
@@ -1422,7 +1547,7 @@ __global__ void __launch_bounds__(256) reduce_partials(const TallyParams P, uint
     const uint32_t *p = P.scratch + i;
 #pragma unroll 8
     for (uint32_t b = g; b < n_slots; b += REDUCE_GROUPS) {
-        const uint32_t v = p[(size_t)b * SCRATCH_WORDS];
+        const uint32_t v = p[(size_t)b * SLOT_WORDS];
         sum += is_delta ? (long long)(int32_t)v : (long long)v;
     }
     if (is_delta && g == 0u) {
@@ -1434,7 +1559,9 @@ __global__ void __launch_bounds__(256) reduce_partials(const TallyParams P, uint
 }
 
 // HIST: dynamic LDS is the staging buffer and, behind it, the 2 * P.hist_lds_bins words of the length histogram
-template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS = false, bool MASKQ = false, bool REGIONS = false, bool HIST = false>
+// SITE: one more static object, the 2 KiB in-context table
+template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS = false, bool MASKQ = false, bool REGIONS = false, bool HIST = false,
+          bool SITE = false>
 __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
@@ -1446,6 +1573,11 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P
     // the kernel's single argument, as it lies in the kernarg segment (for the out-of-line path)
     const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
     uint32_t *hist_lds = HIST ? (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces)) : nullptr;
+    if constexpr (SITE) {
+        __shared__ uint32_t site_lds[SITE_WORDS];
+        tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, true>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
+                                                                                                      lds_delta, refs_lds, nullptr, nullptr, hist_lds, site_lds);
+    } else
     tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
                                                                                             lds_delta, refs_lds, nullptr, nullptr, hist_lds);
 }

@@ -27,6 +27,9 @@ typedef struct run_result {
      * table, hist_max + 2 rows each (row hist_max + 1: every longer read), or NULL */
     int hist_max;
     uint64_t *hist_fwd, *hist_rev;
+    /* pss-bam -X (frontend_site_context): the in-context tables IN, (region_len+2)*16 each with rows 0/1 as fwd / rev,
+     * or NULL */
+    unsigned long *site_fwd, *site_rev;
 } run_result;
 
 /* pss-bam -G: every engine gets the input header's @RG IDs (pssbam_engine_set_read_groups) and run_tally()
@@ -40,6 +43,10 @@ extern int frontend_min_base_quality;
 /* pss-bam -H: the limit of the fragment-length histogram (0: off); every engine gets it
  * (pssbam_engine_set_length_histogram) and run_tally() returns the two arrays.  Set before frontend_warmup_start. */
 extern int frontend_length_hist;
+
+/* pss-bam -X: the site context (PSSBAM_SITE_*; PSSBAM_SITE_NONE: off); every engine gets it
+ * (pssbam_engine_set_site_context) and run_tally() returns the in-context pair.  Set before frontend_warmup_start. */
+extern int frontend_site_context;
 
 /* -T: the intervals of the BED file (regions.h; NULL: none); every engine gets them (pssbam_engine_set_regions), on
  * every input path -- the filter lives in the engine.  Set before frontend_warmup_start. */

@@ -27,6 +27,10 @@
  * Added: -H <max> also writes <prefix>.pss.lengths.txt, the fragment-length histogram (the length -l / -L compare,
  * 0..max and one row for everything longer) of the reads that were added to the forward / reverse table, from the
  * same pass; the other files stay as they are.  Not with -G, -S or -C.
+ * Added: -X cpg also writes <prefix>.cpg.pss.*.txt, the tables over the positions whose reference site lies in a CpG
+ * dinucleotide (C followed by G, or G preceded by C, in the folded reference), and <prefix>.noncpg.pss.*.txt, the tables
+ * over every other position -- what this command writes for the input with the read bases at the other kind of site
+ * replaced by N -- from the same pass; the other files stay as they are.  Not with -G, -S, -C or -H.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -56,9 +60,9 @@ int main(int argc, char *argv[])
     unsigned long min_read_len = 0, max_read_len = 250000000;
     const char *up_ctx = "ACGT", *down_ctx = "ACGT";
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL, *read_group = NULL;
-    const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL, *bed_fn = NULL, *hist_arg = NULL;
+    const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL, *bed_fn = NULL, *hist_arg = NULL, *site_arg = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -76,6 +80,7 @@ int main(int argc, char *argv[])
         case 'Q': min_bq_arg = optarg; break;
         case 'T': bed_fn = optarg; break;
         case 'H': hist_arg = optarg; break;
+        case 'X': site_arg = optarg; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -150,6 +155,18 @@ int main(int argc, char *argv[])
             exit(1);
         }
     }
+    if (site_arg) {
+        if (strcmp(site_arg, "cpg") != 0) {
+            fprintf(stderr, "-X (tables per site context): unknown context \"%s\"; the one context is cpg.\n", site_arg);
+            exit(1);
+        }
+        if (by_group || len_edges || ctg_map || hist_arg) {
+            fprintf(stderr, "-X (tables per site context) and %s exclude each other.\n",
+                    by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)"
+                    : ctg_map ? "-C (tables per contig set)" : "-H (fragment-length histogram)");
+            exit(1);
+        }
+    }
     pss_regions bed;
     memset(&bed, 0, sizeof bed);
     if (bed_fn) {
@@ -204,6 +221,7 @@ int main(int argc, char *argv[])
     if (ctg_map) fprintf(stderr, " -C %s", ctg_map);
     if (min_bq_arg) fprintf(stderr, " -Q %d", min_bq);
     if (hist_arg) fprintf(stderr, " -H %d", hist_max);
+    if (site_arg) fprintf(stderr, " -X %s", site_arg);
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -227,6 +245,7 @@ int main(int argc, char *argv[])
     if (ctg_map) frontend_contig_sets = &sets;
     frontend_min_base_quality = min_bq;
     frontend_length_hist = hist_max;
+    frontend_site_context = site_arg ? PSSBAM_SITE_CPG : PSSBAM_SITE_NONE;
     if (bed_fn) frontend_regions = &bed;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
@@ -252,6 +271,19 @@ int main(int argc, char *argv[])
     pss_write_counts(fasta_fn, bam_fn, out_prefix, region_len, res.fwd, res.rev);
     pss_write_rates(fasta_fn, bam_fn, out_prefix, region_len, fwd_rates, rev_rates);
     if (res.hist_fwd && pss_write_lengths(fasta_fn, bam_fn, out_prefix, res.hist_max, res.hist_fwd, res.hist_rev)) exit(1);
+    if (res.site_fwd) {   /* -X: IN as the engine returns it; OUT = T - IN on the position rows, the context rows as T */
+        const size_t cells = (size_t)(region_len + 2) * 16;
+        unsigned long *out_fwd = (unsigned long *)malloc(cells * sizeof *out_fwd), *out_rev = (unsigned long *)malloc(cells * sizeof *out_rev);
+        if (!out_fwd || !out_rev) { fprintf(stderr, "Error: out of memory\n"); exit(1); }
+        for (size_t i = 0; i < cells; i++) {
+            out_fwd[i] = i < 32 ? res.fwd[i] : res.fwd[i] - res.site_fwd[i];
+            out_rev[i] = i < 32 ? res.rev[i] : res.rev[i] - res.site_rev[i];
+        }
+        if (pss_write_labelled(fasta_fn, bam_fn, out_prefix, "cpg", region_len, res.site_fwd, res.site_rev) ||
+            pss_write_labelled(fasta_fn, bam_fn, out_prefix, "noncpg", region_len, out_fwd, out_rev)) exit(1);
+        free(out_fwd);
+        free(out_rev);
+    }
     if (by_group && res.n_planes == 0)
         fprintf(stderr, "Warning: -G: the header of %s has no @RG line; only the tables of all reads were written.\n", bam_fn);
     /* <prefix>.<tag>: what `-R <ID> -o <prefix>.<ID>` (-G), `-l <lo> -L <hi> -o <prefix>.len<lo>-<hi>` (-S) or -F

@@ -104,6 +104,26 @@ int pss_write_rates(const char *fasta_fn, const char *bam_fn, const char *out_pr
     return 0;
 }
 
+int pss_write_labelled(const char *fasta_fn, const char *bam_fn, const char *out_prefix, const char *tag, int region_len,
+                       const unsigned long *fwd, const unsigned long *rev)
+{
+    const size_t n_rates = (size_t)(region_len ? region_len : 1) * 12;
+    char *prefix = (char *)malloc(strlen(out_prefix) + strlen(tag) + 2);
+    double *fwd_rates = (double *)calloc(n_rates, sizeof(double)), *rev_rates = (double *)calloc(n_rates, sizeof(double));
+    int rc = 1;
+    if (prefix && fwd_rates && rev_rates) {
+        sprintf(prefix, "%s.%s", out_prefix, tag);
+        pss_sub_rates(region_len, fwd, fwd_rates);
+        pss_sub_rates(region_len, rev, rev_rates);
+        rc = pss_write_counts(fasta_fn, bam_fn, prefix, region_len, fwd, rev);
+        rc |= pss_write_rates(fasta_fn, bam_fn, prefix, region_len, fwd_rates, rev_rates);
+    } else fprintf(stderr, "Error: out of memory\n");
+    free(prefix);
+    free(fwd_rates);
+    free(rev_rates);
+    return rc;
+}
+
 int pss_write_lengths(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int max_len, const uint64_t *fwd,
                       const uint64_t *rev)
 {

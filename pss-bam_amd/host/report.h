@@ -10,6 +10,11 @@ int pss_write_counts(const char *fasta_fn, const char *bam_fn, const char *out_p
                      const unsigned long *fwd, const unsigned long *rev);
 int pss_write_rates(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int region_len,
                     const double *fwd_rates, const double *rev_rates);
+/* One labelled pair of files, <out_prefix>.<tag>.pss.counts.txt and .rates.txt, through the two writers above (what
+ * -G / -S / -C write per plane and -X per context); `tag` is already file-name encoded.  Returns 0, or 1 after a
+ * diagnostic. */
+int pss_write_labelled(const char *fasta_fn, const char *bam_fn, const char *out_prefix, const char *tag, int region_len,
+                       const unsigned long *fwd, const unsigned long *rev);
 /* pss-bam -H: <out_prefix>.pss.lengths.txt -- three '#' lines, the column names, then one tab-separated line
  * "<length> <fwd> <rev>" per length 0..max_len (zero rows included) and a last one labelled "><max_len>" for every
  * longer read; fwd / rev hold max_len + 2 counts.  Returns 0, or 1 after a diagnostic. */
