@@ -18,6 +18,8 @@
 #include <map>
 #include <string>
 #include <thread>
+#include <tuple>
+#include <type_traits>
 #include <unordered_map>
 #include <atomic>
 #include <memory>
@@ -154,22 +156,7 @@ void pin_release(const void *p) {
 }
 }  // namespace
 
-// tiled_grid's memo slots: one per kernel instantiation launch_tally launches with dynamic LDS
-enum PrepSlot : int {
-    PREP_TILED_PSS, PREP_TILED_PSS_LATER, PREP_TILED_PSS_KMER, PREP_TILED_PSS_KMER_LDS, PREP_TILED_KMER, PREP_TILED_KMER_LDS,
-    PREP_COMPACT, PREP_COMPACT_KMER, PREP_COMPACT_KMER_LDS,
-    PREP_COMPACT_ONCE, PREP_COMPACT_ONCE_KMER, PREP_COMPACT_ONCE_KMER_LDS, PREP_COMPACT_DECODE_TWICE,
-    PREP_PLANES_RG, PREP_PLANES_RG_LATER, PREP_PLANES_LEN, PREP_PLANES_LEN_LATER, PREP_PLANES_REF, PREP_PLANES_REF_LATER,
-    PREP_KPLANES_RG, PREP_KPLANES_RG_LDS, PREP_KPLANES_LEN, PREP_KPLANES_LEN_LDS, PREP_KPLANES_REF, PREP_KPLANES_REF_LDS,
-    // -Q (min_bq > 0): the MASKQ instantiations, in the order of their unmasked twins
-    PREP_TILED_PSS_BQ, PREP_TILED_PSS_LATER_BQ, PREP_TILED_PSS_KMER_BQ, PREP_TILED_PSS_KMER_LDS_BQ,
-    PREP_PLANES_RG_BQ, PREP_PLANES_RG_LATER_BQ, PREP_PLANES_LEN_BQ, PREP_PLANES_LEN_LATER_BQ, PREP_PLANES_REF_BQ, PREP_PLANES_REF_LATER_BQ,
-    // -H (hist_max > 0): the HIST instantiations of pass 0, without and with -Q
-    PREP_TILED_PSS_H, PREP_TILED_PSS_KMER_H, PREP_TILED_PSS_KMER_LDS_H, PREP_TILED_PSS_H_BQ, PREP_TILED_PSS_KMER_H_BQ, PREP_TILED_PSS_KMER_LDS_H_BQ,
-    // -X (site_mode != 0): the SITE instantiations, without and with -Q
-    PREP_TILED_SITE, PREP_TILED_SITE_LATER, PREP_TILED_SITE_BQ, PREP_TILED_SITE_LATER_BQ,
-    PREP_N   // -T: the REGIONS instantiation of slot s is memo slot PREP_N + s
-};
+struct KernelPrep { uint32_t lds = 0; int occ = 0; };   // tiled_grid's memo of one kernel: dynamic-LDS limit set, occupancy at it
 
 struct pssbam_engine {
     pssbam_config cfg{};
@@ -291,8 +278,7 @@ struct pssbam_engine {
     int env_group_slots = 0;   // PSSBAM_GROUP_SLOTS: at most this many planes per -G launch (tests: plane passes with few groups)
     bool warned_ablate = false;
     bool compact_plan_once = false;   // tally_compact: header decode + filters once per read, plan through LDS (PSSBAM_COMPACT_PLAN_ONCE)
-    uint32_t prep_lds[2 * PREP_N] = {0};   // tiled_grid's memo, by kernel
-    int prep_occ[2 * PREP_N] = {0};
+    std::unordered_map<const void *, KernelPrep> prep;   // tiled_grid's memo, by the kernel's host address
     bool use_compact = true;        // -r N <= 16: tally_compact (PSSBAM_COMPACT=0 keeps tally_tiled, for A/B runs)
     uint32_t *d_scratch = nullptr;  // per-workgroup partial tables of the tiled kernel
     size_t scratch_slots = 0;
@@ -861,20 +847,21 @@ static int resolve_launch_events(pssbam_engine *e) {
 
 // Grid of one launch of a tiled-family kernel over n_tiles tiles: n_cu x occupancy x PSSBAM_GRID_MULT workgroups
 // (PSSBAM_GRID_WGS: that many), at most one per tile; d_scratch grows to `words` per workgroup.  The kernel's
-// dynamic-LDS limit and occupancy are remembered per (slot, LDS size), so the steady state makes no runtime API calls
-// per launch beyond the launches themselves.
+// dynamic-LDS limit and occupancy are remembered per kernel and set again only when its LDS size changes, so the steady
+// state makes no runtime API calls per launch beyond the launches themselves.
 template <class K>
-static int tiled_grid(pssbam_engine *e, PrepSlot slot, K kernel, uint32_t lds, uint32_t n_tiles, uint32_t words, uint32_t *grid) {
-    if (e->prep_lds[slot] != lds || e->prep_occ[slot] < 1) {
+static int tiled_grid(pssbam_engine *e, K kernel, uint32_t lds, uint32_t n_tiles, uint32_t words, uint32_t *grid) {
+    KernelPrep &prep = e->prep[(const void *)kernel];
+    if (prep.lds != lds || prep.occ < 1) {
         int occ = 0;
         HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, TILED_THREADS, lds));
         if (occ < 1) return fail(PSSBAM_EHIP, "kernel does not fit a CU with %u bytes of LDS", lds);
-        e->prep_lds[slot] = lds;
-        e->prep_occ[slot] = occ;
+        prep.lds = lds;
+        prep.occ = occ;
     }
     const int mult = e->env_grid_mult > 0 ? e->env_grid_mult : 1;
-    *grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)e->n_cu * e->prep_occ[slot] * mult);
+    *grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)e->n_cu * prep.occ * mult);
     if (e->env_grid_wgs > 0) *grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)e->env_grid_wgs);
     const size_t need_slots = ((size_t)*grid * words + SCRATCH_WORDS - 1) / SCRATCH_WORDS;
     if (e->scratch_slots < need_slots) {
@@ -887,79 +874,57 @@ static int tiled_grid(pssbam_engine *e, PrepSlot slot, K kernel, uint32_t lds, u
     return PSSBAM_OK;
 }
 
-// One launch of a kernel with a single table plane (tally_tiled, tally_compact*) and its reduce_partials
+// One launch of a tiled-family tally kernel and of the reduce kernel that sums the `words` of scratch each of its workgroups
+// leaves into the counter block: kernel(P, planes...), then reduce(P, planes..., workgroups, tail...)
+template <class K, class R, class... Planes, class... Tail>
+static int launch_with_reduce(pssbam_engine *e, K kernel, R reduce, uint32_t words, uint32_t lds, uint32_t n_tiles, TallyParams &P,
+                              const std::tuple<Planes...> &planes, Tail... tail) {
+    uint32_t grid = 0;
+    const int rc = tiled_grid(e, kernel, lds, n_tiles, words, &grid);
+    if (rc != PSSBAM_OK) return rc;
+    P.scratch = e->d_scratch;
+    std::apply([&](const auto &...G) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(TILED_THREADS), lds, e->stream, P, G...);
+        hipLaunchKernelGGL(reduce, dim3((words * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream, P, G..., grid, tail...);
+    }, planes);
+    return PSSBAM_OK;
+}
+
+// f(std::bool_constant<flag>...): runtime flags turned into template arguments
+template <class F>
+static int with_flags(F f) { return f(); }
+template <class F, class... Flags>
+static int with_flags(F f, bool flag, Flags... rest) {
+    return flag ? with_flags([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
+                : with_flags([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+
+// f(std::integral_constant<PlaneSel, sel>): the same for the plane selector of an engine with planes
+template <class F>
+static int with_planes(PlaneSel sel, F f) {
+    return sel == PLANES_RG    ? f(std::integral_constant<PlaneSel, PLANES_RG>{})
+           : sel == PLANES_LEN ? f(std::integral_constant<PlaneSel, PLANES_LEN>{})
+                               : f(std::integral_constant<PlaneSel, PLANES_REF>{});
+}
+
+static int no_kernel() { return fail(PSSBAM_EINVAL, "no tally kernel is built for this combination of options"); }
+
+// One row pass of tally_tiled and its reduce_partials: the instantiation for the launch's tallies, the pass (LATER: rows
+// 32.. of a large -r) and its -Q, -T, -H and -X state.  `exists` is the list of instantiations: the k-mer tally (alone or
+// beside the substitution tables) and -H belong to pass 0, -Q -H -X to the substitution tables, -X excludes the other two.
 // (SITE: the larger scratch slot of the -X instantiations and the reduce that walks it)
-template <bool SITE = false, class K>
-static int launch_flat(pssbam_engine *e, PrepSlot slot, K kernel, TallyParams &P, uint32_t lds, uint32_t n_tiles, bool lds_kmer) {
-    constexpr uint32_t words = SITE ? SITE_SCRATCH_WORDS : SCRATCH_WORDS;
-    uint32_t grid = 0;
-    const int rc = tiled_grid(e, slot, kernel, lds, n_tiles, words, &grid);
-    if (rc != PSSBAM_OK) return rc;
-    P.scratch = e->d_scratch;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(TILED_THREADS), lds, e->stream, P);
-    hipLaunchKernelGGL(reduce_partials<SITE>, dim3((words * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream, P, grid,
-                       (uint32_t)(lds_kmer ? 1 : 0));
-    return PSSBAM_OK;
-}
-
-// launch_flat of one tally_tiled instantiation, or of its REGIONS twin when the launch carries a region table (-T)
-template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER, bool MASKQ, bool HIST = false>
-static int launch_tiled(pssbam_engine *e, PrepSlot slot, TallyParams &P, uint32_t lds, uint32_t n_tiles) {
-    if (P.region_info)
-        return launch_flat(e, (PrepSlot)(slot + PREP_N), tally_tiled<DO_PSS, DO_KMER, LDS_KMER, LATER, MASKQ, true, HIST>, P, lds, n_tiles, LDS_KMER);
-    return launch_flat(e, slot, tally_tiled<DO_PSS, DO_KMER, LDS_KMER, LATER, MASKQ, false, HIST>, P, lds, n_tiles, LDS_KMER);
-}
-
-// One row pass of a launch with site context (-X): the SITE instantiation for the pass and the launch's -Q and -T state
-template <bool LATER, bool MASKQ>
-static int launch_tiled_site(pssbam_engine *e, TallyParams &P, uint32_t lds, uint32_t n_tiles) {
-    constexpr PrepSlot slot = MASKQ ? (LATER ? PREP_TILED_SITE_LATER_BQ : PREP_TILED_SITE_BQ) : (LATER ? PREP_TILED_SITE_LATER : PREP_TILED_SITE);
-    if (P.region_info)
-        return launch_flat<true>(e, (PrepSlot)(slot + PREP_N), tally_tiled<true, false, false, LATER, MASKQ, true, false, true>, P, lds, n_tiles, false);
-    return launch_flat<true>(e, slot, tally_tiled<true, false, false, LATER, MASKQ, false, false, true>, P, lds, n_tiles, false);
-}
-
-// Pass 0 of a launch with the length histogram (-H): the HIST instantiation for the launch's tallies and -Q state
-template <bool MASKQ>
-static int launch_tiled_hist(pssbam_engine *e, TallyParams &P, bool do_kmer, bool kmer_lds, uint32_t lds, uint32_t n_tiles) {
-    constexpr int bq = MASKQ ? PREP_TILED_PSS_H_BQ - PREP_TILED_PSS_H : 0;
-    if (!do_kmer) return launch_tiled<true, false, false, false, MASKQ, true>(e, (PrepSlot)(PREP_TILED_PSS_H + bq), P, lds, n_tiles);
-    return kmer_lds ? launch_tiled<true, true, true, false, MASKQ, true>(e, (PrepSlot)(PREP_TILED_PSS_KMER_LDS_H + bq), P, lds, n_tiles)
-                    : launch_tiled<true, true, false, false, MASKQ, true>(e, (PrepSlot)(PREP_TILED_PSS_KMER_H + bq), P, lds, n_tiles);
-}
-
-// One (row pass, plane pass) launch of tally_tiled_planes and its reduce_partials_grouped
-template <PlaneSel SEL, bool LATER, bool MASKQ, bool REGIONS>
-static int launch_planes(pssbam_engine *e, TallyParams &P, const PlaneParams &G, uint32_t lds, uint32_t n_tiles) {
-    constexpr PrepSlot plain = SEL == PLANES_RG  ? (LATER ? PREP_PLANES_RG_LATER : PREP_PLANES_RG)
-                             : SEL == PLANES_LEN ? (LATER ? PREP_PLANES_LEN_LATER : PREP_PLANES_LEN)
-                                                 : (LATER ? PREP_PLANES_REF_LATER : PREP_PLANES_REF);
-    constexpr PrepSlot unfiltered = MASKQ ? (PrepSlot)(PREP_PLANES_RG_BQ + (plain - PREP_PLANES_RG)) : plain;
-    constexpr PrepSlot slot = (PrepSlot)(unfiltered + (REGIONS ? PREP_N : 0));
-    uint32_t grid = 0;
-    const int rc = tiled_grid(e, slot, tally_tiled_planes<SEL, LATER, MASKQ, REGIONS>, lds, n_tiles, G.scratch_words, &grid);
-    if (rc != PSSBAM_OK) return rc;
-    P.scratch = e->d_scratch;
-    hipLaunchKernelGGL((tally_tiled_planes<SEL, LATER, MASKQ, REGIONS>), dim3(grid), dim3(TILED_THREADS), lds, e->stream, P, G);
-    hipLaunchKernelGGL(reduce_partials_grouped, dim3((G.scratch_words * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream, P, G, grid);
-    return PSSBAM_OK;
-}
-
-// One plane pass of tally_tiled_kmer_planes and its reduce_partials_kmer_planes
-template <PlaneSel SEL, bool LDS_KMER, bool REGIONS>
-static int launch_kmer_planes(pssbam_engine *e, TallyParams &P, const PlaneParams &G, uint32_t lds, uint32_t n_tiles) {
-    constexpr PrepSlot unfiltered = SEL == PLANES_RG  ? (LDS_KMER ? PREP_KPLANES_RG_LDS : PREP_KPLANES_RG)
-                                  : SEL == PLANES_LEN ? (LDS_KMER ? PREP_KPLANES_LEN_LDS : PREP_KPLANES_LEN)
-                                                      : (LDS_KMER ? PREP_KPLANES_REF_LDS : PREP_KPLANES_REF);
-    constexpr PrepSlot slot = (PrepSlot)(unfiltered + (REGIONS ? PREP_N : 0));
-    uint32_t grid = 0;
-    const int rc = tiled_grid(e, slot, tally_tiled_kmer_planes<SEL, LDS_KMER, REGIONS>, lds, n_tiles, G.scratch_words, &grid);
-    if (rc != PSSBAM_OK) return rc;
-    P.scratch = e->d_scratch;
-    hipLaunchKernelGGL((tally_tiled_kmer_planes<SEL, LDS_KMER, REGIONS>), dim3(grid), dim3(TILED_THREADS), lds, e->stream, P, G);
-    hipLaunchKernelGGL(reduce_partials_kmer_planes, dim3((G.scratch_words * REDUCE_GROUPS + 255) / 256), dim3(256), 0, e->stream, P, G, grid,
-                       (uint32_t)(LDS_KMER ? 1 : 0));
-    return PSSBAM_OK;
+static int launch_tiled(pssbam_engine *e, TallyParams &P, bool do_pss, bool do_kmer, bool kmer_lds, bool later, bool maskq, bool regions,
+                        bool hist, bool site, uint32_t lds, uint32_t n_tiles) {
+    return with_flags([&](auto DO_PSS, auto DO_KMER, auto LDS_KMER, auto LATER, auto MASKQ, auto REGIONS, auto HIST, auto SITE) -> int {
+        constexpr bool exists = (DO_KMER() || !LDS_KMER()) &&
+                                (LATER() ? DO_PSS() && !DO_KMER() && !HIST()
+                                         : (DO_PSS() || DO_KMER()) && (DO_PSS() || !(MASKQ() || HIST() || SITE())) && !(SITE() && (DO_KMER() || HIST())));
+        if constexpr (exists)
+            return launch_with_reduce(e, tally_tiled<DO_PSS(), DO_KMER(), LDS_KMER(), LATER(), MASKQ(), REGIONS(), HIST(), SITE()>, reduce_partials<SITE()>,
+                                      SITE() ? SITE_SCRATCH_WORDS : SCRATCH_WORDS, lds, n_tiles, P, std::tuple<>(), (uint32_t)LDS_KMER());
+        else
+            return no_kernel();
+    }, do_pss, do_kmer, kmer_lds, later, maskq, regions, hist, site);
 }
 
 // How many 16-byte pieces of a record the tiled kernel must stage so that everything the path
@@ -1100,13 +1065,12 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         const bool lds_tab = do_pss && tab_bytes <= 60u * 1024u;
         uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n_records + 255) / 256, (uint64_t)e->n_cu * 8);
         if (e->env_simple_blocks > 0) blocks = (uint32_t)e->env_simple_blocks;
-        if (e->planes != PLANES_NONE && !do_pss) {   // k-mer planes
-            if (e->planes == PLANES_RG) hipLaunchKernelGGL(tally_simple_kmer_planes<PLANES_RG>, dim3(blocks), dim3(256), 0, e->stream, P, G);
-            else if (e->planes == PLANES_LEN) hipLaunchKernelGGL(tally_simple_kmer_planes<PLANES_LEN>, dim3(blocks), dim3(256), 0, e->stream, P, G);
-            else hipLaunchKernelGGL(tally_simple_kmer_planes<PLANES_REF>, dim3(blocks), dim3(256), 0, e->stream, P, G);
-        } else if (e->planes == PLANES_RG) hipLaunchKernelGGL(tally_simple_planes<PLANES_RG>, dim3(blocks), dim3(256), 0, e->stream, P, G);
-        else if (e->planes == PLANES_LEN) hipLaunchKernelGGL(tally_simple_planes<PLANES_LEN>, dim3(blocks), dim3(256), 0, e->stream, P, G);
-        else if (e->planes == PLANES_REF) hipLaunchKernelGGL(tally_simple_planes<PLANES_REF>, dim3(blocks), dim3(256), 0, e->stream, P, G);
+        if (e->planes != PLANES_NONE)
+            with_planes(e->planes, [&](auto SEL) {
+                if (do_pss) hipLaunchKernelGGL(tally_simple_planes<SEL()>, dim3(blocks), dim3(256), 0, e->stream, P, G);
+                else hipLaunchKernelGGL(tally_simple_kmer_planes<SEL()>, dim3(blocks), dim3(256), 0, e->stream, P, G);
+                return PSSBAM_OK;
+            });
         else if (lds_tab) hipLaunchKernelGGL(tally_simple<true>, dim3(blocks), dim3(256), tab_bytes, e->stream, P);
         else hipLaunchKernelGGL(tally_simple<false>, dim3(blocks), dim3(256), 0, e->stream, P);
     } else {
@@ -1167,128 +1131,69 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         const uint32_t lds = tiled_lds_bytes(T, pieces);
         int rc = PSSBAM_OK;
         P.row_base = 0;
-        if (e->planes != PLANES_NONE && !do_pss) {
-            // k-mer planes.  k <= KMER_LDS_MAX_K: a plane pass holds as many 2 * 4^k-word histograms (plus the trash slot) as
-            // fit the LDS beside the staging buffer -- 2 KiB each at k = 4, so 64 bins and plane 0 are one pass -- and more
-            // planes take more passes, each re-reading the records.  Larger k: global atomics, one pass whatever the count.
-            using LaunchK = int (*)(pssbam_engine *, TallyParams &, const PlaneParams &, uint32_t, uint32_t);
-            static constexpr LaunchK launch_kr[2][3][2] = {
-                {{launch_kmer_planes<PLANES_RG, false, false>, launch_kmer_planes<PLANES_RG, true, false>},
-                 {launch_kmer_planes<PLANES_LEN, false, false>, launch_kmer_planes<PLANES_LEN, true, false>},
-                 {launch_kmer_planes<PLANES_REF, false, false>, launch_kmer_planes<PLANES_REF, true, false>}},
-                {{launch_kmer_planes<PLANES_RG, false, true>, launch_kmer_planes<PLANES_RG, true, true>},
-                 {launch_kmer_planes<PLANES_LEN, false, true>, launch_kmer_planes<PLANES_LEN, true, true>},
-                 {launch_kmer_planes<PLANES_REF, false, true>, launch_kmer_planes<PLANES_REF, true, true>}}};
-            const auto &launch_k = launch_kr[regions];
+        if (e->planes != PLANES_NONE) {
+            // -G / -S / -C: every (32-row pass, plane pass) pair is one launch over the block.  A plane pass holds as many
+            // planes as fit the LDS beside the staging buffer, plus a trash plane; more planes take more passes, each
+            // re-reading the records.  Substitution planes are 4 KiB each (8 = 32 KiB always fit: one pass for up to 7 groups
+            // or sets, or 6 bins -- plane 0 of -S stays empty but keeps its slot).  K-mer planes (one row pass) are
+            // 2 * 4^k-word histograms at k <= KMER_LDS_MAX_K -- 2 KiB each at k = 4, so 64 bins and plane 0 are one pass;
+            // larger k: global atomics, no plane in LDS, one pass whatever the count.
             const uint32_t n_planes = G.n_groups + 1u;
-            if (kmer_lds) {
-                const uint32_t hist = 2u * (1u << (2 * c.kmer.klen)) * 4u;   // bytes of one plane's histogram
-                const uint32_t fit = lds + 2u * hist <= KMER_PLANES_LDS_BUDGET ? (KMER_PLANES_LDS_BUDGET - lds) / hist - 1u : 1u;
-                uint32_t per_pass = std::min(n_planes, fit);
+            const uint32_t plane_bytes = do_pss ? GROUP_PLANE_WORDS * 4u : kmer_lds ? 2u * (1u << (2 * c.kmer.klen)) * 4u : 0u;
+            const uint32_t budget = do_pss ? GROUPED_LDS_BUDGET : KMER_PLANES_LDS_BUDGET;
+            uint32_t per_pass = n_planes;
+            if (plane_bytes) {
+                const uint32_t fit = lds + 2u * plane_bytes <= budget ? (budget - lds) / plane_bytes - 1u : 1u;
+                per_pass = std::min(n_planes, fit);
                 if (e->env_group_slots > 0) per_pass = std::min(per_pass, (uint32_t)e->env_group_slots);
-                for (uint32_t plane0 = 0; plane0 < n_planes && rc == PSSBAM_OK; plane0 += per_pass) {
-                    G.plane0 = plane0;
-                    G.n_slots = std::min(per_pass, n_planes - plane0);
-                    G.scratch_words = GROUP_SCRATCH_DELTA + G.n_slots * (hist / 4u);
-                    rc = launch_k[e->planes - PLANES_RG][1](e, P, G, tiled_kmer_planes_lds_bytes(T, pieces, G.n_slots, c.kmer.klen, true), n_tiles);
-                }
-            } else {
-                G.plane0 = 0;
-                G.n_slots = n_planes;
-                G.scratch_words = GROUP_SCRATCH_DELTA;
-                rc = launch_k[e->planes - PLANES_RG][0](e, P, G, lds, n_tiles);
             }
-        } else if (e->planes != PLANES_NONE) {
-            // -G / -S / -C: every (32-row pass, plane pass) pair is one launch over the block.  A plane pass holds
-            // as many planes as fit the LDS beside the staging buffer (8 planes = 32 KiB always do: one pass for
-            // up to 7 groups or sets, or 6 bins -- plane 0 of -S stays empty but keeps its slot); more planes take
-            // more passes, each re-reading the records.
-            using LaunchPlanes = int (*)(pssbam_engine *, TallyParams &, const PlaneParams &, uint32_t, uint32_t);
-            static constexpr LaunchPlanes launch_pass_r[2][2][3][2] = {
-                {{{launch_planes<PLANES_RG, false, false, false>, launch_planes<PLANES_RG, true, false, false>},
-                  {launch_planes<PLANES_LEN, false, false, false>, launch_planes<PLANES_LEN, true, false, false>},
-                  {launch_planes<PLANES_REF, false, false, false>, launch_planes<PLANES_REF, true, false, false>}},
-                 {{launch_planes<PLANES_RG, false, true, false>, launch_planes<PLANES_RG, true, true, false>},
-                  {launch_planes<PLANES_LEN, false, true, false>, launch_planes<PLANES_LEN, true, true, false>},
-                  {launch_planes<PLANES_REF, false, true, false>, launch_planes<PLANES_REF, true, true, false>}}},
-                {{{launch_planes<PLANES_RG, false, false, true>, launch_planes<PLANES_RG, true, false, true>},
-                  {launch_planes<PLANES_LEN, false, false, true>, launch_planes<PLANES_LEN, true, false, true>},
-                  {launch_planes<PLANES_REF, false, false, true>, launch_planes<PLANES_REF, true, false, true>}},
-                 {{launch_planes<PLANES_RG, false, true, true>, launch_planes<PLANES_RG, true, true, true>},
-                  {launch_planes<PLANES_LEN, false, true, true>, launch_planes<PLANES_LEN, true, true, true>},
-                  {launch_planes<PLANES_REF, false, true, true>, launch_planes<PLANES_REF, true, true, true>}}}};
-            const auto &launch_pass = launch_pass_r[regions];
-            const uint32_t n_planes = G.n_groups + 1u;
-            const uint32_t fit = lds + 2u * GROUP_PLANE_WORDS * 4u <= GROUPED_LDS_BUDGET
-                                     ? (GROUPED_LDS_BUDGET - lds) / (GROUP_PLANE_WORDS * 4u) - 1u : 1u;
-            uint32_t per_pass = std::min(n_planes, fit);
-            if (e->env_group_slots > 0) per_pass = std::min(per_pass, (uint32_t)e->env_group_slots);
             for (uint32_t pass = 0; pass < n_passes && rc == PSSBAM_OK; pass++) {
                 P.row_base = pass * TILED_ROWS;
                 for (uint32_t plane0 = 0; plane0 < n_planes && rc == PSSBAM_OK; plane0 += per_pass) {
                     G.plane0 = plane0;
                     G.n_slots = std::min(per_pass, n_planes - plane0);
-                    G.scratch_words = GROUP_SCRATCH_DELTA + G.n_slots * GROUP_PLANE_WORDS;
-                    rc = launch_pass[maskq][e->planes - PLANES_RG][pass > 0](e, P, G, tiled_grouped_lds_bytes(T, pieces, G.n_slots), n_tiles);
+                    G.scratch_words = GROUP_SCRATCH_DELTA + G.n_slots * (plane_bytes / 4u);
+                    rc = with_planes(e->planes, [&](auto SEL) {
+                        if (do_pss)
+                            return with_flags([&](auto LATER, auto MASKQ, auto REGIONS) {
+                                return launch_with_reduce(e, tally_tiled_planes<SEL(), LATER(), MASKQ(), REGIONS()>, reduce_partials_grouped, G.scratch_words,
+                                                          tiled_grouped_lds_bytes(T, pieces, G.n_slots), n_tiles, P, std::tie(G));
+                            }, pass > 0, maskq, regions);
+                        return with_flags([&](auto LDS_KMER, auto REGIONS) {
+                            return launch_with_reduce(e, tally_tiled_kmer_planes<SEL(), LDS_KMER(), REGIONS()>, reduce_partials_kmer_planes, G.scratch_words,
+                                                      tiled_kmer_planes_lds_bytes(T, pieces, G.n_slots, c.kmer.klen, LDS_KMER()), n_tiles, P, std::tie(G),
+                                                      (uint32_t)LDS_KMER());
+                        }, kmer_lds, regions);
+                    });
                 }
             }
-        } else if (site) {
-            // -X: tally_tiled with the neighbour compare and the in-context table, for every -r (tally_compact has no such arm)
-            rc = maskq ? launch_tiled_site<false, true>(e, P, lds, n_tiles) : launch_tiled_site<false, false>(e, P, lds, n_tiles);
-            for (uint32_t pass = 1; pass < n_passes && rc == PSSBAM_OK; pass++) {
-                P.row_base = pass * TILED_ROWS;
-                rc = maskq ? launch_tiled_site<true, true>(e, P, lds, n_tiles) : launch_tiled_site<true, false>(e, P, lds, n_tiles);
-            }
-        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions && !hist) {
+        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions && !hist && !site) {
             // -r N <= 16 (2 context rows + 16 positions): the short-window variant, one pass (it stages prefixes only
             // and has no QUAL path: -R and -Q go to tally_tiled; so do -T, -H and -X, whose arms only tally_tiled carries)
             if (!do_kmer && getenv("PSSBAM_COMPACT_DECODE_TWICE"))   // diagnostics: what the shared header decode costs
-                rc = launch_flat(e, PREP_COMPACT_DECODE_TWICE, tally_compact_decode_twice, P, lds, n_tiles, false);
-            else if (e->compact_plan_once)
-                rc = !do_kmer  ? launch_flat(e, PREP_COMPACT_ONCE, tally_compact<false, false, true>, P, lds, n_tiles, false)
-                     : kmer_lds ? launch_flat(e, PREP_COMPACT_ONCE_KMER_LDS, tally_compact<true, true, true>, P, lds, n_tiles, true)
-                                : launch_flat(e, PREP_COMPACT_ONCE_KMER, tally_compact<true, false, true>, P, lds, n_tiles, false);
+                rc = launch_with_reduce(e, tally_compact_decode_twice, reduce_partials<false>, SCRATCH_WORDS, lds, n_tiles, P, std::tuple<>(), 0u);
             else
-                rc = !do_kmer  ? launch_flat(e, PREP_COMPACT, tally_compact<false, false, false>, P, lds, n_tiles, false)
-                     : kmer_lds ? launch_flat(e, PREP_COMPACT_KMER_LDS, tally_compact<true, true, false>, P, lds, n_tiles, true)
-                                : launch_flat(e, PREP_COMPACT_KMER, tally_compact<true, false, false>, P, lds, n_tiles, false);
-        } else if (hist) {
-            // -H: pass 0 is the HIST instantiation of tally_tiled, with the LDS part of the two arrays behind the staging
-            // buffer (at most HIST_LDS_MAX_BINS bins each: 8 KiB); the later passes of a large -r count nothing again
-            P.hist_lds_bins = std::min(e->hist_max + 2u, HIST_LDS_MAX_BINS);
-            if (e->env_hist_lds_bins >= 0) P.hist_lds_bins = std::min(P.hist_lds_bins, (uint32_t)e->env_hist_lds_bins);
-            const uint32_t lds_h = lds + hist_lds_bytes(P.hist_lds_bins);
-            rc = maskq ? launch_tiled_hist<true>(e, P, do_kmer, kmer_lds, lds_h, n_tiles) : launch_tiled_hist<false>(e, P, do_kmer, kmer_lds, lds_h, n_tiles);
-            for (uint32_t pass = 1; pass < n_passes && rc == PSSBAM_OK; pass++) {
-                P.row_base = pass * TILED_ROWS;
-                rc = maskq ? launch_tiled<true, false, false, true, true>(e, PREP_TILED_PSS_LATER_BQ, P, lds, n_tiles)
-                           : launch_tiled<true, false, false, true, false>(e, PREP_TILED_PSS_LATER, P, lds, n_tiles);
-            }
-        } else if (maskq) {
-            // -Q: tally_tiled with the QUAL fetch and the per-position mask, for every -r (later passes as below)
-            if (do_kmer)
-                rc = kmer_lds ? launch_tiled<true, true, true, false, true>(e, PREP_TILED_PSS_KMER_LDS_BQ, P, lds, n_tiles)
-                              : launch_tiled<true, true, false, false, true>(e, PREP_TILED_PSS_KMER_BQ, P, lds, n_tiles);
-            else
-                rc = launch_tiled<true, false, false, false, true>(e, PREP_TILED_PSS_BQ, P, lds, n_tiles);
-            for (uint32_t pass = 1; pass < n_passes && rc == PSSBAM_OK; pass++) {
-                P.row_base = pass * TILED_ROWS;
-                rc = launch_tiled<true, false, false, true, true>(e, PREP_TILED_PSS_LATER_BQ, P, lds, n_tiles);
-            }
+                rc = with_flags([&](auto DO_KMER, auto LDS_KMER, auto PLAN_ONCE) -> int {
+                    if constexpr (DO_KMER() || !LDS_KMER())
+                        return launch_with_reduce(e, tally_compact<DO_KMER(), LDS_KMER(), PLAN_ONCE()>, reduce_partials<false>, SCRATCH_WORDS, lds, n_tiles, P,
+                                                  std::tuple<>(), (uint32_t)LDS_KMER());
+                    else
+                        return no_kernel();
+                }, do_kmer, kmer_lds, e->compact_plan_once);
         } else {
-            if (do_pss && do_kmer)
-                rc = kmer_lds ? launch_tiled<true, true, true, false, false>(e, PREP_TILED_PSS_KMER_LDS, P, lds, n_tiles)
-                              : launch_tiled<true, true, false, false, false>(e, PREP_TILED_PSS_KMER, P, lds, n_tiles);
-            else if (do_pss)
-                rc = launch_tiled<true, false, false, false, false>(e, PREP_TILED_PSS, P, lds, n_tiles);
-            else
-                rc = kmer_lds ? launch_tiled<false, true, true, false, false>(e, PREP_TILED_KMER_LDS, P, lds, n_tiles)
-                              : launch_tiled<false, true, false, false, false>(e, PREP_TILED_KMER, P, lds, n_tiles);
-            // rows 32.. of a large -r: further passes over the same block, substitution rows only
-            // (the status counters and the k-mer tally belong to pass 0)
-            for (uint32_t pass = 1; pass < n_passes && rc == PSSBAM_OK; pass++) {
+            // tally_tiled, 32 table rows per pass over the block.  Pass 0 has the status counters, the k-mer tally and -H's
+            // histogram, with the LDS part of its two arrays behind the staging buffer (at most HIST_LDS_MAX_BINS bins each:
+            // 8 KiB); rows 32.. of a large -r are further passes, substitution rows only, that count nothing of these again
+            uint32_t lds0 = lds;
+            if (hist) {
+                P.hist_lds_bins = std::min(e->hist_max + 2u, HIST_LDS_MAX_BINS);
+                if (e->env_hist_lds_bins >= 0) P.hist_lds_bins = std::min(P.hist_lds_bins, (uint32_t)e->env_hist_lds_bins);
+                lds0 += hist_lds_bytes(P.hist_lds_bins);
+            }
+            for (uint32_t pass = 0; pass < n_passes && rc == PSSBAM_OK; pass++) {
                 P.row_base = pass * TILED_ROWS;
-                rc = launch_tiled<true, false, false, true, false>(e, PREP_TILED_PSS_LATER, P, lds, n_tiles);
+                rc = pass == 0 ? launch_tiled(e, P, do_pss, do_kmer, kmer_lds, false, maskq, regions, hist, site, lds0, n_tiles)
+                               : launch_tiled(e, P, true, false, false, true, maskq, regions, false, site, lds, n_tiles);
             }
         }
         if (rc != PSSBAM_OK) return rc;
@@ -1521,17 +1426,35 @@ extern "C" int pssbam_engine_finish_kmer_groups(pssbam_engine *e, int32_t group,
     return PSSBAM_OK;
 }
 
-// What set_read_groups and set_length_bins share: the counter block grows to n_planes [fwd | rev] planes behind the stats,
-// zeroed (nothing has been counted yet).  The old block may still be named by work queued on the stream (the compressed
-// feed): it is retired, not freed.  `what` names the caller's planes in the messages.
+// What the setters that resize the counter block require: nothing tallied yet, and the block is the engine's own.  `what`
+// names what is being set in the messages.
+static int check_may_resize(const pssbam_engine *e, const char *what) {
+    if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set %s after create or reset, before the first tally", what);
+    if (e->d_counters != e->d_counters_own) return fail(PSSBAM_ESTATE, "a caller-bound counter block cannot grow: set %s before bind_counters", what);
+    return PSSBAM_OK;
+}
+
+// The counter block becomes n_counters words (more or fewer than before), zeroed: nothing has been counted yet.  The old
+// block may still be named by work queued on the stream (the compressed feed): it is retired, not freed.
+static int grow_counters(pssbam_engine *e, uint64_t n_counters) {
+    unsigned long long *d_counters = nullptr;
+    HIP_TRY(hipMalloc(&d_counters, n_counters * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(d_counters, 0, n_counters * sizeof(unsigned long long), e->stream));
+    if (e->d_counters_own) e->retired.push_back(e->d_counters_own);
+    e->d_counters = e->d_counters_own = d_counters;
+    e->n_counters = n_counters;
+    return PSSBAM_OK;
+}
+
+// What set_read_groups, set_length_bins and set_contig_sets share: the counter block grows to n_planes [fwd | rev] planes
+// (a k-mer engine: [k5 | k3]) behind the stats.  `what` names the caller's planes in the messages.
 static int set_planes(pssbam_engine *e, PlaneSel sel, uint32_t n_planes, const char *what) {
     if (e->hist_max) return fail(PSSBAM_EINVAL, "%s and the length histogram exclude each other", what);
     if (e->site_mode) return fail(PSSBAM_EINVAL, "%s and site context exclude each other", what);
     const bool kmer = e->cfg.tally_mask == PSSBAM_TALLY_KMER;
     if (e->cfg.tally_mask != PSSBAM_TALLY_PSS && !kmer)
         return fail(PSSBAM_EINVAL, "%s split the substitution tables or the k-mer tables, not both (PSSBAM_TALLY_PSS | PSSBAM_TALLY_KMER)", what);
-    if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set %s after create or reset, before the first tally", what);
-    if (e->d_counters != e->d_counters_own) return fail(PSSBAM_ESTATE, "a caller-bound counter block cannot grow: set %s before bind_counters", what);
+    if (const int rc = check_may_resize(e, what)) return rc;
     HIP_TRY(hipSetDevice(e->device));
     // 64-bit throughout: a k-mer plane is 2 * 4^k words (2^31 at k = 15)
     const uint64_t n_counters = (uint64_t)e->off_groups + (uint64_t)n_planes * (kmer ? e->kplane_words : (uint64_t)e->plane_words);
@@ -1543,12 +1466,7 @@ static int set_planes(pssbam_engine *e, PlaneSel sel, uint32_t n_planes, const c
                         e->cfg.kmer.klen, n_planes + 1u, n_planes, what, (unsigned long long)(n_counters * sizeof(unsigned long long)),
                         (unsigned long long)free_b);
     }
-    unsigned long long *d_counters = nullptr;
-    HIP_TRY(hipMalloc(&d_counters, n_counters * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(d_counters, 0, n_counters * sizeof(unsigned long long), e->stream));
-    if (e->d_counters_own) e->retired.push_back(e->d_counters_own);
-    e->d_counters = e->d_counters_own = d_counters;
-    e->n_counters = n_counters;
+    if (const int rc = grow_counters(e, n_counters)) return rc;
     e->planes = sel;
     e->n_planes = n_planes;
     return PSSBAM_OK;
@@ -1624,20 +1542,13 @@ extern "C" int pssbam_engine_set_length_histogram(pssbam_engine *e, int32_t max_
         return fail(PSSBAM_EINVAL, "the length histogram counts the reads added to the substitution tables: the engine needs PSSBAM_TALLY_PSS");
     if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the length histogram and read groups / length bins / contig sets exclude each other");
     if (e->site_mode) return fail(PSSBAM_EINVAL, "the length histogram and site context exclude each other");
-    if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the length histogram after create or reset, before the first tally");
-    if (e->d_counters != e->d_counters_own) return fail(PSSBAM_ESTATE, "a caller-bound counter block cannot grow: set the length histogram before bind_counters");
+    if (const int rc = check_may_resize(e, "the length histogram")) return rc;
     if ((uint32_t)max_len == e->hist_max) return PSSBAM_OK;
     HIP_TRY(hipSetDevice(e->device));
-    // the block grows (or shrinks back) behind everything it holds without the histogram; zeroed: nothing has been counted
-    // yet.  The old block may still be named by work queued on the stream: retired, not freed (set_planes).
+    // the block grows (or shrinks back) behind everything it holds without the histogram
     const uint64_t n_counters = (uint64_t)e->off_groups + (max_len ? 2ull * ((uint64_t)max_len + 2ull) : 0ull);
     if (n_counters > 0xFFFFFFFFull) return fail(PSSBAM_EINVAL, "the counter block would pass 2^32 words");
-    unsigned long long *d_counters = nullptr;
-    HIP_TRY(hipMalloc(&d_counters, n_counters * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(d_counters, 0, n_counters * sizeof(unsigned long long), e->stream));
-    if (e->d_counters_own) e->retired.push_back(e->d_counters_own);
-    e->d_counters = e->d_counters_own = d_counters;
-    e->n_counters = n_counters;
+    if (const int rc = grow_counters(e, n_counters)) return rc;
     e->hist_max = (uint32_t)max_len;
     e->off_hist = e->off_groups;
     return PSSBAM_OK;
@@ -1661,20 +1572,13 @@ extern "C" int pssbam_engine_set_site_context(pssbam_engine *e, int32_t mode) {
         return fail(PSSBAM_EINVAL, "site context splits the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
     if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "site context and read groups / length bins / contig sets exclude each other");
     if (e->hist_max) return fail(PSSBAM_EINVAL, "site context and the length histogram exclude each other");
-    if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the site context after create or reset, before the first tally");
-    if (e->d_counters != e->d_counters_own) return fail(PSSBAM_ESTATE, "a caller-bound counter block cannot grow: set the site context before bind_counters");
+    if (const int rc = check_may_resize(e, "the site context")) return rc;
     if ((uint32_t)mode == e->site_mode) return PSSBAM_OK;
     HIP_TRY(hipSetDevice(e->device));
-    // the block grows (or shrinks back) behind everything it holds without the pair; zeroed: nothing has been counted yet.
-    // The old block may still be named by work queued on the stream: retired, not freed (set_planes).
+    // the block grows (or shrinks back) behind everything it holds without the pair
     const uint64_t n_counters = (uint64_t)e->off_groups + (mode ? 2ull * e->rows * 16ull : 0ull);
     if (n_counters > 0xFFFFFFFFull) return fail(PSSBAM_EINVAL, "the counter block would pass 2^32 words");
-    unsigned long long *d_counters = nullptr;
-    HIP_TRY(hipMalloc(&d_counters, n_counters * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(d_counters, 0, n_counters * sizeof(unsigned long long), e->stream));
-    if (e->d_counters_own) e->retired.push_back(e->d_counters_own);
-    e->d_counters = e->d_counters_own = d_counters;
-    e->n_counters = n_counters;
+    if (const int rc = grow_counters(e, n_counters)) return rc;
     e->site_mode = (uint32_t)mode;
     e->off_site = mode ? e->off_groups : 0u;
     return PSSBAM_OK;

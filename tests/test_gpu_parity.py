@@ -415,3 +415,74 @@ def test_read_group_behind_large_aux_arrays(pkg, oracle, tmp_path):
                 assert got.stats["rg_dropped"] == len(recs) - len(keep)
     finally:
         oracle.free_genome(g)
+
+
+def test_one_engine_through_option_changes_across_reset(pkg, oracle, tmp_path):
+    """one engine walked through -Q, -H and -X and back across reset(): the kernels of all five steps share the engine's
+    launch state and the counter block grows and shrinks twice.  After every step each table the option exposes and the
+    status counters equal those of a fresh engine with the same options; the last step equals the first; the plain and
+    the -Q step are also held against the oracle (-Q: on the masked SAM, as in test_gpu_base_quality.py).  -r 40 is two
+    row passes of tally_tiled"""
+    import base_quality_lib as bq
+    contigs, refs, recs = tl.fuzz_dataset(4040, 3000)
+    raw = tl.raw_records(refs, recs)
+    po = tl.PssOpts(region_len=40)
+    hist_max = 100
+    assert max(len(r.seq) for r in recs) > hist_max
+    sams = {0: tmp_path / "q0.sam", 20: tmp_path / "q20.sam"}
+    tl.write_sam(sams[0], refs, recs)
+    bq.write_masked_sam(sams[20], refs, recs, 20)
+    g = oracle.genome_from_arrays(tl.loaded_contigs(contigs))
+    try:
+        want = {q: oracle.pss(g, sam, po) for q, sam in sams.items()}
+    finally:
+        oracle.free_genome(g)
+
+    def new_engine(**kw):
+        eng = pkg.Engine(pss=_pss_dict(po), kernel=pkg.KERNEL_TILED, **kw)
+        eng.set_genome_arrays(tl.loaded_contigs(contigs))
+        eng.set_references([n for n, _ in refs])
+        return eng
+
+    def tables(eng):
+        """everything the engine's options expose, after one pass over the records"""
+        eng.submit(raw)
+        hist = eng.finish_length_hist() if eng.length_hist else ()
+        site = eng.finish_site_context() if eng.site_context else ()
+        return eng.finish(), hist, site
+
+    def same(a, b, ctx):
+        assert np.array_equal(a[0].fwd, b[0].fwd) and np.array_equal(a[0].rev, b[0].rev) and a[0].stats == b[0].stats, ctx
+        for x, y in zip(a[1:], b[1:]):
+            assert len(x) == len(y) and all(np.array_equal(u, v) for u, v in zip(x, y)), ctx
+
+    # per step: the options a fresh engine is created with, and the setter calls that take the one engine there from the step
+    # before -- an option goes off before the next goes on: -H and -X exclude each other, and each setter says so even when
+    # it is asked to switch its own option off
+    steps = [(dict(), []),
+             (dict(min_base_qual=20), [("set_min_base_quality", 20)]),
+             (dict(length_hist=hist_max), [("set_min_base_quality", 0), ("set_length_histogram", hist_max)]),
+             (dict(site_context="cpg"), [("set_length_histogram", 0), ("set_site_context", "cpg")]),
+             (dict(), [("set_site_context", None)])]
+    eng = new_engine()
+    got = []
+    try:
+        for i, (kw, calls) in enumerate(steps):
+            if i:
+                eng.reset()
+            for setter, value in calls:
+                getattr(eng, setter)(value)
+            got.append(tables(eng))
+            fresh = new_engine(**kw)
+            try:
+                same(got[-1], tables(fresh), (i, kw))
+            finally:
+                fresh.close()
+    finally:
+        eng.close()
+    same(got[4], got[0], "step 5 against step 1")
+    _check_pss(got[0][0], *want[0])
+    _check_pss(got[1][0], *want[20])
+    assert (got[1][0].fwd[2:] != got[0][0].fwd[2:]).any()                  # -Q took bases out
+    assert len(got[2][1]) == 2 and got[2][1][0][-1] + got[2][1][1][-1] > 0   # reads beyond the limit share the last row
+    assert len(got[3][2]) == 2 and 0 < got[3][2][0][2:].sum() < got[3][0].fwd[2:].sum()
