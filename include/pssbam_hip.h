@@ -41,6 +41,7 @@ extern "C" {
 #define PSSBAM_MAX_REGIONS (1 << 26) /* pssbam_engine_set_regions: intervals in one call */
 #define PSSBAM_SITE_NONE 0           /* pssbam_engine_set_site_context: off */
 #define PSSBAM_SITE_CPG 1            /* ... the reference position lies in a CpG dinucleotide */
+#define PSSBAM_MAX_END_DEPTH 8       /* pssbam_engine_set_end_condition: positions of an end that are searched for its mark */
 
 /* error codes */
 #define PSSBAM_OK 0
@@ -352,6 +353,43 @@ int pssbam_engine_set_site_context(pssbam_engine *e, int32_t mode);
  * filled from T; either pointer may be NULL.  PSSBAM_EINVAL when the setting is off. */
 int pssbam_engine_finish_site_context(pssbam_engine *e, unsigned long *fwd_in, unsigned long *rev_in);
 
+/* End condition (pss-bam -E): a second pair of substitution tables, COND, over the unpaired records whose OTHER end
+ * carries a given substitution, from the same pass as the ordinary tables T -- the conditional substitution analysis
+ * of damage (a fragment with a C->T at its 5' end is almost certainly old, so the 3' table over those fragments alone
+ * measures damage in a contaminated library).  For a record that is added to the tables let o[0..L-1] / g[0..L-1] be
+ * the read and reference bases as process_aln pairs them (upper case, both reverse-complemented for a FLAG 0x10 read):
+ * forward-table row 2+i receives (o[i], g[i]), reverse-table row 2+i receives (o[L-1-i], g[L-1-i]), and
+ * cell(r, f) = 4*code(r) + code(f) with A 0, C 1, G 2, T 3 is the column of the counts file; a pair with a member that
+ * is not A/C/G/T has no cell.  With depth d (1..PSSBAM_MAX_END_DEPTH, d <= region_len) and the cells cell5, cell3
+ * (0..15; 13 = read T on reference C, 2 = read A on reference G) a record is
+ *     5'-marked when it is unpaired (FLAG 0x1 clear) and cell(o[i], g[i]) == cell5 for some i < d,
+ *     3'-marked when it is unpaired and cell(o[L-1-i], g[L-1-i]) == cell3 for some i < d.
+ * A base below a minimum base quality has no cell (it behaves as N, as pssbam_engine_set_min_base_quality states).  A
+ * tallied read has L >= region_len >= d, so every position looked at exists; the two windows may overlap (L < 2d).
+ * COND.fwd receives a record's whole forward contribution (rows 0 and 1 included) exactly when the record is added to
+ * T.fwd, is unpaired and is 3'-marked; COND.rev its whole reverse contribution exactly when it is added to T.rev, is
+ * unpaired and is 5'-marked.  Paired records never reach COND: their other end lives in another record.  Four read
+ * counters go with the pair: reads[0] = unpaired records added to the tables, reads[1] = those that are 5'-marked,
+ * reads[2] = those that are 3'-marked, reads[3] = those that are both.  So
+ *     COND.fwd == the forward table of the same options on the input reduced to the unpaired 3'-marked records,
+ *     COND.rev == the reverse table on the input reduced to the unpaired 5'-marked records,
+ * and T, every status counter and the record filters are bit-identical to the engine without the setting.  depth == 0
+ * switches it off: the engine then launches exactly the kernels it launches without this call and n_u64 is unchanged.
+ * Legal after create (or reset) and before the first tally launch; with pssbam_engine_feed_open that is any time
+ * before set_references.  Goes with cfg.read_group, a minimum base quality and regions.  PSSBAM_EINVAL for arguments
+ * outside their ranges, for depth > region_len, for region_len > 30 (the marks are taken from the code words of the
+ * one 32-row pass that holds both ends' first positions; a later pass of a larger -r would have to gather them
+ * again, so it is refused), on an engine with PSSBAM_TALLY_KMER in its mask, and with read groups, length bins, contig
+ * sets, a length histogram or site context set (those setters return PSSBAM_EINVAL once the end condition is on);
+ * PSSBAM_ESTATE once records have been tallied or the counter block has been bound (the block grows, see
+ * pssbam_engine_counters_device).  The setting survives pssbam_engine_reset; engines whose blocks are summed must all
+ * have been given the same arguments. */
+int pssbam_engine_set_end_condition(pssbam_engine *e, int32_t depth, int32_t cell5, int32_t cell3);
+
+/* Drains the engine like pssbam_engine_finish and copies COND's two tables, (region_len+2)*16 words each, and the four
+ * read counters; any pointer may be NULL.  PSSBAM_EINVAL when the setting is off. */
+int pssbam_engine_finish_end_condition(pssbam_engine *e, unsigned long *fwd_c, unsigned long *rev_c, uint64_t reads[4]);
+
 /* The device-resident counter block [fwd | rev | k5 | k3 | stats] as one array of
  * n_u64 64-bit words, for a caller-side RCCL reduce across GPUs (sum, uint64).  With read groups it is
  * [fwd | rev | stats | fwd_0 | rev_0 | ... | fwd_n-1 | rev_n-1]: the leading fwd | rev are the unassigned
@@ -369,7 +407,12 @@ int pssbam_engine_finish_site_context(pssbam_engine *e, unsigned long *fwd_in, u
  * in-context pair is appended: [fwd | rev | stats | fwd_in | rev_in], fwd_in at 2*(region_len+2)*16 + PSSBAM_ST_N (the
  * old n_u64), rev_in (region_len+2)*16 words behind it, n_u64 larger by 2*(region_len+2)*16.  Rows 0 and 1 of the
  * pair stay zero on the device (pssbam_engine_finish_site_context fills them from fwd | rev), so the block still sums
- * across engines as one u64 array. */
+ * across engines as one u64 array.
+ * With an end condition (pssbam_engine_set_end_condition; a PSSBAM_TALLY_PSS engine without planes, histogram or site
+ * context) the conditional pair and its read counters are appended: [fwd | rev | stats | fwd_c | rev_c | reads[4]],
+ * fwd_c at 2*(region_len+2)*16 + PSSBAM_ST_N (the old n_u64), rev_c (region_len+2)*16 words behind it, reads[0..3]
+ * behind that, n_u64 larger by 2*(region_len+2)*16 + 4.  Every word is a plain count, so the block still sums across
+ * engines as one u64 array and the PSSBAM_ST_* slots stay where they are. */
 int pssbam_engine_counters_device(pssbam_engine *e, void **d_counters, size_t *n_u64);
 
 /* Makes the engine accumulate into caller-owned device memory (n_u64 words, as reported

@@ -44,6 +44,7 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_contig_sets", "pssbam_engine_finish_kmer_groups", "pssbam_engine_set_min_base_quality",
     "pssbam_engine_set_regions", "pssbam_engine_set_length_histogram", "pssbam_engine_finish_length_histogram",
     "pssbam_engine_set_site_context", "pssbam_engine_finish_site_context",
+    "pssbam_engine_set_end_condition", "pssbam_engine_finish_end_condition",
 ]
 MAX_READ_GROUPS = 4096
 MAX_LENGTH_BINS = 64
@@ -53,6 +54,8 @@ MAX_HIST_LENGTH = 65535
 MAX_REGIONS = 1 << 26
 SITE_NONE, SITE_CPG = 0, 1
 SITE_MODES = {None: SITE_NONE, "none": SITE_NONE, "cpg": SITE_CPG}
+MAX_END_DEPTH = 8
+END_PRESETS = {"ss": (13, 13), "ds": (13, 2)}   # (cell5, cell3): C->T at both ends / C->T at the 5' end, G->A at the 3' end
 EBUSY = -7
 
 
@@ -122,6 +125,8 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_finish_length_histogram.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_site_context.argtypes = [C.c_void_p, C.c_int32]
     L.pssbam_engine_finish_site_context.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pssbam_engine_set_end_condition.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+    L.pssbam_engine_finish_end_condition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_regions.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_counters_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.pssbam_engine_bind_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -199,13 +204,15 @@ class Engine:
     see set_length_histogram; 0 = off.
     `site_context` = "cpg" (pss-bam -X cpg): a second pair of tables over the positions whose reference site is in CpG
     context, see set_site_context; None = off.
+    `end_condition` = (depth, cell5, cell3) (pss-bam -E): a second pair of tables over the unpaired reads whose other end
+    carries the given cell within its first `depth` positions, see set_end_condition; None = off.
     With `kmer` alone (no `pss`) the three split the k-mer tables instead (fragkon -G / -S / -C): every plane is a
     k5 / k3 pair, and the length bins go by the SEQ length and kmer's min_read_len / max_read_len."""
 
     def __init__(self, pss: dict | None = None, kmer: dict | None = None, read_group: str | None = None,
                  kernel: int = KERNEL_AUTO, device: int = -1, read_groups: list[str] | None = None,
                  length_bins: list[int] | None = None, contig_sets=None, min_base_qual: int = 0,
-                 length_hist: int = 0, site_context: str | None = None):
+                 length_hist: int = 0, site_context: str | None = None, end_condition: tuple[int, int, int] | None = None):
         L = hip_lib()
         cfg = _Config()
         cfg.abi_version = 1
@@ -248,6 +255,9 @@ class Engine:
             self.set_length_histogram(length_hist)
         if site_context is not None:
             self.set_site_context(site_context)
+        self._end_condition = (0, 0, 0)
+        if end_condition is not None:
+            self.set_end_condition(*end_condition)
         if read_groups is not None:
             self.set_read_groups(read_groups)
         if length_bins is not None:
@@ -313,6 +323,31 @@ class Engine:
         rev = np.zeros_like(fwd)
         _chk(self._L.pssbam_engine_finish_site_context(self._h, fwd.ctypes.data, rev.ctypes.data))
         return fwd, rev
+
+    def set_end_condition(self, depth: int, cell5: int = 13, cell3: int = 13):
+        """pss-bam -E: keeps a second pair of tables, COND, and four read counters.  An unpaired read is 5'-marked when one
+        of the first `depth` (1..MAX_END_DEPTH, <= region_len) positions of its 5' end carries cell `cell5`
+        (4 * read base + reference base, A C G T = 0..3, in read orientation; 13 = C->T, 2 = G->A) and 3'-marked likewise
+        with `cell3` at its 3' end; COND's forward table holds the 3'-marked reads, its reverse table the 5'-marked ones.
+        depth 0 switches it off.  Needs region_len <= 30; not with kmer, read groups, length bins, contig sets, the length
+        histogram or site context.  Before the first tally (after feed_open: before set_references) and before
+        bind_counters: the counter block grows by 2 * (region_len + 2) * 16 + 4 words.  Survives reset."""
+        _chk(self._L.pssbam_engine_set_end_condition(self._h, int(depth), int(cell5), int(cell3)))
+        self._end_condition = (int(depth), int(cell5), int(cell3)) if depth else (0, 0, 0)
+
+    @property
+    def end_condition(self) -> tuple[int, int, int] | None:
+        """the end condition in force, (depth, cell5, cell3), or None"""
+        return self._end_condition if self._end_condition[0] else None
+
+    def finish_end_condition(self) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(fwd_c, rev_c, reads): the conditional tables, (region_len + 2, 16) u64 each, and reads[4] = unpaired reads
+        added to the tables, the 5'-marked, the 3'-marked and the both-marked ones among them (drains like finish)"""
+        fwd = np.zeros((self.region_len + 2, 16), dtype=np.uint64)
+        rev = np.zeros_like(fwd)
+        reads = np.zeros(4, dtype=np.uint64)
+        _chk(self._L.pssbam_engine_finish_end_condition(self._h, fwd.ctypes.data, rev.ctypes.data, reads.ctypes.data))
+        return fwd, rev, reads
 
     def set_regions(self, names, name_of, starts, ends):
         """pss-bam -T / fragkon -T: only records whose alignment overlaps one of the intervals are tallied -- the tables
@@ -592,6 +627,9 @@ class Engine:
         if self._site_context:   # site context (never together with planes or the histogram): fwd_in | rev_in behind the stats
             lay["site_fwd"], lay["site_rev"] = base, base + rows * 16
             lay["n_u64"] = base + 2 * rows * 16
+        if self._end_condition[0]:   # the end condition (never together with any of the above): fwd_c | rev_c | reads[4]
+            lay["end_fwd"], lay["end_rev"], lay["end_reads"] = base, base + rows * 16, base + 2 * rows * 16
+            lay["n_u64"] = base + 2 * rows * 16 + 4
         return lay
 
     def genome_kmer_count(self, klen: int) -> np.ndarray:

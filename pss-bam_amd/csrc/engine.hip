@@ -218,6 +218,8 @@ struct pssbam_engine {
     uint32_t hist_max = 0, off_hist = 0;
     // -X (pssbam_engine_set_site_context): fwd_in | rev_in, rows * 16 words each, at off_site = the end of the block as it is without them
     uint32_t site_mode = 0, off_site = 0;
+    // -E (pssbam_engine_set_end_condition): fwd_c | rev_c | reads[4], rows * 16 words per table, at off_end = the end of the block as it is without them
+    uint32_t end_depth = 0, end_cell5 = 0, end_cell3 = 0, off_end = 0;
     int env_hist_lds_bins = -1;   // PSSBAM_HIST_LDS_BINS: at most this many bins of each array in LDS (tests: the global-atomic path with short reads)
     // -T (pssbam_engine_set_regions): contig name -> its merged intervals, kept on the host; the per-refID device table is
     // packed from it whenever the reference list or the map changes (pack_regions)
@@ -910,21 +912,24 @@ static int with_planes(PlaneSel sel, F f) {
 static int no_kernel() { return fail(PSSBAM_EINVAL, "no tally kernel is built for this combination of options"); }
 
 // One row pass of tally_tiled and its reduce_partials: the instantiation for the launch's tallies, the pass (LATER: rows
-// 32.. of a large -r) and its -Q, -T, -H and -X state.  `exists` is the list of instantiations: the k-mer tally (alone or
-// beside the substitution tables) and -H belong to pass 0, -Q -H -X to the substitution tables, -X excludes the other two.
-// (SITE: the larger scratch slot of the -X instantiations and the reduce that walks it)
+// 32.. of a large -r) and its -Q, -T, -H, -X and -E state.  `exists` is the list of instantiations: the k-mer tally (alone or
+// beside the substitution tables) and -H belong to pass 0, -Q -H -X to the substitution tables, -X excludes the other two;
+// -E is the substitution tally of pass 0 alone, with or without -Q and -T.
+// (SITE, END: the larger scratch slot of the -X / -E instantiations and the reduce that walks it)
 static int launch_tiled(pssbam_engine *e, TallyParams &P, bool do_pss, bool do_kmer, bool kmer_lds, bool later, bool maskq, bool regions,
-                        bool hist, bool site, uint32_t lds, uint32_t n_tiles) {
-    return with_flags([&](auto DO_PSS, auto DO_KMER, auto LDS_KMER, auto LATER, auto MASKQ, auto REGIONS, auto HIST, auto SITE) -> int {
+                        bool hist, bool site, bool endc, uint32_t lds, uint32_t n_tiles) {
+    return with_flags([&](auto DO_PSS, auto DO_KMER, auto LDS_KMER, auto LATER, auto MASKQ, auto REGIONS, auto HIST, auto SITE, auto END) -> int {
         constexpr bool exists = (DO_KMER() || !LDS_KMER()) &&
                                 (LATER() ? DO_PSS() && !DO_KMER() && !HIST()
-                                         : (DO_PSS() || DO_KMER()) && (DO_PSS() || !(MASKQ() || HIST() || SITE())) && !(SITE() && (DO_KMER() || HIST())));
+                                         : (DO_PSS() || DO_KMER()) && (DO_PSS() || !(MASKQ() || HIST() || SITE())) && !(SITE() && (DO_KMER() || HIST()))) &&
+                                (!END() || (DO_PSS() && !DO_KMER() && !LATER() && !HIST() && !SITE()));
         if constexpr (exists)
-            return launch_with_reduce(e, tally_tiled<DO_PSS(), DO_KMER(), LDS_KMER(), LATER(), MASKQ(), REGIONS(), HIST(), SITE()>, reduce_partials<SITE()>,
-                                      SITE() ? SITE_SCRATCH_WORDS : SCRATCH_WORDS, lds, n_tiles, P, std::tuple<>(), (uint32_t)LDS_KMER());
+            return launch_with_reduce(e, tally_tiled<DO_PSS(), DO_KMER(), LDS_KMER(), LATER(), MASKQ(), REGIONS(), HIST(), SITE(), END()>,
+                                      reduce_partials<SITE(), END()>, SITE() ? SITE_SCRATCH_WORDS : END() ? END_SCRATCH_WORDS : SCRATCH_WORDS, lds, n_tiles, P,
+                                      std::tuple<>(), (uint32_t)LDS_KMER());
         else
             return no_kernel();
-    }, do_pss, do_kmer, kmer_lds, later, maskq, regions, hist, site);
+    }, do_pss, do_kmer, kmer_lds, later, maskq, regions, hist, site, endc);
 }
 
 // How many 16-byte pieces of a record the tiled kernel must stage so that everything the path
@@ -1036,6 +1041,13 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
     }
     const bool site = do_pss && e->site_mode != PSSBAM_SITE_NONE;   // -X: the SITE instantiations; without it the engine launches what it always did
     if (site) P.off_site = e->off_site;
+    const bool endc = do_pss && e->end_depth > 0;   // -E: the END instantiations; without it the engine launches what it always did
+    if (endc) {
+        P.end_depth = e->end_depth;
+        P.end_cell5 = e->end_cell5;
+        P.end_cell3 = e->end_cell3;
+        P.off_end = e->off_end;
+    }
     if (regions) {
         P.region_info = e->d_region_info;
         P.region_grid = e->d_region_grid;
@@ -1167,9 +1179,9 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                     });
                 }
             }
-        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions && !hist && !site) {
+        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions && !hist && !site && !endc) {
             // -r N <= 16 (2 context rows + 16 positions): the short-window variant, one pass (it stages prefixes only
-            // and has no QUAL path: -R and -Q go to tally_tiled; so do -T, -H and -X, whose arms only tally_tiled carries)
+            // and has no QUAL path: -R and -Q go to tally_tiled; so do -T, -H, -X and -E, whose arms only tally_tiled carries)
             if (!do_kmer && getenv("PSSBAM_COMPACT_DECODE_TWICE"))   // diagnostics: what the shared header decode costs
                 rc = launch_with_reduce(e, tally_compact_decode_twice, reduce_partials<false>, SCRATCH_WORDS, lds, n_tiles, P, std::tuple<>(), 0u);
             else
@@ -1190,10 +1202,11 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                 if (e->env_hist_lds_bins >= 0) P.hist_lds_bins = std::min(P.hist_lds_bins, (uint32_t)e->env_hist_lds_bins);
                 lds0 += hist_lds_bytes(P.hist_lds_bins);
             }
+            if (endc) lds0 += end_lds_bytes(e->rows);   // -E (one pass: -r <= 30): the conditional tables and reads[4] behind the staging buffer
             for (uint32_t pass = 0; pass < n_passes && rc == PSSBAM_OK; pass++) {
                 P.row_base = pass * TILED_ROWS;
-                rc = pass == 0 ? launch_tiled(e, P, do_pss, do_kmer, kmer_lds, false, maskq, regions, hist, site, lds0, n_tiles)
-                               : launch_tiled(e, P, true, false, false, true, maskq, regions, false, site, lds, n_tiles);
+                rc = pass == 0 ? launch_tiled(e, P, do_pss, do_kmer, kmer_lds, false, maskq, regions, hist, site, endc, lds0, n_tiles)
+                               : launch_tiled(e, P, true, false, false, true, maskq, regions, false, site, false, lds, n_tiles);
             }
         }
         if (rc != PSSBAM_OK) return rc;
@@ -1451,6 +1464,7 @@ static int grow_counters(pssbam_engine *e, uint64_t n_counters) {
 static int set_planes(pssbam_engine *e, PlaneSel sel, uint32_t n_planes, const char *what) {
     if (e->hist_max) return fail(PSSBAM_EINVAL, "%s and the length histogram exclude each other", what);
     if (e->site_mode) return fail(PSSBAM_EINVAL, "%s and site context exclude each other", what);
+    if (e->end_depth) return fail(PSSBAM_EINVAL, "%s and the end condition exclude each other", what);
     const bool kmer = e->cfg.tally_mask == PSSBAM_TALLY_KMER;
     if (e->cfg.tally_mask != PSSBAM_TALLY_PSS && !kmer)
         return fail(PSSBAM_EINVAL, "%s split the substitution tables or the k-mer tables, not both (PSSBAM_TALLY_PSS | PSSBAM_TALLY_KMER)", what);
@@ -1542,6 +1556,7 @@ extern "C" int pssbam_engine_set_length_histogram(pssbam_engine *e, int32_t max_
         return fail(PSSBAM_EINVAL, "the length histogram counts the reads added to the substitution tables: the engine needs PSSBAM_TALLY_PSS");
     if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the length histogram and read groups / length bins / contig sets exclude each other");
     if (e->site_mode) return fail(PSSBAM_EINVAL, "the length histogram and site context exclude each other");
+    if (e->end_depth) return fail(PSSBAM_EINVAL, "the length histogram and the end condition exclude each other");
     if (const int rc = check_may_resize(e, "the length histogram")) return rc;
     if ((uint32_t)max_len == e->hist_max) return PSSBAM_OK;
     HIP_TRY(hipSetDevice(e->device));
@@ -1572,6 +1587,7 @@ extern "C" int pssbam_engine_set_site_context(pssbam_engine *e, int32_t mode) {
         return fail(PSSBAM_EINVAL, "site context splits the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
     if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "site context and read groups / length bins / contig sets exclude each other");
     if (e->hist_max) return fail(PSSBAM_EINVAL, "site context and the length histogram exclude each other");
+    if (e->end_depth) return fail(PSSBAM_EINVAL, "site context and the end condition exclude each other");
     if (const int rc = check_may_resize(e, "the site context")) return rc;
     if ((uint32_t)mode == e->site_mode) return PSSBAM_OK;
     HIP_TRY(hipSetDevice(e->device));
@@ -1597,6 +1613,49 @@ extern "C" int pssbam_engine_finish_site_context(pssbam_engine *e, unsigned long
         if (fwd_in) fwd_in[i] = (unsigned long)(i < 32 ? h[i] : h[e->off_site + i]);
         if (rev_in) rev_in[i] = (unsigned long)(i < 32 ? h[e->off_rev + i] : h[e->off_site + tab + i]);
     }
+    return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_set_end_condition(pssbam_engine *e, int32_t depth, int32_t cell5, int32_t cell3) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (depth < 0 || depth > PSSBAM_MAX_END_DEPTH) return fail(PSSBAM_EINVAL, "end condition depth %d outside 0..%d", depth, PSSBAM_MAX_END_DEPTH);
+    if (depth && (cell5 < 0 || cell5 > 15 || cell3 < 0 || cell3 > 15)) return fail(PSSBAM_EINVAL, "end condition cells %d, %d outside 0..15", cell5, cell3);
+    if (e->cfg.tally_mask != PSSBAM_TALLY_PSS)
+        return fail(PSSBAM_EINVAL, "the end condition splits the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
+    if (depth > e->cfg.pss.region_len) return fail(PSSBAM_EINVAL, "end condition depth %d beyond the region length %d", depth, e->cfg.pss.region_len);
+    if (depth && e->cfg.pss.region_len > 30)
+        return fail(PSSBAM_EINVAL, "the end condition needs a region length of at most 30 (one 32-row pass holds both ends' marks), not %d", e->cfg.pss.region_len);
+    if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the end condition and read groups / length bins / contig sets exclude each other");
+    if (e->hist_max) return fail(PSSBAM_EINVAL, "the end condition and the length histogram exclude each other");
+    if (e->site_mode) return fail(PSSBAM_EINVAL, "the end condition and site context exclude each other");
+    if (const int rc = check_may_resize(e, "the end condition")) return rc;
+    if ((uint32_t)depth != e->end_depth) {
+        HIP_TRY(hipSetDevice(e->device));
+        // the block grows (or shrinks back) behind everything it holds without the pair and its read counters
+        const uint64_t n_counters = (uint64_t)e->off_groups + (depth ? 2ull * e->rows * 16ull + 4ull : 0ull);
+        if (n_counters > 0xFFFFFFFFull) return fail(PSSBAM_EINVAL, "the counter block would pass 2^32 words");
+        if (const int rc = grow_counters(e, n_counters)) return rc;
+    }
+    e->end_depth = (uint32_t)depth;
+    e->end_cell5 = depth ? (uint32_t)cell5 : 0u;
+    e->end_cell3 = depth ? (uint32_t)cell3 : 0u;
+    e->off_end = depth ? e->off_groups : 0u;
+    return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_finish_end_condition(pssbam_engine *e, unsigned long *fwd_c, unsigned long *rev_c, uint64_t reads[4]) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (!e->end_depth) return fail(PSSBAM_EINVAL, "pssbam_engine_set_end_condition has not been called");
+    const int rc = pssbam_engine_sync(e);
+    if (rc) return rc;
+    const size_t tab = (size_t)e->rows * 16;
+    std::vector<unsigned long long> h(2 * tab + 4);
+    HIP_TRY(hipMemcpy(h.data(), e->d_counters + e->off_end, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < tab; i++) {
+        if (fwd_c) fwd_c[i] = (unsigned long)h[i];
+        if (rev_c) rev_c[i] = (unsigned long)h[tab + i];
+    }
+    if (reads) for (int k = 0; k < 4; k++) reads[k] = h[2 * tab + k];
     return PSSBAM_OK;
 }
 

@@ -92,6 +92,11 @@ struct TallyParams {
     // off_site: the adds of the interior positions whose reference position is in CpG context.  Read by the SITE
     // instantiations of tally_tiled, their reduce_partials and tally_simple.
     uint32_t off_site;
+    // -E: the end condition (end_depth = 0: off).  [fwd_c | rev_c | reads[4]] in the counter block at off_end, (N + 2) * 16 u64
+    // counters per table: the forward contribution of the unpaired records whose 3' end carries cell end_cell3 within
+    // its first end_depth positions, the reverse contribution of those whose 5' end carries end_cell5.  Read by the END
+    // instantiations of tally_tiled, their reduce_partials and tally_simple.
+    uint32_t end_depth, end_cell5, end_cell3, off_end;
 };
 
 // stats slots, must match include/pssbam_hip.h.  The kernels count EVENTS only: every launch

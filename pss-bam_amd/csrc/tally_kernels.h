@@ -76,6 +76,11 @@ constexpr uint32_t SCRATCH_KMER = 1024, SCRATCH_DELTA = 1536, SCRATCH_WORDS = 15
 // an in-context cell always has reference base C or G (in table coordinates too: complementing swaps the two)
 constexpr uint32_t SITE_WORDS = 16 * 32, SITE_SCRATCH_WORDS = SCRATCH_WORDS + SITE_WORDS;
 constexpr uint32_t CODE_SITE = 64;     // sheet bit "the reference position is in context" (SITE instantiations only)
+// -E (END): the conditional tables of a workgroup live in dynamic LDS as [(cell << 1) | table][N + 2 rows] words with the four
+// read counters behind them; in a scratch slot they follow the plain words as [(cell << 1) | table][32 rows]
+constexpr uint32_t END_SCRATCH_WORDS = SCRATCH_WORDS + 32 * 32;
+constexpr uint32_t CODE_END = 64;      // sheet bit "the read's other end is marked" (END instantiations only)
+__host__ __device__ inline uint32_t end_lds_bytes(uint32_t rows) { return (32u * rows + 4u) * 4u; }
 constexpr uint32_t REF_LDS_ENTRIES = 64;   // BAM references whose contig info is cached in LDS (+1 for "*")
 
 // ---------------------------------------------------------------------------------------
@@ -177,6 +182,54 @@ template <bool MASKQ = false, class Src, class Tab>
 __device__ __forceinline__ void tally_pss_record(const TallyParams &P, const Tab &tab, const Src &src,
                                                  const RecHdr &h, const Plan &pl) {
     tally_pss_record<MASKQ, false>(P, tab, NoSite{}, src, h, pl);
+}
+
+// -E: is one end of a read marked -- does one of its first `depth` positions carry the cell `want` (table coordinates,
+// the cell tally_end would add at row 2 + i)?  left / comp as in tally_end; a base masked by -Q has no cell.
+template <bool MASKQ, class Src>
+__device__ bool end_marked(const Src &src, const RecHdr &h, const uint8_t *G, int64_t s, uint32_t L, uint32_t depth, bool left,
+                           bool comp, uint32_t min_bq, uint32_t want) {
+    for (uint32_t i = 0; i < depth; i++) {
+        const uint32_t ri = left ? i : L - 1u - i;
+        if (MASKQ && ri < h.l_seq && src.u8(h.qual_off + ri) < min_bq) continue;
+        const uint32_t rd = nib_code(read_nibble(src, h, ri));
+        const uint32_t rf = ref_code(G[s + (int64_t)ri]);
+        if (rd < 4u && rf < 4u && (comp ? 15u - (4u * rd + rf) : 4u * rd + rf) == want) return true;
+    }
+    return false;
+}
+struct LdsEndTable {  // the tiled kernel's [(cell << 1) | table][rows] conditional tables, reads[4] behind them
+    uint32_t *t;
+    uint32_t rows;
+    __device__ __forceinline__ void add(uint32_t table, uint32_t row, uint32_t cell) const {
+        atomicAdd(&t[((cell << 1) | table) * rows + row], 1u);
+    }
+    __device__ __forceinline__ void count(uint32_t k) const { atomicAdd(&t[32u * rows + k], 1u); }
+};
+struct GlobalEndTable {  // straight into [fwd_c | rev_c | reads[4]] of the counter block
+    unsigned long long *c;
+    uint32_t off_rev;
+    __device__ __forceinline__ void add(uint32_t table, uint32_t row, uint32_t cell) const {
+        atomicAdd(&c[(table ? off_rev : 0u) + row * 16u + cell], 1ull);
+    }
+    __device__ __forceinline__ void count(uint32_t k) const { atomicAdd(&c[2u * off_rev + k], 1ull); }
+};
+// -E, lane-per-read form: an unpaired record that was added to the tables is counted in reads[], its forward contribution
+// is added to `cond` a second time when its 3' end is marked, its reverse contribution when its 5' end is (the forward
+// table is fed from the 5' end: the left alignment end of a forward read, the complemented right end of a reverse read)
+template <bool MASKQ, class Src, class Cond>
+__device__ __forceinline__ void tally_end_condition(const TallyParams &P, const Cond &cond, const Src &src, const RecHdr &h, const Plan &pl) {
+    if ((pl.flag & FL_PAIRED) || !(pl.pss_fwd && pl.pss_rev)) return;
+    const uint32_t min_bq = MASKQ ? P.min_bq : 0u;
+    const uint8_t *G = P.genome + pl.gbase;
+    const bool m5 = end_marked<MASKQ>(src, h, G, pl.s, pl.L, P.end_depth, !pl.rev, pl.rev, min_bq, P.end_cell5);
+    const bool m3 = end_marked<MASKQ>(src, h, G, pl.s, pl.L, P.end_depth, pl.rev, pl.rev, min_bq, P.end_cell3);
+    cond.count(0u);
+    if (m5) cond.count(1u);
+    if (m3) cond.count(2u);
+    if (m5 && m3) cond.count(3u);
+    if (m3) tally_end<MASKQ, false>(cond, NoSite{}, 0u, src, h, G, pl.s, pl.L, P.N, !pl.rev, pl.rev, min_bq);
+    if (m5) tally_end<MASKQ, false>(cond, NoSite{}, 1u, src, h, G, pl.s, pl.L, P.N, pl.rev, pl.rev, min_bq);
 }
 
 // one k-mer add (5' when which == 0, 3' when which == 1); false = non-ACGT in the window
@@ -284,6 +337,8 @@ __global__ void __launch_bounds__(256) tally_simple(const TallyParams P) {
                 else tally_pss_record<true, true>(P, GlobalTable{P.counters, P.off_rev}, site, src, h, pl);
             } else if (LDS_TABLE) tally_pss_record<true>(P, LdsTableRowMajor{dyn_lds, rows}, src, h, pl);
             else tally_pss_record<true>(P, GlobalTable{P.counters, P.off_rev}, src, h, pl);
+            // -E: the conditional pair and reads[] take their adds straight in the counter block
+            if (P.end_depth) tally_end_condition<true>(P, GlobalEndTable{P.counters + P.off_end, rows * 16u}, src, h, pl);
             // -H: straight into the counter block (hist_lds_bins is 0 in this kernel's launches)
             if (P.hist_max) hist_add(P, nullptr, hist_bin(P, pl.L), pl.pss_fwd, pl.pss_rev, 1u);
         }
@@ -372,10 +427,12 @@ __device__ __forceinline__ void stage_tile_dma(const uint8_t *recs, uint64_t rec
 // nothing.  It reads the kernel arguments through a pointer to the kernarg segment (taken in
 // the kernel): a reference to the kernel's by-value copy would force that whole struct into
 // scratch memory.
-template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool MASKQ = false, bool REGIONS = false, bool HIST = false, bool SITE = false>
+template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool MASKQ = false, bool REGIONS = false, bool HIST = false, bool SITE = false,
+          bool END = false>
 __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyParams *kernarg, uint32_t o0,
                                                                     uint32_t o1, uint32_t *table, uint32_t *lds_kmer,
-                                                                    uint32_t *hist_lds = nullptr, uint32_t *site_lds = nullptr) {
+                                                                    uint32_t *hist_lds = nullptr, uint32_t *site_lds = nullptr,
+                                                                    uint32_t *end_lds = nullptr) {
     const TallyParams &P = *kernarg;
     GlobalBytes gsrc{P.recs + o0};
     const RecHdr gh = decode_hdr(gsrc, o1 - o0);
@@ -387,6 +444,7 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyP
     if constexpr (HIST) {   // (the HIST instantiation is a pass-0 one: counted once)
         if (gpl.pss_fwd || gpl.pss_rev) hist_add(P, hist_lds, hist_bin(P, gpl.L), gpl.pss_fwd, gpl.pss_rev, 1u);
     }
+    if constexpr (END) tally_end_condition<MASKQ>(P, LdsEndTable{end_lds, (uint32_t)P.N + 2u}, gsrc, gh, gpl);   // (a pass-0 one as well)
     bool kfail = false;
     if (DO_KMER && (gpl.fk5 || gpl.fk3)) kfail = tally_kmer_record<LDS_KMER>(P, gpl, lds_kmer);
     return record_events(DO_PSS, DO_KMER, gpl, kfail);
@@ -516,8 +574,16 @@ __device__ __forceinline__ uint32_t base_quality_mask(uint32_t x, uint32_t q4) {
 // comes with the window gather in CODES-A: the one behind it lies in the fifth gathered dword already, the one in
 // front of it is one more dword load of a line the gather touches anyway.  The instantiations without SITE contain
 // none of it.
+//
+// END (-E, P.end_depth > 0; pass 0 of a one-pass launch, one plane, substitution tables only): when CODES-B has formed a
+// lane's codes -- table coordinates, -Q and the blanking of absent bases applied -- the lane compares rows 2 .. 2 + depth - 1
+// of its own end with the wanted code ((cell5 << 1) on the lane that feeds the forward table, (cell3 << 1) | 1 on the one that
+// feeds the reverse table), all of them at once on the four code words that hold them.  The two lanes of a read's pair
+// exchange the result, and a lane whose PARTNER is marked sets CODE_END in all its sheet bytes: COLUMNS adds a real code
+// that carries it a second time, into the conditional tables `end_lds` behind the staging buffer ((N + 2) rows per code,
+// end_lds_bytes).  The left-end lanes count reads[4] with a ballot each.  The instantiations without END contain none of it.
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS, PlaneSel PLANES = PLANES_NONE, bool MASKQ = false,
-          bool REGIONS = false, bool HIST = false, bool SITE = false>
+          bool REGIONS = false, bool HIST = false, bool SITE = false, bool END = false>
 __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const TallyParams *kernarg,
                                                  uint8_t *__restrict__ stage, uint8_t *__restrict__ sheet,
                                                  uint32_t *__restrict__ table,
@@ -525,8 +591,10 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
                                                  uint32_t *__restrict__ lds_kmer,
                                                  int32_t *__restrict__ lds_delta, uint4 *__restrict__ refs_lds,
                                                  const PlaneParams *gk = nullptr, uint32_t *__restrict__ grp_lds = nullptr,
-                                                 uint32_t *__restrict__ hist_lds = nullptr, uint32_t *__restrict__ site_lds = nullptr) {
+                                                 uint32_t *__restrict__ hist_lds = nullptr, uint32_t *__restrict__ site_lds = nullptr,
+                                                 uint32_t *__restrict__ end_lds = nullptr) {
     constexpr bool GROUPED = PLANES != PLANES_NONE;   // one table plane per read group / length bin
+    static_assert(!END || (DO_PSS && !DO_KMER && !LATER_PASS && PLANES == PLANES_NONE && !HIST && !SITE), "the end condition belongs to pass 0 of the one-plane substitution tally without the length histogram and site context");
     static_assert(!SITE || (DO_PSS && !DO_KMER && PLANES == PLANES_NONE && !HIST), "site context belongs to the one-plane substitution tally without the length histogram");
     static_assert(!HIST || (DO_PSS && !LATER_PASS && PLANES == PLANES_NONE), "the length histogram belongs to pass 0 of the one-plane substitution tally");
     constexpr bool KPLANES = GROUPED && DO_KMER;      // ... of k-mer bins (tally_tiled_kmer_planes: no sheet, no table)
@@ -561,6 +629,8 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         for (uint32_t i = tid; i < 2u * P.hist_lds_bins; i += TILED_THREADS) hist_lds[i] = 0u;
     if constexpr (SITE)
         for (uint32_t i = tid; i < SITE_WORDS; i += TILED_THREADS) site_lds[i] = 0u;
+    if constexpr (END)
+        for (uint32_t i = tid; i < 32u * n_pos + 4u; i += TILED_THREADS) end_lds[i] = 0u;
     // contig info of the first BAM references (all of them for a human-sized header) + the "*" entry
     const uint32_t n_ref_cached = min((uint32_t)P.n_ref, REF_LDS_ENTRIES);
     if (tid < n_ref_cached) refs_lds[tid] = P.ref_info[tid];
@@ -737,7 +807,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         if (in_tile && !in_stage && e == 0u) {
             if constexpr (KPLANES) ev_over = tally_overflow_record_kmer_planes<PLANES, LDS_KMER, REGIONS>(kernarg, gk, o0, o1, lds_kmer);
             else if constexpr (GROUPED) ev_over = tally_overflow_record_planes<PLANES, MASKQ, REGIONS>(kernarg, gk, o0, o1, table);
-            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS, HIST, SITE>(kernarg, o0, o1, table, lds_kmer, hist_lds, site_lds);
+            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS, HIST, SITE, END>(kernarg, o0, o1, table, lds_kmer, hist_lds, site_lds, end_lds);
             if (pass0) atomicAdd(&lds_delta[ST_SLOW_PATH], 1);
         }
         // First use of the gathered registers happens HERE, before the next tile's DMA is issued:
@@ -797,6 +867,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
             for (int k = 0; k < 8; k++) code_w[k] = CODE_NONE * 0x01010101u;
             // this lane's end feeds: left -> fwd table on forward reads, rev table on reverse reads
             const uint32_t tsel = e ^ (pl.rev ? 1u : 0u);
+            bool end_hit = false;   // END: this lane's end is marked
             if (cand && (tsel ? pl.pss_rev : pl.pss_fwd) && !(ablate & 2u)) {
                 // Four window positions per VALU instruction, no memory lookups: v_perm_b32 with the
                 // DATA as selector is an 8-entry byte table (selectors 0-7 pick a pool byte, 8-11
@@ -909,6 +980,47 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
                         code_w[2 * m + 1] |= (inO << 5) & keep;
                     }
                 }
+                if constexpr (END) {
+                    // Row 2 + i is window position 2 + i of a left end and 29 - i of a right end; position p is byte
+                    // (p & 7) >> 1 of code word 2 * (p >> 3) + (p & 1).  So rows 2, 4, 6 / 3, 5, 7 / 8 / 9 are bytes 1-3 of
+                    // words 0 / 1 and byte 0 of words 2 / 3 on the left, and the byte-reversed words 7 / 6 / 5 / 4 hold them
+                    // at the same places on the right.  A byte equals the wanted code when the XOR is zero; every byte is
+                    // below 0x40, so + 0x7F sets bit 7 exactly in the non-zero ones without a carry between bytes.
+                    const uint32_t d = P.end_depth;
+                    const uint32_t want4 = (((tsel ? P.end_cell3 : P.end_cell5) << 1) | tsel) * 0x01010101u;
+                    const uint32_t rows_m[4] = {(d > 0u ? 0x00008000u : 0u) | (d > 2u ? 0x00800000u : 0u) | (d > 4u ? 0x80000000u : 0u),
+                                                (d > 1u ? 0x00008000u : 0u) | (d > 3u ? 0x00800000u : 0u) | (d > 5u ? 0x80000000u : 0u),
+                                                d > 6u ? 0x00000080u : 0u, d > 7u ? 0x00000080u : 0u};
+                    uint32_t hit = 0u;
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const uint32_t x = e ? __builtin_bswap32(code_w[7 - k]) : code_w[k];
+                        hit |= ~((x ^ want4) + 0x7F7F7F7Fu) & rows_m[k];
+                    }
+                    end_hit = hit != 0u;
+                }
+            }
+            if constexpr (END) {
+                // every lane takes part in the exchange; paired records never reach the conditional tables, and a lane that
+                // adds nothing holds "no count" codes, which COLUMNS leaves out whatever the flag says
+                const bool other_hit = __shfl_xor((int)end_hit, 1) != 0;
+                const bool unpaired = !(pl.flag & FL_PAIRED);
+                if (unpaired && other_hit) {
+#pragma unroll
+                    for (int k = 0; k < 8; k++) code_w[k] |= CODE_END * 0x01010101u;
+                }
+                // reads[4], from the left-end lane (an unpaired read is added to both tables or to none); the lane that
+                // feeds the forward table holds the 5' mark.  A record on the out-of-line path counted itself there.
+                const bool on = e == 0u && in_stage && unpaired && pl.pss_fwd;
+                const bool m5 = tsel ? other_hit : end_hit, m3 = tsel ? end_hit : other_hit;
+                const unsigned long long b0 = __ballot(on), b1 = __ballot(on && m5), b2 = __ballot(on && m3), b3 = __ballot(on && m5 && m3);
+                if (lane == 0u && b0) {
+                    uint32_t *reads = end_lds + 32u * n_pos;
+                    atomicAdd(&reads[0], (uint32_t)__popcll(b0));
+                    if (b1) atomicAdd(&reads[1], (uint32_t)__popcll(b1));
+                    if (b2) atomicAdd(&reads[2], (uint32_t)__popcll(b2));
+                    if (b3) atomicAdd(&reads[3], (uint32_t)__popcll(b3));
+                }
             }
             bool kmer_ok = true;
             if (kmer_try) {
@@ -993,6 +1105,21 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
                     for (int u = 0; u < 8; u++) add(c[u]);
                 }
                 for (; j < j1; j++) add(sheet[j * 64u + lane]);
+            } else if (END && row < n_live) {
+                // a real code (< 32) with CODE_END set counts a second time, in the conditional tables
+                auto add = [&](uint32_t c) {
+                    atomicAdd(&table[((c & 63u) << 5) + row], 1u);
+                    if ((c & (CODE_END | CODE_NONE)) == CODE_END) atomicAdd(&end_lds[(c & 31u) * n_pos + row], 1u);
+                };
+                uint32_t j = j0;
+                for (; j + 8u <= j1; j += 8u) {
+                    uint32_t c[8];
+#pragma unroll
+                    for (int u = 0; u < 8; u++) c[u] = sheet[(j + u) * 64u + lane];
+#pragma unroll
+                    for (int u = 0; u < 8; u++) add(c[u]);
+                }
+                for (; j < j1; j++) add(sheet[j * 64u + lane]);
             } else if (row < n_live) {  // (lanes of dead rows would only ever see CODE_NONE)
                 uint32_t j = j0;
                 for (; j + 8u <= j1; j += 8u) {
@@ -1023,9 +1150,17 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         for (uint32_t i = tid; i < n_words; i += TILED_THREADS) mine[GROUP_SCRATCH_DELTA + i] = table[i];
         if (tid < 16u) mine[tid] = tid < (uint32_t)ST_USED ? (uint32_t)lds_delta[tid] : 0u;
     } else {
-    uint32_t *mine = P.scratch + (size_t)blockIdx.x * (SITE ? SITE_SCRATCH_WORDS : SCRATCH_WORDS);
+    uint32_t *mine = P.scratch + (size_t)blockIdx.x * (SITE ? SITE_SCRATCH_WORDS : END ? END_SCRATCH_WORDS : SCRATCH_WORDS);
     if constexpr (SITE)   // [table | k-mer bins | deltas | in-context table]
         for (uint32_t i = tid; i < SITE_WORDS; i += TILED_THREADS) mine[SCRATCH_WORDS + i] = site_lds[i];
+    if constexpr (END) {   // [table | k-mer bins | deltas | conditional tables, 32 rows per code (rows >= N + 2 are never read)]
+        for (uint32_t i = tid; i < 32u * n_pos; i += TILED_THREADS) mine[SCRATCH_WORDS + (i / n_pos) * 32u + i % n_pos] = end_lds[i];
+        // reads[4]: a workgroup adds its non-zero ones to the counter block itself, as -H does with its bins
+        if (tid < 4u) {
+            const uint32_t v = end_lds[32u * n_pos + tid];
+            if (v) atomicAdd(&P.counters[P.off_end + 2u * n_pos * 16u + tid], (unsigned long long)v);
+        }
+    }
     for (uint32_t i = tid; i < 32u * 32u; i += TILED_THREADS) mine[i] = DO_PSS ? table[i] : 0u;
     for (uint32_t i = tid; i < 512u; i += TILED_THREADS)
         mine[SCRATCH_KMER + i] = (LDS_KMER && i < 2u * (1u << (2 * P.K))) ? lds_kmer[i] : 0u;
@@ -1517,10 +1652,12 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_compact_decode_twice(cons
 // w) and contributes one atomic; launched on the same stream right behind the tally kernel.
 // SITE: the slots of a SITE launch, SITE_SCRATCH_WORDS apart; word SCRATCH_WORDS + (half code << 5 | row) goes to
 // the [fwd_in | rev_in] pair at P.off_site (rows 0 and 1 of the pair are never written).
+// END: the slots of an END launch, END_SCRATCH_WORDS apart; word SCRATCH_WORDS + (code << 5 | row) goes to the
+// [fwd_c | rev_c] pair at P.off_end.
 constexpr uint32_t REDUCE_GROUPS = 32;
-template <bool SITE = false>
+template <bool SITE = false, bool END = false>
 __global__ void __launch_bounds__(256) reduce_partials(const TallyParams P, uint32_t n_slots, uint32_t lds_kmer_on) {
-    constexpr uint32_t SLOT_WORDS = SITE ? SITE_SCRATCH_WORDS : SCRATCH_WORDS;
+    constexpr uint32_t SLOT_WORDS = SITE ? SITE_SCRATCH_WORDS : END ? END_SCRATCH_WORDS : SCRATCH_WORDS;
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t i = gid % SLOT_WORDS, g = gid / SLOT_WORDS;
     if (g >= REDUCE_GROUPS) return;
@@ -1538,6 +1675,9 @@ __global__ void __launch_bounds__(256) reduce_partials(const TallyParams P, uint
         const uint32_t k = i - SCRATCH_WORDS, row = P.row_base + (k & 31u), hc = k >> 5;
         const uint32_t cell = ((hc >> 2) << 2) | ((hc & 2u) ? 2u : 1u);
         if (row >= 2u && row < n_pos) dst = &P.counters[P.off_site + ((hc & 1u) ? n_pos * 16u : 0u) + row * 16u + cell];
+    } else if (END && i >= SCRATCH_WORDS) {
+        const uint32_t k = i - SCRATCH_WORDS, row = k & 31u, ct = k >> 5;
+        if (row < n_pos) dst = &P.counters[P.off_end + ((ct & 1u) ? n_pos * 16u : 0u) + row * 16u + (ct >> 1)];
     } else {
         const uint32_t k = i - SCRATCH_DELTA;  // status counters belong to pass 0
         if (k < (uint32_t)ST_USED && P.row_base == 0u) { dst = &P.counters[P.off_stats + k]; is_delta = true; }
@@ -1560,8 +1700,9 @@ __global__ void __launch_bounds__(256) reduce_partials(const TallyParams P, uint
 
 // HIST: dynamic LDS is the staging buffer and, behind it, the 2 * P.hist_lds_bins words of the length histogram
 // SITE: one more static object, the 2 KiB in-context table
+// END: behind the staging buffer the conditional tables and reads[4], end_lds_bytes(N + 2) (never together with HIST)
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS = false, bool MASKQ = false, bool REGIONS = false, bool HIST = false,
-          bool SITE = false>
+          bool SITE = false, bool END = false>
 __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
@@ -1577,6 +1718,10 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P
         __shared__ uint32_t site_lds[SITE_WORDS];
         tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, true>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
                                                                                                       lds_delta, refs_lds, nullptr, nullptr, hist_lds, site_lds);
+    } else if constexpr (END) {
+        uint32_t *end_lds = (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces));
+        tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, false, true>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
+                                                                                                             lds_delta, refs_lds, nullptr, nullptr, hist_lds, nullptr, end_lds);
     } else
     tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
                                                                                             lds_delta, refs_lds, nullptr, nullptr, hist_lds);

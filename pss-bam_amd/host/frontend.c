@@ -33,6 +33,7 @@ int frontend_n_length_edges = 0;
 int frontend_min_base_quality = 0;
 int frontend_length_hist = 0;
 int frontend_site_context = PSSBAM_SITE_NONE;
+int frontend_end_depth = 0, frontend_end_cell5 = 0, frontend_end_cell3 = 0;
 const pss_regions *frontend_regions = NULL;
 uint32_t frontend_length_edges[PSSBAM_MAX_LENGTH_BINS - 1];
 const frontend_contig_map *frontend_contig_sets = NULL;
@@ -72,6 +73,7 @@ static struct early_feed {
     int min_bq;                     /* -Q: the minimum base quality, set on every engine after create */
     int hist;                       /* -H: the limit of the length histogram, set on every engine after create */
     int site;                       /* -X: the site context, set on every engine after create */
+    int end_depth, end_cell5, end_cell3; /* -E: the end condition, set on every engine after create */
     const pss_regions *regions;     /* -T: the intervals, set on every engine after create */
     int n_edges;                    /* -S: the length bin edges, set on every engine after create */
     uint32_t edges[PSSBAM_MAX_LENGTH_BINS - 1];
@@ -151,7 +153,8 @@ static void *engine_make_main(void *arg)
     if (pssbam_engine_create(&j->cfg, j->out) || pssbam_engine_feed_open(*j->out, j->n_ref, EF.fasta_bytes) ||
         (EF.min_bq > 0 && pssbam_engine_set_min_base_quality(*j->out, EF.min_bq)) ||
         (EF.hist > 0 && pssbam_engine_set_length_histogram(*j->out, EF.hist)) ||
-        (EF.site != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(*j->out, EF.site)) || send_regions(*j->out, EF.regions) ||
+        (EF.site != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(*j->out, EF.site)) ||
+        (EF.end_depth > 0 && pssbam_engine_set_end_condition(*j->out, EF.end_depth, EF.end_cell5, EF.end_cell3)) || send_regions(*j->out, EF.regions) ||
         (EF.n_rg > 0 && pssbam_engine_set_read_groups(*j->out, EF.n_rg, (const char *const *)EF.rg_ids)) ||
         (EF.n_edges > 0 && pssbam_engine_set_length_bins(*j->out, EF.n_edges, EF.edges)) || send_contig_sets(*j->out, EF.sets)) {
         j->rc = 1;
@@ -281,6 +284,9 @@ void frontend_warmup_start(const pssbam_config *cfg, const char *aln_path, const
             EF.min_bq = frontend_min_base_quality;
             EF.hist = frontend_length_hist;
             EF.site = frontend_site_context;
+            EF.end_depth = frontend_end_depth;
+            EF.end_cell5 = frontend_end_cell5;
+            EF.end_cell3 = frontend_end_cell3;
             EF.regions = frontend_regions;
             memcpy(EF.edges, frontend_length_edges, sizeof EF.edges);
             EF.sets = frontend_contig_sets;
@@ -302,6 +308,7 @@ static int same_length_bins(void)
 {
     return EF.n_edges == frontend_n_length_edges && EF.sets == frontend_contig_sets && EF.min_bq == frontend_min_base_quality &&
            EF.hist == frontend_length_hist && EF.site == frontend_site_context &&
+           EF.end_depth == frontend_end_depth && EF.end_cell5 == frontend_end_cell5 && EF.end_cell3 == frontend_end_cell3 &&
            EF.regions == frontend_regions &&
            memcmp(EF.edges, frontend_length_edges, (size_t)frontend_n_length_edges * sizeof *EF.edges) == 0;
 }
@@ -440,6 +447,8 @@ void run_result_free(run_result *res)
     free(res->hist_rev);
     free(res->site_fwd);
     free(res->site_rev);
+    free(res->end_fwd);
+    free(res->end_rev);
     free(res->fwd);
     free(res->rev);
     free(res->k5);
@@ -636,6 +645,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
                 (frontend_min_base_quality > 0 && pssbam_engine_set_min_base_quality(eng[g], frontend_min_base_quality)) ||
                 (frontend_length_hist > 0 && pssbam_engine_set_length_histogram(eng[g], frontend_length_hist)) ||
                 (frontend_site_context != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(eng[g], frontend_site_context)) ||
+                (frontend_end_depth > 0 && pssbam_engine_set_end_condition(eng[g], frontend_end_depth, frontend_end_cell5, frontend_end_cell3)) ||
                 send_regions(eng[g], frontend_regions) ||
                 (frontend_n_length_edges > 0 && pssbam_engine_set_length_bins(eng[g], frontend_n_length_edges, frontend_length_edges)) ||
                 send_contig_sets(eng[g], frontend_contig_sets)) {
@@ -831,6 +841,16 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
         res->site_rev = (unsigned long *)calloc(cells, sizeof(unsigned long));
         if (!res->site_fwd || !res->site_rev) { fprintf(stderr, "Error: out of memory\n"); goto done; }
         if (pssbam_engine_finish_site_context(eng[0], res->site_fwd, res->site_rev)) {
+            fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+            goto done;
+        }
+    }
+    if (frontend_end_depth > 0 && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -E: summed with the rest of the block */
+        const size_t cells = (size_t)(cfg->pss.region_len + 2) * 16;
+        res->end_fwd = (unsigned long *)calloc(cells, sizeof(unsigned long));
+        res->end_rev = (unsigned long *)calloc(cells, sizeof(unsigned long));
+        if (!res->end_fwd || !res->end_rev) { fprintf(stderr, "Error: out of memory\n"); goto done; }
+        if (pssbam_engine_finish_end_condition(eng[0], res->end_fwd, res->end_rev, res->end_reads)) {
             fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
             goto done;
         }

@@ -30,6 +30,9 @@ typedef struct run_result {
     /* pss-bam -X (frontend_site_context): the in-context tables IN, (region_len+2)*16 each with rows 0/1 as fwd / rev,
      * or NULL */
     unsigned long *site_fwd, *site_rev;
+    /* pss-bam -E (frontend_end_depth): the conditional tables COND, (region_len+2)*16 each, or NULL, and reads[4] */
+    unsigned long *end_fwd, *end_rev;
+    uint64_t end_reads[4];
 } run_result;
 
 /* pss-bam -G: every engine gets the input header's @RG IDs (pssbam_engine_set_read_groups) and run_tally()
@@ -47,6 +50,11 @@ extern int frontend_length_hist;
 /* pss-bam -X: the site context (PSSBAM_SITE_*; PSSBAM_SITE_NONE: off); every engine gets it
  * (pssbam_engine_set_site_context) and run_tally() returns the in-context pair.  Set before frontend_warmup_start. */
 extern int frontend_site_context;
+
+/* pss-bam -E: the end condition (depth 0: off) and its two cells; every engine gets them
+ * (pssbam_engine_set_end_condition) and run_tally() returns the conditional pair and reads[4].  Set before
+ * frontend_warmup_start. */
+extern int frontend_end_depth, frontend_end_cell5, frontend_end_cell3;
 
 /* -T: the intervals of the BED file (regions.h; NULL: none); every engine gets them (pssbam_engine_set_regions), on
  * every input path -- the filter lives in the engine.  Set before frontend_warmup_start. */

@@ -31,6 +31,11 @@
  * dinucleotide (C followed by G, or G preceded by C, in the folded reference), and <prefix>.noncpg.pss.*.txt, the tables
  * over every other position -- what this command writes for the input with the read bases at the other kind of site
  * replaced by N -- from the same pass; the other files stay as they are.  Not with -G, -S, -C or -H.
+ * Added: -E <ss|ds>[,<d>] also writes <prefix>.cond.pss.*.txt, the conditional tables: the forward table over the unpaired
+ * reads that carry a G->A (ds) or C->T (ss) within the first d (default 1) positions of their 3' end, the reverse table
+ * over those that carry a C->T within the first d positions of their 5' end -- what this command writes for the input
+ * reduced to those reads -- and <prefix>.cond.pss.reads.txt with the four read counts, from the same pass; the other
+ * files stay as they are.  Needs -r <= 30.  Not with -G, -S, -C, -H or -X.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -60,9 +65,9 @@ int main(int argc, char *argv[])
     unsigned long min_read_len = 0, max_read_len = 250000000;
     const char *up_ctx = "ACGT", *down_ctx = "ACGT";
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL, *read_group = NULL;
-    const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL, *bed_fn = NULL, *hist_arg = NULL, *site_arg = NULL;
+    const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL, *bed_fn = NULL, *hist_arg = NULL, *site_arg = NULL, *end_arg = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -81,6 +86,7 @@ int main(int argc, char *argv[])
         case 'T': bed_fn = optarg; break;
         case 'H': hist_arg = optarg; break;
         case 'X': site_arg = optarg; break;
+        case 'E': end_arg = optarg; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -109,7 +115,8 @@ int main(int argc, char *argv[])
               "-R <read group name to restrict analysis to (default: all reads)>\n"
               "-U <upstream context base filter; first base before alignment must be one of these (default: ACGT)>\n"
               "-D <downstream context base filter; first base before alignment must be one of these (default: ACGT)>\n"
-              "-m <only consider merged reads>\n",
+              "-m <only consider merged reads>\n"
+              "-E <ss|ds>[,<d>] <also write the tables of each end over the reads damaged within d bases (default: 1) of the other end>\n",
               stderr);
         exit(1);
     }
@@ -164,6 +171,25 @@ int main(int argc, char *argv[])
             fprintf(stderr, "-X (tables per site context) and %s exclude each other.\n",
                     by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)"
                     : ctg_map ? "-C (tables per contig set)" : "-H (fragment-length histogram)");
+            exit(1);
+        }
+    }
+    int end_depth = 0, end_cell5 = 0, end_cell3 = 0;
+    if (end_arg) {
+        char err[200];
+        if (pss_parse_end_condition(end_arg, &end_depth, &end_cell5, &end_cell3, err, sizeof err)) {
+            fprintf(stderr, "%s\n", err);
+            exit(1);
+        }
+        if (by_group || len_edges || ctg_map || hist_arg || site_arg) {
+            fprintf(stderr, "-E (tables conditional on the other end) and %s exclude each other.\n",
+                    by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)"
+                    : ctg_map ? "-C (tables per contig set)" : hist_arg ? "-H (fragment-length histogram)" : "-X (tables per site context)");
+            exit(1);
+        }
+        if (region_len > 30 || end_depth > region_len) {
+            fprintf(stderr, "-E (tables conditional on the other end) needs its depth <= -r <= 30 (both ends' marks are taken from the one pass "
+                            "over 32 table rows), not -r %d with depth %d.\n", region_len, end_depth);
             exit(1);
         }
     }
@@ -222,6 +248,7 @@ int main(int argc, char *argv[])
     if (min_bq_arg) fprintf(stderr, " -Q %d", min_bq);
     if (hist_arg) fprintf(stderr, " -H %d", hist_max);
     if (site_arg) fprintf(stderr, " -X %s", site_arg);
+    if (end_arg) fprintf(stderr, " -E %s", end_arg);
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -246,6 +273,9 @@ int main(int argc, char *argv[])
     frontend_min_base_quality = min_bq;
     frontend_length_hist = hist_max;
     frontend_site_context = site_arg ? PSSBAM_SITE_CPG : PSSBAM_SITE_NONE;
+    frontend_end_depth = end_depth;
+    frontend_end_cell5 = end_cell5;
+    frontend_end_cell3 = end_cell3;
     if (bed_fn) frontend_regions = &bed;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
@@ -284,6 +314,8 @@ int main(int argc, char *argv[])
         free(out_fwd);
         free(out_rev);
     }
+    if (res.end_fwd && (pss_write_labelled(fasta_fn, bam_fn, out_prefix, "cond", region_len, res.end_fwd, res.end_rev) ||
+                        pss_write_end_reads(out_prefix, res.end_reads))) exit(1);   /* -E */
     if (by_group && res.n_planes == 0)
         fprintf(stderr, "Warning: -G: the header of %s has no @RG line; only the tables of all reads were written.\n", bam_fn);
     /* <prefix>.<tag>: what `-R <ID> -o <prefix>.<ID>` (-G), `-l <lo> -L <hi> -o <prefix>.len<lo>-<hi>` (-S) or -F

@@ -4,6 +4,7 @@
  * /root/reference/pss-bam.c:504-633 and fragkon.c:231-249,:367-368.
  */
 #include "report.h"
+#include "pssbam_hip.h"
 
 #include <limits.h>
 #include <stdlib.h>
@@ -122,6 +123,46 @@ int pss_write_labelled(const char *fasta_fn, const char *bam_fn, const char *out
     free(fwd_rates);
     free(rev_rates);
     return rc;
+}
+
+int pss_parse_end_condition(const char *arg, int *depth, int *cell5, int *cell3, char *err, size_t err_len)
+{
+    const int ss = strncmp(arg, "ss", 2) == 0, ds = strncmp(arg, "ds", 2) == 0;
+    const char *rest = arg + 2;
+    long d = 1;
+    if (!ss && !ds) {
+        snprintf(err, err_len, "-E (tables conditional on the other end): unknown preset in \"%s\"; give ss or ds, optionally \",<depth>\".", arg);
+        return -1;
+    }
+    if (*rest) {
+        char *end = NULL;
+        if (*rest != ',' || rest[1] < '0' || rest[1] > '9' || (d = strtol(rest + 1, &end, 10), *end) || d < 1 || d > PSSBAM_MAX_END_DEPTH) {
+            snprintf(err, err_len, "-E (tables conditional on the other end): bad depth in \"%s\"; give <ss|ds>[,<d>] with d in 1..%d.", arg,
+                     PSSBAM_MAX_END_DEPTH);
+            return -1;
+        }
+    }
+    *depth = (int)d;
+    *cell5 = 13;
+    *cell3 = ss ? 13 : 2;
+    return 0;
+}
+
+int pss_write_end_reads(const char *out_prefix, const uint64_t reads[4])
+{
+    static const char *const names[4] = {"unpaired_reads", "marked_5p", "marked_3p", "marked_both"};
+    char *fn = (char *)malloc(strlen(out_prefix) + 32);
+    if (!fn) { fprintf(stderr, "Error: out of memory\n"); return 1; }
+    sprintf(fn, "%s.cond.pss.reads.txt", out_prefix);
+    FILE *f = fopen(fn, "w");
+    if (!f) {
+        fprintf(stderr, "Error: unable to write %s\n", fn);
+        free(fn);
+        return 1;
+    }
+    for (int k = 0; k < 4; k++) fprintf(f, "%s\t%llu\n", names[k], (unsigned long long)reads[k]);
+    free(fn);
+    return fclose(f) ? 1 : 0;
 }
 
 int pss_write_lengths(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int max_len, const uint64_t *fwd,

@@ -15,6 +15,13 @@ int pss_write_rates(const char *fasta_fn, const char *bam_fn, const char *out_pr
  * diagnostic. */
 int pss_write_labelled(const char *fasta_fn, const char *bam_fn, const char *out_prefix, const char *tag, int region_len,
                        const unsigned long *fwd, const unsigned long *rev);
+/* pss-bam -E: parses "<ss|ds>[,<d>]" -- ss: C->T at both ends (cell5 = cell3 = 13, column TC), ds: C->T at the 5' end
+ * and G->A at the 3' end (cell5 = 13, cell3 = 2, column AG); d = 1..PSSBAM_MAX_END_DEPTH, default 1.  Returns 0, or -1
+ * with a one-line message in err. */
+int pss_parse_end_condition(const char *arg, int *depth, int *cell5, int *cell3, char *err, size_t err_len);
+/* pss-bam -E: <out_prefix>.cond.pss.reads.txt -- four "<name><TAB><value>" lines: the unpaired reads added to the tables,
+ * the 5'-marked, the 3'-marked and the both-marked ones among them.  Returns 0, or 1 after a diagnostic. */
+int pss_write_end_reads(const char *out_prefix, const uint64_t reads[4]);
 /* pss-bam -H: <out_prefix>.pss.lengths.txt -- three '#' lines, the column names, then one tab-separated line
  * "<length> <fwd> <rev>" per length 0..max_len (zero rows included) and a last one labelled "><max_len>" for every
  * longer read; fwd / rev hold max_len + 2 counts.  Returns 0, or 1 after a diagnostic. */
