@@ -390,6 +390,35 @@ int pssbam_engine_set_end_condition(pssbam_engine *e, int32_t depth, int32_t cel
  * read counters; any pointer may be NULL.  PSSBAM_EINVAL when the setting is off. */
 int pssbam_engine_finish_end_condition(pssbam_engine *e, unsigned long *fwd_c, unsigned long *rev_c, uint64_t reads[4]);
 
+/* pss-bam -I: clipped and gapped reads are tallied by their anchored ends (on != 0; 0 switches it off again).  A record
+ * ANCHORS when
+ *   1. its CIGAR has at least one op and every op length is >= 1;
+ *   2. it reads [H][S] core [S][H] -- at most one hard clip at either extreme, at most one soft clip inside it
+ *      (lengths clipL / clipR, else 0) -- and the core is non-empty, holds only M I D = X, and starts and ends with a
+ *      match-type op (M, = or X); an N, a P, an interior clip or a core that starts or ends with I / D: no anchor;
+ *   3. SEQ and QUAL are present and clipL + (M I = X of the core) + clipR == l_seq;
+ *   4. span = (M D = X of the core) <= 2^31 - 1.
+ * With a / b the summed lengths of the match-type runs at the core's start / end (a = b = span when the core has no
+ * I / D), the tables and status counters are those of the engine without the setting on the records in which every
+ * anchoring record has been replaced by the one that differs from it in
+ *     CIGAR = <span>M,
+ *     SEQ'  = SEQ[clipL, clipL + a) + "N" * (span - a - b) + SEQ[l_seq - clipR - b, l_seq - clipR)
+ *             (SEQ[clipL, l_seq - clipR) when the core is all match-type),
+ *     QUAL' sliced the same way with Phred 0 as filler;
+ * a record that does not anchor is treated as without the setting, and a <len>M record anchors to itself.  So both
+ * ends sit where the reference has them, the length that min_read_len / max_read_len and region_len compare is the
+ * span of an unpaired read (a paired one still needs |TLEN| == span), and a position counts when no I / D lies between
+ * it and one of the alignment's two ends and adds nothing otherwise, like an N.
+ * PSSBAM_ST_SLOW_PATH alone may differ: a record of more than 16 CIGAR ops, and a gapped record whose every I / D lies
+ * within region_len reference bases of one end, takes the tiled kernels' one-lane path.
+ * The counter block keeps its size and layout (a bound block stays bound) and there is no new status slot.
+ * Legal after create (or reset) and before the first tally launch; with pssbam_engine_feed_open that is any time
+ * before set_references.  Goes with cfg.read_group, a minimum base quality and regions.  PSSBAM_EINVAL on an engine
+ * with PSSBAM_TALLY_KMER in its mask and with read groups, length bins, contig sets, a length histogram, site context
+ * or an end condition set (those setters return PSSBAM_EINVAL once this one is on); PSSBAM_ESTATE once records have
+ * been tallied.  The setting survives pssbam_engine_reset; engines whose blocks are summed must all have it. */
+int pssbam_engine_set_gapped_reads(pssbam_engine *e, int32_t on);
+
 /* The device-resident counter block [fwd | rev | k5 | k3 | stats] as one array of
  * n_u64 64-bit words, for a caller-side RCCL reduce across GPUs (sum, uint64).  With read groups it is
  * [fwd | rev | stats | fwd_0 | rev_0 | ... | fwd_n-1 | rev_n-1]: the leading fwd | rev are the unassigned

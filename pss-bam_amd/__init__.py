@@ -44,7 +44,7 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_contig_sets", "pssbam_engine_finish_kmer_groups", "pssbam_engine_set_min_base_quality",
     "pssbam_engine_set_regions", "pssbam_engine_set_length_histogram", "pssbam_engine_finish_length_histogram",
     "pssbam_engine_set_site_context", "pssbam_engine_finish_site_context",
-    "pssbam_engine_set_end_condition", "pssbam_engine_finish_end_condition",
+    "pssbam_engine_set_end_condition", "pssbam_engine_finish_end_condition", "pssbam_engine_set_gapped_reads",
 ]
 MAX_READ_GROUPS = 4096
 MAX_LENGTH_BINS = 64
@@ -56,6 +56,7 @@ SITE_NONE, SITE_CPG = 0, 1
 SITE_MODES = {None: SITE_NONE, "none": SITE_NONE, "cpg": SITE_CPG}
 MAX_END_DEPTH = 8
 END_PRESETS = {"ss": (13, 13), "ds": (13, 2)}   # (cell5, cell3): C->T at both ends / C->T at the 5' end, G->A at the 3' end
+GAPPED_TILED_OPS = 16   # pss-bam -I: CIGAR ops a lane of the tiled kernel walks (csrc/record_decode.h); more take the one-lane path
 EBUSY = -7
 
 
@@ -127,6 +128,7 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_finish_site_context.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_end_condition.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     L.pssbam_engine_finish_end_condition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pssbam_engine_set_gapped_reads.argtypes = [C.c_void_p, C.c_int32]
     L.pssbam_engine_set_regions.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_counters_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.pssbam_engine_bind_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -206,13 +208,15 @@ class Engine:
     context, see set_site_context; None = off.
     `end_condition` = (depth, cell5, cell3) (pss-bam -E): a second pair of tables over the unpaired reads whose other end
     carries the given cell within its first `depth` positions, see set_end_condition; None = off.
+    `gapped` = True (pss-bam -I): clipped and gapped reads are tallied by their anchored ends, see set_gapped.
     With `kmer` alone (no `pss`) the three split the k-mer tables instead (fragkon -G / -S / -C): every plane is a
     k5 / k3 pair, and the length bins go by the SEQ length and kmer's min_read_len / max_read_len."""
 
     def __init__(self, pss: dict | None = None, kmer: dict | None = None, read_group: str | None = None,
                  kernel: int = KERNEL_AUTO, device: int = -1, read_groups: list[str] | None = None,
                  length_bins: list[int] | None = None, contig_sets=None, min_base_qual: int = 0,
-                 length_hist: int = 0, site_context: str | None = None, end_condition: tuple[int, int, int] | None = None):
+                 length_hist: int = 0, site_context: str | None = None, end_condition: tuple[int, int, int] | None = None,
+                 gapped: bool = False):
         L = hip_lib()
         cfg = _Config()
         cfg.abi_version = 1
@@ -258,6 +262,9 @@ class Engine:
         self._end_condition = (0, 0, 0)
         if end_condition is not None:
             self.set_end_condition(*end_condition)
+        self._gapped = False
+        if gapped:
+            self.set_gapped(True)
         if read_groups is not None:
             self.set_read_groups(read_groups)
         if length_bins is not None:
@@ -348,6 +355,21 @@ class Engine:
         reads = np.zeros(4, dtype=np.uint64)
         _chk(self._L.pssbam_engine_finish_end_condition(self._h, fwd.ctypes.data, rev.ctypes.data, reads.ctypes.data))
         return fwd, rev, reads
+
+    def set_gapped(self, on: bool):
+        """pss-bam -I: a read whose CIGAR is [H][S] core [S][H] with a core of M I D = X ops that starts and ends with a
+        match-type op (and whose query lengths add up to its SEQ) is tallied by its anchored ends -- as the record
+        <span>M whose SEQ keeps the match-type run at either end of the core and holds N in between, so a position
+        between two indels adds nothing; every other record is treated as before.  Not with kmer, read groups, length bins, contig
+        sets, the length histogram, site context or the end condition.  Before the first tally (after feed_open: before
+        set_references); the counter block does not change.  Survives reset."""
+        _chk(self._L.pssbam_engine_set_gapped_reads(self._h, int(bool(on))))
+        self._gapped = bool(on)
+
+    @property
+    def gapped(self) -> bool:
+        """whether clipped and gapped reads are tallied by their anchored ends"""
+        return self._gapped
 
     def set_regions(self, names, name_of, starts, ends):
         """pss-bam -T / fragkon -T: only records whose alignment overlaps one of the intervals are tallied -- the tables

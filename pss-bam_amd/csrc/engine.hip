@@ -220,6 +220,7 @@ struct pssbam_engine {
     uint32_t site_mode = 0, off_site = 0;
     // -E (pssbam_engine_set_end_condition): fwd_c | rev_c | reads[4], rows * 16 words per table, at off_end = the end of the block as it is without them
     uint32_t end_depth = 0, end_cell5 = 0, end_cell3 = 0, off_end = 0;
+    bool gapped = false;   // -I (pssbam_engine_set_gapped_reads): clipped and gapped reads are tallied by their anchored ends; no counter words
     int env_hist_lds_bins = -1;   // PSSBAM_HIST_LDS_BINS: at most this many bins of each array in LDS (tests: the global-atomic path with short reads)
     // -T (pssbam_engine_set_regions): contig name -> its merged intervals, kept on the host; the per-refID device table is
     // packed from it whenever the reference list or the map changes (pack_regions)
@@ -912,24 +913,26 @@ static int with_planes(PlaneSel sel, F f) {
 static int no_kernel() { return fail(PSSBAM_EINVAL, "no tally kernel is built for this combination of options"); }
 
 // One row pass of tally_tiled and its reduce_partials: the instantiation for the launch's tallies, the pass (LATER: rows
-// 32.. of a large -r) and its -Q, -T, -H, -X and -E state.  `exists` is the list of instantiations: the k-mer tally (alone or
+// 32.. of a large -r) and its -Q, -T, -H, -X, -E and -I state.  `exists` is the list of instantiations: the k-mer tally (alone or
 // beside the substitution tables) and -H belong to pass 0, -Q -H -X to the substitution tables, -X excludes the other two;
-// -E is the substitution tally of pass 0 alone, with or without -Q and -T.
+// -E is the substitution tally of pass 0 alone, with or without -Q and -T; -I is the substitution tally alone in every pass, with or
+// without -Q and -T (eight instantiations).
 // (SITE, END: the larger scratch slot of the -X / -E instantiations and the reduce that walks it)
 static int launch_tiled(pssbam_engine *e, TallyParams &P, bool do_pss, bool do_kmer, bool kmer_lds, bool later, bool maskq, bool regions,
-                        bool hist, bool site, bool endc, uint32_t lds, uint32_t n_tiles) {
-    return with_flags([&](auto DO_PSS, auto DO_KMER, auto LDS_KMER, auto LATER, auto MASKQ, auto REGIONS, auto HIST, auto SITE, auto END) -> int {
+                        bool hist, bool site, bool endc, bool gapped, uint32_t lds, uint32_t n_tiles) {
+    return with_flags([&](auto DO_PSS, auto DO_KMER, auto LDS_KMER, auto LATER, auto MASKQ, auto REGIONS, auto HIST, auto SITE, auto END, auto GAPPED) -> int {
         constexpr bool exists = (DO_KMER() || !LDS_KMER()) &&
                                 (LATER() ? DO_PSS() && !DO_KMER() && !HIST()
                                          : (DO_PSS() || DO_KMER()) && (DO_PSS() || !(MASKQ() || HIST() || SITE())) && !(SITE() && (DO_KMER() || HIST()))) &&
-                                (!END() || (DO_PSS() && !DO_KMER() && !LATER() && !HIST() && !SITE()));
+                                (!END() || (DO_PSS() && !DO_KMER() && !LATER() && !HIST() && !SITE())) &&
+                                (!GAPPED() || (DO_PSS() && !DO_KMER() && !LDS_KMER() && !HIST() && !SITE() && !END()));
         if constexpr (exists)
-            return launch_with_reduce(e, tally_tiled<DO_PSS(), DO_KMER(), LDS_KMER(), LATER(), MASKQ(), REGIONS(), HIST(), SITE(), END()>,
+            return launch_with_reduce(e, tally_tiled<DO_PSS(), DO_KMER(), LDS_KMER(), LATER(), MASKQ(), REGIONS(), HIST(), SITE(), END(), GAPPED()>,
                                       reduce_partials<SITE(), END()>, SITE() ? SITE_SCRATCH_WORDS : END() ? END_SCRATCH_WORDS : SCRATCH_WORDS, lds, n_tiles, P,
                                       std::tuple<>(), (uint32_t)LDS_KMER());
         else
             return no_kernel();
-    }, do_pss, do_kmer, kmer_lds, later, maskq, regions, hist, site, endc);
+    }, do_pss, do_kmer, kmer_lds, later, maskq, regions, hist, site, endc, gapped);
 }
 
 // How many 16-byte pieces of a record the tiled kernel must stage so that everything the path
@@ -1048,6 +1051,8 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         P.end_cell3 = e->end_cell3;
         P.off_end = e->off_end;
     }
+    const bool gapped = do_pss && e->gapped;   // -I: the GAPPED instantiations; without it the engine launches what it always did
+    P.gapped = gapped ? 1u : 0u;
     if (regions) {
         P.region_info = e->d_region_info;
         P.region_grid = e->d_region_grid;
@@ -1179,9 +1184,9 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                     });
                 }
             }
-        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions && !hist && !site && !endc) {
+        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions && !hist && !site && !endc && !gapped) {
             // -r N <= 16 (2 context rows + 16 positions): the short-window variant, one pass (it stages prefixes only
-            // and has no QUAL path: -R and -Q go to tally_tiled; so do -T, -H, -X and -E, whose arms only tally_tiled carries)
+            // and has no QUAL path: -R and -Q go to tally_tiled; so do -T, -H, -X, -E and -I, whose arms only tally_tiled carries)
             if (!do_kmer && getenv("PSSBAM_COMPACT_DECODE_TWICE"))   // diagnostics: what the shared header decode costs
                 rc = launch_with_reduce(e, tally_compact_decode_twice, reduce_partials<false>, SCRATCH_WORDS, lds, n_tiles, P, std::tuple<>(), 0u);
             else
@@ -1205,8 +1210,8 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
             if (endc) lds0 += end_lds_bytes(e->rows);   // -E (one pass: -r <= 30): the conditional tables and reads[4] behind the staging buffer
             for (uint32_t pass = 0; pass < n_passes && rc == PSSBAM_OK; pass++) {
                 P.row_base = pass * TILED_ROWS;
-                rc = pass == 0 ? launch_tiled(e, P, do_pss, do_kmer, kmer_lds, false, maskq, regions, hist, site, endc, lds0, n_tiles)
-                               : launch_tiled(e, P, true, false, false, true, maskq, regions, false, site, false, lds, n_tiles);
+                rc = pass == 0 ? launch_tiled(e, P, do_pss, do_kmer, kmer_lds, false, maskq, regions, hist, site, endc, gapped, lds0, n_tiles)
+                               : launch_tiled(e, P, true, false, false, true, maskq, regions, false, site, false, gapped, lds, n_tiles);
             }
         }
         if (rc != PSSBAM_OK) return rc;
@@ -1465,6 +1470,7 @@ static int set_planes(pssbam_engine *e, PlaneSel sel, uint32_t n_planes, const c
     if (e->hist_max) return fail(PSSBAM_EINVAL, "%s and the length histogram exclude each other", what);
     if (e->site_mode) return fail(PSSBAM_EINVAL, "%s and site context exclude each other", what);
     if (e->end_depth) return fail(PSSBAM_EINVAL, "%s and the end condition exclude each other", what);
+    if (e->gapped) return fail(PSSBAM_EINVAL, "%s and gapped reads exclude each other", what);
     const bool kmer = e->cfg.tally_mask == PSSBAM_TALLY_KMER;
     if (e->cfg.tally_mask != PSSBAM_TALLY_PSS && !kmer)
         return fail(PSSBAM_EINVAL, "%s split the substitution tables or the k-mer tables, not both (PSSBAM_TALLY_PSS | PSSBAM_TALLY_KMER)", what);
@@ -1549,6 +1555,21 @@ extern "C" int pssbam_engine_set_min_base_quality(pssbam_engine *e, int32_t q) {
     return PSSBAM_OK;
 }
 
+extern "C" int pssbam_engine_set_gapped_reads(pssbam_engine *e, int32_t on) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (on) {
+        if (e->cfg.tally_mask != PSSBAM_TALLY_PSS)
+            return fail(PSSBAM_EINVAL, "gapped reads are tallied by their anchored ends in the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
+        if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "gapped reads and read groups / length bins / contig sets exclude each other");
+        if (e->hist_max) return fail(PSSBAM_EINVAL, "gapped reads and the length histogram exclude each other");
+        if (e->site_mode) return fail(PSSBAM_EINVAL, "gapped reads and site context exclude each other");
+        if (e->end_depth) return fail(PSSBAM_EINVAL, "gapped reads and the end condition exclude each other");
+    }
+    if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set gapped reads after create or reset, before the first tally");
+    e->gapped = on != 0;   // (the counter block keeps its size: a caller-bound block stays bound)
+    return PSSBAM_OK;
+}
+
 extern "C" int pssbam_engine_set_length_histogram(pssbam_engine *e, int32_t max_len) {
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
     if (max_len < 0 || max_len > PSSBAM_MAX_HIST_LENGTH) return fail(PSSBAM_EINVAL, "length histogram limit %d outside 0..%d", max_len, PSSBAM_MAX_HIST_LENGTH);
@@ -1557,6 +1578,7 @@ extern "C" int pssbam_engine_set_length_histogram(pssbam_engine *e, int32_t max_
     if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the length histogram and read groups / length bins / contig sets exclude each other");
     if (e->site_mode) return fail(PSSBAM_EINVAL, "the length histogram and site context exclude each other");
     if (e->end_depth) return fail(PSSBAM_EINVAL, "the length histogram and the end condition exclude each other");
+    if (e->gapped && max_len) return fail(PSSBAM_EINVAL, "the length histogram and gapped reads exclude each other");
     if (const int rc = check_may_resize(e, "the length histogram")) return rc;
     if ((uint32_t)max_len == e->hist_max) return PSSBAM_OK;
     HIP_TRY(hipSetDevice(e->device));
@@ -1588,6 +1610,7 @@ extern "C" int pssbam_engine_set_site_context(pssbam_engine *e, int32_t mode) {
     if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "site context and read groups / length bins / contig sets exclude each other");
     if (e->hist_max) return fail(PSSBAM_EINVAL, "site context and the length histogram exclude each other");
     if (e->end_depth) return fail(PSSBAM_EINVAL, "site context and the end condition exclude each other");
+    if (e->gapped && mode != PSSBAM_SITE_NONE) return fail(PSSBAM_EINVAL, "site context and gapped reads exclude each other");
     if (const int rc = check_may_resize(e, "the site context")) return rc;
     if ((uint32_t)mode == e->site_mode) return PSSBAM_OK;
     HIP_TRY(hipSetDevice(e->device));
@@ -1628,6 +1651,7 @@ extern "C" int pssbam_engine_set_end_condition(pssbam_engine *e, int32_t depth, 
     if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the end condition and read groups / length bins / contig sets exclude each other");
     if (e->hist_max) return fail(PSSBAM_EINVAL, "the end condition and the length histogram exclude each other");
     if (e->site_mode) return fail(PSSBAM_EINVAL, "the end condition and site context exclude each other");
+    if (e->gapped && depth) return fail(PSSBAM_EINVAL, "the end condition and gapped reads exclude each other");
     if (const int rc = check_may_resize(e, "the end condition")) return rc;
     if ((uint32_t)depth != e->end_depth) {
         HIP_TRY(hipSetDevice(e->device));

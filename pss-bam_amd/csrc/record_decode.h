@@ -33,6 +33,10 @@ struct TallyParams {
     const uint32_t *n_recs_dev;   // non-NULL: the record count is read from device memory (blocks indexed on the device)
     uint64_t recs_bytes;          // bytes of the record block (= offs[n_recs])
     uint32_t tally_mask;          // PSSBAM_TALLY_*
+    // -I: clipped and gapped reads are tallied by their anchored ends (cigar_anchor below).  The GAPPED instantiations of
+    // tally_tiled are picked on the host; this flag is read by tally_simple only.  (It fills the four bytes of padding in
+    // front of the next pointer: the struct keeps its size and every other member its place in the kernarg segment.)
+    uint32_t gapped;
     const uint8_t *genome;        // all contigs, 1 stored byte/base (enc_byte), padded between
     // the same array at 4 bits/base for the tiled kernel's end windows (half the HBM lines):
     // position p = bits 4*(p%8) of dword p/8; nibble 0..3 = A C G T, 4 + (in -U) + 2*(in -D) otherwise
@@ -428,6 +432,72 @@ __device__ __forceinline__ uint32_t read_nibble(const Src &src, const RecHdr &h,
     return (i & 1u) ? (b & 0xFu) : (b >> 4);
 }
 
+// ---- -I: the anchored ends of a clipped / gapped alignment ---------------------------------------------------
+// A record ANCHORS when its CIGAR is [H][S] core [S][H] with every length >= 1, the core holds only M I D = X and
+// starts and ends with a match-type op (M = X), the query lengths add up to l_seq, and the reference span
+// (M D = X of the core) is at most 2^31 - 1.  It is then tallied as the record <span>M whose SEQ is
+//     SEQ[q0, q0 + a) + "N" * (span - a - b) + SEQ[q1 - b, q1)
+// with q0 = the leading soft clip, q1 = l_seq - the trailing one, a / b = the summed match-type runs at the core's two
+// extremes (a = b = span when the core has no I / D): both ends sit where the reference has them, and a position between
+// the two runs adds nothing.  (SEQ / QUAL presence is the caller's clause: plan_head.)
+// 32-bit arithmetic: an op length is below 2^28 and `span` is tested after every add, so it cannot wrap before the
+// test fails; the query side counts l_seq DOWN, which cannot wrap at all.  At most max_ops ops are visited; a record
+// with more does not anchor here (the tiled kernel hands it to its one-lane path, which walks them all).
+constexpr uint32_t GAPPED_TILED_OPS = 16;   // ops a lane of tally_tiled walks
+struct Anchor {
+    bool ok;
+    uint32_t span, q0, q1, a, b;
+};
+template <class Src>
+__device__ __forceinline__ Anchor cigar_anchor(const Src &src, const RecHdr &h, uint32_t max_ops) {
+    const uint32_t n = h.n_cigar;                  // (0 for a malformed record)
+    const uint32_t cig = h.seq_off - 4u * n;
+    bool ok = n >= 1u && n <= max_ops;
+    // st: 0 nothing yet, 1 behind the leading H, 2 behind the leading S, 3 in the core, 4 behind the trailing S, 5 behind the trailing H
+    uint32_t st = 0u, span = 0u, rem = h.l_seq, clip_l = 0u, clip_r = 0u, a = 0u, run = 0u;
+    bool gap = false, last_match = false;
+    const uint32_t n_walk = ok ? n : 0u;
+    for (uint32_t k = 0; k < n_walk; k++) {
+        const uint32_t c = src.u32(cig + 4u * k);
+        const uint32_t len = c >> 4, op = c & 15u;
+        const bool is_m = op == 0u || op == 7u || op == 8u, is_i = op == 1u, is_d = op == 2u, is_s = op == 4u, is_h = op == 5u;
+        uint32_t qlen = 0u;
+        ok = ok && len >= 1u;
+        if (is_m) {
+            ok = ok && st <= 3u;
+            st = 3u;
+            span += len;
+            run += len;
+            if (!gap) a = run;
+            last_match = true;
+            qlen = len;
+        } else if (is_i || is_d) {
+            ok = ok && st == 3u;
+            gap = true;
+            run = 0u;
+            last_match = false;
+            if (is_d) span += len; else qlen = len;
+        } else if (is_s) {
+            if (st <= 1u) { st = 2u; clip_l = len; }
+            else { ok = ok && st == 3u && last_match; st = 4u; clip_r = len; }
+            qlen = len;
+        } else if (is_h) {
+            if (st == 0u) st = 1u;
+            else { ok = ok && ((st == 3u && last_match) || st == 4u); st = 5u; }
+        } else ok = false;                          // N, P, a reserved code
+        ok = ok && span <= 0x7FFFFFFFu && qlen <= rem;
+        rem -= min(qlen, rem);
+    }
+    Anchor A;
+    A.ok = ok && st >= 3u && (st != 3u || last_match) && rem == 0u;
+    A.span = span;
+    A.q0 = clip_l;
+    A.q1 = h.l_seq - clip_r;
+    A.a = a;
+    A.b = run;
+    return A;
+}
+
 // ---- what to do with one record ---------------------------------------------------------
 // status of a record, as the reference's main loops would classify it
 enum : uint32_t { RS_LIVE = 0, RS_RG_DROPPED = 1, RS_PARSE_SKIP = 2, RS_NO_CONTIG = 3 };
@@ -448,6 +518,15 @@ struct Plan {
     bool fk5, fk3;           // which k-mer table(s) this read may add to
     uint32_t Lk;             // strlen(SEQ)
 };
+// -I: the plan of the GAPPED plan_head gains the read-side anchors.  Reference offset g of the alignment is read base
+// q0 + g while g < a (the run at the start) and read base q1 - (L - g) from g = L - b on (the run at the end); s and L
+// stay the reference start and the reference length.  A record that does not anchor has q0 = 0, q1 = a = b = L.  (A type of its own: the plan
+// of every other instantiation keeps its size, and with it the code of the functions that return one.)
+struct GappedPlan : Plan {
+    uint32_t q0, q1, a, b;
+};
+template <bool GAPPED> struct PlanOf { using type = Plan; };
+template <> struct PlanOf<true> { using type = GappedPlan; };
 
 // Text-equivalence + contig lookup + the filters of the enabled tool(s), everything that can be
 // decided from the record alone.  No genome access.  Straight-line predicated code in 32-bit
@@ -468,9 +547,13 @@ struct RefsLdsCached {  // first `n_cached` entries (and the "*" entry, kept at 
     }
 };
 
-template <bool DO_PSS, bool DO_KMER, bool MAY_HAVE_RG = true, class Src, class Refs>
-__device__ __forceinline__ Plan plan_head(const TallyParams &P, const Src &src, const RecHdr &h, const Refs &refs) {
-    Plan pl;
+// GAPPED (-I, substitution tables only): a record that anchors (cigar_anchor, SEQ and QUAL present) passes the CIGAR clause
+// with op_len = its reference span, which is also its unpaired length; max_ops bounds the walk.
+template <bool DO_PSS, bool DO_KMER, bool MAY_HAVE_RG = true, bool GAPPED = false, class Src, class Refs>
+__device__ __forceinline__ typename PlanOf<GAPPED>::type plan_head(const TallyParams &P, const Src &src, const RecHdr &h, const Refs &refs,
+                                                                   uint32_t max_ops = 0xFFFFFFFFu) {
+    static_assert(!GAPPED || (DO_PSS && !DO_KMER), "anchored ends belong to the substitution tally");
+    typename PlanOf<GAPPED>::type pl;
     pl.pss_fwd = pl.pss_rev = false;
     pl.flag = h.flag;
 
@@ -498,16 +581,29 @@ __device__ __forceinline__ Plan plan_head(const TallyParams &P, const Src &src, 
     const bool paired = (h.flag & FL_PAIRED) != 0;
     // cigar_ok: exactly "<len>M"; flags: none of 0x4 0x100 0x200 0x400 0x800; s >= 0 (the `s >= 2`
     // / `s >= k/2` tests below imply it); both tools share these
-    const bool common = live && h.n_cigar == 1u && (h.cigar0 & 0xFu) == 0u && !(h.flag & FL_REJECT) && h.pos >= 0;
-    const uint32_t op_len = h.cigar0 >> 4;
+    // (GAPPED is a constant: without it every expression below is the one it has always been)
+    [[maybe_unused]] Anchor an;
+    if constexpr (GAPPED) {
+        an = cigar_anchor(src, h, max_ops);
+        an.ok = an.ok && h.l_seq >= 1u && q0 != 0xFFu;
+    }
+    const bool common = GAPPED ? live && (an.ok || (h.n_cigar == 1u && (h.cigar0 & 0xFu) == 0u)) && !(h.flag & FL_REJECT) && h.pos >= 0
+                               : live && h.n_cigar == 1u && (h.cigar0 & 0xFu) == 0u && !(h.flag & FL_REJECT) && h.pos >= 0;
+    const uint32_t op_len = GAPPED && an.ok ? an.span : h.cigar0 >> 4;
     const uint32_t s = (uint32_t)h.pos;
     const bool pair_ok = (h.flag & (FL_PROPER | FL_MUNMAP)) == FL_PROPER;
 
     pl.L = pl.Lk = l_text;
     pl.pss_cand = pl.fk5 = pl.fk3 = false;
     if (DO_PSS) {  // process_aln filters, pss-bam.c:401-420
-        const uint32_t L = paired ? (uint32_t)(h.tlen < 0 ? -(int64_t)h.tlen : (int64_t)h.tlen) : l_text;
+        const uint32_t L = paired ? (uint32_t)(h.tlen < 0 ? -(int64_t)h.tlen : (int64_t)h.tlen) : GAPPED && an.ok ? an.span : l_text;
         pl.L = L;
+        if constexpr (GAPPED) {
+            pl.q0 = an.ok ? an.q0 : 0u;
+            pl.q1 = an.ok ? an.q1 : L;
+            pl.a = an.ok ? an.a : L;
+            pl.b = an.ok ? an.b : L;
+        }
         // s >= 2 && s + L + 2 <= glen, without overflow: L <= glen - 4 first (op_len == L < 2^28)
         bool ok = common && op_len == L && glen >= 4u && L <= glen - 4u && s - 2u <= glen - 4u - L;
         ok = ok && !(h.mapq < P.pss_min_mq);
@@ -634,16 +730,20 @@ __device__ __forceinline__ uint32_t region_ref_index(const TallyParams &P, const
 }
 // the two grid words of the query (8 adjacent bytes).  A candidate ends inside its contig (s + L + 2 <= length), so its
 // bin and the one behind it are inside the contig's grid.
-__device__ __forceinline__ void region_grid_load(const TallyParams &P, const RecHdr &h, const uint4 d, RegionQuery &q) {
+// (ref_len: the alignment's reference length -- cigar0 >> 4 for a <len>M candidate; -I: Plan::L, the span of a candidate of the GAPPED plan_head)
+__device__ __forceinline__ void region_grid_load(const TallyParams &P, const RecHdr &h, const uint4 d, RegionQuery &q, uint32_t ref_len) {
     q.d = d;
     q.a = (uint32_t)h.pos;
-    q.b = q.a + (h.cigar0 >> 4);
+    q.b = q.a + ref_len;
     q.lo = q.hi = 0u;
     if (d.y) {
         const uint32_t *g = P.region_grid + d.z + (q.a >> P.region_shift);
         q.lo = g[0];
         q.hi = g[1];
     }
+}
+__device__ __forceinline__ void region_grid_load(const TallyParams &P, const RecHdr &h, const uint4 d, RegionQuery &q) {
+    region_grid_load(P, h, d, q, h.cigar0 >> 4);
 }
 __device__ __forceinline__ bool region_resolve(const TallyParams &P, const RegionQuery &q) {
     if (!q.d.y) return false;   // a contig without intervals tallies nothing
@@ -667,14 +767,23 @@ __device__ __forceinline__ bool region_hit(const TallyParams &P, const RecHdr &h
     region_grid_load(P, h, P.region_info[region_ref_index(P, h)], q);
     return region_resolve(P, q);
 }
+__device__ __forceinline__ bool region_hit(const TallyParams &P, const RecHdr &h, uint32_t ref_len) {   // (-I)
+    RegionQuery q;
+    region_grid_load(P, h, P.region_info[region_ref_index(P, h)], q, ref_len);
+    return region_resolve(P, q);
+}
 
 // both steps with the two context bytes fetched from global memory (lane-per-read kernels)
 // MAY_HAVE_REGIONS: the -T filter, decided at run time (a NULL table pointer = off).  The one-lane overflow paths of
 // the tiled kernels pass their kernel's REGIONS flag, so the instantiations without it contain none of it.
-template <bool DO_PSS, bool DO_KMER, bool MAY_HAVE_REGIONS = true, class Src>
-__device__ Plan make_plan(const TallyParams &P, const Src &src, const RecHdr &h) {
-    Plan pl = plan_head<DO_PSS, DO_KMER>(P, src, h, RefsGlobal{P.ref_info});
+// GAPPED (-I): plan_head's anchored form, any number of CIGAR ops; a candidate's reference length is then Plan::L.
+template <bool DO_PSS, bool DO_KMER, bool MAY_HAVE_REGIONS = true, bool GAPPED = false, class Src>
+__device__ typename PlanOf<GAPPED>::type make_plan(const TallyParams &P, const Src &src, const RecHdr &h) {
+    typename PlanOf<GAPPED>::type pl = plan_head<DO_PSS, DO_KMER, true, GAPPED>(P, src, h, RefsGlobal{P.ref_info});
     // a candidate whose alignment meets no region is filtered
+    if constexpr (GAPPED) {
+        if (MAY_HAVE_REGIONS && P.region_info && pl.pss_cand && !region_hit(P, h, pl.L)) pl.pss_cand = false;
+    } else
     if (MAY_HAVE_REGIONS && P.region_info && (pl.pss_cand || pl.fk5 || pl.fk3) && !region_hit(P, h)) pl.pss_cand = pl.fk5 = pl.fk3 = false;
     if (DO_PSS) {
         uint32_t l1 = 0, r1 = 0;

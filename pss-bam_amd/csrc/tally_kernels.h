@@ -55,6 +55,10 @@
 //                 lengths are merged inside the wave first, the first HIST_LDS_MAX_BINS bins of each array live in
 //                 LDS behind the staging buffer and leave it once, at kernel end (hist_wave_add below).
 //
+//  GAPPED arm of tally_tiled (-I, every pass): clipped and gapped reads by their anchored ends.  plan_head walks the CIGAR in
+//                 the staged prefix (record_decode.h: cigar_anchor), a lane's read stream starts at its end's anchor and
+//                 CODES-B blanks what lies outside the end's matched run; the reference side is the plain kernel's.
+//
 // Integer/byte work only: no MFMA anywhere (the bound is HBM bandwidth).
 #pragma once
 
@@ -146,37 +150,56 @@ __device__ __forceinline__ bool site_in_cpg(const uint8_t *G, int64_t p) {
 // reference-only and never masked.  min_bq == 0 masks nothing.
 // SITE (-X cpg): a position that is counted and whose reference position is in CpG context is added to `site` as well
 // (genome orientation for both strands: the set is its own reverse complement); the context rows never are.
-template <bool MASKQ, bool SITE, class Src, class Tab, class Site>
+// GAPPED (-I): the read-side anchors of the record (GappedPlan::q0 / q1 / a / b); the reference side (s, L) stays as it is.  A
+// position counts when no I / D lies between it and one of the alignment's two ends: reference offset g < a is read base q0 + g (the
+// run at the start), g >= L - b is read base q1 - (L - g) (the run at the end, which a window longer than L - b reaches from the
+// far side), anything between adds nothing, like an N.  Without GAPPED the read index is the reference offset, as for every <len>M
+// record.
+struct ReadAnchors { uint32_t q0, q1, a, b; };
+struct NoAnchors {};   // (an empty argument: the instantiations without GAPPED keep their signature)
+template <bool MASKQ, bool SITE, bool GAPPED = false, class Src, class Tab, class Site, class An = NoAnchors>
 __device__ void tally_end(const Tab &tab, const Site &site, uint32_t table, const Src &src, const RecHdr &h, const uint8_t *G,
-                          int64_t s, uint32_t L, int N, bool left, bool comp, uint32_t min_bq) {
+                          int64_t s, uint32_t L, int N, bool left, bool comp, uint32_t min_bq, An an = An{}) {
     const uint32_t c0 = ref_code(left ? G[s - 2] : G[s + L + 1]);  // second context base -> row 0
     const uint32_t c1 = ref_code(left ? G[s - 1] : G[s + L]);      // first context base  -> row 1
     if (c0 < 4u) tab.add(table, 0, comp ? 15u - 5u * c0 : 5u * c0);
     if (c1 < 4u) tab.add(table, 1, comp ? 15u - 5u * c1 : 5u * c1);
     for (int i = 0; i < N; i++) {
-        const uint32_t ri = left ? (uint32_t)i : L - 1u - (uint32_t)i;
+        const uint32_t gi = left ? (uint32_t)i : L - 1u - (uint32_t)i;   // offset of the position in the alignment's reference stretch
+        uint32_t ri = gi;
+        if constexpr (GAPPED) {
+            if (gi < an.a) ri = an.q0 + gi;
+            else if (gi >= L - an.b) ri = an.q1 - (L - gi);
+            else continue;                                               // between the two runs
+        }
         if (MASKQ && ri < h.l_seq && src.u8(h.qual_off + ri) < min_bq) continue;   // (absent QUAL is 0xFF: never below)
         const uint32_t rd = nib_code(read_nibble(src, h, ri));
-        const uint32_t rf = ref_code(G[s + (int64_t)ri]);
+        const uint32_t rf = ref_code(G[s + (int64_t)gi]);
         if (rd < 4u && rf < 4u) {
             const uint32_t cell = 4u * rd + rf;
             tab.add(table, (uint32_t)i + 2u, comp ? 15u - cell : cell);
             if constexpr (SITE) {
-                if (site_in_cpg(G, s + (int64_t)ri)) site.add(table, (uint32_t)i + 2u, comp ? 15u - cell : cell);
+                if (site_in_cpg(G, s + (int64_t)gi)) site.add(table, (uint32_t)i + 2u, comp ? 15u - cell : cell);
             }
         }
     }
 }
 
-template <bool MASKQ = false, bool SITE = false, class Src, class Tab, class Site>
+template <bool MASKQ = false, bool SITE = false, bool GAPPED = false, class Src, class Tab, class Site>
 __device__ __forceinline__ void tally_pss_record(const TallyParams &P, const Tab &tab, const Site &site, const Src &src,
-                                                 const RecHdr &h, const Plan &pl) {
+                                                 const RecHdr &h, const typename PlanOf<GAPPED>::type &pl) {
     const uint32_t min_bq = MASKQ ? P.min_bq : 0u;
     const uint8_t *G = P.genome + pl.gbase;
     // forward-strand read: fwd table <- left end, rev table <- right end;
     // reverse-strand read: fwd table <- right end complemented, rev table <- left end complemented
+    if constexpr (GAPPED) {   // (a plan made by the GAPPED plan_head)
+        const ReadAnchors an{pl.q0, pl.q1, pl.a, pl.b};
+        if (pl.pss_fwd) tally_end<MASKQ, SITE, true>(tab, site, 0u, src, h, G, pl.s, pl.L, P.N, !pl.rev, pl.rev, min_bq, an);
+        if (pl.pss_rev) tally_end<MASKQ, SITE, true>(tab, site, 1u, src, h, G, pl.s, pl.L, P.N, pl.rev, pl.rev, min_bq, an);
+    } else {
     if (pl.pss_fwd) tally_end<MASKQ, SITE>(tab, site, 0u, src, h, G, pl.s, pl.L, P.N, !pl.rev, pl.rev, min_bq);
     if (pl.pss_rev) tally_end<MASKQ, SITE>(tab, site, 1u, src, h, G, pl.s, pl.L, P.N, pl.rev, pl.rev, min_bq);
+    }
 }
 template <bool MASKQ = false, class Src, class Tab>
 __device__ __forceinline__ void tally_pss_record(const TallyParams &P, const Tab &tab, const Src &src,
@@ -327,11 +350,16 @@ __global__ void __launch_bounds__(256) tally_simple(const TallyParams P) {
         const uint32_t o0 = P.offs[r], o1 = P.offs[r + 1];
         GlobalBytes src{P.recs + o0};
         const RecHdr h = decode_hdr(src, o1 - o0);
-        Plan pl = make_plan<true, true>(P, src, h);
+        GappedPlan pl;   // (-I: substitution tables only; without it the anchors stay unset and unread)
+        if (P.gapped) pl = make_plan<true, false, true, true>(P, src, h);
+        else static_cast<Plan &>(pl) = make_plan<true, true>(P, src, h);
         if (!do_pss) pl.pss_fwd = pl.pss_rev = false;
         if (!do_kmer) pl.fk5 = pl.fk3 = false;
         if (pl.pss_fwd || pl.pss_rev) {
-            if (P.off_site) {   // -X: the in-context pair takes its adds straight in the counter block
+            if (P.gapped) {   // -I (never together with -X, -E or -H)
+                if (LDS_TABLE) tally_pss_record<true, false, true>(P, LdsTableRowMajor{dyn_lds, rows}, NoSite{}, src, h, pl);
+                else tally_pss_record<true, false, true>(P, GlobalTable{P.counters, P.off_rev}, NoSite{}, src, h, pl);
+            } else if (P.off_site) {   // -X: the in-context pair takes its adds straight in the counter block
                 const GlobalSite site{P.counters + P.off_site, rows * 16u};
                 if (LDS_TABLE) tally_pss_record<true, true>(P, LdsTableRowMajor{dyn_lds, rows}, site, src, h, pl);
                 else tally_pss_record<true, true>(P, GlobalTable{P.counters, P.off_rev}, site, src, h, pl);
@@ -428,7 +456,7 @@ __device__ __forceinline__ void stage_tile_dma(const uint8_t *recs, uint64_t rec
 // the kernel): a reference to the kernel's by-value copy would force that whole struct into
 // scratch memory.
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool MASKQ = false, bool REGIONS = false, bool HIST = false, bool SITE = false,
-          bool END = false>
+          bool END = false, bool GAPPED = false>
 __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyParams *kernarg, uint32_t o0,
                                                                     uint32_t o1, uint32_t *table, uint32_t *lds_kmer,
                                                                     uint32_t *hist_lds = nullptr, uint32_t *site_lds = nullptr,
@@ -436,8 +464,10 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyP
     const TallyParams &P = *kernarg;
     GlobalBytes gsrc{P.recs + o0};
     const RecHdr gh = decode_hdr(gsrc, o1 - o0);
-    const Plan gpl = make_plan<DO_PSS, DO_KMER, REGIONS>(P, gsrc, gh);
-    if constexpr (SITE) {
+    const auto gpl = make_plan<DO_PSS, DO_KMER, REGIONS, GAPPED>(P, gsrc, gh);   // (GAPPED: walks every CIGAR op)
+    if constexpr (GAPPED) {
+        if (gpl.pss_fwd || gpl.pss_rev) tally_pss_record<MASKQ, false, true>(P, LdsTableColumnMajor{table, P.row_base}, NoSite{}, gsrc, gh, gpl);
+    } else if constexpr (SITE) {
         if (gpl.pss_fwd || gpl.pss_rev)
             tally_pss_record<MASKQ, true>(P, LdsTableColumnMajor{table, P.row_base}, LdsSiteColumnMajor{site_lds, P.row_base}, gsrc, gh, gpl);
     } else if (DO_PSS && (gpl.pss_fwd || gpl.pss_rev)) tally_pss_record<MASKQ>(P, LdsTableColumnMajor{table, P.row_base}, gsrc, gh, gpl);
@@ -582,8 +612,15 @@ __device__ __forceinline__ uint32_t base_quality_mask(uint32_t x, uint32_t q4) {
 // exchange the result, and a lane whose PARTNER is marked sets CODE_END in all its sheet bytes: COLUMNS adds a real code
 // that carries it a second time, into the conditional tables `end_lds` behind the staging buffer ((N + 2) rows per code,
 // end_lds_bytes).  The left-end lanes count reads[4] with a ballot each.  The instantiations without END contain none of it.
+//
+// GAPPED (-I, P.gapped; one plane, substitution tables only, every pass): plan_head walks the CIGAR in the staged prefix (it lies in
+// front of SEQ; at most GAPPED_TILED_OPS ops, a record with more takes the one-lane path) and returns the read-side anchors.  The
+// reference side -- window, context bases, bounds, -T's interval [s, s + L) -- stays as it is; the read stream (and -Q's QUAL
+// stream) of a left lane starts at q0 - 2, that of a right lane ends at q1, and CODES-B blanks a lane's positions outside
+// [q0, q0 + a) / [q1 - b, q1) with the byte masks of the l_seq blanking, skipped wave-wide when no lane needs it.  The
+// instantiations without GAPPED contain none of it.
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS, PlaneSel PLANES = PLANES_NONE, bool MASKQ = false,
-          bool REGIONS = false, bool HIST = false, bool SITE = false, bool END = false>
+          bool REGIONS = false, bool HIST = false, bool SITE = false, bool END = false, bool GAPPED = false>
 __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const TallyParams *kernarg,
                                                  uint8_t *__restrict__ stage, uint8_t *__restrict__ sheet,
                                                  uint32_t *__restrict__ table,
@@ -600,6 +637,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
     constexpr bool KPLANES = GROUPED && DO_KMER;      // ... of k-mer bins (tally_tiled_kmer_planes: no sheet, no table)
     static_assert(!KPLANES || !DO_PSS, "planes split either the substitution tables or the k-mer tables");
     static_assert(!MASKQ || DO_PSS, "base qualities mask the substitution tables only");
+    static_assert(!GAPPED || (DO_PSS && !DO_KMER && PLANES == PLANES_NONE && !HIST && !SITE && !END), "anchored ends belong to the one-plane substitution tally without the length histogram, site context and the end condition");
     const uint32_t T = P.reads_per_tile;   // <= TILED_MAX_T
     const uint32_t n_recs = P.n_recs_dev ? *P.n_recs_dev : P.n_recs;   // device-indexed blocks: the count lives in device memory
     const uint32_t pieces = P.prefix_pieces;  // 16-byte pieces staged per record
@@ -698,8 +736,16 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         // everything the path reads ends at QUAL[0] (the -R filter and -G walk the aux fields: whole record;
         // a length bin needs nothing behind QUAL[0]; -Q reads QUAL to its end)
         const uint32_t needed = (PLANES == PLANES_RG || P.rg) ? o1 - o0 : MASKQ ? h.aux_off : h.qual_off + 1u;
-        const bool in_stage = hdr_ok && needed <= avail;
-        Plan pl = plan_head<DO_PSS, DO_KMER>(P, src, h, RefsLdsCached{refs_lds, P.ref_info, n_ref_cached, (uint32_t)P.n_ref});
+        // (-I: a CIGAR of more ops than a lane walks sends the record to the one-lane path)
+        bool in_stage = GAPPED ? hdr_ok && needed <= avail && h.n_cigar <= GAPPED_TILED_OPS : hdr_ok && needed <= avail;
+        auto pl = plan_head<DO_PSS, DO_KMER, true, GAPPED>(P, src, h, RefsLdsCached{refs_lds, P.ref_info, n_ref_cached, (uint32_t)P.n_ref},
+                                                           GAPPED && in_stage ? GAPPED_TILED_OPS : 0u);
+        if constexpr (GAPPED) {
+            // -I: a lane reads ONE run of read bases, the one at its own end.  A candidate with a gap whose other run begins
+            // inside this end's N positions (L - b < N on the left, L - a < N on the right: every I / D of the read lies within N
+            // reference bases of one end) has positions that are read through the other end's anchor: the one-lane path takes it.
+            if (pl.pss_cand && pl.a != pl.L && (pl.L - pl.b < (uint32_t)N || pl.L - pl.a < (uint32_t)N)) in_stage = false;
+        }
         if (!in_stage) { pl.status = RS_LIVE; pl.live = pl.pss_cand = pl.fk5 = pl.fk3 = false; }
         // this end's reference window, issued for every candidate before the -U/-D test so the
         // test costs no extra memory round trip
@@ -738,13 +784,18 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         // read bases of this end as a nibble stream aligned with the window bytes: stream nibble
         // b <-> read base n0 + b, n0 = -2 (left: bytes 0,1 are context, their nibbles are never
         // used) or L-30 (right).  20 bytes from SEQ as six aligned dwords, one batch.
-        const int32_t n0 = e ? (int32_t)pl.L - 30 - (int32_t)row_base : (int32_t)row_base - 2;
+        // (-I: the same two streams at the read-side anchors -- base q0 is the left end's position 0, base q1 - 1 the right end's)
+        int32_t n0 = e ? (int32_t)pl.L - 30 - (int32_t)row_base : (int32_t)row_base - 2;
+        if constexpr (GAPPED) n0 = e ? (int32_t)pl.q1 - 30 - (int32_t)row_base : (int32_t)pl.q0 - 2 + (int32_t)row_base;
+        // (-I: a right end whose read bases run out far in front of the window -- a long deletion -- has n0 below -32; all its
+        //  positions are blanked in CODES-B, so the two streams may start anywhere inside the record)
+        const int32_t n0c = GAPPED ? max(n0, -32) : n0;
         uint32_t rr[6];
 #pragma unroll
         for (int k = 0; k < 6; k++) rr[k] = 0u;
         uint32_t ssh = 0u;
         if (cand) {
-            const int32_t n0a = min(n0, (int32_t)h.l_seq);  // (past SEQ everything is blanked anyway: stay inside the record)
+            const int32_t n0a = min(n0c, (int32_t)h.l_seq);  // (past SEQ everything is blanked anyway: stay inside the record)
             const uint32_t sa = src.off + (uint32_t)((int32_t)h.seq_off + (n0a >> 1));  // arithmetic shift = floor
             const uint32_t *qs = (const uint32_t *)(stage + (sa & ~3u));
             ssh = sa & 3u;
@@ -761,7 +812,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
 #pragma unroll
             for (int k = 0; k < 9; k++) qq[k] = 0u;
             if (cand) {
-                const int32_t n0q = min(n0, (int32_t)h.l_seq);   // (at or past l_seq nothing is a read base: blanked in CODES-B)
+                const int32_t n0q = min(n0c, (int32_t)h.l_seq);   // (at or past l_seq nothing is a read base: blanked in CODES-B)
                 const uint32_t qa = src.off + (uint32_t)((int32_t)h.qual_off + n0q);
                 const uint32_t *qp = (const uint32_t *)(stage + (qa & ~3u));
                 qsh = qa & 3u;
@@ -788,6 +839,9 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         // -T: the two grid words, issued behind the window gathers (the descriptor has had their issue time to arrive)
         RegionQuery rq{};
         if constexpr (REGIONS) {
+            if constexpr (GAPPED) {
+                if (rcand) region_grid_load(P, h, rdesc, rq, pl.L);   // (a candidate's L is its reference span)
+            } else
             if (rcand) region_grid_load(P, h, rdesc, rq);
         }
         uint32_t kplane = 0u;   // k-mer planes: the record's plane, resolved by the pair's left-end lane
@@ -807,7 +861,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         if (in_tile && !in_stage && e == 0u) {
             if constexpr (KPLANES) ev_over = tally_overflow_record_kmer_planes<PLANES, LDS_KMER, REGIONS>(kernarg, gk, o0, o1, lds_kmer);
             else if constexpr (GROUPED) ev_over = tally_overflow_record_planes<PLANES, MASKQ, REGIONS>(kernarg, gk, o0, o1, table);
-            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS, HIST, SITE, END>(kernarg, o0, o1, table, lds_kmer, hist_lds, site_lds, end_lds);
+            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS, HIST, SITE, END, GAPPED>(kernarg, o0, o1, table, lds_kmer, hist_lds, site_lds, end_lds);
             if (pass0) atomicAdd(&lds_delta[ST_SLOW_PATH], 1);
         }
         // First use of the gathered registers happens HERE, before the next tile's DMA is issued:
@@ -923,6 +977,28 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
                 }
                 // bases at or beyond l_seq do not exist (precondition P3): blank them.  Rare (reads
                 // shorter than the window), so the whole wave skips it when no lane needs it.
+                if constexpr (GAPPED) {
+                    // -I: this lane's end keeps the read bases [q0, q0 + a) (left) or [q1 - b, q1) (right), and none at or
+                    // beyond l_seq (a record that does not anchor may lack them, as above): window bytes lo .. hi - 1.  Bytes
+                    // 0, 1 of a left lane and 30, 31 of a right lane of pass 0 are the context positions, set below.
+                    // (32-bit: a staged record's l_seq, clips and runs are a few thousand at most, a candidate's L below 2^28)
+                    const int32_t r_lo = e ? (int32_t)pl.q1 - (int32_t)pl.b : (int32_t)pl.q0;
+                    const int32_t r_hi = min(e ? (int32_t)pl.q1 : (int32_t)pl.q0 + (int32_t)pl.a, (int32_t)h.l_seq);
+                    const int32_t lo_s = r_lo - n0, hi_s = r_hi - n0;
+                    const uint32_t lo = lo_s <= 0 ? 0u : lo_s >= 32 ? 32u : (uint32_t)lo_s;
+                    const uint32_t hi = hi_s <= 0 ? 0u : hi_s >= 32 ? 32u : (uint32_t)hi_s;
+                    if (__any(hi < (e && pass0 ? 30u : 32u) || lo > (!e && pass0 ? 2u : 0u))) {
+#pragma unroll
+                        for (int m = 0; m < 4; m++) {
+                            // kept: bytes i of E[m] with lo <= 8m + 2i < hi, of O[m] with lo <= 8m + 2i + 1 < hi
+                            const uint32_t up = hi > 8u * m ? hi - 8u * m : 0u, dn = lo > 8u * m ? lo - 8u * m : 0u;
+                            const uint32_t ne = min((up + 1u) >> 1, 4u), no = min(up >> 1, 4u);
+                            const uint32_t le = min((dn + 1u) >> 1, 4u), lw = min(dn >> 1, 4u);
+                            RE[m] |= (ne >= 4u ? 0u : ~((1u << (8u * ne)) - 1u)) | (le >= 4u ? 0xFFFFFFFFu : (1u << (8u * le)) - 1u);
+                            RO[m] |= (no >= 4u ? 0u : ~((1u << (8u * no)) - 1u)) | (lw >= 4u ? 0xFFFFFFFFu : (1u << (8u * lw)) - 1u);
+                        }
+                    }
+                } else {
                 const int32_t have_s = (int32_t)h.l_seq - n0;
                 const uint32_t have = have_s <= 0 ? 0u : have_s >= 32 ? 32u : (uint32_t)have_s;
                 if (__any(have < (e && pass0 ? 30u : 32u))) {
@@ -934,6 +1010,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
                         RE[m] |= ne >= 4u ? 0u : ~((1u << (8u * ne)) - 1u);
                         RO[m] |= no >= 4u ? 0u : ~((1u << (8u * no)) - 1u);
                     }
+                }
                 }
                 // context positions carry no read base: their cell is the diagonal one of their own
                 // reference base (pss-bam.c:172-184).  Left: positions 0,1 = byte 0 of E[0], O[0];
@@ -1701,8 +1778,9 @@ __global__ void __launch_bounds__(256) reduce_partials(const TallyParams P, uint
 // HIST: dynamic LDS is the staging buffer and, behind it, the 2 * P.hist_lds_bins words of the length histogram
 // SITE: one more static object, the 2 KiB in-context table
 // END: behind the staging buffer the conditional tables and reads[4], end_lds_bytes(N + 2) (never together with HIST)
+// GAPPED: nothing more in LDS (the CIGAR walk reads the staged prefix)
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS = false, bool MASKQ = false, bool REGIONS = false, bool HIST = false,
-          bool SITE = false, bool END = false>
+          bool SITE = false, bool END = false, bool GAPPED = false>
 __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
@@ -1723,8 +1801,8 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P
         tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, false, true>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
                                                                                                              lds_delta, refs_lds, nullptr, nullptr, hist_lds, nullptr, end_lds);
     } else
-    tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
-                                                                                            lds_delta, refs_lds, nullptr, nullptr, hist_lds);
+    tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, false, false, GAPPED>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
+                                                                                                                  lds_delta, refs_lds, nullptr, nullptr, hist_lds);
 }
 
 // ---------------------------------------------------------------------------------------

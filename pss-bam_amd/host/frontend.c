@@ -34,6 +34,7 @@ int frontend_min_base_quality = 0;
 int frontend_length_hist = 0;
 int frontend_site_context = PSSBAM_SITE_NONE;
 int frontend_end_depth = 0, frontend_end_cell5 = 0, frontend_end_cell3 = 0;
+int frontend_gapped_reads = 0;
 const pss_regions *frontend_regions = NULL;
 uint32_t frontend_length_edges[PSSBAM_MAX_LENGTH_BINS - 1];
 const frontend_contig_map *frontend_contig_sets = NULL;
@@ -74,6 +75,7 @@ static struct early_feed {
     int hist;                       /* -H: the limit of the length histogram, set on every engine after create */
     int site;                       /* -X: the site context, set on every engine after create */
     int end_depth, end_cell5, end_cell3; /* -E: the end condition, set on every engine after create */
+    int gapped;                     /* -I: anchored ends, set on every engine after create */
     const pss_regions *regions;     /* -T: the intervals, set on every engine after create */
     int n_edges;                    /* -S: the length bin edges, set on every engine after create */
     uint32_t edges[PSSBAM_MAX_LENGTH_BINS - 1];
@@ -154,7 +156,8 @@ static void *engine_make_main(void *arg)
         (EF.min_bq > 0 && pssbam_engine_set_min_base_quality(*j->out, EF.min_bq)) ||
         (EF.hist > 0 && pssbam_engine_set_length_histogram(*j->out, EF.hist)) ||
         (EF.site != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(*j->out, EF.site)) ||
-        (EF.end_depth > 0 && pssbam_engine_set_end_condition(*j->out, EF.end_depth, EF.end_cell5, EF.end_cell3)) || send_regions(*j->out, EF.regions) ||
+        (EF.end_depth > 0 && pssbam_engine_set_end_condition(*j->out, EF.end_depth, EF.end_cell5, EF.end_cell3)) ||
+        (EF.gapped && pssbam_engine_set_gapped_reads(*j->out, 1)) || send_regions(*j->out, EF.regions) ||
         (EF.n_rg > 0 && pssbam_engine_set_read_groups(*j->out, EF.n_rg, (const char *const *)EF.rg_ids)) ||
         (EF.n_edges > 0 && pssbam_engine_set_length_bins(*j->out, EF.n_edges, EF.edges)) || send_contig_sets(*j->out, EF.sets)) {
         j->rc = 1;
@@ -287,6 +290,7 @@ void frontend_warmup_start(const pssbam_config *cfg, const char *aln_path, const
             EF.end_depth = frontend_end_depth;
             EF.end_cell5 = frontend_end_cell5;
             EF.end_cell3 = frontend_end_cell3;
+            EF.gapped = frontend_gapped_reads;
             EF.regions = frontend_regions;
             memcpy(EF.edges, frontend_length_edges, sizeof EF.edges);
             EF.sets = frontend_contig_sets;
@@ -309,7 +313,7 @@ static int same_length_bins(void)
     return EF.n_edges == frontend_n_length_edges && EF.sets == frontend_contig_sets && EF.min_bq == frontend_min_base_quality &&
            EF.hist == frontend_length_hist && EF.site == frontend_site_context &&
            EF.end_depth == frontend_end_depth && EF.end_cell5 == frontend_end_cell5 && EF.end_cell3 == frontend_end_cell3 &&
-           EF.regions == frontend_regions &&
+           EF.gapped == frontend_gapped_reads && EF.regions == frontend_regions &&
            memcmp(EF.edges, frontend_length_edges, (size_t)frontend_n_length_edges * sizeof *EF.edges) == 0;
 }
 
@@ -646,6 +650,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
                 (frontend_length_hist > 0 && pssbam_engine_set_length_histogram(eng[g], frontend_length_hist)) ||
                 (frontend_site_context != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(eng[g], frontend_site_context)) ||
                 (frontend_end_depth > 0 && pssbam_engine_set_end_condition(eng[g], frontend_end_depth, frontend_end_cell5, frontend_end_cell3)) ||
+                (frontend_gapped_reads && pssbam_engine_set_gapped_reads(eng[g], 1)) ||
                 send_regions(eng[g], frontend_regions) ||
                 (frontend_n_length_edges > 0 && pssbam_engine_set_length_bins(eng[g], frontend_n_length_edges, frontend_length_edges)) ||
                 send_contig_sets(eng[g], frontend_contig_sets)) {

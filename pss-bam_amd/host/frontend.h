@@ -55,6 +55,9 @@ extern int frontend_site_context;
  * (pssbam_engine_set_end_condition) and run_tally() returns the conditional pair and reads[4].  Set before
  * frontend_warmup_start. */
 extern int frontend_end_depth, frontend_end_cell5, frontend_end_cell3;
+/* pss-bam -I: non-zero = every engine tallies clipped and gapped reads by their anchored ends
+ * (pssbam_engine_set_gapped_reads).  Set before frontend_warmup_start(). */
+extern int frontend_gapped_reads;
 
 /* -T: the intervals of the BED file (regions.h; NULL: none); every engine gets them (pssbam_engine_set_regions), on
  * every input path -- the filter lives in the engine.  Set before frontend_warmup_start. */

@@ -36,6 +36,10 @@
  * over those that carry a C->T within the first d positions of their 5' end -- what this command writes for the input
  * reduced to those reads -- and <prefix>.cond.pss.reads.txt with the four read counts, from the same pass; the other
  * files stay as they are.  Needs -r <= 30.  Not with -G, -S, -C, -H or -X.
+ * Added: -I also tallies the reads whose CIGAR is not <len>M but still anchors both ends: optional hard and soft clips around a
+ * core of M I D = X ops that starts and ends with a match-type op.  The two files are what this command writes without -I for
+ * the input in which each such read is the record <span>M (span = the reference length of the core) whose SEQ / QUAL keep the
+ * match-type run at either end of the core, with N / ! in between.  Not with -G, -S, -C, -H, -X or -E.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -61,13 +65,13 @@ int main(int argc, char *argv[])
     const double age_main = frontend_process_age_s();
     frontend_detach_start();   /* the caller gets its prompt back when the reports are written, not when 30 GB of device buffers are gone */
     const double t_main = frontend_now_s();
-    int region_len = 15, min_mq = 0, merged_only = 0, by_group = 0, option;
+    int region_len = 15, min_mq = 0, merged_only = 0, by_group = 0, gapped = 0, option;
     unsigned long min_read_len = 0, max_read_len = 250000000;
     const char *up_ctx = "ACGT", *down_ctx = "ACGT";
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL, *read_group = NULL;
     const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL, *bed_fn = NULL, *hist_arg = NULL, *site_arg = NULL, *end_arg = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:I")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -87,6 +91,7 @@ int main(int argc, char *argv[])
         case 'H': hist_arg = optarg; break;
         case 'X': site_arg = optarg; break;
         case 'E': end_arg = optarg; break;
+        case 'I': gapped = 1; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -116,7 +121,8 @@ int main(int argc, char *argv[])
               "-U <upstream context base filter; first base before alignment must be one of these (default: ACGT)>\n"
               "-D <downstream context base filter; first base before alignment must be one of these (default: ACGT)>\n"
               "-m <only consider merged reads>\n"
-              "-E <ss|ds>[,<d>] <also write the tables of each end over the reads damaged within d bases (default: 1) of the other end>\n",
+              "-E <ss|ds>[,<d>] <also write the tables of each end over the reads damaged within d bases (default: 1) of the other end>\n"
+              "-I <also tally clipped and gapped reads, by the matched runs at their two ends>\n",
               stderr);
         exit(1);
     }
@@ -193,6 +199,12 @@ int main(int argc, char *argv[])
             exit(1);
         }
     }
+    if (gapped && (by_group || len_edges || ctg_map || hist_arg || site_arg || end_arg)) {
+        fprintf(stderr, "-I (clipped and gapped reads by their anchored ends) and %s exclude each other.\n",
+                by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)" : ctg_map ? "-C (tables per contig set)"
+                : hist_arg ? "-H (fragment-length histogram)" : site_arg ? "-X (tables per site context)" : "-E (tables conditional on the other end)");
+        exit(1);
+    }
     pss_regions bed;
     memset(&bed, 0, sizeof bed);
     if (bed_fn) {
@@ -249,6 +261,7 @@ int main(int argc, char *argv[])
     if (hist_arg) fprintf(stderr, " -H %d", hist_max);
     if (site_arg) fprintf(stderr, " -X %s", site_arg);
     if (end_arg) fprintf(stderr, " -E %s", end_arg);
+    if (gapped) fprintf(stderr, " -I");
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -276,6 +289,7 @@ int main(int argc, char *argv[])
     frontend_end_depth = end_depth;
     frontend_end_cell5 = end_cell5;
     frontend_end_cell3 = end_cell3;
+    frontend_gapped_reads = gapped;
     if (bed_fn) frontend_regions = &bed;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
