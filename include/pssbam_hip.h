@@ -250,6 +250,36 @@ int pssbam_engine_set_length_bins(pssbam_engine *e, int32_t n_edges, const uint3
 int pssbam_engine_set_contig_sets(pssbam_engine *e, int32_t n_sets, int64_t n_names, const char *const *names,
                                   const int32_t *set_of);
 
+/* Per-contig tables (pss-bam -A): every reference sequence's own pair of substitution tables in a single pass over the
+ * records, for any number of references (a metagenomic BAM has 10^4 .. 10^6), without a map file.  Plane k belongs to
+ * refID k, k in 0..n_ref-1 of the table pssbam_engine_set_references gives, and plane n_ref to the refID -1 records
+ * (RNAME "*"); plane k receives exactly what the ordinary tables receive from the records whose refID is k, so for a
+ * header of distinct names it equals pssbam_engine_set_contig_sets with the one set {name k} and the reference run with
+ * a FASTA that holds only contig k.  Two refIDs that carry the same name keep separate planes.  The totals
+ * (pssbam_engine_finish, the sum of all planes) and the status counters are those of the engine without the setting.
+ * The counter block is [fwd | rev | stats | fwd_0 | rev_0 | ... | fwd_nref | rev_nref | touched_0 .. touched_nref]:
+ * the leading pair stays zero, plane k lies (k * 2 * (region_len + 2) * 16) words behind the stats -- 64-bit offsets --
+ * and touched_k is non-zero exactly when plane k holds a non-zero word, so a reader of the block need not walk empty
+ * planes; the block still sums across engines as one u64 array.  pssbam_engine_finish_groups(e, k, ...) returns plane
+ * k.  The block is sized when the reference count is known: at pssbam_engine_set_references, or from
+ * pssbam_engine_feed_open's n_ref; a later set_references with another count re-sizes it (once records have been
+ * tallied the count may only grow -- the SAM-text reader -- and the planes keep their contents).  PSSBAM_ENOMEM when
+ * (n_ref + 1) * 2 * (region_len + 2) * 16 words do not fit the device's free memory.  on == 0 switches the setting off:
+ * the engine then launches exactly the kernels it launches without it.  Legal after create (or reset) and before the
+ * first tally launch (after pssbam_engine_feed_open: before set_references); goes with cfg.read_group, a minimum base
+ * quality and regions.  PSSBAM_EINVAL with PSSBAM_TALLY_KMER in the mask and with read groups, length bins, contig sets,
+ * a length histogram, site context, an end condition or gapped reads set (those setters return PSSBAM_EINVAL once this
+ * one is on); PSSBAM_ESTATE once records have been tallied or the counter block has been bound, and from
+ * set_references when a bound block would have to change size.  The setting survives pssbam_engine_reset. */
+int pssbam_engine_set_per_contig(pssbam_engine *e, int32_t on);
+
+/* Planes first_ref .. first_ref + n - 1 of a per-contig engine (plane n_ref: refID -1), drained like
+ * pssbam_engine_finish: fwd and rev take n * (region_len + 2) * 16 words each, touched[i] = 1 when plane first_ref + i
+ * holds a non-zero word (an untouched plane is returned as zeros and is not read back from the device).  Any pointer
+ * may be NULL.  PSSBAM_ESTATE without pssbam_engine_set_per_contig, PSSBAM_EINVAL for a range outside 0..n_ref. */
+int pssbam_engine_finish_contigs(pssbam_engine *e, int32_t first_ref, int32_t n, unsigned long *fwd, unsigned long *rev,
+                                 uint8_t *touched);
+
 /* Minimum base quality (pss-bam -Q): read bases whose quality is below q are left out of the substitution tables,
  * as the tools that estimate damage from such tables do (a sequencing error at a Q2-Q15 base is no substitution).
  * q is a Phred value -- the BAM QUAL byte, the SAM character - 33 -- in 0..PSSBAM_MAX_BASE_QUALITY; 0 switches

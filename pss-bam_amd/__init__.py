@@ -45,6 +45,7 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_regions", "pssbam_engine_set_length_histogram", "pssbam_engine_finish_length_histogram",
     "pssbam_engine_set_site_context", "pssbam_engine_finish_site_context",
     "pssbam_engine_set_end_condition", "pssbam_engine_finish_end_condition", "pssbam_engine_set_gapped_reads",
+    "pssbam_engine_set_per_contig", "pssbam_engine_finish_contigs",
 ]
 MAX_READ_GROUPS = 4096
 MAX_LENGTH_BINS = 64
@@ -129,6 +130,8 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_set_end_condition.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     L.pssbam_engine_finish_end_condition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_gapped_reads.argtypes = [C.c_void_p, C.c_int32]
+    L.pssbam_engine_set_per_contig.argtypes = [C.c_void_p, C.c_int32]
+    L.pssbam_engine_finish_contigs.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_regions.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_counters_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.pssbam_engine_bind_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -209,6 +212,7 @@ class Engine:
     `end_condition` = (depth, cell5, cell3) (pss-bam -E): a second pair of tables over the unpaired reads whose other end
     carries the given cell within its first `depth` positions, see set_end_condition; None = off.
     `gapped` = True (pss-bam -I): clipped and gapped reads are tallied by their anchored ends, see set_gapped.
+    `per_contig` = True (pss-bam -A): every BAM reference's own pair of substitution tables, see set_per_contig.
     With `kmer` alone (no `pss`) the three split the k-mer tables instead (fragkon -G / -S / -C): every plane is a
     k5 / k3 pair, and the length bins go by the SEQ length and kmer's min_read_len / max_read_len."""
 
@@ -216,7 +220,7 @@ class Engine:
                  kernel: int = KERNEL_AUTO, device: int = -1, read_groups: list[str] | None = None,
                  length_bins: list[int] | None = None, contig_sets=None, min_base_qual: int = 0,
                  length_hist: int = 0, site_context: str | None = None, end_condition: tuple[int, int, int] | None = None,
-                 gapped: bool = False):
+                 gapped: bool = False, per_contig: bool = False):
         L = hip_lib()
         cfg = _Config()
         cfg.abi_version = 1
@@ -265,6 +269,10 @@ class Engine:
         self._gapped = False
         if gapped:
             self.set_gapped(True)
+        self._per_contig = False
+        self._n_ref: int | None = None   # the reference count the engine has been told (set_references, feed_open)
+        if per_contig:
+            self.set_per_contig(True)
         if read_groups is not None:
             self.set_read_groups(read_groups)
         if length_bins is not None:
@@ -370,6 +378,42 @@ class Engine:
     def gapped(self) -> bool:
         """whether clipped and gapped reads are tallied by their anchored ends"""
         return self._gapped
+
+    def set_per_contig(self, on: bool = True):
+        """pss-bam -A: plane k of the counter block takes the records whose refID is k (k = 0 .. n_ref - 1 of
+        set_references; plane n_ref: refID -1) -- what the ordinary tables receive from them, so the tables of a run
+        on the genome reduced to that contig -- for any number of references, in one pass.  finish() stays the total,
+        finish_contigs() returns the planes.  Goes with read_group, min_base_qual and regions; not with kmer, read
+        groups, length bins, contig sets, the length histogram, site context, the end condition or gapped reads.
+        Before the first tally (after feed_open: before set_references) and before bind_counters: the block is sized
+        for n_ref + 1 planes when the reference count is known.  Survives reset."""
+        _chk(self._L.pssbam_engine_set_per_contig(self._h, int(bool(on))))
+        self._per_contig = bool(on)
+
+    @property
+    def per_contig(self) -> bool:
+        """whether every BAM reference has its own pair of tables"""
+        return self._per_contig
+
+    def finish_contigs(self, first: int = 0, n: int | None = None) -> dict:
+        """{refID: Tables} of the planes among first .. first + n - 1 (default: all) that hold something; the refID -1
+        records are under key n_ref (drains like finish).  Only the touched planes are read back from the device."""
+        if n is None:
+            n = (self._n_ref or 0) + 1 - first
+        cells = (self.region_len + 2) * 16
+        touched = np.zeros(max(n, 1), dtype=np.uint8)
+        _chk(self._L.pssbam_engine_finish_contigs(self._h, first, n, None, None, touched.ctypes.data))
+        out = {}
+        hit = np.flatnonzero(touched[:n])
+        # runs of touched neighbours, one call each
+        for run in np.split(hit, np.flatnonzero(np.diff(hit) != 1) + 1) if hit.size else []:
+            fwd = np.zeros((run.size, self.region_len + 2, 16), dtype=np.uint64)
+            rev = np.zeros_like(fwd)
+            assert fwd.size == run.size * cells
+            _chk(self._L.pssbam_engine_finish_contigs(self._h, first + int(run[0]), int(run.size), fwd.ctypes.data, rev.ctypes.data, None))
+            for i, k in enumerate(run):
+                out[first + int(k)] = Tables(fwd[i], rev[i], None, None, {})
+        return out
 
     def set_regions(self, names, name_of, starts, ends):
         """pss-bam -T / fragkon -T: only records whose alignment overlaps one of the intervals are tallied -- the tables
@@ -487,6 +531,7 @@ class Engine:
         n = len(names)
         arr = (C.c_char_p * max(n, 1))(*[s.encode() for s in names])
         _chk(self._L.pssbam_engine_set_references(self._h, n, arr))
+        self._n_ref = n
 
     def submit(self, records: np.ndarray, offsets: np.ndarray | None = None):
         records = np.ascontiguousarray(records, dtype=np.uint8)
@@ -523,6 +568,8 @@ class Engine:
         """compressed blocks may be fed before set_genome / set_references; their tallies follow then"""
         self._L.pssbam_engine_feed_open.argtypes = [C.c_void_p, C.c_int32, C.c_uint64]
         _chk(self._L.pssbam_engine_feed_open(self._h, n_ref, genome_bytes_hint))
+        if self._n_ref is None:
+            self._n_ref = n_ref
 
     def submit_bgzf(self, bgzf: np.ndarray, header_bytes: int = 0, max_batch_inflated: int = 1 << 30, on_busy=None) -> int:
         """Whole BGZF blocks (host bytes) through the device-side feed: inflate, CRC, record index and
@@ -643,6 +690,11 @@ class Engine:
         lay["contig_sets"] = [{"label": s, "fwd": base + k * 2 * rows * 16, "rev": base + k * 2 * rows * 16 + rows * 16}
                               for k, s in enumerate(self.contig_sets)]
         lay["n_u64"] = base + (len(self.read_groups) + len(self.length_bins) + len(self.contig_sets)) * 2 * rows * 16
+        if self._per_contig:   # a plane per reference (never together with the other planes): plane k = refID k, k = n_ref: refID -1
+            n_planes = 0 if self._n_ref is None else self._n_ref + 1   # (the block is sized once the count is known)
+            lay["contigs"] = {"first": base, "plane_words": 2 * rows * 16, "n_planes": n_planes,
+                              "touched": base + n_planes * 2 * rows * 16}
+            lay["n_u64"] = base + n_planes * (2 * rows * 16 + 1)
         if self._length_hist:   # the length histogram (never together with planes): hf | hr behind the stats
             lay["hist_fwd"], lay["hist_rev"] = base, base + self._length_hist + 2
             lay["n_u64"] = base + 2 * (self._length_hist + 2)

@@ -789,6 +789,8 @@ extern "C" int pssbam_engine_feed_open(pssbam_engine *e, int32_t n_ref, uint64_t
     if (!e || n_ref < 0) return fail(PSSBAM_EINVAL, "bad argument");
     if (e->cfg.kernel == PSSBAM_KERNEL_SIMPLE) return fail(PSSBAM_EINVAL, "device-indexed blocks need the tiled kernels");
     HIP_TRY(hipSetDevice(e->device));
+    if (e->per_contig && !e->have_refs)   // -A: the header's reference count sizes the planes
+        if (const int rc = size_per_contig(e, n_ref)) return rc;
     e->feed_opened = true;
     e->feed_n_ref = n_ref;
     size_t free_b = 0, total_b = 0;

@@ -212,6 +212,12 @@ struct pssbam_engine {
     std::vector<uint32_t> len_edges;   // -S
     std::unordered_map<std::string, uint32_t> ctg_plane;   // -C: contig name -> 1 + set, packed into ref_info[].w
     std::vector<std::string> ref_names;   // the names of the last set_references (-C set after it packs them again)
+    // -A (pssbam_engine_set_per_contig): planes == PLANES_EACH, n_planes = n_ref + 1 once the reference count is known (plane k
+    // = refID k at off_groups + k * plane_words, the last one refID -1), and behind the planes one touched word per plane
+    bool per_contig = false;
+    uint64_t off_touched = 0;
+    int env_contig_slots = 0;   // PSSBAM_CONTIG_SLOTS: LDS planes a workgroup of the -A kernel holds (tests: down to 1)
+    bool contig_evict = true;   // PSSBAM_CONTIG_EVICT=0: the -A kernel empties its slots at a miss only (A/B runs)
     bool tallied = false;   // a tally launch since create / reset
     uint32_t min_bq = 0;    // -Q: read bases with a QUAL byte below this are left out of the tables (pssbam_engine_set_min_base_quality)
     // -H (pssbam_engine_set_length_histogram): hf | hr, hist_max + 2 words each, at off_hist = the end of the block as it is without them
@@ -422,6 +428,8 @@ extern "C" int pssbam_engine_create(const pssbam_config *cfg, pssbam_engine **ou
     e->env_grid_wgs = env_int("PSSBAM_GRID_WGS");
     e->env_pieces = env_int("PSSBAM_PIECES");
     e->env_group_slots = env_int("PSSBAM_GROUP_SLOTS");
+    e->env_contig_slots = env_int("PSSBAM_CONTIG_SLOTS");
+    if (getenv("PSSBAM_CONTIG_EVICT")) e->contig_evict = env_int("PSSBAM_CONTIG_EVICT") != 0;
     if (getenv("PSSBAM_HIST_LDS_BINS")) e->env_hist_lds_bins = std::max(env_int("PSSBAM_HIST_LDS_BINS"), 0);
     if (const int g = env_int("PSSBAM_REGION_GRID_SHIFT")) e->region_shift = (uint32_t)std::min(std::max(g, 2), 20);
     if (getenv("PSSBAM_COMPACT")) e->use_compact = env_int("PSSBAM_COMPACT") != 0;
@@ -761,6 +769,8 @@ extern "C" int pssbam_engine_set_regions(pssbam_engine *e, int32_t n_names, cons
     return e->have_refs ? pack_regions(e, true) : PSSBAM_OK;   // (otherwise set_references packs the table when it comes)
 }
 
+static int size_per_contig(pssbam_engine *e, int32_t n_ref);
+
 extern "C" int pssbam_engine_set_references(pssbam_engine *e, int32_t n_ref, const char *const *names) {
     if (!e || n_ref < 0 || (n_ref && !names)) return fail(PSSBAM_EINVAL, "bad argument");
     if (!e->d_genome) return fail(PSSBAM_ESTATE, "set_genome must precede set_references");
@@ -789,9 +799,12 @@ extern "C" int pssbam_engine_set_references(pssbam_engine *e, int32_t n_ref, con
         }
     }
     fill((size_t)n_ref, e->star_contig, "*");
-    e->ref_names.assign(names, names + n_ref);   // for a pssbam_engine_set_contig_sets / _set_regions after this call
+    // what can refuse the call comes before anything of the engine changes
     if (e->feed_opened && !e->deferred.empty() && n_ref != e->feed_n_ref)
         return fail(PSSBAM_ESTATE, "pssbam_engine_feed_open announced %d references, set_references brings %d", e->feed_n_ref, n_ref);
+    if (e->per_contig)   // -A: a plane per reference (and one for "*")
+        if (const int rc = size_per_contig(e, n_ref)) return rc;
+    e->ref_names.assign(names, names + n_ref);   // for a pssbam_engine_set_contig_sets / _set_regions after this call
     // a table that is being REPLACED (SAM text: the list grows as new RNAMEs show up) may still be read by queued
     // kernels; the first one cannot be, so nothing waits for the engine's stream then
     if (e->d_ref_info) {
@@ -1082,7 +1095,9 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         const bool lds_tab = do_pss && tab_bytes <= 60u * 1024u;
         uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n_records + 255) / 256, (uint64_t)e->n_cu * 8);
         if (e->env_simple_blocks > 0) blocks = (uint32_t)e->env_simple_blocks;
-        if (e->planes != PLANES_NONE)
+        if (e->planes == PLANES_EACH)   // -A: straight into every reference's plane
+            hipLaunchKernelGGL(tally_simple_planes<PLANES_EACH>, dim3(blocks), dim3(256), 0, e->stream, P, G);
+        else if (e->planes != PLANES_NONE)
             with_planes(e->planes, [&](auto SEL) {
                 if (do_pss) hipLaunchKernelGGL(tally_simple_planes<SEL()>, dim3(blocks), dim3(256), 0, e->stream, P, G);
                 else hipLaunchKernelGGL(tally_simple_kmer_planes<SEL()>, dim3(blocks), dim3(256), 0, e->stream, P, G);
@@ -1148,7 +1163,25 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         const uint32_t lds = tiled_lds_bytes(T, pieces);
         int rc = PSSBAM_OK;
         P.row_base = 0;
-        if (e->planes != PLANES_NONE) {
+        if (e->planes == PLANES_EACH) {
+            // -A: one launch per 32-row pass whatever the number of references.  A workgroup holds `slots` planes (4 KiB each)
+            // and the trash plane behind the staging buffer; the planes leave LDS straight into the counter block, so a
+            // workgroup's scratch slot is the status deltas alone and reduce_partials_grouped walks nothing else.
+            uint32_t slots = e->env_contig_slots > 0 ? (uint32_t)e->env_contig_slots : EACH_DEFAULT_SLOTS;
+            const uint32_t fit = lds + 2u * GROUP_PLANE_WORDS * 4u <= GROUPED_LDS_BUDGET ? (GROUPED_LDS_BUDGET - lds) / (GROUP_PLANE_WORDS * 4u) - 1u : 1u;
+            slots = std::max(1u, std::min({slots, fit, EACH_MAX_SLOTS, G.n_groups}));
+            G.plane0 = 0;
+            G.each_evict = e->contig_evict ? 1u : 0u;
+            G.n_slots = slots;
+            G.scratch_words = GROUP_SCRATCH_DELTA;
+            for (uint32_t pass = 0; pass < n_passes && rc == PSSBAM_OK; pass++) {
+                P.row_base = pass * TILED_ROWS;
+                rc = with_flags([&](auto LATER, auto MASKQ, auto REGIONS) {
+                    return launch_with_reduce(e, tally_tiled_planes<PLANES_EACH, LATER(), MASKQ(), REGIONS()>, reduce_partials_grouped, G.scratch_words,
+                                              tiled_grouped_lds_bytes(T, pieces, slots), n_tiles, P, std::tie(G));
+                }, pass > 0, maskq, regions);
+            }
+        } else if (e->planes != PLANES_NONE) {
             // -G / -S / -C: every (32-row pass, plane pass) pair is one launch over the block.  A plane pass holds as many
             // planes as fit the LDS beside the staging buffer, plus a trash plane; more planes take more passes, each
             // re-reading the records.  Substitution planes are 4 KiB each (8 = 32 KiB always fit: one pass for up to 7 groups
@@ -1391,14 +1424,48 @@ extern "C" int pssbam_engine_sync(pssbam_engine *e) {
     return PSSBAM_OK;
 }
 
+// -A: f(plane, words) for every touched plane among first .. first + n - 1, its 2 * rows * 16 words on the host.  The touched
+// words are read first and the planes copied in runs of touched neighbours, so a block of 10^6 planes of which a few
+// hundred hold something costs a few hundred small copies.  (The stream is quiet: the caller has synced.)
+template <class F>
+static int for_touched_planes(pssbam_engine *e, uint32_t first, uint32_t n, F f) {
+    if (!n) return PSSBAM_OK;
+    std::vector<unsigned long long> flag(n), buf;
+    HIP_TRY(hipMemcpy(flag.data(), e->d_counters + e->off_touched + first, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    const uint32_t max_run = std::max<uint32_t>(1u, (8u << 20) / e->plane_words);   // at most 64 MiB a copy
+    for (uint32_t i = 0; i < n;) {
+        if (!flag[i]) { i++; continue; }
+        uint32_t j = i + 1;
+        while (j < n && flag[j] && j - i < max_run) j++;
+        buf.resize((size_t)(j - i) * e->plane_words);
+        HIP_TRY(hipMemcpy(buf.data(), e->d_counters + e->off_groups + (uint64_t)(first + i) * e->plane_words, buf.size() * sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost));
+        for (uint32_t k = i; k < j; k++) f(first + k, buf.data() + (size_t)(k - i) * e->plane_words);
+        i = j;
+    }
+    return PSSBAM_OK;
+}
+
 extern "C" int pssbam_engine_finish(pssbam_engine *e, unsigned long *fwd, unsigned long *rev, uint64_t *k5,
                                     uint64_t *k3, uint64_t stats[PSSBAM_ST_N]) {
     int rc = pssbam_engine_sync(e);
     if (rc) return rc;
-    std::vector<unsigned long long> h(e->n_counters);
-    HIP_TRY(hipMemcpy(h.data(), e->d_counters, e->n_counters * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     static_assert(sizeof(unsigned long) == 8, "LP64 expected");
     const size_t tab = (size_t)e->rows * 16;
+    if (e->per_contig) {   // -A: the totals are the sum of the touched planes; the rest of the block is not read back
+        std::vector<unsigned long long> h(e->off_groups), sum(2 * tab, 0ull);
+        HIP_TRY(hipMemcpy(h.data(), e->d_counters, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        rc = for_touched_planes(e, 0, e->n_planes, [&](uint32_t, const unsigned long long *p) {
+            for (size_t i = 0; i < 2 * tab; i++) sum[i] += p[i];
+        });
+        if (rc) return rc;
+        if (fwd) for (size_t i = 0; i < tab; i++) fwd[i] = (unsigned long)(h[i] + sum[i]);
+        if (rev) for (size_t i = 0; i < tab; i++) rev[i] = (unsigned long)(h[e->off_rev + i] + sum[tab + i]);
+        if (stats) for (int i = 0; i < PSSBAM_ST_N; i++) stats[i] = h[e->off_stats + i];
+        return PSSBAM_OK;
+    }
+    std::vector<unsigned long long> h(e->n_counters);
+    HIP_TRY(hipMemcpy(h.data(), e->d_counters, e->n_counters * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     // -G / -S: the totals are every plane's sum (plane 0, the unassigned bucket, sits where an ungrouped engine keeps its tables)
     for (size_t g = 0; g < e->n_planes; g++)
         for (size_t i = 0; i < 2 * tab; i++) h[i] += h[e->off_groups + g * e->plane_words + i];
@@ -1417,7 +1484,7 @@ extern "C" int pssbam_engine_finish_groups(pssbam_engine *e, int32_t group, unsi
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
     if (e->cfg.tally_mask == PSSBAM_TALLY_KMER) return fail(PSSBAM_EINVAL, "a k-mer engine's planes are read with pssbam_engine_finish_kmer_groups");
     const int32_t n_planes = (int32_t)e->n_planes;
-    if (!n_planes) return fail(PSSBAM_ESTATE, "none of pssbam_engine_set_read_groups / _set_length_bins / _set_contig_sets has been called");
+    if (!n_planes) return fail(PSSBAM_ESTATE, "none of pssbam_engine_set_read_groups / _set_length_bins / _set_contig_sets / _set_per_contig has been called");
     if (group < -1 || group >= n_planes) return fail(PSSBAM_EINVAL, "group %d outside -1..%d", group, n_planes - 1);
     int rc = pssbam_engine_sync(e);
     if (rc) return rc;
@@ -1467,6 +1534,7 @@ static int grow_counters(pssbam_engine *e, uint64_t n_counters) {
 // What set_read_groups, set_length_bins and set_contig_sets share: the counter block grows to n_planes [fwd | rev] planes
 // (a k-mer engine: [k5 | k3]) behind the stats.  `what` names the caller's planes in the messages.
 static int set_planes(pssbam_engine *e, PlaneSel sel, uint32_t n_planes, const char *what) {
+    if (e->per_contig) return fail(PSSBAM_EINVAL, "%s and per-contig tables exclude each other", what);
     if (e->hist_max) return fail(PSSBAM_EINVAL, "%s and the length histogram exclude each other", what);
     if (e->site_mode) return fail(PSSBAM_EINVAL, "%s and site context exclude each other", what);
     if (e->end_depth) return fail(PSSBAM_EINVAL, "%s and the end condition exclude each other", what);
@@ -1732,6 +1800,108 @@ extern "C" int pssbam_engine_set_contig_sets(pssbam_engine *e, int32_t n_sets, i
     std::vector<const char *> ptrs(refs.size());
     for (size_t i = 0; i < refs.size(); i++) ptrs[i] = refs[i].c_str();
     return pssbam_engine_set_references(e, e->n_ref, ptrs.data());
+}
+
+// -A: the counter block for n_ref references: [fwd | rev | stats | n_ref + 1 planes | n_ref + 1 touched words].  Before the first
+// tally the block is simply made anew.  Afterwards (SAM text: set_references comes again as new RNAMEs show up) the block
+// grows in place of the old one: planes 0 .. old n_ref - 1 keep their offsets, the "*" plane and the touched words move.
+static int size_per_contig(pssbam_engine *e, int32_t n_ref) {
+    const uint32_t n_planes = (uint32_t)n_ref + 1u, old_planes = e->n_planes;
+    if (n_planes == old_planes) return PSSBAM_OK;
+    if (e->d_counters != e->d_counters_own)
+        return fail(PSSBAM_ESTATE, "a caller-bound counter block cannot grow: per-contig tables for %d references need another size than it has", n_ref);
+    if (e->tallied && n_planes < old_planes) return fail(PSSBAM_ESTATE, "records have been tallied already: the reference list can only grow");
+    HIP_TRY(hipSetDevice(e->device));
+    const uint64_t plane_span = (uint64_t)n_planes * e->plane_words;   // (n_ref + 1) * 2 * (region_len + 2) * 16
+    const uint64_t n_counters = (uint64_t)e->off_groups + plane_span + n_planes;
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (n_counters * sizeof(unsigned long long) > (uint64_t)free_b)
+        return fail(PSSBAM_ENOMEM, "per-contig tables for %d references need a counter block of %llu bytes; the device has %llu free", n_ref,
+                    (unsigned long long)(n_counters * sizeof(unsigned long long)), (unsigned long long)free_b);
+    const uint64_t off_touched = (uint64_t)e->off_groups + plane_span;
+    if (!(e->tallied && old_planes > 0)) {   // nothing counted yet
+        if (const int rc = grow_counters(e, n_counters)) return rc;
+        e->n_planes = n_planes;
+        e->off_touched = off_touched;
+        return PSSBAM_OK;
+    }
+    // the counts move over; the old block is freed here, not retired: the list may grow many times, and once the stream has
+    // run dry nothing names the old block any more (tally launches are never put off once references have been set)
+    const size_t w = sizeof(unsigned long long);
+    unsigned long long *old = e->d_counters_own, *d_new = nullptr;
+    const uint64_t star_old = (uint64_t)e->off_groups + (uint64_t)(old_planes - 1u) * e->plane_words;
+    HIP_TRY(hipMalloc(&d_new, n_counters * w));
+    hipError_t err = hipMemsetAsync(d_new, 0, n_counters * w, e->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(d_new, old, star_old * w, hipMemcpyDeviceToDevice, e->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(d_new + off_touched - e->plane_words, old + star_old, e->plane_words * w, hipMemcpyDeviceToDevice, e->stream);
+    if (err == hipSuccess && old_planes > 1u)
+        err = hipMemcpyAsync(d_new + off_touched, old + e->off_touched, (old_planes - 1u) * w, hipMemcpyDeviceToDevice, e->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(d_new + off_touched + n_planes - 1u, old + e->off_touched + old_planes - 1u, w, hipMemcpyDeviceToDevice, e->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+    if (err != hipSuccess) {
+        (void)hipFree(d_new);
+        return fail(PSSBAM_EHIP, "growing the per-contig tables: %s", hipGetErrorString(err));
+    }
+    HIP_TRY(hipFree(old));
+    e->d_counters = e->d_counters_own = d_new;
+    e->n_counters = n_counters;
+    e->n_planes = n_planes;
+    e->off_touched = off_touched;
+    return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_set_per_contig(pssbam_engine *e, int32_t on) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (on) {
+        if (e->cfg.tally_mask != PSSBAM_TALLY_PSS)
+            return fail(PSSBAM_EINVAL, "per-contig tables split the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
+        if (e->planes != PLANES_NONE && e->planes != PLANES_EACH) return fail(PSSBAM_EINVAL, "per-contig tables and read groups / length bins / contig sets exclude each other");
+        if (e->hist_max) return fail(PSSBAM_EINVAL, "per-contig tables and the length histogram exclude each other");
+        if (e->site_mode) return fail(PSSBAM_EINVAL, "per-contig tables and site context exclude each other");
+        if (e->end_depth) return fail(PSSBAM_EINVAL, "per-contig tables and the end condition exclude each other");
+        if (e->gapped) return fail(PSSBAM_EINVAL, "per-contig tables and gapped reads exclude each other");
+    }
+    if (const int rc = check_may_resize(e, "per-contig tables")) return rc;
+    if ((on != 0) == e->per_contig) return PSSBAM_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    if (!on) {   // switched off: the block and the launches of an engine that never had the setting
+        if (const int rc = grow_counters(e, e->off_groups)) return rc;
+        e->per_contig = false;
+        e->planes = PLANES_NONE;
+        e->n_planes = 0;
+        e->off_touched = 0;
+        return PSSBAM_OK;
+    }
+    // the block is sized when the reference count is known: now, or at feed_open / set_references
+    e->per_contig = true;
+    e->planes = PLANES_EACH;
+    e->n_planes = 0;
+    const int rc = e->have_refs ? size_per_contig(e, e->n_ref) : e->feed_opened ? size_per_contig(e, e->feed_n_ref) : PSSBAM_OK;
+    if (rc) {
+        e->per_contig = false;
+        e->planes = PLANES_NONE;
+    }
+    return rc;
+}
+
+extern "C" int pssbam_engine_finish_contigs(pssbam_engine *e, int32_t first_ref, int32_t n, unsigned long *fwd, unsigned long *rev, uint8_t *touched) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (!e->per_contig) return fail(PSSBAM_ESTATE, "pssbam_engine_set_per_contig has not been called");
+    if (first_ref < 0 || n < 0 || (uint64_t)first_ref + (uint64_t)n > e->n_planes)
+        return fail(PSSBAM_EINVAL, "planes %d .. %lld outside 0..%d", first_ref, (long long)first_ref + n - 1, (int)e->n_planes - 1);
+    const int rc = pssbam_engine_sync(e);
+    if (rc) return rc;
+    const size_t tab = (size_t)e->rows * 16;
+    if (fwd) memset(fwd, 0, (size_t)n * tab * sizeof(unsigned long));
+    if (rev) memset(rev, 0, (size_t)n * tab * sizeof(unsigned long));
+    if (touched) memset(touched, 0, (size_t)n);
+    return for_touched_planes(e, (uint32_t)first_ref, (uint32_t)n, [&](uint32_t plane, const unsigned long long *p) {
+        const size_t i = plane - (uint32_t)first_ref;
+        if (touched) touched[i] = 1;
+        if (fwd) for (size_t k = 0; k < tab; k++) fwd[i * tab + k] = (unsigned long)p[k];
+        if (rev) for (size_t k = 0; k < tab; k++) rev[i * tab + k] = (unsigned long)p[tab + k];
+    });
 }
 
 extern "C" int pssbam_engine_reset(pssbam_engine *e) {

@@ -323,9 +323,14 @@ struct PlaneParams {
     // -S: the length bin edges
     uint32_t n_edges;                      // 1..MAX_LENGTH_EDGES, strictly increasing
     uint32_t edges[MAX_LENGTH_EDGES];      // bin k (k >= 1) starts at edges[k-1]
+    // -A: non-zero = a full slot table is emptied behind a tile that did not use all of it (tally_tiled_body, PLANES_EACH).
+    // (It sits in what was padding in front of the 64-bit members: the struct and every other member stay where they were.)
+    uint32_t each_evict;
     // k-mer planes (a PSSBAM_TALLY_KMER engine): plane p >= 1 is the [k5 | k3] pair of 2 * 4^k words at
     // koff_planes + (p - 1) * kplane_words, plane 0 the counter block's leading pair.  64-bit: 2 * 4^15 words a plane.
     uint64_t koff_planes, kplane_words;
+    // (-A, PLANES_EACH: n_groups = n_ref + 1 planes, plane k -- refID k; n_ref: refID -1 -- at off_groups + k * plane_words, 64-bit;
+    //  n_slots = the LDS planes a workgroup holds; the planes' touched words follow the last plane)
 };
 constexpr uint32_t GROUP_SCRATCH_DELTA = 16;   // the deltas lead a plane kernel's scratch slot
 constexpr uint32_t GROUP_PLANE_WORDS = 1024;   // one [(cell << 1) | table][32 rows] plane in LDS / scratch

@@ -41,6 +41,10 @@
 //                 read_group_plane), per fragment-length bin (PLANES_LEN: by Plan::L,
 //                 length_bin_plane) or per contig set (PLANES_REF: by Plan::ref_plane, packed into
 //                 the ref_info entry plan_head loads anyway); -S and -C stage prefixes as without planes.
+//  tally_tiled_planes / tally_simple_planes<PLANES_EACH> (-A): one plane per BAM reference, any number of them.  A workgroup
+//                 holds a few planes in LDS, owned by the refIDs its tiles meet (claimed in CODES-A, kept across tiles); a
+//                 read that finds every slot taken is tallied by one lane straight into its plane of the counter block, and
+//                 held planes leave LDS with 64-bit atomics into theirs (tally_tiled_body, PLANES_EACH).
 //  tally_tiled_kmer_planes / tally_simple_kmer_planes<PLANES> (fragkon -G, -S, -C): the k-mer tally with one
 //                 [k5 | k3] pair of 4^k bins per plane; the length selector reads Plan::Lk (what fragkon's -l / -L
 //                 compare).  k <= KMER_LDS_MAX_K: one 2 * 4^k-word LDS histogram per plane slot of the launch;
@@ -481,14 +485,42 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyP
 }
 
 // What picks a read's table plane in tally_tiled_body: nothing (one plane), its first RG:Z value
-// (-G), its length bin (-S), or its contig's set (-C).
-enum PlaneSel { PLANES_NONE = 0, PLANES_RG, PLANES_LEN, PLANES_REF };
+// (-G), its length bin (-S), its contig's set (-C), or its refID itself (-A: a plane per BAM reference).
+enum PlaneSel { PLANES_NONE = 0, PLANES_RG, PLANES_LEN, PLANES_REF, PLANES_EACH };
+
+// ---- -A: a plane per reference ---------------------------------------------------------------------------------
+// Plane k is refID k, plane n_ref (= n_groups - 1) the refID -1 records; only a record whose reference was found is ever
+// added to a table, so any other refID never asks.  Unlike the planes of -G / -S / -C these are not a fixed short list
+// of a launch: a workgroup keeps the planes of the few references its tiles meet in LDS slots (each_lds below) and adds
+// them to the counter block itself.
+constexpr uint32_t EACH_MAX_SLOTS = 32;       // LDS planes a workgroup can hold ($PSSBAM_CONTIG_SLOTS up to here)
+constexpr uint32_t EACH_DEFAULT_SLOTS = 7;    // 7 + the trash plane = 32 KiB, what a one-pass -G / -S / -C launch takes at most
+constexpr uint32_t EACH_EMPTY = 0xFFFFFFFFu;  // held[s]: no reference owns slot s
+// each_lds: [held EACH_MAX_SLOTS | miss count | miss queue TILED_MAX_T | used EACH_MAX_SLOTS: 1 + the last tile iteration that met the slot]
+constexpr uint32_t EACH_MISS_N = EACH_MAX_SLOTS, EACH_MISSQ = EACH_MAX_SLOTS + 1u, EACH_USED = EACH_MISSQ + 128u, EACH_LDS_WORDS = EACH_USED + EACH_MAX_SLOTS;
+__device__ __forceinline__ uint32_t each_plane(const RecHdr &h, const PlaneParams &G) { return min((uint32_t)h.ref_id, G.n_groups - 1u); }
+__device__ __forceinline__ uint64_t each_plane_base(const PlaneParams &G, uint32_t plane) {
+    return (uint64_t)G.off_groups + (uint64_t)plane * G.plane_words;
+}
+__device__ __forceinline__ uint64_t each_touched_base(const PlaneParams &G) { return each_plane_base(G, G.n_groups); }   // one word per plane
+struct GlobalPlaneTable {  // rows row_base .. row_base + n_rows - 1 straight into one plane of the counter block
+    unsigned long long *c;
+    uint32_t *hit;          // set when something was added: the caller then stores the plane's touched word, once per record
+    uint32_t off_rev, row_base, n_rows;
+    __device__ __forceinline__ void add(uint32_t table, uint32_t row, uint32_t cell) const {
+        if (row - row_base < n_rows) {
+            atomicAdd(&c[(table ? off_rev : 0u) + row * 16u + cell], 1ull);
+            *hit = 1u;
+        }
+    }
+};
 
 // KMER: the plane of the k-mer tally -- its length bins go by Plan::Lk (strlen(SEQ), what fragkon's -l / -L compare,
 // for paired reads too), not by Plan::L.
 template <PlaneSel PLANES, bool KMER = false, class Src>
 __device__ __forceinline__ uint32_t record_plane(const Src &src, const RecHdr &h, const Plan &pl, const PlaneParams &G) {
     if constexpr (PLANES == PLANES_RG) return read_group_plane(src, h, G);
+    else if constexpr (PLANES == PLANES_EACH) return each_plane(h, G);
     else if constexpr (PLANES == PLANES_REF) return pl.ref_plane;   // from the ref_info entry plan_head loaded
     else return length_bin_plane(G, KMER ? pl.Lk : pl.L);
 }
@@ -542,7 +574,7 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record_kmer_planes(
 }
 
 // The same for tally_tiled_planes (substitution tables only): the record's plane slot of this
-// launch, if it has one, decides where its counts go.
+// launch, if it has one, decides where its counts go.  (PLANES_EACH: also the path of a read that found no free slot.)
 template <PlaneSel PLANES, bool MASKQ = false, bool REGIONS = false>
 __device__ __attribute__((noinline)) uint32_t tally_overflow_record_planes(const TallyParams *kernarg, const PlaneParams *gk,
                                                                            uint32_t o0, uint32_t o1, uint32_t *table) {
@@ -550,6 +582,14 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record_planes(const
     GlobalBytes gsrc{P.recs + o0};
     const RecHdr gh = decode_hdr(gsrc, o1 - o0);
     const Plan gpl = make_plan<true, false, REGIONS>(P, gsrc, gh);
+    if constexpr (PLANES == PLANES_EACH) {   // -A: no slot is needed, the rows of this pass go straight into the reference's plane
+        if (gpl.pss_fwd || gpl.pss_rev) {
+            const uint32_t plane = each_plane(gh, *gk);
+            uint32_t hit = 0u;
+            tally_pss_record<MASKQ>(P, GlobalPlaneTable{P.counters + each_plane_base(*gk, plane), &hit, P.off_rev, P.row_base, 32u}, gsrc, gh, gpl);
+            if (hit) P.counters[each_touched_base(*gk) + plane] = 1ull;
+        }
+    } else
     if (gpl.pss_fwd || gpl.pss_rev) {
         const uint32_t slot = record_plane<PLANES>(gsrc, gh, gpl, *gk) - gk->plane0;
         if (slot < gk->n_slots) tally_pss_record<MASKQ>(P, LdsTableColumnMajor{table + slot * GROUP_PLANE_WORDS, P.row_base}, gsrc, gh, gpl);
@@ -579,6 +619,22 @@ __device__ __forceinline__ uint32_t base_quality_mask(uint32_t x, uint32_t q4) {
 // planes of [(cell<<1)|table][row] plus one trash plane behind them; every read's plane slot is
 // resolved in CODES-A (record_plane: read_group_plane or length_bin_plane) and kept in grp_lds, and
 // COLUMNS adds the wave's scalar slot offset to each real code.
+//
+// PLANES_EACH (-A, tally_tiled_planes): a plane per BAM reference, far more than LDS holds, of which one tile touches a
+// handful.  `table` holds gk->n_slots resident planes plus the trash plane, `each_lds` the refIDs that own them
+// (held[], EACH_EMPTY = free).  In CODES-A the left-end lane of every candidate finds its reference's slot in held[] or
+// claims the first free one with an LDS compare-and-swap -- all lanes scan in slot order and a slot never changes
+// owner during the phase, so the lanes of one reference agree -- and COLUMNS runs as for the other selectors.  Slots
+// live across the tiles a workgroup walks.  A read that finds every slot taken does not wait: its codes go to the
+// trash plane, it is queued, and behind COLUMNS one lane tallies it straight into its plane of the counter block
+// (tally_overflow_record_planes, 64-bit atomics).  A tile that had such a miss ends by flushing and emptying every
+// slot, and so does a tile that leaves every slot taken without having used them all (gk->each_evict != 0; it is 0 only for
+// A/B runs): on a coordinate-sorted input a workgroup meets one reference after the other, and emptying the full table
+// behind the tile keeps the next reference from finding no slot -- which would send a whole tile of reads down the
+// one-lane path; a tile that uses every slot gains nothing from it and is left alone.  The kernel ends with the same
+// flush: every non-zero word of a held plane is added to the counter block with
+// one 64-bit atomic, the plane's touched flag is set and the LDS word zeroed.  The planes take no scratch slot and no
+// reduce; the status deltas keep theirs.  The other instantiations contain none of it.
 //
 // MASKQ (-Q, min_bq > 0): whole records are staged (QUAL lies behind SEQ), CODES-A also fetches the 32 QUAL bytes
 // that line up with the end's window and CODES-B turns them into a 0x00 / 0xFF byte per position that is ORed into
@@ -629,8 +685,10 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
                                                  int32_t *__restrict__ lds_delta, uint4 *__restrict__ refs_lds,
                                                  const PlaneParams *gk = nullptr, uint32_t *__restrict__ grp_lds = nullptr,
                                                  uint32_t *__restrict__ hist_lds = nullptr, uint32_t *__restrict__ site_lds = nullptr,
-                                                 uint32_t *__restrict__ end_lds = nullptr) {
+                                                 uint32_t *__restrict__ end_lds = nullptr, uint32_t *__restrict__ each_lds = nullptr) {
     constexpr bool GROUPED = PLANES != PLANES_NONE;   // one table plane per read group / length bin
+    constexpr bool EACH = PLANES == PLANES_EACH;      // ... per BAM reference, resident in LDS slots
+    static_assert(!EACH || (DO_PSS && !DO_KMER), "a plane per reference splits the substitution tables");
     static_assert(!END || (DO_PSS && !DO_KMER && !LATER_PASS && PLANES == PLANES_NONE && !HIST && !SITE), "the end condition belongs to pass 0 of the one-plane substitution tally without the length histogram and site context");
     static_assert(!SITE || (DO_PSS && !DO_KMER && PLANES == PLANES_NONE && !HIST), "site context belongs to the one-plane substitution tally without the length histogram");
     static_assert(!HIST || (DO_PSS && !LATER_PASS && PLANES == PLANES_NONE), "the length histogram belongs to pass 0 of the one-plane substitution tally");
@@ -669,6 +727,30 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         for (uint32_t i = tid; i < SITE_WORDS; i += TILED_THREADS) site_lds[i] = 0u;
     if constexpr (END)
         for (uint32_t i = tid; i < 32u * n_pos + 4u; i += TILED_THREADS) end_lds[i] = 0u;
+    if constexpr (EACH) {
+        if (tid < EACH_MAX_SLOTS) { each_lds[tid] = EACH_EMPTY; each_lds[EACH_USED + tid] = 0u; }
+        if (tid == 0u) each_lds[EACH_MISS_N] = 0u;
+    }
+    // -A: every held plane into the counter block, LDS words zeroed (the caller has put a barrier behind the last COLUMNS
+    // pass and puts one in front of the next change of held[])
+    auto flush_slots = [&]() {
+        if constexpr (EACH) {
+            // (every wave walks 64 consecutive words of ONE slot per round, all its lanes for the same number of rounds)
+            for (uint32_t i = tid; i < gk->n_slots * GROUP_PLANE_WORDS; i += TILED_THREADS) {
+                const uint32_t r = i & 31u;
+                const uint32_t v = r < n_live ? table[i] : 0u;
+                const unsigned long long any = __ballot(v != 0u);
+                if (!any) continue;
+                const uint32_t ref = each_lds[i / GROUP_PLANE_WORDS], ct = (i / 32u) & 31u;   // (a slot nobody owns holds zeros)
+                if (v) {
+                    atomicAdd(&P.counters[each_plane_base(*gk, ref) + ((ct & 1u) ? P.off_rev : 0u) + (row_base + r) * 16u + (ct >> 1)],
+                              (unsigned long long)v);
+                    table[i] = 0u;
+                }
+                if (lane == (uint32_t)__ffsll((long long)any) - 1u) P.counters[each_touched_base(*gk) + ref] = 1ull;   // once per wave and round
+            }
+        }
+    };
     // contig info of the first BAM references (all of them for a human-sized header) + the "*" entry
     const uint32_t n_ref_cached = min((uint32_t)P.n_ref, REF_LDS_ENTRIES);
     if (tid < n_ref_cached) refs_lds[tid] = P.ref_info[tid];
@@ -852,6 +934,23 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         }
         if constexpr (GROUPED && !KPLANES) {
             // the read's plane slot for COLUMNS; n_slots = not in this launch (its codes go to the trash plane)
+            if constexpr (EACH) {
+                // -A: the slot that holds the read's reference, or the first free one, claimed; none: a miss (queued)
+                if (in_tile && e == 0u) {
+                    uint32_t slot = gk->n_slots;
+                    if (cand) {
+                        const uint32_t ref = each_plane(h, *gk);
+                        for (uint32_t s = 0; s < gk->n_slots; s++) {
+                            uint32_t owner = each_lds[s];
+                            if (owner == EACH_EMPTY) owner = atomicCAS(&each_lds[s], EACH_EMPTY, ref);
+                            if (owner == EACH_EMPTY || owner == ref) { slot = s; break; }
+                        }
+                        if (slot == gk->n_slots) each_lds[EACH_MISSQ + atomicAdd(&each_lds[EACH_MISS_N], 1u)] = j;
+                        else each_lds[EACH_USED + slot] = it + 1u;   // (every writer of this tile stores the same value)
+                    }
+                    grp_lds[j] = slot;
+                }
+            } else
             if (in_tile && e == 0u) {
                 const uint32_t slot = cand ? record_plane<PLANES>(src, h, pl, *gk) - gk->plane0 : gk->n_slots;
                 grp_lds[j] = slot < gk->n_slots ? slot : gk->n_slots;
@@ -901,6 +1000,18 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
             }
         }
         __syncthreads();
+        [[maybe_unused]] uint32_t n_miss = 0u;   // -A: reads of this tile that found no slot (the same in every lane)
+        [[maybe_unused]] bool empty_slots = false;   // -A: this tile ends by flushing and emptying every slot (likewise)
+        if constexpr (EACH) {
+            n_miss = each_lds[EACH_MISS_N];
+            bool full = gk->each_evict != 0u;
+            uint32_t n_used = 0u;
+            for (uint32_t s = 0; s < gk->n_slots; s++) {
+                full = full && each_lds[s] != EACH_EMPTY;
+                n_used += each_lds[EACH_USED + s] == it + 1u ? 1u : 0u;
+            }
+            empty_slots = n_miss != 0u || (full && n_used < gk->n_slots);
+        }
 
         // every wave is done with `stage`: the next tile's DMA starts now (its offsets were put
         // into LDS before the barrier at the top) and lands behind the rest of CODES and COLUMNS;
@@ -1209,6 +1320,21 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
                 for (; j < j1; j++) atomicAdd(&table[((uint32_t)sheet[j * 64u + lane] << 5) + row], 1u);
             }
         }
+        if constexpr (EACH) {
+            if (empty_slots) {   // (the whole workgroup takes the branch)
+                // the queued reads, one lane each, from global memory into their planes of the counter block (their events
+                // were booked above, from the staged copy; this tile's offsets stay in toffs until the next tile's top)
+                if (tid < n_miss) {
+                    const uint32_t jm = each_lds[EACH_MISSQ + tid];
+                    (void)tally_overflow_record_planes<PLANES, MASKQ, REGIONS>(kernarg, gk, cur_offs[jm], cur_offs[jm + 1u], table);
+                }
+                __syncthreads();   // every wave's COLUMNS pass is over
+                flush_slots();
+                __syncthreads();   // held[] has been read
+                if (tid < EACH_MAX_SLOTS) each_lds[tid] = EACH_EMPTY;
+                if (tid == 0u) each_lds[EACH_MISS_N] = 0u;
+            }
+        }
     }
 
     __syncthreads();
@@ -1220,6 +1346,10 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         uint32_t *mine = P.scratch + (size_t)blockIdx.x * gk->scratch_words;
         const uint32_t n_words = LDS_KMER ? gk->n_slots * 2u * (1u << (2 * P.K)) : 0u;
         for (uint32_t i = tid; i < n_words; i += TILED_THREADS) mine[GROUP_SCRATCH_DELTA + i] = lds_kmer[i];
+        if (tid < 16u) mine[tid] = tid < (uint32_t)ST_USED ? (uint32_t)lds_delta[tid] : 0u;
+    } else if constexpr (EACH) {   // [deltas 16]; the held planes go to the counter block
+        flush_slots();
+        uint32_t *mine = P.scratch + (size_t)blockIdx.x * gk->scratch_words;
         if (tid < 16u) mine[tid] = tid < (uint32_t)ST_USED ? (uint32_t)lds_delta[tid] : 0u;
     } else if constexpr (GROUPED) {   // [deltas 16 | n_slots planes]
         uint32_t *mine = P.scratch + (size_t)blockIdx.x * gk->scratch_words;
@@ -1830,6 +1960,11 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled_planes(const TallyP
     const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
     const PlaneParams *gk = (const PlaneParams *)((const uint8_t *)kernarg + PLANE_KERNARG_OFFSET);
     uint32_t *table = (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces));
+    if constexpr (PLANES == PLANES_EACH) {   // -A: n_slots resident planes + the trash plane, and who owns them
+        __shared__ uint32_t each_lds[EACH_LDS_WORDS];
+        tally_tiled_body<true, false, false, LATER_PASS, PLANES, MASKQ, REGIONS>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta,
+                                                                                 refs_lds, gk, grp_lds, nullptr, nullptr, nullptr, each_lds);
+    } else
     tally_tiled_body<true, false, false, LATER_PASS, PLANES, MASKQ, REGIONS>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta,
                                                                              refs_lds, gk, grp_lds);
 }
@@ -1885,8 +2020,14 @@ __global__ void __launch_bounds__(256) tally_simple_planes(const TallyParams P, 
         const Plan pl = make_plan<true, false>(P, src, h);
         if (pl.pss_fwd || pl.pss_rev) {
             const uint32_t plane = record_plane<PLANES>(src, h, pl, G);
+            if constexpr (PLANES == PLANES_EACH) {   // -A: plane = refID, every row at once
+                uint32_t hit = 0u;
+                tally_pss_record<true>(P, GlobalPlaneTable{P.counters + each_plane_base(G, plane), &hit, P.off_rev, 0u, 0xFFFFFFFFu}, src, h, pl);
+                if (hit) P.counters[each_touched_base(G) + plane] = 1ull;
+            } else {
             unsigned long long *base = P.counters + (plane ? G.off_groups + (plane - 1u) * G.plane_words : 0u);
             tally_pss_record<true>(P, GlobalTable{base, P.off_rev}, src, h, pl);
+            }
         }
         book_events(true, false, record_events(true, false, pl, false), lds_delta);
     }

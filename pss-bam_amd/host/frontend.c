@@ -35,6 +35,7 @@ int frontend_length_hist = 0;
 int frontend_site_context = PSSBAM_SITE_NONE;
 int frontend_end_depth = 0, frontend_end_cell5 = 0, frontend_end_cell3 = 0;
 int frontend_gapped_reads = 0;
+int frontend_per_contig = 0;
 const pss_regions *frontend_regions = NULL;
 uint32_t frontend_length_edges[PSSBAM_MAX_LENGTH_BINS - 1];
 const frontend_contig_map *frontend_contig_sets = NULL;
@@ -76,6 +77,7 @@ static struct early_feed {
     int site;                       /* -X: the site context, set on every engine after create */
     int end_depth, end_cell5, end_cell3; /* -E: the end condition, set on every engine after create */
     int gapped;                     /* -I: anchored ends, set on every engine after create */
+    int per_contig;                 /* -A: a pair of tables per reference, set on every engine after create (feed_open gave the count) */
     const pss_regions *regions;     /* -T: the intervals, set on every engine after create */
     int n_edges;                    /* -S: the length bin edges, set on every engine after create */
     uint32_t edges[PSSBAM_MAX_LENGTH_BINS - 1];
@@ -152,7 +154,9 @@ typedef struct {
 static void *engine_make_main(void *arg)
 {
     engine_make_job *j = (engine_make_job *)arg;
-    if (pssbam_engine_create(&j->cfg, j->out) || pssbam_engine_feed_open(*j->out, j->n_ref, EF.fasta_bytes) ||
+    /* (-A before feed_open: the planes are sized from its n_ref before the feed works out what memory it may take) */
+    if (pssbam_engine_create(&j->cfg, j->out) || (EF.per_contig && pssbam_engine_set_per_contig(*j->out, 1)) ||
+        pssbam_engine_feed_open(*j->out, j->n_ref, EF.fasta_bytes) ||
         (EF.min_bq > 0 && pssbam_engine_set_min_base_quality(*j->out, EF.min_bq)) ||
         (EF.hist > 0 && pssbam_engine_set_length_histogram(*j->out, EF.hist)) ||
         (EF.site != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(*j->out, EF.site)) ||
@@ -291,6 +295,7 @@ void frontend_warmup_start(const pssbam_config *cfg, const char *aln_path, const
             EF.end_cell5 = frontend_end_cell5;
             EF.end_cell3 = frontend_end_cell3;
             EF.gapped = frontend_gapped_reads;
+            EF.per_contig = frontend_per_contig;
             EF.regions = frontend_regions;
             memcpy(EF.edges, frontend_length_edges, sizeof EF.edges);
             EF.sets = frontend_contig_sets;
@@ -313,7 +318,7 @@ static int same_length_bins(void)
     return EF.n_edges == frontend_n_length_edges && EF.sets == frontend_contig_sets && EF.min_bq == frontend_min_base_quality &&
            EF.hist == frontend_length_hist && EF.site == frontend_site_context &&
            EF.end_depth == frontend_end_depth && EF.end_cell5 == frontend_end_cell5 && EF.end_cell3 == frontend_end_cell3 &&
-           EF.gapped == frontend_gapped_reads && EF.regions == frontend_regions &&
+           EF.gapped == frontend_gapped_reads && EF.per_contig == frontend_per_contig && EF.regions == frontend_regions &&
            memcmp(EF.edges, frontend_length_edges, (size_t)frontend_n_length_edges * sizeof *EF.edges) == 0;
 }
 
@@ -453,6 +458,10 @@ void run_result_free(run_result *res)
     free(res->site_rev);
     free(res->end_fwd);
     free(res->end_rev);
+    for (int k = 0; k < res->n_contigs && res->contig_names; k++) free(res->contig_names[k]);
+    free(res->contig_names);
+    free(res->contig_fwd);
+    free(res->contig_rev);
     free(res->fwd);
     free(res->rev);
     free(res->k5);
@@ -651,6 +660,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
                 (frontend_site_context != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(eng[g], frontend_site_context)) ||
                 (frontend_end_depth > 0 && pssbam_engine_set_end_condition(eng[g], frontend_end_depth, frontend_end_cell5, frontend_end_cell3)) ||
                 (frontend_gapped_reads && pssbam_engine_set_gapped_reads(eng[g], 1)) ||
+                (frontend_per_contig && pssbam_engine_set_per_contig(eng[g], 1)) ||
                 send_regions(eng[g], frontend_regions) ||
                 (frontend_n_length_edges > 0 && pssbam_engine_set_length_bins(eng[g], frontend_n_length_edges, frontend_length_edges)) ||
                 send_contig_sets(eng[g], frontend_contig_sets)) {
@@ -859,6 +869,38 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
             goto done;
         }
+    }
+    if (frontend_per_contig && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -A: the planes that hold something (the touched words were summed with the block) */
+        const int32_t n_ref = rd ? bam_reader_header(rd)->n_ref : sam_reader_n_ref(sd);
+        const char *const *names = rd ? (const char *const *)bam_reader_header(rd)->ref_name : sam_reader_ref_names(sd);
+        const size_t cells = (size_t)(cfg->pss.region_len + 2) * 16;
+        uint8_t *touched = (uint8_t *)calloc((size_t)n_ref + 1, 1);
+        if (!touched) { fprintf(stderr, "Error: out of memory\n"); goto done; }
+        if (pssbam_engine_finish_contigs(eng[0], 0, n_ref + 1, NULL, NULL, touched)) {
+            fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+            free(touched);
+            goto done;
+        }
+        size_t n_touched = 0;
+        for (int32_t k = 0; k <= n_ref; k++) n_touched += touched[k];
+        res->contig_names = (char **)calloc(n_touched ? n_touched : 1, sizeof(char *));
+        res->contig_fwd = (unsigned long *)calloc(cells * (n_touched ? n_touched : 1), sizeof(unsigned long));
+        res->contig_rev = (unsigned long *)calloc(cells * (n_touched ? n_touched : 1), sizeof(unsigned long));
+        if (!res->contig_names || !res->contig_fwd || !res->contig_rev) { fprintf(stderr, "Error: out of memory\n"); free(touched); goto done; }
+        size_t at = 0;
+        for (int32_t k = 0; k <= n_ref;) { /* runs of touched neighbours, one read-back each */
+            if (!touched[k]) { k++; continue; }
+            int32_t end = k;
+            while (end <= n_ref && touched[end]) end++;
+            if (pssbam_engine_finish_contigs(eng[0], k, end - k, res->contig_fwd + at * cells, res->contig_rev + at * cells, NULL)) {
+                fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+                free(touched);
+                goto done;
+            }
+            for (; k < end; k++) res->contig_names[at++] = strdup(k < n_ref ? names[k] : "*");
+        }
+        res->n_contigs = (int)n_touched;
+        free(touched);
     }
     if (frontend_n_length_edges > 0) res->n_planes = frontend_n_length_edges + 1; /* -G: set with the IDs */
     if (frontend_contig_sets) {

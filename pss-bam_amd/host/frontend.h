@@ -33,6 +33,11 @@ typedef struct run_result {
     /* pss-bam -E (frontend_end_depth): the conditional tables COND, (region_len+2)*16 each, or NULL, and reads[4] */
     unsigned long *end_fwd, *end_rev;
     uint64_t end_reads[4];
+    /* pss-bam -A (frontend_per_contig): the tables of every reference that holds something, in header order (the refID -1
+     * records last, under the name "*"): n_contigs names and tables of (region_len+2)*16 each */
+    int n_contigs;
+    char **contig_names;
+    unsigned long *contig_fwd, *contig_rev;
 } run_result;
 
 /* pss-bam -G: every engine gets the input header's @RG IDs (pssbam_engine_set_read_groups) and run_tally()
@@ -58,6 +63,10 @@ extern int frontend_end_depth, frontend_end_cell5, frontend_end_cell3;
 /* pss-bam -I: non-zero = every engine tallies clipped and gapped reads by their anchored ends
  * (pssbam_engine_set_gapped_reads).  Set before frontend_warmup_start(). */
 extern int frontend_gapped_reads;
+
+/* pss-bam -A: non-zero = every engine keeps a pair of tables per reference (pssbam_engine_set_per_contig) and run_tally()
+ * returns those that hold something.  Set before frontend_warmup_start(). */
+extern int frontend_per_contig;
 
 /* -T: the intervals of the BED file (regions.h; NULL: none); every engine gets them (pssbam_engine_set_regions), on
  * every input path -- the filter lives in the engine.  Set before frontend_warmup_start. */

@@ -40,6 +40,10 @@
  * core of M I D = X ops that starts and ends with a match-type op.  The two files are what this command writes without -I for
  * the input in which each such read is the record <span>M (span = the reference length of the core) whose SEQ / QUAL keep the
  * match-type run at either end of the core, with N / ! in between.  Not with -G, -S, -C, -H, -X or -E.
+ * Added: -A also writes <prefix>.pss.contigs.txt: for every reference sequence of the input that holds something, in header
+ * order, the rows of the counts file this command writes with -F reduced to that contig, each behind the contig's name and
+ * "fwd" or "rev" (report.h) -- any number of contigs, one pass, no map file; the other files stay as they are.  The reads
+ * of RNAME "*" come last, as "*".  Goes with -R, -Q and -T.  Not with -G, -S, -C, -H, -X, -E or -I.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -65,13 +69,13 @@ int main(int argc, char *argv[])
     const double age_main = frontend_process_age_s();
     frontend_detach_start();   /* the caller gets its prompt back when the reports are written, not when 30 GB of device buffers are gone */
     const double t_main = frontend_now_s();
-    int region_len = 15, min_mq = 0, merged_only = 0, by_group = 0, gapped = 0, option;
+    int region_len = 15, min_mq = 0, merged_only = 0, by_group = 0, gapped = 0, per_contig = 0, option;
     unsigned long min_read_len = 0, max_read_len = 250000000;
     const char *up_ctx = "ACGT", *down_ctx = "ACGT";
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL, *read_group = NULL;
     const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL, *bed_fn = NULL, *hist_arg = NULL, *site_arg = NULL, *end_arg = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:I")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IA")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -92,6 +96,7 @@ int main(int argc, char *argv[])
         case 'X': site_arg = optarg; break;
         case 'E': end_arg = optarg; break;
         case 'I': gapped = 1; break;
+        case 'A': per_contig = 1; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -122,7 +127,8 @@ int main(int argc, char *argv[])
               "-D <downstream context base filter; first base before alignment must be one of these (default: ACGT)>\n"
               "-m <only consider merged reads>\n"
               "-E <ss|ds>[,<d>] <also write the tables of each end over the reads damaged within d bases (default: 1) of the other end>\n"
-              "-I <also tally clipped and gapped reads, by the matched runs at their two ends>\n",
+              "-I <also tally clipped and gapped reads, by the matched runs at their two ends>\n"
+              "-A <also write the tables of every contig of the input, one pass for any number of contigs>\n",
               stderr);
         exit(1);
     }
@@ -205,6 +211,13 @@ int main(int argc, char *argv[])
                 : hist_arg ? "-H (fragment-length histogram)" : site_arg ? "-X (tables per site context)" : "-E (tables conditional on the other end)");
         exit(1);
     }
+    if (per_contig && (by_group || len_edges || ctg_map || hist_arg || site_arg || end_arg || gapped)) {
+        fprintf(stderr, "-A (tables per contig) and %s exclude each other.\n",
+                by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)" : ctg_map ? "-C (tables per contig set)"
+                : hist_arg ? "-H (fragment-length histogram)" : site_arg ? "-X (tables per site context)"
+                : end_arg ? "-E (tables conditional on the other end)" : "-I (clipped and gapped reads by their anchored ends)");
+        exit(1);
+    }
     pss_regions bed;
     memset(&bed, 0, sizeof bed);
     if (bed_fn) {
@@ -262,6 +275,7 @@ int main(int argc, char *argv[])
     if (site_arg) fprintf(stderr, " -X %s", site_arg);
     if (end_arg) fprintf(stderr, " -E %s", end_arg);
     if (gapped) fprintf(stderr, " -I");
+    if (per_contig) fprintf(stderr, " -A");
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -290,6 +304,7 @@ int main(int argc, char *argv[])
     frontend_end_cell5 = end_cell5;
     frontend_end_cell3 = end_cell3;
     frontend_gapped_reads = gapped;
+    frontend_per_contig = per_contig;
     if (bed_fn) frontend_regions = &bed;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
@@ -330,6 +345,8 @@ int main(int argc, char *argv[])
     }
     if (res.end_fwd && (pss_write_labelled(fasta_fn, bam_fn, out_prefix, "cond", region_len, res.end_fwd, res.end_rev) ||
                         pss_write_end_reads(out_prefix, res.end_reads))) exit(1);   /* -E */
+    if (per_contig && pss_write_contigs(fasta_fn, bam_fn, out_prefix, region_len, res.n_contigs, (const char *const *)res.contig_names,
+                                        res.contig_fwd, res.contig_rev)) exit(1);   /* -A */
     if (by_group && res.n_planes == 0)
         fprintf(stderr, "Warning: -G: the header of %s has no @RG line; only the tables of all reads were written.\n", bam_fn);
     /* <prefix>.<tag>: what `-R <ID> -o <prefix>.<ID>` (-G), `-l <lo> -L <hi> -o <prefix>.len<lo>-<hi>` (-S) or -F

@@ -125,6 +125,36 @@ int pss_write_labelled(const char *fasta_fn, const char *bam_fn, const char *out
     return rc;
 }
 
+static void contig_row(FILE *fp, const char *name, const char *table, int label, const unsigned long *row)
+{
+    fprintf(fp, "%s\t%s\t", name, table);
+    count_row(fp, label, row);
+}
+
+int pss_write_contigs(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int region_len, int n,
+                      const char *const *names, const unsigned long *fwd, const unsigned long *rev)
+{
+    const size_t cells = (size_t)(region_len + 2) * 16;
+    char fn[FN_BUF + 1];
+    FILE *fp;
+    snprintf(fn, sizeof fn, "%s.pss.contigs.txt", out_prefix);
+    fp = fopen(fn, "w");
+    if (!fp) {
+        fprintf(stderr, "ERROR: Cannot write to file %s\n.", fn);
+        return 1;
+    }
+    fprintf(fp, "### pss-bam.c v1.2.1:\n### FASTA: %s\n### BAM: %s\n### OUT: %s\n", fasta_fn, bam_fn, fn);
+    fputs("### CONTIG TABLE POS AA AC AG AT CA CC CG CT GA GC GG GT TA TC TG TT\n", fp);
+    for (int k = 0; k < n; k++) {
+        const unsigned long *f = fwd + (size_t)k * cells, *r = rev + (size_t)k * cells;
+        for (int row = 0; row < region_len + 2; row++) contig_row(fp, names[k], "fwd", row - 2, f + (size_t)row * 16);
+        for (int pos = region_len - 1; pos >= 0; pos--) contig_row(fp, names[k], "rev", pos, r + (size_t)(pos + 2) * 16);
+        contig_row(fp, names[k], "rev", 1, r + 16);
+        contig_row(fp, names[k], "rev", 2, r);
+    }
+    return fclose(fp) ? 1 : 0;
+}
+
 int pss_parse_end_condition(const char *arg, int *depth, int *cell5, int *cell3, char *err, size_t err_len)
 {
     const int ss = strncmp(arg, "ss", 2) == 0, ds = strncmp(arg, "ds", 2) == 0;

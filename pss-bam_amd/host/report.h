@@ -15,6 +15,12 @@ int pss_write_rates(const char *fasta_fn, const char *bam_fn, const char *out_pr
  * diagnostic. */
 int pss_write_labelled(const char *fasta_fn, const char *bam_fn, const char *out_prefix, const char *tag, int region_len,
                        const unsigned long *fwd, const unsigned long *rev);
+/* pss-bam -A: <out_prefix>.pss.contigs.txt -- the four "###" lines that open a counts file (version, FASTA, BAM, OUT: this
+ * file), the line "### CONTIG TABLE POS AA AC ... TT", then for each of the n contigs, in the order given, the body lines
+ * of its counts file, each behind "<name><TAB>fwd<TAB>" or "<name><TAB>rev<TAB>": the forward rows -2 .. N-1, the reverse
+ * rows N-1 .. 0, 1, 2.  fwd / rev hold n tables of (region_len + 2) * 16 counts.  Returns 0, or 1 after a diagnostic. */
+int pss_write_contigs(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int region_len, int n,
+                      const char *const *names, const unsigned long *fwd, const unsigned long *rev);
 /* pss-bam -E: parses "<ss|ds>[,<d>]" -- ss: C->T at both ends (cell5 = cell3 = 13, column TC), ds: C->T at the 5' end
  * and G->A at the 3' end (cell5 = 13, cell3 = 2, column AG); d = 1..PSSBAM_MAX_END_DEPTH, default 1.  Returns 0, or -1
  * with a one-line message in err. */
