@@ -36,6 +36,7 @@ extern "C" {
 #define PSSBAM_MAX_READ_GROUPS 4096  /* pssbam_engine_set_read_groups */
 #define PSSBAM_MAX_LENGTH_BINS 64    /* pssbam_engine_set_length_bins: at most 63 edges */
 #define PSSBAM_MAX_CONTIG_SETS 4096  /* pssbam_engine_set_contig_sets */
+#define PSSBAM_MAX_MISMATCHES 255    /* pssbam_engine_set_mismatches: the largest histogram limit and the largest filter limit */
 #define PSSBAM_MAX_HIST_LENGTH 65535 /* pssbam_engine_set_length_histogram: the largest limit (lengths above it share one row) */
 #define PSSBAM_MAX_BASE_QUALITY 93   /* pssbam_engine_set_min_base_quality: the largest Phred value SAM text can print */
 #define PSSBAM_MAX_REGIONS (1 << 26) /* pssbam_engine_set_regions: intervals in one call */
@@ -449,6 +450,45 @@ int pssbam_engine_finish_end_condition(pssbam_engine *e, unsigned long *fwd_c, u
  * been tallied.  The setting survives pssbam_engine_reset; engines whose blocks are summed must all have it. */
 int pssbam_engine_set_gapped_reads(pssbam_engine *e, int32_t on);
 
+/* Mismatch count (pss-bam -n / -N / -V): a record filter on the number of mismatches between the whole read and the
+ * reference, and the histogram of that number over the reads that are added to the tables, from the same pass.
+ * The mismatch count m of a record is defined for a record whose CIGAR is exactly <L>M, L being the length that
+ * min_read_len / max_read_len compare, on a contig the genome holds.  With seq[i] read base i as stored (the BAM nibble),
+ * g[p] the contig after the case folding the engine applies anyway and s = POS - 1:
+ *     m = #{ i in [0, min(L, l_seq)) : seq[i] in {A,C,G,T}, g[s+i] in {A,C,G,T}, seq[i] != g[s+i] }
+ * and with transversions_only the unordered pair {seq[i], g[s+i]} must also be neither {A,G} nor {C,T}.  Nothing else
+ * counts: N, IUPAC codes and '=' in the read, any non-ACGT reference base, bases at or beyond l_seq.  m is the same for
+ * both strands (complementing both bases keeps inequality and the transition / transversion class), is taken from SEQ as
+ * stored -- a minimum base quality masks table positions and does not change m -- and is a full 32-bit count: a
+ * 300-base read that differs everywhere has m = 300.
+ * Filter, max_mismatches = k (0..PSSBAM_MAX_MISMATCHES; -1 = off): one more record filter, like regions.  A record that
+ * every other filter would add to a table and that has m > k counts as PSSBAM_ST_PSS_FILTERED; RECORDS, RG_DROPPED,
+ * PARSE_SKIP, NO_CONTIG and the sum PSS_OK + PSS_FILTERED stay as without the setting.  With RED(k) the input without
+ * the <L>M records on known contigs whose m exceeds k: fwd, rev and PSS_OK == those of the engine without the setting
+ * on RED(k) with the same options.
+ * Histogram, hist_max = M (1..PSSBAM_MAX_MISMATCHES; 0 = off): two arrays of M + 2 counters, mf and mr.  With
+ * b = min(m, M + 1): mf[b] += 1 when the record is added to the forward table, mr[b] += 1 when it is added to the
+ * reverse table.  These are the identities of the length histogram with "the input reduced to the records whose
+ * min(m, M + 1) equals b" in place of "-l b -L b": unpaired records give mf[b] == mr[b] == OK(b); on any input
+ * mf[b] + mr[b] == 2 * OK_unpaired(b) + OK_paired(b).  With the filter on only kept reads are counted, so rows above k
+ * are zero.  Tables and status counters are bit-identical to the engine without the histogram.
+ * (0, -1, x) switches everything off: the engine then launches exactly the kernels it launches without this call and
+ * n_u64 is unchanged.
+ * Legal after create (or reset) and before the first tally launch; with pssbam_engine_feed_open that is any time
+ * before set_references.  Goes with cfg.read_group, a minimum base quality and regions.  PSSBAM_EINVAL for arguments
+ * outside their ranges, on an engine with PSSBAM_TALLY_KMER in its mask, for region_len > 30 (the decision is taken in
+ * the one pass that holds all rows, as for the end condition), and with read groups, length bins, contig sets, a length
+ * histogram, site context, an end condition, gapped reads or per-contig tables set (each of those setters returns
+ * PSSBAM_EINVAL once this one is on); PSSBAM_ESTATE once records have been tallied, or once a bound counter block would
+ * have to grow (see pssbam_engine_counters_device).  The setting survives pssbam_engine_reset; engines whose blocks are
+ * summed must all have been given the same three arguments. */
+int pssbam_engine_set_mismatches(pssbam_engine *e, int32_t hist_max /*0 = no histogram*/,
+                                 int32_t max_mismatches /*-1 = no filter*/, int32_t transversions_only);
+
+/* Drains the engine like pssbam_engine_finish and copies the two arrays, hist_max + 2 words each; either pointer may
+ * be NULL.  PSSBAM_EINVAL without a histogram. */
+int pssbam_engine_finish_mismatches(pssbam_engine *e, uint64_t *fwd, uint64_t *rev);
+
 /* The device-resident counter block [fwd | rev | k5 | k3 | stats] as one array of
  * n_u64 64-bit words, for a caller-side RCCL reduce across GPUs (sum, uint64).  With read groups it is
  * [fwd | rev | stats | fwd_0 | rev_0 | ... | fwd_n-1 | rev_n-1]: the leading fwd | rev are the unassigned
@@ -471,7 +511,11 @@ int pssbam_engine_set_gapped_reads(pssbam_engine *e, int32_t on);
  * context) the conditional pair and its read counters are appended: [fwd | rev | stats | fwd_c | rev_c | reads[4]],
  * fwd_c at 2*(region_len+2)*16 + PSSBAM_ST_N (the old n_u64), rev_c (region_len+2)*16 words behind it, reads[0..3]
  * behind that, n_u64 larger by 2*(region_len+2)*16 + 4.  Every word is a plain count, so the block still sums across
- * engines as one u64 array and the PSSBAM_ST_* slots stay where they are. */
+ * engines as one u64 array and the PSSBAM_ST_* slots stay where they are.
+ * With a mismatch histogram of limit M (pssbam_engine_set_mismatches; a PSSBAM_TALLY_PSS engine without any of the above)
+ * the two arrays are appended: [fwd | rev | stats | mf | mr], mf at 2*(region_len+2)*16 + PSSBAM_ST_N (the old n_u64), mr
+ * M + 2 words behind it, n_u64 larger by 2*(M+2).  All words are plain counts: the block still sums as one u64 array.  The
+ * filter alone adds no words. */
 int pssbam_engine_counters_device(pssbam_engine *e, void **d_counters, size_t *n_u64);
 
 /* Makes the engine accumulate into caller-owned device memory (n_u64 words, as reported

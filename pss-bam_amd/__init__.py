@@ -46,12 +46,14 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_site_context", "pssbam_engine_finish_site_context",
     "pssbam_engine_set_end_condition", "pssbam_engine_finish_end_condition", "pssbam_engine_set_gapped_reads",
     "pssbam_engine_set_per_contig", "pssbam_engine_finish_contigs",
+    "pssbam_engine_set_mismatches", "pssbam_engine_finish_mismatches",
 ]
 MAX_READ_GROUPS = 4096
 MAX_LENGTH_BINS = 64
 MAX_CONTIG_SETS = 4096
 MAX_BASE_QUALITY = 93
 MAX_HIST_LENGTH = 65535
+MAX_MISMATCHES = 255
 MAX_REGIONS = 1 << 26
 SITE_NONE, SITE_CPG = 0, 1
 SITE_MODES = {None: SITE_NONE, "none": SITE_NONE, "cpg": SITE_CPG}
@@ -131,6 +133,8 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_finish_end_condition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_gapped_reads.argtypes = [C.c_void_p, C.c_int32]
     L.pssbam_engine_set_per_contig.argtypes = [C.c_void_p, C.c_int32]
+    L.pssbam_engine_set_mismatches.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+    L.pssbam_engine_finish_mismatches.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_finish_contigs.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_regions.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_counters_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
@@ -213,6 +217,8 @@ class Engine:
     carries the given cell within its first `depth` positions, see set_end_condition; None = off.
     `gapped` = True (pss-bam -I): clipped and gapped reads are tallied by their anchored ends, see set_gapped.
     `per_contig` = True (pss-bam -A): every BAM reference's own pair of substitution tables, see set_per_contig.
+    `mismatches` = (hist_max, max_mismatches, tv_only) (pss-bam -N / -n / -V): the histogram of, and a filter on, the
+    number of mismatches between the whole read and the reference, see set_mismatches; None = off.
     With `kmer` alone (no `pss`) the three split the k-mer tables instead (fragkon -G / -S / -C): every plane is a
     k5 / k3 pair, and the length bins go by the SEQ length and kmer's min_read_len / max_read_len."""
 
@@ -220,7 +226,7 @@ class Engine:
                  kernel: int = KERNEL_AUTO, device: int = -1, read_groups: list[str] | None = None,
                  length_bins: list[int] | None = None, contig_sets=None, min_base_qual: int = 0,
                  length_hist: int = 0, site_context: str | None = None, end_condition: tuple[int, int, int] | None = None,
-                 gapped: bool = False, per_contig: bool = False):
+                 gapped: bool = False, per_contig: bool = False, mismatches: tuple[int, int, int] | None = None):
         L = hip_lib()
         cfg = _Config()
         cfg.abi_version = 1
@@ -273,6 +279,9 @@ class Engine:
         self._n_ref: int | None = None   # the reference count the engine has been told (set_references, feed_open)
         if per_contig:
             self.set_per_contig(True)
+        self._mismatches = (0, -1, 0)
+        if mismatches is not None:
+            self.set_mismatches(*mismatches)
         if read_groups is not None:
             self.set_read_groups(read_groups)
         if length_bins is not None:
@@ -378,6 +387,32 @@ class Engine:
     def gapped(self) -> bool:
         """whether clipped and gapped reads are tallied by their anchored ends"""
         return self._gapped
+
+    def set_mismatches(self, hist_max: int = 0, max_mismatches: int = -1, tv_only: int = 0):
+        """pss-bam -N / -n / -V.  m = the positions of a <L>M read at which read and reference base are both A/C/G/T and
+        differ (tv_only: differ by a transversion).  max_mismatches = k (0..255, -1 = off): a read that would be tallied
+        and has m > k is filtered instead -- the tables are those of the input without such reads.  hist_max = M (1..255,
+        0 = off): counts min(m, M + 1) of every read that is added to the forward / reverse table, see
+        finish_mismatches.  (0, -1, x) switches both off.  Needs region_len <= 30; goes with read_group, min_base_qual
+        and regions; not with kmer, read groups, length bins, contig sets, per-contig tables, the length histogram, site
+        context, the end condition or gapped reads.  Before the first tally (after feed_open: before set_references);
+        a histogram also before bind_counters: the counter block grows by 2 * (hist_max + 2) words.  Survives reset."""
+        _chk(self._L.pssbam_engine_set_mismatches(self._h, int(hist_max), int(max_mismatches), int(bool(tv_only))))
+        on = hist_max > 0 or max_mismatches >= 0
+        self._mismatches = (int(hist_max), int(max_mismatches), int(bool(tv_only)) if on else 0)
+
+    @property
+    def mismatches(self) -> tuple[int, int, int] | None:
+        """(hist_max, max_mismatches, tv_only) in force, None = off"""
+        return self._mismatches if self._mismatches[0] > 0 or self._mismatches[1] >= 0 else None
+
+    def finish_mismatches(self) -> tuple[np.ndarray, np.ndarray]:
+        """(fwd, rev): u64 arrays of hist_max + 2 rows -- row m = reads with m mismatches added to that table, the last
+        row every larger count (drains like finish)"""
+        fwd = np.zeros(self._mismatches[0] + 2, dtype=np.uint64)
+        rev = np.zeros_like(fwd)
+        _chk(self._L.pssbam_engine_finish_mismatches(self._h, fwd.ctypes.data, rev.ctypes.data))
+        return fwd, rev
 
     def set_per_contig(self, on: bool = True):
         """pss-bam -A: plane k of the counter block takes the records whose refID is k (k = 0 .. n_ref - 1 of
@@ -704,6 +739,9 @@ class Engine:
         if self._end_condition[0]:   # the end condition (never together with any of the above): fwd_c | rev_c | reads[4]
             lay["end_fwd"], lay["end_rev"], lay["end_reads"] = base, base + rows * 16, base + 2 * rows * 16
             lay["n_u64"] = base + 2 * rows * 16 + 4
+        if self._mismatches[0]:   # the mismatch histogram (never together with any of the above): mf | mr behind the stats
+            lay["mism_fwd"], lay["mism_rev"] = base, base + self._mismatches[0] + 2
+            lay["n_u64"] = base + 2 * (self._mismatches[0] + 2)
         return lay
 
     def genome_kmer_count(self, klen: int) -> np.ndarray:

@@ -226,6 +226,11 @@ struct pssbam_engine {
     uint32_t site_mode = 0, off_site = 0;
     // -E (pssbam_engine_set_end_condition): fwd_c | rev_c | reads[4], rows * 16 words per table, at off_end = the end of the block as it is without them
     uint32_t end_depth = 0, end_cell5 = 0, end_cell3 = 0, off_end = 0;
+    // -n / -N / -V (pssbam_engine_set_mismatches): mf | mr, mism_hist + 2 words each, at off_mism = the end of the block as it is without
+    // them (mism_hist = 0: no words); mism_max = -1: no filter
+    uint32_t mism_hist = 0, off_mism = 0;
+    int32_t mism_max = -1;
+    bool mism_tv = false;
     bool gapped = false;   // -I (pssbam_engine_set_gapped_reads): clipped and gapped reads are tallied by their anchored ends; no counter words
     int env_hist_lds_bins = -1;   // PSSBAM_HIST_LDS_BINS: at most this many bins of each array in LDS (tests: the global-atomic path with short reads)
     // -T (pssbam_engine_set_regions): contig name -> its merged intervals, kept on the host; the per-refID device table is
@@ -929,23 +934,24 @@ static int no_kernel() { return fail(PSSBAM_EINVAL, "no tally kernel is built fo
 // 32.. of a large -r) and its -Q, -T, -H, -X, -E and -I state.  `exists` is the list of instantiations: the k-mer tally (alone or
 // beside the substitution tables) and -H belong to pass 0, -Q -H -X to the substitution tables, -X excludes the other two;
 // -E is the substitution tally of pass 0 alone, with or without -Q and -T; -I is the substitution tally alone in every pass, with or
-// without -Q and -T (eight instantiations).
+// without -Q and -T (eight instantiations); -n / -N is the substitution tally of pass 0 alone, with or without -Q and -T (four).
 // (SITE, END: the larger scratch slot of the -X / -E instantiations and the reduce that walks it)
 static int launch_tiled(pssbam_engine *e, TallyParams &P, bool do_pss, bool do_kmer, bool kmer_lds, bool later, bool maskq, bool regions,
-                        bool hist, bool site, bool endc, bool gapped, uint32_t lds, uint32_t n_tiles) {
-    return with_flags([&](auto DO_PSS, auto DO_KMER, auto LDS_KMER, auto LATER, auto MASKQ, auto REGIONS, auto HIST, auto SITE, auto END, auto GAPPED) -> int {
+                        bool hist, bool site, bool endc, bool gapped, bool mism, uint32_t lds, uint32_t n_tiles) {
+    return with_flags([&](auto DO_PSS, auto DO_KMER, auto LDS_KMER, auto LATER, auto MASKQ, auto REGIONS, auto HIST, auto SITE, auto END, auto GAPPED, auto MISM) -> int {
         constexpr bool exists = (DO_KMER() || !LDS_KMER()) &&
                                 (LATER() ? DO_PSS() && !DO_KMER() && !HIST()
                                          : (DO_PSS() || DO_KMER()) && (DO_PSS() || !(MASKQ() || HIST() || SITE())) && !(SITE() && (DO_KMER() || HIST()))) &&
                                 (!END() || (DO_PSS() && !DO_KMER() && !LATER() && !HIST() && !SITE())) &&
-                                (!GAPPED() || (DO_PSS() && !DO_KMER() && !LDS_KMER() && !HIST() && !SITE() && !END()));
+                                (!GAPPED() || (DO_PSS() && !DO_KMER() && !LDS_KMER() && !HIST() && !SITE() && !END())) &&
+                                (!MISM() || (DO_PSS() && !DO_KMER() && !LDS_KMER() && !LATER() && !HIST() && !SITE() && !END() && !GAPPED()));
         if constexpr (exists)
-            return launch_with_reduce(e, tally_tiled<DO_PSS(), DO_KMER(), LDS_KMER(), LATER(), MASKQ(), REGIONS(), HIST(), SITE(), END(), GAPPED()>,
+            return launch_with_reduce(e, tally_tiled<DO_PSS(), DO_KMER(), LDS_KMER(), LATER(), MASKQ(), REGIONS(), HIST(), SITE(), END(), GAPPED(), MISM()>,
                                       reduce_partials<SITE(), END()>, SITE() ? SITE_SCRATCH_WORDS : END() ? END_SCRATCH_WORDS : SCRATCH_WORDS, lds, n_tiles, P,
                                       std::tuple<>(), (uint32_t)LDS_KMER());
         else
             return no_kernel();
-    }, do_pss, do_kmer, kmer_lds, later, maskq, regions, hist, site, endc, gapped);
+    }, do_pss, do_kmer, kmer_lds, later, maskq, regions, hist, site, endc, gapped, mism);
 }
 
 // How many 16-byte pieces of a record the tiled kernel must stage so that everything the path
@@ -1063,6 +1069,14 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         P.end_cell5 = e->end_cell5;
         P.end_cell3 = e->end_cell3;
         P.off_end = e->off_end;
+    }
+    // -n / -N: the MISM instantiations; without the setting the engine launches what it always did
+    const bool mism = do_pss && (e->mism_hist > 0 || e->mism_max >= 0);
+    if (mism) {
+        P.mism_limit = e->mism_max >= 0 ? (uint32_t)e->mism_max + 1u : 0u;
+        P.mism_hist = e->mism_hist;
+        P.mism_tv = e->mism_tv ? 1u : 0u;
+        P.off_mism = e->off_mism;
     }
     const bool gapped = do_pss && e->gapped;   // -I: the GAPPED instantiations; without it the engine launches what it always did
     P.gapped = gapped ? 1u : 0u;
@@ -1217,9 +1231,9 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                     });
                 }
             }
-        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions && !hist && !site && !endc && !gapped) {
+        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions && !hist && !site && !endc && !gapped && !mism) {
             // -r N <= 16 (2 context rows + 16 positions): the short-window variant, one pass (it stages prefixes only
-            // and has no QUAL path: -R and -Q go to tally_tiled; so do -T, -H, -X, -E and -I, whose arms only tally_tiled carries)
+            // and has no QUAL path: -R and -Q go to tally_tiled; so do -T, -H, -X, -E, -I and -n / -N, whose arms only tally_tiled carries)
             if (!do_kmer && getenv("PSSBAM_COMPACT_DECODE_TWICE"))   // diagnostics: what the shared header decode costs
                 rc = launch_with_reduce(e, tally_compact_decode_twice, reduce_partials<false>, SCRATCH_WORDS, lds, n_tiles, P, std::tuple<>(), 0u);
             else
@@ -1240,11 +1254,12 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                 if (e->env_hist_lds_bins >= 0) P.hist_lds_bins = std::min(P.hist_lds_bins, (uint32_t)e->env_hist_lds_bins);
                 lds0 += hist_lds_bytes(P.hist_lds_bins);
             }
+            if (mism && e->mism_hist) lds0 += 2u * (e->mism_hist + 2u) * 4u;   // -N (one pass: -r <= 30): [mf | mr] behind the staging buffer, at most 2 KiB
             if (endc) lds0 += end_lds_bytes(e->rows);   // -E (one pass: -r <= 30): the conditional tables and reads[4] behind the staging buffer
             for (uint32_t pass = 0; pass < n_passes && rc == PSSBAM_OK; pass++) {
                 P.row_base = pass * TILED_ROWS;
-                rc = pass == 0 ? launch_tiled(e, P, do_pss, do_kmer, kmer_lds, false, maskq, regions, hist, site, endc, gapped, lds0, n_tiles)
-                               : launch_tiled(e, P, true, false, false, true, maskq, regions, false, site, false, gapped, lds, n_tiles);
+                rc = pass == 0 ? launch_tiled(e, P, do_pss, do_kmer, kmer_lds, false, maskq, regions, hist, site, endc, gapped, mism, lds0, n_tiles)
+                               : launch_tiled(e, P, true, false, false, true, maskq, regions, false, site, false, gapped, false, lds, n_tiles);
             }
         }
         if (rc != PSSBAM_OK) return rc;
@@ -1513,6 +1528,8 @@ extern "C" int pssbam_engine_finish_kmer_groups(pssbam_engine *e, int32_t group,
 
 // What the setters that resize the counter block require: nothing tallied yet, and the block is the engine's own.  `what`
 // names what is being set in the messages.
+static bool mismatches_on(const pssbam_engine *e) { return e->mism_hist > 0 || e->mism_max >= 0; }   // -n / -N
+
 static int check_may_resize(const pssbam_engine *e, const char *what) {
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set %s after create or reset, before the first tally", what);
     if (e->d_counters != e->d_counters_own) return fail(PSSBAM_ESTATE, "a caller-bound counter block cannot grow: set %s before bind_counters", what);
@@ -1539,6 +1556,7 @@ static int set_planes(pssbam_engine *e, PlaneSel sel, uint32_t n_planes, const c
     if (e->site_mode) return fail(PSSBAM_EINVAL, "%s and site context exclude each other", what);
     if (e->end_depth) return fail(PSSBAM_EINVAL, "%s and the end condition exclude each other", what);
     if (e->gapped) return fail(PSSBAM_EINVAL, "%s and gapped reads exclude each other", what);
+    if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "%s and the mismatch count exclude each other", what);
     const bool kmer = e->cfg.tally_mask == PSSBAM_TALLY_KMER;
     if (e->cfg.tally_mask != PSSBAM_TALLY_PSS && !kmer)
         return fail(PSSBAM_EINVAL, "%s split the substitution tables or the k-mer tables, not both (PSSBAM_TALLY_PSS | PSSBAM_TALLY_KMER)", what);
@@ -1632,6 +1650,7 @@ extern "C" int pssbam_engine_set_gapped_reads(pssbam_engine *e, int32_t on) {
         if (e->hist_max) return fail(PSSBAM_EINVAL, "gapped reads and the length histogram exclude each other");
         if (e->site_mode) return fail(PSSBAM_EINVAL, "gapped reads and site context exclude each other");
         if (e->end_depth) return fail(PSSBAM_EINVAL, "gapped reads and the end condition exclude each other");
+        if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "gapped reads and the mismatch count exclude each other");
     }
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set gapped reads after create or reset, before the first tally");
     e->gapped = on != 0;   // (the counter block keeps its size: a caller-bound block stays bound)
@@ -1647,6 +1666,7 @@ extern "C" int pssbam_engine_set_length_histogram(pssbam_engine *e, int32_t max_
     if (e->site_mode) return fail(PSSBAM_EINVAL, "the length histogram and site context exclude each other");
     if (e->end_depth) return fail(PSSBAM_EINVAL, "the length histogram and the end condition exclude each other");
     if (e->gapped && max_len) return fail(PSSBAM_EINVAL, "the length histogram and gapped reads exclude each other");
+    if (mismatches_on(e) && max_len) return fail(PSSBAM_EINVAL, "the length histogram and the mismatch count exclude each other");
     if (const int rc = check_may_resize(e, "the length histogram")) return rc;
     if ((uint32_t)max_len == e->hist_max) return PSSBAM_OK;
     HIP_TRY(hipSetDevice(e->device));
@@ -1670,6 +1690,48 @@ extern "C" int pssbam_engine_finish_length_histogram(pssbam_engine *e, uint64_t 
     return PSSBAM_OK;
 }
 
+extern "C" int pssbam_engine_set_mismatches(pssbam_engine *e, int32_t hist_max, int32_t max_mismatches, int32_t transversions_only) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (hist_max < 0 || hist_max > PSSBAM_MAX_MISMATCHES) return fail(PSSBAM_EINVAL, "mismatch histogram limit %d outside 0..%d", hist_max, PSSBAM_MAX_MISMATCHES);
+    if (max_mismatches < -1 || max_mismatches > PSSBAM_MAX_MISMATCHES)
+        return fail(PSSBAM_EINVAL, "maximum mismatch count %d outside -1..%d", max_mismatches, PSSBAM_MAX_MISMATCHES);
+    const bool on = hist_max > 0 || max_mismatches >= 0;
+    if (on) {
+        if (e->cfg.tally_mask != PSSBAM_TALLY_PSS)
+            return fail(PSSBAM_EINVAL, "the mismatch count filters the reads of the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
+        if (e->cfg.pss.region_len > 30)
+            return fail(PSSBAM_EINVAL, "the mismatch count needs a region length of at most 30 (the decision is taken in the one pass that holds all rows), not %d", e->cfg.pss.region_len);
+        if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the mismatch count and read groups / length bins / contig sets / per-contig tables exclude each other");
+        if (e->hist_max) return fail(PSSBAM_EINVAL, "the mismatch count and the length histogram exclude each other");
+        if (e->site_mode) return fail(PSSBAM_EINVAL, "the mismatch count and site context exclude each other");
+        if (e->end_depth) return fail(PSSBAM_EINVAL, "the mismatch count and the end condition exclude each other");
+        if (e->gapped) return fail(PSSBAM_EINVAL, "the mismatch count and gapped reads exclude each other");
+    }
+    if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the mismatch count after create or reset, before the first tally");
+    if ((uint32_t)hist_max != e->mism_hist) {
+        if (const int rc = check_may_resize(e, "the mismatch histogram")) return rc;
+        HIP_TRY(hipSetDevice(e->device));
+        // the block grows (or shrinks back) behind everything it holds without the histogram
+        if (const int rc = grow_counters(e, (uint64_t)e->off_groups + (hist_max ? 2ull * ((uint64_t)hist_max + 2ull) : 0ull))) return rc;
+    }
+    e->mism_hist = (uint32_t)hist_max;
+    e->off_mism = hist_max ? e->off_groups : 0u;
+    e->mism_max = max_mismatches;
+    e->mism_tv = on && transversions_only != 0;
+    return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_finish_mismatches(pssbam_engine *e, uint64_t *fwd, uint64_t *rev) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (!e->mism_hist) return fail(PSSBAM_EINVAL, "pssbam_engine_set_mismatches has not been called with a histogram limit");
+    const int rc = pssbam_engine_sync(e);
+    if (rc) return rc;
+    const size_t n = (size_t)e->mism_hist + 2;
+    if (fwd) HIP_TRY(hipMemcpy(fwd, e->d_counters + e->off_mism, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (rev) HIP_TRY(hipMemcpy(rev, e->d_counters + e->off_mism + n, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return PSSBAM_OK;
+}
+
 extern "C" int pssbam_engine_set_site_context(pssbam_engine *e, int32_t mode) {
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
     if (mode != PSSBAM_SITE_NONE && mode != PSSBAM_SITE_CPG) return fail(PSSBAM_EINVAL, "unknown site context %d", mode);
@@ -1679,6 +1741,7 @@ extern "C" int pssbam_engine_set_site_context(pssbam_engine *e, int32_t mode) {
     if (e->hist_max) return fail(PSSBAM_EINVAL, "site context and the length histogram exclude each other");
     if (e->end_depth) return fail(PSSBAM_EINVAL, "site context and the end condition exclude each other");
     if (e->gapped && mode != PSSBAM_SITE_NONE) return fail(PSSBAM_EINVAL, "site context and gapped reads exclude each other");
+    if (mismatches_on(e) && mode != PSSBAM_SITE_NONE) return fail(PSSBAM_EINVAL, "site context and the mismatch count exclude each other");
     if (const int rc = check_may_resize(e, "the site context")) return rc;
     if ((uint32_t)mode == e->site_mode) return PSSBAM_OK;
     HIP_TRY(hipSetDevice(e->device));
@@ -1720,6 +1783,7 @@ extern "C" int pssbam_engine_set_end_condition(pssbam_engine *e, int32_t depth, 
     if (e->hist_max) return fail(PSSBAM_EINVAL, "the end condition and the length histogram exclude each other");
     if (e->site_mode) return fail(PSSBAM_EINVAL, "the end condition and site context exclude each other");
     if (e->gapped && depth) return fail(PSSBAM_EINVAL, "the end condition and gapped reads exclude each other");
+    if (mismatches_on(e) && depth) return fail(PSSBAM_EINVAL, "the end condition and the mismatch count exclude each other");
     if (const int rc = check_may_resize(e, "the end condition")) return rc;
     if ((uint32_t)depth != e->end_depth) {
         HIP_TRY(hipSetDevice(e->device));
@@ -1861,6 +1925,7 @@ extern "C" int pssbam_engine_set_per_contig(pssbam_engine *e, int32_t on) {
         if (e->site_mode) return fail(PSSBAM_EINVAL, "per-contig tables and site context exclude each other");
         if (e->end_depth) return fail(PSSBAM_EINVAL, "per-contig tables and the end condition exclude each other");
         if (e->gapped) return fail(PSSBAM_EINVAL, "per-contig tables and gapped reads exclude each other");
+        if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "per-contig tables and the mismatch count exclude each other");
     }
     if (const int rc = check_may_resize(e, "per-contig tables")) return rc;
     if ((on != 0) == e->per_contig) return PSSBAM_OK;

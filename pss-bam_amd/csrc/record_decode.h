@@ -101,6 +101,11 @@ struct TallyParams {
     // its first end_depth positions, the reverse contribution of those whose 5' end carries end_cell5.  Read by the END
     // instantiations of tally_tiled, their reduce_partials and tally_simple.
     uint32_t end_depth, end_cell5, end_cell3, off_end;
+    // -n / -N / -V: the mismatch count of a whole read against the reference (tally_kernels.h: count_mismatches).  mism_limit = k + 1:
+    // a read with at least that many mismatches is filtered (0 = no filter); mism_hist = M: [mf | mr], M + 2 u64 counters each, in
+    // the counter block at off_mism, bin min(m, M + 1) of the reads added to the forward / reverse table (0 = no histogram);
+    // mism_tv: only transversions count.  Read by the MISM instantiations of tally_tiled and by tally_simple.
+    uint32_t mism_limit, mism_hist, mism_tv, off_mism;
 };
 
 // stats slots, must match include/pssbam_hip.h.  The kernels count EVENTS only: every launch

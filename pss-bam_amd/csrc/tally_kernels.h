@@ -63,6 +63,12 @@
 //                 the staged prefix (record_decode.h: cigar_anchor), a lane's read stream starts at its end's anchor and
 //                 CODES-B blanks what lies outside the end's matched run; the reference side is the plain kernel's.
 //
+//  MISM arm of tally_tiled (-n / -N / -V, pass 0 of a one-pass launch): the mismatch count of the whole read against the reference.
+//                 The two lanes of a read's pair each compare one half of it in CODES-A, eight bases per step and nibble-parallel
+//                 (count_mismatches_staged: SEQ from the staged prefix, the reference from the 4-bit genome image), and add
+//                 their halves; a read beyond the limit stops being a candidate, and the histogram of min(m, M + 1) lives in
+//                 LDS behind the staging buffer (mism_wave_add).  count_mismatches is the definition, one lane per read.
+//
 // Integer/byte work only: no MFMA anywhere (the bound is HBM bandwidth).
 #pragma once
 
@@ -335,6 +341,79 @@ __device__ __forceinline__ void hist_wave_add(const TallyParams &P, uint32_t *hi
 }
 
 // ---------------------------------------------------------------------------------------
+// -n / -N / -V: mismatches of a whole read against the reference
+// ---------------------------------------------------------------------------------------
+// The mismatch count m of a <L>M record (include/pssbam_hip.h): the read positions i < min(L, l_seq) at which both SEQ[i] and the
+// reference base are one of A C G T and differ -- with tv_only, differ by a transversion (stored codes A0 C1 G2 T3: a transition
+// is an XOR of 2).  Strand-independent; -Q does not enter.  This is the definition in code: tally_simple and the one-lane
+// path of tally_tiled use it as it stands.
+template <class Src>
+__device__ uint32_t count_mismatches(const Src &src, const RecHdr &h, const uint8_t *G, int64_t s, uint32_t L, bool tv_only) {
+    const uint32_t n = min(L, h.l_seq);
+    uint32_t m = 0u;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t rd = nib_code(read_nibble(src, h, i));
+        const uint32_t rf = ref_code(G[s + (int64_t)i]);
+        if (rd < 4u && rf < 4u && rd != rf && !(tv_only && (rd ^ rf) == 2u)) m++;
+    }
+    return m;
+}
+// TallyParams::mism_limit is k + 1 (0 = no filter), mism_hist the histogram limit M (0 = no histogram)
+__device__ __forceinline__ bool mism_on(const TallyParams &P) { return (P.mism_hist | P.mism_limit) != 0u; }
+__device__ __forceinline__ bool mism_beyond(const TallyParams &P, uint32_t m) { return P.mism_limit && m >= P.mism_limit; }
+__device__ __forceinline__ uint32_t mism_bin(const TallyParams &P, uint32_t m) { return min(m, P.mism_hist + 1u); }
+// n reads of bin b into mf (fwd) and / or mr (rev): the tiled kernel's LDS bins [mf | mr], or the counter block
+__device__ __forceinline__ void mism_add(const TallyParams &P, uint32_t *mism_lds, uint32_t b, bool fwd, bool rev, uint32_t n) {
+    if (mism_lds) {
+        if (fwd) atomicAdd(&mism_lds[b], n);
+        if (rev) atomicAdd(&mism_lds[P.mism_hist + 2u + b], n);
+    } else {
+        if (fwd) atomicAdd(&P.counters[P.off_mism + b], (unsigned long long)n);
+        if (rev) atomicAdd(&P.counters[P.off_mism + P.mism_hist + 2u + b], (unsigned long long)n);
+    }
+}
+// The whole wave's reads of one tile, merged by value like hist_wave_add (most reads of a wave have 0, 1 or 2 mismatches):
+// two ballot rounds take the modes, what is left adds itself.  Every bin lives in LDS.
+__device__ __forceinline__ void mism_wave_add(const TallyParams &P, uint32_t *mism_lds, bool on, uint32_t b, bool fwd, bool rev) {
+    const uint32_t key = (b << 2) | (fwd ? 2u : 0u) | (rev ? 1u : 0u);
+    const uint32_t lane = threadIdx.x & 63u;
+    bool pending = on && (fwd || rev);
+    for (uint32_t round = 0; __any(pending); round++) {
+        if (pending) {
+            if (round >= 2u) {
+                mism_add(P, mism_lds, b, fwd, rev, 1u);
+                pending = false;
+            } else {
+                const uint32_t v = __builtin_amdgcn_readfirstlane(key);   // (of the lanes still in this branch)
+                const bool same = key == v;
+                const unsigned long long m = __ballot(same);
+                if (same) {
+                    pending = false;
+                    if (lane == (uint32_t)__ffsll((long long)m) - 1u) mism_add(P, mism_lds, b, fwd, rev, (uint32_t)__popcll(m));
+                }
+            }
+        }
+    }
+}
+// Eight positions at once.  g: eight nibbles of the genome image (0..3 = A C G T, 4..7 = other), r: the BAM nibbles of the
+// same eight read bases in the same order.  Returns bit 4q set when position q counts.  The reference nibble becomes the BAM
+// one-hot code (1 2 4 8), so the XOR of the two is zero for a match, 5 (A/G) or 10 (C/T) for a transition; a read nibble is
+// a base when exactly one of its bits is set.
+__device__ __forceinline__ uint32_t mismatch_flags8(uint32_t g, uint32_t r, bool tv_only) {
+    const uint32_t K = 0x11111111u;
+    auto nonzero = [&](uint32_t y) { return (y | (y >> 1) | (y >> 2) | (y >> 3)) & K; };   // bit 0 of every nibble that is not 0
+    const uint32_t g0 = g & K, g1 = (g >> 1) & K;
+    const uint32_t onehot = (~g1 & ~g0 & K) | ((~g1 & g0) << 1) | ((g1 & ~g0) << 2) | ((g1 & g0) << 3);
+    const uint32_t g_ok = ~(g >> 2) & ~(g >> 3) & K;
+    const uint32_t bits = (r & K) + ((r >> 1) & K) + ((r >> 2) & K) + ((r >> 3) & K);   // 0..4 per nibble: no carry
+    const uint32_t r_ok = ~nonzero(bits ^ K) & K;
+    const uint32_t x = r ^ onehot;
+    uint32_t f = g_ok & r_ok & nonzero(x);
+    if (tv_only) f &= nonzero(x ^ 0x55555555u) & nonzero(x ^ 0xAAAAAAAAu);
+    return f;
+}
+
+// ---------------------------------------------------------------------------------------
 // tally_simple
 // ---------------------------------------------------------------------------------------
 // dynamic LDS: [2*(N+2)*16 u32 table, if LDS_TABLE]
@@ -359,6 +438,12 @@ __global__ void __launch_bounds__(256) tally_simple(const TallyParams P) {
         else static_cast<Plan &>(pl) = make_plan<true, true>(P, src, h);
         if (!do_pss) pl.pss_fwd = pl.pss_rev = false;
         if (!do_kmer) pl.fk5 = pl.fk3 = false;
+        // -n / -N: the read's mismatch count; beyond the limit it is filtered like a read that meets no region
+        uint32_t mm = 0u;
+        if (mism_on(P) && (pl.pss_fwd || pl.pss_rev)) {
+            mm = count_mismatches(src, h, P.genome + pl.gbase, pl.s, pl.L, P.mism_tv != 0u);
+            if (mism_beyond(P, mm)) pl.pss_fwd = pl.pss_rev = false;
+        }
         if (pl.pss_fwd || pl.pss_rev) {
             if (P.gapped) {   // -I (never together with -X, -E or -H)
                 if (LDS_TABLE) tally_pss_record<true, false, true>(P, LdsTableRowMajor{dyn_lds, rows}, NoSite{}, src, h, pl);
@@ -373,6 +458,8 @@ __global__ void __launch_bounds__(256) tally_simple(const TallyParams P) {
             if (P.end_depth) tally_end_condition<true>(P, GlobalEndTable{P.counters + P.off_end, rows * 16u}, src, h, pl);
             // -H: straight into the counter block (hist_lds_bins is 0 in this kernel's launches)
             if (P.hist_max) hist_add(P, nullptr, hist_bin(P, pl.L), pl.pss_fwd, pl.pss_rev, 1u);
+            // -N: likewise
+            if (P.mism_hist) mism_add(P, nullptr, mism_bin(P, mm), pl.pss_fwd, pl.pss_rev, 1u);
         }
         bool kfail = false;
         if (pl.fk5 || pl.fk3) kfail = tally_kmer_record<false>(P, pl, nullptr);
@@ -411,6 +498,39 @@ __host__ __device__ inline uint32_t tiled_lds_bytes(uint32_t T, uint32_t pieces)
 // window cost three times what 2 x dwordx4 + 1 x dword do.
 struct __attribute__((packed, aligned(4))) Quad { uint32_t v[4]; };
 struct __attribute__((packed, aligned(4))) Tri { uint32_t v[3]; };
+
+// -n / -N, tiled form: the mismatches among read bases lo .. hi - 1 of a record whose SEQ starts at LDS byte seq_at of `stage`;
+// g0 = the genome position of read base 0, lo a multiple of 8.  32 bases per round trip: five genome dwords gathered like an
+// end window (one dwordx4 + one dword, brought to the read's alignment with v_alignbit) against 16 SEQ bytes, whose nibbles
+// are swapped into the genome image's order (even position = low nibble).  The gather may run up to 39 positions past
+// hi and the SEQ reads 19 bytes: inside the padding between contigs (CONTIG_PAD) and inside STAGE_SLACK; what they bring is masked.
+__device__ __forceinline__ uint32_t count_mismatches_staged(const uint32_t *genome4, uint64_t g0, const uint8_t *stage, uint32_t seq_at,
+                                                            uint32_t lo, uint32_t hi, bool tv_only) {
+    uint32_t m = 0u;
+    for (uint32_t b = lo; b < hi; b += 32u) {
+        const uint64_t ga = g0 + b;
+        const uint32_t *pg = genome4 + (ga >> 3);
+        const Quad q = *(const Quad *)pg;
+        const uint32_t gq[5] = {q.v[0], q.v[1], q.v[2], q.v[3], pg[4]};
+        const uint32_t gsh = 4u * (uint32_t)(ga & 7ull);
+        const uint32_t sa = seq_at + (b >> 1);
+        const uint32_t *qs = (const uint32_t *)(stage + (sa & ~3u));
+        uint32_t sr[5];
+#pragma unroll
+        for (int k = 0; k < 5; k++) sr[k] = qs[k];
+        const uint32_t left = hi - b;
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const uint32_t have = left > 8u * t ? min(left - 8u * t, 8u) : 0u;
+            const uint32_t W = __builtin_amdgcn_alignbit(gq[t + 1], gq[t], gsh);
+            const uint32_t S = __builtin_amdgcn_alignbyte(sr[t + 1], sr[t], sa & 3u);
+            const uint32_t R = ((S >> 4) & 0x0F0F0F0Fu) | ((S & 0x0F0F0F0Fu) << 4);
+            const uint32_t keep = have >= 8u ? 0xFFFFFFFFu : (1u << (4u * have)) - 1u;
+            m += (uint32_t)__popc(mismatch_flags8(W, R, tv_only) & keep);
+        }
+    }
+    return m;
+}
 
 constexpr uint32_t TILED_MAX_T = 128;
 static_assert(TILED_MAX_T * 2 == TILED_THREADS, "CODES maps one (read, end) pair to each thread");
@@ -460,7 +580,7 @@ __device__ __forceinline__ void stage_tile_dma(const uint8_t *recs, uint64_t rec
 // the kernel): a reference to the kernel's by-value copy would force that whole struct into
 // scratch memory.
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool MASKQ = false, bool REGIONS = false, bool HIST = false, bool SITE = false,
-          bool END = false, bool GAPPED = false>
+          bool END = false, bool GAPPED = false, bool MISM = false>
 __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyParams *kernarg, uint32_t o0,
                                                                     uint32_t o1, uint32_t *table, uint32_t *lds_kmer,
                                                                     uint32_t *hist_lds = nullptr, uint32_t *site_lds = nullptr,
@@ -468,7 +588,15 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyP
     const TallyParams &P = *kernarg;
     GlobalBytes gsrc{P.recs + o0};
     const RecHdr gh = decode_hdr(gsrc, o1 - o0);
-    const auto gpl = make_plan<DO_PSS, DO_KMER, REGIONS, GAPPED>(P, gsrc, gh);   // (GAPPED: walks every CIGAR op)
+    auto gpl = make_plan<DO_PSS, DO_KMER, REGIONS, GAPPED>(P, gsrc, gh);   // (GAPPED: walks every CIGAR op)
+    [[maybe_unused]] uint32_t mm = 0u;
+    if constexpr (MISM) {   // (hist_lds: the MISM instantiation's LDS bins)
+        if (gpl.pss_fwd || gpl.pss_rev) {
+            mm = count_mismatches(gsrc, gh, P.genome + gpl.gbase, gpl.s, gpl.L, P.mism_tv != 0u);
+            if (mism_beyond(P, mm)) gpl.pss_fwd = gpl.pss_rev = false;
+            else if (P.mism_hist) mism_add(P, hist_lds, mism_bin(P, mm), gpl.pss_fwd, gpl.pss_rev, 1u);
+        }
+    }
     if constexpr (GAPPED) {
         if (gpl.pss_fwd || gpl.pss_rev) tally_pss_record<MASKQ, false, true>(P, LdsTableColumnMajor{table, P.row_base}, NoSite{}, gsrc, gh, gpl);
     } else if constexpr (SITE) {
@@ -675,8 +803,18 @@ __device__ __forceinline__ uint32_t base_quality_mask(uint32_t x, uint32_t q4) {
 // stream) of a left lane starts at q0 - 2, that of a right lane ends at q1, and CODES-B blanks a lane's positions outside
 // [q0, q0 + a) / [q1 - b, q1) with the byte masks of the l_seq blanking, skipped wave-wide when no lane needs it.  The
 // instantiations without GAPPED contain none of it.
+//
+// MISM (-n / -N / -V, P.mism_limit or P.mism_hist non-zero; pass 0 of a one-pass launch, one plane, substitution tables only): in
+// CODES-A every lane of a candidate's pair compares one half of the read with the reference (count_mismatches_staged; the
+// halves are cut at a multiple of 8 bases so that both start on a whole SEQ byte) and the two lanes add their counts with
+// the exchange END uses.  All of it sits in front of the barrier that releases `stage`, so it reads the staged SEQ and
+// has used its gathered genome dwords before the next tile's DMA is issued.  A read with m >= mism_limit stops being a
+// candidate there, before -U/-D decide pss_fwd / pss_rev: its codes are "no count" and record_events books it as
+// filtered.  Behind CODES-B the left-end lane of every read that is added to a table counts bin min(m, M + 1)
+// (mism_wave_add) into `hist_lds`, here the 2 * (M + 2) words [mf | mr] behind the staging buffer, which leave LDS once, at
+// kernel end, with one 64-bit atomic per non-zero bin.  The instantiations without MISM contain none of it.
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS, PlaneSel PLANES = PLANES_NONE, bool MASKQ = false,
-          bool REGIONS = false, bool HIST = false, bool SITE = false, bool END = false, bool GAPPED = false>
+          bool REGIONS = false, bool HIST = false, bool SITE = false, bool END = false, bool GAPPED = false, bool MISM = false>
 __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const TallyParams *kernarg,
                                                  uint8_t *__restrict__ stage, uint8_t *__restrict__ sheet,
                                                  uint32_t *__restrict__ table,
@@ -696,6 +834,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
     static_assert(!KPLANES || !DO_PSS, "planes split either the substitution tables or the k-mer tables");
     static_assert(!MASKQ || DO_PSS, "base qualities mask the substitution tables only");
     static_assert(!GAPPED || (DO_PSS && !DO_KMER && PLANES == PLANES_NONE && !HIST && !SITE && !END), "anchored ends belong to the one-plane substitution tally without the length histogram, site context and the end condition");
+    static_assert(!MISM || (DO_PSS && !DO_KMER && !LATER_PASS && PLANES == PLANES_NONE && !HIST && !SITE && !END && !GAPPED), "the mismatch count belongs to pass 0 of the one-plane substitution tally without the length histogram, site context, the end condition and anchored ends");
     const uint32_t T = P.reads_per_tile;   // <= TILED_MAX_T
     const uint32_t n_recs = P.n_recs_dev ? *P.n_recs_dev : P.n_recs;   // device-indexed blocks: the count lives in device memory
     const uint32_t pieces = P.prefix_pieces;  // 16-byte pieces staged per record
@@ -723,6 +862,8 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
     if (tid < ST_USED) lds_delta[tid] = 0;
     if constexpr (HIST)
         for (uint32_t i = tid; i < 2u * P.hist_lds_bins; i += TILED_THREADS) hist_lds[i] = 0u;
+    if constexpr (MISM)
+        for (uint32_t i = tid; i < (P.mism_hist ? 2u * (P.mism_hist + 2u) : 0u); i += TILED_THREADS) hist_lds[i] = 0u;
     if constexpr (SITE)
         for (uint32_t i = tid; i < SITE_WORDS; i += TILED_THREADS) site_lds[i] = 0u;
     if constexpr (END)
@@ -884,6 +1025,14 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
 #pragma unroll
             for (int k = 0; k < 6; k++) rr[k] = qs[k];
         }
+        // -n / -N: this lane's half of the whole-read compare -- the left-end lane takes read bases 0 .. cut - 1, the right-end
+        // lane cut .. min(L, l_seq) - 1 (a candidate is staged through QUAL[0], so all of SEQ is in `stage`)
+        [[maybe_unused]] uint32_t mm = 0u;
+        if constexpr (MISM) {
+            const uint32_t n_cmp = min(pl.L, h.l_seq);
+            const uint32_t cut = min(n_cmp, ((n_cmp >> 1) + 7u) & ~7u);
+            if (cand) mm = count_mismatches_staged(P.genome4, pl.gbase + (uint64_t)pl.s, stage, src.off + h.seq_off, e ? cut : 0u, e ? n_cmp : cut, P.mism_tv != 0u);
+        }
         // -Q: the QUAL bytes of the same read bases, one byte per window position: byte b <-> QUAL[n0 + b] (left,
         // pass 0: bytes 0,1 are the last SEQ bytes and belong to the context positions, which CODES-B overwrites).
         // 32 bytes at any alignment = nine aligned dwords; n0 >= -31 and QUAL starts at least 36 bytes into the
@@ -960,7 +1109,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         if (in_tile && !in_stage && e == 0u) {
             if constexpr (KPLANES) ev_over = tally_overflow_record_kmer_planes<PLANES, LDS_KMER, REGIONS>(kernarg, gk, o0, o1, lds_kmer);
             else if constexpr (GROUPED) ev_over = tally_overflow_record_planes<PLANES, MASKQ, REGIONS>(kernarg, gk, o0, o1, table);
-            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS, HIST, SITE, END, GAPPED>(kernarg, o0, o1, table, lds_kmer, hist_lds, site_lds, end_lds);
+            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS, HIST, SITE, END, GAPPED, MISM>(kernarg, o0, o1, table, lds_kmer, hist_lds, site_lds, end_lds);
             if (pass0) atomicAdd(&lds_delta[ST_SLOW_PATH], 1);
         }
         // First use of the gathered registers happens HERE, before the next tile's DMA is issued:
@@ -989,6 +1138,13 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         if constexpr (MASKQ) {   // the QUAL bytes are in registers before `stage` is released to the next tile's DMA
 #pragma unroll
             for (int k = 0; k < 9; k++) asm volatile("" : "+v"(qq[k]));
+        }
+        if constexpr (MISM) {
+            // the compare's genome dwords are used up here as well; the pair's two halves make the read's count (every lane
+            // takes part in the exchange), and a read beyond the limit is no candidate from here on
+            asm volatile("" : "+v"(mm));
+            mm += (uint32_t)__shfl_xor((int)mm, 1);
+            if (mism_beyond(P, mm)) pl.pss_cand = false;
         }
         if constexpr (REGIONS) {
             // -T, resolved here for the same reason: its interval loads must not wait behind the DMA.  A candidate that
@@ -1246,6 +1402,10 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
             // -H: both lanes of a pair hold the same decision; the left-end lane counts the read (a record that took
             // the out-of-line path counted itself there and is no candidate here)
             if constexpr (HIST) hist_wave_add(P, hist_lds, e == 0u, pl.L, pl.pss_fwd, pl.pss_rev);
+            // -N: the same for the mismatch bin (P.mism_hist is the same in every lane)
+            if constexpr (MISM) {
+                if (P.mism_hist) mism_wave_add(P, hist_lds, e == 0u, mism_bin(P, mm), pl.pss_fwd, pl.pss_rev);
+            }
         }
         // (no barrier: wave w wrote the sheet rows of reads 32w .. 32w+31 -- j = tid >> 1 -- and its
         //  COLUMNS pass below reads exactly those rows)
@@ -1379,6 +1539,13 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         for (uint32_t i = tid; i < 2u * P.hist_lds_bins; i += TILED_THREADS) {
             const uint32_t v = hist_lds[i];
             if (v) atomicAdd(&P.counters[P.off_hist + (i < P.hist_lds_bins ? i : P.hist_max + 2u + (i - P.hist_lds_bins))], (unsigned long long)v);
+        }
+    }
+    if constexpr (MISM) {
+        // [mf | mr] lie in LDS as they lie in the counter block: a few bins are non-zero, the workgroup adds those itself
+        for (uint32_t i = tid; i < (P.mism_hist ? 2u * (P.mism_hist + 2u) : 0u); i += TILED_THREADS) {
+            const uint32_t v = hist_lds[i];
+            if (v) atomicAdd(&P.counters[P.off_mism + i], (unsigned long long)v);
         }
     }
 }
@@ -1909,8 +2076,9 @@ __global__ void __launch_bounds__(256) reduce_partials(const TallyParams P, uint
 // SITE: one more static object, the 2 KiB in-context table
 // END: behind the staging buffer the conditional tables and reads[4], end_lds_bytes(N + 2) (never together with HIST)
 // GAPPED: nothing more in LDS (the CIGAR walk reads the staged prefix)
+// MISM: behind the staging buffer the 2 * (P.mism_hist + 2) words of the mismatch histogram, where HIST has its bins (never together)
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS = false, bool MASKQ = false, bool REGIONS = false, bool HIST = false,
-          bool SITE = false, bool END = false, bool GAPPED = false>
+          bool SITE = false, bool END = false, bool GAPPED = false, bool MISM = false>
 __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
@@ -1921,7 +2089,7 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P
     __shared__ uint4 refs_lds[REF_LDS_ENTRIES + 1];
     // the kernel's single argument, as it lies in the kernarg segment (for the out-of-line path)
     const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
-    uint32_t *hist_lds = HIST ? (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces)) : nullptr;
+    uint32_t *hist_lds = (HIST || MISM) ? (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces)) : nullptr;
     if constexpr (SITE) {
         __shared__ uint32_t site_lds[SITE_WORDS];
         tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, true>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
@@ -1931,7 +2099,7 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P
         tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, false, true>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
                                                                                                              lds_delta, refs_lds, nullptr, nullptr, hist_lds, nullptr, end_lds);
     } else
-    tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, false, false, GAPPED>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
+    tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, false, false, GAPPED, MISM>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
                                                                                                                   lds_delta, refs_lds, nullptr, nullptr, hist_lds);
 }
 

@@ -32,6 +32,7 @@ int frontend_group_by_rg = 0;
 int frontend_n_length_edges = 0;
 int frontend_min_base_quality = 0;
 int frontend_length_hist = 0;
+int frontend_mismatch_hist = 0, frontend_max_mismatches = -1, frontend_mismatch_tv = 0;
 int frontend_site_context = PSSBAM_SITE_NONE;
 int frontend_end_depth = 0, frontend_end_cell5 = 0, frontend_end_cell3 = 0;
 int frontend_gapped_reads = 0;
@@ -74,6 +75,7 @@ static struct early_feed {
     int n_rg;
     int min_bq;                     /* -Q: the minimum base quality, set on every engine after create */
     int hist;                       /* -H: the limit of the length histogram, set on every engine after create */
+    int mism_hist, mism_max, mism_tv; /* -N / -n / -V: the mismatch count, set on every engine after create */
     int site;                       /* -X: the site context, set on every engine after create */
     int end_depth, end_cell5, end_cell3; /* -E: the end condition, set on every engine after create */
     int gapped;                     /* -I: anchored ends, set on every engine after create */
@@ -159,6 +161,7 @@ static void *engine_make_main(void *arg)
         pssbam_engine_feed_open(*j->out, j->n_ref, EF.fasta_bytes) ||
         (EF.min_bq > 0 && pssbam_engine_set_min_base_quality(*j->out, EF.min_bq)) ||
         (EF.hist > 0 && pssbam_engine_set_length_histogram(*j->out, EF.hist)) ||
+        ((EF.mism_hist > 0 || EF.mism_max >= 0) && pssbam_engine_set_mismatches(*j->out, EF.mism_hist, EF.mism_max, EF.mism_tv)) ||
         (EF.site != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(*j->out, EF.site)) ||
         (EF.end_depth > 0 && pssbam_engine_set_end_condition(*j->out, EF.end_depth, EF.end_cell5, EF.end_cell3)) ||
         (EF.gapped && pssbam_engine_set_gapped_reads(*j->out, 1)) || send_regions(*j->out, EF.regions) ||
@@ -290,6 +293,9 @@ void frontend_warmup_start(const pssbam_config *cfg, const char *aln_path, const
             EF.n_edges = frontend_n_length_edges;
             EF.min_bq = frontend_min_base_quality;
             EF.hist = frontend_length_hist;
+            EF.mism_hist = frontend_mismatch_hist;
+            EF.mism_max = frontend_max_mismatches;
+            EF.mism_tv = frontend_mismatch_tv;
             EF.site = frontend_site_context;
             EF.end_depth = frontend_end_depth;
             EF.end_cell5 = frontend_end_cell5;
@@ -317,6 +323,7 @@ static int same_length_bins(void)
 {
     return EF.n_edges == frontend_n_length_edges && EF.sets == frontend_contig_sets && EF.min_bq == frontend_min_base_quality &&
            EF.hist == frontend_length_hist && EF.site == frontend_site_context &&
+           EF.mism_hist == frontend_mismatch_hist && EF.mism_max == frontend_max_mismatches && EF.mism_tv == frontend_mismatch_tv &&
            EF.end_depth == frontend_end_depth && EF.end_cell5 == frontend_end_cell5 && EF.end_cell3 == frontend_end_cell3 &&
            EF.gapped == frontend_gapped_reads && EF.per_contig == frontend_per_contig && EF.regions == frontend_regions &&
            memcmp(EF.edges, frontend_length_edges, (size_t)frontend_n_length_edges * sizeof *EF.edges) == 0;
@@ -454,6 +461,8 @@ void run_result_free(run_result *res)
     free(res->plane_k3);
     free(res->hist_fwd);
     free(res->hist_rev);
+    free(res->mism_fwd);
+    free(res->mism_rev);
     free(res->site_fwd);
     free(res->site_rev);
     free(res->end_fwd);
@@ -657,6 +666,8 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             if (pssbam_engine_create(&c, &eng[g]) ||
                 (frontend_min_base_quality > 0 && pssbam_engine_set_min_base_quality(eng[g], frontend_min_base_quality)) ||
                 (frontend_length_hist > 0 && pssbam_engine_set_length_histogram(eng[g], frontend_length_hist)) ||
+                ((frontend_mismatch_hist > 0 || frontend_max_mismatches >= 0) &&
+                 pssbam_engine_set_mismatches(eng[g], frontend_mismatch_hist, frontend_max_mismatches, frontend_mismatch_tv)) ||
                 (frontend_site_context != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(eng[g], frontend_site_context)) ||
                 (frontend_end_depth > 0 && pssbam_engine_set_end_condition(eng[g], frontend_end_depth, frontend_end_cell5, frontend_end_cell3)) ||
                 (frontend_gapped_reads && pssbam_engine_set_gapped_reads(eng[g], 1)) ||
@@ -846,6 +857,16 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
         res->hist_rev = (uint64_t *)calloc((size_t)res->hist_max + 2, sizeof(uint64_t));
         if (!res->hist_fwd || !res->hist_rev) { fprintf(stderr, "Error: out of memory\n"); goto done; }
         if (pssbam_engine_finish_length_histogram(eng[0], res->hist_fwd, res->hist_rev)) {
+            fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+            goto done;
+        }
+    }
+    if (frontend_mismatch_hist > 0 && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -N: summed with the rest of the block */
+        res->mism_max = frontend_mismatch_hist;
+        res->mism_fwd = (uint64_t *)calloc((size_t)res->mism_max + 2, sizeof(uint64_t));
+        res->mism_rev = (uint64_t *)calloc((size_t)res->mism_max + 2, sizeof(uint64_t));
+        if (!res->mism_fwd || !res->mism_rev) { fprintf(stderr, "Error: out of memory\n"); goto done; }
+        if (pssbam_engine_finish_mismatches(eng[0], res->mism_fwd, res->mism_rev)) {
             fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
             goto done;
         }

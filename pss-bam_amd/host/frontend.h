@@ -27,6 +27,10 @@ typedef struct run_result {
      * table, hist_max + 2 rows each (row hist_max + 1: every longer read), or NULL */
     int hist_max;
     uint64_t *hist_fwd, *hist_rev;
+    /* pss-bam -N (frontend_mismatch_hist): the mismatch histogram of the reads added to the forward / reverse table,
+     * mism_max + 2 rows each (row mism_max + 1: every larger count), or NULL */
+    int mism_max;
+    uint64_t *mism_fwd, *mism_rev;
     /* pss-bam -X (frontend_site_context): the in-context tables IN, (region_len+2)*16 each with rows 0/1 as fwd / rev,
      * or NULL */
     unsigned long *site_fwd, *site_rev;
@@ -51,6 +55,11 @@ extern int frontend_min_base_quality;
 /* pss-bam -H: the limit of the fragment-length histogram (0: off); every engine gets it
  * (pssbam_engine_set_length_histogram) and run_tally() returns the two arrays.  Set before frontend_warmup_start. */
 extern int frontend_length_hist;
+
+/* pss-bam -N / -n / -V: the limit of the mismatch histogram (0: off), the largest mismatch count of a tallied read (-1: no
+ * filter) and whether only transversions count; every engine gets them (pssbam_engine_set_mismatches) and run_tally()
+ * returns the two arrays of the histogram.  Set before frontend_warmup_start. */
+extern int frontend_mismatch_hist, frontend_max_mismatches, frontend_mismatch_tv;
 
 /* pss-bam -X: the site context (PSSBAM_SITE_*; PSSBAM_SITE_NONE: off); every engine gets it
  * (pssbam_engine_set_site_context) and run_tally() returns the in-context pair.  Set before frontend_warmup_start. */

@@ -44,6 +44,12 @@
  * order, the rows of the counts file this command writes with -F reduced to that contig, each behind the contig's name and
  * "fwd" or "rev" (report.h) -- any number of contigs, one pass, no map file; the other files stay as they are.  The reads
  * of RNAME "*" come last, as "*".  Goes with -R, -Q and -T.  Not with -G, -S, -C, -H, -X, -E or -I.
+ * Added: -n <k> tallies only the reads with at most k (0..255) mismatches against the reference over their whole length -- the
+ * files are what this command writes without -n for the input without the reads beyond k; -N <M> (1..255) also writes
+ * <prefix>.pss.mismatches.txt, how many of the reads added to the forward / reverse table have 0, 1, ..., M and more than M
+ * mismatches, from the same pass; -V, with either, counts only transversions (deamination makes none).  A position counts
+ * when read and reference base are both one of A C G T.  Needs -r <= 30.  Goes with -R, -Q and -T.  Not with -G, -S, -C, -H, -X,
+ * -E, -I or -A.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -60,6 +66,7 @@
 #include "frontend.h"
 #include "length_bins.h"
 #include "length_hist.h"
+#include "mismatches.h"
 #include "read_groups.h"
 #include "regions.h"
 #include "report.h"
@@ -69,13 +76,14 @@ int main(int argc, char *argv[])
     const double age_main = frontend_process_age_s();
     frontend_detach_start();   /* the caller gets its prompt back when the reports are written, not when 30 GB of device buffers are gone */
     const double t_main = frontend_now_s();
-    int region_len = 15, min_mq = 0, merged_only = 0, by_group = 0, gapped = 0, per_contig = 0, option;
+    int region_len = 15, min_mq = 0, merged_only = 0, by_group = 0, gapped = 0, per_contig = 0, tv_only = 0, option;
     unsigned long min_read_len = 0, max_read_len = 250000000;
     const char *up_ctx = "ACGT", *down_ctx = "ACGT";
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL, *read_group = NULL;
     const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL, *bed_fn = NULL, *hist_arg = NULL, *site_arg = NULL, *end_arg = NULL;
+    const char *max_mm_arg = NULL, *mm_hist_arg = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IA")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:V")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -97,6 +105,9 @@ int main(int argc, char *argv[])
         case 'E': end_arg = optarg; break;
         case 'I': gapped = 1; break;
         case 'A': per_contig = 1; break;
+        case 'n': max_mm_arg = optarg; break;
+        case 'N': mm_hist_arg = optarg; break;
+        case 'V': tv_only = 1; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -128,7 +139,10 @@ int main(int argc, char *argv[])
               "-m <only consider merged reads>\n"
               "-E <ss|ds>[,<d>] <also write the tables of each end over the reads damaged within d bases (default: 1) of the other end>\n"
               "-I <also tally clipped and gapped reads, by the matched runs at their two ends>\n"
-              "-A <also write the tables of every contig of the input, one pass for any number of contigs>\n",
+              "-A <also write the tables of every contig of the input, one pass for any number of contigs>\n"
+              "-n <k> <only tally the reads with at most k mismatches against the reference (0..255)>\n"
+              "-N <M> <also write how many tallied reads have 0, 1, ..., M and more than M mismatches (1..255)>\n"
+              "-V <with -n / -N: count only transversions>\n",
               stderr);
         exit(1);
     }
@@ -218,6 +232,32 @@ int main(int argc, char *argv[])
                 : end_arg ? "-E (tables conditional on the other end)" : "-I (clipped and gapped reads by their anchored ends)");
         exit(1);
     }
+    int max_mm = -1, mm_hist = 0;
+    if (tv_only && !max_mm_arg && !mm_hist_arg) {
+        fprintf(stderr, "-V (count only transversions) needs -n (mismatch filter) or -N (mismatch histogram).\n");
+        exit(1);
+    }
+    if (max_mm_arg || mm_hist_arg) {
+        const char *mine = !mm_hist_arg ? "-n (mismatch filter)" : !max_mm_arg ? "-N (mismatch histogram)" : "-n / -N (mismatch filter and histogram)";
+        if (by_group || len_edges || ctg_map || hist_arg || site_arg || end_arg || gapped || per_contig) {
+            fprintf(stderr, "%s and %s exclude each other.\n", mine,
+                    by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)" : ctg_map ? "-C (tables per contig set)"
+                    : hist_arg ? "-H (fragment-length histogram)" : site_arg ? "-X (tables per site context)"
+                    : end_arg ? "-E (tables conditional on the other end)" : gapped ? "-I (clipped and gapped reads by their anchored ends)"
+                    : "-A (tables per contig)");
+            exit(1);
+        }
+        char err[200];
+        if ((max_mm_arg && (max_mm = pss_parse_max_mismatches(max_mm_arg, err, sizeof err)) < 0) ||
+            (mm_hist_arg && (mm_hist = pss_parse_mismatch_hist(mm_hist_arg, err, sizeof err)) < 0)) {
+            fprintf(stderr, "%s\n", err);
+            exit(1);
+        }
+        if (region_len > 30) {
+            fprintf(stderr, "%s needs -r <= 30 (a read's fate is decided in the one pass over 32 table rows), not -r %d.\n", mine, region_len);
+            exit(1);
+        }
+    }
     pss_regions bed;
     memset(&bed, 0, sizeof bed);
     if (bed_fn) {
@@ -276,6 +316,9 @@ int main(int argc, char *argv[])
     if (end_arg) fprintf(stderr, " -E %s", end_arg);
     if (gapped) fprintf(stderr, " -I");
     if (per_contig) fprintf(stderr, " -A");
+    if (max_mm_arg) fprintf(stderr, " -n %d", max_mm);
+    if (mm_hist_arg) fprintf(stderr, " -N %d", mm_hist);
+    if (tv_only) fprintf(stderr, " -V");
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -305,6 +348,9 @@ int main(int argc, char *argv[])
     frontend_end_cell3 = end_cell3;
     frontend_gapped_reads = gapped;
     frontend_per_contig = per_contig;
+    frontend_mismatch_hist = mm_hist;
+    frontend_max_mismatches = max_mm;
+    frontend_mismatch_tv = tv_only;
     if (bed_fn) frontend_regions = &bed;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
@@ -330,6 +376,7 @@ int main(int argc, char *argv[])
     pss_write_counts(fasta_fn, bam_fn, out_prefix, region_len, res.fwd, res.rev);
     pss_write_rates(fasta_fn, bam_fn, out_prefix, region_len, fwd_rates, rev_rates);
     if (res.hist_fwd && pss_write_lengths(fasta_fn, bam_fn, out_prefix, res.hist_max, res.hist_fwd, res.hist_rev)) exit(1);
+    if (res.mism_fwd && pss_write_mismatches(fasta_fn, bam_fn, out_prefix, res.mism_max, tv_only, res.mism_fwd, res.mism_rev)) exit(1);   /* -N */
     if (res.site_fwd) {   /* -X: IN as the engine returns it; OUT = T - IN on the position rows, the context rows as T */
         const size_t cells = (size_t)(region_len + 2) * 16;
         unsigned long *out_fwd = (unsigned long *)malloc(cells * sizeof *out_fwd), *out_rev = (unsigned long *)malloc(cells * sizeof *out_rev);

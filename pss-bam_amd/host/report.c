@@ -214,6 +214,26 @@ int pss_write_lengths(const char *fasta_fn, const char *bam_fn, const char *out_
     return fclose(fp) ? 1 : 0;
 }
 
+int pss_write_mismatches(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int max_mm, int transversions_only,
+                         const uint64_t *fwd, const uint64_t *rev)
+{
+    char fn[FN_BUF + 1];
+    FILE *fp;
+    snprintf(fn, sizeof fn, "%s.pss.mismatches.txt", out_prefix);
+    fp = fopen(fn, "w");
+    if (!fp) {
+        fprintf(stderr, "ERROR: Cannot write to file %s\n.", fn);
+        return 1;
+    }
+    fprintf(fp, "# mismatches (%s) of the reads added to the forward / reverse table\n# FASTA: %s\n# BAM: %s\n",
+            transversions_only ? "transversions only" : "all", fasta_fn, bam_fn);
+    fputs("mismatches\tfwd\trev\n", fp);
+    for (int m = 0; m <= max_mm; m++)
+        fprintf(fp, "%d\t%llu\t%llu\n", m, (unsigned long long)fwd[m], (unsigned long long)rev[m]);
+    fprintf(fp, ">%d\t%llu\t%llu\n", max_mm, (unsigned long long)fwd[max_mm + 1], (unsigned long long)rev[max_mm + 1]);
+    return fclose(fp) ? 1 : 0;
+}
+
 int fragkon_write_table(FILE *out, const char *fasta_fn, const char *bam_fn, int klen, const uint64_t *k5,
                         const uint64_t *k3)
 {

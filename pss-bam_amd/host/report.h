@@ -33,6 +33,12 @@ int pss_write_end_reads(const char *out_prefix, const uint64_t reads[4]);
  * longer read; fwd / rev hold max_len + 2 counts.  Returns 0, or 1 after a diagnostic. */
 int pss_write_lengths(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int max_len, const uint64_t *fwd,
                       const uint64_t *rev);
+/* pss-bam -N: <out_prefix>.pss.mismatches.txt, in the layout of the lengths file -- three '#' lines (the first says whether all
+ * mismatches or transversions only were counted), the column names, then one tab-separated line "<mismatches> <fwd> <rev>"
+ * per count 0..max_mm (zero rows included) and a last one labelled "><max_mm>" for every larger count; fwd / rev hold
+ * max_mm + 2 counts.  Returns 0, or 1 after a diagnostic. */
+int pss_write_mismatches(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int max_mm, int transversions_only,
+                         const uint64_t *fwd, const uint64_t *rev);
 /* k5 / k3: 4^klen 64-bit bins (clamped to UINT_MAX on output) */
 int fragkon_write_table(FILE *out, const char *fasta_fn, const char *bam_fn, int klen, const uint64_t *k5,
                         const uint64_t *k3);
