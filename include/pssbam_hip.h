@@ -36,6 +36,7 @@ extern "C" {
 #define PSSBAM_MAX_READ_GROUPS 4096  /* pssbam_engine_set_read_groups */
 #define PSSBAM_MAX_LENGTH_BINS 64    /* pssbam_engine_set_length_bins: at most 63 edges */
 #define PSSBAM_MAX_CONTIG_SETS 4096  /* pssbam_engine_set_contig_sets */
+#define PSSBAM_MAX_REPLICATES 64     /* pssbam_engine_set_replicates */
 #define PSSBAM_MAX_MISMATCHES 255    /* pssbam_engine_set_mismatches: the largest histogram limit and the largest filter limit */
 #define PSSBAM_MAX_HIST_LENGTH 65535 /* pssbam_engine_set_length_histogram: the largest limit (lengths above it share one row) */
 #define PSSBAM_MAX_BASE_QUALITY 93   /* pssbam_engine_set_min_base_quality: the largest Phred value SAM text can print */
@@ -202,7 +203,8 @@ int pssbam_engine_set_read_groups(pssbam_engine *e, int32_t n, const char *const
 /* Drains the engine like pssbam_engine_finish and copies one group's two tables ((region_len+2)*16 each, any
  * pointer may be NULL): group -1 is the unassigned bucket, 0..n-1 the IDs in the order given.  With length bins
  * (below) group k is bin k and group -1 is all zeros.  With contig sets (below) group s is set s and group -1
- * holds the records on contigs no set lists. */
+ * holds the records on contigs no set lists.  With replicates (below) group j is replicate j and group -1 is all
+ * zeros. */
 int pssbam_engine_finish_groups(pssbam_engine *e, int32_t group, unsigned long *fwd, unsigned long *rev);
 
 /* K-mer planes (fragkon -G / -S / -C).  An engine whose tally_mask is PSSBAM_TALLY_KMER alone takes the three
@@ -250,6 +252,30 @@ int pssbam_engine_set_length_bins(pssbam_engine *e, int32_t n_edges, const uint3
  * pssbam_engine_finish_groups(e, s, ...) returns set s. */
 int pssbam_engine_set_contig_sets(pssbam_engine *e, int32_t n_sets, int64_t n_names, const char *const *names,
                                   const int32_t *set_of);
+
+/* Read-name replicates (pss-bam -J): K sets of substitution tables, each over a random K-th of the reads, in a single
+ * pass over the records -- the planes a delete-one-group jackknife needs, instead of K runs on K hand-made subsets.
+ * k = K in 2..PSSBAM_MAX_REPLICATES; k = 0 switches the setting off, and the engine then launches exactly the kernels
+ * it launches without it.  The replicate of a record is a hash of its read name: with n = l_read_name - 1 (0 when
+ * l_read_name <= 1) and b[0..n) the name bytes as stored from record offset 36 on (an embedded NUL is a byte like any
+ * other),
+ *     h = 2166136261
+ *     for i = 0, 4, 8, ... < n:  h = (h ^ (b[i] | b[i+1] << 8 | b[i+2] << 16 | b[i+3] << 24)) * 16777619   (b[>= n] = 0)
+ *     h ^= n;  h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16              (all mod 2^32)
+ *     replicate = (uint64(h) * K) >> 32
+ * ("" -> h = 0xab3e7c0b, "a" -> 0x2a681819, "read/1" -> 0x9d5b3ad0, "r0000000" -> 0x4620f828).  Mates share a name and
+ * so a replicate.  Replicate j is plane 1 + j and receives exactly what the same engine tallies on the input reduced
+ * to the records of replicate j; plane 0 stays empty, as with length bins, and the counter block is the length-bin
+ * layout with K planes: [fwd | rev | stats | fwd_0 | rev_0 | ... | fwd_K-1 | rev_K-1], summed across engines as one u64
+ * array.  pssbam_engine_finish keeps returning the totals over every record and the status counters of the engine
+ * without the setting; pssbam_engine_finish_groups(e, j, ...) returns replicate j, group -1 all zeros.  Legal after
+ * create (or reset) and before the first tally launch (after pssbam_engine_feed_open: before set_references); goes
+ * with cfg.read_group, a minimum base quality and regions.  PSSBAM_EINVAL for k = 1 or outside 0..64, with
+ * PSSBAM_TALLY_KMER in the mask, and with read groups, length bins, contig sets, per-contig tables, a length histogram,
+ * site context, an end condition, gapped reads or the mismatch count set (those setters return PSSBAM_EINVAL, "... and
+ * replicates exclude each other", once this one is on); PSSBAM_ESTATE once records have been tallied or the counter
+ * block has been bound.  The setting survives pssbam_engine_reset. */
+int pssbam_engine_set_replicates(pssbam_engine *e, int32_t k);
 
 /* Per-contig tables (pss-bam -A): every reference sequence's own pair of substitution tables in a single pass over the
  * records, for any number of references (a metagenomic BAM has 10^4 .. 10^6), without a map file.  Plane k belongs to

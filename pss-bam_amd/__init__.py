@@ -46,11 +46,12 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_site_context", "pssbam_engine_finish_site_context",
     "pssbam_engine_set_end_condition", "pssbam_engine_finish_end_condition", "pssbam_engine_set_gapped_reads",
     "pssbam_engine_set_per_contig", "pssbam_engine_finish_contigs",
-    "pssbam_engine_set_mismatches", "pssbam_engine_finish_mismatches",
+    "pssbam_engine_set_mismatches", "pssbam_engine_finish_mismatches", "pssbam_engine_set_replicates",
 ]
 MAX_READ_GROUPS = 4096
 MAX_LENGTH_BINS = 64
 MAX_CONTIG_SETS = 4096
+MAX_REPLICATES = 64
 MAX_BASE_QUALITY = 93
 MAX_HIST_LENGTH = 65535
 MAX_MISMATCHES = 255
@@ -133,6 +134,7 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_finish_end_condition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_gapped_reads.argtypes = [C.c_void_p, C.c_int32]
     L.pssbam_engine_set_per_contig.argtypes = [C.c_void_p, C.c_int32]
+    L.pssbam_engine_set_replicates.argtypes = [C.c_void_p, C.c_int32]
     L.pssbam_engine_set_mismatches.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     L.pssbam_engine_finish_mismatches.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_finish_contigs.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -219,6 +221,8 @@ class Engine:
     `per_contig` = True (pss-bam -A): every BAM reference's own pair of substitution tables, see set_per_contig.
     `mismatches` = (hist_max, max_mismatches, tv_only) (pss-bam -N / -n / -V): the histogram of, and a filter on, the
     number of mismatches between the whole read and the reference, see set_mismatches; None = off.
+    `replicates` = K (pss-bam -J): one set of substitution tables per read-name replicate, the planes of a delete-one-group
+    jackknife, see set_replicates; 0 = off.
     With `kmer` alone (no `pss`) the three split the k-mer tables instead (fragkon -G / -S / -C): every plane is a
     k5 / k3 pair, and the length bins go by the SEQ length and kmer's min_read_len / max_read_len."""
 
@@ -226,7 +230,8 @@ class Engine:
                  kernel: int = KERNEL_AUTO, device: int = -1, read_groups: list[str] | None = None,
                  length_bins: list[int] | None = None, contig_sets=None, min_base_qual: int = 0,
                  length_hist: int = 0, site_context: str | None = None, end_condition: tuple[int, int, int] | None = None,
-                 gapped: bool = False, per_contig: bool = False, mismatches: tuple[int, int, int] | None = None):
+                 gapped: bool = False, per_contig: bool = False, mismatches: tuple[int, int, int] | None = None,
+                 replicates: int = 0):
         L = hip_lib()
         cfg = _Config()
         cfg.abi_version = 1
@@ -288,6 +293,9 @@ class Engine:
             self.set_length_bins(length_bins)
         if contig_sets is not None:
             self.set_contig_sets(contig_sets)
+        self._replicates = 0
+        if replicates:
+            self.set_replicates(replicates)
 
     def set_min_base_quality(self, q: int):
         """pss-bam -Q: a read base whose Phred quality is below q (0..93, 0 = off) adds nothing to the substitution
@@ -495,6 +503,31 @@ class Engine:
         lo, hi = self._len_range
         starts, ends = [lo] + edges, [x - 1 for x in edges] + [hi]
         self.length_bins = list(zip(starts, ends))
+
+    def set_replicates(self, k: int):
+        """pss-bam -J: tallies every record into the tables of its replicate among k (2..MAX_REPLICATES; 0 switches it
+        off), picked by a hash of its read name (include/pssbam_hip.h), so mates share one: replicate j holds what the
+        same engine tallies on the input reduced to its records.  finish() stays the total, finish_replicates()
+        returns the planes.  Goes with read_group, min_base_qual and regions; not with kmer, read groups, length bins,
+        contig sets, per-contig tables, the length histogram, site context, the end condition, gapped reads or the
+        mismatch count.  Before the first tally (after feed_open: before set_references) and before bind_counters: the
+        counter block grows by k * 2 * (region_len + 2) * 16 words.  Survives reset."""
+        _chk(self._L.pssbam_engine_set_replicates(self._h, int(k)))
+        self._replicates = int(k)
+
+    @property
+    def replicates(self) -> int:
+        """the number of read-name replicates in force (0 = off)"""
+        return self._replicates
+
+    def finish_replicates(self) -> tuple[np.ndarray, np.ndarray]:
+        """(fwd, rev): the replicates' tables stacked, (k, region_len + 2, 16) u64 each (drains like finish)"""
+        if not self._replicates:
+            raise PssbamError("set_replicates has not been called")
+        planes = self._finish_planes(enumerate(range(self._replicates)))
+        fwd = np.stack([planes[j].fwd for j in range(self._replicates)])
+        rev = np.stack([planes[j].rev for j in range(self._replicates)])
+        return fwd, rev
 
     def set_read_groups(self, ids: list[str]):
         """pss-bam -G: tallies every record into the tables of the ID its first RG:Z value equals (the unassigned
@@ -725,6 +758,10 @@ class Engine:
         lay["contig_sets"] = [{"label": s, "fwd": base + k * 2 * rows * 16, "rev": base + k * 2 * rows * 16 + rows * 16}
                               for k, s in enumerate(self.contig_sets)]
         lay["n_u64"] = base + (len(self.read_groups) + len(self.length_bins) + len(self.contig_sets)) * 2 * rows * 16
+        if self._replicates:   # read-name replicates (never together with the other planes): replicate j's pair sits where bin j's would
+            lay["replicates"] = [{"replicate": j, "fwd": base + j * 2 * rows * 16, "rev": base + j * 2 * rows * 16 + rows * 16}
+                                 for j in range(self._replicates)]
+            lay["n_u64"] = base + self._replicates * 2 * rows * 16
         if self._per_contig:   # a plane per reference (never together with the other planes): plane k = refID k, k = n_ref: refID -1
             n_planes = 0 if self._n_ref is None else self._n_ref + 1   # (the block is sized once the count is known)
             lay["contigs"] = {"first": base, "plane_words": 2 * rows * 16, "n_planes": n_planes,

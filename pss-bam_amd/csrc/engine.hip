@@ -201,7 +201,7 @@ struct pssbam_engine {
     // -R
     uint8_t *d_rg = nullptr;
     // -G / -S / -C: n_planes [fwd | rev] planes of the counter block behind the stats (set_planes); plane 1 + g holds
-    // read group g (pssbam_engine_set_read_groups), length bin g (pssbam_engine_set_length_bins) or contig set g
+    // read group g (pssbam_engine_set_read_groups), length bin g (pssbam_engine_set_length_bins), replicate g (pssbam_engine_set_replicates) or contig set g
     // (pssbam_engine_set_contig_sets)
     PlaneSel planes = PLANES_NONE;
     uint32_t n_planes = 0, off_groups = 0, plane_words = 0;
@@ -925,6 +925,7 @@ template <class F>
 static int with_planes(PlaneSel sel, F f) {
     return sel == PLANES_RG    ? f(std::integral_constant<PlaneSel, PLANES_RG>{})
            : sel == PLANES_LEN ? f(std::integral_constant<PlaneSel, PLANES_LEN>{})
+           : sel == PLANES_HASH ? f(std::integral_constant<PlaneSel, PLANES_HASH>{})
                                : f(std::integral_constant<PlaneSel, PLANES_REF>{});
 }
 
@@ -1114,6 +1115,7 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         else if (e->planes != PLANES_NONE)
             with_planes(e->planes, [&](auto SEL) {
                 if (do_pss) hipLaunchKernelGGL(tally_simple_planes<SEL()>, dim3(blocks), dim3(256), 0, e->stream, P, G);
+                else if constexpr (SEL() == PLANES_HASH) return no_kernel();   // (replicates split the substitution tables only: set_replicates)
                 else hipLaunchKernelGGL(tally_simple_kmer_planes<SEL()>, dim3(blocks), dim3(256), 0, e->stream, P, G);
                 return PSSBAM_OK;
             });
@@ -1196,7 +1198,7 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                 }, pass > 0, maskq, regions);
             }
         } else if (e->planes != PLANES_NONE) {
-            // -G / -S / -C: every (32-row pass, plane pass) pair is one launch over the block.  A plane pass holds as many
+            // -G / -S / -C / -J: every (32-row pass, plane pass) pair is one launch over the block.  A plane pass holds as many
             // planes as fit the LDS beside the staging buffer, plus a trash plane; more planes take more passes, each
             // re-reading the records.  Substitution planes are 4 KiB each (8 = 32 KiB always fit: one pass for up to 7 groups
             // or sets, or 6 bins -- plane 0 of -S stays empty but keeps its slot).  K-mer planes (one row pass) are
@@ -1223,6 +1225,8 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                                 return launch_with_reduce(e, tally_tiled_planes<SEL(), LATER(), MASKQ(), REGIONS()>, reduce_partials_grouped, G.scratch_words,
                                                           tiled_grouped_lds_bytes(T, pieces, G.n_slots), n_tiles, P, std::tie(G));
                             }, pass > 0, maskq, regions);
+                        if constexpr (SEL() == PLANES_HASH) return no_kernel();   // (replicates split the substitution tables only: set_replicates)
+                        else
                         return with_flags([&](auto LDS_KMER, auto REGIONS) {
                             return launch_with_reduce(e, tally_tiled_kmer_planes<SEL(), LDS_KMER(), REGIONS()>, reduce_partials_kmer_planes, G.scratch_words,
                                                       tiled_kmer_planes_lds_bytes(T, pieces, G.n_slots, c.kmer.klen, LDS_KMER()), n_tiles, P, std::tie(G),
@@ -1499,7 +1503,7 @@ extern "C" int pssbam_engine_finish_groups(pssbam_engine *e, int32_t group, unsi
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
     if (e->cfg.tally_mask == PSSBAM_TALLY_KMER) return fail(PSSBAM_EINVAL, "a k-mer engine's planes are read with pssbam_engine_finish_kmer_groups");
     const int32_t n_planes = (int32_t)e->n_planes;
-    if (!n_planes) return fail(PSSBAM_ESTATE, "none of pssbam_engine_set_read_groups / _set_length_bins / _set_contig_sets / _set_per_contig has been called");
+    if (!n_planes) return fail(PSSBAM_ESTATE, "none of pssbam_engine_set_read_groups / _set_length_bins / _set_contig_sets / _set_per_contig / _set_replicates has been called");
     if (group < -1 || group >= n_planes) return fail(PSSBAM_EINVAL, "group %d outside -1..%d", group, n_planes - 1);
     int rc = pssbam_engine_sync(e);
     if (rc) return rc;
@@ -1548,7 +1552,7 @@ static int grow_counters(pssbam_engine *e, uint64_t n_counters) {
     return PSSBAM_OK;
 }
 
-// What set_read_groups, set_length_bins and set_contig_sets share: the counter block grows to n_planes [fwd | rev] planes
+// What set_read_groups, set_length_bins, set_contig_sets and set_replicates share: the counter block grows to n_planes [fwd | rev] planes
 // (a k-mer engine: [k5 | k3]) behind the stats.  `what` names the caller's planes in the messages.
 static int set_planes(pssbam_engine *e, PlaneSel sel, uint32_t n_planes, const char *what) {
     if (e->per_contig) return fail(PSSBAM_EINVAL, "%s and per-contig tables exclude each other", what);
@@ -1584,6 +1588,7 @@ extern "C" int pssbam_engine_set_read_groups(pssbam_engine *e, int32_t n, const 
     if (e->has_rg) return fail(PSSBAM_EINVAL, "read groups and a -R read group filter exclude each other");
     if (e->planes == PLANES_LEN) return fail(PSSBAM_EINVAL, "read groups and length bins exclude each other");
     if (e->planes == PLANES_REF) return fail(PSSBAM_EINVAL, "read groups and contig sets exclude each other");
+    if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "read groups and replicates exclude each other");
     for (int32_t i = 0; i < n; i++)
         if (!ids[i]) return fail(PSSBAM_EINVAL, "read group %d is NULL", i);
     // ID table (concatenated) + open-addressing hash over it; a repeated ID keeps its first index
@@ -1646,6 +1651,7 @@ extern "C" int pssbam_engine_set_gapped_reads(pssbam_engine *e, int32_t on) {
     if (on) {
         if (e->cfg.tally_mask != PSSBAM_TALLY_PSS)
             return fail(PSSBAM_EINVAL, "gapped reads are tallied by their anchored ends in the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
+        if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "gapped reads and replicates exclude each other");
         if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "gapped reads and read groups / length bins / contig sets exclude each other");
         if (e->hist_max) return fail(PSSBAM_EINVAL, "gapped reads and the length histogram exclude each other");
         if (e->site_mode) return fail(PSSBAM_EINVAL, "gapped reads and site context exclude each other");
@@ -1662,6 +1668,7 @@ extern "C" int pssbam_engine_set_length_histogram(pssbam_engine *e, int32_t max_
     if (max_len < 0 || max_len > PSSBAM_MAX_HIST_LENGTH) return fail(PSSBAM_EINVAL, "length histogram limit %d outside 0..%d", max_len, PSSBAM_MAX_HIST_LENGTH);
     if (!(e->cfg.tally_mask & PSSBAM_TALLY_PSS))
         return fail(PSSBAM_EINVAL, "the length histogram counts the reads added to the substitution tables: the engine needs PSSBAM_TALLY_PSS");
+    if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "the length histogram and replicates exclude each other");
     if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the length histogram and read groups / length bins / contig sets exclude each other");
     if (e->site_mode) return fail(PSSBAM_EINVAL, "the length histogram and site context exclude each other");
     if (e->end_depth) return fail(PSSBAM_EINVAL, "the length histogram and the end condition exclude each other");
@@ -1701,6 +1708,7 @@ extern "C" int pssbam_engine_set_mismatches(pssbam_engine *e, int32_t hist_max, 
             return fail(PSSBAM_EINVAL, "the mismatch count filters the reads of the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
         if (e->cfg.pss.region_len > 30)
             return fail(PSSBAM_EINVAL, "the mismatch count needs a region length of at most 30 (the decision is taken in the one pass that holds all rows), not %d", e->cfg.pss.region_len);
+        if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "the mismatch count and replicates exclude each other");
         if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the mismatch count and read groups / length bins / contig sets / per-contig tables exclude each other");
         if (e->hist_max) return fail(PSSBAM_EINVAL, "the mismatch count and the length histogram exclude each other");
         if (e->site_mode) return fail(PSSBAM_EINVAL, "the mismatch count and site context exclude each other");
@@ -1737,6 +1745,7 @@ extern "C" int pssbam_engine_set_site_context(pssbam_engine *e, int32_t mode) {
     if (mode != PSSBAM_SITE_NONE && mode != PSSBAM_SITE_CPG) return fail(PSSBAM_EINVAL, "unknown site context %d", mode);
     if (e->cfg.tally_mask != PSSBAM_TALLY_PSS)
         return fail(PSSBAM_EINVAL, "site context splits the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
+    if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "site context and replicates exclude each other");
     if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "site context and read groups / length bins / contig sets exclude each other");
     if (e->hist_max) return fail(PSSBAM_EINVAL, "site context and the length histogram exclude each other");
     if (e->end_depth) return fail(PSSBAM_EINVAL, "site context and the end condition exclude each other");
@@ -1779,6 +1788,7 @@ extern "C" int pssbam_engine_set_end_condition(pssbam_engine *e, int32_t depth, 
     if (depth > e->cfg.pss.region_len) return fail(PSSBAM_EINVAL, "end condition depth %d beyond the region length %d", depth, e->cfg.pss.region_len);
     if (depth && e->cfg.pss.region_len > 30)
         return fail(PSSBAM_EINVAL, "the end condition needs a region length of at most 30 (one 32-row pass holds both ends' marks), not %d", e->cfg.pss.region_len);
+    if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "the end condition and replicates exclude each other");
     if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the end condition and read groups / length bins / contig sets exclude each other");
     if (e->hist_max) return fail(PSSBAM_EINVAL, "the end condition and the length histogram exclude each other");
     if (e->site_mode) return fail(PSSBAM_EINVAL, "the end condition and site context exclude each other");
@@ -1821,6 +1831,7 @@ extern "C" int pssbam_engine_set_length_bins(pssbam_engine *e, int32_t n_edges, 
         return fail(PSSBAM_EINVAL, "length bin edge count %d outside 1..%d", n_edges, PSSBAM_MAX_LENGTH_BINS - 1);
     if (e->planes == PLANES_RG) return fail(PSSBAM_EINVAL, "length bins and read groups exclude each other");
     if (e->planes == PLANES_REF) return fail(PSSBAM_EINVAL, "length bins and contig sets exclude each other");
+    if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "length bins and replicates exclude each other");
     // l < e1 < ... < ek <= L: every bin [l, e1-1], [e1, e2-1], ..., [ek, L] is a non-empty -l / -L window
     // (a k-mer engine: the window of fragkon's -l / -L, compared with strlen(SEQ))
     const bool kmer = e->cfg.tally_mask == PSSBAM_TALLY_KMER;
@@ -1837,6 +1848,28 @@ extern "C" int pssbam_engine_set_length_bins(pssbam_engine *e, int32_t n_edges, 
     return PSSBAM_OK;
 }
 
+// -J: K read-name replicates, planes 1 .. K of the -S layout (plane 0 stays empty); k = 0: the block and the launches of an
+// engine that never had the setting
+extern "C" int pssbam_engine_set_replicates(pssbam_engine *e, int32_t k) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (k < 0 || k == 1 || k > PSSBAM_MAX_REPLICATES) return fail(PSSBAM_EINVAL, "replicate count %d outside 2..%d (0 = off)", k, PSSBAM_MAX_REPLICATES);
+    if (k) {
+        if (e->cfg.tally_mask != PSSBAM_TALLY_PSS)
+            return fail(PSSBAM_EINVAL, "replicates split the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
+        if (e->planes == PLANES_RG) return fail(PSSBAM_EINVAL, "replicates and read groups exclude each other");
+        if (e->planes == PLANES_LEN) return fail(PSSBAM_EINVAL, "replicates and length bins exclude each other");
+        if (e->planes == PLANES_REF) return fail(PSSBAM_EINVAL, "replicates and contig sets exclude each other");
+        return set_planes(e, PLANES_HASH, (uint32_t)k, "replicates");   // (per-contig tables, -H, -X, -E, -I, -n / -N: refused there)
+    }
+    if (const int rc = check_may_resize(e, "replicates")) return rc;
+    if (e->planes != PLANES_HASH) return PSSBAM_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    if (const int rc = grow_counters(e, e->off_groups)) return rc;
+    e->planes = PLANES_NONE;
+    e->n_planes = 0;
+    return PSSBAM_OK;
+}
+
 extern "C" int pssbam_engine_set_contig_sets(pssbam_engine *e, int32_t n_sets, int64_t n_names, const char *const *names,
                                              const int32_t *set_of) {
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
@@ -1845,6 +1878,7 @@ extern "C" int pssbam_engine_set_contig_sets(pssbam_engine *e, int32_t n_sets, i
     if (n_names < 0 || (n_names && (!names || !set_of))) return fail(PSSBAM_EINVAL, "bad contig name list");
     if (e->planes == PLANES_RG) return fail(PSSBAM_EINVAL, "contig sets and read groups exclude each other");
     if (e->planes == PLANES_LEN) return fail(PSSBAM_EINVAL, "contig sets and length bins exclude each other");
+    if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "contig sets and replicates exclude each other");
     std::unordered_map<std::string, uint32_t> plane;
     plane.reserve((size_t)n_names);
     for (int64_t i = 0; i < n_names; i++) {
@@ -1920,6 +1954,7 @@ extern "C" int pssbam_engine_set_per_contig(pssbam_engine *e, int32_t on) {
     if (on) {
         if (e->cfg.tally_mask != PSSBAM_TALLY_PSS)
             return fail(PSSBAM_EINVAL, "per-contig tables split the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
+        if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "per-contig tables and replicates exclude each other");
         if (e->planes != PLANES_NONE && e->planes != PLANES_EACH) return fail(PSSBAM_EINVAL, "per-contig tables and read groups / length bins / contig sets exclude each other");
         if (e->hist_max) return fail(PSSBAM_EINVAL, "per-contig tables and the length histogram exclude each other");
         if (e->site_mode) return fail(PSSBAM_EINVAL, "per-contig tables and site context exclude each other");

@@ -320,7 +320,7 @@ struct PlaneParams {
     const uint32_t *id_offs;   // n_groups + 1 offsets into ids
     const uint32_t *hash;      // open addressing over FNV-1a of the ID: entry = group + 1, 0 = empty
     uint32_t hash_mask;        // entries - 1 (a power of two, at least twice n_groups)
-    uint32_t n_groups;         // planes behind plane 0: read groups, or length bins
+    uint32_t n_groups;         // planes behind plane 0: read groups, length bins, or -J's replicates (K)
     uint32_t plane0, n_slots;  // this launch tallies planes plane0 .. plane0 + n_slots - 1
     uint32_t plane_words;      // 2 * (N+2) * 16
     uint32_t off_groups;       // first word of plane 1 in the counter block
@@ -408,6 +408,39 @@ __device__ __forceinline__ uint32_t length_bin_plane(const PlaneParams &B, uint3
     uint32_t k = 1u;
     for (uint32_t i = 0; i < B.n_edges; i++) k += B.edges[i] <= L ? 1u : 0u;
     return k;
+}
+
+// ---- read-name replicates (-J): replicate j is plane 1 + j; plane 0 stays empty ---------------
+// Replicate of a record among K: a hash of its read name -- the n = l_read_name - 1 bytes at record offset 36, as stored
+// (an embedded NUL is a byte like any other; n = 0 when l_read_name <= 1) -- scaled to 0 .. K - 1 by its top bits.  The
+// hash is fnv1a_step over the name four bytes at a time (little endian, the last word zero-filled), then the length and
+// a finishing mix, because the top bits choose the replicate.  Mates share a name, so they share a replicate.
+// l_read_name is read from the record's word at offset 12 here: RecHdr, which every kernel carries, has no member for it.
+// A name starts at any byte alignment: the source's own unaligned u32 is used.  The last word's read runs up to three
+// bytes past the name, which a record that is ever asked about (a candidate: it has a CIGAR op there) holds, and so does
+// the staged prefix (it ends behind SEQ); a record too short for that hashes as the empty name.
+// One loop iteration per four name bytes.  The host's restatement is pss_read_name_replicate (host/replicates.c).
+__host__ __device__ __forceinline__ uint32_t read_name_finish(uint32_t h, uint32_t n) {
+    h ^= n;
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h;
+}
+template <class Src>
+__device__ __forceinline__ uint32_t read_name_replicate(const Src &src, uint32_t rec_len, uint32_t K) {
+    const uint32_t l_read_name = rec_len >= 36u ? src.u32(12) & 0xFFu : 0u;
+    const uint32_t n = (l_read_name > 1u && 36u + l_read_name + 3u <= rec_len) ? l_read_name - 1u : 0u;
+    uint32_t h = FNV1A_SEED;
+    for (uint32_t i = 0; i < n; i += 4u) {
+        uint32_t w = src.u32(36u + i);
+        const uint32_t rem = n - i;
+        if (rem < 4u) w &= (1u << (8u * rem)) - 1u;
+        h = fnv1a_step(h, w);
+    }
+    return (uint32_t)(((uint64_t)read_name_finish(h, n) * K) >> 32);
 }
 
 // ---- base codes ----------------------------------------------------------------------

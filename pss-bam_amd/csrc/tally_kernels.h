@@ -41,6 +41,7 @@
 //                 read_group_plane), per fragment-length bin (PLANES_LEN: by Plan::L,
 //                 length_bin_plane) or per contig set (PLANES_REF: by Plan::ref_plane, packed into
 //                 the ref_info entry plan_head loads anyway); -S and -C stage prefixes as without planes.
+//                 -J: per read-name replicate (PLANES_HASH: by read_name_replicate, a hash of the staged name); prefixes too.
 //  tally_tiled_planes / tally_simple_planes<PLANES_EACH> (-A): one plane per BAM reference, any number of them.  A workgroup
 //                 holds a few planes in LDS, owned by the refIDs its tiles meet (claimed in CODES-A, kept across tiles); a
 //                 read that finds every slot taken is tallied by one lane straight into its plane of the counter block, and
@@ -613,8 +614,9 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyP
 }
 
 // What picks a read's table plane in tally_tiled_body: nothing (one plane), its first RG:Z value
-// (-G), its length bin (-S), its contig's set (-C), or its refID itself (-A: a plane per BAM reference).
-enum PlaneSel { PLANES_NONE = 0, PLANES_RG, PLANES_LEN, PLANES_REF, PLANES_EACH };
+// (-G), its length bin (-S), its contig's set (-C), its refID itself (-A: a plane per BAM reference), or a hash of its
+// read name (-J: the jackknife replicates).
+enum PlaneSel { PLANES_NONE = 0, PLANES_RG, PLANES_LEN, PLANES_REF, PLANES_EACH, PLANES_HASH };
 
 // ---- -A: a plane per reference ---------------------------------------------------------------------------------
 // Plane k is refID k, plane n_ref (= n_groups - 1) the refID -1 records; only a record whose reference was found is ever
@@ -650,6 +652,7 @@ __device__ __forceinline__ uint32_t record_plane(const Src &src, const RecHdr &h
     if constexpr (PLANES == PLANES_RG) return read_group_plane(src, h, G);
     else if constexpr (PLANES == PLANES_EACH) return each_plane(h, G);
     else if constexpr (PLANES == PLANES_REF) return pl.ref_plane;   // from the ref_info entry plan_head loaded
+    else if constexpr (PLANES == PLANES_HASH) return 1u + read_name_replicate(src, h.rec_len, G.n_groups);   // K = n_groups
     else return length_bin_plane(G, KMER ? pl.Lk : pl.L);
 }
 
@@ -747,6 +750,11 @@ __device__ __forceinline__ uint32_t base_quality_mask(uint32_t x, uint32_t q4) {
 // planes of [(cell<<1)|table][row] plus one trash plane behind them; every read's plane slot is
 // resolved in CODES-A (record_plane: read_group_plane or length_bin_plane) and kept in grp_lds, and
 // COLUMNS adds the wave's scalar slot offset to each real code.
+//
+// PLANES_HASH (-J, tally_tiled_planes): the same path; the left-end lane of every candidate hashes the read name from the
+// staged bytes in CODES-A (read_name_replicate: the name lies in front of SEQ, so a staged prefix holds it), in front of
+// the barrier that releases `stage`, one loop iteration per four name bytes.  Prefixes are staged as without it, and
+// COLUMNS does not change.  A record that is not staged takes the one-lane path, which hashes from global memory.
 //
 // PLANES_EACH (-A, tally_tiled_planes): a plane per BAM reference, far more than LDS holds, of which one tile touches a
 // handful.  `table` holds gk->n_slots resident planes plus the trash plane, `each_lds` the refIDs that own them

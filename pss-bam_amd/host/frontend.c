@@ -37,6 +37,7 @@ int frontend_site_context = PSSBAM_SITE_NONE;
 int frontend_end_depth = 0, frontend_end_cell5 = 0, frontend_end_cell3 = 0;
 int frontend_gapped_reads = 0;
 int frontend_per_contig = 0;
+int frontend_replicates = 0;
 const pss_regions *frontend_regions = NULL;
 uint32_t frontend_length_edges[PSSBAM_MAX_LENGTH_BINS - 1];
 const frontend_contig_map *frontend_contig_sets = NULL;
@@ -80,6 +81,7 @@ static struct early_feed {
     int end_depth, end_cell5, end_cell3; /* -E: the end condition, set on every engine after create */
     int gapped;                     /* -I: anchored ends, set on every engine after create */
     int per_contig;                 /* -A: a pair of tables per reference, set on every engine after create (feed_open gave the count) */
+    int replicates;                 /* -J: the read-name replicates, set on every engine after create */
     const pss_regions *regions;     /* -T: the intervals, set on every engine after create */
     int n_edges;                    /* -S: the length bin edges, set on every engine after create */
     uint32_t edges[PSSBAM_MAX_LENGTH_BINS - 1];
@@ -166,7 +168,8 @@ static void *engine_make_main(void *arg)
         (EF.end_depth > 0 && pssbam_engine_set_end_condition(*j->out, EF.end_depth, EF.end_cell5, EF.end_cell3)) ||
         (EF.gapped && pssbam_engine_set_gapped_reads(*j->out, 1)) || send_regions(*j->out, EF.regions) ||
         (EF.n_rg > 0 && pssbam_engine_set_read_groups(*j->out, EF.n_rg, (const char *const *)EF.rg_ids)) ||
-        (EF.n_edges > 0 && pssbam_engine_set_length_bins(*j->out, EF.n_edges, EF.edges)) || send_contig_sets(*j->out, EF.sets)) {
+        (EF.n_edges > 0 && pssbam_engine_set_length_bins(*j->out, EF.n_edges, EF.edges)) || send_contig_sets(*j->out, EF.sets) ||
+        (EF.replicates > 0 && pssbam_engine_set_replicates(*j->out, EF.replicates))) {
         j->rc = 1;
         snprintf(j->err, sizeof j->err, "%s", pssbam_last_error());   /* (the message is this thread's) */
     }
@@ -302,6 +305,7 @@ void frontend_warmup_start(const pssbam_config *cfg, const char *aln_path, const
             EF.end_cell3 = frontend_end_cell3;
             EF.gapped = frontend_gapped_reads;
             EF.per_contig = frontend_per_contig;
+            EF.replicates = frontend_replicates;
             EF.regions = frontend_regions;
             memcpy(EF.edges, frontend_length_edges, sizeof EF.edges);
             EF.sets = frontend_contig_sets;
@@ -325,7 +329,7 @@ static int same_length_bins(void)
            EF.hist == frontend_length_hist && EF.site == frontend_site_context &&
            EF.mism_hist == frontend_mismatch_hist && EF.mism_max == frontend_max_mismatches && EF.mism_tv == frontend_mismatch_tv &&
            EF.end_depth == frontend_end_depth && EF.end_cell5 == frontend_end_cell5 && EF.end_cell3 == frontend_end_cell3 &&
-           EF.gapped == frontend_gapped_reads && EF.per_contig == frontend_per_contig && EF.regions == frontend_regions &&
+           EF.gapped == frontend_gapped_reads && EF.per_contig == frontend_per_contig && EF.replicates == frontend_replicates && EF.regions == frontend_regions &&
            memcmp(EF.edges, frontend_length_edges, (size_t)frontend_n_length_edges * sizeof *EF.edges) == 0;
 }
 
@@ -674,7 +678,8 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
                 (frontend_per_contig && pssbam_engine_set_per_contig(eng[g], 1)) ||
                 send_regions(eng[g], frontend_regions) ||
                 (frontend_n_length_edges > 0 && pssbam_engine_set_length_bins(eng[g], frontend_n_length_edges, frontend_length_edges)) ||
-                send_contig_sets(eng[g], frontend_contig_sets)) {
+                send_contig_sets(eng[g], frontend_contig_sets) ||
+                (frontend_replicates > 0 && pssbam_engine_set_replicates(eng[g], frontend_replicates))) {
                 fprintf(stderr, "Error: GPU engine %d: %s\n", g, pssbam_last_error());
                 goto done;
             }
@@ -924,6 +929,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
         free(touched);
     }
     if (frontend_n_length_edges > 0) res->n_planes = frontend_n_length_edges + 1; /* -G: set with the IDs */
+    if (frontend_replicates > 0) res->n_planes = frontend_replicates; /* -J */
     if (frontend_contig_sets) {
         res->n_planes = frontend_contig_sets->n_labels;
         warn_unreached_sets(frontend_contig_sets, genome, rd ? bam_reader_header(rd)->n_ref : sam_reader_n_ref(sd),

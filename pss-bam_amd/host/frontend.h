@@ -17,7 +17,8 @@ typedef struct run_result {
     int n_gpus;
     /* pss-bam -G / -S / -C: the tables of each plane of the engine, (region_len+2)*16 per plane; plane k is the
      * header's k-th @RG ID (frontend_group_by_rg, group_ids[k]), length bin k (frontend_length_edges, group_ids
-     * NULL) or the k-th label of frontend_contig_sets (group_ids NULL) */
+     * NULL) or the k-th label of frontend_contig_sets (group_ids NULL); pss-bam -J: replicate k (frontend_replicates,
+     * group_ids NULL) */
     int n_planes;
     char **group_ids;
     unsigned long *plane_fwd, *plane_rev;
@@ -76,6 +77,11 @@ extern int frontend_gapped_reads;
 /* pss-bam -A: non-zero = every engine keeps a pair of tables per reference (pssbam_engine_set_per_contig) and run_tally()
  * returns those that hold something.  Set before frontend_warmup_start(). */
 extern int frontend_per_contig;
+
+/* pss-bam -J: the number of read-name replicates (0: off); every engine gets it (pssbam_engine_set_replicates) and
+ * run_tally() returns one pair of tables per replicate in plane_fwd / plane_rev (n_planes = the count, group_ids NULL),
+ * summed over the GPUs with the rest of the counter block.  Set before frontend_warmup_start. */
+extern int frontend_replicates;
 
 /* -T: the intervals of the BED file (regions.h; NULL: none); every engine gets them (pssbam_engine_set_regions), on
  * every input path -- the filter lives in the engine.  Set before frontend_warmup_start. */

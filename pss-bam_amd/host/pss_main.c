@@ -50,6 +50,10 @@
  * mismatches, from the same pass; -V, with either, counts only transversions (deamination makes none).  A position counts
  * when read and reference base are both one of A C G T.  Needs -r <= 30.  Goes with -R, -Q and -T.  Not with -G, -S, -C, -H, -X,
  * -E, -I or -A.
+ * Added: -J <K> (2..64) also writes <prefix>.pss.rates.se.txt, the delete-one-group jackknife standard error of every number in the
+ * rates file, in its layout: the reads are split into K replicates by a hash of their names (mates stay together), every replicate's
+ * tables come from the same pass, and the rates of the input without replicate j, j = 0 .. K-1, give the error (replicates.h).  The
+ * other files stay as they are.  Goes with -R, -Q, -T, -m, -l, -L, -q, -U and -D.  Not with -G, -S, -C, -H, -X, -E, -I, -A, -n, -N or -V.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -69,6 +73,7 @@
 #include "mismatches.h"
 #include "read_groups.h"
 #include "regions.h"
+#include "replicates.h"
 #include "report.h"
 
 int main(int argc, char *argv[])
@@ -81,9 +86,9 @@ int main(int argc, char *argv[])
     const char *up_ctx = "ACGT", *down_ctx = "ACGT";
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL, *read_group = NULL;
     const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL, *bed_fn = NULL, *hist_arg = NULL, *site_arg = NULL, *end_arg = NULL;
-    const char *max_mm_arg = NULL, *mm_hist_arg = NULL;
+    const char *max_mm_arg = NULL, *mm_hist_arg = NULL, *rep_arg = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:V")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -108,6 +113,7 @@ int main(int argc, char *argv[])
         case 'n': max_mm_arg = optarg; break;
         case 'N': mm_hist_arg = optarg; break;
         case 'V': tv_only = 1; break;
+        case 'J': rep_arg = optarg; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -142,7 +148,8 @@ int main(int argc, char *argv[])
               "-A <also write the tables of every contig of the input, one pass for any number of contigs>\n"
               "-n <k> <only tally the reads with at most k mismatches against the reference (0..255)>\n"
               "-N <M> <also write how many tallied reads have 0, 1, ..., M and more than M mismatches (1..255)>\n"
-              "-V <with -n / -N: count only transversions>\n",
+              "-V <with -n / -N: count only transversions>\n"
+              "-J <K> <also write the jackknife standard errors of the rates, from K read-name replicates (2..64)>\n",
               stderr);
         exit(1);
     }
@@ -232,6 +239,23 @@ int main(int argc, char *argv[])
                 : end_arg ? "-E (tables conditional on the other end)" : "-I (clipped and gapped reads by their anchored ends)");
         exit(1);
     }
+    int replicates = 0;
+    if (rep_arg) {
+        if (by_group || len_edges || ctg_map || hist_arg || site_arg || end_arg || gapped || per_contig || max_mm_arg || mm_hist_arg || tv_only) {
+            fprintf(stderr, "-J (jackknife replicates) and %s exclude each other.\n",
+                    by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)" : ctg_map ? "-C (tables per contig set)"
+                    : hist_arg ? "-H (fragment-length histogram)" : site_arg ? "-X (tables per site context)"
+                    : end_arg ? "-E (tables conditional on the other end)" : gapped ? "-I (clipped and gapped reads by their anchored ends)"
+                    : per_contig ? "-A (tables per contig)" : max_mm_arg ? "-n (mismatch filter)" : mm_hist_arg ? "-N (mismatch histogram)"
+                    : "-V (count only transversions)");
+            exit(1);
+        }
+        char err[200];
+        if ((replicates = pss_parse_replicates(rep_arg, err, sizeof err)) < 0) {
+            fprintf(stderr, "%s\n", err);
+            exit(1);
+        }
+    }
     int max_mm = -1, mm_hist = 0;
     if (tv_only && !max_mm_arg && !mm_hist_arg) {
         fprintf(stderr, "-V (count only transversions) needs -n (mismatch filter) or -N (mismatch histogram).\n");
@@ -319,6 +343,7 @@ int main(int argc, char *argv[])
     if (max_mm_arg) fprintf(stderr, " -n %d", max_mm);
     if (mm_hist_arg) fprintf(stderr, " -N %d", mm_hist);
     if (tv_only) fprintf(stderr, " -V");
+    if (rep_arg) fprintf(stderr, " -J %d", replicates);
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -351,6 +376,7 @@ int main(int argc, char *argv[])
     frontend_mismatch_hist = mm_hist;
     frontend_max_mismatches = max_mm;
     frontend_mismatch_tv = tv_only;
+    frontend_replicates = replicates;
     if (bed_fn) frontend_regions = &bed;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
@@ -394,11 +420,23 @@ int main(int argc, char *argv[])
                         pss_write_end_reads(out_prefix, res.end_reads))) exit(1);   /* -E */
     if (per_contig && pss_write_contigs(fasta_fn, bam_fn, out_prefix, region_len, res.n_contigs, (const char *const *)res.contig_names,
                                         res.contig_fwd, res.contig_rev)) exit(1);   /* -A */
+    if (replicates) {   /* -J: the planes are the replicates' tables; no file per replicate */
+        const size_t n_rates = (size_t)(region_len ? region_len : 1) * 12;
+        double *fwd_se = (double *)calloc(n_rates, sizeof(double)), *rev_se = (double *)calloc(n_rates, sizeof(double));
+        if (!fwd_se || !rev_se || res.n_planes != replicates || pss_jackknife_se(region_len, replicates, res.fwd, res.plane_fwd, fwd_se) ||
+            pss_jackknife_se(region_len, replicates, res.rev, res.plane_rev, rev_se)) {
+            fprintf(stderr, "Error: out of memory\n");
+            exit(1);
+        }
+        if (pss_write_rates_se(fasta_fn, bam_fn, out_prefix, region_len, replicates, fwd_se, rev_se)) exit(1);
+        free(fwd_se);
+        free(rev_se);
+    }
     if (by_group && res.n_planes == 0)
         fprintf(stderr, "Warning: -G: the header of %s has no @RG line; only the tables of all reads were written.\n", bam_fn);
     /* <prefix>.<tag>: what `-R <ID> -o <prefix>.<ID>` (-G), `-l <lo> -L <hi> -o <prefix>.len<lo>-<hi>` (-S) or -F
      * reduced to the label's contigs with `-o <prefix>.<label>` (-C) writes */
-    for (int k = 0; k < res.n_planes; k++) {
+    for (int k = 0; k < res.n_planes && !replicates; k++) {
         const size_t cells = (size_t)(region_len + 2) * 16;
         unsigned long lo = 0, hi = 0;
         if (len_edges) pss_length_bin_bounds(edges, n_edges, k, min_read_len, max_read_len, &lo, &hi);

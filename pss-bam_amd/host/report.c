@@ -105,6 +105,31 @@ int pss_write_rates(const char *fasta_fn, const char *bam_fn, const char *out_pr
     return 0;
 }
 
+int pss_write_rates_se(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int region_len, int k,
+                       const double *fwd_se, const double *rev_se)
+{
+    char fn[FN_BUF + 1];
+    FILE *fp;
+    snprintf(fn, sizeof fn, "%s.pss.rates.se.txt", out_prefix);
+    fp = fopen(fn, "w");
+    if (!fp) {
+        fprintf(stderr, "ERROR: Cannot write to file %s\n.", fn);
+        return 1;
+    }
+    fprintf(fp, "### pss-bam.c v%s\n### FASTA: %s\n### BAM: %s\n### OUT: %s\n", PSS_VERSION, fasta_fn, bam_fn, fn);
+    fputs("### Format of table:\n", fp);
+    fputs("### Substitution rates for all possible nucleotide substitutions at\n", fp);
+    fputs("### each position in the aligned reads.\n", fp);
+    fputs("### First base is what was seen in the read.\n", fp);
+    fputs("### Second base is what was in the genome at that position.\n", fp);
+    fputs("### POS AC AG AT CA CG CT GA GC GT TA TC TG\n", fp);
+    fprintf(fp, "### jackknife standard errors of the forward read substitution rates, K = %d read-name replicates\n", k);
+    for (int pos = 0; pos < region_len; pos++) rate_row(fp, pos, fwd_se + (size_t)pos * 12);
+    fprintf(fp, "\n\n### jackknife standard errors of the reverse read substitution rates, K = %d read-name replicates\n", k);
+    for (int pos = region_len - 1; pos >= 0; pos--) rate_row(fp, pos, rev_se + (size_t)pos * 12);
+    return fclose(fp) ? 1 : 0;
+}
+
 int pss_write_labelled(const char *fasta_fn, const char *bam_fn, const char *out_prefix, const char *tag, int region_len,
                        const unsigned long *fwd, const unsigned long *rev)
 {

@@ -10,6 +10,12 @@ int pss_write_counts(const char *fasta_fn, const char *bam_fn, const char *out_p
                      const unsigned long *fwd, const unsigned long *rev);
 int pss_write_rates(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int region_len,
                     const double *fwd_rates, const double *rev_rates);
+/* pss-bam -J: <out_prefix>.pss.rates.se.txt in the layout of the rates file -- the same "###" lines (OUT: names this file; the
+ * two captions read "### jackknife standard errors of the forward / reverse read substitution rates, K = <k> read-name
+ * replicates"), the forward rows 0 .. N-1, two blank lines, the reverse rows N-1 .. 0, every value "%.5e".  fwd_se / rev_se
+ * hold region_len * 12 values in pss_sub_rates' order (replicates.h: pss_jackknife_se).  Returns 0, or 1 after a diagnostic. */
+int pss_write_rates_se(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int region_len, int k,
+                       const double *fwd_se, const double *rev_se);
 /* One labelled pair of files, <out_prefix>.<tag>.pss.counts.txt and .rates.txt, through the two writers above (what
  * -G / -S / -C write per plane and -X per context); `tag` is already file-name encoded.  Returns 0, or 1 after a
  * diagnostic. */
