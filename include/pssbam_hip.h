@@ -38,6 +38,7 @@ extern "C" {
 #define PSSBAM_MAX_CONTIG_SETS 4096  /* pssbam_engine_set_contig_sets */
 #define PSSBAM_MAX_REPLICATES 64     /* pssbam_engine_set_replicates */
 #define PSSBAM_MAX_MISMATCHES 255    /* pssbam_engine_set_mismatches: the largest histogram limit and the largest filter limit */
+#define PSSBAM_MAX_INTERIOR_MARGIN 65535 /* pssbam_engine_set_interior: the largest margin */
 #define PSSBAM_MAX_HIST_LENGTH 65535 /* pssbam_engine_set_length_histogram: the largest limit (lengths above it share one row) */
 #define PSSBAM_MAX_BASE_QUALITY 93   /* pssbam_engine_set_min_base_quality: the largest Phred value SAM text can print */
 #define PSSBAM_MAX_REGIONS (1 << 26) /* pssbam_engine_set_regions: intervals in one call */
@@ -515,6 +516,39 @@ int pssbam_engine_set_mismatches(pssbam_engine *e, int32_t hist_max /*0 = no his
  * be NULL.  PSSBAM_EINVAL without a histogram. */
 int pssbam_engine_finish_mismatches(pssbam_engine *e, uint64_t *fwd, uint64_t *rev);
 
+/* Interior table (pss-bam -W): the 4 x 4 substitution table of the read interior, every read position at least `margin` bases
+ * from both ends of its read, from the same pass -- the sequencing-error and polymorphism background that the end rows are
+ * read against.  Take a record that is added to the forward or to the reverse table after every record filter the run has
+ * (flags, mapping quality, lengths, merged_only, the read group, regions, the contig and edge checks, the mate rules, and
+ * up_ctx / down_ctx as they decide today).  With L the length that min_read_len / max_read_len compare, g the contig after the
+ * case folding, s = POS - 1, seq[i] the stored BAM nibble and d = margin, the record's interior is
+ *     I = { i : d <= i, i + d < L, i < l_seq }
+ * and position i of I counts when seq[i] and g[s+i] are both one of A C G T and, with a minimum base quality q, QUAL[i] >= q
+ * (absent qualities, 0xFF, mask nothing).  With rd / rf the codes A0 C1 G2 T3 of read and reference base it counts into
+ * table[4*rd + rf] for a forward-strand record and into table[15 - (4*rd + rf)] for a reverse-strand one (both bases
+ * complemented: the read's orientation, like the tables).  N, IUPAC codes and '=' in the read, any other reference letter
+ * and bases at or beyond l_seq never count.  reads = the number of such records whose I is not empty.  A record that goes
+ * into one table only (a read 1, a read 2) counts once, a
+ * record that enters neither does not count.  d is independent of region_len; d = 0 is the table of the whole read.  For
+ * unpaired <x>M records this is, per length x, the sum of rows d .. x-d-1 of the forward table of a run with
+ * min_read_len = max_read_len = x and region_len = x - d.
+ * margin = 0..PSSBAM_MAX_INTERIOR_MARGIN; -1 switches the setting off: the engine then launches exactly the kernels it
+ * launches without this call and n_u64 is unchanged.  Tables and status counters are bit-identical to the engine without
+ * the setting.
+ * Legal after create (or reset) and before the first tally launch; with pssbam_engine_feed_open that is any time before
+ * set_references.  Goes with cfg.read_group, a minimum base quality and regions.  PSSBAM_EINVAL for a margin out of range, on
+ * an engine whose mask is not PSSBAM_TALLY_PSS alone, for region_len > 30 (a read's fate is decided in the one pass that
+ * holds all rows, as for the mismatch count), and with read groups, length bins, contig sets, per-contig tables,
+ * replicates, a length histogram, site context, an end condition, gapped reads or the mismatch count set (each of those
+ * setters returns PSSBAM_EINVAL once this one is on); PSSBAM_ESTATE once records have been tallied, or once a bound counter
+ * block would have to grow (see pssbam_engine_counters_device).  The setting survives pssbam_engine_reset; engines whose
+ * blocks are summed must all have been given the same margin.  PSSBAM_KERNEL_AUTO never takes tally_compact with it on. */
+int pssbam_engine_set_interior(pssbam_engine *e, int32_t margin /*-1 = off*/);
+
+/* Drains the engine like pssbam_engine_finish and copies table[16] and reads; either pointer may be NULL.  PSSBAM_EINVAL
+ * when the setting is off. */
+int pssbam_engine_finish_interior(pssbam_engine *e, uint64_t table[16], uint64_t *reads);
+
 /* The device-resident counter block [fwd | rev | k5 | k3 | stats] as one array of
  * n_u64 64-bit words, for a caller-side RCCL reduce across GPUs (sum, uint64).  With read groups it is
  * [fwd | rev | stats | fwd_0 | rev_0 | ... | fwd_n-1 | rev_n-1]: the leading fwd | rev are the unassigned
@@ -541,7 +575,10 @@ int pssbam_engine_finish_mismatches(pssbam_engine *e, uint64_t *fwd, uint64_t *r
  * With a mismatch histogram of limit M (pssbam_engine_set_mismatches; a PSSBAM_TALLY_PSS engine without any of the above)
  * the two arrays are appended: [fwd | rev | stats | mf | mr], mf at 2*(region_len+2)*16 + PSSBAM_ST_N (the old n_u64), mr
  * M + 2 words behind it, n_u64 larger by 2*(M+2).  All words are plain counts: the block still sums as one u64 array.  The
- * filter alone adds no words. */
+ * filter alone adds no words.
+ * With the interior table (pssbam_engine_set_interior; a PSSBAM_TALLY_PSS engine without any of the above) its 17 words are
+ * appended in the same place: [fwd | rev | stats | table[16] | reads], table at 2*(region_len+2)*16 + PSSBAM_ST_N (the old
+ * n_u64), n_u64 larger by 17.  All words are plain counts: the block still sums as one u64 array. */
 int pssbam_engine_counters_device(pssbam_engine *e, void **d_counters, size_t *n_u64);
 
 /* Makes the engine accumulate into caller-owned device memory (n_u64 words, as reported

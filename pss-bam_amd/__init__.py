@@ -47,6 +47,7 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_end_condition", "pssbam_engine_finish_end_condition", "pssbam_engine_set_gapped_reads",
     "pssbam_engine_set_per_contig", "pssbam_engine_finish_contigs",
     "pssbam_engine_set_mismatches", "pssbam_engine_finish_mismatches", "pssbam_engine_set_replicates",
+    "pssbam_engine_set_interior", "pssbam_engine_finish_interior",
 ]
 MAX_READ_GROUPS = 4096
 MAX_LENGTH_BINS = 64
@@ -55,6 +56,7 @@ MAX_REPLICATES = 64
 MAX_BASE_QUALITY = 93
 MAX_HIST_LENGTH = 65535
 MAX_MISMATCHES = 255
+MAX_INTERIOR_MARGIN = 65535
 MAX_REGIONS = 1 << 26
 SITE_NONE, SITE_CPG = 0, 1
 SITE_MODES = {None: SITE_NONE, "none": SITE_NONE, "cpg": SITE_CPG}
@@ -137,6 +139,8 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_set_replicates.argtypes = [C.c_void_p, C.c_int32]
     L.pssbam_engine_set_mismatches.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     L.pssbam_engine_finish_mismatches.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pssbam_engine_set_interior.argtypes = [C.c_void_p, C.c_int32]
+    L.pssbam_engine_finish_interior.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_finish_contigs.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_regions.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_counters_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
@@ -223,6 +227,8 @@ class Engine:
     number of mismatches between the whole read and the reference, see set_mismatches; None = off.
     `replicates` = K (pss-bam -J): one set of substitution tables per read-name replicate, the planes of a delete-one-group
     jackknife, see set_replicates; 0 = off.
+    `interior` = d (pss-bam -W): the 4 x 4 substitution table of the read interior, the positions at least d bases from both
+    ends of every tallied read, see set_interior; None = off.
     With `kmer` alone (no `pss`) the three split the k-mer tables instead (fragkon -G / -S / -C): every plane is a
     k5 / k3 pair, and the length bins go by the SEQ length and kmer's min_read_len / max_read_len."""
 
@@ -231,7 +237,7 @@ class Engine:
                  length_bins: list[int] | None = None, contig_sets=None, min_base_qual: int = 0,
                  length_hist: int = 0, site_context: str | None = None, end_condition: tuple[int, int, int] | None = None,
                  gapped: bool = False, per_contig: bool = False, mismatches: tuple[int, int, int] | None = None,
-                 replicates: int = 0):
+                 replicates: int = 0, interior: int | None = None):
         L = hip_lib()
         cfg = _Config()
         cfg.abi_version = 1
@@ -296,6 +302,9 @@ class Engine:
         self._replicates = 0
         if replicates:
             self.set_replicates(replicates)
+        self._interior = -1
+        if interior is not None:
+            self.set_interior(interior)
 
     def set_min_base_quality(self, q: int):
         """pss-bam -Q: a read base whose Phred quality is below q (0..93, 0 = off) adds nothing to the substitution
@@ -503,6 +512,30 @@ class Engine:
         lo, hi = self._len_range
         starts, ends = [lo] + edges, [x - 1 for x in edges] + [hi]
         self.length_bins = list(zip(starts, ends))
+
+    def set_interior(self, margin: int = -1):
+        """pss-bam -W.  margin = d (0..65535, -1 = off): every record that is added to the forward or the reverse table also
+        counts its interior positions i (d <= i, i + d < L, i < l_seq) at which read and reference base are both A/C/G/T --
+        and, with min_base_qual, QUAL[i] is not below it -- into a 4 x 4 table, bin 4 * read + ref, a reverse-strand read into
+        15 - that; see finish_interior.  d = 0 is the whole read.  Needs region_len <= 30; goes with read_group, min_base_qual
+        and regions; not with kmer, read groups, length bins, contig sets, per-contig tables, replicates, the length
+        histogram, site context, the end condition, gapped reads or the mismatch count.  Before the first tally (after
+        feed_open: before set_references) and before bind_counters: the counter block grows by 17 words.  Survives reset."""
+        _chk(self._L.pssbam_engine_set_interior(self._h, int(margin)))
+        self._interior = int(margin)
+
+    @property
+    def interior(self) -> int | None:
+        """the interior margin in force, None = off"""
+        return self._interior if self._interior >= 0 else None
+
+    def finish_interior(self) -> tuple[np.ndarray, int]:
+        """(table, reads): table = u64[16], bin 4 * read + ref (A C G T) in the read's orientation; reads = the tallied
+        records whose interior is not empty (drains like finish)"""
+        table = np.zeros(16, dtype=np.uint64)
+        reads = np.zeros(1, dtype=np.uint64)
+        _chk(self._L.pssbam_engine_finish_interior(self._h, table.ctypes.data, reads.ctypes.data))
+        return table, int(reads[0])
 
     def set_replicates(self, k: int):
         """pss-bam -J: tallies every record into the tables of its replicate among k (2..MAX_REPLICATES; 0 switches it
@@ -779,6 +812,9 @@ class Engine:
         if self._mismatches[0]:   # the mismatch histogram (never together with any of the above): mf | mr behind the stats
             lay["mism_fwd"], lay["mism_rev"] = base, base + self._mismatches[0] + 2
             lay["n_u64"] = base + 2 * (self._mismatches[0] + 2)
+        if self._interior >= 0:   # the interior table (never together with any of the above): table[16] | reads behind the stats
+            lay["interior"], lay["interior_reads"] = base, base + 16
+            lay["n_u64"] = base + 17
         return lay
 
     def genome_kmer_count(self, klen: int) -> np.ndarray:

@@ -106,6 +106,10 @@ struct TallyParams {
     // the counter block at off_mism, bin min(m, M + 1) of the reads added to the forward / reverse table (0 = no histogram);
     // mism_tv: only transversions count.  Read by the MISM instantiations of tally_tiled and by tally_simple.
     uint32_t mism_limit, mism_hist, mism_tv, off_mism;
+    // -W: the read-interior substitution table (tally_kernels.h: count_interior).  interior = d + 1, d the margin that is left out
+    // at both ends of a read (0 = off); [table[16] | reads], 17 u64 counters in the counter block at off_interior.  Read by the
+    // INTERIOR instantiations of tally_tiled and by tally_simple.
+    uint32_t interior, off_interior;
 };
 
 // stats slots, must match include/pssbam_hip.h.  The kernels count EVENTS only: every launch

@@ -70,6 +70,13 @@
 //                 their halves; a read beyond the limit stops being a candidate, and the histogram of min(m, M + 1) lives in
 //                 LDS behind the staging buffer (mism_wave_add).  count_mismatches is the definition, one lane per read.
 //
+//  INTERIOR arm of tally_tiled (-W, pass 0 of a one-pass launch): the 4 x 4 substitution table of the read interior, every position
+//                 at least d bases from both ends of a read that is added to a table.  The MISM arm's walk with another
+//                 reduction (walk_read_staged is what the two share): each lane of a read's pair counts one half of the
+//                 interior into 16 bins (count_interior_staged), keeps them as 16-bit pairs across the barriers until -U/-D
+//                 have decided the read's fate, and the 17 words [table | reads] live in LDS behind the staging buffer
+//                 (interior_wave_add).  count_interior is the definition, one lane per read.
+//
 // Integer/byte work only: no MFMA anywhere (the bound is HBM bandwidth).
 #pragma once
 
@@ -400,18 +407,95 @@ __device__ __forceinline__ void mism_wave_add(const TallyParams &P, uint32_t *mi
 // same eight read bases in the same order.  Returns bit 4q set when position q counts.  The reference nibble becomes the BAM
 // one-hot code (1 2 4 8), so the XOR of the two is zero for a match, 5 (A/G) or 10 (C/T) for a transition; a read nibble is
 // a base when exactly one of its bits is set.
-__device__ __forceinline__ uint32_t mismatch_flags8(uint32_t g, uint32_t r, bool tv_only) {
+__device__ __forceinline__ uint32_t nonzero_nibbles8(uint32_t y) { return (y | (y >> 1) | (y >> 2) | (y >> 3)) & 0x11111111u; }   // bit 0 of every nibble that is not 0
+// bit 4q set when position q holds one of A C G T on both sides: a reference nibble below 4, a read nibble with exactly one bit
+__device__ __forceinline__ uint32_t acgt_pair_flags8(uint32_t g, uint32_t r) {
     const uint32_t K = 0x11111111u;
-    auto nonzero = [&](uint32_t y) { return (y | (y >> 1) | (y >> 2) | (y >> 3)) & K; };   // bit 0 of every nibble that is not 0
-    const uint32_t g0 = g & K, g1 = (g >> 1) & K;
-    const uint32_t onehot = (~g1 & ~g0 & K) | ((~g1 & g0) << 1) | ((g1 & ~g0) << 2) | ((g1 & g0) << 3);
     const uint32_t g_ok = ~(g >> 2) & ~(g >> 3) & K;
     const uint32_t bits = (r & K) + ((r >> 1) & K) + ((r >> 2) & K) + ((r >> 3) & K);   // 0..4 per nibble: no carry
-    const uint32_t r_ok = ~nonzero(bits ^ K) & K;
+    const uint32_t r_ok = ~nonzero_nibbles8(bits ^ K) & K;
+    return g_ok & r_ok;
+}
+__device__ __forceinline__ uint32_t mismatch_flags8(uint32_t g, uint32_t r, bool tv_only) {
+    const uint32_t K = 0x11111111u;
+    const uint32_t g0 = g & K, g1 = (g >> 1) & K;
+    const uint32_t onehot = (~g1 & ~g0 & K) | ((~g1 & g0) << 1) | ((g1 & ~g0) << 2) | ((g1 & g0) << 3);
+    const uint32_t ok = acgt_pair_flags8(g, r);
     const uint32_t x = r ^ onehot;
-    uint32_t f = g_ok & r_ok & nonzero(x);
-    if (tv_only) f &= nonzero(x ^ 0x55555555u) & nonzero(x ^ 0xAAAAAAAAu);
+    uint32_t f = ok & nonzero_nibbles8(x);
+    if (tv_only) f &= nonzero_nibbles8(x ^ 0x55555555u) & nonzero_nibbles8(x ^ 0xAAAAAAAAu);
     return f;
+}
+
+// ---------------------------------------------------------------------------------------
+// -W: the substitution table of the read interior
+// ---------------------------------------------------------------------------------------
+// The interior of a record that is added to the forward or the reverse table (include/pssbam_hip.h): the read positions i with
+// d <= i, i + d < L and i < l_seq, d = P.interior - 1.  A position counts when SEQ[i] and the reference base are both one of A C G T
+// and, under -Q, QUAL[i] is not below the minimum (absent qualities are 0xFF: never below); it counts into bin 4 * read + ref of
+// table[16], a reverse-strand record into 15 - that (both bases complemented), and a record whose interior is not empty
+// counts once in `reads` (word 16).  This is the definition in code: tally_simple and the one-lane path of tally_tiled use it
+// as it stands, and add straight into the counter block.
+template <class Src>
+__device__ void count_interior(const TallyParams &P, const Src &src, const RecHdr &h, const uint8_t *G, int64_t s, uint32_t L, bool rev) {
+    const uint32_t d = P.interior - 1u;
+    const uint32_t hi = L > d ? min(L - d, h.l_seq) : 0u;
+    if (hi <= d) return;
+    for (uint32_t i = d; i < hi; i++) {
+        const uint32_t rd = nib_code(read_nibble(src, h, i));
+        const uint32_t rf = ref_code(G[s + (int64_t)i]);
+        if (rd >= 4u || rf >= 4u) continue;
+        if (P.min_bq && src.u8(h.qual_off + i) < P.min_bq) continue;
+        const uint32_t bin = 4u * rd + rf;
+        atomicAdd(&P.counters[P.off_interior + (rev ? 15u - bin : bin)], 1ull);
+    }
+    atomicAdd(&P.counters[P.off_interior + 16u], 1ull);
+}
+constexpr uint32_t INTERIOR_WORDS = 17;   // table[16] | reads
+// Eight positions at once, g and r as for mismatch_flags8, keep = the nibbles (all four bits) of the positions that belong to
+// the lane's range and pass -Q.  Four read-letter planes against four reference-letter planes; a popcount of each AND is
+// the step's share of a bin (v_bcnt adds it to the running count in the same instruction).
+__device__ __forceinline__ void interior_step8(uint32_t g, uint32_t r, uint32_t keep, uint32_t (&cnt)[16]) {
+    const uint32_t K = 0x11111111u;
+    const uint32_t v = acgt_pair_flags8(g, r) & keep;
+    const uint32_t g0 = g & K, g1 = (g >> 1) & K;
+    const uint32_t rf[4] = {v & ~(g0 | g1), v & g0 & ~g1, v & g1 & ~g0, v & g0 & g1};
+    const uint32_t rd[4] = {r & K, (r >> 1) & K, (r >> 2) & K, (r >> 3) & K};   // (one bit per valid nibble: BAM A 1, C 2, G 4, T 8)
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+        for (int b = 0; b < 4; b++) cnt[4 * a + b] += (uint32_t)__popc(rd[a] & rf[b]);
+}
+// The lanes of one wave into the workgroup's 17 LDS words.  pk[k] holds this lane's counts of bins 2k (low half) and 2k + 1;
+// `on` = the lane's read was added to a table, `read` = it is the lane that counts the read itself.  A reverse-strand lane
+// turns its bins round (bin b -> 15 - b: the registers in reverse order, halves swapped), the lanes of every row of 16 are
+// summed with four DPP adds per register -- 16 lanes of at most 2048 bases each stay inside 16 bits -- and one lane per
+// row adds the non-zero bins: the four diagonal bins take nearly everything, so a wave sends a few dozen LDS atomics
+// instead of a few hundred.  Called from uniform control flow.
+__device__ __forceinline__ void interior_wave_add(uint32_t *lds, const uint32_t (&pk)[8], bool on, bool rev, bool read) {
+    if (!__any(on)) return;
+    uint32_t o[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const uint32_t m = pk[7 - k];
+        o[k] = !on ? 0u : rev ? (m >> 16) | (m << 16) : pk[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        o[k] += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)o[k], 0xB1, 0xF, 0xF, false);    // quad_perm [1,0,3,2]
+        o[k] += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)o[k], 0x4E, 0xF, 0xF, false);    // quad_perm [2,3,0,1]
+        o[k] += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)o[k], 0x141, 0xF, 0xF, false);   // row_half_mirror
+        o[k] += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)o[k], 0x140, 0xF, 0xF, false);   // row_mirror
+    }
+    if ((threadIdx.x & 15u) == 0u) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            if (o[k] & 0xFFFFu) atomicAdd(&lds[2 * k], o[k] & 0xFFFFu);
+            if (o[k] >> 16) atomicAdd(&lds[2 * k + 1], o[k] >> 16);
+        }
+    }
+    const unsigned long long n = __ballot(on && read);
+    if ((threadIdx.x & 63u) == 0u && n) atomicAdd(&lds[16], (uint32_t)__popcll(n));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -461,6 +545,8 @@ __global__ void __launch_bounds__(256) tally_simple(const TallyParams P) {
             if (P.hist_max) hist_add(P, nullptr, hist_bin(P, pl.L), pl.pss_fwd, pl.pss_rev, 1u);
             // -N: likewise
             if (P.mism_hist) mism_add(P, nullptr, mism_bin(P, mm), pl.pss_fwd, pl.pss_rev, 1u);
+            // -W: the read's interior, once, whichever table took the read
+            if (P.interior) count_interior(P, src, h, P.genome + pl.gbase, pl.s, pl.L, pl.rev);
         }
         bool kfail = false;
         if (pl.fk5 || pl.fk3) kfail = tally_kmer_record<false>(P, pl, nullptr);
@@ -500,14 +586,16 @@ __host__ __device__ inline uint32_t tiled_lds_bytes(uint32_t T, uint32_t pieces)
 struct __attribute__((packed, aligned(4))) Quad { uint32_t v[4]; };
 struct __attribute__((packed, aligned(4))) Tri { uint32_t v[3]; };
 
-// -n / -N, tiled form: the mismatches among read bases lo .. hi - 1 of a record whose SEQ starts at LDS byte seq_at of `stage`;
+// -n / -N and -W, tiled form: the walk over read bases lo .. hi - 1 of a record whose SEQ starts at LDS byte seq_at of `stage`;
 // g0 = the genome position of read base 0, lo a multiple of 8.  32 bases per round trip: five genome dwords gathered like an
 // end window (one dwordx4 + one dword, brought to the read's alignment with v_alignbit) against 16 SEQ bytes, whose nibbles
 // are swapped into the genome image's order (even position = low nibble).  The gather may run up to 39 positions past
 // hi and the SEQ reads 19 bytes: inside the padding between contigs (CONTIG_PAD) and inside STAGE_SLACK; what they bring is masked.
-__device__ __forceinline__ uint32_t count_mismatches_staged(const uint32_t *genome4, uint64_t g0, const uint8_t *stage, uint32_t seq_at,
-                                                            uint32_t lo, uint32_t hi, bool tv_only) {
-    uint32_t m = 0u;
+// step(W, R, keep, p): eight positions from p on -- nibble q of W / R = the reference / read nibble of position p + q, keep =
+// the nibbles of the positions below hi.
+template <class Step>
+__device__ __forceinline__ void walk_read_staged(const uint32_t *genome4, uint64_t g0, const uint8_t *stage, uint32_t seq_at,
+                                                 uint32_t lo, uint32_t hi, Step step) {
     for (uint32_t b = lo; b < hi; b += 32u) {
         const uint64_t ga = g0 + b;
         const uint32_t *pg = genome4 + (ga >> 3);
@@ -527,9 +615,16 @@ __device__ __forceinline__ uint32_t count_mismatches_staged(const uint32_t *geno
             const uint32_t S = __builtin_amdgcn_alignbyte(sr[t + 1], sr[t], sa & 3u);
             const uint32_t R = ((S >> 4) & 0x0F0F0F0Fu) | ((S & 0x0F0F0F0Fu) << 4);
             const uint32_t keep = have >= 8u ? 0xFFFFFFFFu : (1u << (4u * have)) - 1u;
-            m += (uint32_t)__popc(mismatch_flags8(W, R, tv_only) & keep);
+            step(W, R, keep, b + 8u * t);
         }
     }
+}
+// -n / -N: the mismatches among read bases lo .. hi - 1
+__device__ __forceinline__ uint32_t count_mismatches_staged(const uint32_t *genome4, uint64_t g0, const uint8_t *stage, uint32_t seq_at,
+                                                            uint32_t lo, uint32_t hi, bool tv_only) {
+    uint32_t m = 0u;
+    walk_read_staged(genome4, g0, stage, seq_at, lo, hi,
+                     [&](uint32_t W, uint32_t R, uint32_t keep, uint32_t) { m += (uint32_t)__popc(mismatch_flags8(W, R, tv_only) & keep); });
     return m;
 }
 
@@ -581,7 +676,7 @@ __device__ __forceinline__ void stage_tile_dma(const uint8_t *recs, uint64_t rec
 // the kernel): a reference to the kernel's by-value copy would force that whole struct into
 // scratch memory.
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool MASKQ = false, bool REGIONS = false, bool HIST = false, bool SITE = false,
-          bool END = false, bool GAPPED = false, bool MISM = false>
+          bool END = false, bool GAPPED = false, bool MISM = false, bool INTERIOR = false>
 __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyParams *kernarg, uint32_t o0,
                                                                     uint32_t o1, uint32_t *table, uint32_t *lds_kmer,
                                                                     uint32_t *hist_lds = nullptr, uint32_t *site_lds = nullptr,
@@ -608,6 +703,9 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyP
         if (gpl.pss_fwd || gpl.pss_rev) hist_add(P, hist_lds, hist_bin(P, gpl.L), gpl.pss_fwd, gpl.pss_rev, 1u);
     }
     if constexpr (END) tally_end_condition<MASKQ>(P, LdsEndTable{end_lds, (uint32_t)P.N + 2u}, gsrc, gh, gpl);   // (a pass-0 one as well)
+    if constexpr (INTERIOR) {   // (likewise; straight into the counter block)
+        if (gpl.pss_fwd || gpl.pss_rev) count_interior(P, gsrc, gh, P.genome + gpl.gbase, gpl.s, gpl.L, gpl.rev);
+    }
     bool kfail = false;
     if (DO_KMER && (gpl.fk5 || gpl.fk3)) kfail = tally_kmer_record<LDS_KMER>(P, gpl, lds_kmer);
     return record_events(DO_PSS, DO_KMER, gpl, kfail);
@@ -736,6 +834,38 @@ __device__ __forceinline__ uint32_t base_quality_mask(uint32_t x, uint32_t q4) {
     return (lt - (lt >> 7)) | lt;   // 0x80 -> 0xFF
 }
 
+// -W, tiled form: read bases lo .. hi - 1 of a staged record (walk_read_staged; lo a multiple of 8) into this lane's 16 bins,
+// of which only the positions from d on count -- the interior has a low edge as well as a high one.  MASKQ: the same eight
+// positions' QUAL bytes come out of `stage` too (a whole record is staged under -Q; three aligned dwords at qual_at + p, at most
+// 11 bytes past QUAL, inside the record's aux fields, the next record or STAGE_SLACK), base_quality_mask's 0xFF bytes become the
+// nibbles of `keep`.  The counts leave as 16-bit pairs, pk[k] = bins 2k | 2k + 1 << 16: a staged record is at most 64 pieces
+// of 16 bytes, fewer than 2048 bases.
+template <bool MASKQ>
+__device__ __forceinline__ void count_interior_staged(const uint32_t *genome4, uint64_t g0, const uint8_t *stage, uint32_t seq_at, uint32_t qual_at,
+                                                      uint32_t lo, uint32_t hi, uint32_t d, uint32_t min_bq, uint32_t (&pk)[8]) {
+    uint32_t cnt[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) cnt[k] = 0u;
+    walk_read_staged(genome4, g0, stage, seq_at, lo, hi, [&](uint32_t W, uint32_t R, uint32_t keep, uint32_t p) {
+        if (p < d) keep &= d - p >= 8u ? 0u : ~((1u << (4u * (d - p))) - 1u);
+        if constexpr (MASKQ) {
+            const uint32_t qa = qual_at + min(p, hi);   // (a step wholly past hi keeps nothing: it stays where the last one read)
+            const uint32_t *qp = (const uint32_t *)(stage + (qa & ~3u));
+            const uint32_t q4 = min_bq * 0x01010101u;
+            uint32_t low = 0u;
+#pragma unroll
+            for (int w = 0; w < 2; w++) {   // byte i of dword w = QUAL[p + 4w + i] -> nibble 4w + i
+                const uint32_t x = base_quality_mask(__builtin_amdgcn_alignbyte(qp[w + 1], qp[w], qa & 3u), q4);
+                low |= ((x & 0xFu) | ((x >> 4) & 0xF0u) | ((x >> 8) & 0xF00u) | ((x >> 12) & 0xF000u)) << (16 * w);
+            }
+            keep &= ~low;
+        }
+        interior_step8(W, R, keep, cnt);
+    });
+#pragma unroll
+    for (int k = 0; k < 8; k++) pk[k] = cnt[2 * k] | (cnt[2 * k + 1] << 16);
+}
+
 // Reference windows, one per alignment end, each with STATIC byte positions:
 //   left  end (e = 0): 32 bytes from s-2      byte w <-> row w          (0,1 context; 2+i = position i)
 //   right end (e = 1): 32 bytes up to s+L+1   byte w <-> row 31-w       (31 -> row 0, 30 -> row 1, 29-i -> 2+i)
@@ -821,8 +951,19 @@ __device__ __forceinline__ uint32_t base_quality_mask(uint32_t x, uint32_t q4) {
 // filtered.  Behind CODES-B the left-end lane of every read that is added to a table counts bin min(m, M + 1)
 // (mism_wave_add) into `hist_lds`, here the 2 * (M + 2) words [mf | mr] behind the staging buffer, which leave LDS once, at
 // kernel end, with one 64-bit atomic per non-zero bin.  The instantiations without MISM contain none of it.
+//
+// INTERIOR (-W, P.interior = d + 1 non-zero; pass 0 of a one-pass launch, one plane, substitution tables only, never with MISM): in
+// CODES-A, where MISM compares, every lane of a candidate's pair walks one half of the read's interior [d, min(L - d, l_seq)) --
+// the halves start at a multiple of 8 bases, d & ~7 and the cut, and the positions below d are masked -- and counts it into 16
+// bins (count_interior_staged; under MASKQ with the staged QUAL bytes of the same positions).  Whether the read is added to a
+// table is only known behind CODES-B (-U / -D need the window), so the counts cross the barrier as 16-bit pairs in eight
+// VGPRs; there the lanes of the reads that were added merge per wave and add into the 17 words [table | reads] in `hist_lds`
+// behind the staging buffer (interior_wave_add), the left-end lane counting the read.  The words leave LDS with one 64-bit
+// atomic per non-zero word at kernel end, and every 8192 tiles of a workgroup: a tile adds fewer than 128 * 2048 = 2^18 to a
+// word, so a u32 word cannot wrap.  The instantiations without INTERIOR contain none of it.
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS, PlaneSel PLANES = PLANES_NONE, bool MASKQ = false,
-          bool REGIONS = false, bool HIST = false, bool SITE = false, bool END = false, bool GAPPED = false, bool MISM = false>
+          bool REGIONS = false, bool HIST = false, bool SITE = false, bool END = false, bool GAPPED = false, bool MISM = false,
+          bool INTERIOR = false>
 __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const TallyParams *kernarg,
                                                  uint8_t *__restrict__ stage, uint8_t *__restrict__ sheet,
                                                  uint32_t *__restrict__ table,
@@ -843,6 +984,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
     static_assert(!MASKQ || DO_PSS, "base qualities mask the substitution tables only");
     static_assert(!GAPPED || (DO_PSS && !DO_KMER && PLANES == PLANES_NONE && !HIST && !SITE && !END), "anchored ends belong to the one-plane substitution tally without the length histogram, site context and the end condition");
     static_assert(!MISM || (DO_PSS && !DO_KMER && !LATER_PASS && PLANES == PLANES_NONE && !HIST && !SITE && !END && !GAPPED), "the mismatch count belongs to pass 0 of the one-plane substitution tally without the length histogram, site context, the end condition and anchored ends");
+    static_assert(!INTERIOR || (DO_PSS && !DO_KMER && !LATER_PASS && PLANES == PLANES_NONE && !HIST && !SITE && !END && !GAPPED && !MISM), "the interior table belongs to pass 0 of the one-plane substitution tally without the length histogram, site context, the end condition, anchored ends and the mismatch count");
     const uint32_t T = P.reads_per_tile;   // <= TILED_MAX_T
     const uint32_t n_recs = P.n_recs_dev ? *P.n_recs_dev : P.n_recs;   // device-indexed blocks: the count lives in device memory
     const uint32_t pieces = P.prefix_pieces;  // 16-byte pieces staged per record
@@ -872,6 +1014,17 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         for (uint32_t i = tid; i < 2u * P.hist_lds_bins; i += TILED_THREADS) hist_lds[i] = 0u;
     if constexpr (MISM)
         for (uint32_t i = tid; i < (P.mism_hist ? 2u * (P.mism_hist + 2u) : 0u); i += TILED_THREADS) hist_lds[i] = 0u;
+    if constexpr (INTERIOR)
+        if (tid < INTERIOR_WORDS) hist_lds[tid] = 0u;
+    // -W: the 17 LDS words into the counter block; an exchange, so that waves that are still adding lose nothing
+    auto flush_interior = [&]() {
+        if constexpr (INTERIOR) {
+            if (tid < INTERIOR_WORDS) {
+                const uint32_t v = atomicExch(&hist_lds[tid], 0u);
+                if (v) atomicAdd(&P.counters[P.off_interior + tid], (unsigned long long)v);
+            }
+        }
+    };
     if constexpr (SITE)
         for (uint32_t i = tid; i < SITE_WORDS; i += TILED_THREADS) site_lds[i] = 0u;
     if constexpr (END)
@@ -1012,6 +1165,24 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
             const uint64_t pc = pl.gbase + (uint64_t)pl.s + (e ? (uint64_t)pl.L : (uint64_t)-1ll);
             cx = (P.genome4[pc >> 3] >> (4u * (uint32_t)(pc & 7ull))) & 15u;
         }
+        // -W: this lane's half of the read's interior [d, n_hi) -- the left-end lane walks from d & ~7 (what lies below d is
+        // masked) to the cut, the right-end lane from the cut on; like MISM it reads all of SEQ, and under -Q all of QUAL, in `stage`.
+        // It stands in front of the loads of the end's own read and QUAL streams so that those registers are not live across the walk.
+        [[maybe_unused]] uint32_t ipk[INTERIOR ? 8 : 1];
+        [[maybe_unused]] bool i_some = false;   // the read's interior is not empty
+        if constexpr (INTERIOR) {
+#pragma unroll
+            for (int k = 0; k < 8; k++) ipk[k] = 0u;
+            const uint32_t d = P.interior - 1u;
+            const uint32_t n_hi = pl.L > d ? min(pl.L - d, h.l_seq) : 0u;
+            i_some = cand && n_hi > d;
+            if (i_some) {
+                const uint32_t lo8 = d & ~7u;
+                const uint32_t cut = min(n_hi, lo8 + ((((n_hi - lo8) >> 1) + 7u) & ~7u));
+                count_interior_staged<MASKQ>(P.genome4, pl.gbase + (uint64_t)pl.s, stage, src.off + h.seq_off, src.off + h.qual_off,
+                                             e ? cut : lo8, e ? n_hi : cut, d, P.min_bq, ipk);
+            }
+        }
         // read bases of this end as a nibble stream aligned with the window bytes: stream nibble
         // b <-> read base n0 + b, n0 = -2 (left: bytes 0,1 are context, their nibbles are never
         // used) or L-30 (right).  20 bytes from SEQ as six aligned dwords, one batch.
@@ -1117,7 +1288,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         if (in_tile && !in_stage && e == 0u) {
             if constexpr (KPLANES) ev_over = tally_overflow_record_kmer_planes<PLANES, LDS_KMER, REGIONS>(kernarg, gk, o0, o1, lds_kmer);
             else if constexpr (GROUPED) ev_over = tally_overflow_record_planes<PLANES, MASKQ, REGIONS>(kernarg, gk, o0, o1, table);
-            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS, HIST, SITE, END, GAPPED, MISM>(kernarg, o0, o1, table, lds_kmer, hist_lds, site_lds, end_lds);
+            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS, HIST, SITE, END, GAPPED, MISM, INTERIOR>(kernarg, o0, o1, table, lds_kmer, hist_lds, site_lds, end_lds);
             if (pass0) atomicAdd(&lds_delta[ST_SLOW_PATH], 1);
         }
         // First use of the gathered registers happens HERE, before the next tile's DMA is issued:
@@ -1153,6 +1324,10 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
             asm volatile("" : "+v"(mm));
             mm += (uint32_t)__shfl_xor((int)mm, 1);
             if (mism_beyond(P, mm)) pl.pss_cand = false;
+        }
+        if constexpr (INTERIOR) {   // the walk's genome dwords and staged bytes are used up here as well
+#pragma unroll
+            for (int k = 0; k < 8; k++) asm volatile("" : "+v"(ipk[k]));
         }
         if constexpr (REGIONS) {
             // -T, resolved here for the same reason: its interval loads must not wait behind the DMA.  A candidate that
@@ -1414,6 +1589,11 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
             if constexpr (MISM) {
                 if (P.mism_hist) mism_wave_add(P, hist_lds, e == 0u, mism_bin(P, mm), pl.pss_fwd, pl.pss_rev);
             }
+            // -W: both lanes of a read that was added to a table hand in their halves; the left-end lane counts the read
+            if constexpr (INTERIOR) {
+                interior_wave_add(hist_lds, ipk, pl.pss_fwd || pl.pss_rev, pl.rev, e == 0u && i_some);
+                if ((it & 8191u) == 8191u) flush_interior();
+            }
         }
         // (no barrier: wave w wrote the sheet rows of reads 32w .. 32w+31 -- j = tid >> 1 -- and its
         //  COLUMNS pass below reads exactly those rows)
@@ -1556,6 +1736,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
             if (v) atomicAdd(&P.counters[P.off_mism + i], (unsigned long long)v);
         }
     }
+    flush_interior();
 }
 
 
@@ -2085,8 +2266,9 @@ __global__ void __launch_bounds__(256) reduce_partials(const TallyParams P, uint
 // END: behind the staging buffer the conditional tables and reads[4], end_lds_bytes(N + 2) (never together with HIST)
 // GAPPED: nothing more in LDS (the CIGAR walk reads the staged prefix)
 // MISM: behind the staging buffer the 2 * (P.mism_hist + 2) words of the mismatch histogram, where HIST has its bins (never together)
+// INTERIOR: in the same place the 17 words [table | reads] of the interior table (never together with either)
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS = false, bool MASKQ = false, bool REGIONS = false, bool HIST = false,
-          bool SITE = false, bool END = false, bool GAPPED = false, bool MISM = false>
+          bool SITE = false, bool END = false, bool GAPPED = false, bool MISM = false, bool INTERIOR = false>
 __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
@@ -2097,7 +2279,7 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P
     __shared__ uint4 refs_lds[REF_LDS_ENTRIES + 1];
     // the kernel's single argument, as it lies in the kernarg segment (for the out-of-line path)
     const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
-    uint32_t *hist_lds = (HIST || MISM) ? (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces)) : nullptr;
+    uint32_t *hist_lds = (HIST || MISM || INTERIOR) ? (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces)) : nullptr;
     if constexpr (SITE) {
         __shared__ uint32_t site_lds[SITE_WORDS];
         tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, true>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
@@ -2107,7 +2289,7 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P
         tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, false, true>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
                                                                                                              lds_delta, refs_lds, nullptr, nullptr, hist_lds, nullptr, end_lds);
     } else
-    tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, false, false, GAPPED, MISM>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
+    tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, false, false, GAPPED, MISM, INTERIOR>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
                                                                                                                   lds_delta, refs_lds, nullptr, nullptr, hist_lds);
 }
 

@@ -33,6 +33,7 @@ int frontend_n_length_edges = 0;
 int frontend_min_base_quality = 0;
 int frontend_length_hist = 0;
 int frontend_mismatch_hist = 0, frontend_max_mismatches = -1, frontend_mismatch_tv = 0;
+int frontend_interior = -1;
 int frontend_site_context = PSSBAM_SITE_NONE;
 int frontend_end_depth = 0, frontend_end_cell5 = 0, frontend_end_cell3 = 0;
 int frontend_gapped_reads = 0;
@@ -77,6 +78,7 @@ static struct early_feed {
     int min_bq;                     /* -Q: the minimum base quality, set on every engine after create */
     int hist;                       /* -H: the limit of the length histogram, set on every engine after create */
     int mism_hist, mism_max, mism_tv; /* -N / -n / -V: the mismatch count, set on every engine after create */
+    int interior;                   /* -W: the interior margin, set on every engine after create */
     int site;                       /* -X: the site context, set on every engine after create */
     int end_depth, end_cell5, end_cell3; /* -E: the end condition, set on every engine after create */
     int gapped;                     /* -I: anchored ends, set on every engine after create */
@@ -164,6 +166,7 @@ static void *engine_make_main(void *arg)
         (EF.min_bq > 0 && pssbam_engine_set_min_base_quality(*j->out, EF.min_bq)) ||
         (EF.hist > 0 && pssbam_engine_set_length_histogram(*j->out, EF.hist)) ||
         ((EF.mism_hist > 0 || EF.mism_max >= 0) && pssbam_engine_set_mismatches(*j->out, EF.mism_hist, EF.mism_max, EF.mism_tv)) ||
+        (EF.interior >= 0 && pssbam_engine_set_interior(*j->out, EF.interior)) ||
         (EF.site != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(*j->out, EF.site)) ||
         (EF.end_depth > 0 && pssbam_engine_set_end_condition(*j->out, EF.end_depth, EF.end_cell5, EF.end_cell3)) ||
         (EF.gapped && pssbam_engine_set_gapped_reads(*j->out, 1)) || send_regions(*j->out, EF.regions) ||
@@ -299,6 +302,7 @@ void frontend_warmup_start(const pssbam_config *cfg, const char *aln_path, const
             EF.mism_hist = frontend_mismatch_hist;
             EF.mism_max = frontend_max_mismatches;
             EF.mism_tv = frontend_mismatch_tv;
+            EF.interior = frontend_interior;
             EF.site = frontend_site_context;
             EF.end_depth = frontend_end_depth;
             EF.end_cell5 = frontend_end_cell5;
@@ -326,7 +330,7 @@ static int same_str(const char *a, const char *b) { return (!a && !b) || (a && b
 static int same_length_bins(void)
 {
     return EF.n_edges == frontend_n_length_edges && EF.sets == frontend_contig_sets && EF.min_bq == frontend_min_base_quality &&
-           EF.hist == frontend_length_hist && EF.site == frontend_site_context &&
+           EF.hist == frontend_length_hist && EF.site == frontend_site_context && EF.interior == frontend_interior &&
            EF.mism_hist == frontend_mismatch_hist && EF.mism_max == frontend_max_mismatches && EF.mism_tv == frontend_mismatch_tv &&
            EF.end_depth == frontend_end_depth && EF.end_cell5 == frontend_end_cell5 && EF.end_cell3 == frontend_end_cell3 &&
            EF.gapped == frontend_gapped_reads && EF.per_contig == frontend_per_contig && EF.replicates == frontend_replicates && EF.regions == frontend_regions &&
@@ -672,6 +676,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
                 (frontend_length_hist > 0 && pssbam_engine_set_length_histogram(eng[g], frontend_length_hist)) ||
                 ((frontend_mismatch_hist > 0 || frontend_max_mismatches >= 0) &&
                  pssbam_engine_set_mismatches(eng[g], frontend_mismatch_hist, frontend_max_mismatches, frontend_mismatch_tv)) ||
+                (frontend_interior >= 0 && pssbam_engine_set_interior(eng[g], frontend_interior)) ||
                 (frontend_site_context != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(eng[g], frontend_site_context)) ||
                 (frontend_end_depth > 0 && pssbam_engine_set_end_condition(eng[g], frontend_end_depth, frontend_end_cell5, frontend_end_cell3)) ||
                 (frontend_gapped_reads && pssbam_engine_set_gapped_reads(eng[g], 1)) ||
@@ -875,6 +880,13 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
             goto done;
         }
+    }
+    if (frontend_interior >= 0 && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -W: summed with the rest of the block */
+        if (pssbam_engine_finish_interior(eng[0], res->interior, &res->interior_reads)) {
+            fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+            goto done;
+        }
+        res->has_interior = 1;
     }
     if (frontend_site_context != PSSBAM_SITE_NONE && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -X: summed with the rest of the block */
         const size_t cells = (size_t)(cfg->pss.region_len + 2) * 16;

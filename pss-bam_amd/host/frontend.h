@@ -32,6 +32,9 @@ typedef struct run_result {
      * mism_max + 2 rows each (row mism_max + 1: every larger count), or NULL */
     int mism_max;
     uint64_t *mism_fwd, *mism_rev;
+    /* pss-bam -W (frontend_interior): the interior table and the number of reads that have an interior (has_interior: filled) */
+    int has_interior;
+    uint64_t interior[16], interior_reads;
     /* pss-bam -X (frontend_site_context): the in-context tables IN, (region_len+2)*16 each with rows 0/1 as fwd / rev,
      * or NULL */
     unsigned long *site_fwd, *site_rev;
@@ -61,6 +64,10 @@ extern int frontend_length_hist;
  * filter) and whether only transversions count; every engine gets them (pssbam_engine_set_mismatches) and run_tally()
  * returns the two arrays of the histogram.  Set before frontend_warmup_start. */
 extern int frontend_mismatch_hist, frontend_max_mismatches, frontend_mismatch_tv;
+
+/* pss-bam -W: the interior margin (-1: off); every engine gets it (pssbam_engine_set_interior) and run_tally() returns the
+ * table and its read count.  Set before frontend_warmup_start. */
+extern int frontend_interior;
 
 /* pss-bam -X: the site context (PSSBAM_SITE_*; PSSBAM_SITE_NONE: off); every engine gets it
  * (pssbam_engine_set_site_context) and run_tally() returns the in-context pair.  Set before frontend_warmup_start. */

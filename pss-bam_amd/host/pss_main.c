@@ -54,6 +54,11 @@
  * rates file, in its layout: the reads are split into K replicates by a hash of their names (mates stay together), every replicate's
  * tables come from the same pass, and the rates of the input without replicate j, j = 0 .. K-1, give the error (replicates.h).  The
  * other files stay as they are.  Goes with -R, -Q, -T, -m, -l, -L, -q, -U and -D.  Not with -G, -S, -C, -H, -X, -E, -I, -A, -n, -N or -V.
+ * Added: -W <d> (0..65535) also writes <prefix>.pss.interior.txt, the 4 x 4 substitution counts and the twelve rates of the read
+ * interior -- every position at least d bases from both ends of a read that is added to a table, in the read's orientation, under
+ * -Q only the bases that pass it -- with the number of such reads and bases, from the same pass: the background the end rows are read
+ * against.  d = 0 is the whole read.  The other files stay as they are.  Needs -r <= 30.  Goes with -R, -Q, -T, -m, -l, -L, -q, -U and
+ * -D.  Not with -G, -S, -C, -H, -X, -E, -I, -A, -n, -N, -V or -J.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -68,6 +73,7 @@
 #include "contig_sets.h"
 #include "fasta-genome-io.h"
 #include "frontend.h"
+#include "interior.h"
 #include "length_bins.h"
 #include "length_hist.h"
 #include "mismatches.h"
@@ -86,9 +92,9 @@ int main(int argc, char *argv[])
     const char *up_ctx = "ACGT", *down_ctx = "ACGT";
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL, *read_group = NULL;
     const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL, *bed_fn = NULL, *hist_arg = NULL, *site_arg = NULL, *end_arg = NULL;
-    const char *max_mm_arg = NULL, *mm_hist_arg = NULL, *rep_arg = NULL;
+    const char *max_mm_arg = NULL, *mm_hist_arg = NULL, *rep_arg = NULL, *interior_arg = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -114,6 +120,7 @@ int main(int argc, char *argv[])
         case 'N': mm_hist_arg = optarg; break;
         case 'V': tv_only = 1; break;
         case 'J': rep_arg = optarg; break;
+        case 'W': interior_arg = optarg; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -149,7 +156,8 @@ int main(int argc, char *argv[])
               "-n <k> <only tally the reads with at most k mismatches against the reference (0..255)>\n"
               "-N <M> <also write how many tallied reads have 0, 1, ..., M and more than M mismatches (1..255)>\n"
               "-V <with -n / -N: count only transversions>\n"
-              "-J <K> <also write the jackknife standard errors of the rates, from K read-name replicates (2..64)>\n",
+              "-J <K> <also write the jackknife standard errors of the rates, from K read-name replicates (2..64)>\n"
+              "-W <d> <also write the substitution counts and rates of the read interior, d bases and more from both ends (0..65535)>\n",
               stderr);
         exit(1);
     }
@@ -282,6 +290,27 @@ int main(int argc, char *argv[])
             exit(1);
         }
     }
+    int interior = -1;
+    if (interior_arg) {
+        if (by_group || len_edges || ctg_map || hist_arg || site_arg || end_arg || gapped || per_contig || max_mm_arg || mm_hist_arg || tv_only || rep_arg) {
+            fprintf(stderr, "-W (read-interior table) and %s exclude each other.\n",
+                    by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)" : ctg_map ? "-C (tables per contig set)"
+                    : hist_arg ? "-H (fragment-length histogram)" : site_arg ? "-X (tables per site context)"
+                    : end_arg ? "-E (tables conditional on the other end)" : gapped ? "-I (clipped and gapped reads by their anchored ends)"
+                    : per_contig ? "-A (tables per contig)" : max_mm_arg ? "-n (mismatch filter)" : mm_hist_arg ? "-N (mismatch histogram)"
+                    : tv_only ? "-V (count only transversions)" : "-J (jackknife replicates)");
+            exit(1);
+        }
+        char err[200];
+        if ((interior = pss_parse_interior_margin(interior_arg, err, sizeof err)) < 0) {
+            fprintf(stderr, "%s\n", err);
+            exit(1);
+        }
+        if (region_len > 30) {
+            fprintf(stderr, "-W (read-interior table) needs -r <= 30 (a read's fate is decided in the one pass over 32 table rows), not -r %d.\n", region_len);
+            exit(1);
+        }
+    }
     pss_regions bed;
     memset(&bed, 0, sizeof bed);
     if (bed_fn) {
@@ -344,6 +373,7 @@ int main(int argc, char *argv[])
     if (mm_hist_arg) fprintf(stderr, " -N %d", mm_hist);
     if (tv_only) fprintf(stderr, " -V");
     if (rep_arg) fprintf(stderr, " -J %d", replicates);
+    if (interior_arg) fprintf(stderr, " -W %d", interior);
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -377,6 +407,7 @@ int main(int argc, char *argv[])
     frontend_max_mismatches = max_mm;
     frontend_mismatch_tv = tv_only;
     frontend_replicates = replicates;
+    frontend_interior = interior;
     if (bed_fn) frontend_regions = &bed;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
@@ -403,6 +434,7 @@ int main(int argc, char *argv[])
     pss_write_rates(fasta_fn, bam_fn, out_prefix, region_len, fwd_rates, rev_rates);
     if (res.hist_fwd && pss_write_lengths(fasta_fn, bam_fn, out_prefix, res.hist_max, res.hist_fwd, res.hist_rev)) exit(1);
     if (res.mism_fwd && pss_write_mismatches(fasta_fn, bam_fn, out_prefix, res.mism_max, tv_only, res.mism_fwd, res.mism_rev)) exit(1);   /* -N */
+    if (res.has_interior && pss_write_interior(fasta_fn, bam_fn, out_prefix, interior, min_bq, res.interior, res.interior_reads)) exit(1);   /* -W */
     if (res.site_fwd) {   /* -X: IN as the engine returns it; OUT = T - IN on the position rows, the context rows as T */
         const size_t cells = (size_t)(region_len + 2) * 16;
         unsigned long *out_fwd = (unsigned long *)malloc(cells * sizeof *out_fwd), *out_rev = (unsigned long *)malloc(cells * sizeof *out_rev);

@@ -4,6 +4,7 @@
  * /root/reference/pss-bam.c:504-633 and fragkon.c:231-249,:367-368.
  */
 #include "report.h"
+#include "interior.h"
 #include "pssbam_hip.h"
 
 #include <limits.h>
@@ -256,6 +257,36 @@ int pss_write_mismatches(const char *fasta_fn, const char *bam_fn, const char *o
     for (int m = 0; m <= max_mm; m++)
         fprintf(fp, "%d\t%llu\t%llu\n", m, (unsigned long long)fwd[m], (unsigned long long)rev[m]);
     fprintf(fp, ">%d\t%llu\t%llu\n", max_mm, (unsigned long long)fwd[max_mm + 1], (unsigned long long)rev[max_mm + 1]);
+    return fclose(fp) ? 1 : 0;
+}
+
+int pss_write_interior(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int margin, int min_bq, const uint64_t table[16],
+                       uint64_t reads)
+{
+    char fn[FN_BUF + 1];
+    FILE *fp;
+    snprintf(fn, sizeof fn, "%s.pss.interior.txt", out_prefix);
+    fp = fopen(fn, "w");
+    if (!fp) {
+        fprintf(stderr, "ERROR: Cannot write to file %s\n.", fn);
+        return 1;
+    }
+    fprintf(fp, "# substitution counts and rates of the read interior: the positions at least %d bases from both ends of the tallied reads", margin);
+    if (min_bq > 0) fprintf(fp, ", base quality at least %d (-Q %d)", min_bq, min_bq);
+    fprintf(fp, "\n# FASTA: %s\n# BAM: %s\n", fasta_fn, bam_fn);
+    unsigned long row[16];
+    double rates[12];
+    uint64_t bases = 0;
+    for (int j = 0; j < 16; j++) {
+        row[j] = (unsigned long)table[j];
+        bases += table[j];
+    }
+    pss_interior_rates(table, rates);
+    fputs("### POS AA AC AG AT CA CC CG CT GA GC GG GT TA TC TG TT\n", fp);
+    count_row(fp, margin, row);
+    fputs("### POS AC AG AT CA CG CT GA GC GT TA TC TG\n", fp);
+    rate_row(fp, margin, rates);
+    fprintf(fp, "reads\t%llu\nbases\t%llu\n", (unsigned long long)reads, (unsigned long long)bases);
     return fclose(fp) ? 1 : 0;
 }
 

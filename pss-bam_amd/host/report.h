@@ -45,6 +45,12 @@ int pss_write_lengths(const char *fasta_fn, const char *bam_fn, const char *out_
  * max_mm + 2 counts.  Returns 0, or 1 after a diagnostic. */
 int pss_write_mismatches(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int max_mm, int transversions_only,
                          const uint64_t *fwd, const uint64_t *rev);
+/* pss-bam -W: <out_prefix>.pss.interior.txt -- a '#' line that states the margin (and the minimum base quality when min_bq > 0) and
+ * two with the input names, the column names of the counts file and one row of the 16 counts labelled with the margin, printed as
+ * a row of the counts file; the column names of the rates file and one row of the 12 rates (pss_interior_rates), printed as a row
+ * of the rates file; then "reads\t<reads>" and "bases\t<sum of the 16 counts>".  Returns 0, or 1 after a diagnostic. */
+int pss_write_interior(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int margin, int min_bq, const uint64_t table[16],
+                       uint64_t reads);
 /* k5 / k3: 4^klen 64-bit bins (clamped to UINT_MAX on output) */
 int fragkon_write_table(FILE *out, const char *fasta_fn, const char *bam_fn, int klen, const uint64_t *k5,
                         const uint64_t *k3);
