@@ -39,6 +39,7 @@ extern "C" {
 #define PSSBAM_MAX_REPLICATES 64     /* pssbam_engine_set_replicates */
 #define PSSBAM_MAX_MISMATCHES 255    /* pssbam_engine_set_mismatches: the largest histogram limit and the largest filter limit */
 #define PSSBAM_MAX_INTERIOR_MARGIN 65535 /* pssbam_engine_set_interior: the largest margin */
+#define PSSBAM_MAX_COMPOSITION 30    /* pssbam_engine_set_composition: the largest width */
 #define PSSBAM_MAX_HIST_LENGTH 65535 /* pssbam_engine_set_length_histogram: the largest limit (lengths above it share one row) */
 #define PSSBAM_MAX_BASE_QUALITY 93   /* pssbam_engine_set_min_base_quality: the largest Phred value SAM text can print */
 #define PSSBAM_MAX_REGIONS (1 << 26) /* pssbam_engine_set_regions: intervals in one call */
@@ -549,6 +550,44 @@ int pssbam_engine_set_interior(pssbam_engine *e, int32_t margin /*-1 = off*/);
  * when the setting is off. */
 int pssbam_engine_finish_interior(pssbam_engine *e, uint64_t table[16], uint64_t *reads);
 
+/* Composition table (pss-bam -P): the reference base composition in a window of `width` = w bases on either side of the two
+ * fragmentation points, outside and inside the read, in the read's orientation, from the same pass -- the depurination
+ * signal (purine excess at -1, C depletion at +1) against its own baseline further out.  Take a record that is added to the
+ * forward table, to the reverse table, or to both, after every record filter the run has (flags, the <L>M CIGAR, mapping
+ * quality, lengths, merged_only, the read group, regions, the contig and edge checks, the mate rules, and up_ctx / down_ctx
+ * as they decide today).  With L the length that min_read_len / max_read_len compare, s = POS - 1, len the contig's length,
+ * g the contig after the case folding, cls(x) = 0 1 2 3 for A C G T and 4 for anything else, and comp(c) = 3 - c for
+ * c < 4, comp(4) = 4: for every offset j in -w .. w-1 (negative: outside the read, -1 adjacent to it; 0 ..: inside, counted
+ * from that end)
+ *   5' block, for a record added to the forward table: p = s + j on a forward-strand record, p = s + L-1 - j on a FLAG 0x10
+ *             record; adds 1 to c5[j + w][c];
+ *   3' block, for a record added to the reverse table: p = s + L-1 - j on a forward-strand record, p = s + j on a FLAG 0x10
+ *             record; adds 1 to c3[j + w][c];
+ *   c = cls(g[p]), on a FLAG 0x10 record comp(cls(g[p])).
+ * A position counts only when 0 <= p < len, and for j >= 0 only when j < L (L >= region_len is all that is guaranteed, and
+ * w is independent of region_len).  Positions are masked by their coordinate, not by their letter: nothing of the
+ * padding between contigs or of a neighbouring contig is ever counted.  SEQ and QUAL play no part, so a minimum base quality
+ * changes nothing; an unpaired read counts in both blocks, a read 1 in the 5' block only, a read 2 in the 3' block only.
+ * c5[w-1] and c5[w-2] are the diagonal cells of the forward table's context rows -1 and -2, c3[w-1] and c3[w-2] those of
+ * the reverse table's.
+ * width = 1..PSSBAM_MAX_COMPOSITION; 0 switches the setting off: the engine then launches exactly the kernels it launches
+ * without this call and n_u64 is unchanged.  Tables and status counters are bit-identical to the engine without the
+ * setting.
+ * Legal after create (or reset) and before the first tally launch; with pssbam_engine_feed_open that is any time before
+ * set_references.  Goes with cfg.read_group, regions and a minimum base quality (which has no effect).  PSSBAM_EINVAL for a
+ * width out of range, on an engine whose mask is not PSSBAM_TALLY_PSS alone, for region_len > 30 (a read's fate and its end
+ * windows are those of the one pass that holds all rows, as for the interior table), and with read groups, length bins,
+ * contig sets, per-contig tables, replicates, a length histogram, site context, an end condition, gapped reads, the
+ * mismatch count or the interior table set (each of those setters returns PSSBAM_EINVAL once this one is on);
+ * PSSBAM_ESTATE once records have been tallied, or once a bound counter block would have to grow (see
+ * pssbam_engine_counters_device).  The setting survives pssbam_engine_reset; engines whose blocks are summed must all have
+ * been given the same width.  PSSBAM_KERNEL_AUTO never takes tally_compact with it on. */
+int pssbam_engine_set_composition(pssbam_engine *e, int32_t width /*0 = off*/);
+
+/* Drains the engine like pssbam_engine_finish and copies c5 and c3, 2 * width * 5 words each, row-major [j + width][class];
+ * either pointer may be NULL.  PSSBAM_EINVAL when the setting is off. */
+int pssbam_engine_finish_composition(pssbam_engine *e, uint64_t *c5, uint64_t *c3);
+
 /* The device-resident counter block [fwd | rev | k5 | k3 | stats] as one array of
  * n_u64 64-bit words, for a caller-side RCCL reduce across GPUs (sum, uint64).  With read groups it is
  * [fwd | rev | stats | fwd_0 | rev_0 | ... | fwd_n-1 | rev_n-1]: the leading fwd | rev are the unassigned
@@ -578,7 +617,11 @@ int pssbam_engine_finish_interior(pssbam_engine *e, uint64_t table[16], uint64_t
  * filter alone adds no words.
  * With the interior table (pssbam_engine_set_interior; a PSSBAM_TALLY_PSS engine without any of the above) its 17 words are
  * appended in the same place: [fwd | rev | stats | table[16] | reads], table at 2*(region_len+2)*16 + PSSBAM_ST_N (the old
- * n_u64), n_u64 larger by 17.  All words are plain counts: the block still sums as one u64 array. */
+ * n_u64), n_u64 larger by 17.  All words are plain counts: the block still sums as one u64 array.
+ * With the composition table of width w (pssbam_engine_set_composition; a PSSBAM_TALLY_PSS engine without any of the above)
+ * its two blocks are appended in the same place: [fwd | rev | stats | c5 | c3], c5 at 2*(region_len+2)*16 + PSSBAM_ST_N (the
+ * old n_u64), c3 10*w words behind it, each row-major [j + w][class], n_u64 larger by 20*w.  All words are plain counts: the
+ * block still sums as one u64 array. */
 int pssbam_engine_counters_device(pssbam_engine *e, void **d_counters, size_t *n_u64);
 
 /* Makes the engine accumulate into caller-owned device memory (n_u64 words, as reported

@@ -48,6 +48,7 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_per_contig", "pssbam_engine_finish_contigs",
     "pssbam_engine_set_mismatches", "pssbam_engine_finish_mismatches", "pssbam_engine_set_replicates",
     "pssbam_engine_set_interior", "pssbam_engine_finish_interior",
+    "pssbam_engine_set_composition", "pssbam_engine_finish_composition",
 ]
 MAX_READ_GROUPS = 4096
 MAX_LENGTH_BINS = 64
@@ -57,6 +58,7 @@ MAX_BASE_QUALITY = 93
 MAX_HIST_LENGTH = 65535
 MAX_MISMATCHES = 255
 MAX_INTERIOR_MARGIN = 65535
+MAX_COMPOSITION = 30
 MAX_REGIONS = 1 << 26
 SITE_NONE, SITE_CPG = 0, 1
 SITE_MODES = {None: SITE_NONE, "none": SITE_NONE, "cpg": SITE_CPG}
@@ -141,6 +143,8 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_finish_mismatches.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_interior.argtypes = [C.c_void_p, C.c_int32]
     L.pssbam_engine_finish_interior.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pssbam_engine_set_composition.argtypes = [C.c_void_p, C.c_int32]
+    L.pssbam_engine_finish_composition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_finish_contigs.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_regions.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_counters_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
@@ -229,6 +233,8 @@ class Engine:
     jackknife, see set_replicates; 0 = off.
     `interior` = d (pss-bam -W): the 4 x 4 substitution table of the read interior, the positions at least d bases from both
     ends of every tallied read, see set_interior; None = off.
+    `composition` = w (pss-bam -P): the reference base composition w bases on either side of the 5' end of the reads in the
+    forward table and of the 3' end of those in the reverse table, see set_composition; None = off.
     With `kmer` alone (no `pss`) the three split the k-mer tables instead (fragkon -G / -S / -C): every plane is a
     k5 / k3 pair, and the length bins go by the SEQ length and kmer's min_read_len / max_read_len."""
 
@@ -237,7 +243,7 @@ class Engine:
                  length_bins: list[int] | None = None, contig_sets=None, min_base_qual: int = 0,
                  length_hist: int = 0, site_context: str | None = None, end_condition: tuple[int, int, int] | None = None,
                  gapped: bool = False, per_contig: bool = False, mismatches: tuple[int, int, int] | None = None,
-                 replicates: int = 0, interior: int | None = None):
+                 replicates: int = 0, interior: int | None = None, composition: int | None = None):
         L = hip_lib()
         cfg = _Config()
         cfg.abi_version = 1
@@ -305,6 +311,9 @@ class Engine:
         self._interior = -1
         if interior is not None:
             self.set_interior(interior)
+        self._composition = 0
+        if composition is not None:
+            self.set_composition(composition)
 
     def set_min_base_quality(self, q: int):
         """pss-bam -Q: a read base whose Phred quality is below q (0..93, 0 = off) adds nothing to the substitution
@@ -536,6 +545,33 @@ class Engine:
         reads = np.zeros(1, dtype=np.uint64)
         _chk(self._L.pssbam_engine_finish_interior(self._h, table.ctypes.data, reads.ctypes.data))
         return table, int(reads[0])
+
+    def set_composition(self, width: int = 0):
+        """pss-bam -P.  width = w (1..MAX_COMPOSITION, 0 = off): every record that is added to the forward table counts the
+        reference bases at the offsets -w .. w-1 from its 5' end (negative: outside the read), every record that is added to
+        the reverse table those around its 3' end, in the read's orientation, as A C G T or other; see finish_composition.
+        Positions outside the contig, and inside offsets at or beyond the read's length, count nothing.  Needs
+        region_len <= 30; goes with read_group, min_base_qual (no effect) and regions; not with kmer, read groups, length
+        bins, contig sets, per-contig tables, replicates, the length histogram, site context, the end condition, gapped
+        reads, the mismatch count or the interior table.  Before the first tally (after feed_open: before set_references)
+        and before bind_counters: the counter block grows by 20 * w words.  Survives reset."""
+        _chk(self._L.pssbam_engine_set_composition(self._h, int(width)))
+        self._composition = int(width)
+
+    @property
+    def composition(self) -> int | None:
+        """the composition width in force, None = off"""
+        return self._composition if self._composition > 0 else None
+
+    def finish_composition(self) -> tuple[np.ndarray, np.ndarray]:
+        """(c5, c3): u64 arrays of shape (2w, 5), row j + w = offset j from the 5' / 3' end, columns A C G T other
+        (drains like finish)"""
+        if not self._composition:
+            raise PssbamError("set_composition has not been called with a width")
+        c5 = np.zeros((2 * self._composition, 5), dtype=np.uint64)
+        c3 = np.zeros((2 * self._composition, 5), dtype=np.uint64)
+        _chk(self._L.pssbam_engine_finish_composition(self._h, c5.ctypes.data, c3.ctypes.data))
+        return c5, c3
 
     def set_replicates(self, k: int):
         """pss-bam -J: tallies every record into the tables of its replicate among k (2..MAX_REPLICATES; 0 switches it
@@ -815,6 +851,9 @@ class Engine:
         if self._interior >= 0:   # the interior table (never together with any of the above): table[16] | reads behind the stats
             lay["interior"], lay["interior_reads"] = base, base + 16
             lay["n_u64"] = base + 17
+        if self._composition:   # the composition table (never together with any of the above): c5 | c3 behind the stats
+            lay["comp5"], lay["comp3"] = base, base + 10 * self._composition
+            lay["n_u64"] = base + 20 * self._composition
         return lay
 
     def genome_kmer_count(self, klen: int) -> np.ndarray:

@@ -235,6 +235,9 @@ struct pssbam_engine {
     // interior_margin = -1: off, no words
     int32_t interior_margin = -1;
     uint32_t off_interior = 0;
+    // -P (pssbam_engine_set_composition): c5 | c3, 2 * width * 5 words each at off_composition = the end of the block as it is
+    // without them; composition = 0: off, no words
+    uint32_t composition = 0, off_composition = 0;
     bool gapped = false;   // -I (pssbam_engine_set_gapped_reads): clipped and gapped reads are tallied by their anchored ends; no counter words
     int env_hist_lds_bins = -1;   // PSSBAM_HIST_LDS_BINS: at most this many bins of each array in LDS (tests: the global-atomic path with short reads)
     // -T (pssbam_engine_set_regions): contig name -> its merged intervals, kept on the host; the per-refID device table is
@@ -940,26 +943,27 @@ static int no_kernel() { return fail(PSSBAM_EINVAL, "no tally kernel is built fo
 // beside the substitution tables) and -H belong to pass 0, -Q -H -X to the substitution tables, -X excludes the other two;
 // -E is the substitution tally of pass 0 alone, with or without -Q and -T; -I is the substitution tally alone in every pass, with or
 // without -Q and -T (eight instantiations); -n / -N is the substitution tally of pass 0 alone, with or without -Q and -T (four), and
-// so is -W (four more; never together with -n / -N).
+// so is -W (four more; never together with -n / -N), and so is -P (four more; never together with either).
 // (SITE, END: the larger scratch slot of the -X / -E instantiations and the reduce that walks it)
 static int launch_tiled(pssbam_engine *e, TallyParams &P, bool do_pss, bool do_kmer, bool kmer_lds, bool later, bool maskq, bool regions,
-                        bool hist, bool site, bool endc, bool gapped, bool mism, bool interior, uint32_t lds, uint32_t n_tiles) {
+                        bool hist, bool site, bool endc, bool gapped, bool mism, bool interior, bool comp, uint32_t lds, uint32_t n_tiles) {
     return with_flags([&](auto DO_PSS, auto DO_KMER, auto LDS_KMER, auto LATER, auto MASKQ, auto REGIONS, auto HIST, auto SITE, auto END, auto GAPPED, auto MISM,
-                          auto INTERIOR) -> int {
+                          auto INTERIOR, auto COMP) -> int {
         constexpr bool exists = (DO_KMER() || !LDS_KMER()) &&
                                 (LATER() ? DO_PSS() && !DO_KMER() && !HIST()
                                          : (DO_PSS() || DO_KMER()) && (DO_PSS() || !(MASKQ() || HIST() || SITE())) && !(SITE() && (DO_KMER() || HIST()))) &&
                                 (!END() || (DO_PSS() && !DO_KMER() && !LATER() && !HIST() && !SITE())) &&
                                 (!GAPPED() || (DO_PSS() && !DO_KMER() && !LDS_KMER() && !HIST() && !SITE() && !END())) &&
                                 (!MISM() || (DO_PSS() && !DO_KMER() && !LDS_KMER() && !LATER() && !HIST() && !SITE() && !END() && !GAPPED())) &&
-                                (!INTERIOR() || (DO_PSS() && !DO_KMER() && !LDS_KMER() && !LATER() && !HIST() && !SITE() && !END() && !GAPPED() && !MISM()));
+                                (!INTERIOR() || (DO_PSS() && !DO_KMER() && !LDS_KMER() && !LATER() && !HIST() && !SITE() && !END() && !GAPPED() && !MISM())) &&
+                                (!COMP() || (DO_PSS() && !DO_KMER() && !LDS_KMER() && !LATER() && !HIST() && !SITE() && !END() && !GAPPED() && !MISM() && !INTERIOR()));
         if constexpr (exists)
-            return launch_with_reduce(e, tally_tiled<DO_PSS(), DO_KMER(), LDS_KMER(), LATER(), MASKQ(), REGIONS(), HIST(), SITE(), END(), GAPPED(), MISM(), INTERIOR()>,
+            return launch_with_reduce(e, tally_tiled<DO_PSS(), DO_KMER(), LDS_KMER(), LATER(), MASKQ(), REGIONS(), HIST(), SITE(), END(), GAPPED(), MISM(), INTERIOR(), COMP()>,
                                       reduce_partials<SITE(), END()>, SITE() ? SITE_SCRATCH_WORDS : END() ? END_SCRATCH_WORDS : SCRATCH_WORDS, lds, n_tiles, P,
                                       std::tuple<>(), (uint32_t)LDS_KMER());
         else
             return no_kernel();
-    }, do_pss, do_kmer, kmer_lds, later, maskq, regions, hist, site, endc, gapped, mism, interior);
+    }, do_pss, do_kmer, kmer_lds, later, maskq, regions, hist, site, endc, gapped, mism, interior, comp);
 }
 
 // How many 16-byte pieces of a record the tiled kernel must stage so that everything the path
@@ -1090,6 +1094,11 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
     if (interior) {
         P.interior = (uint32_t)e->interior_margin + 1u;
         P.off_interior = e->off_interior;
+    }
+    const bool comp = do_pss && e->composition > 0;   // -P: the COMP instantiations; without it the engine launches what it always did
+    if (comp) {
+        P.composition = e->composition;
+        P.off_composition = e->off_composition;
     }
     const bool gapped = do_pss && e->gapped;   // -I: the GAPPED instantiations; without it the engine launches what it always did
     P.gapped = gapped ? 1u : 0u;
@@ -1247,9 +1256,9 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                     });
                 }
             }
-        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions && !hist && !site && !endc && !gapped && !mism && !interior) {
+        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions && !hist && !site && !endc && !gapped && !mism && !interior && !comp) {
             // -r N <= 16 (2 context rows + 16 positions): the short-window variant, one pass (it stages prefixes only
-            // and has no QUAL path: -R and -Q go to tally_tiled; so do -T, -H, -X, -E, -I, -n / -N and -W, whose arms only tally_tiled carries)
+            // and has no QUAL path: -R and -Q go to tally_tiled; so do -T, -H, -X, -E, -I, -n / -N, -W and -P, whose arms only tally_tiled carries)
             if (!do_kmer && getenv("PSSBAM_COMPACT_DECODE_TWICE"))   // diagnostics: what the shared header decode costs
                 rc = launch_with_reduce(e, tally_compact_decode_twice, reduce_partials<false>, SCRATCH_WORDS, lds, n_tiles, P, std::tuple<>(), 0u);
             else
@@ -1272,11 +1281,12 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
             }
             if (mism && e->mism_hist) lds0 += 2u * (e->mism_hist + 2u) * 4u;   // -N (one pass: -r <= 30): [mf | mr] behind the staging buffer, at most 2 KiB
             if (interior) lds0 += INTERIOR_WORDS * 4u;   // -W (one pass: -r <= 30): [table | reads] behind the staging buffer
+            if (comp) lds0 += 20u * e->composition * 4u;   // -P (one pass: -r <= 30): [c5 | c3] behind the staging buffer, at most 2400 bytes
             if (endc) lds0 += end_lds_bytes(e->rows);   // -E (one pass: -r <= 30): the conditional tables and reads[4] behind the staging buffer
             for (uint32_t pass = 0; pass < n_passes && rc == PSSBAM_OK; pass++) {
                 P.row_base = pass * TILED_ROWS;
-                rc = pass == 0 ? launch_tiled(e, P, do_pss, do_kmer, kmer_lds, false, maskq, regions, hist, site, endc, gapped, mism, interior, lds0, n_tiles)
-                               : launch_tiled(e, P, true, false, false, true, maskq, regions, false, site, false, gapped, false, false, lds, n_tiles);
+                rc = pass == 0 ? launch_tiled(e, P, do_pss, do_kmer, kmer_lds, false, maskq, regions, hist, site, endc, gapped, mism, interior, comp, lds0, n_tiles)
+                               : launch_tiled(e, P, true, false, false, true, maskq, regions, false, site, false, gapped, false, false, false, lds, n_tiles);
             }
         }
         if (rc != PSSBAM_OK) return rc;
@@ -1547,6 +1557,7 @@ extern "C" int pssbam_engine_finish_kmer_groups(pssbam_engine *e, int32_t group,
 // names what is being set in the messages.
 static bool mismatches_on(const pssbam_engine *e) { return e->mism_hist > 0 || e->mism_max >= 0; }   // -n / -N
 static bool interior_on(const pssbam_engine *e) { return e->interior_margin >= 0; }   // -W
+static bool composition_on(const pssbam_engine *e) { return e->composition > 0; }   // -P
 
 static int check_may_resize(const pssbam_engine *e, const char *what) {
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set %s after create or reset, before the first tally", what);
@@ -1576,6 +1587,7 @@ static int set_planes(pssbam_engine *e, PlaneSel sel, uint32_t n_planes, const c
     if (e->gapped) return fail(PSSBAM_EINVAL, "%s and gapped reads exclude each other", what);
     if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "%s and the mismatch count exclude each other", what);
     if (interior_on(e)) return fail(PSSBAM_EINVAL, "%s and the interior table exclude each other", what);
+    if (composition_on(e)) return fail(PSSBAM_EINVAL, "%s and the composition table exclude each other", what);
     const bool kmer = e->cfg.tally_mask == PSSBAM_TALLY_KMER;
     if (e->cfg.tally_mask != PSSBAM_TALLY_PSS && !kmer)
         return fail(PSSBAM_EINVAL, "%s split the substitution tables or the k-mer tables, not both (PSSBAM_TALLY_PSS | PSSBAM_TALLY_KMER)", what);
@@ -1673,6 +1685,7 @@ extern "C" int pssbam_engine_set_gapped_reads(pssbam_engine *e, int32_t on) {
         if (e->end_depth) return fail(PSSBAM_EINVAL, "gapped reads and the end condition exclude each other");
         if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "gapped reads and the mismatch count exclude each other");
         if (interior_on(e)) return fail(PSSBAM_EINVAL, "gapped reads and the interior table exclude each other");
+        if (composition_on(e)) return fail(PSSBAM_EINVAL, "gapped reads and the composition table exclude each other");
     }
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set gapped reads after create or reset, before the first tally");
     e->gapped = on != 0;   // (the counter block keeps its size: a caller-bound block stays bound)
@@ -1691,6 +1704,7 @@ extern "C" int pssbam_engine_set_length_histogram(pssbam_engine *e, int32_t max_
     if (e->gapped && max_len) return fail(PSSBAM_EINVAL, "the length histogram and gapped reads exclude each other");
     if (mismatches_on(e) && max_len) return fail(PSSBAM_EINVAL, "the length histogram and the mismatch count exclude each other");
     if (interior_on(e) && max_len) return fail(PSSBAM_EINVAL, "the length histogram and the interior table exclude each other");
+    if (composition_on(e) && max_len) return fail(PSSBAM_EINVAL, "the length histogram and the composition table exclude each other");
     if (const int rc = check_may_resize(e, "the length histogram")) return rc;
     if ((uint32_t)max_len == e->hist_max) return PSSBAM_OK;
     HIP_TRY(hipSetDevice(e->device));
@@ -1732,6 +1746,7 @@ extern "C" int pssbam_engine_set_mismatches(pssbam_engine *e, int32_t hist_max, 
         if (e->end_depth) return fail(PSSBAM_EINVAL, "the mismatch count and the end condition exclude each other");
         if (e->gapped) return fail(PSSBAM_EINVAL, "the mismatch count and gapped reads exclude each other");
         if (interior_on(e)) return fail(PSSBAM_EINVAL, "the mismatch count and the interior table exclude each other");
+        if (composition_on(e)) return fail(PSSBAM_EINVAL, "the mismatch count and the composition table exclude each other");
     }
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the mismatch count after create or reset, before the first tally");
     if ((uint32_t)hist_max != e->mism_hist) {
@@ -1773,6 +1788,7 @@ extern "C" int pssbam_engine_set_interior(pssbam_engine *e, int32_t margin) {
         if (e->end_depth) return fail(PSSBAM_EINVAL, "the interior table and the end condition exclude each other");
         if (e->gapped) return fail(PSSBAM_EINVAL, "the interior table and gapped reads exclude each other");
         if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "the interior table and the mismatch count exclude each other");
+        if (composition_on(e)) return fail(PSSBAM_EINVAL, "the interior table and the composition table exclude each other");
     }
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the interior table after create or reset, before the first tally");
     if ((margin >= 0) != interior_on(e)) {
@@ -1796,6 +1812,46 @@ extern "C" int pssbam_engine_finish_interior(pssbam_engine *e, uint64_t table[16
     return PSSBAM_OK;
 }
 
+extern "C" int pssbam_engine_set_composition(pssbam_engine *e, int32_t width) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (width < 0 || width > PSSBAM_MAX_COMPOSITION) return fail(PSSBAM_EINVAL, "composition width %d outside 0..%d", width, PSSBAM_MAX_COMPOSITION);
+    if (width > 0) {
+        if (e->cfg.tally_mask != PSSBAM_TALLY_PSS)
+            return fail(PSSBAM_EINVAL, "the composition table counts the reads of the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
+        if (e->cfg.pss.region_len > 30)
+            return fail(PSSBAM_EINVAL, "the composition table needs a region length of at most 30 (a read's fate and its end windows are those of the one pass that holds all rows), not %d", e->cfg.pss.region_len);
+        if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "the composition table and replicates exclude each other");
+        if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the composition table and read groups / length bins / contig sets / per-contig tables exclude each other");
+        if (e->hist_max) return fail(PSSBAM_EINVAL, "the composition table and the length histogram exclude each other");
+        if (e->site_mode) return fail(PSSBAM_EINVAL, "the composition table and site context exclude each other");
+        if (e->end_depth) return fail(PSSBAM_EINVAL, "the composition table and the end condition exclude each other");
+        if (e->gapped) return fail(PSSBAM_EINVAL, "the composition table and gapped reads exclude each other");
+        if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "the composition table and the mismatch count exclude each other");
+        if (interior_on(e)) return fail(PSSBAM_EINVAL, "the composition table and the interior table exclude each other");
+    }
+    if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the composition table after create or reset, before the first tally");
+    if ((uint32_t)width != e->composition) {
+        if (const int rc = check_may_resize(e, "the composition table")) return rc;
+        HIP_TRY(hipSetDevice(e->device));
+        // the block grows (or shrinks back) behind everything it holds without the table
+        if (const int rc = grow_counters(e, (uint64_t)e->off_groups + 20ull * (uint64_t)width)) return rc;
+    }
+    e->composition = (uint32_t)width;
+    e->off_composition = width > 0 ? e->off_groups : 0u;
+    return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_finish_composition(pssbam_engine *e, uint64_t *c5, uint64_t *c3) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (!composition_on(e)) return fail(PSSBAM_EINVAL, "pssbam_engine_set_composition has not been called with a width");
+    const int rc = pssbam_engine_sync(e);
+    if (rc) return rc;
+    const size_t words = 10u * (size_t)e->composition;
+    if (c5) HIP_TRY(hipMemcpy(c5, e->d_counters + e->off_composition, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (c3) HIP_TRY(hipMemcpy(c3, e->d_counters + e->off_composition + words, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return PSSBAM_OK;
+}
+
 extern "C" int pssbam_engine_set_site_context(pssbam_engine *e, int32_t mode) {
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
     if (mode != PSSBAM_SITE_NONE && mode != PSSBAM_SITE_CPG) return fail(PSSBAM_EINVAL, "unknown site context %d", mode);
@@ -1808,6 +1864,7 @@ extern "C" int pssbam_engine_set_site_context(pssbam_engine *e, int32_t mode) {
     if (e->gapped && mode != PSSBAM_SITE_NONE) return fail(PSSBAM_EINVAL, "site context and gapped reads exclude each other");
     if (mismatches_on(e) && mode != PSSBAM_SITE_NONE) return fail(PSSBAM_EINVAL, "site context and the mismatch count exclude each other");
     if (interior_on(e) && mode != PSSBAM_SITE_NONE) return fail(PSSBAM_EINVAL, "site context and the interior table exclude each other");
+    if (composition_on(e) && mode != PSSBAM_SITE_NONE) return fail(PSSBAM_EINVAL, "site context and the composition table exclude each other");
     if (const int rc = check_may_resize(e, "the site context")) return rc;
     if ((uint32_t)mode == e->site_mode) return PSSBAM_OK;
     HIP_TRY(hipSetDevice(e->device));
@@ -1852,6 +1909,7 @@ extern "C" int pssbam_engine_set_end_condition(pssbam_engine *e, int32_t depth, 
     if (e->gapped && depth) return fail(PSSBAM_EINVAL, "the end condition and gapped reads exclude each other");
     if (mismatches_on(e) && depth) return fail(PSSBAM_EINVAL, "the end condition and the mismatch count exclude each other");
     if (interior_on(e) && depth) return fail(PSSBAM_EINVAL, "the end condition and the interior table exclude each other");
+    if (composition_on(e) && depth) return fail(PSSBAM_EINVAL, "the end condition and the composition table exclude each other");
     if (const int rc = check_may_resize(e, "the end condition")) return rc;
     if ((uint32_t)depth != e->end_depth) {
         HIP_TRY(hipSetDevice(e->device));
@@ -2020,6 +2078,7 @@ extern "C" int pssbam_engine_set_per_contig(pssbam_engine *e, int32_t on) {
         if (e->gapped) return fail(PSSBAM_EINVAL, "per-contig tables and gapped reads exclude each other");
         if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "per-contig tables and the mismatch count exclude each other");
         if (interior_on(e)) return fail(PSSBAM_EINVAL, "per-contig tables and the interior table exclude each other");
+        if (composition_on(e)) return fail(PSSBAM_EINVAL, "per-contig tables and the composition table exclude each other");
     }
     if (const int rc = check_may_resize(e, "per-contig tables")) return rc;
     if ((on != 0) == e->per_contig) return PSSBAM_OK;

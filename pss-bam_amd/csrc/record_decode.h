@@ -110,6 +110,10 @@ struct TallyParams {
     // at both ends of a read (0 = off); [table[16] | reads], 17 u64 counters in the counter block at off_interior.  Read by the
     // INTERIOR instantiations of tally_tiled and by tally_simple.
     uint32_t interior, off_interior;
+    // -P: the reference base composition around the read ends (tally_kernels.h: count_composition).  composition = w, the number of
+    // offsets on either side of an end (0 = off); [c5 | c3], 2 * w * 5 u64 counters each, row-major [j + w][class], in the counter
+    // block at off_composition.  Read by the COMP instantiations of tally_tiled and by tally_simple.
+    uint32_t composition, off_composition;
 };
 
 // stats slots, must match include/pssbam_hip.h.  The kernels count EVENTS only: every launch

@@ -77,6 +77,13 @@
 //                 have decided the read's fate, and the 17 words [table | reads] live in LDS behind the staging buffer
 //                 (interior_wave_add).  count_interior is the definition, one lane per read.
 //
+//  COMP arm of tally_tiled (-P, pass 0 of a one-pass launch): the reference base composition w bases on either side of the 5' end of
+//                 the reads in the forward table and of the 3' end of those in the reverse table.  The end's own window holds the
+//                 inside half; the outside half is one more five-dword gather per candidate end, issued with the window's.  In
+//                 CODES-B every lane turns the 64 nibbles around its end into classes in offset order, and the wave merges them
+//                 per offset with five ballots into ten scalar counts that ten lanes add to [c5 | c3] in LDS behind the
+//                 staging buffer (composition_wave_add).  count_composition is the definition, one lane per read.
+//
 // Integer/byte work only: no MFMA anywhere (the bound is HBM bandwidth).
 #pragma once
 
@@ -499,6 +506,92 @@ __device__ __forceinline__ void interior_wave_add(uint32_t *lds, const uint32_t 
 }
 
 // ---------------------------------------------------------------------------------------
+// -P: the reference base composition around the read ends
+// ---------------------------------------------------------------------------------------
+// A record that is added to the forward table counts the 2w reference positions around its 5' end into c5, one that is added to
+// the reverse table those around its 3' end into c3 (include/pssbam_hip.h): offset j = -w .. w - 1 from the end, negative outside the
+// read, is position s + j at the alignment's left end and s + L - 1 - j at its right end; a forward-strand record has its 5' end on the
+// left, a FLAG 0x10 record on the right, and the latter's classes are complemented.  class = 0 1 2 3 for A C G T, 4 for anything
+// else; row j + w, five words per row.  A position counts only inside its contig (0 <= p < glen, glen = the contig's length), and an
+// inside offset only below L: masked by position, whatever letter lies there.  This is the definition in code: tally_simple and the
+// one-lane path of tally_tiled use it as it stands, and add straight into the counter block.
+__device__ __forceinline__ uint32_t contig_length(const TallyParams &P, const RecHdr &h) {
+    return P.ref_info[(uint32_t)h.ref_id < (uint32_t)P.n_ref ? (uint32_t)h.ref_id : (uint32_t)P.n_ref].z;
+}
+__device__ void count_composition(const TallyParams &P, const uint8_t *G, int64_t glen, int64_t s, uint32_t L, bool rev, bool fwd_table, bool rev_table) {
+    const int32_t w = (int32_t)P.composition;
+    for (uint32_t blk = 0; blk < 2u; blk++) {
+        if (!(blk ? rev_table : fwd_table)) continue;
+        const bool right = (blk != 0u) != rev;   // the 5' end of a forward-strand record and the 3' end of a reverse-strand one are on the left
+        for (int32_t j = -w; j < w; j++) {
+            if (j >= 0 && (uint32_t)j >= L) continue;
+            const int64_t p = right ? s + (int64_t)L - 1 - j : s + j;
+            if (p < 0 || p >= glen) continue;
+            const uint32_t c = ref_code(G[p]);
+            const uint32_t cls = rev && c < 4u ? 3u - c : c;
+            atomicAdd(&P.counters[P.off_composition + (blk * 2u * (uint32_t)w + (uint32_t)(j + w)) * 5u + cls], 1ull);
+        }
+    }
+}
+constexpr uint32_t COMP_MAX_WORDS = 2u * 2u * 30u * 5u;   // [c5 | c3] at the largest width: 600 words
+
+// Nibble q of the result = nibble 7 - q of x.
+__device__ __forceinline__ uint32_t reverse_nibbles8(uint32_t x) {
+    const uint32_t y = __builtin_bswap32(x);
+    return ((y >> 4) & 0x0F0F0F0Fu) | ((y & 0x0F0F0F0Fu) << 4);
+}
+// How many lanes of the wave hold class X, those of the 5' block into lane X of v and those of the 3' block (in3) into lane 5 + X:
+// the two counts are scalars, and v_writelane places a scalar in one lane of a vector register.
+template <int X>
+__device__ __forceinline__ void composition_class(uint32_t cls, unsigned long long in3, uint32_t &v) {
+    const unsigned long long m = __ballot(cls == (uint32_t)X);
+    const uint32_t n5 = (uint32_t)__popcll(m & ~in3), n3 = (uint32_t)__popcll(m & in3);
+    asm("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(n5), "n"(X));
+    asm("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(n3), "n"(5 + X));
+}
+// -P, tiled form: the lanes of one wave into the workgroup's [c5 | c3] words in LDS.  u[k] holds this lane's reference nibbles (packed
+// reference: 0..3 = A C G T, anything else "other") of the offsets 8k - 32 .. 8k - 25 from its own alignment end, nibble q = offset
+// 8k + q - 32: u[0..3] the 32 positions outside the read, the adjacent one last, u[4..7] the ones inside, the end's own base first.
+// The lane counts the offsets j with lo <= j < hi (lo <= 0 <= hi; lo = hi = 0: nothing) into block `blk` (0 = c5, 1 = c3), complemented
+// when `rev`.  Every nibble becomes its class (0..4; 15 where the lane does not count); per offset one ballot per class, split by
+// block with the ballot of `blk`, gives the wave's ten counts as scalars, which ten lanes add to their own LDS words: 2w wave-wide
+// LDS adds per tile and wave, no two lanes on one word.  Called from uniform control flow.
+__device__ __forceinline__ void composition_wave_add(uint32_t *lds, uint32_t w, const uint32_t (&u)[8], int32_t lo, int32_t hi, uint32_t blk, bool rev) {
+    const uint32_t K = 0x11111111u;
+    const unsigned long long in3 = __ballot(blk != 0u);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t mine = lane < 10u ? (lane >= 5u ? 10u * w + lane - 5u : lane) : 0u;   // word of offset -w, this lane's block and class
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        if (8 * k + 8 <= 32 - (int32_t)w || 8 * k >= 32 + (int32_t)w) continue;   // (uniform: the width is a kernel argument)
+        // classes: a nibble above 3 becomes 4, a base of a reverse-strand lane its complement
+        const uint32_t other = ((u[k] >> 2) | (u[k] >> 3)) & K;
+        const uint32_t base3 = (other ^ K) * 3u;
+        uint32_t c = ((rev ? ~u[k] : u[k]) & base3) | (other << 2);
+        // the offsets this lane counts: nibbles a .. b - 1 of this word
+        const int32_t a_s = lo + 32 - 8 * k, b_s = hi + 32 - 8 * k;
+        const uint32_t a = a_s <= 0 ? 0u : a_s >= 8 ? 8u : (uint32_t)a_s, b = b_s <= 0 ? 0u : b_s >= 8 ? 8u : (uint32_t)b_s;
+        const uint32_t below_b = b >= 8u ? 0xFFFFFFFFu : (1u << (4u * b)) - 1u, below_a = a >= 8u ? 0xFFFFFFFFu : (1u << (4u * a)) - 1u;
+        c |= ~(below_b & ~below_a);
+        // the offsets of this word that the width covers (uniform); a rolled loop, one nibble a turn: the ten counts of an offset are
+        // scalars, and nothing of a later offset is worth holding in registers meanwhile
+        const int32_t q0 = max(0, 32 - (int32_t)w - 8 * k), q1 = min(8, 32 + (int32_t)w - 8 * k);
+        c >>= 4 * q0;
+#pragma unroll 1
+        for (int32_t q = q0; q < q1; q++, c >>= 4) {
+            const uint32_t cls = c & 15u;
+            uint32_t v = 0u;
+            composition_class<0>(cls, in3, v);
+            composition_class<1>(cls, in3, v);
+            composition_class<2>(cls, in3, v);
+            composition_class<3>(cls, in3, v);
+            composition_class<4>(cls, in3, v);
+            if (lane < 10u && v) atomicAdd(&lds[mine + 5u * (uint32_t)(8 * k + q - 32 + (int32_t)w)], v);   // row j + w
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // tally_simple
 // ---------------------------------------------------------------------------------------
 // dynamic LDS: [2*(N+2)*16 u32 table, if LDS_TABLE]
@@ -547,6 +640,8 @@ __global__ void __launch_bounds__(256) tally_simple(const TallyParams P) {
             if (P.mism_hist) mism_add(P, nullptr, mism_bin(P, mm), pl.pss_fwd, pl.pss_rev, 1u);
             // -W: the read's interior, once, whichever table took the read
             if (P.interior) count_interior(P, src, h, P.genome + pl.gbase, pl.s, pl.L, pl.rev);
+            // -P: the reference around the 5' end of a read in the forward table, around the 3' end of one in the reverse table
+            if (P.composition) count_composition(P, P.genome + pl.gbase, contig_length(P, h), pl.s, pl.L, pl.rev, pl.pss_fwd, pl.pss_rev);
         }
         bool kfail = false;
         if (pl.fk5 || pl.fk3) kfail = tally_kmer_record<false>(P, pl, nullptr);
@@ -676,7 +771,7 @@ __device__ __forceinline__ void stage_tile_dma(const uint8_t *recs, uint64_t rec
 // the kernel): a reference to the kernel's by-value copy would force that whole struct into
 // scratch memory.
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool MASKQ = false, bool REGIONS = false, bool HIST = false, bool SITE = false,
-          bool END = false, bool GAPPED = false, bool MISM = false, bool INTERIOR = false>
+          bool END = false, bool GAPPED = false, bool MISM = false, bool INTERIOR = false, bool COMP = false>
 __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyParams *kernarg, uint32_t o0,
                                                                     uint32_t o1, uint32_t *table, uint32_t *lds_kmer,
                                                                     uint32_t *hist_lds = nullptr, uint32_t *site_lds = nullptr,
@@ -705,6 +800,9 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyP
     if constexpr (END) tally_end_condition<MASKQ>(P, LdsEndTable{end_lds, (uint32_t)P.N + 2u}, gsrc, gh, gpl);   // (a pass-0 one as well)
     if constexpr (INTERIOR) {   // (likewise; straight into the counter block)
         if (gpl.pss_fwd || gpl.pss_rev) count_interior(P, gsrc, gh, P.genome + gpl.gbase, gpl.s, gpl.L, gpl.rev);
+    }
+    if constexpr (COMP) {   // (likewise)
+        if (gpl.pss_fwd || gpl.pss_rev) count_composition(P, P.genome + gpl.gbase, contig_length(P, gh), gpl.s, gpl.L, gpl.rev, gpl.pss_fwd, gpl.pss_rev);
     }
     bool kfail = false;
     if (DO_KMER && (gpl.fk5 || gpl.fk3)) kfail = tally_kmer_record<LDS_KMER>(P, gpl, lds_kmer);
@@ -961,9 +1059,20 @@ __device__ __forceinline__ void count_interior_staged(const uint32_t *genome4, u
 // behind the staging buffer (interior_wave_add), the left-end lane counting the read.  The words leave LDS with one 64-bit
 // atomic per non-zero word at kernel end, and every 8192 tiles of a workgroup: a tile adds fewer than 128 * 2048 = 2^18 to a
 // word, so a u32 word cannot wrap.  The instantiations without INTERIOR contain none of it.
+//
+// COMP (-P, P.composition = w non-zero; pass 0 of a one-pass launch, one plane, substitution tables only, never with MISM or INTERIOR):
+// CODES-A gathers, next to the end's window, the 32 reference positions outside the read at this end (s - 32 .. s - 1 on the left,
+// s + L .. s + L + 31 on the right: inside the padding between contigs where they leave the contig) and works out how many of the w
+// outside offsets lie inside the contig; both are first used where the window's registers are, in front of the next tile's DMA.
+// In CODES-B, once -U / -D have decided pss_fwd / pss_rev and in front of the forming of the code words, a lane whose end feeds
+// a table lays the 64 nibbles around its end out in the order of the offsets -- a right end turned round -- and the wave adds
+// them to the 20 w words [c5 | c3] in `hist_lds` behind the staging buffer (composition_wave_add): class by class, masked by
+// position, a reverse-strand lane complemented.  The words leave LDS with one 64-bit atomic per non-zero word at kernel end,
+// and every 8192 tiles of a workgroup: a tile adds at most 128 to a word, so a u32 word cannot wrap.  The instantiations
+// without COMP contain none of it.
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS, PlaneSel PLANES = PLANES_NONE, bool MASKQ = false,
           bool REGIONS = false, bool HIST = false, bool SITE = false, bool END = false, bool GAPPED = false, bool MISM = false,
-          bool INTERIOR = false>
+          bool INTERIOR = false, bool COMP = false>
 __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const TallyParams *kernarg,
                                                  uint8_t *__restrict__ stage, uint8_t *__restrict__ sheet,
                                                  uint32_t *__restrict__ table,
@@ -985,6 +1094,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
     static_assert(!GAPPED || (DO_PSS && !DO_KMER && PLANES == PLANES_NONE && !HIST && !SITE && !END), "anchored ends belong to the one-plane substitution tally without the length histogram, site context and the end condition");
     static_assert(!MISM || (DO_PSS && !DO_KMER && !LATER_PASS && PLANES == PLANES_NONE && !HIST && !SITE && !END && !GAPPED), "the mismatch count belongs to pass 0 of the one-plane substitution tally without the length histogram, site context, the end condition and anchored ends");
     static_assert(!INTERIOR || (DO_PSS && !DO_KMER && !LATER_PASS && PLANES == PLANES_NONE && !HIST && !SITE && !END && !GAPPED && !MISM), "the interior table belongs to pass 0 of the one-plane substitution tally without the length histogram, site context, the end condition, anchored ends and the mismatch count");
+    static_assert(!COMP || (DO_PSS && !DO_KMER && !LATER_PASS && PLANES == PLANES_NONE && !HIST && !SITE && !END && !GAPPED && !MISM && !INTERIOR), "the composition table belongs to pass 0 of the one-plane substitution tally without the length histogram, site context, the end condition, anchored ends, the mismatch count and the interior table");
     const uint32_t T = P.reads_per_tile;   // <= TILED_MAX_T
     const uint32_t n_recs = P.n_recs_dev ? *P.n_recs_dev : P.n_recs;   // device-indexed blocks: the count lives in device memory
     const uint32_t pieces = P.prefix_pieces;  // 16-byte pieces staged per record
@@ -1022,6 +1132,18 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
             if (tid < INTERIOR_WORDS) {
                 const uint32_t v = atomicExch(&hist_lds[tid], 0u);
                 if (v) atomicAdd(&P.counters[P.off_interior + tid], (unsigned long long)v);
+            }
+        }
+    };
+    [[maybe_unused]] const uint32_t comp_words = COMP ? 20u * P.composition : 0u;   // -P: [c5 | c3]
+    if constexpr (COMP)
+        for (uint32_t i = tid; i < comp_words; i += TILED_THREADS) hist_lds[i] = 0u;
+    // -P: the LDS words into the counter block; an exchange, so that waves that are still adding lose nothing
+    auto flush_composition = [&]() {
+        if constexpr (COMP) {
+            for (uint32_t i = tid; i < comp_words; i += TILED_THREADS) {
+                const uint32_t v = atomicExch(&hist_lds[i], 0u);
+                if (v) atomicAdd(&P.counters[P.off_composition + i], (unsigned long long)v);
             }
         }
     };
@@ -1158,6 +1280,28 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
             }
             gsh = 4u * (uint32_t)(ga & 7ull);
         }
+        // -P: the 32 reference positions outside the read at this end -- s - 32 .. s - 1 on the left, s + L .. s + L + 31 on the right --
+        // gathered like the window and with it, in front of the -U/-D test: no further dependent round trip.  A candidate has
+        // s >= 2 and s + L + 2 <= glen, so the five dwords start at most 37 bases in front of the contig and end at most 37 behind
+        // it: inside the padding between contigs (CONTIG_PAD), whose nibbles are masked by position below.  comp_out = how many
+        // of the w outside offsets lie inside the contig.
+        [[maybe_unused]] uint32_t go[COMP ? 5 : 1];
+        [[maybe_unused]] uint32_t gosh = 0u, comp_out = 0u;
+        if constexpr (COMP) {
+#pragma unroll
+            for (int k = 0; k < 5; k++) go[k] = 0u;
+            if (cand) {
+                const uint64_t oa = pl.gbase + (uint64_t)pl.s + (e ? (uint64_t)pl.L : (uint64_t)-32ll);
+                const uint32_t *po = P.genome4 + (oa >> 3);
+                const Quad q1 = *(const Quad *)po;
+#pragma unroll
+                for (int k = 0; k < 4; k++) go[k] = q1.v[k];
+                go[4] = po[4];
+                gosh = 4u * (uint32_t)(oa & 7ull);
+                const uint32_t glen = RefsLdsCached{refs_lds, P.ref_info, n_ref_cached, (uint32_t)P.n_ref}.get((uint32_t)h.ref_id < (uint32_t)P.n_ref ? (uint32_t)h.ref_id : (uint32_t)P.n_ref).z;
+                comp_out = min(P.composition, e ? glen - ((uint32_t)pl.s + pl.L) : (uint32_t)pl.s);
+            }
+        }
         // the first context base of this end (position s-1 / s+L) decides -U / -D in every pass; only
         // the window of pass 0 holds it
         uint32_t cx = 0u;
@@ -1288,7 +1432,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         if (in_tile && !in_stage && e == 0u) {
             if constexpr (KPLANES) ev_over = tally_overflow_record_kmer_planes<PLANES, LDS_KMER, REGIONS>(kernarg, gk, o0, o1, lds_kmer);
             else if constexpr (GROUPED) ev_over = tally_overflow_record_planes<PLANES, MASKQ, REGIONS>(kernarg, gk, o0, o1, table);
-            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS, HIST, SITE, END, GAPPED, MISM, INTERIOR>(kernarg, o0, o1, table, lds_kmer, hist_lds, site_lds, end_lds);
+            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS, HIST, SITE, END, GAPPED, MISM, INTERIOR, COMP>(kernarg, o0, o1, table, lds_kmer, hist_lds, site_lds, end_lds);
             if (pass0) atomicAdd(&lds_delta[ST_SLOW_PATH], 1);
         }
         // First use of the gathered registers happens HERE, before the next tile's DMA is issued:
@@ -1328,6 +1472,15 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         if constexpr (INTERIOR) {   // the walk's genome dwords and staged bytes are used up here as well
 #pragma unroll
             for (int k = 0; k < 8; k++) asm volatile("" : "+v"(ipk[k]));
+        }
+        [[maybe_unused]] uint32_t OU[COMP ? 4 : 1];   // -P: nibble q of OU[m] = outside position 8m + q of the gather, first used here like W
+        if constexpr (COMP) {
+#pragma unroll
+            for (int m = 0; m < 4; m++) {
+                OU[m] = __builtin_amdgcn_alignbit(go[m + 1], go[m], gosh);
+                asm volatile("" : "+v"(OU[m]));
+            }
+            asm volatile("" : "+v"(comp_out));
         }
         if constexpr (REGIONS) {
             // -T, resolved here for the same reason: its interval loads must not wait behind the DMA.  A candidate that
@@ -1371,6 +1524,24 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
             for (int k = 0; k < 8; k++) code_w[k] = CODE_NONE * 0x01010101u;
             // this lane's end feeds: left -> fwd table on forward reads, rev table on reverse reads
             const uint32_t tsel = e ^ (pl.rev ? 1u : 0u);
+            // -P: this lane's end feeds c5 when it is the read's 5' end (tsel = 0: the end that feeds the forward table) and the read
+            // was added to the forward table, c3 likewise.  The 64 nibbles around the end in the order of the offsets: a left end
+            // has them in genome order (the window holds s - 2 .. s + 29: two nibbles down), a right end in reverse (the window
+            // holds s + L - 30 .. s + L + 1: two nibbles up, then turned round like the outside half).
+            if constexpr (COMP) {
+                uint32_t u[8];
+#pragma unroll
+                for (int m = 0; m < 4; m++) {
+                    const uint32_t in_l = m < 3 ? __builtin_amdgcn_alignbit(W[m < 3 ? m + 1 : 3], W[m], 8) : W[3] >> 8;
+                    const uint32_t in_r = reverse_nibbles8(m < 3 ? __builtin_amdgcn_alignbit(W[3 - m], W[m < 3 ? 2 - m : 0], 24) : W[0] << 8);
+                    u[m] = e ? reverse_nibbles8(OU[3 - m]) : OU[m];
+                    u[4 + m] = e ? in_r : in_l;
+                }
+                const bool on = cand && (tsel ? pl.pss_rev : pl.pss_fwd);
+                composition_wave_add(hist_lds, P.composition, u, on ? -(int32_t)comp_out : 0, on ? (int32_t)min(P.composition, pl.L) : 0, tsel, pl.rev);
+                if ((it & 8191u) == 8191u) flush_composition();   // (a tile adds at most 128 to a word)
+                // (in front of the codes: the outside half's registers are free again where the code words need theirs)
+            }
             bool end_hit = false;   // END: this lane's end is marked
             if (cand && (tsel ? pl.pss_rev : pl.pss_fwd) && !(ablate & 2u)) {
                 // Four window positions per VALU instruction, no memory lookups: v_perm_b32 with the
@@ -1737,6 +1908,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         }
     }
     flush_interior();
+    flush_composition();
 }
 
 
@@ -2267,8 +2439,9 @@ __global__ void __launch_bounds__(256) reduce_partials(const TallyParams P, uint
 // GAPPED: nothing more in LDS (the CIGAR walk reads the staged prefix)
 // MISM: behind the staging buffer the 2 * (P.mism_hist + 2) words of the mismatch histogram, where HIST has its bins (never together)
 // INTERIOR: in the same place the 17 words [table | reads] of the interior table (never together with either)
+// COMP: in the same place the 20 * P.composition words [c5 | c3] of the composition table (never together with any of them)
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS = false, bool MASKQ = false, bool REGIONS = false, bool HIST = false,
-          bool SITE = false, bool END = false, bool GAPPED = false, bool MISM = false, bool INTERIOR = false>
+          bool SITE = false, bool END = false, bool GAPPED = false, bool MISM = false, bool INTERIOR = false, bool COMP = false>
 __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
@@ -2279,7 +2452,7 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P
     __shared__ uint4 refs_lds[REF_LDS_ENTRIES + 1];
     // the kernel's single argument, as it lies in the kernarg segment (for the out-of-line path)
     const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
-    uint32_t *hist_lds = (HIST || MISM || INTERIOR) ? (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces)) : nullptr;
+    uint32_t *hist_lds = (HIST || MISM || INTERIOR || COMP) ? (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces)) : nullptr;
     if constexpr (SITE) {
         __shared__ uint32_t site_lds[SITE_WORDS];
         tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, true>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
@@ -2289,7 +2462,7 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P
         tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, false, true>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
                                                                                                              lds_delta, refs_lds, nullptr, nullptr, hist_lds, nullptr, end_lds);
     } else
-    tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, false, false, GAPPED, MISM, INTERIOR>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
+    tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, false, false, GAPPED, MISM, INTERIOR, COMP>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
                                                                                                                   lds_delta, refs_lds, nullptr, nullptr, hist_lds);
 }
 

@@ -34,6 +34,7 @@ int frontend_min_base_quality = 0;
 int frontend_length_hist = 0;
 int frontend_mismatch_hist = 0, frontend_max_mismatches = -1, frontend_mismatch_tv = 0;
 int frontend_interior = -1;
+int frontend_composition = 0;
 int frontend_site_context = PSSBAM_SITE_NONE;
 int frontend_end_depth = 0, frontend_end_cell5 = 0, frontend_end_cell3 = 0;
 int frontend_gapped_reads = 0;
@@ -79,6 +80,7 @@ static struct early_feed {
     int hist;                       /* -H: the limit of the length histogram, set on every engine after create */
     int mism_hist, mism_max, mism_tv; /* -N / -n / -V: the mismatch count, set on every engine after create */
     int interior;                   /* -W: the interior margin, set on every engine after create */
+    int composition;                /* -P: the composition width, set on every engine after create */
     int site;                       /* -X: the site context, set on every engine after create */
     int end_depth, end_cell5, end_cell3; /* -E: the end condition, set on every engine after create */
     int gapped;                     /* -I: anchored ends, set on every engine after create */
@@ -167,6 +169,7 @@ static void *engine_make_main(void *arg)
         (EF.hist > 0 && pssbam_engine_set_length_histogram(*j->out, EF.hist)) ||
         ((EF.mism_hist > 0 || EF.mism_max >= 0) && pssbam_engine_set_mismatches(*j->out, EF.mism_hist, EF.mism_max, EF.mism_tv)) ||
         (EF.interior >= 0 && pssbam_engine_set_interior(*j->out, EF.interior)) ||
+        (EF.composition > 0 && pssbam_engine_set_composition(*j->out, EF.composition)) ||
         (EF.site != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(*j->out, EF.site)) ||
         (EF.end_depth > 0 && pssbam_engine_set_end_condition(*j->out, EF.end_depth, EF.end_cell5, EF.end_cell3)) ||
         (EF.gapped && pssbam_engine_set_gapped_reads(*j->out, 1)) || send_regions(*j->out, EF.regions) ||
@@ -303,6 +306,7 @@ void frontend_warmup_start(const pssbam_config *cfg, const char *aln_path, const
             EF.mism_max = frontend_max_mismatches;
             EF.mism_tv = frontend_mismatch_tv;
             EF.interior = frontend_interior;
+            EF.composition = frontend_composition;
             EF.site = frontend_site_context;
             EF.end_depth = frontend_end_depth;
             EF.end_cell5 = frontend_end_cell5;
@@ -330,7 +334,7 @@ static int same_str(const char *a, const char *b) { return (!a && !b) || (a && b
 static int same_length_bins(void)
 {
     return EF.n_edges == frontend_n_length_edges && EF.sets == frontend_contig_sets && EF.min_bq == frontend_min_base_quality &&
-           EF.hist == frontend_length_hist && EF.site == frontend_site_context && EF.interior == frontend_interior &&
+           EF.hist == frontend_length_hist && EF.site == frontend_site_context && EF.interior == frontend_interior && EF.composition == frontend_composition &&
            EF.mism_hist == frontend_mismatch_hist && EF.mism_max == frontend_max_mismatches && EF.mism_tv == frontend_mismatch_tv &&
            EF.end_depth == frontend_end_depth && EF.end_cell5 == frontend_end_cell5 && EF.end_cell3 == frontend_end_cell3 &&
            EF.gapped == frontend_gapped_reads && EF.per_contig == frontend_per_contig && EF.replicates == frontend_replicates && EF.regions == frontend_regions &&
@@ -471,6 +475,8 @@ void run_result_free(run_result *res)
     free(res->hist_rev);
     free(res->mism_fwd);
     free(res->mism_rev);
+    free(res->comp5);
+    free(res->comp3);
     free(res->site_fwd);
     free(res->site_rev);
     free(res->end_fwd);
@@ -677,6 +683,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
                 ((frontend_mismatch_hist > 0 || frontend_max_mismatches >= 0) &&
                  pssbam_engine_set_mismatches(eng[g], frontend_mismatch_hist, frontend_max_mismatches, frontend_mismatch_tv)) ||
                 (frontend_interior >= 0 && pssbam_engine_set_interior(eng[g], frontend_interior)) ||
+                (frontend_composition > 0 && pssbam_engine_set_composition(eng[g], frontend_composition)) ||
                 (frontend_site_context != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(eng[g], frontend_site_context)) ||
                 (frontend_end_depth > 0 && pssbam_engine_set_end_condition(eng[g], frontend_end_depth, frontend_end_cell5, frontend_end_cell3)) ||
                 (frontend_gapped_reads && pssbam_engine_set_gapped_reads(eng[g], 1)) ||
@@ -887,6 +894,20 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             goto done;
         }
         res->has_interior = 1;
+    }
+    if (frontend_composition > 0 && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -P: summed with the rest of the block */
+        const size_t words = (size_t)frontend_composition * 10;
+        res->comp5 = (uint64_t *)calloc(words, sizeof(uint64_t));
+        res->comp3 = (uint64_t *)calloc(words, sizeof(uint64_t));
+        if (!res->comp5 || !res->comp3) {
+            fprintf(stderr, "Error: out of memory\n");
+            goto done;
+        }
+        if (pssbam_engine_finish_composition(eng[0], res->comp5, res->comp3)) {
+            fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+            goto done;
+        }
+        res->composition_width = frontend_composition;
     }
     if (frontend_site_context != PSSBAM_SITE_NONE && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -X: summed with the rest of the block */
         const size_t cells = (size_t)(cfg->pss.region_len + 2) * 16;

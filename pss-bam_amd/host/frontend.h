@@ -35,6 +35,10 @@ typedef struct run_result {
     /* pss-bam -W (frontend_interior): the interior table and the number of reads that have an interior (has_interior: filled) */
     int has_interior;
     uint64_t interior[16], interior_reads;
+    /* pss-bam -P (frontend_composition): the two blocks of the composition table, 2 * composition_width rows of five counts
+     * each (malloc'ed), or NULL */
+    int composition_width;
+    uint64_t *comp5, *comp3;
     /* pss-bam -X (frontend_site_context): the in-context tables IN, (region_len+2)*16 each with rows 0/1 as fwd / rev,
      * or NULL */
     unsigned long *site_fwd, *site_rev;
@@ -68,6 +72,10 @@ extern int frontend_mismatch_hist, frontend_max_mismatches, frontend_mismatch_tv
 /* pss-bam -W: the interior margin (-1: off); every engine gets it (pssbam_engine_set_interior) and run_tally() returns the
  * table and its read count.  Set before frontend_warmup_start. */
 extern int frontend_interior;
+
+/* pss-bam -P: the width of the composition table (0: off); every engine gets it (pssbam_engine_set_composition) and
+ * run_tally() returns the two blocks.  Set before frontend_warmup_start. */
+extern int frontend_composition;
 
 /* pss-bam -X: the site context (PSSBAM_SITE_*; PSSBAM_SITE_NONE: off); every engine gets it
  * (pssbam_engine_set_site_context) and run_tally() returns the in-context pair.  Set before frontend_warmup_start. */

@@ -59,6 +59,12 @@
  * -Q only the bases that pass it -- with the number of such reads and bases, from the same pass: the background the end rows are read
  * against.  d = 0 is the whole read.  The other files stay as they are.  Needs -r <= 30.  Goes with -R, -Q, -T, -m, -l, -L, -q, -U and
  * -D.  Not with -G, -S, -C, -H, -X, -E, -I, -A, -n, -N, -V or -J.
+ * Added: -P <w> (1..30) also writes <prefix>.pss.composition.txt, the reference base composition (A C G T, other, and the four base
+ * fractions) at every offset -w .. w-1 from the 5' end of the reads that are added to the forward table and from the 3' end of those
+ * that are added to the reverse table, outside (negative) and inside the read, in the read's orientation, from the same pass: the
+ * depurination signal next to the read against its own baseline further out.  Rows -1 and -2 are the diagonal of the counts
+ * file's context rows.  The other files stay as they are.  Needs -r <= 30.  Goes with -R, -Q (no effect), -T, -m, -l, -L, -q, -U and -D.
+ * Not with -G, -S, -C, -H, -X, -E, -I, -A, -n, -N, -V, -J or -W.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -70,6 +76,7 @@
 #include <unistd.h>
 
 #include "base_quality.h"
+#include "composition.h"
 #include "contig_sets.h"
 #include "fasta-genome-io.h"
 #include "frontend.h"
@@ -92,9 +99,9 @@ int main(int argc, char *argv[])
     const char *up_ctx = "ACGT", *down_ctx = "ACGT";
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL, *read_group = NULL;
     const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL, *bed_fn = NULL, *hist_arg = NULL, *site_arg = NULL, *end_arg = NULL;
-    const char *max_mm_arg = NULL, *mm_hist_arg = NULL, *rep_arg = NULL, *interior_arg = NULL;
+    const char *max_mm_arg = NULL, *mm_hist_arg = NULL, *rep_arg = NULL, *interior_arg = NULL, *comp_arg = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:P:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -121,6 +128,7 @@ int main(int argc, char *argv[])
         case 'V': tv_only = 1; break;
         case 'J': rep_arg = optarg; break;
         case 'W': interior_arg = optarg; break;
+        case 'P': comp_arg = optarg; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -157,7 +165,8 @@ int main(int argc, char *argv[])
               "-N <M> <also write how many tallied reads have 0, 1, ..., M and more than M mismatches (1..255)>\n"
               "-V <with -n / -N: count only transversions>\n"
               "-J <K> <also write the jackknife standard errors of the rates, from K read-name replicates (2..64)>\n"
-              "-W <d> <also write the substitution counts and rates of the read interior, d bases and more from both ends (0..65535)>\n",
+              "-W <d> <also write the substitution counts and rates of the read interior, d bases and more from both ends (0..65535)>\n"
+              "-P <w> <also write the reference base composition w bases on either side of the read ends (1..30)>\n",
               stderr);
         exit(1);
     }
@@ -311,6 +320,28 @@ int main(int argc, char *argv[])
             exit(1);
         }
     }
+    int composition = 0;
+    if (comp_arg) {
+        if (by_group || len_edges || ctg_map || hist_arg || site_arg || end_arg || gapped || per_contig || max_mm_arg || mm_hist_arg || tv_only || rep_arg ||
+            interior_arg) {
+            fprintf(stderr, "-P (base composition around the read ends) and %s exclude each other.\n",
+                    by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)" : ctg_map ? "-C (tables per contig set)"
+                    : hist_arg ? "-H (fragment-length histogram)" : site_arg ? "-X (tables per site context)"
+                    : end_arg ? "-E (tables conditional on the other end)" : gapped ? "-I (clipped and gapped reads by their anchored ends)"
+                    : per_contig ? "-A (tables per contig)" : max_mm_arg ? "-n (mismatch filter)" : mm_hist_arg ? "-N (mismatch histogram)"
+                    : tv_only ? "-V (count only transversions)" : rep_arg ? "-J (jackknife replicates)" : "-W (read-interior table)");
+            exit(1);
+        }
+        char err[200];
+        if ((composition = pss_parse_composition_width(comp_arg, err, sizeof err)) < 0) {
+            fprintf(stderr, "%s\n", err);
+            exit(1);
+        }
+        if (region_len > 30) {
+            fprintf(stderr, "-P (base composition around the read ends) needs -r <= 30 (a read's fate and its end windows are those of the one pass over 32 table rows), not -r %d.\n", region_len);
+            exit(1);
+        }
+    }
     pss_regions bed;
     memset(&bed, 0, sizeof bed);
     if (bed_fn) {
@@ -374,6 +405,7 @@ int main(int argc, char *argv[])
     if (tv_only) fprintf(stderr, " -V");
     if (rep_arg) fprintf(stderr, " -J %d", replicates);
     if (interior_arg) fprintf(stderr, " -W %d", interior);
+    if (comp_arg) fprintf(stderr, " -P %d", composition);
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -408,6 +440,7 @@ int main(int argc, char *argv[])
     frontend_mismatch_tv = tv_only;
     frontend_replicates = replicates;
     frontend_interior = interior;
+    frontend_composition = composition;
     if (bed_fn) frontend_regions = &bed;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
@@ -435,6 +468,7 @@ int main(int argc, char *argv[])
     if (res.hist_fwd && pss_write_lengths(fasta_fn, bam_fn, out_prefix, res.hist_max, res.hist_fwd, res.hist_rev)) exit(1);
     if (res.mism_fwd && pss_write_mismatches(fasta_fn, bam_fn, out_prefix, res.mism_max, tv_only, res.mism_fwd, res.mism_rev)) exit(1);   /* -N */
     if (res.has_interior && pss_write_interior(fasta_fn, bam_fn, out_prefix, interior, min_bq, res.interior, res.interior_reads)) exit(1);   /* -W */
+    if (res.comp5 && pss_write_composition(fasta_fn, bam_fn, out_prefix, res.composition_width, res.comp5, res.comp3)) exit(1);   /* -P */
     if (res.site_fwd) {   /* -X: IN as the engine returns it; OUT = T - IN on the position rows, the context rows as T */
         const size_t cells = (size_t)(region_len + 2) * 16;
         unsigned long *out_fwd = (unsigned long *)malloc(cells * sizeof *out_fwd), *out_rev = (unsigned long *)malloc(cells * sizeof *out_rev);

@@ -4,6 +4,7 @@
  * /root/reference/pss-bam.c:504-633 and fragkon.c:231-249,:367-368.
  */
 #include "report.h"
+#include "composition.h"
 #include "interior.h"
 #include "pssbam_hip.h"
 
@@ -287,6 +288,41 @@ int pss_write_interior(const char *fasta_fn, const char *bam_fn, const char *out
     fputs("### POS AC AG AT CA CG CT GA GC GT TA TC TG\n", fp);
     rate_row(fp, margin, rates);
     fprintf(fp, "reads\t%llu\nbases\t%llu\n", (unsigned long long)reads, (unsigned long long)bases);
+    return fclose(fp) ? 1 : 0;
+}
+
+static void composition_row(FILE *fp, int label, const uint64_t *row)
+{
+    double frac[4];
+    pss_composition_fractions(row, frac);
+    fprintf(fp, "%d\t", label);
+    for (int j = 0; j < 5; j++) fprintf(fp, "%lu\t", (unsigned long)row[j]); /* every row ends in a TAB */
+    for (int j = 0; j < 4; j++) fprintf(fp, "%.5e\t", frac[j]);
+    fputc('\n', fp);
+}
+
+int pss_write_composition(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int width, const uint64_t *c5,
+                          const uint64_t *c3)
+{
+    char fn[FN_BUF + 1];
+    FILE *fp;
+    snprintf(fn, sizeof fn, "%s.pss.composition.txt", out_prefix);
+    fp = fopen(fn, "w");
+    if (!fp) {
+        fprintf(stderr, "ERROR: Cannot write to file %s\n.", fn);
+        return 1;
+    }
+    fprintf(fp, "# reference base composition %d bases on either side of the ends of the tallied reads, in the read's orientation"
+                " (negative: outside the read)\n", width);
+    fprintf(fp, "# FASTA: %s\n# BAM: %s\n", fasta_fn, bam_fn);
+    fputs("### POS A C G T other fA fC fG fT\n", fp);
+    fputs("### Forward read base composition around the 5' end\n", fp);
+    for (int j = -width; j < width; j++) composition_row(fp, j, c5 + (size_t)(j + width) * 5);
+    /* two blank lines separate the gnuplot data sets; the 3' block mirrors the counts file: inside rows down to the end, then
+     * the bases past the alignment labelled 1 .. width */
+    fputs("\n\n### Reverse read base composition around the 3' end\n", fp);
+    for (int j = width - 1; j >= 0; j--) composition_row(fp, j, c3 + (size_t)(j + width) * 5);
+    for (int j = 1; j <= width; j++) composition_row(fp, j, c3 + (size_t)(width - j) * 5);
     return fclose(fp) ? 1 : 0;
 }
 

@@ -51,6 +51,14 @@ int pss_write_mismatches(const char *fasta_fn, const char *bam_fn, const char *o
  * of the rates file; then "reads\t<reads>" and "bases\t<sum of the 16 counts>".  Returns 0, or 1 after a diagnostic. */
 int pss_write_interior(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int margin, int min_bq, const uint64_t table[16],
                        uint64_t reads);
+/* pss-bam -P: <out_prefix>.pss.composition.txt -- a '#' line that states the width and two with the input names, the column
+ * names "### POS A C G T other fA fC fG fT", a "### Forward..." line and the 5' block's rows labelled -width .. -1, 0 .. width-1;
+ * two blank lines; a "### Reverse..." line and the 3' block's inside rows labelled width-1 .. 0, then its outside rows labelled
+ * 1 .. width (1 = the base next to the read), as the counts file orders its reverse table.  A row is the label, the five counts
+ * of A C G T and other ("%lu") and the four fractions count / (A + C + G + T) ("%.5e", all zero when the sum is zero), every
+ * field followed by a TAB.  c5 / c3: 2 * width rows of five counts, row j + width = offset j.  Returns 0, or 1 after a diagnostic. */
+int pss_write_composition(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int width, const uint64_t *c5,
+                          const uint64_t *c3);
 /* k5 / k3: 4^klen 64-bit bins (clamped to UINT_MAX on output) */
 int fragkon_write_table(FILE *out, const char *fasta_fn, const char *bam_fn, int klen, const uint64_t *k5,
                         const uint64_t *k3);
