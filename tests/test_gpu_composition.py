@@ -396,6 +396,29 @@ def test_seventy_thousand_identical_records(pkg, kernel):
     assert int(c5.max()) >= n // 2 > 1 << 15 and int(c5.sum()) == 2 * w * n == int(c3.sum())
 
 
+def test_one_workgroup_walks_more_than_8192_tiles(pkg, monkeypatch):
+    """the LDS words are handed to the counter block every 8192 tiles of a workgroup (so that a u32 word cannot wrap): one
+    workgroup, tiles of 16 reads, 8 200 tiles -- the counts on both sides of the hand-over add up"""
+    monkeypatch.setenv("PSSBAM_GRID_WGS", "1")
+    monkeypatch.setenv("PSSBAM_TILE_READS", "16")
+    contigs, refs, text = clean()
+    recs = [il.read_on(text, 100 + 13 * j, 24, name=f"t{j:03d}", flag=16 * (j & 1)) for j in range(160)]
+    o, w, times = tl.PssOpts(region_len=5), 30, 820
+    w5, w3, n_fwd, n_rev = cl.composition(recs, contigs, w, o)
+    assert n_fwd == n_rev == 160 and w5[:w + 24, :4].all() and w3[:w + 24, :4].all() and not np.array_equal(w5, w3)
+    assert int(w5[w + 23].sum()) == 160 and not w5[w + 24:].any()              # reads of 24 bases: the inside offsets from 24 on stay empty
+    block = np.tile(tl.raw_records(refs, recs), times)
+    eng = pkg.Engine(pss=pss_dict(o), kernel=pkg.KERNEL_TILED, composition=w)
+    eng.set_genome_arrays(tl.loaded_contigs(contigs))
+    eng.set_references([nm for nm, _ in refs])
+    eng.submit(block)
+    c5, c3 = eng.finish_composition()
+    tot = eng.finish()
+    eng.close()
+    assert tot.stats["records"] == 160 * times > 8192 * 16 and tot.stats["pss_ok"] == 160 * times
+    assert np.array_equal(c5, w5 * np.uint64(times)) and np.array_equal(c3, w3 * np.uint64(times))
+
+
 def test_submit_bgzf(pkg, fuzz, tmp_path):
     """the compressed feed (device-indexed blocks) goes through the same launches; the setting follows feed_open"""
     contigs, refs, recs = fuzz

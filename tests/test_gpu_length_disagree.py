@@ -3,25 +3,25 @@
 Two thirds of the 3 200 records of each dataset are proper pairs whose CIGAR is `<|TLEN|>M` while SEQ holds fewer bases
 (down to one, or none: SEQ *), as many, or more (up to twice as many): length_disagree_lib.  The kernels carry code for
 exactly this case -- read_nibble returns 0 past l_seq, the staged arms blank the codes at or past l_seq (and their
-qualities under -Q), count_mismatches stops at min(L, l_seq), the 3' window sits at SEQ[L-1-i] -- and no other test
-runs it beyond first mates with a shorter SEQ under -n / -N.  Their QUAL bytes are made of base codes, so a kernel that
-reads past SEQ changes a cell.
+qualities under -Q), count_mismatches stops at min(L, l_seq), the interior walk of -W stops at min(L - d, l_seq), the
+3' window sits at SEQ[L-1-i] -- and no other test runs it beyond first mates with a shorter SEQ under -n / -N and -W.
+Their QUAL bytes are made of base codes, so a kernel that reads past SEQ changes a cell.
 
 The engine always gets the records as they are.  Every pss expectation is the arm's own feature expectation, built on
 the CPU from normalise(recs) (SEQ cut to |TLEN| bases or N-padded up to them) the way the arm's feature test builds it;
 the k-mer expectation is the oracle's on the records as they are (fragkon filters a disagreeing record).
-test_length_disagree_host.py shows without a GPU that the oracle itself obeys that rule on these very records, that two
+test_length_disagree_host.py shows without a GPU that the oracle itself obeys that rule on these very records, that three
 wrong kernels would be caught, and that normalise commutes with each feature lib.  Launch shapes, Arm and run_arm (and
 through it check) are test_gpu_tile_loop's.  Bit-exact (integer work)."""
-from types import SimpleNamespace
-
 import numpy as np
 import pytest
 
 import __graft_entry__ as ge
 import base_quality_lib as bq
+import composition_lib as cl
 import end_condition_lib as ec
 import gapped_lib as gl
+import interior_lib as il
 import length_disagree_lib as ld
 import mismatch_lib as ml
 import pssbam_testlib as tl
@@ -41,6 +41,8 @@ pytestmark = pytest.mark.gpu
 SEED, N_READS, REGION = ld.SEED, ld.N_READS, ld.REGION
 MISM = (10, 3)          # -N 10 -n 3
 REPLICATES = 5
+INTERIOR_MARGIN = 5     # -W 5
+COMPOSITION = 10        # -P 10
 
 
 # ---- expectations (CPU only) ------------------------------------------------------------------------------------------
@@ -168,6 +170,31 @@ def build_arms(oracle, tmp):
     # -J 5: read-name replicates
     reps = [table_pair(oracle.pss(g, sam_of(tmp, "rep.sam", p.refs, rp.reduce(norm, REPLICATES, j)), o)[:2]) for j in range(REPLICATES)]
     A["J5_r25"] = Arm("main", dict(pss=dict(region_len=25), replicates=REPLICATES), dict(tables=plain[25][0], replicates=reps, stats=stats_of(N_READS, plain[25][1])))
+    # -W 5 (and under -Q 20) and -P 10: the interior is { i : d <= i, i + d < L, i < l_seq }, so the table is that of the
+    # normalised records (cut at L, N beyond l_seq); `reads` counts the records whose interior is not empty, which a
+    # record with l_seq <= d is not: that count comes from the records as they are.  -P looks at the reference alone.
+    ctg = dict(p.contigs)
+    entered = {k: [x for x in ld.crafted(p.recs) if ld.kind(x) == k and any(il.tables_entered(x, ctg, o))] for k in ("short", "long", "star")}
+    assert min(len(v) for v in entered.values()) >= 50, {k: len(v) for k, v in entered.items()}     # each kind is among the reads added to a table
+    for q in (0, 20):
+        table, n_norm, tallied = il.interior(norm, p.contigs, INTERIOR_MARGIN, o, q)
+        as_is_table, reads, as_is_tallied = il.interior(p.recs, p.contigs, INTERIOR_MARGIN, o, q)
+        assert np.array_equal(table, as_is_table) and tallied == as_is_tallied == plain[25][1][tl.ST_OK] and table.all()
+        empty = sum(1 for x in p.recs if ld.governed(x) and any(il.tables_entered(x, ctg, o))
+                    and (0 if x.seq == "*" else len(x.seq)) <= INTERIOR_MARGIN < abs(x.tlen) - INTERIOR_MARGIN)
+        assert 0 < empty == n_norm - reads                                      # SEQ ends before the interior begins
+        for k in ("short", "long"):     # ... and each of these kinds adds bases of its own (a star read has none)
+            assert il.interior(entered[k], p.contigs, INTERIOR_MARGIN, o, q)[0].any(), k
+        tabs = plain[25][0] if not q else A["Q20_r25"].want["tables"]
+        A["W5_r25" if not q else "W5_Q20_r25"] = Arm("main", dict(pss=dict(region_len=25), interior=INTERIOR_MARGIN, min_base_qual=q),
+                                                     dict(tables=tabs, interior=(table, reads), stats=stats_of(N_READS, plain[25][1])))
+    assert int(A["W5_Q20_r25"].want["interior"][0].sum()) < int(A["W5_r25"].want["interior"][0].sum())
+    c5, c3, n_fwd, n_rev = cl.composition(norm, p.contigs, COMPOSITION, o)
+    assert all(np.array_equal(a, b) for a, b in zip((c5, c3), cl.composition(p.recs, p.contigs, COMPOSITION, o)[:2])) and n_fwd > 500 and n_rev > 500
+    for k, sub in entered.items():
+        k5, k3, _, _ = cl.composition(sub, p.contigs, COMPOSITION, o)
+        assert k5.any() and k3.any(), k
+    A["P10_r25"] = Arm("main", dict(pss=dict(region_len=25), composition=COMPOSITION), dict(tables=plain[25][0], composition=(c5, c3), stats=stats_of(N_READS, plain[25][1])))
     oracle.free_genome(g)
 
     # ---- -C and -A: four contigs ----------------------------------------------------------------------------------------
@@ -212,11 +239,12 @@ def build_arms(oracle, tmp):
 # ---- the cases ------------------------------------------------------------------------------------------------------
 
 COMPACT = ["compact_r7", "compact_r16", "compact_r16_k4", "plan_once_r15"]
-TILED = ["tiled_r25", "tiled_r40", "tiled_r25_k5", "Q20_r25", "Q20_r40", "T_r15", "T_r40", "H100_r25", "X_r25", "I_r25", "mism_r25", "mism_r25_V", "E_ds2_r25"]
+TILED = ["tiled_r25", "tiled_r40", "tiled_r25_k5", "Q20_r25", "Q20_r40", "T_r15", "T_r40", "H100_r25", "X_r25", "I_r25", "mism_r25", "mism_r25_V", "E_ds2_r25",
+         "W5_r25", "W5_Q20_r25", "P10_r25"]
 PLANES = ["S_r25", "S_r40", "C_r25", "G_r25", "A_r25", "J5_r25"]
-OVERFLOW = ["tiled_r25", "Q20_r25", "I_r25"]
+OVERFLOW = ["tiled_r25", "Q20_r25", "I_r25", "W5_r25", "W5_Q20_r25", "P10_r25"]
 SIMPLE = ["compact_r7", "tiled_r40", "tiled_r25_k5", "Q20_r25", "T_r15", "H100_r25", "X_r25", "I_r25", "mism_r25", "mism_r25_V", "E_ds2_r25",
-          "S_r25", "C_r25", "G_r25", "A_r25", "J5_r25"]
+          "S_r25", "C_r25", "G_r25", "A_r25", "J5_r25", "W5_r25", "W5_Q20_r25", "P10_r25"]
 FEED = ["plan_once_r15", "Q20_r25"]      # (plain -r 15; the environment of plan_once is not set for the feed)
 
 
@@ -234,42 +262,10 @@ def built(oracle, tmp_path_factory):
     return D, A
 
 
-def check_more(eng, want: dict):
-    """the tables test_gpu_tile_loop.check does not know: -N, -A and -J"""
-    if "mism" in want:
-        mf, mr = eng.finish_mismatches()
-        assert np.array_equal(mf, want["mism"][0]) and np.array_equal(mr, want["mism"][1]), "mismatch histograms differ"
-    if "contigs" in want:
-        got = eng.finish_contigs()
-        assert sorted(got) == sorted(want["contigs"])
-        for k, (wf, wr) in want["contigs"].items():
-            assert np.array_equal(got[k].fwd, wf) and np.array_equal(got[k].rev, wr), ("contig plane", k)
-    if "replicates" in want:
-        fwd, rev = eng.finish_replicates()
-        assert len(fwd) == len(rev) == len(want["replicates"])
-        for j, (wf, wr) in enumerate(want["replicates"]):
-            assert np.array_equal(fwd[j], wf) and np.array_equal(rev[j], wr), ("replicate", j)
-
-
-def checking(pkg, want: dict):
-    """pkg as run_arm takes it, with engines whose finish() looks at the -N / -A / -J tables first (run_arm's check then
-    compares the rest)"""
-    def engine(**kw):
-        eng = pkg.Engine(**kw)
-        finish = eng.finish
-
-        def checked_finish():
-            check_more(eng, want)
-            return finish()
-        eng.finish = checked_finish
-        return eng
-    return SimpleNamespace(Engine=engine)
-
-
 def case(pkg, built, monkeypatch, name, shape=None, kernel=None, feed=None, env=True):
     arm = built[1][name]
     set_env(monkeypatch, SHAPES[shape] if shape else {}, arm.env if env else {})
-    tot, _ = run_arm(checking(pkg, arm.want), built, name, pkg.KERNEL_AUTO if kernel is None else kernel, feed=feed)
+    tot, _ = run_arm(pkg, built, name, pkg.KERNEL_AUTO if kernel is None else kernel, feed=feed)
     return tot
 
 

@@ -373,6 +373,25 @@ def check(eng, want: dict):
         for key, (a, b) in exp.items():
             t = got[key]
             assert (same(t.k5, a) and same(t.k3, b)) if t.fwd is None else (same(t.fwd, a) and same(t.rev, b)), (kind, key)
+    if "mism" in want:
+        mf, mr = eng.finish_mismatches()
+        assert same(mf, want["mism"][0]) and same(mr, want["mism"][1]), "mismatch histograms differ"
+    if "contigs" in want:
+        got = eng.finish_contigs()
+        assert sorted(got) == sorted(want["contigs"])
+        for k, (wf, wr) in want["contigs"].items():
+            assert same(got[k].fwd, wf) and same(got[k].rev, wr), ("contig plane", k)
+    if "replicates" in want:
+        fwd, rev = eng.finish_replicates()
+        assert len(fwd) == len(rev) == len(want["replicates"])
+        for j, (wf, wr) in enumerate(want["replicates"]):
+            assert same(fwd[j], wf) and same(rev[j], wr), ("replicate", j)
+    if "interior" in want:
+        table, reads = eng.finish_interior()
+        assert same(table, want["interior"][0]) and reads == want["interior"][1], ("interior table differs", reads, want["interior"][1])
+    if "composition" in want:
+        c5, c3 = eng.finish_composition()
+        assert same(c5, want["composition"][0]) and same(c3, want["composition"][1]), "composition blocks differ"
     tot = eng.finish()
     if want.get("tables") is not None:
         assert same(tot.fwd, want["tables"][0]) and same(tot.rev, want["tables"][1]), "substitution tables differ"

@@ -3,15 +3,17 @@
 A paired `<|TLEN|>M` record is tallied as if SEQ were cut to |TLEN| bases or N-padded on the right up to |TLEN| bases
 (length_disagree_lib.normalise).  Here the oracle shows that on the very dataset the GPU test feeds the engine, that
 most of the disagreeing records are tallied, that the dataset covers every residue of l_seq mod 8 and every record
-offset mod 16, that two wrong models (the 3' end anchored on l_seq; missing bases read from QUAL) give other tables,
-and that normalise commutes with every feature lib the GPU test builds its expectations with.  Bit-exact."""
+offset mod 16, that three wrong models (the 3' end anchored on l_seq; missing bases read from QUAL; the interior walk
+of -W running to L - d whatever l_seq) give other tables, and that normalise commutes with every feature lib the GPU test builds its expectations with.  Bit-exact."""
 from collections import Counter
 
 import numpy as np
 import pytest
 
 import base_quality_lib as bq
+import composition_lib as cl
 import gapped_lib as gl
+import interior_lib as il
 import length_disagree_lib as ld
 import mismatch_lib as ml
 import pssbam_testlib as tl
@@ -104,7 +106,9 @@ def test_share_tallied(case, n):
 @pytest.mark.parametrize("which", ["short", "long"])
 def test_wrong_models_give_other_tables(case, which, n):
     """the 3' end anchored on l_seq: other tables for short and for long SEQ.  Missing bases read from the QUAL nibbles:
-    other tables for short SEQ; a long SEQ has no missing base, and there the model must be the identity."""
+    other tables for short SEQ; a long SEQ has no missing base, and there the model must be the identity.  The -W walk
+    that runs to L - d and ignores l_seq reads those same nibbles: another interior table for short SEQ, with and without
+    -Q 20 (the bytes behind a short SEQ are QUAL, so the wrong walk also takes its qualities from the wrong place)."""
     sub = [r for r in ld.crafted(case["recs"]) if ld.kind(r) == which]
     true = case["run"]("true.sam", sub, n)
     anch = case["run"]("anchor.sam", ld.anchor_on_l_seq(sub), n)
@@ -117,6 +121,11 @@ def test_wrong_models_give_other_tables(case, which, n):
         masked = case["run"]("unblanked_q20.sam", bq.mask_recs(ld.unblanked(sub), 20), n)           # and with -Q 20 still
         true_q = case["run"]("true_q20.sam", bq.mask_recs(ld.normalise(sub), 20), n)
         assert (masked[0][2:] != true_q[0][2:]).any() and (masked[1][2:] != true_q[1][2:]).any()
+        o = tl.PssOpts(region_len=n)
+        for q in (0, 20):
+            right = il.interior(sub, case["contigs"], 5, o, q)
+            wrong = il.interior(ld.unblanked(sub), case["contigs"], 5, o, q)
+            assert right[2] == wrong[2] > 300 and (wrong[0] != right[0]).any() and wrong[1] > right[1], (q, right[1:], wrong[1:])
     else:
         assert ld.unblanked(sub) == ld.normalise(sub)
 
@@ -141,6 +150,13 @@ def test_normalise_commutes_with_the_feature_libs(oracle, case):
     assert ml.reduce_to(norm, contigs, 3) == ld.normalise(ml.reduce_to(recs, contigs, 3))
     assert 0 < len(ml.reduce_to(odd, contigs, 3)) < len(odd)
     o = tl.PssOpts(region_len=25)
+    for q in (0, 20):       # -W: the table and the reads added to a table commute; a record whose SEQ ends at or before d has an empty interior as it is
+        x, y = il.interior(recs, contigs, 5, o, q), il.interior(norm, contigs, 5, o, q)
+        assert np.array_equal(x[0], y[0]) and x[0].all() and x[2] == y[2] > 0.6 * N_READS
+        ended = sum(1 for r in recs if ld.governed(r) and any(il.tables_entered(r, dict(contigs), o)) and (0 if r.seq == "*" else len(r.seq)) <= 5 < abs(r.tlen) - 5)
+        assert y[1] - x[1] == ended > 50
+    x, y = cl.composition(recs, contigs, 10, o), cl.composition(norm, contigs, 10, o)      # -P looks at no read base
+    assert all(np.array_equal(a, b) for a, b in zip(x[:2], y[:2])) and x[2:] == y[2:] and x[0].any() and x[1].any()
     a, b = direct_hist(contigs, recs, o, HIST_MAX), direct_hist(contigs, norm, o, HIST_MAX)
     assert all(same(a[c], b[c]) for c in a)
     for name, rs in (("asis.sam", recs), ("norm.sam", norm)):
