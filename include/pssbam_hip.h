@@ -40,6 +40,10 @@ extern "C" {
 #define PSSBAM_MAX_MISMATCHES 255    /* pssbam_engine_set_mismatches: the largest histogram limit and the largest filter limit */
 #define PSSBAM_MAX_INTERIOR_MARGIN 65535 /* pssbam_engine_set_interior: the largest margin */
 #define PSSBAM_MAX_COMPOSITION 30    /* pssbam_engine_set_composition: the largest width */
+#define PSSBAM_MAX_SCORE_DIST 64     /* pssbam_engine_set_read_score: the most distance rows of the weight table */
+#define PSSBAM_MAX_SCORE_QUAL 64     /* pssbam_engine_set_read_score: the most quality columns of the weight table */
+#define PSSBAM_MAX_SCORE_WEIGHT 2047 /* pssbam_engine_set_read_score: the largest weight, either sign */
+#define PSSBAM_MAX_SCORE_HALF 128    /* pssbam_engine_set_read_score: the largest half width of the score histogram */
 #define PSSBAM_MAX_HIST_LENGTH 65535 /* pssbam_engine_set_length_histogram: the largest limit (lengths above it share one row) */
 #define PSSBAM_MAX_BASE_QUALITY 93   /* pssbam_engine_set_min_base_quality: the largest Phred value SAM text can print */
 #define PSSBAM_MAX_REGIONS (1 << 26) /* pssbam_engine_set_regions: intervals in one call */
@@ -588,6 +592,52 @@ int pssbam_engine_set_composition(pssbam_engine *e, int32_t width /*0 = off*/);
  * either pointer may be NULL.  PSSBAM_EINVAL when the setting is off. */
 int pssbam_engine_finish_composition(pssbam_engine *e, uint64_t *c5, uint64_t *c3);
 
+/* Read score (pss-bam -y / -Y): a record filter on a sum of caller-supplied integer weights over the C and G sites of the whole
+ * read, and the histogram of that sum over the reads that are added to the tables, from the same pass.  The engine knows
+ * nothing of what the weights mean; pss-bam passes the log-likelihood ratios of a post-mortem-damage model.
+ * The score S of a record is defined for the records the mismatch count is defined for: a CIGAR of exactly <L>M, L being the
+ * length that min_read_len / max_read_len compare, on a contig the genome holds.  With s = POS - 1, seq[i] read base i as stored
+ * (the BAM nibble), g[p] the contig after the case folding the engine applies anyway and rev = FLAG 0x10, position
+ * i < min(L, l_seq) takes part when s + i lies inside the contig, seq[i] and g[s+i] are both one of A C G T and -- with a minimum
+ * base quality set -- QUAL[i] >= min_bq (the rule of the interior table: absent qualities, 0xFF, are never below).  A position that
+ * takes part contributes weights[kind][d][q]:
+ *     g = C, seq = C:  d = min(i, n_dist-1),        kind 0 on a forward read, 2 on a reverse read
+ *     g = C, seq = T:  d = min(i, n_dist-1),        kind 1 / 3
+ *     g = G, seq = G:  d = min(L-1-i, n_dist-1),    kind 2 / 0
+ *     g = G, seq = A:  d = min(L-1-i, n_dist-1),    kind 3 / 1
+ *     anything else:   nothing
+ * q = min(QUAL[i], n_qual-1) on the stored byte, so absent qualities land in the last column.  In read orientation kinds 0 / 1
+ * are C->C and C->T by distance from the 5' end, kinds 2 / 3 G->G and G->A by distance from the 3' end.  S is the mathematical
+ * sum clamped to the int32 range (with |w| <= PSSBAM_MAX_SCORE_WEIGHT 32 bits cannot overflow below 2^20 bases).
+ * weights: int16 [4][n_dist][n_qual], n_dist = 1..PSSBAM_MAX_SCORE_DIST, n_qual = 1..PSSBAM_MAX_SCORE_QUAL, every entry within
+ * +-PSSBAM_MAX_SCORE_WEIGHT; copied to the device at the call.  NULL switches everything off (the other arguments are then
+ * ignored): the engine then launches exactly the kernels it launches without this call and n_u64 is unchanged.
+ * Filter, use_filter != 0: one more record filter, like the mismatch limit.  A record that every other filter would add to a
+ * table and that has S < min_score counts as PSSBAM_ST_PSS_FILTERED; RECORDS, RG_DROPPED, PARSE_SKIP, NO_CONTIG and the sum
+ * PSS_OK + PSS_FILTERED stay as without the setting.  fwd, rev and PSS_OK == those of the engine without the setting on the input
+ * without the records whose S is defined and below min_score.
+ * Histogram, hist_half = H (1..PSSBAM_MAX_SCORE_HALF; 0 = off), hist_shift = 0..16: two arrays of 2H counters, sf and sr.  With
+ * b = clamp(S >> hist_shift, -H, H-1) + H, the shift arithmetic (it floors negative scores too): sf[b] += 1 when the record is
+ * added to the forward table, sr[b] += 1 when it is added to the reverse table -- the identities of the mismatch histogram with
+ * "the records whose bin is b".  With the filter on only kept reads are counted.  Tables and status counters are bit-identical to
+ * the engine without the histogram.
+ * Legal after create (or reset) and before the first tally launch; with pssbam_engine_feed_open that is any time before
+ * set_references.  Goes with cfg.read_group, a minimum base quality and regions.  PSSBAM_EINVAL for arguments outside their
+ * ranges or a weight beyond the limit, on an engine whose mask is not PSSBAM_TALLY_PSS alone, for region_len > 30 (the decision is
+ * taken in the one pass that holds all rows), and with read groups, length bins, contig sets, per-contig tables, replicates, a
+ * length histogram, site context, an end condition, gapped reads, the mismatch count, the interior table or the composition
+ * table set (each of those setters returns PSSBAM_EINVAL once this one is on); PSSBAM_ESTATE once records have been tallied, or
+ * once a bound counter block would have to grow (see pssbam_engine_counters_device).  The setting survives pssbam_engine_reset;
+ * engines whose blocks are summed must all have been given the same arguments.  PSSBAM_KERNEL_AUTO never takes tally_compact
+ * with it on. */
+int pssbam_engine_set_read_score(pssbam_engine *e, const int16_t *weights /*[4][n_dist][n_qual], NULL = off*/, int32_t n_dist,
+                                 int32_t n_qual, int32_t use_filter, int32_t min_score, int32_t hist_half /*0 = no histogram*/,
+                                 int32_t hist_shift /*0..16*/);
+
+/* Drains the engine like pssbam_engine_finish and copies the two arrays, 2 * hist_half words each; either pointer may be
+ * NULL.  PSSBAM_EINVAL without a histogram. */
+int pssbam_engine_finish_read_score(pssbam_engine *e, uint64_t *fwd, uint64_t *rev);
+
 /* The device-resident counter block [fwd | rev | k5 | k3 | stats] as one array of
  * n_u64 64-bit words, for a caller-side RCCL reduce across GPUs (sum, uint64).  With read groups it is
  * [fwd | rev | stats | fwd_0 | rev_0 | ... | fwd_n-1 | rev_n-1]: the leading fwd | rev are the unassigned
@@ -621,7 +671,11 @@ int pssbam_engine_finish_composition(pssbam_engine *e, uint64_t *c5, uint64_t *c
  * With the composition table of width w (pssbam_engine_set_composition; a PSSBAM_TALLY_PSS engine without any of the above)
  * its two blocks are appended in the same place: [fwd | rev | stats | c5 | c3], c5 at 2*(region_len+2)*16 + PSSBAM_ST_N (the
  * old n_u64), c3 10*w words behind it, each row-major [j + w][class], n_u64 larger by 20*w.  All words are plain counts: the
- * block still sums as one u64 array. */
+ * block still sums as one u64 array.
+ * With a read-score histogram of half width H (pssbam_engine_set_read_score; a PSSBAM_TALLY_PSS engine without any of the above)
+ * the two arrays are appended in the same place: [fwd | rev | stats | sf | sr], sf at 2*(region_len+2)*16 + PSSBAM_ST_N (the old
+ * n_u64), sr 2H words behind it, n_u64 larger by 4H.  All words are plain counts: the block still sums as one u64 array.  The
+ * filter alone adds no words. */
 int pssbam_engine_counters_device(pssbam_engine *e, void **d_counters, size_t *n_u64);
 
 /* Makes the engine accumulate into caller-owned device memory (n_u64 words, as reported

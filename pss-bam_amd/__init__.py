@@ -49,6 +49,7 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_mismatches", "pssbam_engine_finish_mismatches", "pssbam_engine_set_replicates",
     "pssbam_engine_set_interior", "pssbam_engine_finish_interior",
     "pssbam_engine_set_composition", "pssbam_engine_finish_composition",
+    "pssbam_engine_set_read_score", "pssbam_engine_finish_read_score",
 ]
 MAX_READ_GROUPS = 4096
 MAX_LENGTH_BINS = 64
@@ -59,6 +60,10 @@ MAX_HIST_LENGTH = 65535
 MAX_MISMATCHES = 255
 MAX_INTERIOR_MARGIN = 65535
 MAX_COMPOSITION = 30
+MAX_SCORE_DIST = 64
+MAX_SCORE_QUAL = 64
+MAX_SCORE_WEIGHT = 2047
+MAX_SCORE_HALF = 128
 MAX_REGIONS = 1 << 26
 SITE_NONE, SITE_CPG = 0, 1
 SITE_MODES = {None: SITE_NONE, "none": SITE_NONE, "cpg": SITE_CPG}
@@ -145,6 +150,8 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_finish_interior.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_composition.argtypes = [C.c_void_p, C.c_int32]
     L.pssbam_engine_finish_composition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pssbam_engine_set_read_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    L.pssbam_engine_finish_read_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_finish_contigs.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_set_regions.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_engine_counters_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
@@ -235,6 +242,8 @@ class Engine:
     ends of every tallied read, see set_interior; None = off.
     `composition` = w (pss-bam -P): the reference base composition w bases on either side of the 5' end of the reads in the
     forward table and of the 3' end of those in the reverse table, see set_composition; None = off.
+    `read_score` = dict(weights=, min_score=, hist_half=, hist_shift=) (pss-bam -y / -Y): a filter on, and the histogram of, a
+    weighted score over the C and G sites of the whole read, see set_read_score; None = off.
     With `kmer` alone (no `pss`) the three split the k-mer tables instead (fragkon -G / -S / -C): every plane is a
     k5 / k3 pair, and the length bins go by the SEQ length and kmer's min_read_len / max_read_len."""
 
@@ -243,7 +252,8 @@ class Engine:
                  length_bins: list[int] | None = None, contig_sets=None, min_base_qual: int = 0,
                  length_hist: int = 0, site_context: str | None = None, end_condition: tuple[int, int, int] | None = None,
                  gapped: bool = False, per_contig: bool = False, mismatches: tuple[int, int, int] | None = None,
-                 replicates: int = 0, interior: int | None = None, composition: int | None = None):
+                 replicates: int = 0, interior: int | None = None, composition: int | None = None,
+                 read_score: dict | None = None):
         L = hip_lib()
         cfg = _Config()
         cfg.abi_version = 1
@@ -314,6 +324,9 @@ class Engine:
         self._composition = 0
         if composition is not None:
             self.set_composition(composition)
+        self._read_score = None
+        if read_score is not None:
+            self.set_read_score(**read_score)
 
     def set_min_base_quality(self, q: int):
         """pss-bam -Q: a read base whose Phred quality is below q (0..93, 0 = off) adds nothing to the substitution
@@ -545,6 +558,47 @@ class Engine:
         reads = np.zeros(1, dtype=np.uint64)
         _chk(self._L.pssbam_engine_finish_interior(self._h, table.ctypes.data, reads.ctypes.data))
         return table, int(reads[0])
+
+    def set_read_score(self, weights=None, min_score: int | None = None, hist_half: int = 0, hist_shift: int = 0):
+        """pss-bam -y / -Y.  weights: integers [4][n_dist][n_qual] (n_dist, n_qual 1..64, |w| <= 2047), None = off.  The score S
+        of a <L>M read sums weights[kind][d][q] over the positions where read and reference are both A/C/G/T (and QUAL passes
+        min_base_qual): reference C under read C / T is kind 0 / 1 at d = i, reference G under read G / A kind 2 / 3 at
+        d = L-1-i, a reverse-strand read swaps 0 1 with 2 3; d and q = QUAL[i] saturate at the last row / column.  min_score
+        (None = no filter): a read that would be tallied and has S < min_score is filtered instead.  hist_half = H (1..128,
+        0 = off): counts bin clamp(S >> hist_shift, -H, H-1) + H of every read added to the forward / reverse table, see
+        finish_read_score.  Needs region_len <= 30; goes with read_group, min_base_qual and regions; not with kmer, any
+        plane split, the length histogram, site context, the end condition, gapped reads, the mismatch count, the interior
+        or the composition table.  Before the first tally (after feed_open: before set_references); a histogram also before
+        bind_counters: the counter block grows by 4 * hist_half words.  Survives reset."""
+        if weights is None:
+            _chk(self._L.pssbam_engine_set_read_score(self._h, None, 0, 0, 0, 0, 0, 0))
+            self._read_score = None
+            return
+        w = np.asarray(weights)
+        if w.ndim != 3 or w.shape[0] != 4:
+            raise PssbamError("read-score weights must have the shape [4][n_dist][n_qual]")
+        if w.size and (np.abs(w.astype(np.int64)) > 32767).any():
+            raise PssbamError("read-score weights must fit 16 bits")
+        w16 = np.ascontiguousarray(w, dtype=np.int16)
+        _chk(self._L.pssbam_engine_set_read_score(self._h, w16.ctypes.data, w.shape[1], w.shape[2], int(min_score is not None),
+                                                  int(min_score or 0), int(hist_half), int(hist_shift)))
+        self._read_score = dict(weights=w16, min_score=None if min_score is None else int(min_score), hist_half=int(hist_half),
+                                hist_shift=int(hist_shift))
+
+    @property
+    def read_score(self) -> dict | None:
+        """the read-score setting in force (weights, min_score, hist_half, hist_shift), None = off"""
+        return self._read_score
+
+    def finish_read_score(self) -> tuple[np.ndarray, np.ndarray]:
+        """(fwd, rev): u64 arrays of 2 * hist_half rows -- row b = reads of score bin b - hist_half added to that table, the
+        first and last row everything below / above (drains like finish)"""
+        if not self._read_score or not self._read_score["hist_half"]:
+            raise PssbamError("set_read_score has not been called with a histogram")
+        fwd = np.zeros(2 * self._read_score["hist_half"], dtype=np.uint64)
+        rev = np.zeros_like(fwd)
+        _chk(self._L.pssbam_engine_finish_read_score(self._h, fwd.ctypes.data, rev.ctypes.data))
+        return fwd, rev
 
     def set_composition(self, width: int = 0):
         """pss-bam -P.  width = w (1..MAX_COMPOSITION, 0 = off): every record that is added to the forward table counts the
@@ -854,6 +908,9 @@ class Engine:
         if self._composition:   # the composition table (never together with any of the above): c5 | c3 behind the stats
             lay["comp5"], lay["comp3"] = base, base + 10 * self._composition
             lay["n_u64"] = base + 20 * self._composition
+        if self._read_score and self._read_score["hist_half"]:   # the score histogram (never together with any of the above): sf | sr
+            lay["score_fwd"], lay["score_rev"] = base, base + 2 * self._read_score["hist_half"]
+            lay["n_u64"] = base + 4 * self._read_score["hist_half"]
         return lay
 
     def genome_kmer_count(self, klen: int) -> np.ndarray:

@@ -238,6 +238,13 @@ struct pssbam_engine {
     // -P (pssbam_engine_set_composition): c5 | c3, 2 * width * 5 words each at off_composition = the end of the block as it is
     // without them; composition = 0: off, no words
     uint32_t composition = 0, off_composition = 0;
+    // -y / -Y (pssbam_engine_set_read_score): the weights [4][score_nd][score_nq] in device memory (d_score_w = NULL: off); the
+    // filter S >= score_min when score_filter; sf | sr, 2 * score_half words each at off_score = the end of the block as it is
+    // without them (score_half = 0: no words)
+    int16_t *d_score_w = nullptr;
+    uint32_t score_nd = 0, score_nq = 0, score_half = 0, score_shift = 0, off_score = 0;
+    int32_t score_min = 0;
+    bool score_filter = false;
     bool gapped = false;   // -I (pssbam_engine_set_gapped_reads): clipped and gapped reads are tallied by their anchored ends; no counter words
     int env_hist_lds_bins = -1;   // PSSBAM_HIST_LDS_BINS: at most this many bins of each array in LDS (tests: the global-atomic path with short reads)
     // -T (pssbam_engine_set_regions): contig name -> its merged intervals, kept on the host; the per-refID device table is
@@ -507,6 +514,7 @@ extern "C" void pssbam_engine_destroy(pssbam_engine *e) {
     if (e->d_rg) (void)hipFree(e->d_rg);
     for (void *q : {(void *)e->d_region_info, (void *)e->d_region_grid, (void *)e->d_region_iv})
         if (q) (void)hipFree(q);
+    if (e->d_score_w) (void)hipFree(e->d_score_w);
     if (e->d_grp_ids) (void)hipFree(e->d_grp_ids);
     if (e->d_grp_offs) (void)hipFree(e->d_grp_offs);
     if (e->d_grp_hash) (void)hipFree(e->d_grp_hash);
@@ -938,12 +946,21 @@ static int with_planes(PlaneSel sel, F f) {
 
 static int no_kernel() { return fail(PSSBAM_EINVAL, "no tally kernel is built for this combination of options"); }
 
+// -y / -Y: the one row pass of tally_tiled_score (pss-bam -r <= 30: every row in pass 0; the substitution tally alone, one plane), with
+// or without -Q and -T: four instantiations, and the plain reduce_partials behind them
+static int launch_tiled_score(pssbam_engine *e, TallyParams &P, bool maskq, bool regions, uint32_t lds, uint32_t n_tiles) {
+    return with_flags([&](auto MASKQ, auto REGIONS) -> int {
+        return launch_with_reduce(e, tally_tiled_score<MASKQ(), REGIONS()>, reduce_partials<false>, SCRATCH_WORDS, lds, n_tiles, P, std::tuple<>(), 0u);
+    }, maskq, regions);
+}
+
 // One row pass of tally_tiled and its reduce_partials: the instantiation for the launch's tallies, the pass (LATER: rows
 // 32.. of a large -r) and its -Q, -T, -H, -X, -E and -I state.  `exists` is the list of instantiations: the k-mer tally (alone or
 // beside the substitution tables) and -H belong to pass 0, -Q -H -X to the substitution tables, -X excludes the other two;
 // -E is the substitution tally of pass 0 alone, with or without -Q and -T; -I is the substitution tally alone in every pass, with or
 // without -Q and -T (eight instantiations); -n / -N is the substitution tally of pass 0 alone, with or without -Q and -T (four), and
-// so is -W (four more; never together with -n / -N), and so is -P (four more; never together with either).
+// so is -W (four more; never together with -n / -N), and so is -P (four more; never together with either).  -y / -Y has a kernel of
+// its own, tally_tiled_score (launch_tiled_score).
 // (SITE, END: the larger scratch slot of the -X / -E instantiations and the reduce that walks it)
 static int launch_tiled(pssbam_engine *e, TallyParams &P, bool do_pss, bool do_kmer, bool kmer_lds, bool later, bool maskq, bool regions,
                         bool hist, bool site, bool endc, bool gapped, bool mism, bool interior, bool comp, uint32_t lds, uint32_t n_tiles) {
@@ -965,6 +982,7 @@ static int launch_tiled(pssbam_engine *e, TallyParams &P, bool do_pss, bool do_k
             return no_kernel();
     }, do_pss, do_kmer, kmer_lds, later, maskq, regions, hist, site, endc, gapped, mism, interior, comp);
 }
+
 
 // How many 16-byte pieces of a record the tiled kernel must stage so that everything the path
 // reads (through QUAL[0]; the whole record when the -R filter walks the aux fields) is in LDS
@@ -989,8 +1007,8 @@ static uint64_t sample_prefix_need(const uint8_t *bytes, uint64_t nbytes, bool w
     return need_max;
 }
 
-// -R and -G walk the aux fields, which sit behind QUAL, and -Q reads QUAL itself: the tiled kernels stage whole records
-static bool whole_records(const pssbam_engine *e) { return e->has_rg || e->planes == PLANES_RG || e->min_bq > 0; }
+// -R and -G walk the aux fields, which sit behind QUAL, and -Q and -y / -Y read QUAL itself: the tiled kernels stage whole records
+static bool whole_records(const pssbam_engine *e) { return e->has_rg || e->planes == PLANES_RG || e->min_bq > 0 || e->d_score_w != nullptr; }
 
 // The plane kernels' argument for the engine's -G / -S state (plane0, n_slots and scratch_words are per launch)
 static PlaneParams plane_params(const pssbam_engine *e) {
@@ -1099,6 +1117,17 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
     if (comp) {
         P.composition = e->composition;
         P.off_composition = e->off_composition;
+    }
+    const bool score = do_pss && e->d_score_w != nullptr;   // -y / -Y: the SCORE instantiations; without it the engine launches what it always did
+    if (score) {
+        P.score_w = e->d_score_w;
+        P.score_nd = e->score_nd;
+        P.score_nq = e->score_nq;
+        P.score_filter = e->score_filter ? 1u : 0u;
+        P.score_min = e->score_min;
+        P.score_half = e->score_half;
+        P.score_shift = e->score_shift;
+        P.off_score = e->off_score;
     }
     const bool gapped = do_pss && e->gapped;   // -I: the GAPPED instantiations; without it the engine launches what it always did
     P.gapped = gapped ? 1u : 0u;
@@ -1256,6 +1285,10 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                     });
                 }
             }
+        } else if (score) {
+            // -y / -Y (one pass: -r <= 30; never tally_compact, which has no QUAL path): tally_tiled_score, with [sf | sr] behind the
+            // staging buffer, at most 2 KiB
+            rc = launch_tiled_score(e, P, maskq, regions, lds + 4u * e->score_half * 4u, n_tiles);
         } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions && !hist && !site && !endc && !gapped && !mism && !interior && !comp) {
             // -r N <= 16 (2 context rows + 16 positions): the short-window variant, one pass (it stages prefixes only
             // and has no QUAL path: -R and -Q go to tally_tiled; so do -T, -H, -X, -E, -I, -n / -N, -W and -P, whose arms only tally_tiled carries)
@@ -1558,6 +1591,7 @@ extern "C" int pssbam_engine_finish_kmer_groups(pssbam_engine *e, int32_t group,
 static bool mismatches_on(const pssbam_engine *e) { return e->mism_hist > 0 || e->mism_max >= 0; }   // -n / -N
 static bool interior_on(const pssbam_engine *e) { return e->interior_margin >= 0; }   // -W
 static bool composition_on(const pssbam_engine *e) { return e->composition > 0; }   // -P
+static bool read_score_on(const pssbam_engine *e) { return e->d_score_w != nullptr; }   // -y / -Y
 
 static int check_may_resize(const pssbam_engine *e, const char *what) {
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set %s after create or reset, before the first tally", what);
@@ -1588,6 +1622,7 @@ static int set_planes(pssbam_engine *e, PlaneSel sel, uint32_t n_planes, const c
     if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "%s and the mismatch count exclude each other", what);
     if (interior_on(e)) return fail(PSSBAM_EINVAL, "%s and the interior table exclude each other", what);
     if (composition_on(e)) return fail(PSSBAM_EINVAL, "%s and the composition table exclude each other", what);
+    if (read_score_on(e)) return fail(PSSBAM_EINVAL, "%s and the read score exclude each other", what);
     const bool kmer = e->cfg.tally_mask == PSSBAM_TALLY_KMER;
     if (e->cfg.tally_mask != PSSBAM_TALLY_PSS && !kmer)
         return fail(PSSBAM_EINVAL, "%s split the substitution tables or the k-mer tables, not both (PSSBAM_TALLY_PSS | PSSBAM_TALLY_KMER)", what);
@@ -1686,6 +1721,7 @@ extern "C" int pssbam_engine_set_gapped_reads(pssbam_engine *e, int32_t on) {
         if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "gapped reads and the mismatch count exclude each other");
         if (interior_on(e)) return fail(PSSBAM_EINVAL, "gapped reads and the interior table exclude each other");
         if (composition_on(e)) return fail(PSSBAM_EINVAL, "gapped reads and the composition table exclude each other");
+        if (read_score_on(e)) return fail(PSSBAM_EINVAL, "gapped reads and the read score exclude each other");
     }
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set gapped reads after create or reset, before the first tally");
     e->gapped = on != 0;   // (the counter block keeps its size: a caller-bound block stays bound)
@@ -1705,6 +1741,7 @@ extern "C" int pssbam_engine_set_length_histogram(pssbam_engine *e, int32_t max_
     if (mismatches_on(e) && max_len) return fail(PSSBAM_EINVAL, "the length histogram and the mismatch count exclude each other");
     if (interior_on(e) && max_len) return fail(PSSBAM_EINVAL, "the length histogram and the interior table exclude each other");
     if (composition_on(e) && max_len) return fail(PSSBAM_EINVAL, "the length histogram and the composition table exclude each other");
+    if (read_score_on(e) && max_len) return fail(PSSBAM_EINVAL, "the length histogram and the read score exclude each other");
     if (const int rc = check_may_resize(e, "the length histogram")) return rc;
     if ((uint32_t)max_len == e->hist_max) return PSSBAM_OK;
     HIP_TRY(hipSetDevice(e->device));
@@ -1747,6 +1784,7 @@ extern "C" int pssbam_engine_set_mismatches(pssbam_engine *e, int32_t hist_max, 
         if (e->gapped) return fail(PSSBAM_EINVAL, "the mismatch count and gapped reads exclude each other");
         if (interior_on(e)) return fail(PSSBAM_EINVAL, "the mismatch count and the interior table exclude each other");
         if (composition_on(e)) return fail(PSSBAM_EINVAL, "the mismatch count and the composition table exclude each other");
+        if (read_score_on(e)) return fail(PSSBAM_EINVAL, "the mismatch count and the read score exclude each other");
     }
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the mismatch count after create or reset, before the first tally");
     if ((uint32_t)hist_max != e->mism_hist) {
@@ -1789,6 +1827,7 @@ extern "C" int pssbam_engine_set_interior(pssbam_engine *e, int32_t margin) {
         if (e->gapped) return fail(PSSBAM_EINVAL, "the interior table and gapped reads exclude each other");
         if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "the interior table and the mismatch count exclude each other");
         if (composition_on(e)) return fail(PSSBAM_EINVAL, "the interior table and the composition table exclude each other");
+        if (read_score_on(e)) return fail(PSSBAM_EINVAL, "the interior table and the read score exclude each other");
     }
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the interior table after create or reset, before the first tally");
     if ((margin >= 0) != interior_on(e)) {
@@ -1828,6 +1867,7 @@ extern "C" int pssbam_engine_set_composition(pssbam_engine *e, int32_t width) {
         if (e->gapped) return fail(PSSBAM_EINVAL, "the composition table and gapped reads exclude each other");
         if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "the composition table and the mismatch count exclude each other");
         if (interior_on(e)) return fail(PSSBAM_EINVAL, "the composition table and the interior table exclude each other");
+        if (read_score_on(e)) return fail(PSSBAM_EINVAL, "the composition table and the read score exclude each other");
     }
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the composition table after create or reset, before the first tally");
     if ((uint32_t)width != e->composition) {
@@ -1852,6 +1892,76 @@ extern "C" int pssbam_engine_finish_composition(pssbam_engine *e, uint64_t *c5, 
     return PSSBAM_OK;
 }
 
+extern "C" int pssbam_engine_set_read_score(pssbam_engine *e, const int16_t *weights, int32_t n_dist, int32_t n_qual, int32_t use_filter,
+                                            int32_t min_score, int32_t hist_half, int32_t hist_shift) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    const bool on = weights != nullptr;
+    if (!on) n_dist = n_qual = use_filter = min_score = hist_half = hist_shift = 0;
+    if (on) {
+        if (n_dist < 1 || n_dist > PSSBAM_MAX_SCORE_DIST) return fail(PSSBAM_EINVAL, "read score: %d distances outside 1..%d", n_dist, PSSBAM_MAX_SCORE_DIST);
+        if (n_qual < 1 || n_qual > PSSBAM_MAX_SCORE_QUAL) return fail(PSSBAM_EINVAL, "read score: %d quality columns outside 1..%d", n_qual, PSSBAM_MAX_SCORE_QUAL);
+        if (hist_half < 0 || hist_half > PSSBAM_MAX_SCORE_HALF) return fail(PSSBAM_EINVAL, "read score: histogram half width %d outside 0..%d", hist_half, PSSBAM_MAX_SCORE_HALF);
+        if (hist_shift < 0 || hist_shift > 16) return fail(PSSBAM_EINVAL, "read score: histogram shift %d outside 0..16", hist_shift);
+        for (int32_t i = 0; i < 4 * n_dist * n_qual; i++)
+            if (weights[i] < -PSSBAM_MAX_SCORE_WEIGHT || weights[i] > PSSBAM_MAX_SCORE_WEIGHT)
+                return fail(PSSBAM_EINVAL, "read score: weight %d (entry %d) beyond +-%d", (int)weights[i], i, PSSBAM_MAX_SCORE_WEIGHT);
+        if (e->cfg.tally_mask != PSSBAM_TALLY_PSS)
+            return fail(PSSBAM_EINVAL, "the read score filters the reads of the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
+        if (e->cfg.pss.region_len > 30)
+            return fail(PSSBAM_EINVAL, "the read score needs a region length of at most 30 (the decision is taken in the one pass that holds all rows), not %d", e->cfg.pss.region_len);
+        if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "the read score and replicates exclude each other");
+        if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the read score and read groups / length bins / contig sets / per-contig tables exclude each other");
+        if (e->hist_max) return fail(PSSBAM_EINVAL, "the read score and the length histogram exclude each other");
+        if (e->site_mode) return fail(PSSBAM_EINVAL, "the read score and site context exclude each other");
+        if (e->end_depth) return fail(PSSBAM_EINVAL, "the read score and the end condition exclude each other");
+        if (e->gapped) return fail(PSSBAM_EINVAL, "the read score and gapped reads exclude each other");
+        if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "the read score and the mismatch count exclude each other");
+        if (interior_on(e)) return fail(PSSBAM_EINVAL, "the read score and the interior table exclude each other");
+        if (composition_on(e)) return fail(PSSBAM_EINVAL, "the read score and the composition table exclude each other");
+    }
+    if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the read score after create or reset, before the first tally");
+    if ((uint32_t)hist_half != e->score_half)
+        if (const int rc = check_may_resize(e, "the read-score histogram")) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    int16_t *d_w = nullptr;
+    if (on) {   // the weights go to the device here; an earlier table may still be named by nothing (nothing has been tallied)
+        const size_t bytes = (size_t)4 * (size_t)n_dist * (size_t)n_qual * sizeof(int16_t);
+        HIP_TRY(hipMalloc(&d_w, bytes));
+        if (hipMemcpy(d_w, weights, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(d_w);
+            return fail(PSSBAM_EHIP, "read score: the weights could not be copied to the device");
+        }
+    }
+    if ((uint32_t)hist_half != e->score_half) {
+        // the block grows (or shrinks back) behind everything it holds without the histogram
+        if (const int rc = grow_counters(e, (uint64_t)e->off_groups + 4ull * (uint64_t)hist_half)) {
+            if (d_w) (void)hipFree(d_w);
+            return rc;
+        }
+    }
+    if (e->d_score_w) (void)hipFree(e->d_score_w);
+    e->d_score_w = d_w;
+    e->score_nd = (uint32_t)n_dist;
+    e->score_nq = (uint32_t)n_qual;
+    e->score_filter = use_filter != 0;
+    e->score_min = min_score;
+    e->score_half = (uint32_t)hist_half;
+    e->score_shift = (uint32_t)hist_shift;
+    e->off_score = hist_half ? e->off_groups : 0u;
+    return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_finish_read_score(pssbam_engine *e, uint64_t *fwd, uint64_t *rev) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (!e->score_half) return fail(PSSBAM_EINVAL, "pssbam_engine_set_read_score has not been called with a histogram");
+    const int rc = pssbam_engine_sync(e);
+    if (rc) return rc;
+    const size_t n = 2u * (size_t)e->score_half;
+    if (fwd) HIP_TRY(hipMemcpy(fwd, e->d_counters + e->off_score, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (rev) HIP_TRY(hipMemcpy(rev, e->d_counters + e->off_score + n, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return PSSBAM_OK;
+}
+
 extern "C" int pssbam_engine_set_site_context(pssbam_engine *e, int32_t mode) {
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
     if (mode != PSSBAM_SITE_NONE && mode != PSSBAM_SITE_CPG) return fail(PSSBAM_EINVAL, "unknown site context %d", mode);
@@ -1865,6 +1975,7 @@ extern "C" int pssbam_engine_set_site_context(pssbam_engine *e, int32_t mode) {
     if (mismatches_on(e) && mode != PSSBAM_SITE_NONE) return fail(PSSBAM_EINVAL, "site context and the mismatch count exclude each other");
     if (interior_on(e) && mode != PSSBAM_SITE_NONE) return fail(PSSBAM_EINVAL, "site context and the interior table exclude each other");
     if (composition_on(e) && mode != PSSBAM_SITE_NONE) return fail(PSSBAM_EINVAL, "site context and the composition table exclude each other");
+    if (read_score_on(e) && mode != PSSBAM_SITE_NONE) return fail(PSSBAM_EINVAL, "site context and the read score exclude each other");
     if (const int rc = check_may_resize(e, "the site context")) return rc;
     if ((uint32_t)mode == e->site_mode) return PSSBAM_OK;
     HIP_TRY(hipSetDevice(e->device));
@@ -1910,6 +2021,7 @@ extern "C" int pssbam_engine_set_end_condition(pssbam_engine *e, int32_t depth, 
     if (mismatches_on(e) && depth) return fail(PSSBAM_EINVAL, "the end condition and the mismatch count exclude each other");
     if (interior_on(e) && depth) return fail(PSSBAM_EINVAL, "the end condition and the interior table exclude each other");
     if (composition_on(e) && depth) return fail(PSSBAM_EINVAL, "the end condition and the composition table exclude each other");
+    if (read_score_on(e) && depth) return fail(PSSBAM_EINVAL, "the end condition and the read score exclude each other");
     if (const int rc = check_may_resize(e, "the end condition")) return rc;
     if ((uint32_t)depth != e->end_depth) {
         HIP_TRY(hipSetDevice(e->device));
@@ -2079,6 +2191,7 @@ extern "C" int pssbam_engine_set_per_contig(pssbam_engine *e, int32_t on) {
         if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "per-contig tables and the mismatch count exclude each other");
         if (interior_on(e)) return fail(PSSBAM_EINVAL, "per-contig tables and the interior table exclude each other");
         if (composition_on(e)) return fail(PSSBAM_EINVAL, "per-contig tables and the composition table exclude each other");
+        if (read_score_on(e)) return fail(PSSBAM_EINVAL, "per-contig tables and the read score exclude each other");
     }
     if (const int rc = check_may_resize(e, "per-contig tables")) return rc;
     if ((on != 0) == e->per_contig) return PSSBAM_OK;

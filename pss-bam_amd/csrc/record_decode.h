@@ -114,6 +114,15 @@ struct TallyParams {
     // offsets on either side of an end (0 = off); [c5 | c3], 2 * w * 5 u64 counters each, row-major [j + w][class], in the counter
     // block at off_composition.  Read by the COMP instantiations of tally_tiled and by tally_simple.
     uint32_t composition, off_composition;
+    // -y / -Y: the read score, a sum of caller-supplied weights over the C and G sites of a whole read (tally_kernels.h: read_score).
+    // score_w = the weights [4][score_nd][score_nq] in device memory (NULL = off); score_filter: a read with S < score_min is
+    // filtered; score_half = H: [sf | sr], 2H u64 counters each, in the counter block at off_score, bin
+    // clamp(S >> score_shift, -H, H - 1) + H of the reads added to the forward / reverse table (0 = no histogram).  Read by the SCORE
+    // instantiations of tally_tiled and by tally_simple.
+    const int16_t *score_w;
+    uint32_t score_nd, score_nq, score_filter;
+    int32_t score_min;
+    uint32_t score_half, score_shift, off_score;
 };
 
 // stats slots, must match include/pssbam_hip.h.  The kernels count EVENTS only: every launch

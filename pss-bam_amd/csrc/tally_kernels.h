@@ -64,6 +64,11 @@
 //                 the staged prefix (record_decode.h: cigar_anchor), a lane's read stream starts at its end's anchor and
 //                 CODES-B blanks what lies outside the end's matched run; the reference side is the plain kernel's.
 //
+//  SCORE arm of the tiled body (-y / -Y, kernel tally_tiled_score, one pass): a sum of caller-supplied weights over the C and G sites of the
+//                 whole read, by distance from the read's ends and base quality (read_score is the definition, one lane per read;
+//                 read_score_staged the pair's two halves in CODES-A); a read below the minimum stops being a candidate, and the
+//                 histogram of the score lives in LDS behind the staging buffer.
+//
 //  MISM arm of tally_tiled (-n / -N / -V, pass 0 of a one-pass launch): the mismatch count of the whole read against the reference.
 //                 The two lanes of a read's pair each compare one half of it in CODES-A, eight bases per step and nibble-parallel
 //                 (count_mismatches_staged: SEQ from the staged prefix, the reference from the 4-bit genome image), and add
@@ -388,15 +393,16 @@ __device__ __forceinline__ void mism_add(const TallyParams &P, uint32_t *mism_ld
     }
 }
 // The whole wave's reads of one tile, merged by value like hist_wave_add (most reads of a wave have 0, 1 or 2 mismatches):
-// two ballot rounds take the modes, what is left adds itself.  Every bin lives in LDS.
-__device__ __forceinline__ void mism_wave_add(const TallyParams &P, uint32_t *mism_lds, bool on, uint32_t b, bool fwd, bool rev) {
+// two ballot rounds take the modes, what is left adds itself.  Every bin lives in LDS.  add(b, fwd, rev, n): n reads of bin b.
+template <class Add>
+__device__ __forceinline__ void bin_wave_add(bool on, uint32_t b, bool fwd, bool rev, Add add) {
     const uint32_t key = (b << 2) | (fwd ? 2u : 0u) | (rev ? 1u : 0u);
     const uint32_t lane = threadIdx.x & 63u;
     bool pending = on && (fwd || rev);
     for (uint32_t round = 0; __any(pending); round++) {
         if (pending) {
             if (round >= 2u) {
-                mism_add(P, mism_lds, b, fwd, rev, 1u);
+                add(b, fwd, rev, 1u);
                 pending = false;
             } else {
                 const uint32_t v = __builtin_amdgcn_readfirstlane(key);   // (of the lanes still in this branch)
@@ -404,11 +410,14 @@ __device__ __forceinline__ void mism_wave_add(const TallyParams &P, uint32_t *mi
                 const unsigned long long m = __ballot(same);
                 if (same) {
                     pending = false;
-                    if (lane == (uint32_t)__ffsll((long long)m) - 1u) mism_add(P, mism_lds, b, fwd, rev, (uint32_t)__popcll(m));
+                    if (lane == (uint32_t)__ffsll((long long)m) - 1u) add(b, fwd, rev, (uint32_t)__popcll(m));
                 }
             }
         }
     }
+}
+__device__ __forceinline__ void mism_wave_add(const TallyParams &P, uint32_t *mism_lds, bool on, uint32_t b, bool fwd, bool rev) {
+    bin_wave_add(on, b, fwd, rev, [&](uint32_t bin, bool f, bool r, uint32_t n) { mism_add(P, mism_lds, bin, f, r, n); });
 }
 // Eight positions at once.  g: eight nibbles of the genome image (0..3 = A C G T, 4..7 = other), r: the BAM nibbles of the
 // same eight read bases in the same order.  Returns bit 4q set when position q counts.  The reference nibble becomes the BAM
@@ -432,6 +441,51 @@ __device__ __forceinline__ uint32_t mismatch_flags8(uint32_t g, uint32_t r, bool
     uint32_t f = ok & nonzero_nibbles8(x);
     if (tv_only) f &= nonzero_nibbles8(x ^ 0x55555555u) & nonzero_nibbles8(x ^ 0xAAAAAAAAu);
     return f;
+}
+
+// ---------------------------------------------------------------------------------------
+// -y / -Y: a weighted score over the C and G sites of a whole read
+// ---------------------------------------------------------------------------------------
+// The score S of a <L>M record (include/pssbam_hip.h): over the read positions i < min(L, l_seq) at which SEQ[i] and the reference base
+// are both one of A C G T and, under -Q, QUAL[i] is not below the minimum, the sum of weights[kind][d][q] -- reference C against read
+// C / T is kind 0 / 1 at d = i, reference G against read G / A kind 2 / 3 at d = L - 1 - i, a FLAG 0x10 record swaps 0 1 with 2 3, d and
+// q = QUAL[i] saturate at the table's last row and column, every other pair adds nothing.  Stored codes A0 C1 G2 T3.  This is the
+// definition in code: tally_simple and the one-lane path of tally_tiled use it as it stands; a record there may be longer than 2^20
+// bases, hence the 64-bit sum.
+template <class Src>
+__device__ int32_t read_score(const TallyParams &P, const Src &src, const RecHdr &h, const uint8_t *G, int64_t s, uint32_t L, bool rev) {
+    const uint32_t n = min(L, h.l_seq);
+    long long S = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t rd = nib_code(read_nibble(src, h, i));
+        const uint32_t rf = ref_code(G[s + (int64_t)i]);
+        if (rd >= 4u || rf >= 4u) continue;
+        const uint32_t qv = src.u8(h.qual_off + i);
+        if (P.min_bq && qv < P.min_bq) continue;
+        uint32_t kind, d;
+        if (rf == 1u && (rd == 1u || rd == 3u)) { kind = rd == 3u ? 1u : 0u; d = i; }
+        else if (rf == 2u && (rd == 2u || rd == 0u)) { kind = rd == 0u ? 3u : 2u; d = L - 1u - i; }
+        else continue;
+        if (rev) kind ^= 2u;
+        S += P.score_w[(kind * P.score_nd + min(d, P.score_nd - 1u)) * P.score_nq + min(qv, P.score_nq - 1u)];
+    }
+    return (int32_t)max(-2147483647ll - 1ll, min(S, 2147483647ll));
+}
+__device__ __forceinline__ bool score_below(const TallyParams &P, int32_t S) { return P.score_filter && S < P.score_min; }
+// bin clamp(S >> shift, -H, H - 1) + H: the shift is arithmetic, so it floors negative scores as well
+__device__ __forceinline__ uint32_t score_bin(const TallyParams &P, int32_t S) {
+    const int32_t H = (int32_t)P.score_half;
+    return (uint32_t)(max(-H, min(S >> P.score_shift, H - 1)) + H);
+}
+// n reads of bin b into sf (fwd) and / or sr (rev): the tiled kernel's LDS bins [sf | sr], or the counter block
+__device__ __forceinline__ void score_add(const TallyParams &P, uint32_t *score_lds, uint32_t b, bool fwd, bool rev, uint32_t n) {
+    if (score_lds) {
+        if (fwd) atomicAdd(&score_lds[b], n);
+        if (rev) atomicAdd(&score_lds[2u * P.score_half + b], n);
+    } else {
+        if (fwd) atomicAdd(&P.counters[P.off_score + b], (unsigned long long)n);
+        if (rev) atomicAdd(&P.counters[P.off_score + 2u * P.score_half + b], (unsigned long long)n);
+    }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -622,6 +676,12 @@ __global__ void __launch_bounds__(256) tally_simple(const TallyParams P) {
             mm = count_mismatches(src, h, P.genome + pl.gbase, pl.s, pl.L, P.mism_tv != 0u);
             if (mism_beyond(P, mm)) pl.pss_fwd = pl.pss_rev = false;
         }
+        // -y / -Y: the read's score; below the minimum it is filtered in the same way
+        int32_t sc = 0;
+        if (P.score_w && (pl.pss_fwd || pl.pss_rev)) {
+            sc = read_score(P, src, h, P.genome + pl.gbase, pl.s, pl.L, pl.rev);
+            if (score_below(P, sc)) pl.pss_fwd = pl.pss_rev = false;
+        }
         if (pl.pss_fwd || pl.pss_rev) {
             if (P.gapped) {   // -I (never together with -X, -E or -H)
                 if (LDS_TABLE) tally_pss_record<true, false, true>(P, LdsTableRowMajor{dyn_lds, rows}, NoSite{}, src, h, pl);
@@ -638,6 +698,8 @@ __global__ void __launch_bounds__(256) tally_simple(const TallyParams P) {
             if (P.hist_max) hist_add(P, nullptr, hist_bin(P, pl.L), pl.pss_fwd, pl.pss_rev, 1u);
             // -N: likewise
             if (P.mism_hist) mism_add(P, nullptr, mism_bin(P, mm), pl.pss_fwd, pl.pss_rev, 1u);
+            // -Y: likewise
+            if (P.score_half) score_add(P, nullptr, score_bin(P, sc), pl.pss_fwd, pl.pss_rev, 1u);
             // -W: the read's interior, once, whichever table took the read
             if (P.interior) count_interior(P, src, h, P.genome + pl.gbase, pl.s, pl.L, pl.rev);
             // -P: the reference around the 5' end of a read in the forward table, around the 3' end of one in the reverse table
@@ -723,6 +785,38 @@ __device__ __forceinline__ uint32_t count_mismatches_staged(const uint32_t *geno
     return m;
 }
 
+// -y / -Y: the score's share of read bases lo .. hi - 1 (read_score is the definition).  Eight positions a step: the nibbles where the
+// reference is C and the read C or T, or the reference G and the read G or A, are found nibble-parallel (a BAM read nibble is
+// one-hot: A 1, C 2, G 4, T 8); only those -- about half of a read -- fetch their QUAL byte from the staged record (qual_at: LDS byte
+// of QUAL[0]) and their weight from the table in global memory.  A staged record has fewer than 2048 bases: 32 bits hold the sum.
+template <bool MASKQ>
+__device__ __forceinline__ int32_t read_score_staged(const TallyParams &P, uint64_t g0, const uint8_t *stage, uint32_t seq_at, uint32_t qual_at,
+                                                     uint32_t lo, uint32_t hi, uint32_t L, bool rev) {
+    int32_t S = 0;
+    const uint32_t nd1 = P.score_nd - 1u, nq1 = P.score_nq - 1u;
+    const int16_t *__restrict__ w = P.score_w;
+    walk_read_staged(P.genome4, g0, stage, seq_at, lo, hi, [&](uint32_t W, uint32_t R, uint32_t keep, uint32_t p) {
+        const uint32_t K = 0x11111111u;
+        const uint32_t g_lo = W & K, g_hi = (W >> 1) & K, g_other = ((W >> 2) | (W >> 3)) & K;
+        const uint32_t is_c = g_lo & ~g_hi & ~g_other, is_g = g_hi & ~g_lo & ~g_other;
+        const uint32_t r_a = R & K, r_c = (R >> 1) & K, r_g = (R >> 2) & K, r_t = (R >> 3) & K;
+        const uint32_t mis = (is_c & r_t & ~(r_a | r_c | r_g)) | (is_g & r_a & ~(r_c | r_g | r_t));   // C->T, G->A
+        uint32_t m = (mis | (is_c & r_c & ~(r_a | r_g | r_t)) | (is_g & r_g & ~(r_a | r_c | r_t))) & keep;
+        while (m) {
+            const uint32_t bit = (uint32_t)__ffs((int)m) - 1u;
+            m &= m - 1u;
+            const uint32_t i = p + (bit >> 2);
+            const uint32_t qv = stage[qual_at + i];
+            if (MASKQ && qv < P.min_bq) continue;
+            const bool at_c = (is_c >> bit) & 1u;
+            const uint32_t kind = ((at_c != rev) ? 0u : 2u) + ((mis >> bit) & 1u);
+            const uint32_t d = at_c ? i : L - 1u - i;
+            S += w[(kind * P.score_nd + min(d, nd1)) * P.score_nq + min(qv, nq1)];
+        }
+    });
+    return S;
+}
+
 constexpr uint32_t TILED_MAX_T = 128;
 static_assert(TILED_MAX_T * 2 == TILED_THREADS, "CODES maps one (read, end) pair to each thread");
 
@@ -771,7 +865,7 @@ __device__ __forceinline__ void stage_tile_dma(const uint8_t *recs, uint64_t rec
 // the kernel): a reference to the kernel's by-value copy would force that whole struct into
 // scratch memory.
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool MASKQ = false, bool REGIONS = false, bool HIST = false, bool SITE = false,
-          bool END = false, bool GAPPED = false, bool MISM = false, bool INTERIOR = false, bool COMP = false>
+          bool END = false, bool GAPPED = false, bool MISM = false, bool INTERIOR = false, bool COMP = false, bool SCORE = false>
 __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyParams *kernarg, uint32_t o0,
                                                                     uint32_t o1, uint32_t *table, uint32_t *lds_kmer,
                                                                     uint32_t *hist_lds = nullptr, uint32_t *site_lds = nullptr,
@@ -786,6 +880,13 @@ __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyP
             mm = count_mismatches(gsrc, gh, P.genome + gpl.gbase, gpl.s, gpl.L, P.mism_tv != 0u);
             if (mism_beyond(P, mm)) gpl.pss_fwd = gpl.pss_rev = false;
             else if (P.mism_hist) mism_add(P, hist_lds, mism_bin(P, mm), gpl.pss_fwd, gpl.pss_rev, 1u);
+        }
+    }
+    if constexpr (SCORE) {   // (hist_lds: the SCORE instantiation's LDS bins)
+        if (gpl.pss_fwd || gpl.pss_rev) {
+            const int32_t sc = read_score(P, gsrc, gh, P.genome + gpl.gbase, gpl.s, gpl.L, gpl.rev);
+            if (score_below(P, sc)) gpl.pss_fwd = gpl.pss_rev = false;
+            else if (P.score_half) score_add(P, hist_lds, score_bin(P, sc), gpl.pss_fwd, gpl.pss_rev, 1u);
         }
     }
     if constexpr (GAPPED) {
@@ -1070,9 +1171,19 @@ __device__ __forceinline__ void count_interior_staged(const uint32_t *genome4, u
 // position, a reverse-strand lane complemented.  The words leave LDS with one 64-bit atomic per non-zero word at kernel end,
 // and every 8192 tiles of a workgroup: a tile adds at most 128 to a word, so a u32 word cannot wrap.  The instantiations
 // without COMP contain none of it.
+//
+// SCORE (-y / -Y, P.score_w non-null; pass 0 of a one-pass launch, one plane, substitution tables only, never with MISM, INTERIOR or COMP):
+// in CODES-A, where MISM compares, every lane of a candidate's pair sums the weights of one half of [0, min(L, l_seq)), cut at a
+// multiple of 8 bases (read_score_staged: SEQ and QUAL from the staged record -- a whole record is staged, as under -Q -- the
+// reference from the 4-bit genome image, the weights from their table in global memory, which every workgroup re-reads and which
+// therefore stays in L2), and the two lanes add their halves with the exchange MISM uses, in front of the barrier that releases
+// `stage`.  With the filter a read below P.score_min stops being a candidate there, before -U/-D decide.  Behind CODES-B the
+// left-end lane of every read that is added to a table counts its bin (bin_wave_add) into `hist_lds`, here the 4 * P.score_half
+// words [sf | sr] behind the staging buffer, which leave LDS once, at kernel end, with one 64-bit atomic per non-zero word.  The
+// instantiations without SCORE contain none of it.
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS, PlaneSel PLANES = PLANES_NONE, bool MASKQ = false,
           bool REGIONS = false, bool HIST = false, bool SITE = false, bool END = false, bool GAPPED = false, bool MISM = false,
-          bool INTERIOR = false, bool COMP = false>
+          bool INTERIOR = false, bool COMP = false, bool SCORE = false>
 __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const TallyParams *kernarg,
                                                  uint8_t *__restrict__ stage, uint8_t *__restrict__ sheet,
                                                  uint32_t *__restrict__ table,
@@ -1095,6 +1206,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
     static_assert(!MISM || (DO_PSS && !DO_KMER && !LATER_PASS && PLANES == PLANES_NONE && !HIST && !SITE && !END && !GAPPED), "the mismatch count belongs to pass 0 of the one-plane substitution tally without the length histogram, site context, the end condition and anchored ends");
     static_assert(!INTERIOR || (DO_PSS && !DO_KMER && !LATER_PASS && PLANES == PLANES_NONE && !HIST && !SITE && !END && !GAPPED && !MISM), "the interior table belongs to pass 0 of the one-plane substitution tally without the length histogram, site context, the end condition, anchored ends and the mismatch count");
     static_assert(!COMP || (DO_PSS && !DO_KMER && !LATER_PASS && PLANES == PLANES_NONE && !HIST && !SITE && !END && !GAPPED && !MISM && !INTERIOR), "the composition table belongs to pass 0 of the one-plane substitution tally without the length histogram, site context, the end condition, anchored ends, the mismatch count and the interior table");
+    static_assert(!SCORE || (DO_PSS && !DO_KMER && !LATER_PASS && PLANES == PLANES_NONE && !HIST && !SITE && !END && !GAPPED && !MISM && !INTERIOR && !COMP), "the read score belongs to pass 0 of the one-plane substitution tally without the length histogram, site context, the end condition, anchored ends, the mismatch count, the interior table and the composition table");
     const uint32_t T = P.reads_per_tile;   // <= TILED_MAX_T
     const uint32_t n_recs = P.n_recs_dev ? *P.n_recs_dev : P.n_recs;   // device-indexed blocks: the count lives in device memory
     const uint32_t pieces = P.prefix_pieces;  // 16-byte pieces staged per record
@@ -1124,6 +1236,8 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         for (uint32_t i = tid; i < 2u * P.hist_lds_bins; i += TILED_THREADS) hist_lds[i] = 0u;
     if constexpr (MISM)
         for (uint32_t i = tid; i < (P.mism_hist ? 2u * (P.mism_hist + 2u) : 0u); i += TILED_THREADS) hist_lds[i] = 0u;
+    if constexpr (SCORE)
+        for (uint32_t i = tid; i < 4u * P.score_half; i += TILED_THREADS) hist_lds[i] = 0u;
     if constexpr (INTERIOR)
         if (tid < INTERIOR_WORDS) hist_lds[tid] = 0u;
     // -W: the 17 LDS words into the counter block; an exchange, so that waves that are still adding lose nothing
@@ -1240,8 +1354,8 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         LdsBytes src{stage, hdr_ok ? j * pieces * 16u + (o0 & 15u) : 0u};
         const RecHdr h = decode_hdr_lds(src, hdr_ok ? o1 - o0 : 0u);
         // everything the path reads ends at QUAL[0] (the -R filter and -G walk the aux fields: whole record;
-        // a length bin needs nothing behind QUAL[0]; -Q reads QUAL to its end)
-        const uint32_t needed = (PLANES == PLANES_RG || P.rg) ? o1 - o0 : MASKQ ? h.aux_off : h.qual_off + 1u;
+        // a length bin needs nothing behind QUAL[0]; -Q and the read score read QUAL to its end)
+        const uint32_t needed = (PLANES == PLANES_RG || P.rg) ? o1 - o0 : (MASKQ || SCORE) ? h.aux_off : h.qual_off + 1u;
         // (-I: a CIGAR of more ops than a lane walks sends the record to the one-lane path)
         bool in_stage = GAPPED ? hdr_ok && needed <= avail && h.n_cigar <= GAPPED_TILED_OPS : hdr_ok && needed <= avail;
         auto pl = plan_head<DO_PSS, DO_KMER, true, GAPPED>(P, src, h, RefsLdsCached{refs_lds, P.ref_info, n_ref_cached, (uint32_t)P.n_ref},
@@ -1356,6 +1470,14 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
             const uint32_t cut = min(n_cmp, ((n_cmp >> 1) + 7u) & ~7u);
             if (cand) mm = count_mismatches_staged(P.genome4, pl.gbase + (uint64_t)pl.s, stage, src.off + h.seq_off, e ? cut : 0u, e ? n_cmp : cut, P.mism_tv != 0u);
         }
+        // -y / -Y: this lane's half of the read's score, cut like the compare (all of SEQ and QUAL is in `stage`)
+        [[maybe_unused]] int32_t sc = 0;
+        if constexpr (SCORE) {
+            const uint32_t n_cmp = min(pl.L, h.l_seq);
+            const uint32_t cut = min(n_cmp, ((n_cmp >> 1) + 7u) & ~7u);
+            if (cand) sc = read_score_staged<MASKQ>(P, pl.gbase + (uint64_t)pl.s, stage, src.off + h.seq_off, src.off + h.qual_off,
+                                                    e ? cut : 0u, e ? n_cmp : cut, pl.L, pl.rev);
+        }
         // -Q: the QUAL bytes of the same read bases, one byte per window position: byte b <-> QUAL[n0 + b] (left,
         // pass 0: bytes 0,1 are the last SEQ bytes and belong to the context positions, which CODES-B overwrites).
         // 32 bytes at any alignment = nine aligned dwords; n0 >= -31 and QUAL starts at least 36 bytes into the
@@ -1432,7 +1554,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         if (in_tile && !in_stage && e == 0u) {
             if constexpr (KPLANES) ev_over = tally_overflow_record_kmer_planes<PLANES, LDS_KMER, REGIONS>(kernarg, gk, o0, o1, lds_kmer);
             else if constexpr (GROUPED) ev_over = tally_overflow_record_planes<PLANES, MASKQ, REGIONS>(kernarg, gk, o0, o1, table);
-            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS, HIST, SITE, END, GAPPED, MISM, INTERIOR, COMP>(kernarg, o0, o1, table, lds_kmer, hist_lds, site_lds, end_lds);
+            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS, HIST, SITE, END, GAPPED, MISM, INTERIOR, COMP, SCORE>(kernarg, o0, o1, table, lds_kmer, hist_lds, site_lds, end_lds);
             if (pass0) atomicAdd(&lds_delta[ST_SLOW_PATH], 1);
         }
         // First use of the gathered registers happens HERE, before the next tile's DMA is issued:
@@ -1468,6 +1590,13 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
             asm volatile("" : "+v"(mm));
             mm += (uint32_t)__shfl_xor((int)mm, 1);
             if (mism_beyond(P, mm)) pl.pss_cand = false;
+        }
+        if constexpr (SCORE) {
+            // likewise: the walk's loads are used up here, the pair's halves make the read's score, and a read below the
+            // minimum is no candidate from here on
+            asm volatile("" : "+v"(sc));
+            sc += __shfl_xor(sc, 1);
+            if (score_below(P, sc)) pl.pss_cand = false;
         }
         if constexpr (INTERIOR) {   // the walk's genome dwords and staged bytes are used up here as well
 #pragma unroll
@@ -1760,6 +1889,12 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
             if constexpr (MISM) {
                 if (P.mism_hist) mism_wave_add(P, hist_lds, e == 0u, mism_bin(P, mm), pl.pss_fwd, pl.pss_rev);
             }
+            // -Y: the same for the score bin (P.score_half is the same in every lane)
+            if constexpr (SCORE) {
+                if (P.score_half)
+                    bin_wave_add(e == 0u, score_bin(P, sc), pl.pss_fwd, pl.pss_rev,
+                                 [&](uint32_t bin, bool f, bool r, uint32_t n) { score_add(P, hist_lds, bin, f, r, n); });
+            }
             // -W: both lanes of a read that was added to a table hand in their halves; the left-end lane counts the read
             if constexpr (INTERIOR) {
                 interior_wave_add(hist_lds, ipk, pl.pss_fwd || pl.pss_rev, pl.rev, e == 0u && i_some);
@@ -1905,6 +2040,13 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         for (uint32_t i = tid; i < (P.mism_hist ? 2u * (P.mism_hist + 2u) : 0u); i += TILED_THREADS) {
             const uint32_t v = hist_lds[i];
             if (v) atomicAdd(&P.counters[P.off_mism + i], (unsigned long long)v);
+        }
+    }
+    if constexpr (SCORE) {
+        // [sf | sr] lie in LDS as they lie in the counter block
+        for (uint32_t i = tid; i < 4u * P.score_half; i += TILED_THREADS) {
+            const uint32_t v = hist_lds[i];
+            if (v) atomicAdd(&P.counters[P.off_score + i], (unsigned long long)v);
         }
     }
     flush_interior();
@@ -2464,6 +2606,26 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P
     } else
     tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, false, false, GAPPED, MISM, INTERIOR, COMP>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
                                                                                                                   lds_delta, refs_lds, nullptr, nullptr, hist_lds);
+}
+
+// -y / -Y: tally_tiled's pass 0 of the one-plane substitution tally with the SCORE arm of the body, a kernel of its own name so that
+// tally_tiled's argument list, and with it the name of every kernel the engine launches without the setting, stays what it is.
+// Dynamic LDS: the staging buffer (whole records, as under -Q) and, behind it, the 4 * P.score_half words of the score histogram,
+// where HIST and MISM have their bins.  The weight table stays in global memory (beside the staging buffer it does not in general leave
+// room for two workgroups per CU).
+template <bool MASKQ, bool REGIONS>
+__global__ void __launch_bounds__(TILED_THREADS) tally_tiled_score(const TallyParams P) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
+    __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
+    __shared__ uint32_t table[TABLE_WORDS];
+    __shared__ uint32_t toffs[2u * (TILED_MAX_T + 4u)];
+    __shared__ uint32_t lds_kmer[1];
+    __shared__ int32_t lds_delta[ST_USED];
+    __shared__ uint4 refs_lds[REF_LDS_ENTRIES + 1];
+    const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
+    uint32_t *hist_lds = (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces));
+    tally_tiled_body<true, false, false, false, PLANES_NONE, MASKQ, REGIONS, false, false, false, false, false, false, false, true>(
+        P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta, refs_lds, nullptr, nullptr, hist_lds);
 }
 
 // ---------------------------------------------------------------------------------------

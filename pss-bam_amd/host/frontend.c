@@ -35,6 +35,7 @@ int frontend_length_hist = 0;
 int frontend_mismatch_hist = 0, frontend_max_mismatches = -1, frontend_mismatch_tv = 0;
 int frontend_interior = -1;
 int frontend_composition = 0;
+const frontend_score *frontend_read_score = NULL;
 int frontend_site_context = PSSBAM_SITE_NONE;
 int frontend_end_depth = 0, frontend_end_cell5 = 0, frontend_end_cell3 = 0;
 int frontend_gapped_reads = 0;
@@ -81,6 +82,7 @@ static struct early_feed {
     int mism_hist, mism_max, mism_tv; /* -N / -n / -V: the mismatch count, set on every engine after create */
     int interior;                   /* -W: the interior margin, set on every engine after create */
     int composition;                /* -P: the composition width, set on every engine after create */
+    const frontend_score *score;    /* -y / -Y: the read score, set on every engine after create */
     int site;                       /* -X: the site context, set on every engine after create */
     int end_depth, end_cell5, end_cell3; /* -E: the end condition, set on every engine after create */
     int gapped;                     /* -I: anchored ends, set on every engine after create */
@@ -159,6 +161,12 @@ typedef struct {
     char err[400];
 } engine_make_job;
 
+/* -y / -Y: the read score of the run, if any, onto one engine */
+static int send_read_score(pssbam_engine *e, const frontend_score *sc)
+{
+    return sc && pssbam_engine_set_read_score(e, sc->weights, sc->n_dist, sc->n_qual, sc->use_filter, sc->min_score, sc->hist_half, sc->hist_shift);
+}
+
 static void *engine_make_main(void *arg)
 {
     engine_make_job *j = (engine_make_job *)arg;
@@ -169,7 +177,7 @@ static void *engine_make_main(void *arg)
         (EF.hist > 0 && pssbam_engine_set_length_histogram(*j->out, EF.hist)) ||
         ((EF.mism_hist > 0 || EF.mism_max >= 0) && pssbam_engine_set_mismatches(*j->out, EF.mism_hist, EF.mism_max, EF.mism_tv)) ||
         (EF.interior >= 0 && pssbam_engine_set_interior(*j->out, EF.interior)) ||
-        (EF.composition > 0 && pssbam_engine_set_composition(*j->out, EF.composition)) ||
+        (EF.composition > 0 && pssbam_engine_set_composition(*j->out, EF.composition)) || send_read_score(*j->out, EF.score) ||
         (EF.site != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(*j->out, EF.site)) ||
         (EF.end_depth > 0 && pssbam_engine_set_end_condition(*j->out, EF.end_depth, EF.end_cell5, EF.end_cell3)) ||
         (EF.gapped && pssbam_engine_set_gapped_reads(*j->out, 1)) || send_regions(*j->out, EF.regions) ||
@@ -307,6 +315,7 @@ void frontend_warmup_start(const pssbam_config *cfg, const char *aln_path, const
             EF.mism_tv = frontend_mismatch_tv;
             EF.interior = frontend_interior;
             EF.composition = frontend_composition;
+            EF.score = frontend_read_score;
             EF.site = frontend_site_context;
             EF.end_depth = frontend_end_depth;
             EF.end_cell5 = frontend_end_cell5;
@@ -335,6 +344,7 @@ static int same_length_bins(void)
 {
     return EF.n_edges == frontend_n_length_edges && EF.sets == frontend_contig_sets && EF.min_bq == frontend_min_base_quality &&
            EF.hist == frontend_length_hist && EF.site == frontend_site_context && EF.interior == frontend_interior && EF.composition == frontend_composition &&
+           EF.score == frontend_read_score &&
            EF.mism_hist == frontend_mismatch_hist && EF.mism_max == frontend_max_mismatches && EF.mism_tv == frontend_mismatch_tv &&
            EF.end_depth == frontend_end_depth && EF.end_cell5 == frontend_end_cell5 && EF.end_cell3 == frontend_end_cell3 &&
            EF.gapped == frontend_gapped_reads && EF.per_contig == frontend_per_contig && EF.replicates == frontend_replicates && EF.regions == frontend_regions &&
@@ -477,6 +487,8 @@ void run_result_free(run_result *res)
     free(res->mism_rev);
     free(res->comp5);
     free(res->comp3);
+    free(res->score_fwd);
+    free(res->score_rev);
     free(res->site_fwd);
     free(res->site_rev);
     free(res->end_fwd);
@@ -684,6 +696,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
                  pssbam_engine_set_mismatches(eng[g], frontend_mismatch_hist, frontend_max_mismatches, frontend_mismatch_tv)) ||
                 (frontend_interior >= 0 && pssbam_engine_set_interior(eng[g], frontend_interior)) ||
                 (frontend_composition > 0 && pssbam_engine_set_composition(eng[g], frontend_composition)) ||
+                send_read_score(eng[g], frontend_read_score) ||
                 (frontend_site_context != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(eng[g], frontend_site_context)) ||
                 (frontend_end_depth > 0 && pssbam_engine_set_end_condition(eng[g], frontend_end_depth, frontend_end_cell5, frontend_end_cell3)) ||
                 (frontend_gapped_reads && pssbam_engine_set_gapped_reads(eng[g], 1)) ||
@@ -908,6 +921,16 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             goto done;
         }
         res->composition_width = frontend_composition;
+    }
+    if (frontend_read_score && frontend_read_score->hist_half > 0 && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -Y: summed with the rest of the block */
+        res->score_half = frontend_read_score->hist_half;
+        res->score_fwd = (uint64_t *)calloc(2 * (size_t)res->score_half, sizeof(uint64_t));
+        res->score_rev = (uint64_t *)calloc(2 * (size_t)res->score_half, sizeof(uint64_t));
+        if (!res->score_fwd || !res->score_rev) { fprintf(stderr, "Error: out of memory\n"); goto done; }
+        if (pssbam_engine_finish_read_score(eng[0], res->score_fwd, res->score_rev)) {
+            fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+            goto done;
+        }
     }
     if (frontend_site_context != PSSBAM_SITE_NONE && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -X: summed with the rest of the block */
         const size_t cells = (size_t)(cfg->pss.region_len + 2) * 16;

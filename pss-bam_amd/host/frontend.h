@@ -39,6 +39,10 @@ typedef struct run_result {
      * each (malloc'ed), or NULL */
     int composition_width;
     uint64_t *comp5, *comp3;
+    /* pss-bam -Y (frontend_read_score with a histogram): the score histogram of the reads added to the forward / reverse
+     * table, 2 * score_half rows each, or NULL */
+    int score_half;
+    uint64_t *score_fwd, *score_rev;
     /* pss-bam -X (frontend_site_context): the in-context tables IN, (region_len+2)*16 each with rows 0/1 as fwd / rev,
      * or NULL */
     unsigned long *site_fwd, *site_rev;
@@ -76,6 +80,16 @@ extern int frontend_interior;
 /* pss-bam -P: the width of the composition table (0: off); every engine gets it (pssbam_engine_set_composition) and
  * run_tally() returns the two blocks.  Set before frontend_warmup_start. */
 extern int frontend_composition;
+
+/* pss-bam -y / -Y: the read score (NULL: off) -- the weight table [4][n_dist][n_qual], the filter (use_filter: only reads with a
+ * score of at least min_score are tallied) and the histogram (hist_half = 0: none); every engine gets it
+ * (pssbam_engine_set_read_score) and run_tally() returns the two arrays of the histogram.  Set before frontend_warmup_start;
+ * the pointer is kept. */
+typedef struct frontend_score {
+    const int16_t *weights;
+    int n_dist, n_qual, use_filter, min_score, hist_half, hist_shift;
+} frontend_score;
+extern const frontend_score *frontend_read_score;
 
 /* pss-bam -X: the site context (PSSBAM_SITE_*; PSSBAM_SITE_NONE: off); every engine gets it
  * (pssbam_engine_set_site_context) and run_tally() returns the in-context pair.  Set before frontend_warmup_start. */

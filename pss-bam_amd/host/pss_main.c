@@ -65,6 +65,14 @@
  * depurination signal next to the read against its own baseline further out.  Rows -1 and -2 are the diagonal of the counts
  * file's context rows.  The other files stay as they are.  Needs -r <= 30.  Goes with -R, -Q (no effect), -T, -m, -l, -L, -q, -U and -D.
  * Not with -G, -S, -C, -H, -X, -E, -I, -A, -n, -N, -V, -J or -W.
+ * Added: -y <t> tallies only the reads whose post-mortem-damage score is at least t -- the files are what this command writes
+ * without -y for the input without the other reads; -Y also writes <prefix>.pss.pmd.txt, how many of the reads added to the forward
+ * / reverse table have a score of n nats, rounded down, n = -31 .. 30, and below / above, from the same pass.  The score is the
+ * log-likelihood ratio "ancient" against "modern" of Skoglund et al. 2014 for a double-stranded library with its default
+ * parameters, summed over the C and G sites of the read (read_score.h; under -Q only the bases that pass it), held as an integer in
+ * units of 1/256 nat: -y 3 keeps the reads with a score of at least 768 units.  No number-for-number parity with another
+ * implementation of the score is claimed.  Needs -r <= 30.  Goes with -R, -Q, -T, -m, -l, -L, -q, -U and -D.  Not with -G, -S, -C,
+ * -H, -X, -E, -I, -A, -n, -N, -V, -J, -W or -P.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -85,6 +93,7 @@
 #include "length_hist.h"
 #include "mismatches.h"
 #include "read_groups.h"
+#include "read_score.h"
 #include "regions.h"
 #include "replicates.h"
 #include "report.h"
@@ -94,14 +103,14 @@ int main(int argc, char *argv[])
     const double age_main = frontend_process_age_s();
     frontend_detach_start();   /* the caller gets its prompt back when the reports are written, not when 30 GB of device buffers are gone */
     const double t_main = frontend_now_s();
-    int region_len = 15, min_mq = 0, merged_only = 0, by_group = 0, gapped = 0, per_contig = 0, tv_only = 0, option;
+    int region_len = 15, min_mq = 0, merged_only = 0, by_group = 0, gapped = 0, per_contig = 0, tv_only = 0, score_hist = 0, option;
     unsigned long min_read_len = 0, max_read_len = 250000000;
     const char *up_ctx = "ACGT", *down_ctx = "ACGT";
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL, *read_group = NULL;
     const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL, *bed_fn = NULL, *hist_arg = NULL, *site_arg = NULL, *end_arg = NULL;
-    const char *max_mm_arg = NULL, *mm_hist_arg = NULL, *rep_arg = NULL, *interior_arg = NULL, *comp_arg = NULL;
+    const char *max_mm_arg = NULL, *mm_hist_arg = NULL, *rep_arg = NULL, *interior_arg = NULL, *comp_arg = NULL, *min_score_arg = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:P:")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:P:y:Y")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -129,6 +138,8 @@ int main(int argc, char *argv[])
         case 'J': rep_arg = optarg; break;
         case 'W': interior_arg = optarg; break;
         case 'P': comp_arg = optarg; break;
+        case 'y': min_score_arg = optarg; break;
+        case 'Y': score_hist = 1; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -166,7 +177,9 @@ int main(int argc, char *argv[])
               "-V <with -n / -N: count only transversions>\n"
               "-J <K> <also write the jackknife standard errors of the rates, from K read-name replicates (2..64)>\n"
               "-W <d> <also write the substitution counts and rates of the read interior, d bases and more from both ends (0..65535)>\n"
-              "-P <w> <also write the reference base composition w bases on either side of the read ends (1..30)>\n",
+              "-P <w> <also write the reference base composition w bases on either side of the read ends (1..30)>\n"
+              "-y <t> <only tally the reads with a post-mortem-damage score of at least t nats (double-stranded model, held in units of 1/256 nat)>\n"
+              "-Y <also write how many tallied reads have a post-mortem-damage score of -31 .. 30 nats and beyond; no parity with another implementation is claimed>\n",
               stderr);
         exit(1);
     }
@@ -342,6 +355,40 @@ int main(int argc, char *argv[])
             exit(1);
         }
     }
+    static int16_t pmd_weights[4 * PSS_PMD_DIST * PSS_PMD_QUAL];
+    static frontend_score score;
+    if (min_score_arg || score_hist) {
+        const char *mine = !score_hist ? "-y (damage-score filter)" : !min_score_arg ? "-Y (damage-score histogram)" : "-y / -Y (damage-score filter and histogram)";
+        if (by_group || len_edges || ctg_map || hist_arg || site_arg || end_arg || gapped || per_contig || max_mm_arg || mm_hist_arg || tv_only || rep_arg ||
+            interior_arg || comp_arg) {
+            fprintf(stderr, "%s and %s exclude each other.\n", mine,
+                    by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)" : ctg_map ? "-C (tables per contig set)"
+                    : hist_arg ? "-H (fragment-length histogram)" : site_arg ? "-X (tables per site context)"
+                    : end_arg ? "-E (tables conditional on the other end)" : gapped ? "-I (clipped and gapped reads by their anchored ends)"
+                    : per_contig ? "-A (tables per contig)" : max_mm_arg ? "-n (mismatch filter)" : mm_hist_arg ? "-N (mismatch histogram)"
+                    : tv_only ? "-V (count only transversions)" : rep_arg ? "-J (jackknife replicates)" : interior_arg ? "-W (read-interior table)"
+                    : "-P (base composition around the read ends)");
+            exit(1);
+        }
+        int32_t min_score = 0;
+        char err[200];
+        if (min_score_arg && pss_parse_min_score(min_score_arg, &min_score, err, sizeof err)) {
+            fprintf(stderr, "%s\n", err);
+            exit(1);
+        }
+        if (region_len > 30) {
+            fprintf(stderr, "%s needs -r <= 30 (a read's fate is decided in the one pass over 32 table rows), not -r %d.\n", mine, region_len);
+            exit(1);
+        }
+        pss_pmd_weights(pmd_weights);
+        score.weights = pmd_weights;
+        score.n_dist = PSS_PMD_DIST;
+        score.n_qual = PSS_PMD_QUAL;
+        score.use_filter = min_score_arg != NULL;
+        score.min_score = min_score;
+        score.hist_half = score_hist ? PSS_PMD_HIST_HALF : 0;
+        score.hist_shift = score_hist ? PSS_PMD_HIST_SHIFT : 0;
+    }
     pss_regions bed;
     memset(&bed, 0, sizeof bed);
     if (bed_fn) {
@@ -406,6 +453,8 @@ int main(int argc, char *argv[])
     if (rep_arg) fprintf(stderr, " -J %d", replicates);
     if (interior_arg) fprintf(stderr, " -W %d", interior);
     if (comp_arg) fprintf(stderr, " -P %d", composition);
+    if (min_score_arg) fprintf(stderr, " -y %s", min_score_arg);
+    if (score_hist) fprintf(stderr, " -Y");
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -441,6 +490,7 @@ int main(int argc, char *argv[])
     frontend_replicates = replicates;
     frontend_interior = interior;
     frontend_composition = composition;
+    if (score.weights) frontend_read_score = &score;
     if (bed_fn) frontend_regions = &bed;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
@@ -469,6 +519,7 @@ int main(int argc, char *argv[])
     if (res.mism_fwd && pss_write_mismatches(fasta_fn, bam_fn, out_prefix, res.mism_max, tv_only, res.mism_fwd, res.mism_rev)) exit(1);   /* -N */
     if (res.has_interior && pss_write_interior(fasta_fn, bam_fn, out_prefix, interior, min_bq, res.interior, res.interior_reads)) exit(1);   /* -W */
     if (res.comp5 && pss_write_composition(fasta_fn, bam_fn, out_prefix, res.composition_width, res.comp5, res.comp3)) exit(1);   /* -P */
+    if (res.score_fwd && pss_write_read_scores(fasta_fn, bam_fn, out_prefix, res.score_half, res.score_fwd, res.score_rev)) exit(1);   /* -Y */
     if (res.site_fwd) {   /* -X: IN as the engine returns it; OUT = T - IN on the position rows, the context rows as T */
         const size_t cells = (size_t)(region_len + 2) * 16;
         unsigned long *out_fwd = (unsigned long *)malloc(cells * sizeof *out_fwd), *out_rev = (unsigned long *)malloc(cells * sizeof *out_rev);

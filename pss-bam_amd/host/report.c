@@ -326,6 +326,27 @@ int pss_write_composition(const char *fasta_fn, const char *bam_fn, const char *
     return fclose(fp) ? 1 : 0;
 }
 
+int pss_write_read_scores(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int hist_half, const uint64_t *fwd,
+                          const uint64_t *rev)
+{
+    char fn[FN_BUF + 1];
+    FILE *fp;
+    snprintf(fn, sizeof fn, "%s.pss.pmd.txt", out_prefix);
+    fp = fopen(fn, "w");
+    if (!fp) {
+        fprintf(stderr, "ERROR: Cannot write to file %s\n.", fn);
+        return 1;
+    }
+    fprintf(fp, "# post-mortem-damage score (whole nats, rounded down) of the reads added to the forward / reverse table\n# FASTA: %s\n# BAM: %s\n",
+            fasta_fn, bam_fn);
+    fputs("score\tfwd\trev\n", fp);
+    fprintf(fp, "<%d\t%llu\t%llu\n", 1 - hist_half, (unsigned long long)fwd[0], (unsigned long long)rev[0]);
+    for (int b = 1; b < 2 * hist_half - 1; b++)
+        fprintf(fp, "%d\t%llu\t%llu\n", b - hist_half, (unsigned long long)fwd[b], (unsigned long long)rev[b]);
+    fprintf(fp, ">=%d\t%llu\t%llu\n", hist_half - 1, (unsigned long long)fwd[2 * hist_half - 1], (unsigned long long)rev[2 * hist_half - 1]);
+    return fclose(fp) ? 1 : 0;
+}
+
 int fragkon_write_table(FILE *out, const char *fasta_fn, const char *bam_fn, int klen, const uint64_t *k5,
                         const uint64_t *k3)
 {

@@ -59,6 +59,12 @@ int pss_write_interior(const char *fasta_fn, const char *bam_fn, const char *out
  * field followed by a TAB.  c5 / c3: 2 * width rows of five counts, row j + width = offset j.  Returns 0, or 1 after a diagnostic. */
 int pss_write_composition(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int width, const uint64_t *c5,
                           const uint64_t *c3);
+/* pss-bam -Y: <out_prefix>.pss.pmd.txt, in the layout of the mismatches file -- three '#' lines, the column names, then one
+ * tab-separated line "<score> <fwd> <rev>" per bin of the engine's score histogram (zero rows included): the first labelled
+ * "<-(hist_half-1)" for every score below that many nats, then one per whole nat -(hist_half-1) .. hist_half-2 (a score is rounded
+ * down), the last ">=(hist_half-1)"; fwd / rev hold 2 * hist_half counts.  Returns 0, or 1 after a diagnostic. */
+int pss_write_read_scores(const char *fasta_fn, const char *bam_fn, const char *out_prefix, int hist_half, const uint64_t *fwd,
+                          const uint64_t *rev);
 /* k5 / k3: 4^klen 64-bit bins (clamped to UINT_MAX on output) */
 int fragkon_write_table(FILE *out, const char *fasta_fn, const char *bam_fn, int klen, const uint64_t *k5,
                         const uint64_t *k3);
