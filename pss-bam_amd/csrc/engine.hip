@@ -220,29 +220,28 @@ struct pssbam_engine {
     bool contig_evict = true;   // PSSBAM_CONTIG_EVICT=0: the -A kernel empties its slots at a miss only (A/B runs)
     bool tallied = false;   // a tally launch since create / reset
     uint32_t min_bq = 0;    // -Q: read bases with a QUAL byte below this are left out of the tables (pssbam_engine_set_min_base_quality)
-    // -H (pssbam_engine_set_length_histogram): hf | hr, hist_max + 2 words each, at off_hist = the end of the block as it is without them
-    uint32_t hist_max = 0, off_hist = 0;
-    // -X (pssbam_engine_set_site_context): fwd_in | rev_in, rows * 16 words each, at off_site = the end of the block as it is without them
-    uint32_t site_mode = 0, off_site = 0;
-    // -E (pssbam_engine_set_end_condition): fwd_c | rev_c | reads[4], rows * 16 words per table, at off_end = the end of the block as it is without them
-    uint32_t end_depth = 0, end_cell5 = 0, end_cell3 = 0, off_end = 0;
-    // -n / -N / -V (pssbam_engine_set_mismatches): mf | mr, mism_hist + 2 words each, at off_mism = the end of the block as it is without
+    // -H (pssbam_engine_set_length_histogram): hf | hr, hist_max + 2 words each, at off_groups = the end of the block as it is without them
+    uint32_t hist_max = 0;
+    // -X (pssbam_engine_set_site_context): fwd_in | rev_in, rows * 16 words each, at off_groups = the end of the block as it is without them
+    uint32_t site_mode = 0;
+    // -E (pssbam_engine_set_end_condition): fwd_c | rev_c | reads[4], rows * 16 words per table, at off_groups = the end of the block as it is without them
+    uint32_t end_depth = 0, end_cell5 = 0, end_cell3 = 0;
+    // -n / -N / -V (pssbam_engine_set_mismatches): mf | mr, mism_hist + 2 words each, at off_groups = the end of the block as it is without
     // them (mism_hist = 0: no words); mism_max = -1: no filter
-    uint32_t mism_hist = 0, off_mism = 0;
+    uint32_t mism_hist = 0;
     int32_t mism_max = -1;
     bool mism_tv = false;
-    // -W (pssbam_engine_set_interior): table[16] | reads, 17 words at off_interior = the end of the block as it is without them;
+    // -W (pssbam_engine_set_interior): table[16] | reads, 17 words at off_groups = the end of the block as it is without them;
     // interior_margin = -1: off, no words
     int32_t interior_margin = -1;
-    uint32_t off_interior = 0;
-    // -P (pssbam_engine_set_composition): c5 | c3, 2 * width * 5 words each at off_composition = the end of the block as it is
+    // -P (pssbam_engine_set_composition): c5 | c3, 2 * width * 5 words each at off_groups = the end of the block as it is
     // without them; composition = 0: off, no words
-    uint32_t composition = 0, off_composition = 0;
+    uint32_t composition = 0;
     // -y / -Y (pssbam_engine_set_read_score): the weights [4][score_nd][score_nq] in device memory (d_score_w = NULL: off); the
-    // filter S >= score_min when score_filter; sf | sr, 2 * score_half words each at off_score = the end of the block as it is
+    // filter S >= score_min when score_filter; sf | sr, 2 * score_half words each at off_groups = the end of the block as it is
     // without them (score_half = 0: no words)
     int16_t *d_score_w = nullptr;
-    uint32_t score_nd = 0, score_nq = 0, score_half = 0, score_shift = 0, off_score = 0;
+    uint32_t score_nd = 0, score_nq = 0, score_half = 0, score_shift = 0;
     int32_t score_min = 0;
     bool score_filter = false;
     bool gapped = false;   // -I (pssbam_engine_set_gapped_reads): clipped and gapped reads are tallied by their anchored ends; no counter words
@@ -1089,16 +1088,16 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
     const bool hist = do_pss && e->hist_max > 0;   // -H: the HIST instantiations; without a histogram the engine launches what it always did
     if (hist) {
         P.hist_max = e->hist_max;
-        P.off_hist = e->off_hist;
+        P.off_hist = e->off_groups;
     }
     const bool site = do_pss && e->site_mode != PSSBAM_SITE_NONE;   // -X: the SITE instantiations; without it the engine launches what it always did
-    if (site) P.off_site = e->off_site;
+    if (site) P.off_site = e->off_groups;
     const bool endc = do_pss && e->end_depth > 0;   // -E: the END instantiations; without it the engine launches what it always did
     if (endc) {
         P.end_depth = e->end_depth;
         P.end_cell5 = e->end_cell5;
         P.end_cell3 = e->end_cell3;
-        P.off_end = e->off_end;
+        P.off_end = e->off_groups;
     }
     // -n / -N: the MISM instantiations; without the setting the engine launches what it always did
     const bool mism = do_pss && (e->mism_hist > 0 || e->mism_max >= 0);
@@ -1106,17 +1105,17 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         P.mism_limit = e->mism_max >= 0 ? (uint32_t)e->mism_max + 1u : 0u;
         P.mism_hist = e->mism_hist;
         P.mism_tv = e->mism_tv ? 1u : 0u;
-        P.off_mism = e->off_mism;
+        P.off_mism = e->mism_hist ? e->off_groups : 0u;
     }
     const bool interior = do_pss && e->interior_margin >= 0;   // -W: the INTERIOR instantiations; without it the engine launches what it always did
     if (interior) {
         P.interior = (uint32_t)e->interior_margin + 1u;
-        P.off_interior = e->off_interior;
+        P.off_interior = e->off_groups;
     }
     const bool comp = do_pss && e->composition > 0;   // -P: the COMP instantiations; without it the engine launches what it always did
     if (comp) {
         P.composition = e->composition;
-        P.off_composition = e->off_composition;
+        P.off_composition = e->off_groups;
     }
     const bool score = do_pss && e->d_score_w != nullptr;   // -y / -Y: the SCORE instantiations; without it the engine launches what it always did
     if (score) {
@@ -1127,7 +1126,7 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         P.score_min = e->score_min;
         P.score_half = e->score_half;
         P.score_shift = e->score_shift;
-        P.off_score = e->off_score;
+        P.off_score = e->score_half ? e->off_groups : 0u;
     }
     const bool gapped = do_pss && e->gapped;   // -I: the GAPPED instantiations; without it the engine launches what it always did
     P.gapped = gapped ? 1u : 0u;
@@ -1586,13 +1585,40 @@ extern "C" int pssbam_engine_finish_kmer_groups(pssbam_engine *e, int32_t group,
     return PSSBAM_OK;
 }
 
-// What the setters that resize the counter block require: nothing tallied yet, and the block is the engine's own.  `what`
-// names what is being set in the messages.
 static bool mismatches_on(const pssbam_engine *e) { return e->mism_hist > 0 || e->mism_max >= 0; }   // -n / -N
 static bool interior_on(const pssbam_engine *e) { return e->interior_margin >= 0; }   // -W
 static bool composition_on(const pssbam_engine *e) { return e->composition > 0; }   // -P
 static bool read_score_on(const pssbam_engine *e) { return e->d_score_w != nullptr; }   // -y / -Y
 
+// The exclusive modes: at most one is on in an engine.  Their extra counter words all start at off_groups, and the ones that
+// take a read's fate from the whole read do so in the one 32-row pass.  A new mode is one row here.
+enum Mode { MODE_RG, MODE_LEN, MODE_REF, MODE_HASH, MODE_EACH, MODE_HIST, MODE_SITE, MODE_END, MODE_GAPPED, MODE_MISM, MODE_INTERIOR,
+            MODE_COMPOSITION, MODE_SCORE };
+static const struct { const char *name; bool (*on)(const pssbam_engine *); } MODES[] = {
+    {"read groups", [](const pssbam_engine *e) { return e->planes == PLANES_RG; }},
+    {"length bins", [](const pssbam_engine *e) { return e->planes == PLANES_LEN; }},
+    {"contig sets", [](const pssbam_engine *e) { return e->planes == PLANES_REF; }},
+    {"replicates", [](const pssbam_engine *e) { return e->planes == PLANES_HASH; }},
+    {"per-contig tables", [](const pssbam_engine *e) { return e->per_contig; }},
+    {"the length histogram", [](const pssbam_engine *e) { return e->hist_max > 0; }},
+    {"site context", [](const pssbam_engine *e) { return e->site_mode != PSSBAM_SITE_NONE; }},
+    {"the end condition", [](const pssbam_engine *e) { return e->end_depth > 0; }},
+    {"gapped reads", [](const pssbam_engine *e) { return e->gapped; }},
+    {"the mismatch count", mismatches_on},
+    {"the interior table", interior_on},
+    {"the composition table", composition_on},
+    {"the read score", read_score_on},
+};
+
+// What every setter that switches `mine` on asks first: no other mode is on (setting the one that is on again is no conflict)
+static int check_exclusive(const pssbam_engine *e, Mode mine) {
+    for (size_t m = 0; m < sizeof MODES / sizeof *MODES; m++)
+        if (m != (size_t)mine && MODES[m].on(e)) return fail(PSSBAM_EINVAL, "%s and %s exclude each other", MODES[mine].name, MODES[m].name);
+    return PSSBAM_OK;
+}
+
+// What the setters that resize the counter block require: nothing tallied yet, and the block is the engine's own.  `what`
+// names what is being set in the messages.
 static int check_may_resize(const pssbam_engine *e, const char *what) {
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set %s after create or reset, before the first tally", what);
     if (e->d_counters != e->d_counters_own) return fail(PSSBAM_ESTATE, "a caller-bound counter block cannot grow: set %s before bind_counters", what);
@@ -1611,18 +1637,20 @@ static int grow_counters(pssbam_engine *e, uint64_t n_counters) {
     return PSSBAM_OK;
 }
 
+// The exclusive modes' extra words: the block becomes off_groups + words long (it grows, or shrinks back), zeroed.
+static int resize_extra(pssbam_engine *e, uint64_t words, const char *what) {
+    if (const int rc = check_may_resize(e, what)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    const uint64_t n_counters = (uint64_t)e->off_groups + words;
+    if (n_counters > 0xFFFFFFFFull) return fail(PSSBAM_EINVAL, "the counter block would pass 2^32 words");
+    return grow_counters(e, n_counters);
+}
+
 // What set_read_groups, set_length_bins, set_contig_sets and set_replicates share: the counter block grows to n_planes [fwd | rev] planes
 // (a k-mer engine: [k5 | k3]) behind the stats.  `what` names the caller's planes in the messages.
-static int set_planes(pssbam_engine *e, PlaneSel sel, uint32_t n_planes, const char *what) {
-    if (e->per_contig) return fail(PSSBAM_EINVAL, "%s and per-contig tables exclude each other", what);
-    if (e->hist_max) return fail(PSSBAM_EINVAL, "%s and the length histogram exclude each other", what);
-    if (e->site_mode) return fail(PSSBAM_EINVAL, "%s and site context exclude each other", what);
-    if (e->end_depth) return fail(PSSBAM_EINVAL, "%s and the end condition exclude each other", what);
-    if (e->gapped) return fail(PSSBAM_EINVAL, "%s and gapped reads exclude each other", what);
-    if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "%s and the mismatch count exclude each other", what);
-    if (interior_on(e)) return fail(PSSBAM_EINVAL, "%s and the interior table exclude each other", what);
-    if (composition_on(e)) return fail(PSSBAM_EINVAL, "%s and the composition table exclude each other", what);
-    if (read_score_on(e)) return fail(PSSBAM_EINVAL, "%s and the read score exclude each other", what);
+static int set_planes(pssbam_engine *e, PlaneSel sel, Mode mode, uint32_t n_planes) {
+    const char *what = MODES[mode].name;
+    if (const int rc = check_exclusive(e, mode)) return rc;
     const bool kmer = e->cfg.tally_mask == PSSBAM_TALLY_KMER;
     if (e->cfg.tally_mask != PSSBAM_TALLY_PSS && !kmer)
         return fail(PSSBAM_EINVAL, "%s split the substitution tables or the k-mer tables, not both (PSSBAM_TALLY_PSS | PSSBAM_TALLY_KMER)", what);
@@ -1648,9 +1676,6 @@ extern "C" int pssbam_engine_set_read_groups(pssbam_engine *e, int32_t n, const 
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
     if (n < 1 || n > PSSBAM_MAX_READ_GROUPS || !ids) return fail(PSSBAM_EINVAL, "read group count %d outside 1..%d", n, PSSBAM_MAX_READ_GROUPS);
     if (e->has_rg) return fail(PSSBAM_EINVAL, "read groups and a -R read group filter exclude each other");
-    if (e->planes == PLANES_LEN) return fail(PSSBAM_EINVAL, "read groups and length bins exclude each other");
-    if (e->planes == PLANES_REF) return fail(PSSBAM_EINVAL, "read groups and contig sets exclude each other");
-    if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "read groups and replicates exclude each other");
     for (int32_t i = 0; i < n; i++)
         if (!ids[i]) return fail(PSSBAM_EINVAL, "read group %d is NULL", i);
     // ID table (concatenated) + open-addressing hash over it; a repeated ID keeps its first index
@@ -1684,7 +1709,7 @@ extern "C" int pssbam_engine_set_read_groups(pssbam_engine *e, int32_t n, const 
     HIP_TRY(hipMemcpy(d_ids, cat.data(), cat.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_offs, offs.data(), offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_hash, hash.data(), hash.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (const int rc = set_planes(e, PLANES_RG, (uint32_t)n, "read groups")) {
+    if (const int rc = set_planes(e, PLANES_RG, MODE_RG, (uint32_t)n)) {
         for (void *p : {(void *)d_ids, (void *)d_offs, (void *)d_hash}) (void)hipFree(p);
         return rc;
     }
@@ -1713,15 +1738,7 @@ extern "C" int pssbam_engine_set_gapped_reads(pssbam_engine *e, int32_t on) {
     if (on) {
         if (e->cfg.tally_mask != PSSBAM_TALLY_PSS)
             return fail(PSSBAM_EINVAL, "gapped reads are tallied by their anchored ends in the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
-        if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "gapped reads and replicates exclude each other");
-        if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "gapped reads and read groups / length bins / contig sets exclude each other");
-        if (e->hist_max) return fail(PSSBAM_EINVAL, "gapped reads and the length histogram exclude each other");
-        if (e->site_mode) return fail(PSSBAM_EINVAL, "gapped reads and site context exclude each other");
-        if (e->end_depth) return fail(PSSBAM_EINVAL, "gapped reads and the end condition exclude each other");
-        if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "gapped reads and the mismatch count exclude each other");
-        if (interior_on(e)) return fail(PSSBAM_EINVAL, "gapped reads and the interior table exclude each other");
-        if (composition_on(e)) return fail(PSSBAM_EINVAL, "gapped reads and the composition table exclude each other");
-        if (read_score_on(e)) return fail(PSSBAM_EINVAL, "gapped reads and the read score exclude each other");
+        if (const int rc = check_exclusive(e, MODE_GAPPED)) return rc;
     }
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set gapped reads after create or reset, before the first tally");
     e->gapped = on != 0;   // (the counter block keeps its size: a caller-bound block stays bound)
@@ -1733,24 +1750,11 @@ extern "C" int pssbam_engine_set_length_histogram(pssbam_engine *e, int32_t max_
     if (max_len < 0 || max_len > PSSBAM_MAX_HIST_LENGTH) return fail(PSSBAM_EINVAL, "length histogram limit %d outside 0..%d", max_len, PSSBAM_MAX_HIST_LENGTH);
     if (!(e->cfg.tally_mask & PSSBAM_TALLY_PSS))
         return fail(PSSBAM_EINVAL, "the length histogram counts the reads added to the substitution tables: the engine needs PSSBAM_TALLY_PSS");
-    if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "the length histogram and replicates exclude each other");
-    if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the length histogram and read groups / length bins / contig sets exclude each other");
-    if (e->site_mode) return fail(PSSBAM_EINVAL, "the length histogram and site context exclude each other");
-    if (e->end_depth) return fail(PSSBAM_EINVAL, "the length histogram and the end condition exclude each other");
-    if (e->gapped && max_len) return fail(PSSBAM_EINVAL, "the length histogram and gapped reads exclude each other");
-    if (mismatches_on(e) && max_len) return fail(PSSBAM_EINVAL, "the length histogram and the mismatch count exclude each other");
-    if (interior_on(e) && max_len) return fail(PSSBAM_EINVAL, "the length histogram and the interior table exclude each other");
-    if (composition_on(e) && max_len) return fail(PSSBAM_EINVAL, "the length histogram and the composition table exclude each other");
-    if (read_score_on(e) && max_len) return fail(PSSBAM_EINVAL, "the length histogram and the read score exclude each other");
-    if (const int rc = check_may_resize(e, "the length histogram")) return rc;
-    if ((uint32_t)max_len == e->hist_max) return PSSBAM_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    // the block grows (or shrinks back) behind everything it holds without the histogram
-    const uint64_t n_counters = (uint64_t)e->off_groups + (max_len ? 2ull * ((uint64_t)max_len + 2ull) : 0ull);
-    if (n_counters > 0xFFFFFFFFull) return fail(PSSBAM_EINVAL, "the counter block would pass 2^32 words");
-    if (const int rc = grow_counters(e, n_counters)) return rc;
+    if (max_len)
+        if (const int rc = check_exclusive(e, MODE_HIST)) return rc;
+    if ((uint32_t)max_len == e->hist_max) return check_may_resize(e, "the length histogram");
+    if (const int rc = resize_extra(e, max_len ? 2ull * ((uint64_t)max_len + 2ull) : 0ull, "the length histogram")) return rc;
     e->hist_max = (uint32_t)max_len;
-    e->off_hist = e->off_groups;
     return PSSBAM_OK;
 }
 
@@ -1760,8 +1764,8 @@ extern "C" int pssbam_engine_finish_length_histogram(pssbam_engine *e, uint64_t 
     const int rc = pssbam_engine_sync(e);
     if (rc) return rc;
     const size_t n = (size_t)e->hist_max + 2;
-    if (fwd) HIP_TRY(hipMemcpy(fwd, e->d_counters + e->off_hist, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (rev) HIP_TRY(hipMemcpy(rev, e->d_counters + e->off_hist + n, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (fwd) HIP_TRY(hipMemcpy(fwd, e->d_counters + e->off_groups, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (rev) HIP_TRY(hipMemcpy(rev, e->d_counters + e->off_groups + n, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return PSSBAM_OK;
 }
 
@@ -1776,25 +1780,12 @@ extern "C" int pssbam_engine_set_mismatches(pssbam_engine *e, int32_t hist_max, 
             return fail(PSSBAM_EINVAL, "the mismatch count filters the reads of the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
         if (e->cfg.pss.region_len > 30)
             return fail(PSSBAM_EINVAL, "the mismatch count needs a region length of at most 30 (the decision is taken in the one pass that holds all rows), not %d", e->cfg.pss.region_len);
-        if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "the mismatch count and replicates exclude each other");
-        if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the mismatch count and read groups / length bins / contig sets / per-contig tables exclude each other");
-        if (e->hist_max) return fail(PSSBAM_EINVAL, "the mismatch count and the length histogram exclude each other");
-        if (e->site_mode) return fail(PSSBAM_EINVAL, "the mismatch count and site context exclude each other");
-        if (e->end_depth) return fail(PSSBAM_EINVAL, "the mismatch count and the end condition exclude each other");
-        if (e->gapped) return fail(PSSBAM_EINVAL, "the mismatch count and gapped reads exclude each other");
-        if (interior_on(e)) return fail(PSSBAM_EINVAL, "the mismatch count and the interior table exclude each other");
-        if (composition_on(e)) return fail(PSSBAM_EINVAL, "the mismatch count and the composition table exclude each other");
-        if (read_score_on(e)) return fail(PSSBAM_EINVAL, "the mismatch count and the read score exclude each other");
+        if (const int rc = check_exclusive(e, MODE_MISM)) return rc;
     }
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the mismatch count after create or reset, before the first tally");
-    if ((uint32_t)hist_max != e->mism_hist) {
-        if (const int rc = check_may_resize(e, "the mismatch histogram")) return rc;
-        HIP_TRY(hipSetDevice(e->device));
-        // the block grows (or shrinks back) behind everything it holds without the histogram
-        if (const int rc = grow_counters(e, (uint64_t)e->off_groups + (hist_max ? 2ull * ((uint64_t)hist_max + 2ull) : 0ull))) return rc;
-    }
+    if ((uint32_t)hist_max != e->mism_hist)
+        if (const int rc = resize_extra(e, hist_max ? 2ull * ((uint64_t)hist_max + 2ull) : 0ull, "the mismatch histogram")) return rc;
     e->mism_hist = (uint32_t)hist_max;
-    e->off_mism = hist_max ? e->off_groups : 0u;
     e->mism_max = max_mismatches;
     e->mism_tv = on && transversions_only != 0;
     return PSSBAM_OK;
@@ -1806,8 +1797,8 @@ extern "C" int pssbam_engine_finish_mismatches(pssbam_engine *e, uint64_t *fwd, 
     const int rc = pssbam_engine_sync(e);
     if (rc) return rc;
     const size_t n = (size_t)e->mism_hist + 2;
-    if (fwd) HIP_TRY(hipMemcpy(fwd, e->d_counters + e->off_mism, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (rev) HIP_TRY(hipMemcpy(rev, e->d_counters + e->off_mism + n, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (fwd) HIP_TRY(hipMemcpy(fwd, e->d_counters + e->off_groups, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (rev) HIP_TRY(hipMemcpy(rev, e->d_counters + e->off_groups + n, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return PSSBAM_OK;
 }
 
@@ -1819,25 +1810,12 @@ extern "C" int pssbam_engine_set_interior(pssbam_engine *e, int32_t margin) {
             return fail(PSSBAM_EINVAL, "the interior table counts the reads of the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
         if (e->cfg.pss.region_len > 30)
             return fail(PSSBAM_EINVAL, "the interior table needs a region length of at most 30 (a read's fate is decided in the one pass that holds all rows), not %d", e->cfg.pss.region_len);
-        if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "the interior table and replicates exclude each other");
-        if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the interior table and read groups / length bins / contig sets / per-contig tables exclude each other");
-        if (e->hist_max) return fail(PSSBAM_EINVAL, "the interior table and the length histogram exclude each other");
-        if (e->site_mode) return fail(PSSBAM_EINVAL, "the interior table and site context exclude each other");
-        if (e->end_depth) return fail(PSSBAM_EINVAL, "the interior table and the end condition exclude each other");
-        if (e->gapped) return fail(PSSBAM_EINVAL, "the interior table and gapped reads exclude each other");
-        if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "the interior table and the mismatch count exclude each other");
-        if (composition_on(e)) return fail(PSSBAM_EINVAL, "the interior table and the composition table exclude each other");
-        if (read_score_on(e)) return fail(PSSBAM_EINVAL, "the interior table and the read score exclude each other");
+        if (const int rc = check_exclusive(e, MODE_INTERIOR)) return rc;
     }
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the interior table after create or reset, before the first tally");
-    if ((margin >= 0) != interior_on(e)) {
-        if (const int rc = check_may_resize(e, "the interior table")) return rc;
-        HIP_TRY(hipSetDevice(e->device));
-        // the block grows (or shrinks back) behind everything it holds without the table
-        if (const int rc = grow_counters(e, (uint64_t)e->off_groups + (margin >= 0 ? (uint64_t)INTERIOR_WORDS : 0ull))) return rc;
-    }
+    if ((margin >= 0) != interior_on(e))
+        if (const int rc = resize_extra(e, margin >= 0 ? (uint64_t)INTERIOR_WORDS : 0ull, "the interior table")) return rc;
     e->interior_margin = margin;
-    e->off_interior = margin >= 0 ? e->off_groups : 0u;
     return PSSBAM_OK;
 }
 
@@ -1846,8 +1824,8 @@ extern "C" int pssbam_engine_finish_interior(pssbam_engine *e, uint64_t table[16
     if (!interior_on(e)) return fail(PSSBAM_EINVAL, "pssbam_engine_set_interior has not been called with a margin");
     const int rc = pssbam_engine_sync(e);
     if (rc) return rc;
-    if (table) HIP_TRY(hipMemcpy(table, e->d_counters + e->off_interior, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (reads) HIP_TRY(hipMemcpy(reads, e->d_counters + e->off_interior + 16, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (table) HIP_TRY(hipMemcpy(table, e->d_counters + e->off_groups, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (reads) HIP_TRY(hipMemcpy(reads, e->d_counters + e->off_groups + 16, sizeof(uint64_t), hipMemcpyDeviceToHost));
     return PSSBAM_OK;
 }
 
@@ -1859,25 +1837,12 @@ extern "C" int pssbam_engine_set_composition(pssbam_engine *e, int32_t width) {
             return fail(PSSBAM_EINVAL, "the composition table counts the reads of the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
         if (e->cfg.pss.region_len > 30)
             return fail(PSSBAM_EINVAL, "the composition table needs a region length of at most 30 (a read's fate and its end windows are those of the one pass that holds all rows), not %d", e->cfg.pss.region_len);
-        if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "the composition table and replicates exclude each other");
-        if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the composition table and read groups / length bins / contig sets / per-contig tables exclude each other");
-        if (e->hist_max) return fail(PSSBAM_EINVAL, "the composition table and the length histogram exclude each other");
-        if (e->site_mode) return fail(PSSBAM_EINVAL, "the composition table and site context exclude each other");
-        if (e->end_depth) return fail(PSSBAM_EINVAL, "the composition table and the end condition exclude each other");
-        if (e->gapped) return fail(PSSBAM_EINVAL, "the composition table and gapped reads exclude each other");
-        if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "the composition table and the mismatch count exclude each other");
-        if (interior_on(e)) return fail(PSSBAM_EINVAL, "the composition table and the interior table exclude each other");
-        if (read_score_on(e)) return fail(PSSBAM_EINVAL, "the composition table and the read score exclude each other");
+        if (const int rc = check_exclusive(e, MODE_COMPOSITION)) return rc;
     }
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the composition table after create or reset, before the first tally");
-    if ((uint32_t)width != e->composition) {
-        if (const int rc = check_may_resize(e, "the composition table")) return rc;
-        HIP_TRY(hipSetDevice(e->device));
-        // the block grows (or shrinks back) behind everything it holds without the table
-        if (const int rc = grow_counters(e, (uint64_t)e->off_groups + 20ull * (uint64_t)width)) return rc;
-    }
+    if ((uint32_t)width != e->composition)
+        if (const int rc = resize_extra(e, 20ull * (uint64_t)width, "the composition table")) return rc;
     e->composition = (uint32_t)width;
-    e->off_composition = width > 0 ? e->off_groups : 0u;
     return PSSBAM_OK;
 }
 
@@ -1887,8 +1852,8 @@ extern "C" int pssbam_engine_finish_composition(pssbam_engine *e, uint64_t *c5, 
     const int rc = pssbam_engine_sync(e);
     if (rc) return rc;
     const size_t words = 10u * (size_t)e->composition;
-    if (c5) HIP_TRY(hipMemcpy(c5, e->d_counters + e->off_composition, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (c3) HIP_TRY(hipMemcpy(c3, e->d_counters + e->off_composition + words, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (c5) HIP_TRY(hipMemcpy(c5, e->d_counters + e->off_groups, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (c3) HIP_TRY(hipMemcpy(c3, e->d_counters + e->off_groups + words, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return PSSBAM_OK;
 }
 
@@ -1909,19 +1874,9 @@ extern "C" int pssbam_engine_set_read_score(pssbam_engine *e, const int16_t *wei
             return fail(PSSBAM_EINVAL, "the read score filters the reads of the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
         if (e->cfg.pss.region_len > 30)
             return fail(PSSBAM_EINVAL, "the read score needs a region length of at most 30 (the decision is taken in the one pass that holds all rows), not %d", e->cfg.pss.region_len);
-        if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "the read score and replicates exclude each other");
-        if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the read score and read groups / length bins / contig sets / per-contig tables exclude each other");
-        if (e->hist_max) return fail(PSSBAM_EINVAL, "the read score and the length histogram exclude each other");
-        if (e->site_mode) return fail(PSSBAM_EINVAL, "the read score and site context exclude each other");
-        if (e->end_depth) return fail(PSSBAM_EINVAL, "the read score and the end condition exclude each other");
-        if (e->gapped) return fail(PSSBAM_EINVAL, "the read score and gapped reads exclude each other");
-        if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "the read score and the mismatch count exclude each other");
-        if (interior_on(e)) return fail(PSSBAM_EINVAL, "the read score and the interior table exclude each other");
-        if (composition_on(e)) return fail(PSSBAM_EINVAL, "the read score and the composition table exclude each other");
+        if (const int rc = check_exclusive(e, MODE_SCORE)) return rc;
     }
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set the read score after create or reset, before the first tally");
-    if ((uint32_t)hist_half != e->score_half)
-        if (const int rc = check_may_resize(e, "the read-score histogram")) return rc;
     HIP_TRY(hipSetDevice(e->device));
     int16_t *d_w = nullptr;
     if (on) {   // the weights go to the device here; an earlier table may still be named by nothing (nothing has been tallied)
@@ -1932,13 +1887,11 @@ extern "C" int pssbam_engine_set_read_score(pssbam_engine *e, const int16_t *wei
             return fail(PSSBAM_EHIP, "read score: the weights could not be copied to the device");
         }
     }
-    if ((uint32_t)hist_half != e->score_half) {
-        // the block grows (or shrinks back) behind everything it holds without the histogram
-        if (const int rc = grow_counters(e, (uint64_t)e->off_groups + 4ull * (uint64_t)hist_half)) {
+    if ((uint32_t)hist_half != e->score_half)
+        if (const int rc = resize_extra(e, 4ull * (uint64_t)hist_half, "the read-score histogram")) {
             if (d_w) (void)hipFree(d_w);
             return rc;
         }
-    }
     if (e->d_score_w) (void)hipFree(e->d_score_w);
     e->d_score_w = d_w;
     e->score_nd = (uint32_t)n_dist;
@@ -1947,7 +1900,6 @@ extern "C" int pssbam_engine_set_read_score(pssbam_engine *e, const int16_t *wei
     e->score_min = min_score;
     e->score_half = (uint32_t)hist_half;
     e->score_shift = (uint32_t)hist_shift;
-    e->off_score = hist_half ? e->off_groups : 0u;
     return PSSBAM_OK;
 }
 
@@ -1957,8 +1909,8 @@ extern "C" int pssbam_engine_finish_read_score(pssbam_engine *e, uint64_t *fwd, 
     const int rc = pssbam_engine_sync(e);
     if (rc) return rc;
     const size_t n = 2u * (size_t)e->score_half;
-    if (fwd) HIP_TRY(hipMemcpy(fwd, e->d_counters + e->off_score, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (rev) HIP_TRY(hipMemcpy(rev, e->d_counters + e->off_score + n, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (fwd) HIP_TRY(hipMemcpy(fwd, e->d_counters + e->off_groups, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (rev) HIP_TRY(hipMemcpy(rev, e->d_counters + e->off_groups + n, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return PSSBAM_OK;
 }
 
@@ -1967,24 +1919,11 @@ extern "C" int pssbam_engine_set_site_context(pssbam_engine *e, int32_t mode) {
     if (mode != PSSBAM_SITE_NONE && mode != PSSBAM_SITE_CPG) return fail(PSSBAM_EINVAL, "unknown site context %d", mode);
     if (e->cfg.tally_mask != PSSBAM_TALLY_PSS)
         return fail(PSSBAM_EINVAL, "site context splits the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
-    if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "site context and replicates exclude each other");
-    if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "site context and read groups / length bins / contig sets exclude each other");
-    if (e->hist_max) return fail(PSSBAM_EINVAL, "site context and the length histogram exclude each other");
-    if (e->end_depth) return fail(PSSBAM_EINVAL, "site context and the end condition exclude each other");
-    if (e->gapped && mode != PSSBAM_SITE_NONE) return fail(PSSBAM_EINVAL, "site context and gapped reads exclude each other");
-    if (mismatches_on(e) && mode != PSSBAM_SITE_NONE) return fail(PSSBAM_EINVAL, "site context and the mismatch count exclude each other");
-    if (interior_on(e) && mode != PSSBAM_SITE_NONE) return fail(PSSBAM_EINVAL, "site context and the interior table exclude each other");
-    if (composition_on(e) && mode != PSSBAM_SITE_NONE) return fail(PSSBAM_EINVAL, "site context and the composition table exclude each other");
-    if (read_score_on(e) && mode != PSSBAM_SITE_NONE) return fail(PSSBAM_EINVAL, "site context and the read score exclude each other");
-    if (const int rc = check_may_resize(e, "the site context")) return rc;
-    if ((uint32_t)mode == e->site_mode) return PSSBAM_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    // the block grows (or shrinks back) behind everything it holds without the pair
-    const uint64_t n_counters = (uint64_t)e->off_groups + (mode ? 2ull * e->rows * 16ull : 0ull);
-    if (n_counters > 0xFFFFFFFFull) return fail(PSSBAM_EINVAL, "the counter block would pass 2^32 words");
-    if (const int rc = grow_counters(e, n_counters)) return rc;
+    if (mode != PSSBAM_SITE_NONE)
+        if (const int rc = check_exclusive(e, MODE_SITE)) return rc;
+    if ((uint32_t)mode == e->site_mode) return check_may_resize(e, "the site context");
+    if (const int rc = resize_extra(e, mode ? 2ull * e->rows * 16ull : 0ull, "the site context")) return rc;
     e->site_mode = (uint32_t)mode;
-    e->off_site = mode ? e->off_groups : 0u;
     return PSSBAM_OK;
 }
 
@@ -1998,8 +1937,8 @@ extern "C" int pssbam_engine_finish_site_context(pssbam_engine *e, unsigned long
     const size_t tab = (size_t)e->rows * 16;
     // rows 0 and 1 (the context bases) are never masked: they stay zero on the device and are T's here
     for (size_t i = 0; i < tab; i++) {
-        if (fwd_in) fwd_in[i] = (unsigned long)(i < 32 ? h[i] : h[e->off_site + i]);
-        if (rev_in) rev_in[i] = (unsigned long)(i < 32 ? h[e->off_rev + i] : h[e->off_site + tab + i]);
+        if (fwd_in) fwd_in[i] = (unsigned long)(i < 32 ? h[i] : h[e->off_groups + i]);
+        if (rev_in) rev_in[i] = (unsigned long)(i < 32 ? h[e->off_rev + i] : h[e->off_groups + tab + i]);
     }
     return PSSBAM_OK;
 }
@@ -2013,27 +1952,14 @@ extern "C" int pssbam_engine_set_end_condition(pssbam_engine *e, int32_t depth, 
     if (depth > e->cfg.pss.region_len) return fail(PSSBAM_EINVAL, "end condition depth %d beyond the region length %d", depth, e->cfg.pss.region_len);
     if (depth && e->cfg.pss.region_len > 30)
         return fail(PSSBAM_EINVAL, "the end condition needs a region length of at most 30 (one 32-row pass holds both ends' marks), not %d", e->cfg.pss.region_len);
-    if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "the end condition and replicates exclude each other");
-    if (e->planes != PLANES_NONE) return fail(PSSBAM_EINVAL, "the end condition and read groups / length bins / contig sets exclude each other");
-    if (e->hist_max) return fail(PSSBAM_EINVAL, "the end condition and the length histogram exclude each other");
-    if (e->site_mode) return fail(PSSBAM_EINVAL, "the end condition and site context exclude each other");
-    if (e->gapped && depth) return fail(PSSBAM_EINVAL, "the end condition and gapped reads exclude each other");
-    if (mismatches_on(e) && depth) return fail(PSSBAM_EINVAL, "the end condition and the mismatch count exclude each other");
-    if (interior_on(e) && depth) return fail(PSSBAM_EINVAL, "the end condition and the interior table exclude each other");
-    if (composition_on(e) && depth) return fail(PSSBAM_EINVAL, "the end condition and the composition table exclude each other");
-    if (read_score_on(e) && depth) return fail(PSSBAM_EINVAL, "the end condition and the read score exclude each other");
-    if (const int rc = check_may_resize(e, "the end condition")) return rc;
-    if ((uint32_t)depth != e->end_depth) {
-        HIP_TRY(hipSetDevice(e->device));
-        // the block grows (or shrinks back) behind everything it holds without the pair and its read counters
-        const uint64_t n_counters = (uint64_t)e->off_groups + (depth ? 2ull * e->rows * 16ull + 4ull : 0ull);
-        if (n_counters > 0xFFFFFFFFull) return fail(PSSBAM_EINVAL, "the counter block would pass 2^32 words");
-        if (const int rc = grow_counters(e, n_counters)) return rc;
-    }
+    if (depth)
+        if (const int rc = check_exclusive(e, MODE_END)) return rc;
+    // (the pair and its read counters)
+    if (const int rc = (uint32_t)depth != e->end_depth ? resize_extra(e, depth ? 2ull * e->rows * 16ull + 4ull : 0ull, "the end condition")
+                                                       : check_may_resize(e, "the end condition")) return rc;
     e->end_depth = (uint32_t)depth;
     e->end_cell5 = depth ? (uint32_t)cell5 : 0u;
     e->end_cell3 = depth ? (uint32_t)cell3 : 0u;
-    e->off_end = depth ? e->off_groups : 0u;
     return PSSBAM_OK;
 }
 
@@ -2044,7 +1970,7 @@ extern "C" int pssbam_engine_finish_end_condition(pssbam_engine *e, unsigned lon
     if (rc) return rc;
     const size_t tab = (size_t)e->rows * 16;
     std::vector<unsigned long long> h(2 * tab + 4);
-    HIP_TRY(hipMemcpy(h.data(), e->d_counters + e->off_end, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h.data(), e->d_counters + e->off_groups, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < tab; i++) {
         if (fwd_c) fwd_c[i] = (unsigned long)h[i];
         if (rev_c) rev_c[i] = (unsigned long)h[tab + i];
@@ -2057,9 +1983,6 @@ extern "C" int pssbam_engine_set_length_bins(pssbam_engine *e, int32_t n_edges, 
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
     if (n_edges < 1 || n_edges > PSSBAM_MAX_LENGTH_BINS - 1 || !edges)
         return fail(PSSBAM_EINVAL, "length bin edge count %d outside 1..%d", n_edges, PSSBAM_MAX_LENGTH_BINS - 1);
-    if (e->planes == PLANES_RG) return fail(PSSBAM_EINVAL, "length bins and read groups exclude each other");
-    if (e->planes == PLANES_REF) return fail(PSSBAM_EINVAL, "length bins and contig sets exclude each other");
-    if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "length bins and replicates exclude each other");
     // l < e1 < ... < ek <= L: every bin [l, e1-1], [e1, e2-1], ..., [ek, L] is a non-empty -l / -L window
     // (a k-mer engine: the window of fragkon's -l / -L, compared with strlen(SEQ))
     const bool kmer = e->cfg.tally_mask == PSSBAM_TALLY_KMER;
@@ -2070,7 +1993,7 @@ extern "C" int pssbam_engine_set_length_bins(pssbam_engine *e, int32_t n_edges, 
             return fail(PSSBAM_EINVAL, "length bin edge %d (%u) must lie above %llu and at most at %llu", i, edges[i],
                         (unsigned long long)prev, (unsigned long long)hi);
     }
-    const int rc = set_planes(e, PLANES_LEN, (uint32_t)n_edges + 1u, "length bins");
+    const int rc = set_planes(e, PLANES_LEN, MODE_LEN, (uint32_t)n_edges + 1u);
     if (rc) return rc;
     e->len_edges.assign(edges, edges + n_edges);
     return PSSBAM_OK;
@@ -2084,15 +2007,10 @@ extern "C" int pssbam_engine_set_replicates(pssbam_engine *e, int32_t k) {
     if (k) {
         if (e->cfg.tally_mask != PSSBAM_TALLY_PSS)
             return fail(PSSBAM_EINVAL, "replicates split the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
-        if (e->planes == PLANES_RG) return fail(PSSBAM_EINVAL, "replicates and read groups exclude each other");
-        if (e->planes == PLANES_LEN) return fail(PSSBAM_EINVAL, "replicates and length bins exclude each other");
-        if (e->planes == PLANES_REF) return fail(PSSBAM_EINVAL, "replicates and contig sets exclude each other");
-        return set_planes(e, PLANES_HASH, (uint32_t)k, "replicates");   // (per-contig tables, -H, -X, -E, -I, -n / -N: refused there)
+        return set_planes(e, PLANES_HASH, MODE_HASH, (uint32_t)k);   // (the other modes: refused there)
     }
-    if (const int rc = check_may_resize(e, "replicates")) return rc;
-    if (e->planes != PLANES_HASH) return PSSBAM_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    if (const int rc = grow_counters(e, e->off_groups)) return rc;
+    if (e->planes != PLANES_HASH) return check_may_resize(e, "replicates");
+    if (const int rc = resize_extra(e, 0, "replicates")) return rc;
     e->planes = PLANES_NONE;
     e->n_planes = 0;
     return PSSBAM_OK;
@@ -2104,9 +2022,6 @@ extern "C" int pssbam_engine_set_contig_sets(pssbam_engine *e, int32_t n_sets, i
     if (n_sets < 1 || n_sets > PSSBAM_MAX_CONTIG_SETS)
         return fail(PSSBAM_EINVAL, "contig set count %d outside 1..%d", n_sets, PSSBAM_MAX_CONTIG_SETS);
     if (n_names < 0 || (n_names && (!names || !set_of))) return fail(PSSBAM_EINVAL, "bad contig name list");
-    if (e->planes == PLANES_RG) return fail(PSSBAM_EINVAL, "contig sets and read groups exclude each other");
-    if (e->planes == PLANES_LEN) return fail(PSSBAM_EINVAL, "contig sets and length bins exclude each other");
-    if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "contig sets and replicates exclude each other");
     std::unordered_map<std::string, uint32_t> plane;
     plane.reserve((size_t)n_names);
     for (int64_t i = 0; i < n_names; i++) {
@@ -2117,7 +2032,7 @@ extern "C" int pssbam_engine_set_contig_sets(pssbam_engine *e, int32_t n_sets, i
         if (!ins.second && ins.first->second != (uint32_t)set_of[i] + 1u)
             return fail(PSSBAM_EINVAL, "contig %s is given under two sets (%u and %d)", names[i], ins.first->second - 1u, set_of[i]);
     }
-    const int rc = set_planes(e, PLANES_REF, (uint32_t)n_sets, "contig sets");
+    const int rc = set_planes(e, PLANES_REF, MODE_REF, (uint32_t)n_sets);
     if (rc) return rc;
     e->ctg_plane.swap(plane);
     if (!e->have_refs) return PSSBAM_OK;   // set_references packs the planes into ref_info when it comes
@@ -2182,22 +2097,12 @@ extern "C" int pssbam_engine_set_per_contig(pssbam_engine *e, int32_t on) {
     if (on) {
         if (e->cfg.tally_mask != PSSBAM_TALLY_PSS)
             return fail(PSSBAM_EINVAL, "per-contig tables split the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
-        if (e->planes == PLANES_HASH) return fail(PSSBAM_EINVAL, "per-contig tables and replicates exclude each other");
-        if (e->planes != PLANES_NONE && e->planes != PLANES_EACH) return fail(PSSBAM_EINVAL, "per-contig tables and read groups / length bins / contig sets exclude each other");
-        if (e->hist_max) return fail(PSSBAM_EINVAL, "per-contig tables and the length histogram exclude each other");
-        if (e->site_mode) return fail(PSSBAM_EINVAL, "per-contig tables and site context exclude each other");
-        if (e->end_depth) return fail(PSSBAM_EINVAL, "per-contig tables and the end condition exclude each other");
-        if (e->gapped) return fail(PSSBAM_EINVAL, "per-contig tables and gapped reads exclude each other");
-        if (mismatches_on(e)) return fail(PSSBAM_EINVAL, "per-contig tables and the mismatch count exclude each other");
-        if (interior_on(e)) return fail(PSSBAM_EINVAL, "per-contig tables and the interior table exclude each other");
-        if (composition_on(e)) return fail(PSSBAM_EINVAL, "per-contig tables and the composition table exclude each other");
-        if (read_score_on(e)) return fail(PSSBAM_EINVAL, "per-contig tables and the read score exclude each other");
+        if (const int rc = check_exclusive(e, MODE_EACH)) return rc;
     }
     if (const int rc = check_may_resize(e, "per-contig tables")) return rc;
     if ((on != 0) == e->per_contig) return PSSBAM_OK;
-    HIP_TRY(hipSetDevice(e->device));
     if (!on) {   // switched off: the block and the launches of an engine that never had the setting
-        if (const int rc = grow_counters(e, e->off_groups)) return rc;
+        if (const int rc = resize_extra(e, 0, "per-contig tables")) return rc;
         e->per_contig = false;
         e->planes = PLANES_NONE;
         e->n_planes = 0;

@@ -160,11 +160,11 @@ int main(int argc, char *argv[])
     cfg.device = 0;
     cfg.kernel = PSSBAM_KERNEL_AUTO;
 
-    frontend_group_by_rg = by_group;
-    frontend_n_length_edges = n_edges;
-    memcpy(frontend_length_edges, edges, (size_t)n_edges * sizeof *edges);
-    if (ctg_map) frontend_contig_sets = &sets;
-    if (bed_fn) frontend_regions = &bed;
+    frontend_opts.group_by_rg = by_group;
+    frontend_opts.n_length_edges = n_edges;
+    memcpy(frontend_opts.length_edges, edges, (size_t)n_edges * sizeof *edges);
+    if (ctg_map) frontend_opts.contig_sets = &sets;
+    if (bed_fn) frontend_opts.regions = &bed;
     /* HIP start-up, engines and the compressed BAM feed overlap the FASTA load (frontend.c) */
     frontend_warmup_start(&cfg, bam_fn, fasta_fn);
     Genome *genome = init_genome(fasta_fn);

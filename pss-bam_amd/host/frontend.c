@@ -28,22 +28,7 @@
 #include "sam_reader.h"
 
 int frontend_fast_exit = 0;
-int frontend_group_by_rg = 0;
-int frontend_n_length_edges = 0;
-int frontend_min_base_quality = 0;
-int frontend_length_hist = 0;
-int frontend_mismatch_hist = 0, frontend_max_mismatches = -1, frontend_mismatch_tv = 0;
-int frontend_interior = -1;
-int frontend_composition = 0;
-const frontend_score *frontend_read_score = NULL;
-int frontend_site_context = PSSBAM_SITE_NONE;
-int frontend_end_depth = 0, frontend_end_cell5 = 0, frontend_end_cell3 = 0;
-int frontend_gapped_reads = 0;
-int frontend_per_contig = 0;
-int frontend_replicates = 0;
-const pss_regions *frontend_regions = NULL;
-uint32_t frontend_length_edges[PSSBAM_MAX_LENGTH_BINS - 1];
-const frontend_contig_map *frontend_contig_sets = NULL;
+frontend_options frontend_opts = {.max_mismatches = -1, .interior = -1, .site_context = PSSBAM_SITE_NONE};
 
 /* -C: the map on one engine (0 when there is none) */
 static int send_contig_sets(pssbam_engine *e, const frontend_contig_map *m)
@@ -77,21 +62,6 @@ static struct early_feed {
     pssbam_engine *eng[64];
     char **rg_ids;                  /* -G: the BAM header's @RG IDs, set on every engine after create */
     int n_rg;
-    int min_bq;                     /* -Q: the minimum base quality, set on every engine after create */
-    int hist;                       /* -H: the limit of the length histogram, set on every engine after create */
-    int mism_hist, mism_max, mism_tv; /* -N / -n / -V: the mismatch count, set on every engine after create */
-    int interior;                   /* -W: the interior margin, set on every engine after create */
-    int composition;                /* -P: the composition width, set on every engine after create */
-    const frontend_score *score;    /* -y / -Y: the read score, set on every engine after create */
-    int site;                       /* -X: the site context, set on every engine after create */
-    int end_depth, end_cell5, end_cell3; /* -E: the end condition, set on every engine after create */
-    int gapped;                     /* -I: anchored ends, set on every engine after create */
-    int per_contig;                 /* -A: a pair of tables per reference, set on every engine after create (feed_open gave the count) */
-    int replicates;                 /* -J: the read-name replicates, set on every engine after create */
-    const pss_regions *regions;     /* -T: the intervals, set on every engine after create */
-    int n_edges;                    /* -S: the length bin edges, set on every engine after create */
-    uint32_t edges[PSSBAM_MAX_LENGTH_BINS - 1];
-    const frontend_contig_map *sets; /* -C: the map, set on every engine after create */
     int n_gpus, engines_ok, engines_done, fed, feed_rc, genome_set, failed;
     device_feed_stats dfs;
     char err[600];
@@ -167,23 +137,31 @@ static int send_read_score(pssbam_engine *e, const frontend_score *sc)
     return sc && pssbam_engine_set_read_score(e, sc->weights, sc->n_dist, sc->n_qual, sc->use_filter, sc->min_score, sc->hist_half, sc->hist_shift);
 }
 
+/* The run's options (frontend_opts) onto one engine; non-zero: pssbam_last_error() says why.  Two are left to the callers, who
+ * need them at a place of their own: -A (before feed_open on the helper's engines) and -G (the header's @RG IDs).  A new
+ * option is one line here. */
+static int apply_options(pssbam_engine *e)
+{
+    const frontend_options *o = &frontend_opts;
+    return (o->min_base_quality > 0 && pssbam_engine_set_min_base_quality(e, o->min_base_quality)) ||
+           (o->length_hist > 0 && pssbam_engine_set_length_histogram(e, o->length_hist)) ||
+           ((o->mismatch_hist > 0 || o->max_mismatches >= 0) && pssbam_engine_set_mismatches(e, o->mismatch_hist, o->max_mismatches, o->mismatch_tv)) ||
+           (o->interior >= 0 && pssbam_engine_set_interior(e, o->interior)) ||
+           (o->composition > 0 && pssbam_engine_set_composition(e, o->composition)) || send_read_score(e, o->read_score) ||
+           (o->site_context != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(e, o->site_context)) ||
+           (o->end_depth > 0 && pssbam_engine_set_end_condition(e, o->end_depth, o->end_cell5, o->end_cell3)) ||
+           (o->gapped_reads && pssbam_engine_set_gapped_reads(e, 1)) || send_regions(e, o->regions) ||
+           (o->n_length_edges > 0 && pssbam_engine_set_length_bins(e, o->n_length_edges, o->length_edges)) ||
+           send_contig_sets(e, o->contig_sets) || (o->replicates > 0 && pssbam_engine_set_replicates(e, o->replicates));
+}
+
 static void *engine_make_main(void *arg)
 {
     engine_make_job *j = (engine_make_job *)arg;
     /* (-A before feed_open: the planes are sized from its n_ref before the feed works out what memory it may take) */
-    if (pssbam_engine_create(&j->cfg, j->out) || (EF.per_contig && pssbam_engine_set_per_contig(*j->out, 1)) ||
-        pssbam_engine_feed_open(*j->out, j->n_ref, EF.fasta_bytes) ||
-        (EF.min_bq > 0 && pssbam_engine_set_min_base_quality(*j->out, EF.min_bq)) ||
-        (EF.hist > 0 && pssbam_engine_set_length_histogram(*j->out, EF.hist)) ||
-        ((EF.mism_hist > 0 || EF.mism_max >= 0) && pssbam_engine_set_mismatches(*j->out, EF.mism_hist, EF.mism_max, EF.mism_tv)) ||
-        (EF.interior >= 0 && pssbam_engine_set_interior(*j->out, EF.interior)) ||
-        (EF.composition > 0 && pssbam_engine_set_composition(*j->out, EF.composition)) || send_read_score(*j->out, EF.score) ||
-        (EF.site != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(*j->out, EF.site)) ||
-        (EF.end_depth > 0 && pssbam_engine_set_end_condition(*j->out, EF.end_depth, EF.end_cell5, EF.end_cell3)) ||
-        (EF.gapped && pssbam_engine_set_gapped_reads(*j->out, 1)) || send_regions(*j->out, EF.regions) ||
-        (EF.n_rg > 0 && pssbam_engine_set_read_groups(*j->out, EF.n_rg, (const char *const *)EF.rg_ids)) ||
-        (EF.n_edges > 0 && pssbam_engine_set_length_bins(*j->out, EF.n_edges, EF.edges)) || send_contig_sets(*j->out, EF.sets) ||
-        (EF.replicates > 0 && pssbam_engine_set_replicates(*j->out, EF.replicates))) {
+    if (pssbam_engine_create(&j->cfg, j->out) || (frontend_opts.per_contig && pssbam_engine_set_per_contig(*j->out, 1)) ||
+        pssbam_engine_feed_open(*j->out, j->n_ref, EF.fasta_bytes) || apply_options(*j->out) ||
+        (EF.n_rg > 0 && pssbam_engine_set_read_groups(*j->out, EF.n_rg, (const char *const *)EF.rg_ids))) {
         j->rc = 1;
         snprintf(j->err, sizeof j->err, "%s", pssbam_last_error());   /* (the message is this thread's) */
     }
@@ -205,7 +183,7 @@ static void early_feed_main(void)
     pthread_t pin_th;
     const int pin_started = pthread_create(&pin_th, NULL, pin_main, NULL) == 0;
     const bam_header *h = bam_reader_header(early_rd);
-    if (frontend_group_by_rg && (EF.n_rg = pss_parse_read_groups(h->text, h->l_text, &EF.rg_ids)) < 0) EF.n_rg = 0;
+    if (frontend_opts.group_by_rg && (EF.n_rg = pss_parse_read_groups(h->text, h->l_text, &EF.rg_ids)) < 0) EF.n_rg = 0;
     /* one engine per GPU, all created at once: a device's first touch (context, queues, code objects) takes ~0.08 s, and
      * eight of them one after the other would cost more than the whole command does on one GPU */
     engine_make_job job[64];
@@ -307,25 +285,6 @@ void frontend_warmup_start(const pssbam_config *cfg, const char *aln_path, const
         if (early_rd && early_light && cfg && !getenv("PSSBAM_NO_EARLY_FEED")) {
             EF.want = 1;
             EF.cfg = *cfg;
-            EF.n_edges = frontend_n_length_edges;
-            EF.min_bq = frontend_min_base_quality;
-            EF.hist = frontend_length_hist;
-            EF.mism_hist = frontend_mismatch_hist;
-            EF.mism_max = frontend_max_mismatches;
-            EF.mism_tv = frontend_mismatch_tv;
-            EF.interior = frontend_interior;
-            EF.composition = frontend_composition;
-            EF.score = frontend_read_score;
-            EF.site = frontend_site_context;
-            EF.end_depth = frontend_end_depth;
-            EF.end_cell5 = frontend_end_cell5;
-            EF.end_cell3 = frontend_end_cell3;
-            EF.gapped = frontend_gapped_reads;
-            EF.per_contig = frontend_per_contig;
-            EF.replicates = frontend_replicates;
-            EF.regions = frontend_regions;
-            memcpy(EF.edges, frontend_length_edges, sizeof EF.edges);
-            EF.sets = frontend_contig_sets;
             EF.cfg.pss.up_ctx = EF.up = dup_or_null(cfg->pss.up_ctx);
             EF.cfg.pss.down_ctx = EF.down = dup_or_null(cfg->pss.down_ctx);
             EF.cfg.read_group = EF.rg = dup_or_null(cfg->read_group);
@@ -338,18 +297,6 @@ void frontend_warmup_start(const pssbam_config *cfg, const char *aln_path, const
 }
 
 static int same_str(const char *a, const char *b) { return (!a && !b) || (a && b && strcmp(a, b) == 0); }
-
-/* the helper's engines carry the length bins, contig sets, minimum base quality and regions that were set when it started */
-static int same_length_bins(void)
-{
-    return EF.n_edges == frontend_n_length_edges && EF.sets == frontend_contig_sets && EF.min_bq == frontend_min_base_quality &&
-           EF.hist == frontend_length_hist && EF.site == frontend_site_context && EF.interior == frontend_interior && EF.composition == frontend_composition &&
-           EF.score == frontend_read_score &&
-           EF.mism_hist == frontend_mismatch_hist && EF.mism_max == frontend_max_mismatches && EF.mism_tv == frontend_mismatch_tv &&
-           EF.end_depth == frontend_end_depth && EF.end_cell5 == frontend_end_cell5 && EF.end_cell3 == frontend_end_cell3 &&
-           EF.gapped == frontend_gapped_reads && EF.per_contig == frontend_per_contig && EF.replicates == frontend_replicates && EF.regions == frontend_regions &&
-           memcmp(EF.edges, frontend_length_edges, (size_t)frontend_n_length_edges * sizeof *EF.edges) == 0;
-}
 
 static int same_config(const pssbam_config *a, const pssbam_config *b)
 {
@@ -589,7 +536,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
     int fed_on_device = 0, adopted = 0, light = 0;
     int device_feed = is_bam && device_feed_enabled() && cfg->kernel != PSSBAM_KERNEL_SIMPLE;
     if (warmup_running) { /* HIP is needed from here on; the helper thread may be feeding already */
-        const int mine = EF.want && is_bam && strcmp(early_path, aln_path) == 0 && same_config(cfg, &EF.cfg) && same_length_bins() && device_feed;
+        const int mine = EF.want && is_bam && strcmp(early_path, aln_path) == 0 && same_config(cfg, &EF.cfg) && device_feed;
         if (EF.want) {
             int upload_ok = 0;
             if (mine) { /* the engines exist a few dozen ms after the runtime is up: normally long before the FASTA is in */
@@ -674,7 +621,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
         }
         refs_sent = bam_reader_header(rd)->n_ref;
         dfs = EF.dfs;
-        if (frontend_group_by_rg) { /* the helper set these IDs on its engines */
+        if (frontend_opts.group_by_rg) { /* the helper set these IDs on its engines */
             res->n_planes = EF.n_rg;
             res->group_ids = EF.rg_ids;
             EF.rg_ids = NULL;
@@ -689,22 +636,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             pssbam_config c = *cfg;
             const int have = pssbam_device_count();
             c.device = have > 0 ? g % have : g;
-            if (pssbam_engine_create(&c, &eng[g]) ||
-                (frontend_min_base_quality > 0 && pssbam_engine_set_min_base_quality(eng[g], frontend_min_base_quality)) ||
-                (frontend_length_hist > 0 && pssbam_engine_set_length_histogram(eng[g], frontend_length_hist)) ||
-                ((frontend_mismatch_hist > 0 || frontend_max_mismatches >= 0) &&
-                 pssbam_engine_set_mismatches(eng[g], frontend_mismatch_hist, frontend_max_mismatches, frontend_mismatch_tv)) ||
-                (frontend_interior >= 0 && pssbam_engine_set_interior(eng[g], frontend_interior)) ||
-                (frontend_composition > 0 && pssbam_engine_set_composition(eng[g], frontend_composition)) ||
-                send_read_score(eng[g], frontend_read_score) ||
-                (frontend_site_context != PSSBAM_SITE_NONE && pssbam_engine_set_site_context(eng[g], frontend_site_context)) ||
-                (frontend_end_depth > 0 && pssbam_engine_set_end_condition(eng[g], frontend_end_depth, frontend_end_cell5, frontend_end_cell3)) ||
-                (frontend_gapped_reads && pssbam_engine_set_gapped_reads(eng[g], 1)) ||
-                (frontend_per_contig && pssbam_engine_set_per_contig(eng[g], 1)) ||
-                send_regions(eng[g], frontend_regions) ||
-                (frontend_n_length_edges > 0 && pssbam_engine_set_length_bins(eng[g], frontend_n_length_edges, frontend_length_edges)) ||
-                send_contig_sets(eng[g], frontend_contig_sets) ||
-                (frontend_replicates > 0 && pssbam_engine_set_replicates(eng[g], frontend_replicates))) {
+            if (pssbam_engine_create(&c, &eng[g]) || (frontend_opts.per_contig && pssbam_engine_set_per_contig(eng[g], 1)) || apply_options(eng[g])) {
                 fprintf(stderr, "Error: GPU engine %d: %s\n", g, pssbam_last_error());
                 goto done;
             }
@@ -716,10 +648,10 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
                 goto done;
             }
         /* -G on BAM input: the header is known now (SAM text: once its header lines have been read, below) */
-        if (frontend_group_by_rg && rd && send_read_groups(eng, n_gpus, bam_reader_header(rd)->text, bam_reader_header(rd)->l_text, res))
+        if (frontend_opts.group_by_rg && rd && send_read_groups(eng, n_gpus, bam_reader_header(rd)->text, bam_reader_header(rd)->l_text, res))
             goto done;
     }
-    int groups_sent = !frontend_group_by_rg || rd != NULL;
+    int groups_sent = !frontend_opts.group_by_rg || rd != NULL;
     t_engine = now_s() - t_mark; t_mark = now_s();
     if (device_feed && rd && !adopted) {
         const bam_header *h = bam_reader_header(rd);
@@ -881,8 +813,8 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
         fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
         goto done;
     }
-    if (frontend_length_hist > 0 && (cfg->tally_mask & PSSBAM_TALLY_PSS)) { /* -H: summed with the rest of the block */
-        res->hist_max = frontend_length_hist;
+    if (frontend_opts.length_hist > 0 && (cfg->tally_mask & PSSBAM_TALLY_PSS)) { /* -H: summed with the rest of the block */
+        res->hist_max = frontend_opts.length_hist;
         res->hist_fwd = (uint64_t *)calloc((size_t)res->hist_max + 2, sizeof(uint64_t));
         res->hist_rev = (uint64_t *)calloc((size_t)res->hist_max + 2, sizeof(uint64_t));
         if (!res->hist_fwd || !res->hist_rev) { fprintf(stderr, "Error: out of memory\n"); goto done; }
@@ -891,8 +823,8 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             goto done;
         }
     }
-    if (frontend_mismatch_hist > 0 && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -N: summed with the rest of the block */
-        res->mism_max = frontend_mismatch_hist;
+    if (frontend_opts.mismatch_hist > 0 && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -N: summed with the rest of the block */
+        res->mism_max = frontend_opts.mismatch_hist;
         res->mism_fwd = (uint64_t *)calloc((size_t)res->mism_max + 2, sizeof(uint64_t));
         res->mism_rev = (uint64_t *)calloc((size_t)res->mism_max + 2, sizeof(uint64_t));
         if (!res->mism_fwd || !res->mism_rev) { fprintf(stderr, "Error: out of memory\n"); goto done; }
@@ -901,15 +833,15 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             goto done;
         }
     }
-    if (frontend_interior >= 0 && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -W: summed with the rest of the block */
+    if (frontend_opts.interior >= 0 && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -W: summed with the rest of the block */
         if (pssbam_engine_finish_interior(eng[0], res->interior, &res->interior_reads)) {
             fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
             goto done;
         }
         res->has_interior = 1;
     }
-    if (frontend_composition > 0 && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -P: summed with the rest of the block */
-        const size_t words = (size_t)frontend_composition * 10;
+    if (frontend_opts.composition > 0 && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -P: summed with the rest of the block */
+        const size_t words = (size_t)frontend_opts.composition * 10;
         res->comp5 = (uint64_t *)calloc(words, sizeof(uint64_t));
         res->comp3 = (uint64_t *)calloc(words, sizeof(uint64_t));
         if (!res->comp5 || !res->comp3) {
@@ -920,10 +852,10 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
             goto done;
         }
-        res->composition_width = frontend_composition;
+        res->composition_width = frontend_opts.composition;
     }
-    if (frontend_read_score && frontend_read_score->hist_half > 0 && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -Y: summed with the rest of the block */
-        res->score_half = frontend_read_score->hist_half;
+    if (frontend_opts.read_score && frontend_opts.read_score->hist_half > 0 && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -Y: summed with the rest of the block */
+        res->score_half = frontend_opts.read_score->hist_half;
         res->score_fwd = (uint64_t *)calloc(2 * (size_t)res->score_half, sizeof(uint64_t));
         res->score_rev = (uint64_t *)calloc(2 * (size_t)res->score_half, sizeof(uint64_t));
         if (!res->score_fwd || !res->score_rev) { fprintf(stderr, "Error: out of memory\n"); goto done; }
@@ -932,7 +864,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             goto done;
         }
     }
-    if (frontend_site_context != PSSBAM_SITE_NONE && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -X: summed with the rest of the block */
+    if (frontend_opts.site_context != PSSBAM_SITE_NONE && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -X: summed with the rest of the block */
         const size_t cells = (size_t)(cfg->pss.region_len + 2) * 16;
         res->site_fwd = (unsigned long *)calloc(cells, sizeof(unsigned long));
         res->site_rev = (unsigned long *)calloc(cells, sizeof(unsigned long));
@@ -942,7 +874,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             goto done;
         }
     }
-    if (frontend_end_depth > 0 && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -E: summed with the rest of the block */
+    if (frontend_opts.end_depth > 0 && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -E: summed with the rest of the block */
         const size_t cells = (size_t)(cfg->pss.region_len + 2) * 16;
         res->end_fwd = (unsigned long *)calloc(cells, sizeof(unsigned long));
         res->end_rev = (unsigned long *)calloc(cells, sizeof(unsigned long));
@@ -952,7 +884,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             goto done;
         }
     }
-    if (frontend_per_contig && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -A: the planes that hold something (the touched words were summed with the block) */
+    if (frontend_opts.per_contig && cfg->tally_mask == PSSBAM_TALLY_PSS) { /* -A: the planes that hold something (the touched words were summed with the block) */
         const int32_t n_ref = rd ? bam_reader_header(rd)->n_ref : sam_reader_n_ref(sd);
         const char *const *names = rd ? (const char *const *)bam_reader_header(rd)->ref_name : sam_reader_ref_names(sd);
         const size_t cells = (size_t)(cfg->pss.region_len + 2) * 16;
@@ -984,11 +916,11 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
         res->n_contigs = (int)n_touched;
         free(touched);
     }
-    if (frontend_n_length_edges > 0) res->n_planes = frontend_n_length_edges + 1; /* -G: set with the IDs */
-    if (frontend_replicates > 0) res->n_planes = frontend_replicates; /* -J */
-    if (frontend_contig_sets) {
-        res->n_planes = frontend_contig_sets->n_labels;
-        warn_unreached_sets(frontend_contig_sets, genome, rd ? bam_reader_header(rd)->n_ref : sam_reader_n_ref(sd),
+    if (frontend_opts.n_length_edges > 0) res->n_planes = frontend_opts.n_length_edges + 1; /* -G: set with the IDs */
+    if (frontend_opts.replicates > 0) res->n_planes = frontend_opts.replicates; /* -J */
+    if (frontend_opts.contig_sets) {
+        res->n_planes = frontend_opts.contig_sets->n_labels;
+        warn_unreached_sets(frontend_opts.contig_sets, genome, rd ? bam_reader_header(rd)->n_ref : sam_reader_n_ref(sd),
                             rd ? (const char *const *)bam_reader_header(rd)->ref_name : sam_reader_ref_names(sd), aln_path);
     }
     if (res->n_planes > 0 && cfg->tally_mask == PSSBAM_TALLY_KMER) {

@@ -16,122 +16,114 @@ typedef struct run_result {
     double inflate_s, total_s;
     int n_gpus;
     /* pss-bam -G / -S / -C: the tables of each plane of the engine, (region_len+2)*16 per plane; plane k is the
-     * header's k-th @RG ID (frontend_group_by_rg, group_ids[k]), length bin k (frontend_length_edges, group_ids
-     * NULL) or the k-th label of frontend_contig_sets (group_ids NULL); pss-bam -J: replicate k (frontend_replicates,
+     * header's k-th @RG ID (frontend_opts.group_by_rg, group_ids[k]), length bin k (frontend_opts.length_edges, group_ids
+     * NULL) or the k-th label of frontend_opts.contig_sets (group_ids NULL); pss-bam -J: replicate k (frontend_opts.replicates,
      * group_ids NULL) */
     int n_planes;
     char **group_ids;
     unsigned long *plane_fwd, *plane_rev;
     /* fragkon -G / -S / -C (a PSSBAM_TALLY_KMER engine): the planes' k-mer tables instead, 4^klen per plane */
     uint64_t *plane_k5, *plane_k3;
-    /* pss-bam -H (frontend_length_hist): the fragment-length histogram of the reads added to the forward / reverse
+    /* pss-bam -H (frontend_opts.length_hist): the fragment-length histogram of the reads added to the forward / reverse
      * table, hist_max + 2 rows each (row hist_max + 1: every longer read), or NULL */
     int hist_max;
     uint64_t *hist_fwd, *hist_rev;
-    /* pss-bam -N (frontend_mismatch_hist): the mismatch histogram of the reads added to the forward / reverse table,
+    /* pss-bam -N (frontend_opts.mismatch_hist): the mismatch histogram of the reads added to the forward / reverse table,
      * mism_max + 2 rows each (row mism_max + 1: every larger count), or NULL */
     int mism_max;
     uint64_t *mism_fwd, *mism_rev;
-    /* pss-bam -W (frontend_interior): the interior table and the number of reads that have an interior (has_interior: filled) */
+    /* pss-bam -W (frontend_opts.interior): the interior table and the number of reads that have an interior (has_interior: filled) */
     int has_interior;
     uint64_t interior[16], interior_reads;
-    /* pss-bam -P (frontend_composition): the two blocks of the composition table, 2 * composition_width rows of five counts
+    /* pss-bam -P (frontend_opts.composition): the two blocks of the composition table, 2 * composition_width rows of five counts
      * each (malloc'ed), or NULL */
     int composition_width;
     uint64_t *comp5, *comp3;
-    /* pss-bam -Y (frontend_read_score with a histogram): the score histogram of the reads added to the forward / reverse
+    /* pss-bam -Y (frontend_opts.read_score with a histogram): the score histogram of the reads added to the forward / reverse
      * table, 2 * score_half rows each, or NULL */
     int score_half;
     uint64_t *score_fwd, *score_rev;
-    /* pss-bam -X (frontend_site_context): the in-context tables IN, (region_len+2)*16 each with rows 0/1 as fwd / rev,
+    /* pss-bam -X (frontend_opts.site_context): the in-context tables IN, (region_len+2)*16 each with rows 0/1 as fwd / rev,
      * or NULL */
     unsigned long *site_fwd, *site_rev;
-    /* pss-bam -E (frontend_end_depth): the conditional tables COND, (region_len+2)*16 each, or NULL, and reads[4] */
+    /* pss-bam -E (frontend_opts.end_depth): the conditional tables COND, (region_len+2)*16 each, or NULL, and reads[4] */
     unsigned long *end_fwd, *end_rev;
     uint64_t end_reads[4];
-    /* pss-bam -A (frontend_per_contig): the tables of every reference that holds something, in header order (the refID -1
+    /* pss-bam -A (frontend_opts.per_contig): the tables of every reference that holds something, in header order (the refID -1
      * records last, under the name "*"): n_contigs names and tables of (region_len+2)*16 each */
     int n_contigs;
     char **contig_names;
     unsigned long *contig_fwd, *contig_rev;
 } run_result;
 
-/* pss-bam -G: every engine gets the input header's @RG IDs (pssbam_engine_set_read_groups) and run_tally()
- * returns one pair of tables per ID beside the totals.  Set before frontend_warmup_start. */
-extern int frontend_group_by_rg;
-
-/* pss-bam -Q: the minimum base quality (0: off); every engine gets it (pssbam_engine_set_min_base_quality).  Set
- * before frontend_warmup_start. */
-extern int frontend_min_base_quality;
-
-/* pss-bam -H: the limit of the fragment-length histogram (0: off); every engine gets it
- * (pssbam_engine_set_length_histogram) and run_tally() returns the two arrays.  Set before frontend_warmup_start. */
-extern int frontend_length_hist;
-
-/* pss-bam -N / -n / -V: the limit of the mismatch histogram (0: off), the largest mismatch count of a tallied read (-1: no
- * filter) and whether only transversions count; every engine gets them (pssbam_engine_set_mismatches) and run_tally()
- * returns the two arrays of the histogram.  Set before frontend_warmup_start. */
-extern int frontend_mismatch_hist, frontend_max_mismatches, frontend_mismatch_tv;
-
-/* pss-bam -W: the interior margin (-1: off); every engine gets it (pssbam_engine_set_interior) and run_tally() returns the
- * table and its read count.  Set before frontend_warmup_start. */
-extern int frontend_interior;
-
-/* pss-bam -P: the width of the composition table (0: off); every engine gets it (pssbam_engine_set_composition) and
- * run_tally() returns the two blocks.  Set before frontend_warmup_start. */
-extern int frontend_composition;
-
-/* pss-bam -y / -Y: the read score (NULL: off) -- the weight table [4][n_dist][n_qual], the filter (use_filter: only reads with a
- * score of at least min_score are tallied) and the histogram (hist_half = 0: none); every engine gets it
- * (pssbam_engine_set_read_score) and run_tally() returns the two arrays of the histogram.  Set before frontend_warmup_start;
- * the pointer is kept. */
+/* -y / -Y: the weight table [4][n_dist][n_qual], the filter (use_filter: only reads with a score of at least min_score are
+ * tallied) and the histogram (hist_half = 0: none) */
 typedef struct frontend_score {
     const int16_t *weights;
     int n_dist, n_qual, use_filter, min_score, hist_half, hist_shift;
 } frontend_score;
-extern const frontend_score *frontend_read_score;
 
-/* pss-bam -X: the site context (PSSBAM_SITE_*; PSSBAM_SITE_NONE: off); every engine gets it
- * (pssbam_engine_set_site_context) and run_tally() returns the in-context pair.  Set before frontend_warmup_start. */
-extern int frontend_site_context;
-
-/* pss-bam -E: the end condition (depth 0: off) and its two cells; every engine gets them
- * (pssbam_engine_set_end_condition) and run_tally() returns the conditional pair and reads[4].  Set before
- * frontend_warmup_start. */
-extern int frontend_end_depth, frontend_end_cell5, frontend_end_cell3;
-/* pss-bam -I: non-zero = every engine tallies clipped and gapped reads by their anchored ends
- * (pssbam_engine_set_gapped_reads).  Set before frontend_warmup_start(). */
-extern int frontend_gapped_reads;
-
-/* pss-bam -A: non-zero = every engine keeps a pair of tables per reference (pssbam_engine_set_per_contig) and run_tally()
- * returns those that hold something.  Set before frontend_warmup_start(). */
-extern int frontend_per_contig;
-
-/* pss-bam -J: the number of read-name replicates (0: off); every engine gets it (pssbam_engine_set_replicates) and
- * run_tally() returns one pair of tables per replicate in plane_fwd / plane_rev (n_planes = the count, group_ids NULL),
- * summed over the GPUs with the rest of the counter block.  Set before frontend_warmup_start. */
-extern int frontend_replicates;
-
-/* -T: the intervals of the BED file (regions.h; NULL: none); every engine gets them (pssbam_engine_set_regions), on
- * every input path -- the filter lives in the engine.  Set before frontend_warmup_start. */
-extern const pss_regions *frontend_regions;
-
-/* pss-bam -S: the edges of the length bins (frontend_n_length_edges = 0: none); every engine gets them
- * (pssbam_engine_set_length_bins) and run_tally() returns one pair of tables per bin.  Set before
- * frontend_warmup_start. */
-extern int frontend_n_length_edges;
-extern uint32_t frontend_length_edges[PSSBAM_MAX_LENGTH_BINS - 1];
-
-/* pss-bam -C: the contig -> set map (contig_sets.h; NULL: none); every engine gets it
- * (pssbam_engine_set_contig_sets) and run_tally() returns one pair of tables per label, and warns on stderr
- * about a label none of whose contigs is both in the input's references and in the genome.  Set before
- * frontend_warmup_start. */
+/* -C: the contig -> set map (contig_sets.h) */
 typedef struct frontend_contig_map {
     int n_names, n_labels;
     char **names, **labels;
     int32_t *set_of;
 } frontend_contig_map;
-extern const frontend_contig_map *frontend_contig_sets;
+
+/* The tally options of a run: main() fills frontend_opts before frontend_warmup_start and leaves it alone from then on (the
+ * helper thread and run_tally() read it; the pointers are kept).  Every engine of the run gets them (apply_options in
+ * frontend.c). */
+typedef struct frontend_options {
+    /* pss-bam -G: every engine gets the input header's @RG IDs (pssbam_engine_set_read_groups) and run_tally()
+     * returns one pair of tables per ID beside the totals. */
+    int group_by_rg;
+    /* pss-bam -S: the edges of the length bins (n_length_edges = 0: none); every engine gets them
+     * (pssbam_engine_set_length_bins) and run_tally() returns one pair of tables per bin. */
+    int n_length_edges;
+    uint32_t length_edges[PSSBAM_MAX_LENGTH_BINS - 1];
+    /* pss-bam -C: the contig -> set map (NULL: none); every engine gets it (pssbam_engine_set_contig_sets) and run_tally()
+     * returns one pair of tables per label, and warns on stderr about a label none of whose contigs is both in the input's
+     * references and in the genome. */
+    const frontend_contig_map *contig_sets;
+    /* pss-bam -Q: the minimum base quality (0: off); every engine gets it (pssbam_engine_set_min_base_quality). */
+    int min_base_quality;
+    /* pss-bam -H: the limit of the fragment-length histogram (0: off); every engine gets it
+     * (pssbam_engine_set_length_histogram) and run_tally() returns the two arrays. */
+    int length_hist;
+    /* pss-bam -N / -n / -V: the limit of the mismatch histogram (0: off), the largest mismatch count of a tallied read (-1: no
+     * filter) and whether only transversions count; every engine gets them (pssbam_engine_set_mismatches) and run_tally()
+     * returns the two arrays of the histogram. */
+    int mismatch_hist, max_mismatches, mismatch_tv;
+    /* pss-bam -W: the interior margin (-1: off); every engine gets it (pssbam_engine_set_interior) and run_tally() returns the
+     * table and its read count. */
+    int interior;
+    /* pss-bam -P: the width of the composition table (0: off); every engine gets it (pssbam_engine_set_composition) and
+     * run_tally() returns the two blocks. */
+    int composition;
+    /* pss-bam -y / -Y: the read score (NULL: off); every engine gets it (pssbam_engine_set_read_score) and run_tally() returns
+     * the two arrays of the histogram. */
+    const frontend_score *read_score;
+    /* pss-bam -X: the site context (PSSBAM_SITE_*; PSSBAM_SITE_NONE: off); every engine gets it
+     * (pssbam_engine_set_site_context) and run_tally() returns the in-context pair. */
+    int site_context;
+    /* pss-bam -E: the end condition (depth 0: off) and its two cells; every engine gets them
+     * (pssbam_engine_set_end_condition) and run_tally() returns the conditional pair and reads[4]. */
+    int end_depth, end_cell5, end_cell3;
+    /* pss-bam -I: non-zero = every engine tallies clipped and gapped reads by their anchored ends
+     * (pssbam_engine_set_gapped_reads). */
+    int gapped_reads;
+    /* pss-bam -A: non-zero = every engine keeps a pair of tables per reference (pssbam_engine_set_per_contig) and run_tally()
+     * returns those that hold something. */
+    int per_contig;
+    /* pss-bam -J: the number of read-name replicates (0: off); every engine gets it (pssbam_engine_set_replicates) and
+     * run_tally() returns one pair of tables per replicate in plane_fwd / plane_rev (n_planes = the count, group_ids NULL),
+     * summed over the GPUs with the rest of the counter block. */
+    int replicates;
+    /* -T: the intervals of the BED file (regions.h; NULL: none); every engine gets them (pssbam_engine_set_regions), on
+     * every input path -- the filter lives in the engine. */
+    const pss_regions *regions;
+} frontend_options;
+extern frontend_options frontend_opts;   /* everything off */
 
 /* Streams every alignment of `aln_path` (BGZF BAM, or SAM text plain/gzip) through engines built from `cfg` on
  * n_gpus devices (batches dealt round-robin), sums the counter blocks onto device 0 with

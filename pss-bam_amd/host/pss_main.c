@@ -98,6 +98,14 @@
 #include "replicates.h"
 #include "report.h"
 
+/* the options' names in the messages, each spelt once */
+static const char L_G[] = "-G (tables per read group)", L_S[] = "-S (tables per length bin)", L_C[] = "-C (tables per contig set)",
+                  L_H[] = "-H (fragment-length histogram)", L_X[] = "-X (tables per site context)", L_E[] = "-E (tables conditional on the other end)",
+                  L_I[] = "-I (clipped and gapped reads by their anchored ends)", L_A[] = "-A (tables per contig)", L_n[] = "-n (mismatch filter)",
+                  L_N[] = "-N (mismatch histogram)", L_V[] = "-V (count only transversions)", L_J[] = "-J (jackknife replicates)",
+                  L_W[] = "-W (read-interior table)", L_P[] = "-P (base composition around the read ends)", L_y[] = "-y (damage-score filter)",
+                  L_Y[] = "-Y (damage-score histogram)";
+
 int main(int argc, char *argv[])
 {
     const double age_main = frontend_process_age_s();
@@ -188,16 +196,58 @@ int main(int argc, char *argv[])
         exit(1);
     }
     if (by_group && read_group) {
-        fprintf(stderr, "-G (tables per read group) and -R (one read group) exclude each other.\n");
+        fprintf(stderr, "%s and -R (one read group) exclude each other.\n", L_G);
         exit(1);
+    }
+    if (site_arg && strcmp(site_arg, "cpg") != 0) {
+        fprintf(stderr, "%s: unknown context \"%s\"; the one context is cpg.\n", L_X, site_arg);
+        exit(1);
+    }
+    int end_depth = 0, end_cell5 = 0, end_cell3 = 0;
+    if (end_arg) {   /* (the one value that is parsed before the exclusive options are checked) */
+        char err[200];
+        if (pss_parse_end_condition(end_arg, &end_depth, &end_cell5, &end_cell3, err, sizeof err)) {
+            fprintf(stderr, "%s\n", err);
+            exit(1);
+        }
+    }
+    if (tv_only && !max_mm_arg && !mm_hist_arg && !rep_arg) {
+        fprintf(stderr, "%s needs %s or %s.\n", L_V, L_n, L_N);
+        exit(1);
+    }
+    /* The exclusive options: at most one row may be given (their tables share the words behind the engine's planes, and
+     * one pass over 32 table rows).  Of two, the later row is named first, by all it was given with, the earlier one by
+     * its first option.  A new option is one row here. */
+    const char *mism_one = max_mm_arg ? L_n : mm_hist_arg ? L_N : L_V, *score_one = min_score_arg ? L_y : L_Y;
+    const char *mism_all = max_mm_arg && mm_hist_arg ? "-n / -N (mismatch filter and histogram)" : mism_one;
+    const char *score_all = min_score_arg && score_hist ? "-y / -Y (damage-score filter and histogram)" : score_one;
+    const struct { int given; const char *mine, *other; } exclusive[] = {
+        {by_group, L_G, L_G},
+        {len_edges != NULL, L_S, L_S},
+        {ctg_map != NULL, L_C, L_C},
+        {hist_arg != NULL, L_H, L_H},
+        {site_arg != NULL, L_X, L_X},
+        {end_arg != NULL, L_E, L_E},
+        {gapped, L_I, L_I},
+        {per_contig, L_A, L_A},
+        {max_mm_arg || mm_hist_arg || tv_only, mism_all, mism_one},
+        {rep_arg != NULL, L_J, L_J},
+        {interior_arg != NULL, L_W, L_W},
+        {comp_arg != NULL, L_P, L_P},
+        {min_score_arg || score_hist, score_all, score_one},
+    };
+    const char *other = NULL;
+    for (size_t i = 0; i < sizeof exclusive / sizeof *exclusive; i++) {
+        if (!exclusive[i].given) continue;
+        if (other) {
+            fprintf(stderr, "%s and %s exclude each other.\n", exclusive[i].mine, other);
+            exit(1);
+        }
+        other = exclusive[i].other;
     }
     uint32_t edges[PSSBAM_MAX_LENGTH_BINS - 1];
     int n_edges = 0;
     if (len_edges) {
-        if (by_group) {
-            fprintf(stderr, "-S (tables per length bin) and -G (tables per read group) exclude each other.\n");
-            exit(1);
-        }
         char err[200];
         if ((n_edges = pss_parse_length_edges(len_edges, min_read_len, max_read_len, edges, err, sizeof err)) < 0) {
             fprintf(stderr, "%s\n", err);
@@ -214,72 +264,19 @@ int main(int argc, char *argv[])
     }
     int hist_max = 0;
     if (hist_arg) {
-        if (by_group || len_edges || ctg_map) {
-            fprintf(stderr, "-H (fragment-length histogram) and %s exclude each other.\n",
-                    by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)" : "-C (tables per contig set)");
-            exit(1);
-        }
         char err[200];
         if ((hist_max = pss_parse_length_hist(hist_arg, err, sizeof err)) < 0) {
             fprintf(stderr, "%s\n", err);
             exit(1);
         }
     }
-    if (site_arg) {
-        if (strcmp(site_arg, "cpg") != 0) {
-            fprintf(stderr, "-X (tables per site context): unknown context \"%s\"; the one context is cpg.\n", site_arg);
-            exit(1);
-        }
-        if (by_group || len_edges || ctg_map || hist_arg) {
-            fprintf(stderr, "-X (tables per site context) and %s exclude each other.\n",
-                    by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)"
-                    : ctg_map ? "-C (tables per contig set)" : "-H (fragment-length histogram)");
-            exit(1);
-        }
-    }
-    int end_depth = 0, end_cell5 = 0, end_cell3 = 0;
-    if (end_arg) {
-        char err[200];
-        if (pss_parse_end_condition(end_arg, &end_depth, &end_cell5, &end_cell3, err, sizeof err)) {
-            fprintf(stderr, "%s\n", err);
-            exit(1);
-        }
-        if (by_group || len_edges || ctg_map || hist_arg || site_arg) {
-            fprintf(stderr, "-E (tables conditional on the other end) and %s exclude each other.\n",
-                    by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)"
-                    : ctg_map ? "-C (tables per contig set)" : hist_arg ? "-H (fragment-length histogram)" : "-X (tables per site context)");
-            exit(1);
-        }
-        if (region_len > 30 || end_depth > region_len) {
-            fprintf(stderr, "-E (tables conditional on the other end) needs its depth <= -r <= 30 (both ends' marks are taken from the one pass "
-                            "over 32 table rows), not -r %d with depth %d.\n", region_len, end_depth);
-            exit(1);
-        }
-    }
-    if (gapped && (by_group || len_edges || ctg_map || hist_arg || site_arg || end_arg)) {
-        fprintf(stderr, "-I (clipped and gapped reads by their anchored ends) and %s exclude each other.\n",
-                by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)" : ctg_map ? "-C (tables per contig set)"
-                : hist_arg ? "-H (fragment-length histogram)" : site_arg ? "-X (tables per site context)" : "-E (tables conditional on the other end)");
-        exit(1);
-    }
-    if (per_contig && (by_group || len_edges || ctg_map || hist_arg || site_arg || end_arg || gapped)) {
-        fprintf(stderr, "-A (tables per contig) and %s exclude each other.\n",
-                by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)" : ctg_map ? "-C (tables per contig set)"
-                : hist_arg ? "-H (fragment-length histogram)" : site_arg ? "-X (tables per site context)"
-                : end_arg ? "-E (tables conditional on the other end)" : "-I (clipped and gapped reads by their anchored ends)");
+    if (end_arg && (region_len > 30 || end_depth > region_len)) {
+        fprintf(stderr, "%s needs its depth <= -r <= 30 (both ends' marks are taken from the one pass "
+                        "over 32 table rows), not -r %d with depth %d.\n", L_E, region_len, end_depth);
         exit(1);
     }
     int replicates = 0;
     if (rep_arg) {
-        if (by_group || len_edges || ctg_map || hist_arg || site_arg || end_arg || gapped || per_contig || max_mm_arg || mm_hist_arg || tv_only) {
-            fprintf(stderr, "-J (jackknife replicates) and %s exclude each other.\n",
-                    by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)" : ctg_map ? "-C (tables per contig set)"
-                    : hist_arg ? "-H (fragment-length histogram)" : site_arg ? "-X (tables per site context)"
-                    : end_arg ? "-E (tables conditional on the other end)" : gapped ? "-I (clipped and gapped reads by their anchored ends)"
-                    : per_contig ? "-A (tables per contig)" : max_mm_arg ? "-n (mismatch filter)" : mm_hist_arg ? "-N (mismatch histogram)"
-                    : "-V (count only transversions)");
-            exit(1);
-        }
         char err[200];
         if ((replicates = pss_parse_replicates(rep_arg, err, sizeof err)) < 0) {
             fprintf(stderr, "%s\n", err);
@@ -287,20 +284,7 @@ int main(int argc, char *argv[])
         }
     }
     int max_mm = -1, mm_hist = 0;
-    if (tv_only && !max_mm_arg && !mm_hist_arg) {
-        fprintf(stderr, "-V (count only transversions) needs -n (mismatch filter) or -N (mismatch histogram).\n");
-        exit(1);
-    }
     if (max_mm_arg || mm_hist_arg) {
-        const char *mine = !mm_hist_arg ? "-n (mismatch filter)" : !max_mm_arg ? "-N (mismatch histogram)" : "-n / -N (mismatch filter and histogram)";
-        if (by_group || len_edges || ctg_map || hist_arg || site_arg || end_arg || gapped || per_contig) {
-            fprintf(stderr, "%s and %s exclude each other.\n", mine,
-                    by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)" : ctg_map ? "-C (tables per contig set)"
-                    : hist_arg ? "-H (fragment-length histogram)" : site_arg ? "-X (tables per site context)"
-                    : end_arg ? "-E (tables conditional on the other end)" : gapped ? "-I (clipped and gapped reads by their anchored ends)"
-                    : "-A (tables per contig)");
-            exit(1);
-        }
         char err[200];
         if ((max_mm_arg && (max_mm = pss_parse_max_mismatches(max_mm_arg, err, sizeof err)) < 0) ||
             (mm_hist_arg && (mm_hist = pss_parse_mismatch_hist(mm_hist_arg, err, sizeof err)) < 0)) {
@@ -308,68 +292,37 @@ int main(int argc, char *argv[])
             exit(1);
         }
         if (region_len > 30) {
-            fprintf(stderr, "%s needs -r <= 30 (a read's fate is decided in the one pass over 32 table rows), not -r %d.\n", mine, region_len);
+            fprintf(stderr, "%s needs -r <= 30 (a read's fate is decided in the one pass over 32 table rows), not -r %d.\n", mism_all, region_len);
             exit(1);
         }
     }
     int interior = -1;
     if (interior_arg) {
-        if (by_group || len_edges || ctg_map || hist_arg || site_arg || end_arg || gapped || per_contig || max_mm_arg || mm_hist_arg || tv_only || rep_arg) {
-            fprintf(stderr, "-W (read-interior table) and %s exclude each other.\n",
-                    by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)" : ctg_map ? "-C (tables per contig set)"
-                    : hist_arg ? "-H (fragment-length histogram)" : site_arg ? "-X (tables per site context)"
-                    : end_arg ? "-E (tables conditional on the other end)" : gapped ? "-I (clipped and gapped reads by their anchored ends)"
-                    : per_contig ? "-A (tables per contig)" : max_mm_arg ? "-n (mismatch filter)" : mm_hist_arg ? "-N (mismatch histogram)"
-                    : tv_only ? "-V (count only transversions)" : "-J (jackknife replicates)");
-            exit(1);
-        }
         char err[200];
         if ((interior = pss_parse_interior_margin(interior_arg, err, sizeof err)) < 0) {
             fprintf(stderr, "%s\n", err);
             exit(1);
         }
         if (region_len > 30) {
-            fprintf(stderr, "-W (read-interior table) needs -r <= 30 (a read's fate is decided in the one pass over 32 table rows), not -r %d.\n", region_len);
+            fprintf(stderr, "%s needs -r <= 30 (a read's fate is decided in the one pass over 32 table rows), not -r %d.\n", L_W, region_len);
             exit(1);
         }
     }
     int composition = 0;
     if (comp_arg) {
-        if (by_group || len_edges || ctg_map || hist_arg || site_arg || end_arg || gapped || per_contig || max_mm_arg || mm_hist_arg || tv_only || rep_arg ||
-            interior_arg) {
-            fprintf(stderr, "-P (base composition around the read ends) and %s exclude each other.\n",
-                    by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)" : ctg_map ? "-C (tables per contig set)"
-                    : hist_arg ? "-H (fragment-length histogram)" : site_arg ? "-X (tables per site context)"
-                    : end_arg ? "-E (tables conditional on the other end)" : gapped ? "-I (clipped and gapped reads by their anchored ends)"
-                    : per_contig ? "-A (tables per contig)" : max_mm_arg ? "-n (mismatch filter)" : mm_hist_arg ? "-N (mismatch histogram)"
-                    : tv_only ? "-V (count only transversions)" : rep_arg ? "-J (jackknife replicates)" : "-W (read-interior table)");
-            exit(1);
-        }
         char err[200];
         if ((composition = pss_parse_composition_width(comp_arg, err, sizeof err)) < 0) {
             fprintf(stderr, "%s\n", err);
             exit(1);
         }
         if (region_len > 30) {
-            fprintf(stderr, "-P (base composition around the read ends) needs -r <= 30 (a read's fate and its end windows are those of the one pass over 32 table rows), not -r %d.\n", region_len);
+            fprintf(stderr, "%s needs -r <= 30 (a read's fate and its end windows are those of the one pass over 32 table rows), not -r %d.\n", L_P, region_len);
             exit(1);
         }
     }
     static int16_t pmd_weights[4 * PSS_PMD_DIST * PSS_PMD_QUAL];
     static frontend_score score;
     if (min_score_arg || score_hist) {
-        const char *mine = !score_hist ? "-y (damage-score filter)" : !min_score_arg ? "-Y (damage-score histogram)" : "-y / -Y (damage-score filter and histogram)";
-        if (by_group || len_edges || ctg_map || hist_arg || site_arg || end_arg || gapped || per_contig || max_mm_arg || mm_hist_arg || tv_only || rep_arg ||
-            interior_arg || comp_arg) {
-            fprintf(stderr, "%s and %s exclude each other.\n", mine,
-                    by_group ? "-G (tables per read group)" : len_edges ? "-S (tables per length bin)" : ctg_map ? "-C (tables per contig set)"
-                    : hist_arg ? "-H (fragment-length histogram)" : site_arg ? "-X (tables per site context)"
-                    : end_arg ? "-E (tables conditional on the other end)" : gapped ? "-I (clipped and gapped reads by their anchored ends)"
-                    : per_contig ? "-A (tables per contig)" : max_mm_arg ? "-n (mismatch filter)" : mm_hist_arg ? "-N (mismatch histogram)"
-                    : tv_only ? "-V (count only transversions)" : rep_arg ? "-J (jackknife replicates)" : interior_arg ? "-W (read-interior table)"
-                    : "-P (base composition around the read ends)");
-            exit(1);
-        }
         int32_t min_score = 0;
         char err[200];
         if (min_score_arg && pss_parse_min_score(min_score_arg, &min_score, err, sizeof err)) {
@@ -377,7 +330,7 @@ int main(int argc, char *argv[])
             exit(1);
         }
         if (region_len > 30) {
-            fprintf(stderr, "%s needs -r <= 30 (a read's fate is decided in the one pass over 32 table rows), not -r %d.\n", mine, region_len);
+            fprintf(stderr, "%s needs -r <= 30 (a read's fate is decided in the one pass over 32 table rows), not -r %d.\n", score_all, region_len);
             exit(1);
         }
         pss_pmd_weights(pmd_weights);
@@ -401,11 +354,6 @@ int main(int argc, char *argv[])
     frontend_contig_map sets;
     memset(&sets, 0, sizeof sets);
     if (ctg_map) {
-        if (by_group || len_edges) {
-            fprintf(stderr, "-C (tables per contig set) and %s exclude each other.\n",
-                    by_group ? "-G (tables per read group)" : "-S (tables per length bin)");
-            exit(1);
-        }
         FILE *mf = fopen(ctg_map, "rb");
         char *text = NULL;
         size_t len = 0, cap = 0;
@@ -472,26 +420,26 @@ int main(int argc, char *argv[])
     cfg.device = 0;
     cfg.kernel = PSSBAM_KERNEL_AUTO;
 
-    frontend_group_by_rg = by_group;
-    frontend_n_length_edges = n_edges;
-    memcpy(frontend_length_edges, edges, (size_t)n_edges * sizeof *edges);
-    if (ctg_map) frontend_contig_sets = &sets;
-    frontend_min_base_quality = min_bq;
-    frontend_length_hist = hist_max;
-    frontend_site_context = site_arg ? PSSBAM_SITE_CPG : PSSBAM_SITE_NONE;
-    frontend_end_depth = end_depth;
-    frontend_end_cell5 = end_cell5;
-    frontend_end_cell3 = end_cell3;
-    frontend_gapped_reads = gapped;
-    frontend_per_contig = per_contig;
-    frontend_mismatch_hist = mm_hist;
-    frontend_max_mismatches = max_mm;
-    frontend_mismatch_tv = tv_only;
-    frontend_replicates = replicates;
-    frontend_interior = interior;
-    frontend_composition = composition;
-    if (score.weights) frontend_read_score = &score;
-    if (bed_fn) frontend_regions = &bed;
+    frontend_opts.group_by_rg = by_group;
+    frontend_opts.n_length_edges = n_edges;
+    memcpy(frontend_opts.length_edges, edges, (size_t)n_edges * sizeof *edges);
+    if (ctg_map) frontend_opts.contig_sets = &sets;
+    frontend_opts.min_base_quality = min_bq;
+    frontend_opts.length_hist = hist_max;
+    frontend_opts.site_context = site_arg ? PSSBAM_SITE_CPG : PSSBAM_SITE_NONE;
+    frontend_opts.end_depth = end_depth;
+    frontend_opts.end_cell5 = end_cell5;
+    frontend_opts.end_cell3 = end_cell3;
+    frontend_opts.gapped_reads = gapped;
+    frontend_opts.per_contig = per_contig;
+    frontend_opts.mismatch_hist = mm_hist;
+    frontend_opts.max_mismatches = max_mm;
+    frontend_opts.mismatch_tv = tv_only;
+    frontend_opts.replicates = replicates;
+    frontend_opts.interior = interior;
+    frontend_opts.composition = composition;
+    if (score.weights) frontend_opts.read_score = &score;
+    if (bed_fn) frontend_opts.regions = &bed;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
      * load; only the tally launches wait for the genome (frontend.c) */
