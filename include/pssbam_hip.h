@@ -634,6 +634,31 @@ int pssbam_engine_set_read_score(pssbam_engine *e, const int16_t *weights /*[4][
                                  int32_t n_qual, int32_t use_filter, int32_t min_score, int32_t hist_half /*0 = no histogram*/,
                                  int32_t hist_shift /*0..16*/);
 
+/* The record sink (pss-bam -O): besides tallying them, the engine hands over the alignment records that were added to the
+ * forward or the reverse main table -- the records for which PSSBAM_ST_PSS_OK counts, after every filter of the run (cfg.pss,
+ * cfg.read_group, regions, gapped reads, the mismatch limit, the read score's minimum; each mate on its own; a minimum base
+ * quality masks bases and drops no record, except through the score).  The sink receives whole records (le32 block_size +
+ * body) back to back, byte-identical to the input and in input order across all submits, n_records of them in nbytes bytes;
+ * the memory is valid during the call only.  It is called on the thread that calls the engine and nowhere else, from inside
+ * the submit functions, pssbam_engine_sync, _finish and _reset: every submit delivers the chunks whose copy to the host has
+ * completed, sync / finish / reset deliver everything outstanding before they return.  A block none of whose records is kept
+ * delivers nothing.  A non-zero return makes the engine call fail with PSSBAM_EINVAL, and the sink is not called again.  The call
+ * that fails is always in a clean state: a submit fails at its top, before anything of it is queued (its block has NOT been
+ * tallied and may be submitted again); sync / finish / reset fail after everything else they do is done (calling them again
+ * succeeds).  A chunk that arrives while a submit is already queuing its kernels is handed over there, but a failure of the sink
+ * on it is reported by the next engine call of the kinds above -- the block of that submit is tallied, and launches that were put
+ * off for the genome all go on.  The tallies go on after a failure; only the hand-over stops.
+ * The engine starts no thread for it.
+ * The selection runs on the device behind the tally kernels of each block (three steps: mark, prefix sum, gather) and its
+ * output crosses to the host beside the next block's kernels; tables, status counters and the launch count of
+ * pssbam_engine_kernel_time are those of the run without a sink.  Without a sink the engine allocates and launches
+ * nothing for it.  Blocks given to an engine with a sink hold at most 2^32 - 256 bytes.
+ * Legal before the first submit after create or reset (PSSBAM_ESTATE otherwise); sink = NULL switches it off.  PSSBAM_EINVAL
+ * on an engine without PSSBAM_TALLY_PSS.  The setting survives pssbam_engine_reset.  Engines are independent: the order
+ * across the engines of a multi-GPU run is the caller's business. */
+typedef int (*pssbam_record_sink)(void *ctx, const void *records, uint64_t nbytes, uint64_t n_records);
+int pssbam_engine_set_record_sink(pssbam_engine *e, pssbam_record_sink sink, void *ctx);
+
 /* Drains the engine like pssbam_engine_finish and copies the two arrays, 2 * hist_half words each; either pointer may be
  * NULL.  PSSBAM_EINVAL without a histogram. */
 int pssbam_engine_finish_read_score(pssbam_engine *e, uint64_t *fwd, uint64_t *rev);

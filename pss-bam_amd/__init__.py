@@ -50,6 +50,7 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_interior", "pssbam_engine_finish_interior",
     "pssbam_engine_set_composition", "pssbam_engine_finish_composition",
     "pssbam_engine_set_read_score", "pssbam_engine_finish_read_score",
+    "pssbam_engine_set_record_sink",
 ]
 MAX_READ_GROUPS = 4096
 MAX_LENGTH_BINS = 64
@@ -98,6 +99,8 @@ class _Config(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("tally_mask", C.c_uint32), ("pss", _PssOpts), ("kmer", _KmerOpts),
                 ("read_group", C.c_char_p), ("device", C.c_int32), ("kernel", C.c_int32)]
 
+
+_RECORD_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64)   # pssbam_record_sink
 
 _hip = None
 
@@ -160,6 +163,8 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_timer_begin.argtypes = [C.c_void_p]
     L.pssbam_engine_timer_end.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.pssbam_engine_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
+    if hasattr(L, "pssbam_engine_set_record_sink"):   # (tools/select_bench.py also loads the library of the commit before the sink)
+        L.pssbam_engine_set_record_sink.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_index_records.restype = C.c_int64
     L.pssbam_index_records.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     _hip = L
@@ -693,6 +698,40 @@ class Engine:
             self._h = None
 
     __del__ = close
+
+    def set_record_sink(self, sink="collect"):
+        """The record sink (pssbam_engine_set_record_sink): the engine hands over the records it added to the forward or the
+        reverse table, byte-identical and in input order.  sink = "collect": the chunks are kept and finish_records() returns
+        them as one uint8 array; a callable f(chunk: uint8 array, n_records) -> int | None is called per chunk (a non-zero
+        return fails the engine call, and the sink is not called again); None: off.  Before the first submit."""
+        self._sink_chunks, self._sink_records = [], 0
+        if sink is None:
+            self._sink_cb = None
+            _chk(self._L.pssbam_engine_set_record_sink(self._h, None, None))
+            return
+        collect = sink == "collect"
+
+        def cb(_ctx, ptr, nbytes, n_records):
+            chunk = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(int(nbytes),)).copy()   # (valid during the call only)
+            if collect:
+                self._sink_chunks.append(chunk)
+                self._sink_records += int(n_records)
+                return 0
+            try:
+                return int(sink(chunk, int(n_records)) or 0)
+            except Exception:   # (an exception cannot cross the C frames)
+                return 1
+
+        self._sink_cb = _RECORD_SINK(cb)   # (kept alive with the engine)
+        _chk(self._L.pssbam_engine_set_record_sink(self._h, self._sink_cb, None))
+
+    def finish_records(self) -> np.ndarray:
+        """sync, then every record collected since set_record_sink() / the last finish_records(), as one uint8 array"""
+        self.sync()
+        out = np.concatenate(self._sink_chunks) if self._sink_chunks else np.zeros(0, dtype=np.uint8)
+        self.records_kept = self._sink_records
+        self._sink_chunks, self._sink_records = [], 0
+        return out
 
     def set_stream(self, hip_stream: int):
         _chk(self._L.pssbam_engine_set_stream(self._h, C.c_void_p(hip_stream)))

@@ -462,6 +462,14 @@ static uint64_t feed_slot_bytes(const pssbam_engine *e) {
     return out + e->feed_comp_cap + out / 8 + (64ull << 20);
 }
 
+// what the record sink takes beside the ring when one is set: two output buffers for a whole tally sub-batch each and
+// the len[] / dst[] array of one (36 bytes is the shortest record)
+static uint64_t select_reserve_bytes(const pssbam_engine *e) {
+    if (!e->sink) return 0;
+    const uint64_t sub = std::min<uint64_t>(FEED_SUB_MAX, e->feed_out_target) + 2 * FEED_GAP;
+    return 2 * (sub + sub / 8) + sub / 36 * 5;
+}
+
 // buffers of a super-batch that do not depend on its contents
 static int feed_prepare(pssbam_engine *e, FeedAcc &s) {
     const size_t out_need = (size_t)(FEED_GAP + e->feed_out_target + FEED_OUT_SLACK);
@@ -506,7 +514,8 @@ static int feed_acquire(pssbam_engine *e, int *out_slot, bool force) {
             size_t free_b = 0, total_b = 0;
             if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 64ull << 30;
             const uint64_t used = e->feed.size() * feed_slot_bytes(e);
-            e->feed_mem_budget = used + (free_b > (24ull << 30) ? free_b - (24ull << 30) : 0);   // leaves room for genome, 4-bit image, k-mer bins
+            const uint64_t keep = (24ull << 30) + select_reserve_bytes(e);
+            e->feed_mem_budget = used + (free_b > keep ? free_b - keep : 0);   // leaves room for genome, 4-bit image, k-mer bins
         }
         limit = std::max<size_t>(FEED_SLOTS_READY, (size_t)(e->feed_mem_budget / feed_slot_bytes(e)));
         if (const char *v = getenv("PSSBAM_FEED_MAX_SLOTS")) limit = std::max<size_t>(1, (size_t)atoi(v));
@@ -795,7 +804,7 @@ extern "C" int pssbam_engine_feed_open(pssbam_engine *e, int32_t n_ref, uint64_t
     e->feed_n_ref = n_ref;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const uint64_t keep = genome_bytes_hint + genome_bytes_hint / 2 + (8ull << 30);   // genome + 4-bit image + slack
+        const uint64_t keep = genome_bytes_hint + genome_bytes_hint / 2 + (8ull << 30) + select_reserve_bytes(e);   // genome + 4-bit image + slack (+ the record sink's buffers)
         e->feed_mem_budget = e->feed.size() * feed_slot_bytes(e) + (free_b > keep ? free_b - keep : 0);
     }
     return PSSBAM_OK;
@@ -810,6 +819,7 @@ extern "C" int pssbam_engine_submit_bgzf(pssbam_engine *e, const void *comp, uin
     }
     int rc;
     if (ticket) *ticket = 0;
+    if ((rc = select_entry(e, 0))) return rc;   // the record sink: what has arrived goes out at every submit, before any of it is taken
     if (!n_blocks) return PSSBAM_OK;
     if (!comp || !blocks) return fail(PSSBAM_EINVAL, "null buffer");
     if (e->cfg.kernel == PSSBAM_KERNEL_SIMPLE) return fail(PSSBAM_EINVAL, "device-indexed blocks need the tiled kernels");

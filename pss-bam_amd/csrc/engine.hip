@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "tally_kernels.h"
+#include "select_kernels.h"
 
 using namespace pssbam;
 
@@ -156,6 +157,21 @@ void pin_release(const void *p) {
 }
 }  // namespace
 
+// One of the record sink's two output buffers (pssbam_engine_set_record_sink): the kept records of one tally launch on the
+// device, their {bytes, records} totals, and the page-locked host memory both are copied to.  free -> the selection is
+// queued and the totals are on their way (SEL_TOTALS) -> the totals are known and the data is on its way (SEL_DATA) ->
+// delivered, free again.
+enum SelectState { SEL_FREE = 0, SEL_TOTALS, SEL_DATA };
+struct SelectBuf {
+    uint8_t *d_out = nullptr;
+    size_t out_cap = 0;
+    unsigned long long *d_totals = nullptr, *h_totals = nullptr;
+    uint8_t *h_data = nullptr;
+    size_t h_cap = 0;
+    hipEvent_t totals_ev = nullptr, data_ev = nullptr;
+    SelectState state = SEL_FREE;
+};
+
 struct KernelPrep { uint32_t lds = 0; int occ = 0; };   // tiled_grid's memo of one kernel: dynamic-LDS limit set, occupancy at it
 
 struct pssbam_engine {
@@ -244,6 +260,20 @@ struct pssbam_engine {
     uint32_t score_nd = 0, score_nq = 0, score_half = 0, score_shift = 0;
     int32_t score_min = 0;
     bool score_filter = false;
+    // the record sink (pssbam_engine_set_record_sink, select_kernels.h).  Without one nothing below is allocated and nothing
+    // more is launched.  sel_queue: the buffers in flight, oldest first (the order of delivery).
+    pssbam_record_sink sink = nullptr;
+    void *sink_ctx = nullptr;
+    bool sink_failed = false;          // the sink returned non-zero and no engine call has reported it yet (select_report)
+    SelectBuf sel[2];
+    int sel_next = 0;
+    std::vector<int> sel_queue;
+    uint32_t *d_sel_len = nullptr;     // len[] / dst[] of the launch being selected (stream order keeps the launches apart)
+    size_t sel_len_cap = 0;
+    uint2 *d_sel_sums = nullptr;
+    size_t sel_sums_cap = 0;
+    hipStream_t sel_stream = nullptr;  // the D2H copies of the kept records, beside the next block's kernels
+    uint64_t sel_launches = 0;         // (not part of kernel_launches: that count is the tally's)
     bool gapped = false;   // -I (pssbam_engine_set_gapped_reads): clipped and gapped reads are tallied by their anchored ends; no counter words
     int env_hist_lds_bins = -1;   // PSSBAM_HIST_LDS_BINS: at most this many bins of each array in LDS (tests: the global-atomic path with short reads)
     // -T (pssbam_engine_set_regions): contig name -> its merged intervals, kept on the host; the per-refID device table is
@@ -495,6 +525,17 @@ extern "C" void pssbam_engine_destroy(pssbam_engine *e) {
     if (e->d_carry) (void)hipFree(e->d_carry);
     if (e->h_handoff) (void)hipHostFree(e->h_handoff);
     if (e->handoff_ev) (void)hipEventDestroy(e->handoff_ev);
+    for (SelectBuf &b : e->sel) {
+        if (b.d_out) (void)hipFree(b.d_out);
+        if (b.d_totals) (void)hipFree(b.d_totals);
+        if (b.h_totals) (void)hipHostFree(b.h_totals);
+        if (b.h_data) (void)hipHostFree(b.h_data);
+        if (b.totals_ev) (void)hipEventDestroy(b.totals_ev);
+        if (b.data_ev) (void)hipEventDestroy(b.data_ev);
+    }
+    if (e->sel_stream) { (void)hipStreamSynchronize(e->sel_stream); (void)hipStreamDestroy(e->sel_stream); }
+    if (e->d_sel_len) (void)hipFree(e->d_sel_len);
+    if (e->d_sel_sums) (void)hipFree(e->d_sel_sums);
     for (void *q : e->retired) (void)hipFree(q);
     if (e->d_feed_tail) (void)hipFree(e->d_feed_tail);
     for (auto &p : e->feed_copies) (void)hipEventDestroy(p.second);
@@ -1035,6 +1076,139 @@ static uint32_t pieces_for(uint64_t need_max) {
     return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(pieces, 5), 41);
 }
 
+// --------------------------------------------------------------------------------------
+// the record sink: mark, scan, gather behind a tally launch; totals, then data, to the host; delivery in order
+// --------------------------------------------------------------------------------------
+static uint64_t select_reserve_bytes(const pssbam_engine *e);   // (bgzf_api.h: what the sink's buffers take from the feed's memory budget)
+
+extern "C" int pssbam_engine_set_record_sink(pssbam_engine *e, pssbam_record_sink sink, void *ctx) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (e->tallied || e->cur_feed >= 0 || !e->deferred.empty() || !e->sel_queue.empty())
+        return fail(PSSBAM_ESTATE, "the record sink is set before the first submit (after create or reset)");
+    if (sink && !(e->cfg.tally_mask & PSSBAM_TALLY_PSS)) return fail(PSSBAM_EINVAL, "the record sink follows the substitution tally (PSSBAM_TALLY_PSS)");
+    const uint64_t before = select_reserve_bytes(e);
+    e->sink = sink;
+    e->sink_ctx = sink ? ctx : nullptr;
+    if (e->feed_mem_budget) {   // worked out already (pssbam_engine_feed_open): the sink's buffers come out of it, or go back
+        const uint64_t budget = e->feed_mem_budget + before, after = select_reserve_bytes(e);
+        e->feed_mem_budget = budget > after ? budget - after : 1;
+    }
+    return PSSBAM_OK;
+}
+
+// Moves the buffers in flight along: a buffer whose totals have arrived starts the copy of its data, the oldest buffer
+// whose data has arrived is handed to the sink.  wait: until nothing is in flight.
+static int select_poll(pssbam_engine *e, bool wait) {
+    while (!e->sel_queue.empty()) {
+        for (int k : e->sel_queue) {
+            SelectBuf &b = e->sel[k];
+            if (b.state != SEL_TOTALS) continue;
+            if (wait && k == e->sel_queue.front()) HIP_TRY(hipEventSynchronize(b.totals_ev));
+            const hipError_t q = hipEventQuery(b.totals_ev);
+            if (q == hipErrorNotReady) { (void)hipGetLastError(); break; }   // (the ones behind it are later on the same stream)
+            if (q != hipSuccess) return fail(PSSBAM_EHIP, "hipEventQuery failed: %s", hipGetErrorString(q));
+            const uint64_t bytes = b.h_totals[0];
+            if (bytes > b.out_cap) return fail(PSSBAM_EHIP, "record selection reports %llu bytes in a buffer of %zu", (unsigned long long)bytes, b.out_cap);
+            if (bytes > b.h_cap) {
+                if (b.h_data) HIP_TRY(hipHostFree(b.h_data));
+                b.h_data = nullptr;
+                b.h_cap = (size_t)(bytes + bytes / 4 + (1u << 20));
+                HIP_TRY(hipHostMalloc((void **)&b.h_data, b.h_cap, hipHostMallocDefault));
+            }
+            if (bytes) HIP_TRY(hipMemcpyAsync(b.h_data, b.d_out, bytes, hipMemcpyDeviceToHost, e->sel_stream));
+            HIP_TRY(hipEventRecord(b.data_ev, e->sel_stream));
+            b.state = SEL_DATA;
+        }
+        SelectBuf &b = e->sel[e->sel_queue.front()];
+        if (b.state != SEL_DATA) return PSSBAM_OK;   // (only without `wait`)
+        if (wait) HIP_TRY(hipEventSynchronize(b.data_ev));
+        const hipError_t q = hipEventQuery(b.data_ev);
+        if (q == hipErrorNotReady) { (void)hipGetLastError(); return PSSBAM_OK; }
+        if (q != hipSuccess) return fail(PSSBAM_EHIP, "hipEventQuery failed: %s", hipGetErrorString(q));
+        b.state = SEL_FREE;
+        e->sel_queue.erase(e->sel_queue.begin());
+        if (e->sink && b.h_totals[1] && e->sink(e->sink_ctx, b.h_data, b.h_totals[0], b.h_totals[1]) != 0) {
+            e->sink = nullptr;       // never called again; what is still in flight is dropped as it arrives
+            e->sink_failed = true;   // reported by select_report, where the engine call can fail without leaving work half queued
+        }
+    }
+    return PSSBAM_OK;
+}
+
+// The sink's failure becomes the engine call's: only where nothing of the call is queued yet (the top of a submit) or everything
+// is through (sync, finish, reset).  A chunk that arrives while a submit is queuing its kernels (launch_select polls too) is
+// handed over there, but a failure of the sink waits for the next of these places: the block's tally, its slot's `consumed` event
+// and the launches put off for the genome all go on as they would have.
+static int select_report(pssbam_engine *e) {
+    if (!e->sink_failed) return PSSBAM_OK;
+    e->sink_failed = false;
+    return fail(PSSBAM_EINVAL, "the record sink returned non-zero");
+}
+
+// the top of every submit: what has arrived goes out, before anything of this call is queued
+static int select_entry(pssbam_engine *e, uint64_t nbytes) {
+    if (e->sink && nbytes > 0xFFFFFF00ull) return fail(PSSBAM_EINVAL, "record block of %llu bytes is too large for the record sink", (unsigned long long)nbytes);
+    if (!e->sel_queue.empty())
+        if (const int rc = select_poll(e, false)) return rc;
+    return select_report(e);
+}
+
+template <class T>
+static int select_grow(T **p, size_t *cap, size_t need) {
+    if (*cap >= need) return PSSBAM_OK;
+    if (*p) HIP_TRY(hipFree(*p));   // (waits for the device: no kernel still reads it)
+    *p = nullptr;
+    *cap = need + need / 4 + 1024;
+    HIP_TRY(hipMalloc((void **)p, *cap * sizeof(T)));
+    return PSSBAM_OK;
+}
+
+// behind the tally kernels of the block P describes, on the engine's stream
+static int launch_select(pssbam_engine *e, const TallyParams &P, uint64_t nbytes) {
+    int rc = select_poll(e, false);   // (a sink that fails here is reported by the next select_report: the tally of this block is queued)
+    if (rc) return rc;
+    const int k = e->sel_next;
+    SelectBuf &b = e->sel[k];
+    if (b.state != SEL_FREE && (rc = select_poll(e, true))) return rc;   // both buffers in flight: the older one first
+    if (!e->sink) return PSSBAM_OK;
+    if (!e->sel_stream) HIP_TRY(hipStreamCreateWithFlags(&e->sel_stream, hipStreamNonBlocking));
+    if (!b.d_totals) {
+        HIP_TRY(hipMalloc((void **)&b.d_totals, 2 * sizeof(unsigned long long)));
+        HIP_TRY(hipHostMalloc((void **)&b.h_totals, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&b.totals_ev, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&b.data_ev, hipEventDisableTiming));
+    }
+    const uint32_t n = P.n_recs, n_tiles = (n + SELECT_SCAN_TILE - 1) / SELECT_SCAN_TILE;
+    const size_t out_need = (size_t)((nbytes + 15ull) & ~15ull) + 16;   // every record kept, whole 16-byte stores
+    if (b.out_cap < out_need) {
+        if (b.d_out) HIP_TRY(hipFree(b.d_out));
+        b.d_out = nullptr;
+        b.out_cap = out_need + out_need / 8 + 4096;
+        HIP_TRY(hipMalloc((void **)&b.d_out, b.out_cap));
+    }
+    if ((rc = select_grow(&e->d_sel_len, &e->sel_len_cap, (size_t)n + 1))) return rc;
+    if ((rc = select_grow(&e->d_sel_sums, &e->sel_sums_cap, (size_t)n_tiles))) return rc;
+    const uint32_t cap = (uint32_t)e->n_cu * 8u;
+    const uint32_t g_mark = (uint32_t)std::min<uint64_t>(((uint64_t)n + 1 + 255) / 256, cap), g_tiles = std::min(n_tiles, cap);
+    const uint64_t pieces = (nbytes / 16 + 1 + SELECT_GATHER_THREADS * SELECT_GATHER_CHUNKS - 1) / (SELECT_GATHER_THREADS * SELECT_GATHER_CHUNKS);
+    const uint32_t g_gather = (uint32_t)std::min<uint64_t>(pieces, cap);
+    hipLaunchKernelGGL(select_mark, dim3(g_mark), dim3(256), 0, e->stream, P, e->d_sel_len);
+    hipLaunchKernelGGL(select_tile_sums, dim3(g_tiles), dim3(SELECT_SCAN_THREADS), 0, e->stream, (const uint32_t *)e->d_sel_len, n, e->d_sel_sums);
+    hipLaunchKernelGGL(select_scan_sums, dim3(1), dim3(SELECT_SUMS_ROUND), 0, e->stream, e->d_sel_sums, n_tiles, b.d_totals);
+    hipLaunchKernelGGL(select_scan_tiles, dim3(g_tiles), dim3(SELECT_SCAN_THREADS), 0, e->stream, e->d_sel_len, n, (const uint2 *)e->d_sel_sums,
+                       (const unsigned long long *)b.d_totals);
+    hipLaunchKernelGGL(select_gather, dim3(g_gather), dim3(SELECT_GATHER_THREADS), 0, e->stream, P.recs, P.offs, (const uint32_t *)e->d_sel_len, n,
+                       (const unsigned long long *)b.d_totals, b.d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b.h_totals, b.d_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipEventRecord(b.totals_ev, e->stream));
+    b.state = SEL_TOTALS;
+    e->sel_queue.push_back(k);
+    e->sel_next ^= 1;
+    e->sel_launches += 5;
+    return PSSBAM_OK;
+}
+
 // d_n_recs != NULL: the record count lives in device memory (blocks indexed on the device); n_records
 // is then only an upper bound for the launch geometry, and the prefix sample is taken sample_off
 // bytes into the block.
@@ -1326,7 +1500,10 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev1, e->stream));
     e->launch_events.emplace_back(ev0, ev1);
-    if (e->launch_events.size() > 4096) return resolve_launch_events(e);
+    if (e->launch_events.size() > 4096)
+        if (const int rc = resolve_launch_events(e)) return rc;
+    // the record sink: the kept records of this block, behind its tally and in front of whatever frees the block's buffers
+    if (e->sink) return launch_select(e, P, nbytes);
     return PSSBAM_OK;
 }
 
@@ -1357,6 +1534,7 @@ extern "C" int pssbam_engine_submit_device(pssbam_engine *e, const void *d_recor
     if (((uintptr_t)d_records & 15u) || ((uintptr_t)d_offsets & 3u))
         return fail(PSSBAM_EINVAL, "d_records must be 16-byte aligned, d_offsets 4-byte aligned");
     HIP_TRY(hipSetDevice(e->device));
+    if ((rc = select_entry(e, nbytes))) return rc;
     return launch_tally(e, (const uint8_t *)d_records, nbytes, d_offsets, n_records, nullptr, 0);
 }
 
@@ -1373,6 +1551,10 @@ extern "C" int pssbam_engine_submit_async(pssbam_engine *e, const void *records,
     int rc = check_ready(e);
     if (rc) return rc;
     if (ticket) *ticket = 0;
+    if (e->sink || e->sink_failed || !e->sel_queue.empty()) {   // the record sink: an empty submit is a poll, too
+        HIP_TRY(hipSetDevice(e->device));
+        if ((rc = select_entry(e, n_records ? nbytes : 0))) return rc;
+    }
     if (!n_records) return PSSBAM_OK;
     if (!records || !offsets) return fail(PSSBAM_EINVAL, "null buffer");
     if (nbytes >= (1ull << 32)) return fail(PSSBAM_EINVAL, "record block must be < 4 GiB (got %llu)", (unsigned long long)nbytes);
@@ -1492,6 +1674,9 @@ extern "C" int pssbam_engine_sync(pssbam_engine *e) {
     HIP_TRY(hipStreamSynchronize(e->stream));
     const int rc = genome_settle(e);
     if (rc) return rc;
+    if (!e->sel_queue.empty())   // the record sink: everything outstanding is delivered before sync returns
+        if (const int rs = select_poll(e, true)) return rs;
+    if (const int rs = select_report(e)) return rs;
     // (the streams are quiet either way: the caller's buffers are free)
     if (!e->deferred.empty())
         return fail(PSSBAM_ESTATE, "compressed blocks were fed (pssbam_engine_feed_open) but set_genome / set_references never followed");
@@ -2143,6 +2328,9 @@ extern "C" int pssbam_engine_finish_contigs(pssbam_engine *e, int32_t first_ref,
 extern "C" int pssbam_engine_reset(pssbam_engine *e) {
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
     HIP_TRY(hipSetDevice(e->device));
+    if (!e->sel_queue.empty())   // the record sink: what the run so far kept still goes out
+        if (const int rs = select_poll(e, true)) return rs;
+    if (const int rs = select_report(e)) return rs;
     e->tallied = false;
     e->feed_fresh = true;   // a compressed stream fed from here on starts a new record chain
     e->feed_skip = 0;

@@ -24,6 +24,7 @@
 #include <unistd.h>
 
 #include "bam_reader.h"
+#include "bam_writer.h"
 #include "device_feed.h"
 #include "sam_reader.h"
 
@@ -39,6 +40,60 @@ static int send_contig_sets(pssbam_engine *e, const frontend_contig_map *m)
 static int send_regions(pssbam_engine *e, const pss_regions *r)
 {
     return r ? pssbam_engine_set_regions(e, r->n_names, (const char *const *)r->names, r->n, r->name_of, r->starts, r->ends) : 0;
+}
+
+/* -O: the writer behind the engine's record sink.  It is opened at the first chunk (the input's header is known by then:
+ * out_header is set before any engine is fed) or, when no record is kept, at the end; the sink runs on whichever thread
+ * calls the engine -- the helper thread while it feeds, run_tally's after the join -- never on two at once. */
+static bam_writer *out_writer = NULL;
+static const bam_header *out_header = NULL;
+static int out_failed = 0;
+static char out_err[700];
+
+/* a diagnosed exit(1) elsewhere in the command (an unreadable FASTA, say) while the file is being written: no <out.bam>.tmp stays */
+static volatile int out_tmp_live = 0;
+static void out_at_exit(void)
+{
+    if (!out_tmp_live || !frontend_opts.out_bam) return;
+    char tmp[4200];
+    if ((size_t)snprintf(tmp, sizeof tmp, "%s.tmp", frontend_opts.out_bam) < sizeof tmp) unlink(tmp);
+}
+
+static int out_open(void)
+{
+    static int registered = 0;
+    if (out_writer) return 0;
+    if (!registered) registered = atexit(out_at_exit) == 0;
+    out_tmp_live = 1;
+    out_writer = out_header ? bam_writer_open(frontend_opts.out_bam, out_header, frontend_opts.out_level, 0) : NULL;
+    if (!out_writer) {
+        snprintf(out_err, sizeof out_err, "-O: %s", out_header ? bam_writer_open_error() : "the input's header is not known");
+        out_failed = 1;
+        out_tmp_live = 0;
+        return -1;
+    }
+    return 0;
+}
+
+static int out_sink(void *ctx, const void *records, uint64_t nbytes, uint64_t n_records)
+{
+    (void)ctx;
+    (void)n_records;
+    if (out_failed || out_open()) return 1;
+    if (bam_writer_append(out_writer, records, (size_t)nbytes)) {
+        snprintf(out_err, sizeof out_err, "-O: %s", bam_writer_error(out_writer));
+        out_failed = 1;
+        return 1;
+    }
+    return 0;
+}
+
+/* gives up what was written so far (the run failed, or starts over with the host reader) */
+static void out_discard(void)
+{
+    if (out_writer) bam_writer_abort(out_writer);
+    out_writer = NULL;
+    out_tmp_live = 0;
 }
 
 /* Start-up work that overlaps the caller's FASTA load.  The reference is serial by construction -- load the
@@ -152,7 +207,8 @@ static int apply_options(pssbam_engine *e)
            (o->end_depth > 0 && pssbam_engine_set_end_condition(e, o->end_depth, o->end_cell5, o->end_cell3)) ||
            (o->gapped_reads && pssbam_engine_set_gapped_reads(e, 1)) || send_regions(e, o->regions) ||
            (o->n_length_edges > 0 && pssbam_engine_set_length_bins(e, o->n_length_edges, o->length_edges)) ||
-           send_contig_sets(e, o->contig_sets) || (o->replicates > 0 && pssbam_engine_set_replicates(e, o->replicates));
+           send_contig_sets(e, o->contig_sets) || (o->replicates > 0 && pssbam_engine_set_replicates(e, o->replicates)) ||
+           (o->out_bam && pssbam_engine_set_record_sink(e, out_sink, NULL));
 }
 
 static void *engine_make_main(void *arg)
@@ -183,6 +239,7 @@ static void early_feed_main(void)
     pthread_t pin_th;
     const int pin_started = pthread_create(&pin_th, NULL, pin_main, NULL) == 0;
     const bam_header *h = bam_reader_header(early_rd);
+    out_header = h;   /* -O (the reader lives until run_tally() is through) */
     if (frontend_opts.group_by_rg && (EF.n_rg = pss_parse_read_groups(h->text, h->l_text, &EF.rg_ids)) < 0) EF.n_rg = 0;
     /* one engine per GPU, all created at once: a device's first touch (context, queues, code objects) takes ~0.08 s, and
      * eight of them one after the other would cost more than the whole command does on one GPU */
@@ -605,6 +662,11 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
         goto done;
     }
     t_open = now_s() - t_mark; t_mark = now_s();
+    if (frontend_opts.out_bam) {
+        if (!rd) { fprintf(stderr, "Error: -O needs BAM input.\n"); goto done; }
+        if (!adopted) out_discard();   /* (a helper whose engines were not taken over may have written) */
+        out_header = bam_reader_header(rd);
+    }
     if (adopted) {
         /* the helper created the engines, fed the file and (usually) set the genome when it was posted */
         if (EF.feed_rc || EF.failed) {
@@ -677,11 +739,14 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
         if (dfs.fallback) {
             if (verbose) fprintf(stderr, "[pssbam] device feed not usable for this file: falling back to the host reader\n");
             for (int g = 0; g < n_gpus; g++)
-                if (pssbam_engine_reset(eng[g])) { fprintf(stderr, "Error: GPU engine %d: %s\n", g, pssbam_last_error()); goto done; }
+                if (pssbam_engine_reset(eng[g])) { fprintf(stderr, "Error: GPU engine %d: %s\n", g, out_failed ? out_err : pssbam_last_error()); goto done; }
+            out_discard();   /* -O: the records come again, from the start */
+            out_header = NULL;
             bam_reader_close(rd);
             rd = bam_reader_open_slots(aln_path, 0, 0, feed_slots(n_gpus), err, sizeof err);
             light = 0;
             if (!rd) { fprintf(stderr, "Error: Unable to open %s: %s\n", aln_path, err); goto done; }
+            out_header = bam_reader_header(rd);
         } else fed_on_device = 1;
         t_submit = now_s() - t_mark; t_mark = now_s();
     }
@@ -810,7 +875,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
         res->k3 = (uint64_t *)calloc(bins, sizeof(uint64_t));
     }
     if (pssbam_engine_finish(eng[0], res->fwd, res->rev, res->k5, res->k3, res->stats)) {
-        fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+        fprintf(stderr, "Error: GPU engine: %s\n", out_failed ? out_err : pssbam_last_error());
         goto done;
     }
     if (frontend_opts.length_hist > 0 && (cfg->tally_mask & PSSBAM_TALLY_PSS)) { /* -H: summed with the rest of the block */
@@ -970,8 +1035,18 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
     res->inflate_s = fed_on_device ? dfs.inflate_ms * 1e-3 : rd ? bam_reader_inflate_seconds(rd) : 0.0;
     if (sd) res->stats[PSSBAM_ST_PARSE_SKIP] += sam_reader_lines_skipped(sd), res->stats[PSSBAM_ST_RECORDS] += sam_reader_lines_skipped(sd);
     res->n_gpus = n_gpus;
+    if (frontend_opts.out_bam) {   /* -O: every kept record has been delivered (finish syncs); the file takes its name now, the last thing that can fail */
+        if (out_failed || out_open()) { fprintf(stderr, "Error: %s\n", out_err); goto done; }
+        bam_writer *w = out_writer;
+        out_writer = NULL;
+        const int bad = bam_writer_close(w, err, sizeof err);
+        out_tmp_live = 0;
+        if (bad) { fprintf(stderr, "Error: -O: %s\n", err); goto done; }
+    }
     rc = 0;
 done:
+    if (rc && out_failed) fprintf(stderr, "Error: %s\n", out_err);
+    if (rc) out_discard();   /* -O: a failed run leaves no file behind */
     t_mark = now_s();
     if (!(frontend_fast_exit && rc == 0)) {
         device_feed_prefetch_cancel(); /* a loader opened ahead of time that no feed took over; the staging slots of one that ran */

@@ -122,6 +122,11 @@ typedef struct frontend_options {
     /* -T: the intervals of the BED file (regions.h; NULL: none); every engine gets them (pssbam_engine_set_regions), on
      * every input path -- the filter lives in the engine. */
     const pss_regions *regions;
+    /* pss-bam -O / -z: the BAM that receives the records added to a table (NULL: none) and its compression level; the run's
+     * one engine gets a record sink (pssbam_engine_set_record_sink) that appends to a bam_writer.  run_tally() closes the file
+     * -- it takes its name only then -- before it returns, and removes it when the run fails.  BAM input, one GPU. */
+    const char *out_bam;
+    int out_level;
 } frontend_options;
 extern frontend_options frontend_opts;   /* everything off */
 

@@ -73,6 +73,12 @@
  * units of 1/256 nat: -y 3 keeps the reads with a score of at least 768 units.  No number-for-number parity with another
  * implementation of the score is claimed.  Needs -r <= 30.  Goes with -R, -Q, -T, -m, -l, -L, -q, -U and -D.  Not with -G, -S, -C,
  * -H, -X, -E, -I, -A, -n, -N, -V, -J, -W or -P.
+ * Added: -O <out.bam> also writes a BAM that holds exactly the alignment records that were added to the forward or the reverse
+ * table of this run -- after every filter given, each mate judged on its own -- in input order and byte for byte as they are in the
+ * input, under the input's header (no @PG line), from the same pass: the file the other options' "the input without the other
+ * reads" speaks of.  -Q masks bases, not reads: it changes the file only through -y.  -z <level> (0..9, default 1) is its BGZF
+ * compression level.  The file is written as <out.bam>.tmp and takes its name when it is complete; a failed run leaves none.  Goes
+ * with every other option.  Needs BAM input and one GPU (PSSBAM_NGPU unset or 1); must not be the file -B names.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -81,6 +87,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include "base_quality.h"
@@ -97,6 +104,7 @@
 #include "regions.h"
 #include "replicates.h"
 #include "report.h"
+#include "sam_reader.h"
 
 /* the options' names in the messages, each spelt once */
 static const char L_G[] = "-G (tables per read group)", L_S[] = "-S (tables per length bin)", L_C[] = "-C (tables per contig set)",
@@ -117,8 +125,9 @@ int main(int argc, char *argv[])
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL, *read_group = NULL;
     const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL, *bed_fn = NULL, *hist_arg = NULL, *site_arg = NULL, *end_arg = NULL;
     const char *max_mm_arg = NULL, *mm_hist_arg = NULL, *rep_arg = NULL, *interior_arg = NULL, *comp_arg = NULL, *min_score_arg = NULL;
+    const char *out_bam = NULL, *out_level_arg = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:P:y:Y")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:P:y:YO:z:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -148,6 +157,8 @@ int main(int argc, char *argv[])
         case 'P': comp_arg = optarg; break;
         case 'y': min_score_arg = optarg; break;
         case 'Y': score_hist = 1; break;
+        case 'O': out_bam = optarg; break;
+        case 'z': out_level_arg = optarg; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -187,7 +198,9 @@ int main(int argc, char *argv[])
               "-W <d> <also write the substitution counts and rates of the read interior, d bases and more from both ends (0..65535)>\n"
               "-P <w> <also write the reference base composition w bases on either side of the read ends (1..30)>\n"
               "-y <t> <only tally the reads with a post-mortem-damage score of at least t nats (double-stranded model, held in units of 1/256 nat)>\n"
-              "-Y <also write how many tallied reads have a post-mortem-damage score of -31 .. 30 nats and beyond; no parity with another implementation is claimed>\n",
+              "-Y <also write how many tallied reads have a post-mortem-damage score of -31 .. 30 nats and beyond; no parity with another implementation is claimed>\n"
+              "-O <out.bam> <also write the tallied reads, as they are in the input and in its order, to this BAM (BAM input, one GPU)>\n"
+              "-z <level> <with -O: BGZF compression level 0..9 (default: 1)>\n",
               stderr);
         exit(1);
     }
@@ -214,6 +227,48 @@ int main(int argc, char *argv[])
     if (tv_only && !max_mm_arg && !mm_hist_arg && !rep_arg) {
         fprintf(stderr, "%s needs %s or %s.\n", L_V, L_n, L_N);
         exit(1);
+    }
+    /* -O / -z: no row of the table below (the output uses no counter words; it goes with every option) */
+    int out_level = 1;
+    if (out_level_arg) {
+        char *end = NULL;
+        const long v = strtol(out_level_arg, &end, 10);
+        if (!*out_level_arg || *end || v < 0 || v > 9) {
+            fprintf(stderr, "-z: the compression level must be 0..9, not \"%s\".\n", out_level_arg);
+            exit(1);
+        }
+        out_level = (int)v;
+        if (!out_bam) {
+            fprintf(stderr, "-z (compression level) needs -O (the BAM of the tallied reads).\n");
+            exit(1);
+        }
+    }
+    if (out_bam) {
+        struct stat sa, sb;
+        if (!strcmp(out_bam, bam_fn) || (stat(out_bam, &sa) == 0 && stat(bam_fn, &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino)) {
+            fprintf(stderr, "-O must not name the input (-B %s).\n", bam_fn);
+            exit(1);
+        }
+        if (getenv("PSSBAM_NGPU") && atoi(getenv("PSSBAM_NGPU")) > 1) {
+            fprintf(stderr, "-O writes the reads in input order, which one GPU keeps: not with PSSBAM_NGPU=%s.\n", getenv("PSSBAM_NGPU"));
+            exit(1);
+        }
+        if (file_is_bam(bam_fn) == 0) {
+            fprintf(stderr, "-O copies BAM records: it needs BAM input, and %s is SAM text.\n", bam_fn);
+            exit(1);
+        }
+        /* (a place that cannot be written is found out now, not after the genome has been loaded) */
+        char *tmp = (char *)malloc(strlen(out_bam) + 5);
+        if (!tmp) { fprintf(stderr, "Error: out of memory\n"); exit(1); }
+        sprintf(tmp, "%s.tmp", out_bam);
+        FILE *probe = fopen(tmp, "wb");
+        if (!probe) {
+            fprintf(stderr, "-O: cannot create %s.\n", tmp);
+            exit(1);
+        }
+        fclose(probe);
+        remove(tmp);
+        free(tmp);
     }
     /* The exclusive options: at most one row may be given (their tables share the words behind the engine's planes, and
      * one pass over 32 table rows).  Of two, the later row is named first, by all it was given with, the earlier one by
@@ -403,6 +458,7 @@ int main(int argc, char *argv[])
     if (comp_arg) fprintf(stderr, " -P %d", composition);
     if (min_score_arg) fprintf(stderr, " -y %s", min_score_arg);
     if (score_hist) fprintf(stderr, " -Y");
+    if (out_bam) fprintf(stderr, " -O %s -z %d", out_bam, out_level);
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -440,6 +496,8 @@ int main(int argc, char *argv[])
     frontend_opts.composition = composition;
     if (score.weights) frontend_opts.read_score = &score;
     if (bed_fn) frontend_opts.regions = &bed;
+    frontend_opts.out_bam = out_bam;
+    frontend_opts.out_level = out_level;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
      * load; only the tally launches wait for the genome (frontend.c) */
