@@ -659,6 +659,30 @@ int pssbam_engine_set_read_score(pssbam_engine *e, const int16_t *weights /*[4][
 typedef int (*pssbam_record_sink)(void *ctx, const void *records, uint64_t nbytes, uint64_t n_records);
 int pssbam_engine_set_record_sink(pssbam_engine *e, pssbam_record_sink sink, void *ctx);
 
+/* The block sink (pss-bam -O ... -Z): the record sink's stream, deflated on the device.  The records the record sink would
+ * receive are cut into BGZF payloads of 0xFF00 bytes at fixed offsets of each chunk (records may cross blocks, as in files
+ * written by htsjdk), every payload becomes one complete BGZF block on the device (csrc/deflate_kernels.h: dynamic-Huffman
+ * DEFLATE over LZ77 matches, or stored where that is not smaller; CRC-32 and ISIZE included), and the blocks cross to the
+ * host packed back to back.  The sink receives a whole number of complete blocks: n_blocks of them in nbytes bytes, which
+ * inflate to raw_bytes bytes holding n_records whole records.  Concatenated over all calls they inflate to exactly the byte
+ * stream the record sink would have delivered for the same input and settings.  The compressed bytes depend on the input
+ * AND on how it was cut into submits -- each chunk closes its last block, so a different cut moves the block boundaries --
+ * while the inflated stream does not depend on the cut.  The same input in the same submits gives the same bytes on every
+ * run.  No EOF block is delivered: the stream's end is the caller's to mark.
+ * Everything else is as for pssbam_engine_set_record_sink: which records are kept, the thread that calls the sink, the
+ * calls that deliver (every submit delivers the chunks whose copy to the host has completed; sync / finish / reset deliver
+ * everything outstanding), a chunk with no kept record delivers nothing, a non-zero return makes the engine call fail with
+ * PSSBAM_EINVAL in the same clean states and the sink is not called again, the tallies go on.  Tables, status counters and
+ * the time and launch count of pssbam_engine_kernel_time are those of the run without a sink; without a block sink nothing
+ * is allocated or launched for it (three more kernels behind the gather -- deflate, and the pack's scan and copy --, one
+ * strided buffer of 64 KiB per block, a length and an offset per block otherwise; under pssbam_engine_feed_open they come out of the feed's memory budget).  Legal before the first
+ * submit after create or reset (PSSBAM_ESTATE otherwise); sink = NULL switches it off; PSSBAM_EINVAL on an engine without
+ * PSSBAM_TALLY_PSS and while a record sink is set (pssbam_engine_set_record_sink likewise returns PSSBAM_EINVAL while a
+ * block sink is set: one or the other).  The setting survives pssbam_engine_reset. */
+typedef int (*pssbam_block_sink)(void *ctx, const void *bgzf, uint64_t nbytes, uint64_t n_blocks, uint64_t raw_bytes,
+                                 uint64_t n_records);
+int pssbam_engine_set_block_sink(pssbam_engine *e, pssbam_block_sink sink, void *ctx);
+
 /* Drains the engine like pssbam_engine_finish and copies the two arrays, 2 * hist_half words each; either pointer may be
  * NULL.  PSSBAM_EINVAL without a histogram. */
 int pssbam_engine_finish_read_score(pssbam_engine *e, uint64_t *fwd, uint64_t *rev);
@@ -821,6 +845,23 @@ int pssbam_feed_release(int device);
 int pssbam_bgzf_inflate_host(int device, const void *bgzf, uint64_t nbytes, void *out, uint64_t out_cap, uint64_t *out_len,
                              uint32_t *n_blocks, uint32_t *first_bad_block, uint32_t *first_bad_status, double *kernel_ms,
                              int check_crc, int repeats);
+
+/* Deflates d_raw[0, raw_bytes) into whole BGZF blocks on the current device, asynchronously on hip_stream.  The stream is
+ * cut into payloads of 0xFF00 bytes at fixed offsets (the last one short); the blocks are written back to back to d_bgzf
+ * and d_totals = {bytes written, blocks}.  d_raw is 16-byte aligned and readable up to the next multiple of 16 bytes;
+ * d_bgzf holds bgzf_cap >= raw_bytes + 31 * blocks bytes (blocks = ceil(raw_bytes / 0xFF00); no block is larger than its
+ * stored form, 31 bytes over its payload); d_work is 16-byte aligned scratch of work_bytes >=
+ * pssbam_bgzf_deflate_work_bytes(raw_bytes): a 64 KiB slot, a length and an offset per block.  d_raw and d_bgzf may not
+ * overlap d_work; d_bgzf may be d_raw (the raw bytes are dead once deflated) when d_raw has the capacity.  raw_bytes == 0
+ * writes {0, 0}.  PSSBAM_EINVAL for a buffer too small or misaligned. */
+uint64_t pssbam_bgzf_deflate_work_bytes(uint64_t raw_bytes);
+int pssbam_bgzf_deflate_device(void *hip_stream, const void *d_raw, uint64_t raw_bytes, void *d_bgzf, uint64_t bgzf_cap,
+                               uint64_t *d_totals, void *d_work, uint64_t work_bytes);
+
+/* Test / tool convenience: host bytes in, BGZF blocks out (out may be NULL; PSSBAM_EINVAL when out_cap is below the bytes
+ * written), kernels timed with HIP events (*kernel_ms = best of `repeats` runs of deflate + pack). */
+int pssbam_bgzf_deflate_host(int device, const void *raw, uint64_t nbytes, void *out, uint64_t out_cap, uint64_t *out_len,
+                             uint32_t *n_blocks, double *kernel_ms, int repeats);
 
 /* Host helper: walks the block_size chain of an inflated BAM record stream.  Writes up
  * to max_records offsets (+ the end sentinel), returns the number of whole records

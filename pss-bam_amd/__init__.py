@@ -50,7 +50,8 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_interior", "pssbam_engine_finish_interior",
     "pssbam_engine_set_composition", "pssbam_engine_finish_composition",
     "pssbam_engine_set_read_score", "pssbam_engine_finish_read_score",
-    "pssbam_engine_set_record_sink",
+    "pssbam_engine_set_record_sink", "pssbam_engine_set_block_sink",
+    "pssbam_bgzf_deflate_work_bytes", "pssbam_bgzf_deflate_device", "pssbam_bgzf_deflate_host",
 ]
 MAX_READ_GROUPS = 4096
 MAX_LENGTH_BINS = 64
@@ -101,6 +102,8 @@ class _Config(C.Structure):
 
 
 _RECORD_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64)   # pssbam_record_sink
+
+_BLOCK_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64)   # pssbam_block_sink
 
 _hip = None
 
@@ -165,6 +168,13 @@ def hip_lib() -> C.CDLL:
     L.pssbam_engine_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
     if hasattr(L, "pssbam_engine_set_record_sink"):   # (tools/select_bench.py also loads the library of the commit before the sink)
         L.pssbam_engine_set_record_sink.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "pssbam_engine_set_block_sink"):   # (tools/deflate_bench.py also loads the library of the commit before it)
+        L.pssbam_engine_set_block_sink.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pssbam_bgzf_deflate_work_bytes.restype = C.c_uint64
+        L.pssbam_bgzf_deflate_work_bytes.argtypes = [C.c_uint64]
+        L.pssbam_bgzf_deflate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.pssbam_bgzf_deflate_host.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                               C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.c_int]
     L.pssbam_index_records.restype = C.c_int64
     L.pssbam_index_records.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     _hip = L
@@ -198,6 +208,32 @@ def bgzf_inflate(bgzf: np.ndarray, check_crc: bool = True, repeats: int = 1, wan
     return {"data": out, "inflated_bytes": int(out_len.value), "n_blocks": int(nb.value),
             "bad_block": None if bad_b.value == 0xFFFFFFFF else int(bad_b.value), "bad_status": int(bad_s.value),
             "kernel_ms": float(ms.value)}
+
+
+BGZF_PAYLOAD = 0xFF00   # bytes of the stream per block of the device deflate
+
+
+def bgzf_deflate(raw: np.ndarray, repeats: int = 1) -> dict:
+    """Deflates bytes into whole BGZF blocks on the GPU (pssbam_bgzf_deflate_host), cut every 0xFF00 bytes: {"data" (the
+    blocks back to back, no EOF block), "n_blocks", "kernel_ms"}."""
+    L = hip_lib()
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    n_blocks = (raw.size + BGZF_PAYLOAD - 1) // BGZF_PAYLOAD
+    out = np.empty(raw.size + 31 * n_blocks, dtype=np.uint8)   # (no block is larger than its stored form)
+    out_len, nb, ms = C.c_uint64(), C.c_uint32(), C.c_double()
+    _chk(L.pssbam_bgzf_deflate_host(-1, raw.ctypes.data if raw.size else None, raw.size, out.ctypes.data if out.size else None, out.size,
+                                    C.byref(out_len), C.byref(nb), C.byref(ms), repeats))
+    return {"data": out[:int(out_len.value)].copy(), "n_blocks": int(nb.value), "kernel_ms": float(ms.value)}
+
+
+def bgzf_deflate_device(hip_stream: int, d_raw: int, raw_bytes: int, d_bgzf: int, bgzf_cap: int, d_totals: int, d_work: int, work_bytes: int):
+    """pssbam_bgzf_deflate_device on device pointers (e.g. torch tensors' data_ptr()); bgzf_deflate_work_bytes() sizes d_work"""
+    _chk(hip_lib().pssbam_bgzf_deflate_device(C.c_void_p(hip_stream), C.c_void_p(d_raw), raw_bytes, C.c_void_p(d_bgzf), bgzf_cap,
+                                              C.c_void_p(d_totals), C.c_void_p(d_work), work_bytes))
+
+
+def bgzf_deflate_work_bytes(raw_bytes: int) -> int:
+    return int(hip_lib().pssbam_bgzf_deflate_work_bytes(raw_bytes))
 
 
 def index_records(buf: np.ndarray) -> np.ndarray:
@@ -724,6 +760,43 @@ class Engine:
 
         self._sink_cb = _RECORD_SINK(cb)   # (kept alive with the engine)
         _chk(self._L.pssbam_engine_set_record_sink(self._h, self._sink_cb, None))
+
+    def set_block_sink(self, sink="collect"):
+        """The block sink (pssbam_engine_set_block_sink): the record sink's stream as whole BGZF blocks, deflated on the
+        device.  sink = "collect": the chunks are kept and finish_blocks() returns them as one uint8 array; a callable
+        f(blocks: uint8 array, n_blocks, raw_bytes, n_records) -> int | None is called per chunk (a non-zero return fails the
+        engine call, and the sink is not called again); None: off.  Before the first submit; not beside a record sink."""
+        self._block_chunks, self._block_totals = [], [0, 0, 0]
+        if sink is None:
+            self._block_cb = None
+            _chk(self._L.pssbam_engine_set_block_sink(self._h, None, None))
+            return
+        collect = sink == "collect"
+
+        def cb(_ctx, ptr, nbytes, n_blocks, raw_bytes, n_records):
+            chunk = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(int(nbytes),)).copy()   # (valid during the call only)
+            if collect:
+                self._block_chunks.append(chunk)
+                for k, v in enumerate((n_blocks, raw_bytes, n_records)):
+                    self._block_totals[k] += int(v)
+                return 0
+            try:
+                return int(sink(chunk, int(n_blocks), int(raw_bytes), int(n_records)) or 0)
+            except Exception:   # (an exception cannot cross the C frames)
+                return 1
+
+        cb_c = _BLOCK_SINK(cb)
+        _chk(self._L.pssbam_engine_set_block_sink(self._h, cb_c, None))
+        self._block_cb = cb_c   # (kept alive with the engine)
+
+    def finish_blocks(self) -> np.ndarray:
+        """sync, then every block collected since set_block_sink() / the last finish_blocks(), as one uint8 array;
+        blocks_kept = {"n_blocks", "raw_bytes", "n_records"} of them"""
+        self.sync()
+        out = np.concatenate(self._block_chunks) if self._block_chunks else np.zeros(0, dtype=np.uint8)
+        self.blocks_kept = dict(zip(("n_blocks", "raw_bytes", "n_records"), self._block_totals))
+        self._block_chunks, self._block_totals = [], [0, 0, 0]
+        return out
 
     def finish_records(self) -> np.ndarray:
         """sync, then every record collected since set_record_sink() / the last finish_records(), as one uint8 array"""

@@ -343,6 +343,130 @@ extern "C" int pssbam_bgzf_inflate_host(int device, const void *bgzf, uint64_t n
 }
 
 // --------------------------------------------------------------------------------------
+// BGZF deflate on the device (deflate_kernels.h)
+// --------------------------------------------------------------------------------------
+namespace {
+uint32_t *g_xpow64_dev[64] = {nullptr};   // per device: x^(8*64*k) mod P, k = 0..1023 (bgzf_deflate's CRC: 64 bytes a thread)
+int ensure_xpow64(int dev, uint32_t **out) {
+    if (dev < 0 || dev >= 64) return fail(PSSBAM_EINVAL, "device %d out of range", dev);
+    if (!g_xpow64_dev[dev]) {
+        uint32_t x64 = 0x80000000u;   // x^0
+        for (uint32_t i = 0; i < 8 * pssbam::DFL_CRC_CHUNK; i++) x64 = (x64 >> 1) ^ ((x64 & 1u) ? 0xEDB88320u : 0u);
+        std::vector<uint32_t> h(pssbam::DFL_THREADS);
+        h[0] = 0x80000000u;
+        for (size_t k = 1; k < h.size(); k++) h[k] = host_gf2_mul(h[k - 1], x64);
+        HIP_TRY(hipMalloc(&g_xpow64_dev[dev], h.size() * sizeof(uint32_t)));
+        HIP_TRY(hipMemcpy(g_xpow64_dev[dev], h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    *out = g_xpow64_dev[dev];
+    return PSSBAM_OK;
+}
+}  // namespace
+
+static uint64_t deflate_blocks_of(uint64_t raw_bytes) { return (raw_bytes + pssbam::DFL_PAYLOAD - 1) / pssbam::DFL_PAYLOAD; }
+
+// Queues deflate + scan + pack for a stream of at most max_bytes bytes whose length is *d_total (NULL: max_bytes itself):
+// d_raw -> d_comp (a slot per block) -> d_packed, totals_out = {bytes, blocks}.  The grids are sized for max_bytes.
+static int launch_deflate(hipStream_t st, const uint8_t *d_raw, uint64_t max_bytes, const unsigned long long *d_total, uint8_t *d_comp,
+                          uint32_t *d_comp_len, unsigned long long *d_comp_off, uint8_t *d_packed, unsigned long long *totals_out) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    uint32_t *xpow64 = nullptr;
+    if (const int rc = ensure_xpow64(dev, &xpow64)) return rc;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(deflate_blocks_of(max_bytes), 1), 1u << 20);
+    hipLaunchKernelGGL(pssbam::bgzf_deflate, dim3(grid), dim3(pssbam::DFL_THREADS), 0, st, d_raw, d_total, (unsigned long long)max_bytes, d_comp,
+                       d_comp_len, (const uint32_t *)xpow64);
+    hipLaunchKernelGGL(pssbam::bgzf_pack_scan, dim3(1), dim3(pssbam::PACK_SCAN_THREADS), 0, st, (const uint32_t *)d_comp_len, d_total,
+                       (unsigned long long)max_bytes, d_comp_off, totals_out);
+    hipLaunchKernelGGL(pssbam::bgzf_pack_copy, dim3(grid), dim3(pssbam::PACK_COPY_THREADS), 0, st, (const uint8_t *)d_comp, (const uint32_t *)d_comp_len,
+                       (const unsigned long long *)d_comp_off, d_total, (unsigned long long)max_bytes, d_packed);
+    HIP_TRY(hipGetLastError());
+    return PSSBAM_OK;
+}
+
+// the scratch of launch_deflate for max_bytes: [slots | offsets | lengths]
+static uint64_t deflate_work_bytes(uint64_t max_bytes) {
+    const uint64_t n = std::max<uint64_t>(deflate_blocks_of(max_bytes), 1);
+    return n * pssbam::DFL_SLOT + n * 8 + ((n * 4 + 15) & ~15ull);
+}
+
+extern "C" uint64_t pssbam_bgzf_deflate_work_bytes(uint64_t raw_bytes) { return deflate_work_bytes(raw_bytes); }
+
+extern "C" int pssbam_bgzf_deflate_device(void *hip_stream, const void *d_raw, uint64_t raw_bytes, void *d_bgzf, uint64_t bgzf_cap,
+                                          uint64_t *d_totals, void *d_work, uint64_t work_bytes) {
+    if (!d_totals) return fail(PSSBAM_EINVAL, "null totals");
+    const uint64_t n = deflate_blocks_of(raw_bytes);
+    if (raw_bytes && (!d_raw || !d_bgzf || !d_work)) return fail(PSSBAM_EINVAL, "null buffer");
+    if (((uintptr_t)d_raw | (uintptr_t)d_work) & 15u) return fail(PSSBAM_EINVAL, "d_raw and d_work are 16-byte aligned");
+    if (bgzf_cap < raw_bytes + 31 * n) return fail(PSSBAM_EINVAL, "bgzf_cap %llu is below %llu", (unsigned long long)bgzf_cap, (unsigned long long)(raw_bytes + 31 * n));
+    if (raw_bytes && work_bytes < deflate_work_bytes(raw_bytes)) return fail(PSSBAM_EINVAL, "work_bytes %llu is below %llu", (unsigned long long)work_bytes, (unsigned long long)deflate_work_bytes(raw_bytes));
+    if (!raw_bytes) {
+        HIP_TRY(hipMemsetAsync(d_totals, 0, 2 * sizeof(uint64_t), (hipStream_t)hip_stream));
+        return PSSBAM_OK;
+    }
+    uint8_t *w = (uint8_t *)d_work;
+    return launch_deflate((hipStream_t)hip_stream, (const uint8_t *)d_raw, raw_bytes, nullptr, w, (uint32_t *)(w + n * pssbam::DFL_SLOT + n * 8),
+                          (unsigned long long *)(w + n * pssbam::DFL_SLOT), (uint8_t *)d_bgzf, (unsigned long long *)d_totals);
+}
+
+// Convenience for tests and tools: host bytes in -> BGZF blocks out (host), everything in between on the device.
+// *kernel_ms = device time of the deflate + pack kernels alone.
+extern "C" int pssbam_bgzf_deflate_host(int device, const void *raw, uint64_t nbytes, void *out, uint64_t out_cap, uint64_t *out_len,
+                                        uint32_t *n_blocks_out, double *kernel_ms, int repeats) {
+    if (out_len) *out_len = 0;
+    if (n_blocks_out) *n_blocks_out = 0;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (!nbytes) return PSSBAM_OK;
+    if (!raw) return fail(PSSBAM_EINVAL, "null input");
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    const uint64_t n = deflate_blocks_of(nbytes), cap = nbytes + 31 * n, work = deflate_work_bytes(nbytes);
+    uint8_t *d_raw = nullptr, *d_bgzf = nullptr, *d_work = nullptr;
+    uint64_t *d_totals = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&]() {
+        if (d_raw) (void)hipFree(d_raw);
+        if (d_bgzf) (void)hipFree(d_bgzf);
+        if (d_work) (void)hipFree(d_work);
+        if (d_totals) (void)hipFree(d_totals);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    };
+#define TRY_C(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { cleanup(); return fail(PSSBAM_EHIP, "%s failed: %s", #expr, hipGetErrorString(_e)); } } while (0)
+    TRY_C(hipMalloc(&d_raw, nbytes + 16));
+    TRY_C(hipMalloc(&d_bgzf, cap + 16));
+    TRY_C(hipMalloc(&d_work, work));
+    TRY_C(hipMalloc(&d_totals, 2 * sizeof(uint64_t)));
+    TRY_C(hipMemset(d_raw + nbytes, 0, 16));
+    TRY_C(hipMemcpy(d_raw, raw, nbytes, hipMemcpyHostToDevice));
+    TRY_C(hipEventCreate(&e0));
+    TRY_C(hipEventCreate(&e1));
+    if (repeats < 1) repeats = 1;
+    float best = 1e30f;
+    for (int r = 0; r < repeats; r++) {
+        TRY_C(hipEventRecord(e0, nullptr));
+        if (const int rc = pssbam_bgzf_deflate_device(nullptr, d_raw, nbytes, d_bgzf, cap, d_totals, d_work, work)) { cleanup(); return rc; }
+        TRY_C(hipEventRecord(e1, nullptr));
+        TRY_C(hipEventSynchronize(e1));
+        float ms = 0.f;
+        TRY_C(hipEventElapsedTime(&ms, e0, e1));
+        best = std::min(best, ms);
+    }
+    uint64_t totals[2] = {0, 0};
+    TRY_C(hipMemcpy(totals, d_totals, sizeof totals, hipMemcpyDeviceToHost));
+    if (kernel_ms) *kernel_ms = best;
+    if (out_len) *out_len = totals[0];
+    if (n_blocks_out) *n_blocks_out = (uint32_t)totals[1];
+    if (totals[0] > cap) { cleanup(); return fail(PSSBAM_EHIP, "deflate reports %llu bytes in a buffer of %llu", (unsigned long long)totals[0], (unsigned long long)cap); }
+    if (out) {
+        if (totals[0] > out_cap) { cleanup(); return fail(PSSBAM_EINVAL, "output buffer too small (%llu needed)", (unsigned long long)totals[0]); }
+        TRY_C(hipMemcpy(out, d_bgzf, totals[0], hipMemcpyDeviceToHost));
+    }
+#undef TRY_C
+    cleanup();
+    return PSSBAM_OK;
+}
+
+// --------------------------------------------------------------------------------------
 // the feed: compressed chunks -> device inflate -> device record index -> tally
 // --------------------------------------------------------------------------------------
 // The inflate kernel runs one lane per BGZF block, 65 536 lanes resident: it wants whole "rounds" of that many
@@ -464,10 +588,15 @@ static uint64_t feed_slot_bytes(const pssbam_engine *e) {
 
 // what the record sink takes beside the ring when one is set: two output buffers for a whole tally sub-batch each and
 // the len[] / dst[] array of one (36 bytes is the shortest record)
+// (the block sink: the strided buffer of one sub-batch's blocks, their lengths and offsets, and the stored form's slack in
+// the two output buffers, on top)
 static uint64_t select_reserve_bytes(const pssbam_engine *e) {
-    if (!e->sink) return 0;
+    if (!e->sink && !e->block_sink) return 0;
     const uint64_t sub = std::min<uint64_t>(FEED_SUB_MAX, e->feed_out_target) + 2 * FEED_GAP;
-    return 2 * (sub + sub / 8) + sub / 36 * 5;
+    const uint64_t records = 2 * (sub + sub / 8) + sub / 36 * 5;
+    if (!e->block_sink) return records;
+    const uint64_t blocks = deflate_blocks_of(sub) + deflate_blocks_of(sub) / 8 + 16;
+    return records + blocks * (pssbam::DFL_SLOT + 12 + 2 * 31);
 }
 
 // buffers of a super-batch that do not depend on its contents

@@ -28,6 +28,7 @@
 
 #include "tally_kernels.h"
 #include "select_kernels.h"
+#include "deflate_kernels.h"
 
 using namespace pssbam;
 
@@ -158,7 +159,7 @@ void pin_release(const void *p) {
 }  // namespace
 
 // One of the record sink's two output buffers (pssbam_engine_set_record_sink): the kept records of one tally launch on the
-// device, their {bytes, records} totals, and the page-locked host memory both are copied to.  free -> the selection is
+// device, their {bytes, records} totals (with the block sink {raw bytes, records, compressed bytes, blocks}), and the page-locked host memory both are copied to.  free -> the selection is
 // queued and the totals are on their way (SEL_TOTALS) -> the totals are known and the data is on its way (SEL_DATA) ->
 // delivered, free again.
 enum SelectState { SEL_FREE = 0, SEL_TOTALS, SEL_DATA };
@@ -170,6 +171,7 @@ struct SelectBuf {
     size_t h_cap = 0;
     hipEvent_t totals_ev = nullptr, data_ev = nullptr;
     SelectState state = SEL_FREE;
+    bool deflated = false;   // the block sink's: d_out holds totals[3] BGZF blocks in totals[2] bytes
 };
 
 struct KernelPrep { uint32_t lds = 0; int occ = 0; };   // tiled_grid's memo of one kernel: dynamic-LDS limit set, occupancy at it
@@ -265,6 +267,16 @@ struct pssbam_engine {
     pssbam_record_sink sink = nullptr;
     void *sink_ctx = nullptr;
     bool sink_failed = false;          // the sink returned non-zero and no engine call has reported it yet (select_report)
+    // the block sink (pssbam_engine_set_block_sink, deflate_kernels.h): the same selection, deflated into BGZF blocks behind
+    // the gather.  One or the other is set.  d_comp: a 64 KiB slot per block of the chunk being deflated, shared by both
+    // selection buffers (stream order keeps the chunks apart); the packed blocks go back into the chunk's own d_out.
+    pssbam_block_sink block_sink = nullptr;
+    void *block_ctx = nullptr;
+    bool block_sink_failed = false;    // which of the two sink_failed speaks of
+    uint8_t *d_comp = nullptr;
+    size_t comp_cap = 0;               // in blocks
+    uint32_t *d_comp_len = nullptr;
+    unsigned long long *d_comp_off = nullptr;
     SelectBuf sel[2];
     int sel_next = 0;
     std::vector<int> sel_queue;
@@ -536,6 +548,9 @@ extern "C" void pssbam_engine_destroy(pssbam_engine *e) {
     if (e->sel_stream) { (void)hipStreamSynchronize(e->sel_stream); (void)hipStreamDestroy(e->sel_stream); }
     if (e->d_sel_len) (void)hipFree(e->d_sel_len);
     if (e->d_sel_sums) (void)hipFree(e->d_sel_sums);
+    if (e->d_comp) (void)hipFree(e->d_comp);
+    if (e->d_comp_len) (void)hipFree(e->d_comp_len);
+    if (e->d_comp_off) (void)hipFree(e->d_comp_off);
     for (void *q : e->retired) (void)hipFree(q);
     if (e->d_feed_tail) (void)hipFree(e->d_feed_tail);
     for (auto &p : e->feed_copies) (void)hipEventDestroy(p.second);
@@ -1081,20 +1096,38 @@ static uint32_t pieces_for(uint64_t need_max) {
 // --------------------------------------------------------------------------------------
 static uint64_t select_reserve_bytes(const pssbam_engine *e);   // (bgzf_api.h: what the sink's buffers take from the feed's memory budget)
 
-extern "C" int pssbam_engine_set_record_sink(pssbam_engine *e, pssbam_record_sink sink, void *ctx) {
+// (bgzf_api.h) deflate + scan + pack of a stream of at most max_bytes bytes, *d_total of them
+static int launch_deflate(hipStream_t st, const uint8_t *d_raw, uint64_t max_bytes, const unsigned long long *d_total, uint8_t *d_comp,
+                          uint32_t *d_comp_len, unsigned long long *d_comp_off, uint8_t *d_packed, unsigned long long *totals_out);
+
+static bool sink_on(const pssbam_engine *e) { return e->sink || e->block_sink; }
+
+// both setters: record != NULL sets the record sink, block != NULL the block sink, neither switches `which` off
+static int set_sink(pssbam_engine *e, pssbam_record_sink record, pssbam_block_sink block, void *ctx, bool which_block) {
+    const char *name = which_block ? "block" : "record";
     if (!e) return fail(PSSBAM_EINVAL, "null engine");
     if (e->tallied || e->cur_feed >= 0 || !e->deferred.empty() || !e->sel_queue.empty())
-        return fail(PSSBAM_ESTATE, "the record sink is set before the first submit (after create or reset)");
-    if (sink && !(e->cfg.tally_mask & PSSBAM_TALLY_PSS)) return fail(PSSBAM_EINVAL, "the record sink follows the substitution tally (PSSBAM_TALLY_PSS)");
+        return fail(PSSBAM_ESTATE, "the %s sink is set before the first submit (after create or reset)", name);
+    if ((record || block) && !(e->cfg.tally_mask & PSSBAM_TALLY_PSS)) return fail(PSSBAM_EINVAL, "the %s sink follows the substitution tally (PSSBAM_TALLY_PSS)", name);
+    if (block && e->sink) return fail(PSSBAM_EINVAL, "a record sink is set: the block sink goes instead of it, not beside it");
+    if (record && e->block_sink) return fail(PSSBAM_EINVAL, "a block sink is set: the record sink goes instead of it, not beside it");
     const uint64_t before = select_reserve_bytes(e);
-    e->sink = sink;
-    e->sink_ctx = sink ? ctx : nullptr;
+    if (which_block) {
+        e->block_sink = block;
+        e->block_ctx = block ? ctx : nullptr;
+    } else {
+        e->sink = record;
+        e->sink_ctx = record ? ctx : nullptr;
+    }
     if (e->feed_mem_budget) {   // worked out already (pssbam_engine_feed_open): the sink's buffers come out of it, or go back
         const uint64_t budget = e->feed_mem_budget + before, after = select_reserve_bytes(e);
         e->feed_mem_budget = budget > after ? budget - after : 1;
     }
     return PSSBAM_OK;
 }
+
+extern "C" int pssbam_engine_set_record_sink(pssbam_engine *e, pssbam_record_sink sink, void *ctx) { return set_sink(e, sink, nullptr, ctx, false); }
+extern "C" int pssbam_engine_set_block_sink(pssbam_engine *e, pssbam_block_sink sink, void *ctx) { return set_sink(e, nullptr, sink, ctx, true); }
 
 // Moves the buffers in flight along: a buffer whose totals have arrived starts the copy of its data, the oldest buffer
 // whose data has arrived is handed to the sink.  wait: until nothing is in flight.
@@ -1107,7 +1140,7 @@ static int select_poll(pssbam_engine *e, bool wait) {
             const hipError_t q = hipEventQuery(b.totals_ev);
             if (q == hipErrorNotReady) { (void)hipGetLastError(); break; }   // (the ones behind it are later on the same stream)
             if (q != hipSuccess) return fail(PSSBAM_EHIP, "hipEventQuery failed: %s", hipGetErrorString(q));
-            const uint64_t bytes = b.h_totals[0];
+            const uint64_t bytes = b.h_totals[b.deflated ? 2 : 0];
             if (bytes > b.out_cap) return fail(PSSBAM_EHIP, "record selection reports %llu bytes in a buffer of %zu", (unsigned long long)bytes, b.out_cap);
             if (bytes > b.h_cap) {
                 if (b.h_data) HIP_TRY(hipHostFree(b.h_data));
@@ -1127,9 +1160,15 @@ static int select_poll(pssbam_engine *e, bool wait) {
         if (q != hipSuccess) return fail(PSSBAM_EHIP, "hipEventQuery failed: %s", hipGetErrorString(q));
         b.state = SEL_FREE;
         e->sel_queue.erase(e->sel_queue.begin());
-        if (e->sink && b.h_totals[1] && e->sink(e->sink_ctx, b.h_data, b.h_totals[0], b.h_totals[1]) != 0) {
+        if (!b.deflated && e->sink && b.h_totals[1] && e->sink(e->sink_ctx, b.h_data, b.h_totals[0], b.h_totals[1]) != 0) {
             e->sink = nullptr;       // never called again; what is still in flight is dropped as it arrives
             e->sink_failed = true;   // reported by select_report, where the engine call can fail without leaving work half queued
+            e->block_sink_failed = false;
+        }
+        if (b.deflated && e->block_sink && b.h_totals[1] &&
+            e->block_sink(e->block_ctx, b.h_data, b.h_totals[2], b.h_totals[3], b.h_totals[0], b.h_totals[1]) != 0) {
+            e->block_sink = nullptr;
+            e->sink_failed = e->block_sink_failed = true;
         }
     }
     return PSSBAM_OK;
@@ -1142,12 +1181,12 @@ static int select_poll(pssbam_engine *e, bool wait) {
 static int select_report(pssbam_engine *e) {
     if (!e->sink_failed) return PSSBAM_OK;
     e->sink_failed = false;
-    return fail(PSSBAM_EINVAL, "the record sink returned non-zero");
+    return fail(PSSBAM_EINVAL, "the %s sink returned non-zero", e->block_sink_failed ? "block" : "record");
 }
 
 // the top of every submit: what has arrived goes out, before anything of this call is queued
 static int select_entry(pssbam_engine *e, uint64_t nbytes) {
-    if (e->sink && nbytes > 0xFFFFFF00ull) return fail(PSSBAM_EINVAL, "record block of %llu bytes is too large for the record sink", (unsigned long long)nbytes);
+    if (sink_on(e) && nbytes > 0xFFFFFF00ull) return fail(PSSBAM_EINVAL, "record block of %llu bytes is too large for the record sink", (unsigned long long)nbytes);
     if (!e->sel_queue.empty())
         if (const int rc = select_poll(e, false)) return rc;
     return select_report(e);
@@ -1170,16 +1209,19 @@ static int launch_select(pssbam_engine *e, const TallyParams &P, uint64_t nbytes
     const int k = e->sel_next;
     SelectBuf &b = e->sel[k];
     if (b.state != SEL_FREE && (rc = select_poll(e, true))) return rc;   // both buffers in flight: the older one first
-    if (!e->sink) return PSSBAM_OK;
+    if (!sink_on(e)) return PSSBAM_OK;
     if (!e->sel_stream) HIP_TRY(hipStreamCreateWithFlags(&e->sel_stream, hipStreamNonBlocking));
     if (!b.d_totals) {
-        HIP_TRY(hipMalloc((void **)&b.d_totals, 2 * sizeof(unsigned long long)));
-        HIP_TRY(hipHostMalloc((void **)&b.h_totals, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+        HIP_TRY(hipMalloc((void **)&b.d_totals, 4 * sizeof(unsigned long long)));
+        HIP_TRY(hipHostMalloc((void **)&b.h_totals, 4 * sizeof(unsigned long long), hipHostMallocDefault));
         HIP_TRY(hipEventCreateWithFlags(&b.totals_ev, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&b.data_ev, hipEventDisableTiming));
     }
     const uint32_t n = P.n_recs, n_tiles = (n + SELECT_SCAN_TILE - 1) / SELECT_SCAN_TILE;
-    const size_t out_need = (size_t)((nbytes + 15ull) & ~15ull) + 16;   // every record kept, whole 16-byte stores
+    const bool deflate = e->block_sink != nullptr;
+    const size_t n_blocks = (size_t)((nbytes + DFL_PAYLOAD - 1) / DFL_PAYLOAD);   // of the block sink: every record kept
+    // every record kept, whole 16-byte stores; the block sink packs its blocks into the same buffer: a stored block is 31 bytes over its payload
+    const size_t out_need = (size_t)((nbytes + 15ull) & ~15ull) + 16 + (deflate ? 31 * n_blocks : 0);
     if (b.out_cap < out_need) {
         if (b.d_out) HIP_TRY(hipFree(b.d_out));
         b.d_out = nullptr;
@@ -1188,6 +1230,20 @@ static int launch_select(pssbam_engine *e, const TallyParams &P, uint64_t nbytes
     }
     if ((rc = select_grow(&e->d_sel_len, &e->sel_len_cap, (size_t)n + 1))) return rc;
     if ((rc = select_grow(&e->d_sel_sums, &e->sel_sums_cap, (size_t)n_tiles))) return rc;
+    if (deflate && e->comp_cap < n_blocks) {
+        if (e->d_comp) HIP_TRY(hipFree(e->d_comp));   // (waits for the device: no kernel still reads it)
+        if (e->d_comp_len) HIP_TRY(hipFree(e->d_comp_len));
+        if (e->d_comp_off) HIP_TRY(hipFree(e->d_comp_off));
+        e->d_comp = nullptr;
+        e->d_comp_len = nullptr;
+        e->d_comp_off = nullptr;
+        e->comp_cap = 0;
+        const size_t cap_blocks = n_blocks + n_blocks / 8 + 16;
+        HIP_TRY(hipMalloc((void **)&e->d_comp, cap_blocks * DFL_SLOT));
+        HIP_TRY(hipMalloc((void **)&e->d_comp_len, cap_blocks * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void **)&e->d_comp_off, cap_blocks * sizeof(unsigned long long)));
+        e->comp_cap = cap_blocks;
+    }
     const uint32_t cap = (uint32_t)e->n_cu * 8u;
     const uint32_t g_mark = (uint32_t)std::min<uint64_t>(((uint64_t)n + 1 + 255) / 256, cap), g_tiles = std::min(n_tiles, cap);
     const uint64_t pieces = (nbytes / 16 + 1 + SELECT_GATHER_THREADS * SELECT_GATHER_CHUNKS - 1) / (SELECT_GATHER_THREADS * SELECT_GATHER_CHUNKS);
@@ -1200,12 +1256,14 @@ static int launch_select(pssbam_engine *e, const TallyParams &P, uint64_t nbytes
     hipLaunchKernelGGL(select_gather, dim3(g_gather), dim3(SELECT_GATHER_THREADS), 0, e->stream, P.recs, P.offs, (const uint32_t *)e->d_sel_len, n,
                        (const unsigned long long *)b.d_totals, b.d_out);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(b.h_totals, b.d_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    if (deflate && (rc = launch_deflate(e->stream, b.d_out, nbytes, b.d_totals, e->d_comp, e->d_comp_len, e->d_comp_off, b.d_out, b.d_totals + 2))) return rc;
+    b.deflated = deflate;
+    HIP_TRY(hipMemcpyAsync(b.h_totals, b.d_totals, (deflate ? 4 : 2) * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipEventRecord(b.totals_ev, e->stream));
     b.state = SEL_TOTALS;
     e->sel_queue.push_back(k);
     e->sel_next ^= 1;
-    e->sel_launches += 5;
+    e->sel_launches += deflate ? 8 : 5;
     return PSSBAM_OK;
 }
 
@@ -1503,7 +1561,7 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
     if (e->launch_events.size() > 4096)
         if (const int rc = resolve_launch_events(e)) return rc;
     // the record sink: the kept records of this block, behind its tally and in front of whatever frees the block's buffers
-    if (e->sink) return launch_select(e, P, nbytes);
+    if (sink_on(e)) return launch_select(e, P, nbytes);
     return PSSBAM_OK;
 }
 
@@ -1551,7 +1609,7 @@ extern "C" int pssbam_engine_submit_async(pssbam_engine *e, const void *records,
     int rc = check_ready(e);
     if (rc) return rc;
     if (ticket) *ticket = 0;
-    if (e->sink || e->sink_failed || !e->sel_queue.empty()) {   // the record sink: an empty submit is a poll, too
+    if (sink_on(e) || e->sink_failed || !e->sel_queue.empty()) {   // the record sink: an empty submit is a poll, too
         HIP_TRY(hipSetDevice(e->device));
         if ((rc = select_entry(e, n_records ? nbytes : 0))) return rc;
     }

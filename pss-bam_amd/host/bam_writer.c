@@ -276,6 +276,33 @@ int bam_writer_append(bam_writer *w, const void *records, size_t nbytes)
     return 0;
 }
 
+int bam_writer_append_blocks(bam_writer *w, const void *bgzf, size_t nbytes)
+{
+    if (!w) return -1;
+    if (w->failed) return -1;
+    /* the BSIZE chain first: nothing is written unless it covers the buffer exactly */
+    const uint8_t *p = (const uint8_t *)bgzf;
+    static const uint8_t head[4] = {0x1f, 0x8b, 0x08, 0x04};
+    for (size_t o = 0; o < nbytes;) {
+        if (nbytes - o < BGZF_HDR + BGZF_FTR) { set_err(w, "block set ends inside a BGZF block"); return -1; }
+        const uint8_t *b = p + o;
+        if (memcmp(b, head, 4) || b[10] != 6 || b[11] != 0 || b[12] != 'B' || b[13] != 'C' || b[14] != 2 || b[15] != 0) {
+            set_err(w, "block set: no BGZF header at byte %zu", o);
+            return -1;
+        }
+        const size_t len = (size_t)(b[16] | (uint32_t)b[17] << 8) + 1;
+        if (len < BGZF_HDR + BGZF_FTR) { set_err(w, "block set: BSIZE %zu at byte %zu is below a block's frame", len - 1, o); return -1; }
+        if (len > nbytes - o) { set_err(w, "block set ends inside a BGZF block"); return -1; }
+        o += len;
+    }
+    if (close_block(w) || flush_batch(w)) return -1;   /* what the writer holds goes first */
+    if (nbytes && fwrite(p, 1, nbytes, w->fp) != nbytes) {
+        set_err(w, "cannot write %s: %s", w->tmp, strerror(errno));
+        return -1;
+    }
+    return 0;
+}
+
 const char *bam_writer_error(const bam_writer *w) { return w ? w->err : "null writer"; }
 
 int bam_writer_close(bam_writer *w, char *err, size_t errlen)

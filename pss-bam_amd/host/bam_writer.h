@@ -31,6 +31,12 @@ const char *bam_writer_open_error(void);
 /* Whole records; a block is closed when the next record does not fit, a record larger than a
  * block spans blocks.  0, or -1 (bam_writer_error). */
 int bam_writer_append(bam_writer *w, const void *records, size_t nbytes);
+/* Whole BGZF blocks made elsewhere (the engine's block sink, pss-bam -O ... -Z), written as they are: what the writer
+ * holds (the header's blocks, records of earlier bam_writer_append calls) is closed and written first, so the two calls
+ * may be mixed on one writer and the file keeps their order.  The BSIZE chain is walked first: a buffer that is not a whole
+ * number of blocks with well-formed BGZF headers fails the call (and the writer) before a byte of it is written.  The
+ * payloads are not inflated or checked.  0, or -1 (bam_writer_error). */
+int bam_writer_append_blocks(bam_writer *w, const void *bgzf, size_t nbytes);
 /* Flushes, writes the EOF block, closes the file and renames it to its path.  0, or -1 after
  * removing the temporary file; the writer is freed either way (read the reason first with
  * bam_writer_error -- or pass err). */

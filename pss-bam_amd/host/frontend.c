@@ -88,6 +88,22 @@ static int out_sink(void *ctx, const void *records, uint64_t nbytes, uint64_t n_
     return 0;
 }
 
+/* -Z: the same behind the engine's block sink -- the blocks are written as they come */
+static int out_block_sink(void *ctx, const void *bgzf, uint64_t nbytes, uint64_t n_blocks, uint64_t raw_bytes, uint64_t n_records)
+{
+    (void)ctx;
+    (void)n_blocks;
+    (void)raw_bytes;
+    (void)n_records;
+    if (out_failed || out_open()) return 1;
+    if (bam_writer_append_blocks(out_writer, bgzf, (size_t)nbytes)) {
+        snprintf(out_err, sizeof out_err, "-O: %s", bam_writer_error(out_writer));
+        out_failed = 1;
+        return 1;
+    }
+    return 0;
+}
+
 /* gives up what was written so far (the run failed, or starts over with the host reader) */
 static void out_discard(void)
 {
@@ -208,7 +224,7 @@ static int apply_options(pssbam_engine *e)
            (o->gapped_reads && pssbam_engine_set_gapped_reads(e, 1)) || send_regions(e, o->regions) ||
            (o->n_length_edges > 0 && pssbam_engine_set_length_bins(e, o->n_length_edges, o->length_edges)) ||
            send_contig_sets(e, o->contig_sets) || (o->replicates > 0 && pssbam_engine_set_replicates(e, o->replicates)) ||
-           (o->out_bam && pssbam_engine_set_record_sink(e, out_sink, NULL));
+           (o->out_bam && (o->out_deflate ? pssbam_engine_set_block_sink(e, out_block_sink, NULL) : pssbam_engine_set_record_sink(e, out_sink, NULL)));
 }
 
 static void *engine_make_main(void *arg)

@@ -127,6 +127,9 @@ typedef struct frontend_options {
      * -- it takes its name only then -- before it returns, and removes it when the run fails.  BAM input, one GPU. */
     const char *out_bam;
     int out_level;
+    /* pss-bam -Z: the engine deflates the kept records into BGZF blocks itself (pssbam_engine_set_block_sink) and the writer
+     * only writes them (bam_writer_append_blocks); the header still goes through the writer's own blocks */
+    int out_deflate;
 } frontend_options;
 extern frontend_options frontend_opts;   /* everything off */
 

@@ -3,7 +3,10 @@
  * multi-threaded piece of the host library without a GPU and prints a digest of what came out:
  * the FASTA loader (block + parallel parser), the three-stage BGZF/BAM reader and the threaded
  * SAM-text reader; with -w also the BAM writer (bam_writer.h), which then receives every batch of a
- * BAM input as it comes from the reader.  It exists for the sanitizer builds (`make sanitize`: ThreadSanitizer and
+ * BAM input as it comes from the reader; with -w and -b the record stream is cut into BGZF payloads of 0xFF00 bytes at fixed
+ * offsets here (records cross blocks), every payload is deflated with zlib, and the finished blocks reach the writer through
+ * bam_writer_append_blocks in uneven pieces -- the path of pss-bam -O ... -Z without a GPU (-x trunc / -x chain damage the last
+ * piece: the call must fail and leave no file).  It exists for the sanitizer builds (`make sanitize`: ThreadSanitizer and
  * AddressSanitizer + UBSan; tests/test_sanitizers.py) -- the digests of the instrumented
  * binaries must equal the plain build's, and the sanitizers must stay silent.
  */
@@ -17,6 +20,8 @@
 #include "fasta-genome-io.h"
 #include "sam_reader.h"
 
+#include <zlib.h>
+
 static uint64_t fnv(uint64_t h, const void *p, size_t n)
 {
     const uint8_t *b = (const uint8_t *)p;
@@ -24,10 +29,86 @@ static uint64_t fnv(uint64_t h, const void *p, size_t n)
     return h;
 }
 
+/* -b: the blocks made so far and the tail of the stream that has not filled a payload yet */
+struct reblock {
+    uint8_t *pend, *blk;
+    size_t n_pend, cap_pend, n_blk, cap_blk, n_blocks, piece;
+    int level;
+};
+
+static int reblock_one(struct reblock *r, const uint8_t *src, uint32_t len)
+{
+    if (r->cap_blk - r->n_blk < 0x10000u) {
+        r->cap_blk = r->cap_blk * 2 + 0x20000u;
+        r->blk = (uint8_t *)realloc(r->blk, r->cap_blk);
+        if (!r->blk) return -1;
+    }
+    uint8_t *dst = r->blk + r->n_blk;
+    z_stream zs;
+    memset(&zs, 0, sizeof zs);
+    if (deflateInit2(&zs, r->level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return -1;
+    zs.next_in = (Bytef *)src;
+    zs.avail_in = len;
+    zs.next_out = dst + 18;
+    zs.avail_out = 0x10000u - 26u;
+    const int zrc = deflate(&zs, Z_FINISH);
+    const uint32_t total = 18u + (uint32_t)zs.total_out + 8u;
+    deflateEnd(&zs);
+    if (zrc != Z_STREAM_END) return -1;
+    static const uint8_t head[16] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0};
+    memcpy(dst, head, 16);
+    dst[16] = (uint8_t)((total - 1u) & 0xffu);
+    dst[17] = (uint8_t)((total - 1u) >> 8);
+    const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), src, len);
+    for (int i = 0; i < 4; i++) {
+        dst[total - 8 + i] = (uint8_t)(crc >> (8 * i));
+        dst[total - 4 + i] = (uint8_t)(len >> (8 * i));
+    }
+    r->n_blk += total;
+    r->n_blocks++;
+    return 0;
+}
+
+/* hands the blocks made so far to the writer once there are as many as the next piece takes: 1, 3, 7, 2, 5 blocks in turn */
+static int reblock_hand_over(struct reblock *r, bam_writer *wr, int last, const char *damage)
+{
+    static const size_t pieces[5] = {1, 3, 7, 2, 5};
+    if (!last && r->n_blocks < pieces[r->piece % 5]) return 0;
+    size_t n = r->n_blk;
+    if (last && damage && n) {
+        if (!strcmp(damage, "trunc")) n -= 5;
+        else r->blk[16] ^= 0x10;   /* chain: the first BSIZE of the piece no longer leads to a header */
+    }
+    const int rc = bam_writer_append_blocks(wr, r->blk, n);
+    r->n_blk = r->n_blocks = 0;
+    r->piece++;
+    return rc;
+}
+
+static int reblock_add(struct reblock *r, bam_writer *wr, const uint8_t *p, size_t n)
+{
+    if (r->cap_pend - r->n_pend < n) {
+        r->cap_pend = (r->n_pend + n) * 2;
+        r->pend = (uint8_t *)realloc(r->pend, r->cap_pend);
+        if (!r->pend) return -1;
+    }
+    memcpy(r->pend + r->n_pend, p, n);
+    r->n_pend += n;
+    size_t o = 0;
+    for (; r->n_pend - o >= BAM_WRITER_BLOCK_MAX; o += BAM_WRITER_BLOCK_MAX) {
+        if (reblock_one(r, r->pend + o, BAM_WRITER_BLOCK_MAX)) return -1;
+        if (reblock_hand_over(r, wr, 0, NULL)) return -1;
+    }
+    memmove(r->pend, r->pend + o, r->n_pend - o);
+    r->n_pend -= o;
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     const char *fa = NULL, *aln = NULL, *out = NULL;
-    int level = 1, wthreads = 0;
+    int level = 1, wthreads = 0, blocks = 0;
+    const char *damage = NULL;
     int quick = 0; /* -q: no digest, just drain the reader and report its inflate seconds (throughput probe) */
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-q")) { quick = 1; continue; }
@@ -36,9 +117,11 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "-w") && i + 1 < argc) out = argv[++i];
         else if (!strcmp(argv[i], "-z") && i + 1 < argc) level = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-t") && i + 1 < argc) wthreads = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "-b")) blocks = 1;
+        else if (!strcmp(argv[i], "-x") && i + 1 < argc) damage = argv[++i];
     }
     if (!fa && !aln) {
-        fprintf(stderr, "usage: hostcheck [-f genome.fa[.gz]] [-a file.bam|file.sam[.gz] [-w out.bam [-z level] [-t threads]]]\n");
+        fprintf(stderr, "usage: hostcheck [-f genome.fa[.gz]] [-a file.bam|file.sam[.gz] [-w out.bam [-z level] [-t threads] [-b [-x trunc|chain]]]]\n");
         return 2;
     }
     if (fa) {
@@ -66,6 +149,9 @@ int main(int argc, char **argv)
             wr = bam_writer_open(out, bam_reader_header(rd), level, wthreads);
             if (!wr) { fprintf(stderr, "hostcheck: %s\n", bam_writer_open_error()); return 1; }
         }
+        struct reblock rb;
+        memset(&rb, 0, sizeof rb);
+        rb.level = level;
         uint64_t h = 1469598103934665603ull, recs = 0, bytes = 0, batches = 0;
         for (;;) {
             const uint8_t *p;
@@ -81,7 +167,7 @@ int main(int argc, char **argv)
                 if (offs[i + 1] - offs[i] != 4u + bs) { fprintf(stderr, "hostcheck: record %lld mis-indexed\n", (long long)(recs + i)); return 1; }
             }
             if (!quick) h = fnv(h, p, nbytes);
-            if (wr && bam_writer_append(wr, p, nbytes)) {
+            if (wr && (blocks ? reblock_add(&rb, wr, p, nbytes) : bam_writer_append(wr, p, nbytes))) {
                 fprintf(stderr, "hostcheck: %s\n", bam_writer_error(wr));
                 bam_writer_abort(wr);
                 return 1;
@@ -89,6 +175,18 @@ int main(int argc, char **argv)
             recs += (uint64_t)n;
             bytes += nbytes;
             batches++;
+        }
+        if (wr && blocks) {   /* the short last payload, and whatever has not been handed over */
+            if ((rb.n_pend && reblock_one(&rb, rb.pend, (uint32_t)rb.n_pend)) || reblock_hand_over(&rb, wr, 1, damage)) {
+                fprintf(stderr, "hostcheck: %s\n", bam_writer_error(wr));
+                bam_writer_abort(wr);
+                free(rb.pend);
+                free(rb.blk);
+                bam_reader_close(rd);
+                return 1;
+            }
+            free(rb.pend);
+            free(rb.blk);
         }
         if (wr && bam_writer_close(wr, err, sizeof err)) { fprintf(stderr, "hostcheck: %s\n", err); return 1; }
         const int32_t n_ref = rd ? bam_reader_header(rd)->n_ref : sam_reader_n_ref(sd);

@@ -79,6 +79,9 @@
  * reads" speaks of.  -Q masks bases, not reads: it changes the file only through -y.  -z <level> (0..9, default 1) is its BGZF
  * compression level.  The file is written as <out.bam>.tmp and takes its name when it is complete; a failed run leaves none.  Goes
  * with every other option.  Needs BAM input and one GPU (PSSBAM_NGPU unset or 1); must not be the file -B names.
+ * Added: -Z, with -O: the file's blocks are deflated on the GPU in the same pass (the engine's block sink), not by zlib on the
+ * host; the kept records are cut every 0xFF00 bytes, records crossing blocks, the header stays in blocks of its own, and the file
+ * inflates to the bytes it inflates to without -Z.  Not with -z (zlib's level has no meaning there); refused without -O.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -126,8 +129,9 @@ int main(int argc, char *argv[])
     const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL, *bed_fn = NULL, *hist_arg = NULL, *site_arg = NULL, *end_arg = NULL;
     const char *max_mm_arg = NULL, *mm_hist_arg = NULL, *rep_arg = NULL, *interior_arg = NULL, *comp_arg = NULL, *min_score_arg = NULL;
     const char *out_bam = NULL, *out_level_arg = NULL;
+    int out_deflate = 0;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:P:y:YO:z:")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:P:y:YO:z:Z")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -159,6 +163,7 @@ int main(int argc, char *argv[])
         case 'Y': score_hist = 1; break;
         case 'O': out_bam = optarg; break;
         case 'z': out_level_arg = optarg; break;
+        case 'Z': out_deflate = 1; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -200,7 +205,8 @@ int main(int argc, char *argv[])
               "-y <t> <only tally the reads with a post-mortem-damage score of at least t nats (double-stranded model, held in units of 1/256 nat)>\n"
               "-Y <also write how many tallied reads have a post-mortem-damage score of -31 .. 30 nats and beyond; no parity with another implementation is claimed>\n"
               "-O <out.bam> <also write the tallied reads, as they are in the input and in its order, to this BAM (BAM input, one GPU)>\n"
-              "-z <level> <with -O: BGZF compression level 0..9 (default: 1)>\n",
+              "-z <level> <with -O: BGZF compression level 0..9 (default: 1)>\n"
+              "-Z <with -O: deflate the BAM's blocks on the GPU, not with zlib on the host (blocks cut every 0xFF00 bytes; not with -z)>\n",
               stderr);
         exit(1);
     }
@@ -242,6 +248,14 @@ int main(int argc, char *argv[])
             fprintf(stderr, "-z (compression level) needs -O (the BAM of the tallied reads).\n");
             exit(1);
         }
+    }
+    if (out_deflate && !out_bam) {
+        fprintf(stderr, "-Z (deflate on the GPU) needs -O (the BAM of the tallied reads).\n");
+        exit(1);
+    }
+    if (out_deflate && out_level_arg) {
+        fprintf(stderr, "-Z deflates on the GPU, where -z (zlib's compression level) has no meaning: one or the other.\n");
+        exit(1);
     }
     if (out_bam) {
         struct stat sa, sb;
@@ -458,7 +472,8 @@ int main(int argc, char *argv[])
     if (comp_arg) fprintf(stderr, " -P %d", composition);
     if (min_score_arg) fprintf(stderr, " -y %s", min_score_arg);
     if (score_hist) fprintf(stderr, " -Y");
-    if (out_bam) fprintf(stderr, " -O %s -z %d", out_bam, out_level);
+    if (out_bam && out_deflate) fprintf(stderr, " -O %s -Z", out_bam);
+    else if (out_bam) fprintf(stderr, " -O %s -z %d", out_bam, out_level);
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -498,6 +513,7 @@ int main(int argc, char *argv[])
     if (bed_fn) frontend_opts.regions = &bed;
     frontend_opts.out_bam = out_bam;
     frontend_opts.out_level = out_level;
+    frontend_opts.out_deflate = out_deflate;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
      * load; only the tally launches wait for the genome (frontend.c) */
