@@ -50,6 +50,11 @@ extern "C" {
 #define PSSBAM_SITE_NONE 0           /* pssbam_engine_set_site_context: off */
 #define PSSBAM_SITE_CPG 1            /* ... the reference position lies in a CpG dinucleotide */
 #define PSSBAM_MAX_END_DEPTH 8       /* pssbam_engine_set_end_condition: positions of an end that are searched for its mark */
+#define PSSBAM_END_MASK_OFF 0        /* pssbam_engine_set_end_mask: the sinks' records are the input's, byte for byte */
+#define PSSBAM_END_MASK_ALL 1        /* ... every base of the two end regions becomes N */
+#define PSSBAM_END_MASK_DS 2         /* ... only T in the 5' and A in the 3' region, in the read's orientation */
+#define PSSBAM_END_MASK_SS 3         /* ... only T in either region, in the read's orientation */
+#define PSSBAM_MAX_END_MASK 65535    /* pssbam_engine_set_end_mask: the widest region */
 
 /* error codes */
 #define PSSBAM_OK 0
@@ -638,7 +643,8 @@ int pssbam_engine_set_read_score(pssbam_engine *e, const int16_t *weights /*[4][
  * forward or the reverse main table -- the records for which PSSBAM_ST_PSS_OK counts, after every filter of the run (cfg.pss,
  * cfg.read_group, regions, gapped reads, the mismatch limit, the read score's minimum; each mate on its own; a minimum base
  * quality masks bases and drops no record, except through the score).  The sink receives whole records (le32 block_size +
- * body) back to back, byte-identical to the input and in input order across all submits, n_records of them in nbytes bytes;
+ * body) back to back, byte-identical to the input (unless an end mask is set: pssbam_engine_set_end_mask) and in input order
+ * across all submits, n_records of them in nbytes bytes;
  * the memory is valid during the call only.  It is called on the thread that calls the engine and nowhere else, from inside
  * the submit functions, pssbam_engine_sync, _finish and _reset: every submit delivers the chunks whose copy to the host has
  * completed, sync / finish / reset deliver everything outstanding before they return.  A block none of whose records is kept
@@ -682,6 +688,27 @@ int pssbam_engine_set_record_sink(pssbam_engine *e, pssbam_record_sink sink, voi
 typedef int (*pssbam_block_sink)(void *ctx, const void *bgzf, uint64_t nbytes, uint64_t n_blocks, uint64_t raw_bytes,
                                  uint64_t n_records);
 int pssbam_engine_set_block_sink(pssbam_engine *e, pssbam_block_sink sink, void *ctx);
+
+/* The end mask (pss-bam -K): the records a sink receives are the input's except at their masked positions, where the 4-bit
+ * SEQ code is 15 (N) and the QUAL byte 0; nothing else of a record changes, no length, and neither which records are kept nor
+ * their order.  With l = l_seq, rev = flag & 0x10 and i the 0-based index into SEQ as stored, the 5' region is i < min(n5, l)
+ * on a forward read and i >= l - min(n5, l) on a reverse one, the 3' region i >= l - min(n3, l) and i < min(n3, l).
+ * PSSBAM_END_MASK_ALL masks every position of either region; PSSBAM_END_MASK_DS (double-stranded library: C->T from the 5',
+ * G->A from the 3' end) the positions of the 5' region whose stored code is T (8) on a forward and A (1) on a reverse read and
+ * those of the 3' region whose stored code is A on a forward and T on a reverse read; PSSBAM_END_MASK_SS (C->T at both ends) the
+ * positions of either region whose stored code is T on a forward and A on a reverse read.  A position of both regions is
+ * masked when either rule masks it.  Soft-clipped bases are SEQ bases and count from the ends of SEQ; each mate goes by its own
+ * 0x10.  When the first QUAL byte is 0xFF (no qualities) QUAL is left alone.  A record whose fields do not fit inside it
+ * (36 + l_read_name + 4 * n_cigar_op + (l + 1) / 2 + l > 4 + block_size) goes out unchanged; no byte outside a record's own SEQ
+ * and QUAL is ever written.
+ * The mask acts on the sinks' copy alone, behind the tally and behind the selection (one more kernel between the gather and
+ * the deflate, csrc/end_mask_kernels.h; no memory of its own): tables, status counters, the set of kept records and the time
+ * and launch count of pssbam_engine_kernel_time are those of the run without it; a minimum base quality, the mismatch limit
+ * and the read score judge the unmasked read.  The block sink's blocks deflate the masked stream.  Without a sink, and with
+ * PSSBAM_END_MASK_OFF, it has no effect: nothing more is launched.  May be set before or after the sink.
+ * Legal before the first submit after create or reset (PSSBAM_ESTATE otherwise).  PSSBAM_EINVAL for an unknown mode, for
+ * n5 or n3 above PSSBAM_MAX_END_MASK, and for n5 == n3 == 0 with a mode other than PSSBAM_END_MASK_OFF.  The setting survives pssbam_engine_reset. */
+int pssbam_engine_set_end_mask(pssbam_engine *e, int32_t mode, uint32_t n5, uint32_t n3);
 
 /* Drains the engine like pssbam_engine_finish and copies the two arrays, 2 * hist_half words each; either pointer may be
  * NULL.  PSSBAM_EINVAL without a histogram. */

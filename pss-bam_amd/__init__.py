@@ -50,7 +50,7 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_interior", "pssbam_engine_finish_interior",
     "pssbam_engine_set_composition", "pssbam_engine_finish_composition",
     "pssbam_engine_set_read_score", "pssbam_engine_finish_read_score",
-    "pssbam_engine_set_record_sink", "pssbam_engine_set_block_sink",
+    "pssbam_engine_set_record_sink", "pssbam_engine_set_block_sink", "pssbam_engine_set_end_mask",
     "pssbam_bgzf_deflate_work_bytes", "pssbam_bgzf_deflate_device", "pssbam_bgzf_deflate_host",
 ]
 MAX_READ_GROUPS = 4096
@@ -70,6 +70,9 @@ MAX_REGIONS = 1 << 26
 SITE_NONE, SITE_CPG = 0, 1
 SITE_MODES = {None: SITE_NONE, "none": SITE_NONE, "cpg": SITE_CPG}
 MAX_END_DEPTH = 8
+END_MASK_OFF, END_MASK_ALL, END_MASK_DS, END_MASK_SS = 0, 1, 2, 3
+END_MASK_MODES = {None: END_MASK_OFF, "off": END_MASK_OFF, "all": END_MASK_ALL, "ds": END_MASK_DS, "ss": END_MASK_SS}
+MAX_END_MASK = 65535
 END_PRESETS = {"ss": (13, 13), "ds": (13, 2)}   # (cell5, cell3): C->T at both ends / C->T at the 5' end, G->A at the 3' end
 GAPPED_TILED_OPS = 16   # pss-bam -I: CIGAR ops a lane of the tiled kernel walks (csrc/record_decode.h); more take the one-lane path
 EBUSY = -7
@@ -175,6 +178,8 @@ def hip_lib() -> C.CDLL:
         L.pssbam_bgzf_deflate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]
         L.pssbam_bgzf_deflate_host.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                                C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.c_int]
+    if hasattr(L, "pssbam_engine_set_end_mask"):   # (tools/end_mask_bench.py also loads the library of the commit before it)
+        L.pssbam_engine_set_end_mask.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32]
     L.pssbam_index_records.restype = C.c_int64
     L.pssbam_index_records.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     _hip = L
@@ -788,6 +793,14 @@ class Engine:
         cb_c = _BLOCK_SINK(cb)
         _chk(self._L.pssbam_engine_set_block_sink(self._h, cb_c, None))
         self._block_cb = cb_c   # (kept alive with the engine)
+
+    def set_end_mask(self, mode, n5, n3=None):
+        """The end mask (pssbam_engine_set_end_mask): the first n5 bases of the 5' end and the first n3 (default: n5) of the 3'
+        end of every record a sink receives become N with quality 0 -- mode "all": every base there; "ds": T at the 5' and A
+        at the 3' end, in the read's orientation; "ss": T at both; None, "off" or 0: off.  The tables do not change.  Before
+        the first submit."""
+        m = END_MASK_MODES[mode] if mode is None or isinstance(mode, str) else int(mode)
+        _chk(self._L.pssbam_engine_set_end_mask(self._h, m, int(n5), int(n5 if n3 is None else n3)))
 
     def finish_blocks(self) -> np.ndarray:
         """sync, then every block collected since set_block_sink() / the last finish_blocks(), as one uint8 array;

@@ -28,6 +28,7 @@
 
 #include "tally_kernels.h"
 #include "select_kernels.h"
+#include "end_mask_kernels.h"
 #include "deflate_kernels.h"
 
 using namespace pssbam;
@@ -286,6 +287,8 @@ struct pssbam_engine {
     size_t sel_sums_cap = 0;
     hipStream_t sel_stream = nullptr;  // the D2H copies of the kept records, beside the next block's kernels
     uint64_t sel_launches = 0;         // (not part of kernel_launches: that count is the tally's)
+    // the end mask (pssbam_engine_set_end_mask, end_mask_kernels.h): one kernel between the gather and the deflate, nothing of its own
+    uint32_t end_mask_mode = PSSBAM_END_MASK_OFF, end_mask_n5 = 0, end_mask_n3 = 0;
     bool gapped = false;   // -I (pssbam_engine_set_gapped_reads): clipped and gapped reads are tallied by their anchored ends; no counter words
     int env_hist_lds_bins = -1;   // PSSBAM_HIST_LDS_BINS: at most this many bins of each array in LDS (tests: the global-atomic path with short reads)
     // -T (pssbam_engine_set_regions): contig name -> its merged intervals, kept on the host; the per-refID device table is
@@ -1129,6 +1132,23 @@ static int set_sink(pssbam_engine *e, pssbam_record_sink record, pssbam_block_si
 extern "C" int pssbam_engine_set_record_sink(pssbam_engine *e, pssbam_record_sink sink, void *ctx) { return set_sink(e, sink, nullptr, ctx, false); }
 extern "C" int pssbam_engine_set_block_sink(pssbam_engine *e, pssbam_block_sink sink, void *ctx) { return set_sink(e, nullptr, sink, ctx, true); }
 
+static_assert(PSSBAM_EM_OFF == PSSBAM_END_MASK_OFF && PSSBAM_EM_ALL == PSSBAM_END_MASK_ALL && PSSBAM_EM_DS == PSSBAM_END_MASK_DS &&
+              PSSBAM_EM_SS == PSSBAM_END_MASK_SS && PSSBAM_EM_MAX_N == PSSBAM_MAX_END_MASK, "end_mask_kernels.h and pssbam_hip.h name the same modes");
+
+extern "C" int pssbam_engine_set_end_mask(pssbam_engine *e, int32_t mode, uint32_t n5, uint32_t n3) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (e->tallied || e->cur_feed >= 0 || !e->deferred.empty() || !e->sel_queue.empty())
+        return fail(PSSBAM_ESTATE, "the end mask is set before the first submit (after create or reset)");
+    if (mode < PSSBAM_END_MASK_OFF || mode > PSSBAM_END_MASK_SS) return fail(PSSBAM_EINVAL, "end mask: unknown mode %d (0 off, 1 all, 2 ds, 3 ss)", (int)mode);
+    if (n5 > PSSBAM_MAX_END_MASK || n3 > PSSBAM_MAX_END_MASK)
+        return fail(PSSBAM_EINVAL, "end mask: the regions are at most %d bases wide, not %u and %u", PSSBAM_MAX_END_MASK, n5, n3);
+    if (mode != PSSBAM_END_MASK_OFF && n5 == 0 && n3 == 0) return fail(PSSBAM_EINVAL, "end mask: both regions are empty");
+    e->end_mask_mode = (uint32_t)mode;
+    e->end_mask_n5 = n5;
+    e->end_mask_n3 = n3;
+    return PSSBAM_OK;
+}
+
 // Moves the buffers in flight along: a buffer whose totals have arrived starts the copy of its data, the oldest buffer
 // whose data has arrived is handed to the sink.  wait: until nothing is in flight.
 static int select_poll(pssbam_engine *e, bool wait) {
@@ -1255,6 +1275,10 @@ static int launch_select(pssbam_engine *e, const TallyParams &P, uint64_t nbytes
                        (const unsigned long long *)b.d_totals);
     hipLaunchKernelGGL(select_gather, dim3(g_gather), dim3(SELECT_GATHER_THREADS), 0, e->stream, P.recs, P.offs, (const uint32_t *)e->d_sel_len, n,
                        (const unsigned long long *)b.d_totals, b.d_out);
+    const bool mask = e->end_mask_mode != PSSBAM_END_MASK_OFF;
+    if (mask)   // in the output copy, in front of the deflate and of the copy to the host (started behind totals_ev)
+        hipLaunchKernelGGL(select_mask_ends, dim3(std::max(1u, std::min((n + 255u) / 256u, cap))), dim3(256), 0, e->stream, b.d_out,
+                           (const uint32_t *)e->d_sel_len, n, nbytes, e->end_mask_mode, e->end_mask_n5, e->end_mask_n3);
     HIP_TRY(hipGetLastError());
     if (deflate && (rc = launch_deflate(e->stream, b.d_out, nbytes, b.d_totals, e->d_comp, e->d_comp_len, e->d_comp_off, b.d_out, b.d_totals + 2))) return rc;
     b.deflated = deflate;
@@ -1263,7 +1287,7 @@ static int launch_select(pssbam_engine *e, const TallyParams &P, uint64_t nbytes
     b.state = SEL_TOTALS;
     e->sel_queue.push_back(k);
     e->sel_next ^= 1;
-    e->sel_launches += deflate ? 8 : 5;
+    e->sel_launches += (deflate ? 8 : 5) + (mask ? 1 : 0);
     return PSSBAM_OK;
 }
 

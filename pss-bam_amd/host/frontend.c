@@ -224,7 +224,8 @@ static int apply_options(pssbam_engine *e)
            (o->gapped_reads && pssbam_engine_set_gapped_reads(e, 1)) || send_regions(e, o->regions) ||
            (o->n_length_edges > 0 && pssbam_engine_set_length_bins(e, o->n_length_edges, o->length_edges)) ||
            send_contig_sets(e, o->contig_sets) || (o->replicates > 0 && pssbam_engine_set_replicates(e, o->replicates)) ||
-           (o->out_bam && (o->out_deflate ? pssbam_engine_set_block_sink(e, out_block_sink, NULL) : pssbam_engine_set_record_sink(e, out_sink, NULL)));
+           (o->out_bam && (o->out_deflate ? pssbam_engine_set_block_sink(e, out_block_sink, NULL) : pssbam_engine_set_record_sink(e, out_sink, NULL))) ||
+           (o->out_bam && o->out_mask_mode != PSSBAM_END_MASK_OFF && pssbam_engine_set_end_mask(e, o->out_mask_mode, o->out_mask_n5, o->out_mask_n3));
 }
 
 static void *engine_make_main(void *arg)

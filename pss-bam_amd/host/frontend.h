@@ -130,6 +130,10 @@ typedef struct frontend_options {
     /* pss-bam -Z: the engine deflates the kept records into BGZF blocks itself (pssbam_engine_set_block_sink) and the writer
      * only writes them (bam_writer_append_blocks); the header still goes through the writer's own blocks */
     int out_deflate;
+    /* pss-bam -K: the end mask of the -O file (PSSBAM_END_MASK_*; PSSBAM_END_MASK_OFF: none) and the widths of its 5' and 3'
+     * regions; the run's one engine gets them beside its sink (pssbam_engine_set_end_mask) */
+    int out_mask_mode;
+    uint32_t out_mask_n5, out_mask_n3;
 } frontend_options;
 extern frontend_options frontend_opts;   /* everything off */
 

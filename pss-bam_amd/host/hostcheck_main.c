@@ -6,7 +6,9 @@
  * BAM input as it comes from the reader; with -w and -b the record stream is cut into BGZF payloads of 0xFF00 bytes at fixed
  * offsets here (records cross blocks), every payload is deflated with zlib, and the finished blocks reach the writer through
  * bam_writer_append_blocks in uneven pieces -- the path of pss-bam -O ... -Z without a GPU (-x trunc / -x chain damage the last
- * piece: the call must fail and leave no file).  It exists for the sanitizer builds (`make sanitize`: ThreadSanitizer and
+ * piece: the call must fail and leave no file); with -w and -K <all|ds|ss>,<n5>[,<n3>] every record passes through the end mask
+ * of pss-bam -K on its way to the writer -- the per-record function the device kernel runs (csrc/end_mask_kernels.h), compiled
+ * for the host.  It exists for the sanitizer builds (`make sanitize`: ThreadSanitizer and
  * AddressSanitizer + UBSan; tests/test_sanitizers.py) -- the digests of the instrumented
  * binaries must equal the plain build's, and the sanitizers must stay silent.
  */
@@ -17,6 +19,8 @@
 
 #include "bam_reader.h"
 #include "bam_writer.h"
+#include "end_mask.h"
+#include "end_mask_kernels.h"
 #include "fasta-genome-io.h"
 #include "sam_reader.h"
 
@@ -108,7 +112,11 @@ int main(int argc, char **argv)
 {
     const char *fa = NULL, *aln = NULL, *out = NULL;
     int level = 1, wthreads = 0, blocks = 0;
-    const char *damage = NULL;
+    const char *damage = NULL, *mask_arg = NULL;
+    int mask_mode = PSSBAM_EM_OFF;
+    uint32_t mask_n5 = 0, mask_n3 = 0;
+    uint8_t *masked = NULL;   /* -K: the batch on its way to the writer */
+    size_t masked_cap = 0;
     int quick = 0; /* -q: no digest, just drain the reader and report its inflate seconds (throughput probe) */
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-q")) { quick = 1; continue; }
@@ -119,9 +127,15 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "-t") && i + 1 < argc) wthreads = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-b")) blocks = 1;
         else if (!strcmp(argv[i], "-x") && i + 1 < argc) damage = argv[++i];
+        else if (!strcmp(argv[i], "-K") && i + 1 < argc) mask_arg = argv[++i];
+    }
+    if (mask_arg) {
+        char err[200];
+        if (pss_parse_end_mask(mask_arg, &mask_mode, &mask_n5, &mask_n3, err, sizeof err)) { fprintf(stderr, "hostcheck: %s\n", err); return 1; }
+        if (!out) { fprintf(stderr, "hostcheck: -K masks what -w writes\n"); return 1; }
     }
     if (!fa && !aln) {
-        fprintf(stderr, "usage: hostcheck [-f genome.fa[.gz]] [-a file.bam|file.sam[.gz] [-w out.bam [-z level] [-t threads] [-b [-x trunc|chain]]]]\n");
+        fprintf(stderr, "usage: hostcheck [-f genome.fa[.gz]] [-a file.bam|file.sam[.gz] [-w out.bam [-z level] [-t threads] [-b [-x trunc|chain]] [-K mode,n5[,n3]]]]\n");
         return 2;
     }
     if (fa) {
@@ -167,6 +181,17 @@ int main(int argc, char **argv)
                 if (offs[i + 1] - offs[i] != 4u + bs) { fprintf(stderr, "hostcheck: record %lld mis-indexed\n", (long long)(recs + i)); return 1; }
             }
             if (!quick) h = fnv(h, p, nbytes);
+            if (wr && mask_mode != PSSBAM_EM_OFF) {   /* a buffer of exactly the batch's size: a stray write is one past a heap block */
+                if (masked_cap != nbytes) {
+                    free(masked);
+                    masked = (uint8_t *)malloc(nbytes ? nbytes : 1);
+                    masked_cap = nbytes;
+                    if (!masked) { fprintf(stderr, "hostcheck: out of memory\n"); return 1; }
+                }
+                memcpy(masked, p, nbytes);
+                for (int64_t i = 0; i < n; i++) pssbam_end_mask_record(masked + offs[i], offs[i + 1] - offs[i], (uint32_t)mask_mode, mask_n5, mask_n3);
+                p = masked;
+            }
             if (wr && (blocks ? reblock_add(&rb, wr, p, nbytes) : bam_writer_append(wr, p, nbytes))) {
                 fprintf(stderr, "hostcheck: %s\n", bam_writer_error(wr));
                 bam_writer_abort(wr);
@@ -188,6 +213,7 @@ int main(int argc, char **argv)
             free(rb.pend);
             free(rb.blk);
         }
+        free(masked);
         if (wr && bam_writer_close(wr, err, sizeof err)) { fprintf(stderr, "hostcheck: %s\n", err); return 1; }
         const int32_t n_ref = rd ? bam_reader_header(rd)->n_ref : sam_reader_n_ref(sd);
         printf("alignments input=%s refs=%d records=%llu bytes=%llu digest=%016llx\n", is_bam ? "bam" : "sam", n_ref,

@@ -75,13 +75,18 @@
  * -H, -X, -E, -I, -A, -n, -N, -V, -J, -W or -P.
  * Added: -O <out.bam> also writes a BAM that holds exactly the alignment records that were added to the forward or the reverse
  * table of this run -- after every filter given, each mate judged on its own -- in input order and byte for byte as they are in the
- * input, under the input's header (no @PG line), from the same pass: the file the other options' "the input without the other
+ * input (unless -K), under the input's header (no @PG line), from the same pass: the file the other options' "the input without the other
  * reads" speaks of.  -Q masks bases, not reads: it changes the file only through -y.  -z <level> (0..9, default 1) is its BGZF
  * compression level.  The file is written as <out.bam>.tmp and takes its name when it is complete; a failed run leaves none.  Goes
  * with every other option.  Needs BAM input and one GPU (PSSBAM_NGPU unset or 1); must not be the file -B names.
  * Added: -Z, with -O: the file's blocks are deflated on the GPU in the same pass (the engine's block sink), not by zlib on the
  * host; the kept records are cut every 0xFF00 bytes, records crossing blocks, the header stays in blocks of its own, and the file
  * inflates to the bytes it inflates to without -Z.  Not with -z (zlib's level has no meaning there); refused without -O.
+ * Added: -K <all|ds|ss>,<n5>[,<n3>], with -O: in the file's records the first n5 bases of the 5' end and the first n3 (default: n5)
+ * of the 3' end of each read -- all of them (all), the T of the 5' and the A of the 3' end (ds: a double-stranded library's C->T
+ * and G->A) or the T of both ends (ss), in the read's orientation -- are N with quality 0, from the same pass (the engine's end
+ * mask, include/pssbam_hip.h); everything else of the file is what it is without -K, and so is every other file: the tables are
+ * those of the unmasked reads.  Goes with -Z, -z and every option -O goes with; refused without -O.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -96,6 +101,7 @@
 #include "base_quality.h"
 #include "composition.h"
 #include "contig_sets.h"
+#include "end_mask.h"
 #include "fasta-genome-io.h"
 #include "frontend.h"
 #include "interior.h"
@@ -129,9 +135,10 @@ int main(int argc, char *argv[])
     const char *len_edges = NULL, *ctg_map = NULL, *min_bq_arg = NULL, *bed_fn = NULL, *hist_arg = NULL, *site_arg = NULL, *end_arg = NULL;
     const char *max_mm_arg = NULL, *mm_hist_arg = NULL, *rep_arg = NULL, *interior_arg = NULL, *comp_arg = NULL, *min_score_arg = NULL;
     const char *out_bam = NULL, *out_level_arg = NULL;
+    const char *out_mask_arg = NULL;
     int out_deflate = 0;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:P:y:YO:z:Z")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:P:y:YO:z:ZK:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -164,6 +171,7 @@ int main(int argc, char *argv[])
         case 'O': out_bam = optarg; break;
         case 'z': out_level_arg = optarg; break;
         case 'Z': out_deflate = 1; break;
+        case 'K': out_mask_arg = optarg; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -206,7 +214,8 @@ int main(int argc, char *argv[])
               "-Y <also write how many tallied reads have a post-mortem-damage score of -31 .. 30 nats and beyond; no parity with another implementation is claimed>\n"
               "-O <out.bam> <also write the tallied reads, as they are in the input and in its order, to this BAM (BAM input, one GPU)>\n"
               "-z <level> <with -O: BGZF compression level 0..9 (default: 1)>\n"
-              "-Z <with -O: deflate the BAM's blocks on the GPU, not with zlib on the host (blocks cut every 0xFF00 bytes; not with -z)>\n",
+              "-Z <with -O: deflate the BAM's blocks on the GPU, not with zlib on the host (blocks cut every 0xFF00 bytes; not with -z)>\n"
+              "-K <all|ds|ss>,<n5>[,<n3>] <with -O: in that BAM, mask the first n5 bases of the 5' and n3 (default: n5) of the 3' end of each read with N, quality 0: all of them, T at 5' / A at 3' (ds) or T at both (ss)>\n",
               stderr);
         exit(1);
     }
@@ -256,6 +265,19 @@ int main(int argc, char *argv[])
     if (out_deflate && out_level_arg) {
         fprintf(stderr, "-Z deflates on the GPU, where -z (zlib's compression level) has no meaning: one or the other.\n");
         exit(1);
+    }
+    int out_mask_mode = PSSBAM_END_MASK_OFF;
+    uint32_t out_mask_n5 = 0, out_mask_n3 = 0;
+    if (out_mask_arg) {
+        char err[200];
+        if (pss_parse_end_mask(out_mask_arg, &out_mask_mode, &out_mask_n5, &out_mask_n3, err, sizeof err)) {
+            fprintf(stderr, "%s\n", err);
+            exit(1);
+        }
+        if (!out_bam) {
+            fprintf(stderr, "-K (mask the read ends) needs -O (the BAM of the tallied reads).\n");
+            exit(1);
+        }
     }
     if (out_bam) {
         struct stat sa, sb;
@@ -474,6 +496,7 @@ int main(int argc, char *argv[])
     if (score_hist) fprintf(stderr, " -Y");
     if (out_bam && out_deflate) fprintf(stderr, " -O %s -Z", out_bam);
     else if (out_bam) fprintf(stderr, " -O %s -z %d", out_bam, out_level);
+    if (out_mask_arg) fprintf(stderr, " -K %s,%u,%u", out_mask_mode == PSSBAM_END_MASK_ALL ? "all" : out_mask_mode == PSSBAM_END_MASK_DS ? "ds" : "ss", out_mask_n5, out_mask_n3);
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -514,6 +537,9 @@ int main(int argc, char *argv[])
     frontend_opts.out_bam = out_bam;
     frontend_opts.out_level = out_level;
     frontend_opts.out_deflate = out_deflate;
+    frontend_opts.out_mask_mode = out_mask_mode;
+    frontend_opts.out_mask_n5 = out_mask_n5;
+    frontend_opts.out_mask_n3 = out_mask_n3;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
      * load; only the tally launches wait for the genome (frontend.c) */
