@@ -710,6 +710,39 @@ int pssbam_engine_set_block_sink(pssbam_engine *e, pssbam_block_sink sink, void 
  * n5 or n3 above PSSBAM_MAX_END_MASK, and for n5 == n3 == 0 with a mode other than PSSBAM_END_MASK_OFF.  The setting survives pssbam_engine_reset. */
 int pssbam_engine_set_end_mask(pssbam_engine *e, int32_t mode, uint32_t n5, uint32_t n3);
 
+/* Duplicate flagging (pss-bam -d, fragkon -d): with the setting on, a run equals the same run on the same input after the
+ * duplicates, as defined here, have had FLAG bit 0x400 set.  The engine sets that bit in its device copy of every block, in front
+ * of the block's tally kernels (csrc/dedup_kernels.h), so every other setting works on the deduplicated input unchanged: a flagged
+ * record counts as PSSBAM_ST_PSS_FILTERED / _KMER_FILTERED and reaches no table, plane, histogram or sink.
+ *   Input order: the order of the submit calls, and the record order inside each block.
+ *   Eligible: an unpaired record (FLAG 0x1 clear) that is a candidate of the engine's tool -- not dropped by cfg.read_group, not a
+ *     parse skip, contig known, none of 0x4 0x100 0x200 0x400 0x800, CIGAR exactly <L>M, the tool's mapping quality and length
+ *     window, inside the contig by the tool's margin, and the regions when set.  What looks at the read's bases or at the reference
+ *     (-U / -D contexts, a minimum base quality, the mismatch limit, the read score) takes no part: those filters apply after
+ *     deduplication, so a group whose first record fails one of them contributes nothing.
+ *   Key: (refID, POS, L, FLAG & 0x10, g); L = the SEQ length, g = with read groups (pssbam_engine_set_read_groups) 0 for the
+ *     unassigned bucket and 1 + the group's index otherwise, without them 0: duplicates are per library.
+ *   Duplicate: an eligible record with an earlier eligible record of the same key, in input order, across all blocks since create
+ *     or reset.  The first record of a key wins (not the one with the best base qualities: that needs look-ahead across blocks).
+ *     The result depends neither on how the input is cut into blocks, nor on its being sorted, nor on GPU scheduling.
+ *   Paired and ineligible records are never flagged and shadow nothing; records that arrive flagged 0x400 stay flagged and count
+ *     nowhere.  Pairing mates is out of scope.
+ * on != 0 switches it on; initial_slots is the first size of the key table, rounded up to a power of two (0 = the engine's default;
+ * the table doubles as the run needs, PSSBAM_ENOMEM from the submit that cannot grow it).  Legal after create or reset and before
+ * the first submit (with pssbam_engine_feed_open: before the first submit_bgzf), PSSBAM_ESTATE later.  It goes with every other
+ * setting except gapped reads (pssbam_engine_set_gapped_reads): PSSBAM_EINVAL in either order of the two calls, and on an engine
+ * with PSSBAM_TALLY_PSS | PSSBAM_TALLY_KMER together, whose two eligibilities differ.  The counter block keeps its size and layout,
+ * and the time and launch count of pssbam_engine_kernel_time stay the tally's.  The setting survives pssbam_engine_reset, which
+ * empties the table.  Engines do not share a table.  Off, nothing is allocated and nothing more is launched.
+ * With pssbam_engine_submit_device the device copy is the caller's: the engine sets bit 0x400 of the duplicates' FLAG in the
+ * caller's buffer.  A caller who needs the bytes unchanged uses pssbam_engine_submit. */
+#define PSSBAM_MAX_DUP_HIST 65535
+int pssbam_engine_set_duplicates(pssbam_engine *e, int32_t on, uint32_t initial_slots);
+/* Drains like pssbam_engine_finish.  totals = {eligible records, distinct keys, records flagged = eligible - distinct};
+ * hist[c], c in 1..hist_max: keys with exactly c eligible records; hist[hist_max+1]: keys with more; hist[0] = 0;
+ * hist_max+2 words, hist may be NULL.  PSSBAM_EINVAL when the setting is off. */
+int pssbam_engine_finish_duplicates(pssbam_engine *e, uint64_t totals[3], uint64_t *hist, int32_t hist_max);
+
 /* Drains the engine like pssbam_engine_finish and copies the two arrays, 2 * hist_half words each; either pointer may be
  * NULL.  PSSBAM_EINVAL without a histogram. */
 int pssbam_engine_finish_read_score(pssbam_engine *e, uint64_t *fwd, uint64_t *rev);

@@ -51,6 +51,7 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_composition", "pssbam_engine_finish_composition",
     "pssbam_engine_set_read_score", "pssbam_engine_finish_read_score",
     "pssbam_engine_set_record_sink", "pssbam_engine_set_block_sink", "pssbam_engine_set_end_mask",
+    "pssbam_engine_set_duplicates", "pssbam_engine_finish_duplicates",
     "pssbam_bgzf_deflate_work_bytes", "pssbam_bgzf_deflate_device", "pssbam_bgzf_deflate_host",
 ]
 MAX_READ_GROUPS = 4096
@@ -73,6 +74,7 @@ MAX_END_DEPTH = 8
 END_MASK_OFF, END_MASK_ALL, END_MASK_DS, END_MASK_SS = 0, 1, 2, 3
 END_MASK_MODES = {None: END_MASK_OFF, "off": END_MASK_OFF, "all": END_MASK_ALL, "ds": END_MASK_DS, "ss": END_MASK_SS}
 MAX_END_MASK = 65535
+MAX_DUP_HIST = 65535
 END_PRESETS = {"ss": (13, 13), "ds": (13, 2)}   # (cell5, cell3): C->T at both ends / C->T at the 5' end, G->A at the 3' end
 GAPPED_TILED_OPS = 16   # pss-bam -I: CIGAR ops a lane of the tiled kernel walks (csrc/record_decode.h); more take the one-lane path
 EBUSY = -7
@@ -181,6 +183,9 @@ def hip_lib() -> C.CDLL:
     if hasattr(L, "pssbam_engine_set_end_mask"):   # (tools/end_mask_bench.py also loads the library of the commit before it)
         L.pssbam_engine_set_end_mask.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32]
     L.pssbam_index_records.restype = C.c_int64
+    if hasattr(L, "pssbam_engine_set_duplicates"):   # (tools/dedup_bench.py also loads the library of the commit before it)
+        L.pssbam_engine_set_duplicates.argtypes = [C.c_void_p, C.c_int32, C.c_uint32]
+        L.pssbam_engine_finish_duplicates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     L.pssbam_index_records.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     _hip = L
     return L
@@ -801,6 +806,21 @@ class Engine:
         the first submit."""
         m = END_MASK_MODES[mode] if mode is None or isinstance(mode, str) else int(mode)
         _chk(self._L.pssbam_engine_set_end_mask(self._h, m, int(n5), int(n5 if n3 is None else n3)))
+
+    def set_duplicates(self, on: bool = True, initial_slots: int = 0):
+        """Duplicate flagging (pssbam_engine_set_duplicates): the engine sets FLAG 0x400 of every eligible unpaired record that an
+        earlier one, in input order, shares (refID, POS, SEQ length, strand, read-group plane) with, in its device copy and in front
+        of the tally.  initial_slots: the key table's first size (0 = the default; it doubles as needed).  Before the first submit;
+        not with set_gapped, not on an engine with both tallies."""
+        _chk(self._L.pssbam_engine_set_duplicates(self._h, 1 if on else 0, int(initial_slots)))
+
+    def finish_duplicates(self, hist_max: int = 255) -> tuple[dict, np.ndarray]:
+        """sync, then ({"eligible", "distinct", "flagged"}, hist): hist[c] = the keys with exactly c eligible records for c in
+        1..hist_max, hist[hist_max + 1] the keys with more"""
+        totals = np.zeros(3, dtype=np.uint64)
+        hist = np.zeros(int(hist_max) + 2, dtype=np.uint64)
+        _chk(self._L.pssbam_engine_finish_duplicates(self._h, totals.ctypes.data, hist.ctypes.data, int(hist_max)))
+        return dict(zip(("eligible", "distinct", "flagged"), (int(v) for v in totals))), hist
 
     def finish_blocks(self) -> np.ndarray:
         """sync, then every block collected since set_block_sink() / the last finish_blocks(), as one uint8 array;

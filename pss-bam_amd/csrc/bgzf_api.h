@@ -599,6 +599,15 @@ static uint64_t select_reserve_bytes(const pssbam_engine *e) {
     return records + blocks * (pssbam::DFL_SLOT + 12 + 2 * 31);
 }
 
+// what duplicate flagging (pssbam_engine_set_duplicates) takes beside the ring: the first table three times over -- itself, and the
+// doubled one that lives beside it during a rehash -- and slot_of[] of a whole tally sub-batch.  A table that outgrows this is
+// allocated from what the device has left, PSSBAM_ENOMEM when that fails.
+static uint64_t dedup_reserve_bytes(const pssbam_engine *e) {
+    if (!e->dedup) return 0;
+    const uint64_t sub = std::min<uint64_t>(FEED_SUB_MAX, e->feed_out_target) + 2 * FEED_GAP;
+    return 3 * dedup_first_slots(e) * sizeof(pssbam::DedupSlot) + sub / 36 * sizeof(uint32_t);
+}
+
 // buffers of a super-batch that do not depend on its contents
 static int feed_prepare(pssbam_engine *e, FeedAcc &s) {
     const size_t out_need = (size_t)(FEED_GAP + e->feed_out_target + FEED_OUT_SLACK);
@@ -643,7 +652,7 @@ static int feed_acquire(pssbam_engine *e, int *out_slot, bool force) {
             size_t free_b = 0, total_b = 0;
             if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 64ull << 30;
             const uint64_t used = e->feed.size() * feed_slot_bytes(e);
-            const uint64_t keep = (24ull << 30) + select_reserve_bytes(e);
+            const uint64_t keep = (24ull << 30) + select_reserve_bytes(e) + dedup_reserve_bytes(e);
             e->feed_mem_budget = used + (free_b > keep ? free_b - keep : 0);   // leaves room for genome, 4-bit image, k-mer bins
         }
         limit = std::max<size_t>(FEED_SLOTS_READY, (size_t)(e->feed_mem_budget / feed_slot_bytes(e)));
@@ -933,7 +942,7 @@ extern "C" int pssbam_engine_feed_open(pssbam_engine *e, int32_t n_ref, uint64_t
     e->feed_n_ref = n_ref;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const uint64_t keep = genome_bytes_hint + genome_bytes_hint / 2 + (8ull << 30) + select_reserve_bytes(e);   // genome + 4-bit image + slack (+ the record sink's buffers)
+        const uint64_t keep = genome_bytes_hint + genome_bytes_hint / 2 + (8ull << 30) + select_reserve_bytes(e) + dedup_reserve_bytes(e);   // genome + 4-bit image + slack (+ the record sink's buffers, the duplicate table)
         e->feed_mem_budget = e->feed.size() * feed_slot_bytes(e) + (free_b > keep ? free_b - keep : 0);
     }
     return PSSBAM_OK;

@@ -29,6 +29,7 @@
 #include "tally_kernels.h"
 #include "select_kernels.h"
 #include "end_mask_kernels.h"
+#include "dedup_kernels.h"
 #include "deflate_kernels.h"
 
 using namespace pssbam;
@@ -289,6 +290,24 @@ struct pssbam_engine {
     uint64_t sel_launches = 0;         // (not part of kernel_launches: that count is the tally's)
     // the end mask (pssbam_engine_set_end_mask, end_mask_kernels.h): one kernel between the gather and the deflate, nothing of its own
     uint32_t end_mask_mode = PSSBAM_END_MASK_OFF, end_mask_n5 = 0, end_mask_n3 = 0;
+    // duplicate flagging (pssbam_engine_set_duplicates, dedup_kernels.h).  Off: nothing below is allocated and nothing more is launched.
+    // The table holds dedup_cap slots (a power of two, 0: not allocated yet); d_dedup_slot is slot_of[] of the block being flagged
+    // (stream order keeps the blocks apart); d_dedup_state the device's {occupied slots | DEDUP_FULL}, read back through
+    // h_dedup_state behind a block's resolve kernel and an event that is polled, never waited on: dedup_known is the last value
+    // that arrived and dedup_known_at the records submitted up to that reading (the host's bound), dedup_submitted all of them.
+    bool dedup = false;
+    uint32_t dedup_initial = 0;        // the first table's slots as the caller asked (0: DEDUP_DEFAULT_SLOTS)
+    DedupSlot *d_dedup = nullptr;
+    uint64_t dedup_cap = 0;
+    uint32_t *d_dedup_slot = nullptr;
+    size_t dedup_slot_cap = 0;
+    unsigned long long *d_dedup_state = nullptr, *h_dedup_state = nullptr;
+    hipEvent_t dedup_ev = nullptr;
+    bool dedup_reading = false;        // a copy of the state word is on its way
+    uint64_t dedup_known = 0, dedup_known_at = 0, dedup_reading_at = 0, dedup_submitted = 0;
+    uint32_t dedup_seq = 0;            // blocks flagged since create / reset: the high word of a record's ordinal
+    uint64_t dedup_launches = 0;       // (not part of kernel_launches: that count is the tally's)
+    std::vector<std::pair<void *, hipEvent_t>> dedup_old;   // tables replaced by a larger one: freed once the stream has passed the rehash
     bool gapped = false;   // -I (pssbam_engine_set_gapped_reads): clipped and gapped reads are tallied by their anchored ends; no counter words
     int env_hist_lds_bins = -1;   // PSSBAM_HIST_LDS_BINS: at most this many bins of each array in LDS (tests: the global-atomic path with short reads)
     // -T (pssbam_engine_set_regions): contig name -> its merged intervals, kept on the host; the per-refID device table is
@@ -550,6 +569,12 @@ extern "C" void pssbam_engine_destroy(pssbam_engine *e) {
     }
     if (e->sel_stream) { (void)hipStreamSynchronize(e->sel_stream); (void)hipStreamDestroy(e->sel_stream); }
     if (e->d_sel_len) (void)hipFree(e->d_sel_len);
+    for (auto &p : e->dedup_old) { (void)hipFree(p.first); (void)hipEventDestroy(p.second); }
+    if (e->d_dedup) (void)hipFree(e->d_dedup);
+    if (e->d_dedup_slot) (void)hipFree(e->d_dedup_slot);
+    if (e->d_dedup_state) (void)hipFree(e->d_dedup_state);
+    if (e->h_dedup_state) (void)hipHostFree(e->h_dedup_state);
+    if (e->dedup_ev) (void)hipEventDestroy(e->dedup_ev);
     if (e->d_sel_sums) (void)hipFree(e->d_sel_sums);
     if (e->d_comp) (void)hipFree(e->d_comp);
     if (e->d_comp_len) (void)hipFree(e->d_comp_len);
@@ -1291,6 +1316,109 @@ static int launch_select(pssbam_engine *e, const TallyParams &P, uint64_t nbytes
     return PSSBAM_OK;
 }
 
+// --------------------------------------------------------------------------------------
+// duplicate flagging: insert + resolve in front of a block's tally kernels (dedup_kernels.h)
+// --------------------------------------------------------------------------------------
+static constexpr uint64_t DEDUP_DEFAULT_SLOTS = 1ull << 20, DEDUP_MAX_SLOTS = 1ull << 31;   // (a slot index fits slot_of[]'s 32 bits beside DEDUP_NO_SLOT)
+
+static uint64_t dedup_first_slots(const pssbam_engine *e) {
+    uint64_t cap = 16;
+    const uint64_t want = e->dedup_initial ? e->dedup_initial : DEDUP_DEFAULT_SLOTS;
+    while (cap < want) cap <<= 1;
+    return cap;
+}
+
+static uint64_t dedup_reserve_bytes(const pssbam_engine *e);   // (bgzf_api.h: what the table and slot_of[] take from the feed's memory budget)
+
+static uint32_t dedup_grid(const pssbam_engine *e, uint64_t lanes) {
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((lanes + 255) / 256, (uint64_t)e->n_cu * 8));
+}
+
+// the state word that has arrived, if one has: the occupied count the growth rule starts from, and the table-full error
+static int dedup_poll(pssbam_engine *e, bool wait) {
+    for (size_t i = 0; i < e->dedup_old.size();) {   // tables the stream has passed
+        const hipError_t q = wait ? hipEventSynchronize(e->dedup_old[i].second) : hipEventQuery(e->dedup_old[i].second);
+        if (q == hipErrorNotReady) { (void)hipGetLastError(); i++; continue; }
+        if (q != hipSuccess) return fail(PSSBAM_EHIP, "hipEventQuery failed: %s", hipGetErrorString(q));
+        HIP_TRY(hipFree(e->dedup_old[i].first));
+        HIP_TRY(hipEventDestroy(e->dedup_old[i].second));
+        e->dedup_old.erase(e->dedup_old.begin() + (long)i);
+    }
+    if (!e->dedup_reading) return PSSBAM_OK;
+    const hipError_t q = wait ? hipEventSynchronize(e->dedup_ev) : hipEventQuery(e->dedup_ev);
+    if (q == hipErrorNotReady) { (void)hipGetLastError(); return PSSBAM_OK; }
+    if (q != hipSuccess) return fail(PSSBAM_EHIP, "hipEventQuery failed: %s", hipGetErrorString(q));
+    e->dedup_reading = false;
+    const unsigned long long st = *e->h_dedup_state;
+    if (st & DEDUP_FULL) return fail(PSSBAM_ENOMEM, "the duplicate table ran full (%llu slots): records went unflagged", (unsigned long long)e->dedup_cap);
+    e->dedup_known = st;
+    e->dedup_known_at = e->dedup_reading_at;
+    return PSSBAM_OK;
+}
+
+// an empty table of `cap` slots; with an old one, its keys go over first
+static int dedup_table(pssbam_engine *e, uint64_t cap) {
+    if (cap > DEDUP_MAX_SLOTS) return fail(PSSBAM_ENOMEM, "the duplicate table would pass %llu slots", (unsigned long long)DEDUP_MAX_SLOTS);
+    DedupSlot *d_new = nullptr;
+    if (hipMalloc((void **)&d_new, cap * sizeof(DedupSlot)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PSSBAM_ENOMEM, "a duplicate table of %llu slots (%llu bytes) does not fit the device", (unsigned long long)cap,
+                    (unsigned long long)(cap * sizeof(DedupSlot)));
+    }
+    hipLaunchKernelGGL(dedup_clear, dim3(dedup_grid(e, cap)), dim3(256), 0, e->stream, d_new, cap);
+    e->dedup_launches++;
+    if (e->d_dedup) {
+        if (e->dedup_submitted) {   // (a table nothing was inserted into has nothing to carry over)
+            hipLaunchKernelGGL(dedup_rehash, dim3(dedup_grid(e, e->dedup_cap)), dim3(256), 0, e->stream, (const DedupSlot *)e->d_dedup, e->dedup_cap, d_new,
+                               (uint32_t)(cap - 1), e->d_dedup_state);
+            e->dedup_launches++;
+        }
+        hipEvent_t passed = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&passed, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(passed, e->stream));
+        e->dedup_old.emplace_back((void *)e->d_dedup, passed);
+    }
+    HIP_TRY(hipGetLastError());
+    e->d_dedup = d_new;
+    e->dedup_cap = cap;
+    return PSSBAM_OK;
+}
+
+// In front of the tally kernels of the block P describes, on the engine's stream: the block's duplicates get FLAG bit 0x400 in the
+// device copy of the records.  Before the insert the table has at least twice as many slots as it can hold keys afterwards: the
+// occupied slots as last known plus every record submitted since that reading, this block's included (the host's bound).
+static int launch_dedup(pssbam_engine *e, const TallyParams &P) {
+    int rc = dedup_poll(e, false);
+    if (rc) return rc;
+    if (!e->d_dedup_state) {
+        HIP_TRY(hipMalloc((void **)&e->d_dedup_state, sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(e->d_dedup_state, 0, sizeof(unsigned long long), e->stream));
+        HIP_TRY(hipHostMalloc((void **)&e->h_dedup_state, sizeof(unsigned long long), hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&e->dedup_ev, hipEventDisableTiming));
+    }
+    const uint64_t need = 2 * (e->dedup_known + (e->dedup_submitted - e->dedup_known_at) + P.n_recs);
+    uint64_t cap = e->dedup_cap ? e->dedup_cap : dedup_first_slots(e);
+    while (cap < need) cap <<= 1;
+    if (cap != e->dedup_cap && (rc = dedup_table(e, cap))) return rc;
+    if ((rc = select_grow(&e->d_dedup_slot, &e->dedup_slot_cap, (size_t)P.n_recs))) return rc;
+    const uint32_t grid = dedup_grid(e, P.n_recs), seq = e->dedup_seq++;
+    const bool groups = e->planes == PLANES_RG;
+    hipLaunchKernelGGL(dedup_insert, dim3(grid), dim3(256), 0, e->stream, P, plane_params(e), groups ? 1u : 0u, e->d_dedup, (uint32_t)(e->dedup_cap - 1), seq,
+                       e->d_dedup_slot, e->d_dedup_state);
+    hipLaunchKernelGGL(dedup_resolve, dim3(grid), dim3(256), 0, e->stream, const_cast<uint8_t *>(P.recs), P.offs, P.n_recs, (const DedupSlot *)e->d_dedup, seq,
+                       (const uint32_t *)e->d_dedup_slot);
+    HIP_TRY(hipGetLastError());
+    e->dedup_launches += 2;
+    e->dedup_submitted += P.n_recs;
+    if (!e->dedup_reading) {
+        HIP_TRY(hipMemcpyAsync(e->h_dedup_state, e->d_dedup_state, sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipEventRecord(e->dedup_ev, e->stream));
+        e->dedup_reading = true;
+        e->dedup_reading_at = e->dedup_submitted;
+    }
+    return PSSBAM_OK;
+}
+
 // d_n_recs != NULL: the record count lives in device memory (blocks indexed on the device); n_records
 // is then only an upper bound for the launch geometry, and the prefix sample is taken sample_off
 // bytes into the block.
@@ -1406,6 +1534,9 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         HIP_TRY(hipStreamWaitEvent(e->stream, e->genome_ready, 0));
         e->genome_wait_pending = false;
     }
+    // duplicate flagging: in front of the tally kernels and of the opening event -- the time and the launch count stay the tally's
+    if (e->dedup)
+        if (const int rc = launch_dedup(e, P)) return rc;
     hipEvent_t ev0 = take_event(e), ev1 = take_event(e);
     if (!ev0 || !ev1) return fail(PSSBAM_EHIP, "hipEventCreate failed");
     HIP_TRY(hipEventRecord(ev0, e->stream));
@@ -2006,6 +2137,7 @@ extern "C" int pssbam_engine_set_gapped_reads(pssbam_engine *e, int32_t on) {
         if (e->cfg.tally_mask != PSSBAM_TALLY_PSS)
             return fail(PSSBAM_EINVAL, "gapped reads are tallied by their anchored ends in the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
         if (const int rc = check_exclusive(e, MODE_GAPPED)) return rc;
+        if (e->dedup) return fail(PSSBAM_EINVAL, "gapped reads do not go with duplicate flagging (pssbam_engine_set_duplicates): the key of a clipped read is not defined");
     }
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set gapped reads after create or reset, before the first tally");
     e->gapped = on != 0;   // (the counter block keeps its size: a caller-bound block stays bound)
@@ -2428,6 +2560,86 @@ extern "C" int pssbam_engine_reset(pssbam_engine *e) {
     if (e->d_feed_tail) HIP_TRY(hipMemsetAsync(e->d_feed_tail, 0, sizeof(uint64_t), e->stream));
     if (e->d_feed_flags) HIP_TRY(hipMemsetAsync(e->d_feed_flags, 0, sizeof(uint32_t), e->stream));
     HIP_TRY(hipMemsetAsync(e->d_counters, 0, e->n_counters * sizeof(unsigned long long), e->stream));
+    if (e->d_dedup_state) {   // duplicate flagging: the table is empty again, at the size it has; the setting stays
+        const int rd = dedup_poll(e, true);   // (a table that ran full is reported here at the latest)
+        HIP_TRY(hipMemsetAsync(e->d_dedup_state, 0, sizeof(unsigned long long), e->stream));
+        if (e->d_dedup) {
+            hipLaunchKernelGGL(dedup_clear, dim3(dedup_grid(e, e->dedup_cap)), dim3(256), 0, e->stream, e->d_dedup, e->dedup_cap);
+            HIP_TRY(hipGetLastError());
+            e->dedup_launches++;
+        }
+        e->dedup_known = e->dedup_known_at = e->dedup_reading_at = e->dedup_submitted = 0;
+        e->dedup_seq = 0;
+        if (rd) return rd;
+    }
+    return PSSBAM_OK;
+}
+
+// Duplicate flagging (dedup_kernels.h).  A filter like -R, -Q and -T, no row of the exclusive-modes table: it goes with every mode but
+// gapped reads (the key of a clipped read is a question of its own).
+extern "C" int pssbam_engine_set_duplicates(pssbam_engine *e, int32_t on, uint32_t initial_slots) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (on) {
+        if (e->cfg.tally_mask != PSSBAM_TALLY_PSS && e->cfg.tally_mask != PSSBAM_TALLY_KMER)
+            return fail(PSSBAM_EINVAL, "duplicates are the duplicates of one tool's candidates: PSSBAM_TALLY_PSS or PSSBAM_TALLY_KMER, not both");
+        if (e->gapped) return fail(PSSBAM_EINVAL, "duplicate flagging does not go with gapped reads (pssbam_engine_set_gapped_reads): the key of a clipped read is not defined");
+        if (initial_slots > DEDUP_MAX_SLOTS) return fail(PSSBAM_EINVAL, "initial_slots %u above %llu", initial_slots, (unsigned long long)DEDUP_MAX_SLOTS);
+    }
+    if (e->tallied || e->cur_feed >= 0 || !e->deferred.empty())
+        return fail(PSSBAM_ESTATE, "records have been tallied already: set duplicate flagging after create or reset, before the first submit");
+    HIP_TRY(hipSetDevice(e->device));
+    const uint64_t before = dedup_reserve_bytes(e);
+    e->dedup = on != 0;
+    e->dedup_initial = on ? initial_slots : 0u;
+    // nothing has been inserted (create, or a reset since): the table, if there is one from an earlier run, is given back, so that
+    // the next launch starts from the size asked for here, and with the setting off nothing stays allocated
+    if (e->d_dedup || e->d_dedup_slot) {
+        if (const int rc = dedup_poll(e, true)) return rc;
+        HIP_TRY(hipStreamSynchronize(e->stream));   // (reset's dedup_clear)
+        if (e->d_dedup) HIP_TRY(hipFree(e->d_dedup));
+        if (e->d_dedup_slot) HIP_TRY(hipFree(e->d_dedup_slot));
+        e->d_dedup = nullptr;
+        e->d_dedup_slot = nullptr;
+        e->dedup_cap = 0;
+        e->dedup_slot_cap = 0;
+    }
+    if (e->feed_mem_budget) {   // worked out already (pssbam_engine_feed_open): the table comes out of it, or goes back
+        const uint64_t budget = e->feed_mem_budget + before, after = dedup_reserve_bytes(e);
+        e->feed_mem_budget = budget > after ? budget - after : 1;
+    }
+    return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_finish_duplicates(pssbam_engine *e, uint64_t totals[3], uint64_t *hist, int32_t hist_max) {
+    if (!e || !totals) return fail(PSSBAM_EINVAL, "null argument");
+    if (!e->dedup) return fail(PSSBAM_EINVAL, "duplicate flagging is off (pssbam_engine_set_duplicates)");
+    if (hist_max < 0 || hist_max > PSSBAM_MAX_DUP_HIST) return fail(PSSBAM_EINVAL, "duplicate histogram limit %d outside 0..%d", (int)hist_max, PSSBAM_MAX_DUP_HIST);
+    int rc = pssbam_engine_sync(e);
+    if (rc) return rc;
+    if ((rc = dedup_poll(e, true))) return rc;
+    const size_t words = 2 + (size_t)hist_max + 2;
+    std::vector<unsigned long long> h(words, 0ull);
+    if (e->d_dedup && e->dedup_submitted) {
+        unsigned long long state = 0, *d_out = nullptr;
+        HIP_TRY(hipMemcpy(&state, e->d_dedup_state, sizeof state, hipMemcpyDeviceToHost));
+        if (state & DEDUP_FULL) return fail(PSSBAM_ENOMEM, "the duplicate table ran full (%llu slots): records went unflagged", (unsigned long long)e->dedup_cap);
+        HIP_TRY(hipMalloc((void **)&d_out, words * sizeof(unsigned long long)));
+        hipError_t q = hipMemsetAsync(d_out, 0, words * sizeof(unsigned long long), e->stream);
+        if (q == hipSuccess) {
+            hipLaunchKernelGGL(dedup_census, dim3(dedup_grid(e, e->dedup_cap)), dim3(256), 0, e->stream, (const DedupSlot *)e->d_dedup, e->dedup_cap, (uint32_t)hist_max, d_out);
+            e->dedup_launches++;
+            q = hipGetLastError();
+        }
+        if (q == hipSuccess) q = hipMemcpyAsync(h.data(), d_out, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream);
+        if (q == hipSuccess) q = hipStreamSynchronize(e->stream);
+        (void)hipFree(d_out);
+        if (q != hipSuccess) return fail(PSSBAM_EHIP, "the duplicate census failed: %s", hipGetErrorString(q));
+    }
+    totals[0] = h[0];
+    totals[1] = h[1];
+    totals[2] = h[0] - h[1];
+    if (hist)
+        for (size_t i = 0; i < (size_t)hist_max + 2; i++) hist[i] = h[2 + i];
     return PSSBAM_OK;
 }
 

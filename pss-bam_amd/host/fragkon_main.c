@@ -11,6 +11,9 @@
  * contigs -- from one pass over the input.  Without these options nothing differs from the reference front end.
  * Added: -T <bed> tallies only the reads whose alignment overlaps an interval of the BED file, as in pss-bam: every
  * table is what this command gives without -T for the input reduced by `samtools view -L <bed>`.
+ * Added: -d flags the duplicates on the GPU in front of the tally, as in pss-bam (pss_main.c has the definition; eligible here =
+ * an unpaired candidate of this command's own filters): every table is what this command gives without -d for the input whose
+ * duplicates carry FLAG 0x400.  With -o it also writes <prefix>.fragkon.duplicates.txt (duplicates.h).  One GPU.
  */
 #include <ctype.h>
 #include <stdio.h>
@@ -33,10 +36,10 @@ int main(int argc, char *argv[])
     int klen = 8, min_mq = 0, merged_only = 0, option;
     unsigned long min_read_len = 0, max_read_len = 250000000;
     char *fasta_fn = NULL, *bam_fn = NULL, *out_prefix = NULL;
-    int by_group = 0;
+    int by_group = 0, duplicates = 0;
     const char *len_edges = NULL, *ctg_map = NULL, *bed_fn = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:k:l:L:q:mGS:C:o:T:")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:k:l:L:q:mGS:C:o:T:d")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -49,6 +52,7 @@ int main(int argc, char *argv[])
         case 'S': len_edges = optarg; break;
         case 'C': ctg_map = optarg; break;
         case 'T': bed_fn = optarg; break;
+        case 'd': duplicates = 1; break;
         case 'o': out_prefix = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -73,7 +77,8 @@ int main(int argc, char *argv[])
               "-l <minimum length of read to report (default: 0)>\n"
               "-L <maximum length of read to report (default: 250000000)>\n"
               "-q <map quality filter of read to report (default: 0)>\n"
-              "-m <only consider merged reads>\n",
+              "-m <only consider merged reads>\n"
+              "-d <flag duplicates before the tally: unpaired reads with the contig, position, length, strand (and, where the tables are split by read group, read group) of an earlier read; with -o, also write the duplication histogram (one GPU)>\n",
               stderr);
         exit(1);
     }
@@ -85,6 +90,10 @@ int main(int argc, char *argv[])
     if (n_selectors && !out_prefix) {
         fprintf(stderr, "-%c needs -o <output filename prefix> for the per-%s tables (<prefix>.<tag>.fragkon.txt).\n",
                 by_group ? 'G' : len_edges ? 'S' : 'C', by_group ? "read-group" : len_edges ? "length-bin" : "contig-set");
+        exit(1);
+    }
+    if (duplicates && getenv("PSSBAM_NGPU") && atoi(getenv("PSSBAM_NGPU")) > 1) {
+        fprintf(stderr, "-d keeps the first read of a group in input order, which one GPU keeps: not with PSSBAM_NGPU=%s.\n", getenv("PSSBAM_NGPU"));
         exit(1);
     }
     uint32_t edges[PSSBAM_MAX_LENGTH_BINS - 1];
@@ -165,12 +174,13 @@ int main(int argc, char *argv[])
     memcpy(frontend_opts.length_edges, edges, (size_t)n_edges * sizeof *edges);
     if (ctg_map) frontend_opts.contig_sets = &sets;
     if (bed_fn) frontend_opts.regions = &bed;
+    frontend_opts.duplicates = duplicates;   /* -d: pss-bam's, for the k-mer tables (pss_main.c) */
     /* HIP start-up, engines and the compressed BAM feed overlap the FASTA load (frontend.c) */
     frontend_warmup_start(&cfg, bam_fn, fasta_fn);
     Genome *genome = init_genome(fasta_fn);
     if (!genome) {
         fprintf(stderr, "Error: Unable to load genome from %s.\n", fasta_fn);
-        exit(1);
+        front_end_fail(1);   /* (not exit(): the helper thread may still be starting the HIP runtime up) */
     }
     fprintf(stderr, "Finished loading genome.\nCounting kmer contexts for: %s\n", bam_fn);
 
@@ -179,6 +189,8 @@ int main(int argc, char *argv[])
     if (run_tally(&cfg, genome, bam_fn, env_gpu_count(), &res)) exit(1);
     fragkon_write_table(stdout, fasta_fn, bam_fn, klen, res.k5, res.k3);
     fflush(stdout);
+    /* -d: <prefix>.fragkon.duplicates.txt, only when there is a prefix to write it under */
+    if (res.has_duplicates && out_prefix && pss_write_duplicates(fasta_fn, bam_fn, out_prefix, "fragkon", res.dup_totals, res.dup_hist, PSS_DUP_HIST_MAX)) exit(1);
     if (by_group && res.n_planes == 0)
         fprintf(stderr, "Warning: -G: the header of %s has no @RG line; only the table of all reads was written.\n", bam_fn);
     /* <prefix>.<tag>.fragkon.txt: what the same command prints for the plane's records alone */

@@ -225,7 +225,8 @@ static int apply_options(pssbam_engine *e)
            (o->n_length_edges > 0 && pssbam_engine_set_length_bins(e, o->n_length_edges, o->length_edges)) ||
            send_contig_sets(e, o->contig_sets) || (o->replicates > 0 && pssbam_engine_set_replicates(e, o->replicates)) ||
            (o->out_bam && (o->out_deflate ? pssbam_engine_set_block_sink(e, out_block_sink, NULL) : pssbam_engine_set_record_sink(e, out_sink, NULL))) ||
-           (o->out_bam && o->out_mask_mode != PSSBAM_END_MASK_OFF && pssbam_engine_set_end_mask(e, o->out_mask_mode, o->out_mask_n5, o->out_mask_n3));
+           (o->out_bam && o->out_mask_mode != PSSBAM_END_MASK_OFF && pssbam_engine_set_end_mask(e, o->out_mask_mode, o->out_mask_n5, o->out_mask_n3)) ||
+           (o->duplicates && pssbam_engine_set_duplicates(e, 1, 0));
 }
 
 static void *engine_make_main(void *arg)
@@ -451,6 +452,12 @@ void front_end_exit(int status)
     }
     if (frontend_fast_exit) _exit(status);
     exit(status);
+}
+
+void front_end_fail(int status)
+{
+    fflush(NULL);
+    _exit(status); /* (a detached worker sends no status byte: the caller's process waits for it and relays this one) */
 }
 
 /* seconds since the process was created (exec + dynamic loading included): /proc/self/stat field 22 is the
@@ -894,6 +901,13 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
     if (pssbam_engine_finish(eng[0], res->fwd, res->rev, res->k5, res->k3, res->stats)) {
         fprintf(stderr, "Error: GPU engine: %s\n", out_failed ? out_err : pssbam_last_error());
         goto done;
+    }
+    if (frontend_opts.duplicates) { /* -d: the one engine's table */
+        if (pssbam_engine_finish_duplicates(eng[0], res->dup_totals, res->dup_hist, PSS_DUP_HIST_MAX)) {
+            fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+            goto done;
+        }
+        res->has_duplicates = 1;
     }
     if (frontend_opts.length_hist > 0 && (cfg->tally_mask & PSSBAM_TALLY_PSS)) { /* -H: summed with the rest of the block */
         res->hist_max = frontend_opts.length_hist;

@@ -7,6 +7,7 @@
 
 #include "fasta-genome-io.h"
 #include "pssbam_hip.h"
+#include "duplicates.h"
 #include "regions.h"
 
 typedef struct run_result {
@@ -54,6 +55,10 @@ typedef struct run_result {
     int n_contigs;
     char **contig_names;
     unsigned long *contig_fwd, *contig_rev;
+    /* -d (frontend_opts.duplicates; has_duplicates: filled): {eligible, distinct, flagged} and the group-size histogram,
+     * PSS_DUP_HIST_MAX + 2 entries (duplicates.h) */
+    int has_duplicates;
+    uint64_t dup_totals[3], dup_hist[PSS_DUP_HIST_MAX + 2];
 } run_result;
 
 /* -y / -Y: the weight table [4][n_dist][n_qual], the filter (use_filter: only reads with a score of at least min_score are
@@ -134,6 +139,9 @@ typedef struct frontend_options {
      * regions; the run's one engine gets them beside its sink (pssbam_engine_set_end_mask) */
     int out_mask_mode;
     uint32_t out_mask_n5, out_mask_n3;
+    /* -d: non-zero = the run's one engine flags the duplicates in front of its tally (pssbam_engine_set_duplicates) and
+     * run_tally() returns the totals and the group-size histogram.  One GPU: duplicates are defined by the input order. */
+    int duplicates;
 } frontend_options;
 extern frontend_options frontend_opts;   /* everything off */
 
@@ -163,6 +171,10 @@ int frontend_detached(void); /* 1 in a worker whose caller will be released by f
 
 extern int frontend_fast_exit;
 void front_end_exit(int status);
+/* The end of a front end whose run has failed, after its message, while the helper thread of frontend_warmup_start() may still be
+ * inside the HIP runtime's start-up: flushes stdio and ends the process without running exit handlers or destructors -- exit()
+ * would take the runtime's own state apart under that thread, which now and then ended in SIGSEGV or abort() instead of `status`. */
+void front_end_fail(int status);
 void run_result_free(run_result *res);
 double frontend_now_s(void); /* CLOCK_MONOTONIC seconds */
 double frontend_process_age_s(void); /* seconds since the process was created (10 ms resolution), -1 if unknown */

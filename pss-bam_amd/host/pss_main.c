@@ -87,6 +87,14 @@
  * and G->A) or the T of both ends (ss), in the read's orientation -- are N with quality 0, from the same pass (the engine's end
  * mask, include/pssbam_hip.h); everything else of the file is what it is without -K, and so is every other file: the tables are
  * those of the unmasked reads.  Goes with -Z, -z and every option -O goes with; refused without -O.
+ * Added: -d flags the duplicates on the GPU in front of the tally, in the same pass: every file is what this command writes without -d
+ * for the input in which the duplicates carry FLAG 0x400.  A duplicate is an unpaired read that passes the filters which do not look at
+ * its bases (-R, -q, -l, -L, -T, <L>M, the flags, inside its contig) and has the contig, position, length, strand and -- under -G --
+ * read group of an earlier such read of the input; the first one is kept, whatever its qualities (the known difference from DeDup and
+ * Picard), and the filters that look at the bases (-y, -n, -V, -Q, -U, -D) come afterwards.  Paired reads are never flagged: pairing
+ * mates is out of scope.  Also writes <prefix>.pss.duplicates.txt: eligible reads, distinct keys, flagged reads, their fraction, and
+ * how many keys have 1, 2, ..., 255 and more reads (duplicates.h).  With -O the BAM is the filtered, deduplicated one.  Goes with every
+ * other option except -I; SAM text is fine; one GPU (PSSBAM_NGPU unset or 1): the input order defines the duplicates.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -101,6 +109,7 @@
 #include "base_quality.h"
 #include "composition.h"
 #include "contig_sets.h"
+#include "duplicates.h"
 #include "end_mask.h"
 #include "fasta-genome-io.h"
 #include "frontend.h"
@@ -136,9 +145,9 @@ int main(int argc, char *argv[])
     const char *max_mm_arg = NULL, *mm_hist_arg = NULL, *rep_arg = NULL, *interior_arg = NULL, *comp_arg = NULL, *min_score_arg = NULL;
     const char *out_bam = NULL, *out_level_arg = NULL;
     const char *out_mask_arg = NULL;
-    int out_deflate = 0;
+    int out_deflate = 0, duplicates = 0;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:P:y:YO:z:ZK:")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:P:y:YO:z:ZK:d")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -172,6 +181,7 @@ int main(int argc, char *argv[])
         case 'z': out_level_arg = optarg; break;
         case 'Z': out_deflate = 1; break;
         case 'K': out_mask_arg = optarg; break;
+        case 'd': duplicates = 1; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -215,7 +225,8 @@ int main(int argc, char *argv[])
               "-O <out.bam> <also write the tallied reads, as they are in the input and in its order, to this BAM (BAM input, one GPU)>\n"
               "-z <level> <with -O: BGZF compression level 0..9 (default: 1)>\n"
               "-Z <with -O: deflate the BAM's blocks on the GPU, not with zlib on the host (blocks cut every 0xFF00 bytes; not with -z)>\n"
-              "-K <all|ds|ss>,<n5>[,<n3>] <with -O: in that BAM, mask the first n5 bases of the 5' and n3 (default: n5) of the 3' end of each read with N, quality 0: all of them, T at 5' / A at 3' (ds) or T at both (ss)>\n",
+              "-K <all|ds|ss>,<n5>[,<n3>] <with -O: in that BAM, mask the first n5 bases of the 5' and n3 (default: n5) of the 3' end of each read with N, quality 0: all of them, T at 5' / A at 3' (ds) or T at both (ss)>\n"
+              "-d <flag duplicates before the tally: unpaired reads with the contig, position, length, strand (and, where the tables are split by read group, read group) of an earlier read; also write the duplication histogram (one GPU; not with -I)>\n",
               stderr);
         exit(1);
     }
@@ -305,6 +316,15 @@ int main(int argc, char *argv[])
         fclose(probe);
         remove(tmp);
         free(tmp);
+    }
+    /* -d: no row of the table below either (a filter in front of the tally; it goes with every option but -I) */
+    if (duplicates && gapped) {
+        fprintf(stderr, "-d (flag duplicates) does not go with %s: the key of a clipped read is not defined.\n", L_I);
+        exit(1);
+    }
+    if (duplicates && getenv("PSSBAM_NGPU") && atoi(getenv("PSSBAM_NGPU")) > 1) {
+        fprintf(stderr, "-d keeps the first read of a group in input order, which one GPU keeps: not with PSSBAM_NGPU=%s.\n", getenv("PSSBAM_NGPU"));
+        exit(1);
     }
     /* The exclusive options: at most one row may be given (their tables share the words behind the engine's planes, and
      * one pass over 32 table rows).  Of two, the later row is named first, by all it was given with, the earlier one by
@@ -497,6 +517,7 @@ int main(int argc, char *argv[])
     if (out_bam && out_deflate) fprintf(stderr, " -O %s -Z", out_bam);
     else if (out_bam) fprintf(stderr, " -O %s -z %d", out_bam, out_level);
     if (out_mask_arg) fprintf(stderr, " -K %s,%u,%u", out_mask_mode == PSSBAM_END_MASK_ALL ? "all" : out_mask_mode == PSSBAM_END_MASK_DS ? "ds" : "ss", out_mask_n5, out_mask_n3);
+    if (duplicates) fprintf(stderr, " -d");
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -540,6 +561,7 @@ int main(int argc, char *argv[])
     frontend_opts.out_mask_mode = out_mask_mode;
     frontend_opts.out_mask_n5 = out_mask_n5;
     frontend_opts.out_mask_n3 = out_mask_n3;
+    frontend_opts.duplicates = duplicates;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
      * load; only the tally launches wait for the genome (frontend.c) */
@@ -549,7 +571,7 @@ int main(int argc, char *argv[])
     if (getenv("PSSBAM_STATS")) fprintf(stderr, "[pssbam] genome: fasta load %.3f s\n", frontend_now_s() - t_fa);
     if (!genome) {
         fprintf(stderr, "Error: Unable to load genome from %s.\n", fasta_fn);
-        exit(1);
+        front_end_fail(1);   /* (not exit(): the helper thread may still be starting the HIP runtime up) */
     }
     fprintf(stderr, "Finished loading genome.\nCounting matches/mismatches from:\n%s\n", bam_fn);
 
@@ -568,6 +590,7 @@ int main(int argc, char *argv[])
     if (res.has_interior && pss_write_interior(fasta_fn, bam_fn, out_prefix, interior, min_bq, res.interior, res.interior_reads)) exit(1);   /* -W */
     if (res.comp5 && pss_write_composition(fasta_fn, bam_fn, out_prefix, res.composition_width, res.comp5, res.comp3)) exit(1);   /* -P */
     if (res.score_fwd && pss_write_read_scores(fasta_fn, bam_fn, out_prefix, res.score_half, res.score_fwd, res.score_rev)) exit(1);   /* -Y */
+    if (res.has_duplicates && pss_write_duplicates(fasta_fn, bam_fn, out_prefix, "pss", res.dup_totals, res.dup_hist, PSS_DUP_HIST_MAX)) exit(1);   /* -d */
     if (res.site_fwd) {   /* -X: IN as the engine returns it; OUT = T - IN on the position rows, the context rows as T */
         const size_t cells = (size_t)(region_len + 2) * 16;
         unsigned long *out_fwd = (unsigned long *)malloc(cells * sizeof *out_fwd), *out_rev = (unsigned long *)malloc(cells * sizeof *out_rev);
