@@ -743,6 +743,47 @@ int pssbam_engine_set_duplicates(pssbam_engine *e, int32_t on, uint32_t initial_
  * hist_max+2 words, hist may be NULL.  PSSBAM_EINVAL when the setting is off. */
 int pssbam_engine_finish_duplicates(pssbam_engine *e, uint64_t totals[3], uint64_t *hist, int32_t hist_max);
 
+/* Depth of coverage of the kept records (pss-bam -c / -b), from the same pass.
+ *   Kept: exactly the records a record sink delivers -- added to the forward or the reverse main table of this run, after every
+ *     filter given (read group, mapping quality, lengths, merged only, contexts, regions, the mismatch limit, the read score, and the
+ *     0x400 bits duplicate flagging sets).  Each mate of a pair is judged on its own.
+ *   depth(c, p) = the kept records on contig c with POS <= p < POS + L; L = the record's length in the tables, which for a kept record
+ *     is the length of its <L>M CIGAR (and of its SEQ, unless a paired record's SEQ disagrees with its CIGAR and TLEN).  Mates that
+ *     overlap count twice.  A minimum base quality masks bases, not reads, and the end mask changes the sink's bytes only: neither
+ *     changes the depth.
+ * The engine keeps one uint32_t per stored genome position (4 bytes per base: 12.4 GB for a human genome) holding differences; behind
+ * each block's tally kernels one more kernel adds the kept records' two entries each (csrc/coverage_kernels.h).  Depth is exact below
+ * 2^32.  The counter block keeps its size and layout, and the time and launch count of pssbam_engine_kernel_time stay the tally's.
+ * on != 0 switches it on; positions_hint = the positions the genome is expected to have (the sum of the BAM header's LN values; 0 =
+ * unknown): with pssbam_engine_feed_open, 4 x positions_hint plus the contigs' padding is left out of the feed's memory budget.  The
+ * array is allocated when the genome's size is known -- by this call when the genome is set already, by set_genome otherwise --
+ * and PSSBAM_ENOMEM comes from the call that cannot get it.  Legal after create or reset and before the first submit (with
+ * pssbam_engine_feed_open: before the first submit_bgzf), PSSBAM_ESTATE later.  PSSBAM_EINVAL without PSSBAM_TALLY_PSS, and with
+ * gapped reads (pssbam_engine_set_gapped_reads) in either order of the two calls: the span of a clipped or gapped read needs a
+ * definition of its own.  The setting survives pssbam_engine_reset, which zeroes the array at the size it has.  Engines do not share
+ * an array, and pssbam_reduce_counters does not sum them.  Off, nothing is allocated and nothing more is launched. */
+#define PSSBAM_COV_HIST_MAX 255
+int pssbam_engine_set_coverage(pssbam_engine *e, int32_t on, uint64_t positions_hint);
+/* Drains like pssbam_engine_finish, then computes the totals of everything submitted since create or reset.  Non-destructive: it may
+ * be called any number of times, more blocks may follow it, and the depth array itself is never stored.
+ *   per_contig: n x {covered positions, sum of depth, maximum depth} for the references first_ref .. first_ref + n - 1 of the last
+ *     set_references (index n_ref = a contig named "*"); all zero for a name the genome lacks, and for the later one of two
+ *     references of the same name.
+ *   hist[d], d in 0..hist_max (at most PSSBAM_COV_HIST_MAX): the positions at depth d of the contigs of the reference list, each
+ *     contig once; hist[hist_max + 1]: the positions above; hist_max + 2 words.  The padding between contigs counts nowhere.
+ *   n_runs: the number of maximal runs of equal non-zero depth (pssbam_engine_finish_coverage_runs).
+ * Any of the three pointers may be NULL.  PSSBAM_EINVAL when the setting is off. */
+int pssbam_engine_finish_coverage(pssbam_engine *e, int32_t first_ref, int32_t n, uint64_t *per_contig, uint64_t *hist, int32_t hist_max,
+                                  uint64_t *n_runs);
+/* The covered intervals (a bedGraph): run i is the half-open interval [start[i], end[i]) of reference ref[i] (-1: the contig named
+ * "*") at depth[i] > 0.  Runs are maximal (a run ends where the depth changes, and only there: two runs that touch differ in depth),
+ * ordered by refID, then start, and never cross a contig.  *n_runs = the exact count, always; with all four arrays NULL that is
+ * all the call does.  Any single array may be NULL.  PSSBAM_EINVAL when cap, the room of each array, is below the count, and when
+ * the setting is off.  Called behind pssbam_engine_finish_coverage with nothing submitted in between, it starts from that call's
+ * tile sums instead of computing them again. */
+int pssbam_engine_finish_coverage_runs(pssbam_engine *e, uint64_t cap, int32_t *ref, uint32_t *start, uint32_t *end, uint32_t *depth,
+                                       uint64_t *n_runs);
+
 /* Drains the engine like pssbam_engine_finish and copies the two arrays, 2 * hist_half words each; either pointer may be
  * NULL.  PSSBAM_EINVAL without a histogram. */
 int pssbam_engine_finish_read_score(pssbam_engine *e, uint64_t *fwd, uint64_t *rev);

@@ -52,6 +52,7 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_read_score", "pssbam_engine_finish_read_score",
     "pssbam_engine_set_record_sink", "pssbam_engine_set_block_sink", "pssbam_engine_set_end_mask",
     "pssbam_engine_set_duplicates", "pssbam_engine_finish_duplicates",
+    "pssbam_engine_set_coverage", "pssbam_engine_finish_coverage", "pssbam_engine_finish_coverage_runs",
     "pssbam_bgzf_deflate_work_bytes", "pssbam_bgzf_deflate_device", "pssbam_bgzf_deflate_host",
 ]
 MAX_READ_GROUPS = 4096
@@ -75,6 +76,7 @@ END_MASK_OFF, END_MASK_ALL, END_MASK_DS, END_MASK_SS = 0, 1, 2, 3
 END_MASK_MODES = {None: END_MASK_OFF, "off": END_MASK_OFF, "all": END_MASK_ALL, "ds": END_MASK_DS, "ss": END_MASK_SS}
 MAX_END_MASK = 65535
 MAX_DUP_HIST = 65535
+COV_HIST_MAX = 255
 END_PRESETS = {"ss": (13, 13), "ds": (13, 2)}   # (cell5, cell3): C->T at both ends / C->T at the 5' end, G->A at the 3' end
 GAPPED_TILED_OPS = 16   # pss-bam -I: CIGAR ops a lane of the tiled kernel walks (csrc/record_decode.h); more take the one-lane path
 EBUSY = -7
@@ -186,6 +188,10 @@ def hip_lib() -> C.CDLL:
     if hasattr(L, "pssbam_engine_set_duplicates"):   # (tools/dedup_bench.py also loads the library of the commit before it)
         L.pssbam_engine_set_duplicates.argtypes = [C.c_void_p, C.c_int32, C.c_uint32]
         L.pssbam_engine_finish_duplicates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    if hasattr(L, "pssbam_engine_set_coverage"):   # (tools/coverage_bench.py also loads the library of the commit before it)
+        L.pssbam_engine_set_coverage.argtypes = [C.c_void_p, C.c_int32, C.c_uint64]
+        L.pssbam_engine_finish_coverage.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.pssbam_engine_finish_coverage_runs.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_index_records.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     _hip = L
     return L
@@ -821,6 +827,39 @@ class Engine:
         hist = np.zeros(int(hist_max) + 2, dtype=np.uint64)
         _chk(self._L.pssbam_engine_finish_duplicates(self._h, totals.ctypes.data, hist.ctypes.data, int(hist_max)))
         return dict(zip(("eligible", "distinct", "flagged"), (int(v) for v in totals))), hist
+
+    def set_coverage(self, on: bool = True, positions_hint: int = 0):
+        """Depth of coverage of the kept records (pssbam_engine_set_coverage): one uint32 per stored genome position, two atomic
+        adds per kept record behind each block's tally.  positions_hint: the genome's expected positions, for the feed's memory
+        budget.  Before the first submit; needs the substitution tally; not with set_gapped."""
+        _chk(self._L.pssbam_engine_set_coverage(self._h, 1 if on else 0, int(positions_hint)))
+
+    def finish_coverage(self, n_ref: int, hist_max: int = COV_HIST_MAX) -> tuple[np.ndarray, np.ndarray, int]:
+        """sync, then (per_contig, hist, n_runs) of everything since create / reset: per_contig[i] = {covered, depth_sum, max_depth}
+        of reference i in 0..n_ref-1, hist[d] = the positions at depth d for d in 0..hist_max and hist[hist_max + 1] those above.
+        Non-destructive."""
+        per = np.zeros((int(n_ref), 3), dtype=np.uint64)
+        hist = np.zeros(int(hist_max) + 2, dtype=np.uint64)
+        n_runs = C.c_uint64(0)
+        _chk(self._L.pssbam_engine_finish_coverage(self._h, 0, int(n_ref), per.ctypes.data if n_ref else None, hist.ctypes.data, int(hist_max),
+                                                   C.addressof(n_runs)))
+        return per, hist, int(n_runs.value)
+
+    def finish_coverage_runs(self, cap: int | None = None, count_only: bool = False):
+        """sync, then the covered intervals as (ref, start, end, depth) arrays -- half-open, by refID then start -- or, with
+        count_only, their number.  cap: the room to offer (default: the exact count, asked for first)."""
+        n_runs = C.c_uint64(0)
+        if count_only or cap is None:
+            _chk(self._L.pssbam_engine_finish_coverage_runs(self._h, 0, None, None, None, None, C.addressof(n_runs)))
+            if count_only:
+                return int(n_runs.value)
+            cap = int(n_runs.value)
+        ref = np.zeros(max(int(cap), 1), dtype=np.int32)
+        start, end, depth = (np.zeros(max(int(cap), 1), dtype=np.uint32) for _ in range(3))
+        _chk(self._L.pssbam_engine_finish_coverage_runs(self._h, int(cap), ref.ctypes.data, start.ctypes.data, end.ctypes.data, depth.ctypes.data,
+                                                        C.addressof(n_runs)))
+        n = int(n_runs.value)
+        return ref[:n], start[:n], end[:n], depth[:n]
 
     def finish_blocks(self) -> np.ndarray:
         """sync, then every block collected since set_block_sink() / the last finish_blocks(), as one uint8 array;

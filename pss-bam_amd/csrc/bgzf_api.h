@@ -652,7 +652,7 @@ static int feed_acquire(pssbam_engine *e, int *out_slot, bool force) {
             size_t free_b = 0, total_b = 0;
             if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 64ull << 30;
             const uint64_t used = e->feed.size() * feed_slot_bytes(e);
-            const uint64_t keep = (24ull << 30) + select_reserve_bytes(e) + dedup_reserve_bytes(e);
+            const uint64_t keep = (24ull << 30) + select_reserve_bytes(e) + dedup_reserve_bytes(e) + coverage_reserve_bytes(e);
             e->feed_mem_budget = used + (free_b > keep ? free_b - keep : 0);   // leaves room for genome, 4-bit image, k-mer bins
         }
         limit = std::max<size_t>(FEED_SLOTS_READY, (size_t)(e->feed_mem_budget / feed_slot_bytes(e)));
@@ -942,7 +942,7 @@ extern "C" int pssbam_engine_feed_open(pssbam_engine *e, int32_t n_ref, uint64_t
     e->feed_n_ref = n_ref;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const uint64_t keep = genome_bytes_hint + genome_bytes_hint / 2 + (8ull << 30) + select_reserve_bytes(e) + dedup_reserve_bytes(e);   // genome + 4-bit image + slack (+ the record sink's buffers, the duplicate table)
+        const uint64_t keep = genome_bytes_hint + genome_bytes_hint / 2 + (8ull << 30) + select_reserve_bytes(e) + dedup_reserve_bytes(e) + coverage_reserve_bytes(e);   // genome + 4-bit image + slack (+ the record sink's buffers, the duplicate table, the coverage array)
         e->feed_mem_budget = e->feed.size() * feed_slot_bytes(e) + (free_b > keep ? free_b - keep : 0);
     }
     return PSSBAM_OK;

@@ -30,6 +30,7 @@
 #include "select_kernels.h"
 #include "end_mask_kernels.h"
 #include "dedup_kernels.h"
+#include "coverage_kernels.h"
 #include "deflate_kernels.h"
 
 using namespace pssbam;
@@ -308,6 +309,26 @@ struct pssbam_engine {
     uint32_t dedup_seq = 0;            // blocks flagged since create / reset: the high word of a record's ordinal
     uint64_t dedup_launches = 0;       // (not part of kernel_launches: that count is the tally's)
     std::vector<std::pair<void *, hipEvent_t>> dedup_old;   // tables replaced by a larger one: freed once the stream has passed the rehash
+    // depth of coverage (pssbam_engine_set_coverage, coverage_kernels.h).  Off: nothing below is allocated and nothing more is launched.
+    // d_cov holds the differences, cov_len entries (the stored genome length rounded up to whole tiles; 0: no genome yet -- it is
+    // allocated when the genome's size is known); the rest are finish's buffers, kept between calls: per-tile sums and run counts,
+    // the totals {histogram, runs, 3 words per listed contig}, and the listed contigs sorted by their place in the genome.
+    bool coverage = false;
+    uint64_t cov_hint = 0;             // positions_hint of the caller (what the array is expected to take, for the feed's memory budget)
+    uint32_t *d_cov = nullptr;
+    uint64_t cov_len = 0;
+    unsigned long long *d_cov_sums = nullptr, *d_cov_runcnt = nullptr, *d_cov_out = nullptr;
+    size_t cov_sums_cap = 0, cov_out_cap = 0;
+    uint4 *d_cov_contigs = nullptr;
+    size_t cov_contigs_cap = 0;
+    std::vector<uint4> cov_contigs;    // the contigs of the reference list, each once, sorted by lo: {lo low, lo high, length, first refID}
+    bool cov_contigs_sent = false;
+    // what the last finish computed, while nothing has been added since: the totals on the host, the tiles' bases in d_cov_sums,
+    // and the tiles' run counts in d_cov_runcnt (cov_runs_scanned: already turned into their exclusive scan)
+    bool cov_totals_valid = false, cov_runs_scanned = false;
+    std::vector<unsigned long long> cov_out_host;
+    uint32_t *d_cov_runs = nullptr;    // finish_coverage_runs' [slot | start | end | depth], cov_runs_cap words each
+    uint64_t cov_runs_cap = 0;
     bool gapped = false;   // -I (pssbam_engine_set_gapped_reads): clipped and gapped reads are tallied by their anchored ends; no counter words
     int env_hist_lds_bins = -1;   // PSSBAM_HIST_LDS_BINS: at most this many bins of each array in LDS (tests: the global-atomic path with short reads)
     // -T (pssbam_engine_set_regions): contig name -> its merged intervals, kept on the host; the per-refID device table is
@@ -575,6 +596,12 @@ extern "C" void pssbam_engine_destroy(pssbam_engine *e) {
     if (e->d_dedup_state) (void)hipFree(e->d_dedup_state);
     if (e->h_dedup_state) (void)hipHostFree(e->h_dedup_state);
     if (e->dedup_ev) (void)hipEventDestroy(e->dedup_ev);
+    if (e->d_cov) (void)hipFree(e->d_cov);
+    if (e->d_cov_sums) (void)hipFree(e->d_cov_sums);
+    if (e->d_cov_runcnt) (void)hipFree(e->d_cov_runcnt);
+    if (e->d_cov_out) (void)hipFree(e->d_cov_out);
+    if (e->d_cov_contigs) (void)hipFree(e->d_cov_contigs);
+    if (e->d_cov_runs) (void)hipFree(e->d_cov_runs);
     if (e->d_sel_sums) (void)hipFree(e->d_sel_sums);
     if (e->d_comp) (void)hipFree(e->d_comp);
     if (e->d_comp_len) (void)hipFree(e->d_comp_len);
@@ -631,6 +658,8 @@ static constexpr uint64_t CONTIG_ALIGN = 256, CONTIG_PAD = 256;
 
 static hipEvent_t take_event(pssbam_engine *e);
 static int feed_resume(pssbam_engine *e);
+static int coverage_array(pssbam_engine *e, uint64_t genome_bytes);
+static void coverage_contigs(pssbam_engine *e);
 
 // The upload still in flight (if any) has completed: its page locks go back.
 static int genome_settle(pssbam_engine *e) {
@@ -665,6 +694,10 @@ static int genome_upload(pssbam_engine *e, size_t n, const char *const *ids, con
         len[k] = (uint32_t)lens[order[k]];
         total += ((uint64_t)len[k] + CONTIG_PAD + CONTIG_ALIGN - 1) / CONTIG_ALIGN * CONTIG_ALIGN;
     }
+    // depth of coverage: the array for this genome's size first -- a refusal (PSSBAM_ENOMEM) leaves the genome that was set before
+    // as it is; coverage then has no array, and a submit is refused until a set_genome succeeds
+    if (e->coverage)
+        if ((rc = coverage_array(e, total))) return rc;
     if (e->d_genome) {   // a genome is being replaced: kernels queued on the engine's stream may still read the old one
         HIP_TRY(hipStreamSynchronize(e->stream));
         HIP_TRY(hipFree(e->d_genome));
@@ -714,6 +747,9 @@ static int genome_upload(pssbam_engine *e, size_t n, const char *const *ids, con
         hipLaunchKernelGGL(pack_genome4_kernel, dim3(4096), dim3(256), 0, gs, e->d_genome, e->d_genome4, n_out, sets);
         HIP_TRY(hipGetLastError());
     }
+    // depth of coverage: zeroed on the genome's stream (every tally waits for genome_ready; kernels of an earlier genome that
+    // added to it on the engine's stream have been waited for above, where that genome was freed)
+    if (e->coverage) HIP_TRY(hipMemsetAsync(e->d_cov, 0, e->cov_len * sizeof(uint32_t), gs));
     HIP_TRY(hipEventRecord(e->genome_ready, gs));
     e->genome_wait_pending = true;
     e->contig_start.assign(start.begin(), start.begin() + n);
@@ -932,6 +968,7 @@ extern "C" int pssbam_engine_set_references(pssbam_engine *e, int32_t n_ref, con
     e->n_ref = n_ref;
     e->have_refs = true;
     e->ref_info_host.swap(info);
+    coverage_contigs(e);   // depth of coverage: the list its finish kernels find a position's contig in
     if (const int rc = pack_regions(e, replaced)) return rc;   // -T: the region table follows the reference list
     return feed_resume(e);   // super-batches inflated ahead of the genome are tallied now
 }
@@ -1715,6 +1752,15 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
     e->launch_events.emplace_back(ev0, ev1);
     if (e->launch_events.size() > 4096)
         if (const int rc = resolve_launch_events(e)) return rc;
+    // depth of coverage: the kept records' two differences each, behind the tally and its closing event (time and launch count stay
+    // the tally's) and, like the sink's kernels, in front of whatever frees the block's buffers
+    if (e->coverage) {
+        if (!e->d_cov) return fail(PSSBAM_ESTATE, "coverage is on but the genome's array is missing");
+        const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)n_records + 255) / 256, (uint64_t)e->n_cu * 8));
+        hipLaunchKernelGGL(coverage_add, dim3(grid), dim3(256), 0, e->stream, P, e->d_cov, e->cov_len);
+        HIP_TRY(hipGetLastError());
+        e->cov_totals_valid = false;
+    }
     // the record sink: the kept records of this block, behind its tally and in front of whatever frees the block's buffers
     if (sink_on(e)) return launch_select(e, P, nbytes);
     return PSSBAM_OK;
@@ -2138,6 +2184,7 @@ extern "C" int pssbam_engine_set_gapped_reads(pssbam_engine *e, int32_t on) {
             return fail(PSSBAM_EINVAL, "gapped reads are tallied by their anchored ends in the substitution tables: the engine needs PSSBAM_TALLY_PSS alone");
         if (const int rc = check_exclusive(e, MODE_GAPPED)) return rc;
         if (e->dedup) return fail(PSSBAM_EINVAL, "gapped reads do not go with duplicate flagging (pssbam_engine_set_duplicates): the key of a clipped read is not defined");
+        if (e->coverage) return fail(PSSBAM_EINVAL, "gapped reads do not go with coverage (pssbam_engine_set_coverage): the span of a clipped or gapped read is not defined");
     }
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set gapped reads after create or reset, before the first tally");
     e->gapped = on != 0;   // (the counter block keeps its size: a caller-bound block stays bound)
@@ -2572,6 +2619,261 @@ extern "C" int pssbam_engine_reset(pssbam_engine *e) {
         e->dedup_seq = 0;
         if (rd) return rd;
     }
+    if (e->d_cov) {   // coverage: all zero again, at the size it has; the setting stays
+        HIP_TRY(hipMemsetAsync(e->d_cov, 0, e->cov_len * sizeof(uint32_t), e->stream));
+        e->cov_totals_valid = false;
+    }
+    return PSSBAM_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// depth of coverage of the kept records (coverage_kernels.h)
+// --------------------------------------------------------------------------------------
+// what the array is expected to take, from the caller's hint: 4 bytes per position, and per contig the padding and the rounding of
+// genome_upload's layout (bgzf_api.h takes it out of the feed's memory budget)
+static uint64_t coverage_reserve_bytes(const pssbam_engine *e) {
+    if (!e->coverage) return 0;
+    const uint64_t n_ref = e->feed_opened ? (uint64_t)std::max(e->feed_n_ref, 0) : 0ull;
+    return sizeof(uint32_t) * (e->cov_hint + (n_ref + 1) * (CONTIG_PAD + CONTIG_ALIGN) + COV_TILE);
+}
+
+// the array for a genome of genome_bytes stored positions; the caller zeroes it
+static int coverage_array(pssbam_engine *e, uint64_t genome_bytes) {
+    e->cov_totals_valid = false;
+    const uint64_t len = (genome_bytes + COV_TILE - 1) / COV_TILE * COV_TILE;
+    if (e->d_cov && e->cov_len != len) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipFree(e->d_cov));
+        e->d_cov = nullptr;
+        e->cov_len = 0;
+    }
+    if (!e->d_cov) {
+        if (hipMalloc((void **)&e->d_cov, len * sizeof(uint32_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            e->d_cov = nullptr;
+            return fail(PSSBAM_ENOMEM, "the coverage array of %llu positions (%llu bytes) does not fit the device", (unsigned long long)len,
+                        (unsigned long long)(len * sizeof(uint32_t)));
+        }
+        e->cov_len = len;
+    }
+    return PSSBAM_OK;
+}
+
+// the contigs of the reference list, each once, sorted by their place in the genome
+static void coverage_contigs(pssbam_engine *e) {
+    e->cov_contigs.clear();
+    e->cov_contigs_sent = false;
+    e->cov_totals_valid = false;
+    for (size_t i = 0; i < e->ref_info_host.size(); i++) {   // (the last entry answers RNAME "*": a contig of that name is listed too)
+        const uint4 ri = e->ref_info_host[i];
+        if (ri.w) e->cov_contigs.push_back(make_uint4(ri.x, ri.y, ri.z, (uint32_t)i));
+    }
+    std::stable_sort(e->cov_contigs.begin(), e->cov_contigs.end(), [](const uint4 &a, const uint4 &b) {
+        return (((uint64_t)a.y << 32) | a.x) < (((uint64_t)b.y << 32) | b.x);
+    });
+    e->cov_contigs.erase(std::unique(e->cov_contigs.begin(), e->cov_contigs.end(), [](const uint4 &a, const uint4 &b) { return a.x == b.x && a.y == b.y; }),
+                         e->cov_contigs.end());   // (a name listed twice: its first refID stands for the contig)
+}
+
+extern "C" int pssbam_engine_set_coverage(pssbam_engine *e, int32_t on, uint64_t positions_hint) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (on) {
+        if (!(e->cfg.tally_mask & PSSBAM_TALLY_PSS)) return fail(PSSBAM_EINVAL, "coverage is the coverage of the reads in the substitution tables: the engine needs PSSBAM_TALLY_PSS");
+        if (e->gapped) return fail(PSSBAM_EINVAL, "coverage does not go with gapped reads (pssbam_engine_set_gapped_reads): the span of a clipped or gapped read is not defined");
+    }
+    if (e->tallied || e->cur_feed >= 0 || !e->deferred.empty())
+        return fail(PSSBAM_ESTATE, "records have been tallied already: set coverage after create or reset, before the first submit");
+    HIP_TRY(hipSetDevice(e->device));
+    const uint64_t before = coverage_reserve_bytes(e);
+    if (on) {
+        if (e->d_genome && !e->d_cov) {   // the genome's size is known: the array now, or PSSBAM_ENOMEM
+            if (const int rc = coverage_array(e, e->genome_bytes)) return rc;
+            HIP_TRY(hipMemsetAsync(e->d_cov, 0, e->cov_len * sizeof(uint32_t), e->stream));
+        }
+        e->coverage = true;
+        e->cov_hint = positions_hint;
+    } else {
+        e->coverage = false;
+        e->cov_hint = 0;
+        if (e->d_cov || e->d_cov_sums || e->d_cov_out || e->d_cov_contigs || e->d_cov_runs) {   // off: nothing stays allocated
+            HIP_TRY(hipStreamSynchronize(e->stream));   // (reset's memset)
+            if (e->genome_stream) HIP_TRY(hipStreamSynchronize(e->genome_stream));
+            if (e->d_cov) HIP_TRY(hipFree(e->d_cov));
+            if (e->d_cov_sums) HIP_TRY(hipFree(e->d_cov_sums));
+            if (e->d_cov_runcnt) HIP_TRY(hipFree(e->d_cov_runcnt));
+            if (e->d_cov_out) HIP_TRY(hipFree(e->d_cov_out));
+            if (e->d_cov_contigs) HIP_TRY(hipFree(e->d_cov_contigs));
+            if (e->d_cov_runs) HIP_TRY(hipFree(e->d_cov_runs));
+            e->d_cov_runs = nullptr;
+            e->cov_runs_cap = 0;
+            e->cov_totals_valid = false;
+            e->d_cov = nullptr;
+            e->d_cov_sums = e->d_cov_runcnt = e->d_cov_out = nullptr;
+            e->d_cov_contigs = nullptr;
+            e->cov_len = 0;
+            e->cov_sums_cap = e->cov_out_cap = e->cov_contigs_cap = 0;
+            e->cov_contigs_sent = false;
+        }
+    }
+    if (e->feed_mem_budget) {   // worked out already (pssbam_engine_feed_open): the array comes out of it, or goes back
+        const uint64_t budget = e->feed_mem_budget + before, after = coverage_reserve_bytes(e);
+        e->feed_mem_budget = budget > after ? budget - after : 1;
+    }
+    return PSSBAM_OK;
+}
+
+static uint32_t coverage_grid(const pssbam_engine *e, uint64_t n_tiles) {
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_tiles, (uint64_t)e->n_cu * 8));
+}
+
+// Tile sums, their scan and coverage_stats, unless the last finish's results still stand (nothing was added since): cov_out_host
+// then holds the totals, d_cov_sums every tile's base and d_cov_runcnt every tile's run count.  Nothing of d_cov changes.
+static int coverage_totals(pssbam_engine *e) {
+    if (e->cov_totals_valid) return PSSBAM_OK;
+    const uint64_t n_tiles = e->cov_len / COV_TILE;
+    const size_t n_contigs = e->cov_contigs.size(), out_words = COV_OUT_CONTIGS + 3 * std::max<size_t>(n_contigs, 1);
+    if (e->cov_sums_cap < n_tiles) {
+        if (e->d_cov_sums) HIP_TRY(hipFree(e->d_cov_sums));
+        if (e->d_cov_runcnt) HIP_TRY(hipFree(e->d_cov_runcnt));
+        e->d_cov_sums = e->d_cov_runcnt = nullptr;
+        e->cov_sums_cap = 0;
+        if (hipMalloc((void **)&e->d_cov_sums, n_tiles * sizeof(unsigned long long)) != hipSuccess ||
+            hipMalloc((void **)&e->d_cov_runcnt, n_tiles * sizeof(unsigned long long)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(PSSBAM_ENOMEM, "the coverage scan's %llu tile sums do not fit the device", (unsigned long long)n_tiles);
+        }
+        e->cov_sums_cap = n_tiles;
+    }
+    if (e->cov_out_cap < out_words) {
+        if (e->d_cov_out) HIP_TRY(hipFree(e->d_cov_out));
+        e->d_cov_out = nullptr;
+        e->cov_out_cap = 0;
+        HIP_TRY(hipMalloc((void **)&e->d_cov_out, out_words * sizeof(unsigned long long)));
+        e->cov_out_cap = out_words;
+    }
+    if (e->cov_contigs_cap < std::max<size_t>(n_contigs, 1)) {
+        if (e->d_cov_contigs) HIP_TRY(hipFree(e->d_cov_contigs));
+        e->d_cov_contigs = nullptr;
+        e->cov_contigs_cap = 0;
+        HIP_TRY(hipMalloc((void **)&e->d_cov_contigs, std::max<size_t>(n_contigs, 1) * sizeof(uint4)));
+        e->cov_contigs_cap = std::max<size_t>(n_contigs, 1);
+        e->cov_contigs_sent = false;
+    }
+    if (!e->cov_contigs_sent && n_contigs) {   // (the stream is idle: every finish drains it first)
+        HIP_TRY(hipMemcpy(e->d_cov_contigs, e->cov_contigs.data(), n_contigs * sizeof(uint4), hipMemcpyHostToDevice));
+        e->cov_contigs_sent = true;
+    }
+    HIP_TRY(hipMemsetAsync(e->d_cov_out, 0, out_words * sizeof(unsigned long long), e->stream));
+    const uint32_t grid = coverage_grid(e, n_tiles);
+    hipLaunchKernelGGL(coverage_tile_sums, dim3(grid), dim3(COV_THREADS), 0, e->stream, (const uint32_t *)e->d_cov, n_tiles, e->d_cov_sums);
+    hipLaunchKernelGGL(coverage_scan_sums, dim3(1), dim3(COV_SUMS_ROUND), 0, e->stream, e->d_cov_sums, n_tiles, (unsigned long long *)nullptr);
+    hipLaunchKernelGGL(coverage_stats, dim3(grid), dim3(COV_THREADS), 0, e->stream, (const uint32_t *)e->d_cov, n_tiles, (const unsigned long long *)e->d_cov_sums,
+                       (const uint4 *)e->d_cov_contigs, (uint32_t)n_contigs, e->d_cov_out, e->d_cov_runcnt);
+    HIP_TRY(hipGetLastError());
+    e->cov_out_host.assign(out_words, 0ull);
+    HIP_TRY(hipMemcpyAsync(e->cov_out_host.data(), e->d_cov_out, out_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->cov_totals_valid = true;
+    e->cov_runs_scanned = false;
+    return PSSBAM_OK;
+}
+
+static int coverage_ready(pssbam_engine *e) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (!e->coverage) return fail(PSSBAM_EINVAL, "coverage is off (pssbam_engine_set_coverage)");
+    return pssbam_engine_sync(e);
+}
+
+extern "C" int pssbam_engine_finish_coverage(pssbam_engine *e, int32_t first_ref, int32_t n, uint64_t *per_contig, uint64_t *hist, int32_t hist_max,
+                                             uint64_t *n_runs) {
+    int rc = coverage_ready(e);
+    if (rc) return rc;
+    if (hist && (hist_max < 0 || hist_max > PSSBAM_COV_HIST_MAX)) return fail(PSSBAM_EINVAL, "coverage histogram limit %d outside 0..%d", (int)hist_max, PSSBAM_COV_HIST_MAX);
+    if (per_contig && (first_ref < 0 || n < 0 || (int64_t)first_ref + n > (int64_t)e->n_ref + 1))
+        return fail(PSSBAM_EINVAL, "references %d..%lld outside the %d of the list (and one for \"*\")", (int)first_ref, (long long)first_ref + n, (int)e->n_ref);
+    std::vector<unsigned long long> out(COV_OUT_CONTIGS + 3 * std::max<size_t>(e->cov_contigs.size(), 1), 0ull);
+    if (e->d_cov && e->have_refs) {
+        if ((rc = coverage_totals(e))) return rc;
+        out = e->cov_out_host;
+    }
+    if (hist) {   // hist[d], d in 0..hist_max: positions at depth d; hist[hist_max + 1]: the positions above
+        for (int32_t d = 0; d <= hist_max + 1; d++) hist[d] = 0;
+        for (uint32_t d = 0; d < COV_HIST_BINS; d++) hist[std::min<uint32_t>(d, (uint32_t)hist_max + 1u)] += out[d];
+    }
+    if (per_contig)
+        for (int32_t i = 0; i < n; i++) {
+            uint64_t *o = per_contig + 3 * (size_t)i;
+            o[0] = o[1] = o[2] = 0;
+            const uint4 ri = e->ref_info_host[(size_t)(first_ref + i)];
+            if (!ri.w) continue;   // a name the genome lacks
+            const auto it = std::lower_bound(e->cov_contigs.begin(), e->cov_contigs.end(), ri, [](const uint4 &a, const uint4 &b) {
+                return (((uint64_t)a.y << 32) | a.x) < (((uint64_t)b.y << 32) | b.x);
+            });
+            if (it == e->cov_contigs.end() || it->w != (uint32_t)(first_ref + i)) continue;   // (a name listed twice counts under its first refID)
+            const size_t k = (size_t)(it - e->cov_contigs.begin());
+            for (int w = 0; w < 3; w++) o[w] = out[COV_OUT_CONTIGS + 3 * k + (size_t)w];
+        }
+    if (n_runs) *n_runs = out[COV_OUT_RUNS];
+    return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_finish_coverage_runs(pssbam_engine *e, uint64_t cap, int32_t *ref, uint32_t *start, uint32_t *end, uint32_t *depth, uint64_t *n_runs) {
+    int rc = coverage_ready(e);
+    if (rc) return rc;
+    const bool count_only = !ref && !start && !end && !depth;
+    uint64_t total = 0;
+    if (e->d_cov && e->have_refs) {
+        if ((rc = coverage_totals(e))) return rc;
+        total = e->cov_out_host[COV_OUT_RUNS];
+    }
+    if (n_runs) *n_runs = total;
+    if (count_only) return PSSBAM_OK;
+    if (cap < total) return fail(PSSBAM_EINVAL, "room for %llu runs, the coverage has %llu", (unsigned long long)cap, (unsigned long long)total);
+    if (!total) return PSSBAM_OK;
+    const uint64_t n_tiles = e->cov_len / COV_TILE;
+    if (e->cov_runs_cap < total) {   // [slot | start | end | depth], `total` words each; kept for the next call
+        if (e->d_cov_runs) HIP_TRY(hipFree(e->d_cov_runs));
+        e->d_cov_runs = nullptr;
+        e->cov_runs_cap = 0;
+        if (hipMalloc((void **)&e->d_cov_runs, 4 * total * sizeof(uint32_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(PSSBAM_ENOMEM, "the %llu coverage runs do not fit the device", (unsigned long long)total);
+        }
+        e->cov_runs_cap = total;
+    }
+    uint32_t *const d_runs = e->d_cov_runs;
+    std::vector<uint32_t> h(4 * total);
+    if (!e->cov_runs_scanned) {
+        hipLaunchKernelGGL(coverage_scan_sums, dim3(1), dim3(COV_SUMS_ROUND), 0, e->stream, e->d_cov_runcnt, n_tiles, (unsigned long long *)nullptr);
+        e->cov_runs_scanned = true;
+    }
+    hipLaunchKernelGGL(coverage_runs, dim3(coverage_grid(e, n_tiles)), dim3(COV_THREADS), 0, e->stream, (const uint32_t *)e->d_cov, n_tiles,
+                       (const unsigned long long *)e->d_cov_sums, (const unsigned long long *)e->d_cov_runcnt, (const uint4 *)e->d_cov_contigs,
+                       (uint32_t)e->cov_contigs.size(), total, d_runs, d_runs + total, d_runs + 2 * total, d_runs + 3 * total);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h.data(), d_runs, 4 * total * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    // the device's order is the genome's (contigs by name); the caller's is by refID: a contig's runs are one stretch of it
+    std::vector<std::pair<uint64_t, uint64_t>> stretch(e->cov_contigs.size(), {0, 0});
+    for (uint64_t i = 0; i < total;) {
+        const uint32_t s = h[i];
+        uint64_t j = i + 1;
+        while (j < total && h[j] == s) j++;
+        if (s < stretch.size()) stretch[s] = {i, j};
+        i = j;
+    }
+    std::vector<std::pair<uint32_t, uint32_t>> by_ref;   // {refID, slot}
+    for (size_t k = 0; k < e->cov_contigs.size(); k++) by_ref.emplace_back(e->cov_contigs[k].w, (uint32_t)k);
+    std::sort(by_ref.begin(), by_ref.end());
+    uint64_t at = 0;
+    for (const auto &rs : by_ref)
+        for (uint64_t i = stretch[rs.second].first; i < stretch[rs.second].second; i++, at++) {
+            if (ref) ref[at] = rs.first == (uint32_t)e->n_ref ? -1 : (int32_t)rs.first;
+            if (start) start[at] = h[total + i];
+            if (end) end[at] = h[2 * total + i];
+            if (depth) depth[at] = h[3 * total + i];
+        }
+    if (at != total) return fail(PSSBAM_EHIP, "coverage runs outside the listed contigs: %llu of %llu placed", (unsigned long long)at, (unsigned long long)total);
     return PSSBAM_OK;
 }
 

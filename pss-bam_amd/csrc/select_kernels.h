@@ -3,7 +3,8 @@
 // order, in one contiguous buffer.  Three steps behind the tally kernels of the same block, on the same stream:
 //
 //   select_mark    lane per read: the decision of tally_simple (decode_hdr, make_plan in its GAPPED form under -I, the -n
-//                  and -y filters), written as len[r] = kept ? record length : 0.  No counter, no event, no table add.
+//                  and -y filters: select_keep, which coverage_kernels.h asks too), written as len[r] = kept ? record length : 0.
+//                  No counter, no event, no table add.
 //   scan           exclusive prefix sum of len[] in place, plus the totals {bytes, records} kept: select_tile_sums (a sum
 //                  pair per tile of SELECT_SCAN_TILE entries), select_scan_sums (one workgroup, SELECT_SUMS_ROUND tile sums a
 //                  round, a carry between rounds), select_scan_tiles (the tile's own scan on top of its base).  After it
@@ -25,24 +26,32 @@ static constexpr uint32_t SELECT_GATHER_THREADS = 256, SELECT_GATHER_CHUNKS = 8;
 
 __device__ __forceinline__ uint32_t select_n_recs(const TallyParams &P) { return P.n_recs_dev ? min(*P.n_recs_dev, P.n_recs) : P.n_recs; }
 
+// Was record r (below the block's count) added to the forward or the reverse main table?  The one statement of "kept" on the
+// device: select_mark and coverage_add (coverage_kernels.h) both ask it.  pl = the record's plan, rec_len = its bytes in the block.
+__device__ __forceinline__ bool select_keep(const TallyParams &P, uint32_t r, GappedPlan &pl, uint32_t &rec_len) {
+    const uint32_t o0 = P.offs[r], o1 = P.offs[r + 1];
+    rec_len = o1 - o0;
+    GlobalBytes src{P.recs + o0};
+    const RecHdr h = decode_hdr(src, o1 - o0);
+    if (P.gapped) pl = make_plan<true, false, true, true>(P, src, h);
+    else static_cast<Plan &>(pl) = make_plan<true, true>(P, src, h);
+    bool keep = (P.tally_mask & 1u) != 0 && (pl.pss_fwd || pl.pss_rev);
+    if (keep && mism_on(P)) keep = !mism_beyond(P, count_mismatches(src, h, P.genome + pl.gbase, pl.s, pl.L, P.mism_tv != 0u));
+    if (keep && P.score_w) keep = !score_below(P, read_score(P, src, h, P.genome + pl.gbase, pl.s, pl.L, pl.rev));
+    return keep;
+}
+
 // len has P.n_recs + 1 entries (the host's bound of the count); the ones from the device's count on are zero
 __global__ void __launch_bounds__(256) select_mark(const TallyParams P, uint32_t *len) {
     const uint32_t n = select_n_recs(P);
-    const bool do_pss = (P.tally_mask & 1u) != 0;
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint64_t r64 = blockIdx.x * blockDim.x + threadIdx.x; r64 <= P.n_recs; r64 += stride) {
         const uint32_t r = (uint32_t)r64;
         if (r >= n) { len[r] = 0u; continue; }
-        const uint32_t o0 = P.offs[r], o1 = P.offs[r + 1];
-        GlobalBytes src{P.recs + o0};
-        const RecHdr h = decode_hdr(src, o1 - o0);
         GappedPlan pl;
-        if (P.gapped) pl = make_plan<true, false, true, true>(P, src, h);
-        else static_cast<Plan &>(pl) = make_plan<true, true>(P, src, h);
-        bool keep = do_pss && (pl.pss_fwd || pl.pss_rev);
-        if (keep && mism_on(P)) keep = !mism_beyond(P, count_mismatches(src, h, P.genome + pl.gbase, pl.s, pl.L, P.mism_tv != 0u));
-        if (keep && P.score_w) keep = !score_below(P, read_score(P, src, h, P.genome + pl.gbase, pl.s, pl.L, pl.rev));
-        len[r] = keep ? o1 - o0 : 0u;
+        uint32_t rec_len;
+        const bool keep = select_keep(P, r, pl, rec_len);
+        len[r] = keep ? rec_len : 0u;
     }
 }
 

@@ -208,6 +208,16 @@ static int send_read_score(pssbam_engine *e, const frontend_score *sc)
     return sc && pssbam_engine_set_read_score(e, sc->weights, sc->n_dist, sc->n_qual, sc->use_filter, sc->min_score, sc->hist_half, sc->hist_shift);
 }
 
+/* -c / -b: the sum of the BAM header's LN values (0: SAM text, whose references show up as they come), set before the engines are made */
+static uint64_t coverage_positions_hint;
+
+static void coverage_hint_from(const bam_header *h)
+{
+    uint64_t sum = 0;
+    for (int32_t i = 0; h && i < h->n_ref; i++) sum += h->ref_len[i];
+    coverage_positions_hint = sum;
+}
+
 /* The run's options (frontend_opts) onto one engine; non-zero: pssbam_last_error() says why.  Two are left to the callers, who
  * need them at a place of their own: -A (before feed_open on the helper's engines) and -G (the header's @RG IDs).  A new
  * option is one line here. */
@@ -226,7 +236,8 @@ static int apply_options(pssbam_engine *e)
            send_contig_sets(e, o->contig_sets) || (o->replicates > 0 && pssbam_engine_set_replicates(e, o->replicates)) ||
            (o->out_bam && (o->out_deflate ? pssbam_engine_set_block_sink(e, out_block_sink, NULL) : pssbam_engine_set_record_sink(e, out_sink, NULL))) ||
            (o->out_bam && o->out_mask_mode != PSSBAM_END_MASK_OFF && pssbam_engine_set_end_mask(e, o->out_mask_mode, o->out_mask_n5, o->out_mask_n3)) ||
-           (o->duplicates && pssbam_engine_set_duplicates(e, 1, 0));
+           (o->duplicates && pssbam_engine_set_duplicates(e, 1, 0)) ||
+           ((o->coverage || o->coverage_bedgraph) && pssbam_engine_set_coverage(e, 1, coverage_positions_hint));
 }
 
 static void *engine_make_main(void *arg)
@@ -258,6 +269,7 @@ static void early_feed_main(void)
     const int pin_started = pthread_create(&pin_th, NULL, pin_main, NULL) == 0;
     const bam_header *h = bam_reader_header(early_rd);
     out_header = h;   /* -O (the reader lives until run_tally() is through) */
+    coverage_hint_from(h);
     if (frontend_opts.group_by_rg && (EF.n_rg = pss_parse_read_groups(h->text, h->l_text, &EF.rg_ids)) < 0) EF.n_rg = 0;
     /* one engine per GPU, all created at once: a device's first touch (context, queues, code objects) takes ~0.08 s, and
      * eight of them one after the other would cost more than the whole command does on one GPU */
@@ -505,6 +517,15 @@ int env_gpu_count(void)
 void run_result_free(run_result *res)
 {
     pss_free_read_groups(res->group_ids, res->group_ids ? res->n_planes : 0);
+    for (int i = 0; res->cov_names && i < res->cov_n; i++) free(res->cov_names[i]);
+    free(res->cov_names);
+    free(res->cov_held);
+    free(res->cov_lengths);
+    free(res->cov_per_contig);
+    free(res->cov_run_ref);
+    free(res->cov_run_start);
+    free(res->cov_run_end);
+    free(res->cov_run_depth);
     free(res->plane_fwd);
     free(res->plane_rev);
     free(res->plane_k5);
@@ -718,6 +739,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
                             "enqueued %.3f (took this thread %.3f), references set + put-off tallies launched %.3f (took %.3f), feed drained %.3f\n",
                     EF.t_hip, EF.t_engines, EF.t_posted, EF.t_upload_dur, EF.t_genome_set, EF.t_genome_set_dur, EF.t_feed_end);
     } else {
+        coverage_hint_from(rd ? bam_reader_header(rd) : NULL);
         for (int g = 0; g < n_gpus; g++) {
             pssbam_config c = *cfg;
             const int have = pssbam_device_count();
@@ -908,6 +930,40 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             goto done;
         }
         res->has_duplicates = 1;
+    }
+    if (frontend_opts.coverage || frontend_opts.coverage_bedgraph) { /* -c / -b: the one engine's array */
+        const int32_t n_ref = rd ? bam_reader_header(rd)->n_ref : sam_reader_n_ref(sd);
+        const char *const *names = rd ? (const char *const *)bam_reader_header(rd)->ref_name : sam_reader_ref_names(sd);
+        res->cov_n = n_ref;
+        res->cov_names = (char **)calloc((size_t)n_ref + 1, sizeof *res->cov_names);
+        res->cov_held = (uint8_t *)calloc((size_t)n_ref + 1, 1);
+        res->cov_lengths = (uint64_t *)calloc((size_t)n_ref + 1, sizeof(uint64_t));
+        res->cov_per_contig = (uint64_t *)calloc(3 * ((size_t)n_ref + 1), sizeof(uint64_t));
+        if (!res->cov_names || !res->cov_held || !res->cov_lengths || !res->cov_per_contig) { fprintf(stderr, "Error: out of memory\n"); goto done; }
+        for (int32_t i = 0; i < n_ref; i++) {
+            const Seq *sq = find_seq(genome, names[i]);
+            res->cov_names[i] = strdup(names[i]);
+            res->cov_held[i] = sq != NULL;
+            res->cov_lengths[i] = sq ? sq->len : 0;
+        }
+        if (pssbam_engine_finish_coverage(eng[0], 0, n_ref, res->cov_per_contig, res->cov_hist, PSS_COV_HIST_MAX, &res->cov_n_runs)) {
+            fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+            goto done;
+        }
+        if (frontend_opts.coverage_bedgraph) {
+            const size_t room = (size_t)res->cov_n_runs + 1;
+            res->cov_run_ref = (int32_t *)malloc(room * sizeof(int32_t));
+            res->cov_run_start = (uint32_t *)malloc(room * sizeof(uint32_t));
+            res->cov_run_end = (uint32_t *)malloc(room * sizeof(uint32_t));
+            res->cov_run_depth = (uint32_t *)malloc(room * sizeof(uint32_t));
+            if (!res->cov_run_ref || !res->cov_run_start || !res->cov_run_end || !res->cov_run_depth) { fprintf(stderr, "Error: out of memory\n"); goto done; }
+            if (pssbam_engine_finish_coverage_runs(eng[0], res->cov_n_runs, res->cov_run_ref, res->cov_run_start, res->cov_run_end, res->cov_run_depth,
+                                                   &res->cov_n_runs)) {
+                fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+                goto done;
+            }
+        }
+        res->has_coverage = 1;
     }
     if (frontend_opts.length_hist > 0 && (cfg->tally_mask & PSSBAM_TALLY_PSS)) { /* -H: summed with the rest of the block */
         res->hist_max = frontend_opts.length_hist;

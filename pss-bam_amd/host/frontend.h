@@ -7,6 +7,7 @@
 
 #include "fasta-genome-io.h"
 #include "pssbam_hip.h"
+#include "coverage.h"
 #include "duplicates.h"
 #include "regions.h"
 
@@ -59,6 +60,15 @@ typedef struct run_result {
      * PSS_DUP_HIST_MAX + 2 entries (duplicates.h) */
     int has_duplicates;
     uint64_t dup_totals[3], dup_hist[PSS_DUP_HIST_MAX + 2];
+    /* -c / -b (frontend_opts.coverage / .coverage_bedgraph; has_coverage: filled): the cov_n references of the input, in header
+     * order -- name, whether the FASTA holds it, its length there, {covered, depth_sum, max_depth} -- the depth histogram,
+     * PSS_COV_HIST_MAX + 2 entries (coverage.h), and, for -b, the cov_n_runs runs (pssbam_engine_finish_coverage_runs) */
+    int has_coverage, cov_n;
+    char **cov_names;
+    uint8_t *cov_held;
+    uint64_t *cov_lengths, *cov_per_contig, cov_hist[PSS_COV_HIST_MAX + 2], cov_n_runs;
+    int32_t *cov_run_ref;
+    uint32_t *cov_run_start, *cov_run_end, *cov_run_depth;
 } run_result;
 
 /* -y / -Y: the weight table [4][n_dist][n_qual], the filter (use_filter: only reads with a score of at least min_score are
@@ -142,6 +152,11 @@ typedef struct frontend_options {
     /* -d: non-zero = the run's one engine flags the duplicates in front of its tally (pssbam_engine_set_duplicates) and
      * run_tally() returns the totals and the group-size histogram.  One GPU: duplicates are defined by the input order. */
     int duplicates;
+    /* pss-bam -c / -b: coverage != 0 = the summary is wanted, coverage_bedgraph != NULL = the runs are; with either, the run's one
+     * engine keeps the depth of coverage of the reads it adds to a table (pssbam_engine_set_coverage, with the sum of the header's
+     * LN values as its hint) and run_tally() returns the per-contig figures and the histogram, and for -b the runs.  One GPU. */
+    int coverage;
+    const char *coverage_bedgraph;
 } frontend_options;
 extern frontend_options frontend_opts;   /* everything off */
 

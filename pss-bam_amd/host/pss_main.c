@@ -95,6 +95,15 @@
  * mates is out of scope.  Also writes <prefix>.pss.duplicates.txt: eligible reads, distinct keys, flagged reads, their fraction, and
  * how many keys have 1, 2, ..., 255 and more reads (duplicates.h).  With -O the BAM is the filtered, deduplicated one.  Goes with every
  * other option except -I; SAM text is fine; one GPU (PSSBAM_NGPU unset or 1): the input order defines the duplicates.
+ * Added: -c and -b <file> report the depth of coverage of the tallied reads, from the same pass: a read added to a table -- exactly the
+ * reads -O writes, after every filter given and after -d -- covers POS .. POS + length - 1 of its contig, mates that overlap count
+ * twice, and -Q and -K change nothing.  -c writes <prefix>.pss.coverage.txt: per reference of the input's header that the FASTA
+ * holds its length, covered bases, breadth, depth sum, mean and maximum depth, a total line, and the positions at depth 0..255 and
+ * above (coverage.h); it is what per-base depth over the -O file of the same run gives.  -b writes the covered intervals as a
+ * bedGraph (0-based, half-open, non-zero depth only, header order), what `bedtools genomecov -bg` gives for that file; it takes its
+ * name when it is complete and must not name the -B or the -O file.  Either switches the engine's array on (4 bytes per genome
+ * position on the device); -b alone writes no summary.  Not with -I (the span of a clipped read needs a definition of its own); SAM
+ * text is fine; one GPU (PSSBAM_NGPU unset or 1): the arrays of several engines are not summed.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -109,6 +118,7 @@
 #include "base_quality.h"
 #include "composition.h"
 #include "contig_sets.h"
+#include "coverage.h"
 #include "duplicates.h"
 #include "end_mask.h"
 #include "fasta-genome-io.h"
@@ -145,9 +155,10 @@ int main(int argc, char *argv[])
     const char *max_mm_arg = NULL, *mm_hist_arg = NULL, *rep_arg = NULL, *interior_arg = NULL, *comp_arg = NULL, *min_score_arg = NULL;
     const char *out_bam = NULL, *out_level_arg = NULL;
     const char *out_mask_arg = NULL;
-    int out_deflate = 0, duplicates = 0;
+    int out_deflate = 0, duplicates = 0, coverage = 0;
+    const char *bedgraph = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:P:y:YO:z:ZK:d")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:P:y:YO:z:ZK:dcb:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -182,6 +193,8 @@ int main(int argc, char *argv[])
         case 'Z': out_deflate = 1; break;
         case 'K': out_mask_arg = optarg; break;
         case 'd': duplicates = 1; break;
+        case 'c': coverage = 1; break;
+        case 'b': bedgraph = optarg; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -226,7 +239,9 @@ int main(int argc, char *argv[])
               "-z <level> <with -O: BGZF compression level 0..9 (default: 1)>\n"
               "-Z <with -O: deflate the BAM's blocks on the GPU, not with zlib on the host (blocks cut every 0xFF00 bytes; not with -z)>\n"
               "-K <all|ds|ss>,<n5>[,<n3>] <with -O: in that BAM, mask the first n5 bases of the 5' and n3 (default: n5) of the 3' end of each read with N, quality 0: all of them, T at 5' / A at 3' (ds) or T at both (ss)>\n"
-              "-d <flag duplicates before the tally: unpaired reads with the contig, position, length, strand (and, where the tables are split by read group, read group) of an earlier read; also write the duplication histogram (one GPU; not with -I)>\n",
+              "-d <flag duplicates before the tally: unpaired reads with the contig, position, length, strand (and, where the tables are split by read group, read group) of an earlier read; also write the duplication histogram (one GPU; not with -I)>\n"
+              "-c <also write the depth of coverage of the tallied reads: per contig covered bases, breadth, mean and maximum depth, and the depth histogram (one GPU; not with -I)>\n"
+              "-b <out.bedgraph> <also write the intervals the tallied reads cover, with their depth, as a bedGraph (one GPU; not with -I)>\n",
               stderr);
         exit(1);
     }
@@ -325,6 +340,40 @@ int main(int argc, char *argv[])
     if (duplicates && getenv("PSSBAM_NGPU") && atoi(getenv("PSSBAM_NGPU")) > 1) {
         fprintf(stderr, "-d keeps the first read of a group in input order, which one GPU keeps: not with PSSBAM_NGPU=%s.\n", getenv("PSSBAM_NGPU"));
         exit(1);
+    }
+    /* -c / -b: no row of the table below either (they use no counter words; they go with every option but -I) */
+    if ((coverage || bedgraph) && gapped) {
+        fprintf(stderr, "%s does not go with %s: the span of a clipped or gapped read is not defined.\n", coverage ? "-c (depth of coverage)" : "-b (coverage bedGraph)", L_I);
+        exit(1);
+    }
+    if ((coverage || bedgraph) && getenv("PSSBAM_NGPU") && atoi(getenv("PSSBAM_NGPU")) > 1) {
+        fprintf(stderr, "%s keeps one depth array, on one GPU: not with PSSBAM_NGPU=%s.\n", coverage ? "-c" : "-b", getenv("PSSBAM_NGPU"));
+        exit(1);
+    }
+    if (bedgraph) {
+        const struct { const char *what, *path; } others[] = {{"the input (-B", bam_fn}, {"the BAM of the tallied reads (-O", out_bam}};
+        for (size_t i = 0; i < sizeof others / sizeof *others; i++) {
+            struct stat sa, sb;
+            const char *path = others[i].path;
+            if (path && (!strcmp(bedgraph, path) || (stat(bedgraph, &sa) == 0 && stat(path, &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino))) {
+                fprintf(stderr, "-b must not name %s %s).\n", others[i].what, path);
+                exit(1);
+            }
+        }
+        /* (a place that cannot be written is found out now, not after the genome has been loaded; a file that is there already
+         * under the temporary name is opened for appending and left as it is) */
+        char *tmp = (char *)malloc(strlen(bedgraph) + 5);
+        if (!tmp) { fprintf(stderr, "Error: out of memory\n"); exit(1); }
+        sprintf(tmp, "%s.tmp", bedgraph);
+        const int was_there = access(tmp, F_OK) == 0;
+        FILE *probe = fopen(tmp, "a");
+        if (!probe) {
+            fprintf(stderr, "-b: cannot create %s.\n", tmp);
+            exit(1);
+        }
+        fclose(probe);
+        if (!was_there) remove(tmp);
+        free(tmp);
     }
     /* The exclusive options: at most one row may be given (their tables share the words behind the engine's planes, and
      * one pass over 32 table rows).  Of two, the later row is named first, by all it was given with, the earlier one by
@@ -518,6 +567,8 @@ int main(int argc, char *argv[])
     else if (out_bam) fprintf(stderr, " -O %s -z %d", out_bam, out_level);
     if (out_mask_arg) fprintf(stderr, " -K %s,%u,%u", out_mask_mode == PSSBAM_END_MASK_ALL ? "all" : out_mask_mode == PSSBAM_END_MASK_DS ? "ds" : "ss", out_mask_n5, out_mask_n3);
     if (duplicates) fprintf(stderr, " -d");
+    if (coverage) fprintf(stderr, " -c");
+    if (bedgraph) fprintf(stderr, " -b %s", bedgraph);
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -562,6 +613,8 @@ int main(int argc, char *argv[])
     frontend_opts.out_mask_n5 = out_mask_n5;
     frontend_opts.out_mask_n3 = out_mask_n3;
     frontend_opts.duplicates = duplicates;
+    frontend_opts.coverage = coverage;
+    frontend_opts.coverage_bedgraph = bedgraph;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
      * load; only the tally launches wait for the genome (frontend.c) */
@@ -591,6 +644,14 @@ int main(int argc, char *argv[])
     if (res.comp5 && pss_write_composition(fasta_fn, bam_fn, out_prefix, res.composition_width, res.comp5, res.comp3)) exit(1);   /* -P */
     if (res.score_fwd && pss_write_read_scores(fasta_fn, bam_fn, out_prefix, res.score_half, res.score_fwd, res.score_rev)) exit(1);   /* -Y */
     if (res.has_duplicates && pss_write_duplicates(fasta_fn, bam_fn, out_prefix, "pss", res.dup_totals, res.dup_hist, PSS_DUP_HIST_MAX)) exit(1);   /* -d */
+    if (res.has_coverage && coverage &&
+        pss_write_coverage(fasta_fn, bam_fn, out_prefix, res.cov_n, (const char *const *)res.cov_names, res.cov_held, res.cov_lengths, res.cov_per_contig, res.cov_hist,
+                           PSS_COV_HIST_MAX))
+        exit(1);   /* -c */
+    if (res.has_coverage && bedgraph &&
+        pss_write_coverage_bedgraph(bedgraph, res.cov_n, (const char *const *)res.cov_names, res.cov_n_runs, res.cov_run_ref, res.cov_run_start, res.cov_run_end,
+                                    res.cov_run_depth))
+        exit(1);   /* -b */
     if (res.site_fwd) {   /* -X: IN as the engine returns it; OUT = T - IN on the position rows, the context rows as T */
         const size_t cells = (size_t)(region_len + 2) * 16;
         unsigned long *out_fwd = (unsigned long *)malloc(cells * sizeof *out_fwd), *out_rev = (unsigned long *)malloc(cells * sizeof *out_rev);
