@@ -784,6 +784,41 @@ int pssbam_engine_finish_coverage(pssbam_engine *e, int32_t first_ref, int32_t n
 int pssbam_engine_finish_coverage_runs(pssbam_engine *e, uint64_t cap, int32_t *ref, uint32_t *start, uint32_t *end, uint32_t *depth,
                                        uint64_t *n_runs);
 
+/* Strand-split allele counts of the kept records at listed sites (pss-bam -a / -t), from the same pass: the pileup at a SNP panel.
+ *   A site is a (contig, 0-based position) pair: site i is pos0[i] on the contig named names[name_of[i]].  Positions may come in any
+ *     order; duplicates are merged.  Names are matched to the names of pssbam_engine_set_references exactly as
+ *     pssbam_engine_set_regions matches them: a name no reference carries is dropped, so is a position at or beyond the contig's
+ *     stored length, and so is the later of two references of the same name.  The engine keeps the name -> positions map and
+ *     packs the device table whenever this call or set_references arrives.
+ *   Kept: exactly the records a record sink delivers and the coverage counts (above), each mate on its own.
+ *   A kept record with start s and table length L (the length of its <L>M CIGAR) shows, at every resolved site p of its contig with
+ *     s + trim <= p < s + L - trim, the stored SEQ base at offset p - s; a record with 2 * trim >= L shows nothing.  The site's counter
+ *     [strand][code] goes up by one: strand 0 = forward, 1 = FLAG 0x10; code = A, C, G, T or other.  Other takes N and every IUPAC
+ *     nibble, under a minimum base quality a base whose QUAL is below it (an absent QUAL, 0xFF, is never below), and an offset at or
+ *     beyond l_seq (a paired record whose SEQ disagrees with its CIGAR).  With trim 0 the ten counters of a site sum to the depth of
+ *     coverage there.  The end mask changes the sink's bytes only: the counts are of the unmasked read.
+ * Device side (csrc/allele_kernels.h): the resolved sites as sorted 64-bit genome indices (8 bytes a site), a lookup grid of one
+ * uint32_t per 2^shift genome positions ($PSSBAM_SITE_GRID_SHIFT, 2..20, default 10) and ten uint32_t counters a site, exact below
+ * 2^32; one more kernel behind each block's tally kernels.  The counter block keeps its size and layout, and the time and launch
+ * count of pssbam_engine_kernel_time stay the tally's.
+ * n_sites == 0 switches it off.  Legal after create or reset, before or after set_references, and before the first submit
+ * (PSSBAM_ESTATE later).  PSSBAM_EINVAL without PSSBAM_TALLY_PSS, with gapped reads (pssbam_engine_set_gapped_reads) in either order of
+ * the two calls, for n_sites above PSSBAM_MAX_REGIONS and for trim above PSSBAM_MAX_SITE_TRIM; PSSBAM_ENOMEM from the call that cannot
+ * get the memory.  The setting survives pssbam_engine_reset, which zeroes the counters.  Engines share nothing, and
+ * pssbam_reduce_counters does not sum these counters.  Off, nothing is allocated and nothing more is launched. */
+#define PSSBAM_MAX_SITE_TRIM 65535
+int pssbam_engine_set_sites(pssbam_engine *e, int32_t n_names, const char *const *names, int64_t n_sites, const int32_t *name_of,
+                            const uint32_t *pos0, uint32_t trim);
+/* Drains like pssbam_engine_finish, then gives the counts of everything submitted since create or reset.  Non-destructive: it may be
+ * called any number of times, and more blocks may follow.  The resolved sites come ordered by reference index, then
+ * position: ref[i], pos0[i], ref_base[i] = the genome's stored base there as a letter (A C G T, anything else N;
+ * gathered by a small kernel) and counts[10 * i ..] = fA fC fG fT fO rA rC rG rT rO.  *n_sites = the exact count, always; with the
+ * four arrays and totals NULL that is all the call does.  Any single array may be NULL.  totals (may be NULL) = {sites given after
+ * merging, sites resolved, sites with a non-zero sum, bases counted}.  PSSBAM_EINVAL when cap, the room of each array, is below the
+ * count, and when the setting is off. */
+int pssbam_engine_finish_sites(pssbam_engine *e, uint64_t cap, int32_t *ref, uint32_t *pos0, uint8_t *ref_base,
+                               uint32_t *counts /* 10 per site: fA fC fG fT fO rA rC rG rT rO */, uint64_t *n_sites, uint64_t totals[4]);
+
 /* Drains the engine like pssbam_engine_finish and copies the two arrays, 2 * hist_half words each; either pointer may be
  * NULL.  PSSBAM_EINVAL without a histogram. */
 int pssbam_engine_finish_read_score(pssbam_engine *e, uint64_t *fwd, uint64_t *rev);

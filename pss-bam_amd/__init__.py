@@ -53,6 +53,7 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_record_sink", "pssbam_engine_set_block_sink", "pssbam_engine_set_end_mask",
     "pssbam_engine_set_duplicates", "pssbam_engine_finish_duplicates",
     "pssbam_engine_set_coverage", "pssbam_engine_finish_coverage", "pssbam_engine_finish_coverage_runs",
+    "pssbam_engine_set_sites", "pssbam_engine_finish_sites",
     "pssbam_bgzf_deflate_work_bytes", "pssbam_bgzf_deflate_device", "pssbam_bgzf_deflate_host",
 ]
 MAX_READ_GROUPS = 4096
@@ -77,6 +78,7 @@ END_MASK_MODES = {None: END_MASK_OFF, "off": END_MASK_OFF, "all": END_MASK_ALL, 
 MAX_END_MASK = 65535
 MAX_DUP_HIST = 65535
 COV_HIST_MAX = 255
+MAX_SITE_TRIM = 65535
 END_PRESETS = {"ss": (13, 13), "ds": (13, 2)}   # (cell5, cell3): C->T at both ends / C->T at the 5' end, G->A at the 3' end
 GAPPED_TILED_OPS = 16   # pss-bam -I: CIGAR ops a lane of the tiled kernel walks (csrc/record_decode.h); more take the one-lane path
 EBUSY = -7
@@ -192,6 +194,9 @@ def hip_lib() -> C.CDLL:
         L.pssbam_engine_set_coverage.argtypes = [C.c_void_p, C.c_int32, C.c_uint64]
         L.pssbam_engine_finish_coverage.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.pssbam_engine_finish_coverage_runs.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "pssbam_engine_set_sites"):   # (tools/allele_bench.py also loads the library of the commit before it)
+        L.pssbam_engine_set_sites.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int64, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.pssbam_engine_finish_sites.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pssbam_index_records.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     _hip = L
     return L
@@ -860,6 +865,38 @@ class Engine:
                                                         C.addressof(n_runs)))
         n = int(n_runs.value)
         return ref[:n], start[:n], end[:n], depth[:n]
+
+    def set_sites(self, names, name_of, pos0, trim: int = 0):
+        """Strand-split allele counts of the kept records at listed sites (pssbam_engine_set_sites): site i is the 0-based position
+        pos0[i] on contig names[name_of[i]] (numpy arrays or sequences; any order, duplicates merge); a kept read counts at the sites
+        between its first and last `trim` bases.  No site switches it off.  Before the first submit, before or after
+        set_references; needs the substitution tally; not with set_gapped; survives reset."""
+        raw = [nm.encode() if isinstance(nm, str) else bytes(nm) for nm in names]
+        arr = (C.c_char_p * max(len(raw), 1))(*raw)
+        name_of = np.ascontiguousarray(name_of, dtype=np.int32)
+        pos0 = np.ascontiguousarray(pos0, dtype=np.uint32)
+        if name_of.size != pos0.size:
+            raise ValueError("name_of and pos0 must have one entry per site")
+        _chk(self._L.pssbam_engine_set_sites(self._h, len(raw), arr, name_of.size, name_of.ctypes.data, pos0.ctypes.data, int(trim)))
+
+    def finish_sites(self, cap: int | None = None):
+        """sync, then (ref, pos0, ref_base, counts, totals) of everything since create / reset: the resolved sites by refID then
+        position, ref_base as uint8 letters, counts[n, 10] = fA fC fG fT fO rA rC rG rT rO, totals = {"given", "resolved", "covered",
+        "bases"}.  Non-destructive.  cap: the room to offer (default: the exact count, asked for first)."""
+        n_sites = C.c_uint64(0)
+        if cap is None:
+            _chk(self._L.pssbam_engine_finish_sites(self._h, 0, None, None, None, None, C.addressof(n_sites), None))
+            cap = int(n_sites.value)
+        room = max(int(cap), 1)
+        ref = np.zeros(room, dtype=np.int32)
+        pos0 = np.zeros(room, dtype=np.uint32)
+        base = np.zeros(room, dtype=np.uint8)
+        counts = np.zeros((room, 10), dtype=np.uint32)
+        totals = np.zeros(4, dtype=np.uint64)
+        _chk(self._L.pssbam_engine_finish_sites(self._h, int(cap), ref.ctypes.data, pos0.ctypes.data, base.ctypes.data, counts.ctypes.data,
+                                                C.addressof(n_sites), totals.ctypes.data))
+        n = int(n_sites.value)
+        return ref[:n], pos0[:n], base[:n], counts[:n], dict(zip(("given", "resolved", "covered", "bases"), (int(v) for v in totals)))
 
     def finish_blocks(self) -> np.ndarray:
         """sync, then every block collected since set_block_sink() / the last finish_blocks(), as one uint8 array;

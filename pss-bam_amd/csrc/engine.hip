@@ -21,6 +21,7 @@
 #include <tuple>
 #include <type_traits>
 #include <unordered_map>
+#include <unordered_set>
 #include <atomic>
 #include <memory>
 #include <mutex>
@@ -31,6 +32,7 @@
 #include "end_mask_kernels.h"
 #include "dedup_kernels.h"
 #include "coverage_kernels.h"
+#include "allele_kernels.h"
 #include "deflate_kernels.h"
 
 using namespace pssbam;
@@ -340,6 +342,23 @@ struct pssbam_engine {
     uint4 *d_region_info = nullptr;
     uint32_t *d_region_grid = nullptr;
     uint2 *d_region_iv = nullptr;
+    // allele counts at listed sites (pssbam_engine_set_sites, allele_kernels.h): contig name -> its positions, sorted and merged,
+    // kept on the host; the device table is packed from it whenever the reference list or the map changes (pack_sites).  Off:
+    // nothing below is allocated and nothing more is launched.  The packed table is in the genome's order (sorted indices);
+    // site_ref / site_pos / site_slot list the resolved sites in the caller's order, by refID then position, with their slot there.
+    std::unordered_map<std::string, std::vector<uint32_t>> sites;
+    bool has_sites = false;
+    uint32_t site_trim = 0;
+    uint32_t site_shift = 10;              // a grid word per 2^shift genome indices ($PSSBAM_SITE_GRID_SHIFT)
+    uint64_t sites_given = 0;              // after merging
+    std::vector<uint64_t> site_idx;        // the packed table's genome indices, ascending (without the closing entry)
+    std::vector<int32_t> site_ref;
+    std::vector<uint32_t> site_pos, site_slot;
+    bool site_counts_void = false;         // a genome was set since the packing: the next one starts from zero
+    uint64_t *d_site_idx = nullptr;
+    uint32_t *d_site_grid = nullptr, *d_site_counts = nullptr;
+    uint8_t *d_site_base = nullptr;        // finish_sites' reference letters
+    uint64_t site_cells = 0;
     // counters
     unsigned long long *d_counters = nullptr;      // block in use (own or caller-bound)
     unsigned long long *d_counters_own = nullptr;  // the engine's own allocation
@@ -535,6 +554,7 @@ extern "C" int pssbam_engine_create(const pssbam_config *cfg, pssbam_engine **ou
     if (getenv("PSSBAM_CONTIG_EVICT")) e->contig_evict = env_int("PSSBAM_CONTIG_EVICT") != 0;
     if (getenv("PSSBAM_HIST_LDS_BINS")) e->env_hist_lds_bins = std::max(env_int("PSSBAM_HIST_LDS_BINS"), 0);
     if (const int g = env_int("PSSBAM_REGION_GRID_SHIFT")) e->region_shift = (uint32_t)std::min(std::max(g, 2), 20);
+    if (const int g = env_int("PSSBAM_SITE_GRID_SHIFT")) e->site_shift = (uint32_t)std::min(std::max(g, 2), 20);
     if (getenv("PSSBAM_COMPACT")) e->use_compact = env_int("PSSBAM_COMPACT") != 0;
     if (getenv("PSSBAM_COMPACT_PLAN_ONCE")) e->compact_plan_once = env_int("PSSBAM_COMPACT_PLAN_ONCE") != 0;
     if (tstat)
@@ -596,6 +616,8 @@ extern "C" void pssbam_engine_destroy(pssbam_engine *e) {
     if (e->d_dedup_state) (void)hipFree(e->d_dedup_state);
     if (e->h_dedup_state) (void)hipHostFree(e->h_dedup_state);
     if (e->dedup_ev) (void)hipEventDestroy(e->dedup_ev);
+    for (void *q : {(void *)e->d_site_idx, (void *)e->d_site_grid, (void *)e->d_site_counts, (void *)e->d_site_base})
+        if (q) (void)hipFree(q);
     if (e->d_cov) (void)hipFree(e->d_cov);
     if (e->d_cov_sums) (void)hipFree(e->d_cov_sums);
     if (e->d_cov_runcnt) (void)hipFree(e->d_cov_runcnt);
@@ -750,6 +772,7 @@ static int genome_upload(pssbam_engine *e, size_t n, const char *const *ids, con
     // depth of coverage: zeroed on the genome's stream (every tally waits for genome_ready; kernels of an earlier genome that
     // added to it on the engine's stream have been waited for above, where that genome was freed)
     if (e->coverage) HIP_TRY(hipMemsetAsync(e->d_cov, 0, e->cov_len * sizeof(uint32_t), gs));
+    e->site_counts_void = true;   // allele counts: the table packed for the genome before counts nothing of this one
     HIP_TRY(hipEventRecord(e->genome_ready, gs));
     e->genome_wait_pending = true;
     e->contig_start.assign(start.begin(), start.begin() + n);
@@ -908,6 +931,140 @@ extern "C" int pssbam_engine_set_regions(pssbam_engine *e, int32_t n_names, cons
     return e->have_refs ? pack_regions(e, true) : PSSBAM_OK;   // (otherwise set_references packs the table when it comes)
 }
 
+// Allele counts: packs the site table for the current reference list (ref_names / ref_info_host) and genome on the device: the
+// resolved sites as sorted genome indices with a closing entry, the grid over them and the counters (allele_kernels.h).  A name
+// no reference carries, a position at or beyond the contig's stored length and the later of two references of one name are
+// dropped.  Counters of a table that has counted (SAM text: the reference list grows while blocks are tallied) move to the new
+// table by genome index; after create, reset or a new genome they start from zero.
+static void free_sites(pssbam_engine *e) {
+    for (void **q : {(void **)&e->d_site_idx, (void **)&e->d_site_grid, (void **)&e->d_site_counts, (void **)&e->d_site_base})
+        if (*q) { (void)hipFree(*q); *q = nullptr; }
+    e->site_cells = 0;
+}
+
+static int pack_sites(pssbam_engine *e) {
+    if (!e->has_sites) return PSSBAM_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<uint32_t> old_counts;
+    std::vector<uint64_t> old_idx;
+    if (e->d_site_idx) {   // queued kernels may still add to the table that is replaced
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        if (e->tallied && !e->site_counts_void && !e->site_idx.empty()) {
+            old_counts.resize(e->site_idx.size() * ALLELE_WORDS);
+            HIP_TRY(hipMemcpy(old_counts.data(), e->d_site_counts, old_counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            old_idx.swap(e->site_idx);
+        }
+        free_sites(e);
+    }
+    e->site_counts_void = false;
+    e->site_idx.clear();
+    e->site_ref.clear();
+    e->site_pos.clear();
+    e->site_slot.clear();
+    std::unordered_set<uint64_t> seen;   // the contigs met so far, by their place in the genome
+    for (size_t i = 0; i < (size_t)e->n_ref; i++) {   // (the entry behind them answers RNAME "*": no site is listed there)
+        const uint4 ri = e->ref_info_host[i];
+        if (!ri.w) continue;   // the genome lacks the name
+        const auto it = e->sites.find(e->ref_names[i]);
+        if (it == e->sites.end()) continue;
+        const uint64_t lo = ((uint64_t)ri.y << 32) | ri.x;
+        if (!seen.insert(lo).second) continue;   // the later of two references of one name
+        for (const uint32_t p : it->second) {   // (ascending: the ones inside the contig lead)
+            if (p >= ri.z) break;
+            e->site_ref.push_back((int32_t)i);
+            e->site_pos.push_back(p);
+            e->site_idx.push_back(lo + p);
+        }
+    }
+    const size_t n = e->site_idx.size();
+    if (!n) return PSSBAM_OK;   // nothing resolved: nothing allocated, nothing launched
+    std::vector<uint32_t> order(n);
+    for (size_t j = 0; j < n; j++) order[j] = (uint32_t)j;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return e->site_idx[a] < e->site_idx[b]; });
+    std::vector<uint64_t> idx(n + 1);
+    e->site_slot.assign(n, 0u);
+    for (size_t k = 0; k < n; k++) {
+        idx[k] = e->site_idx[order[k]];
+        e->site_slot[order[k]] = (uint32_t)k;
+    }
+    idx[n] = ~0ull;
+    e->site_idx.assign(idx.begin(), idx.begin() + (ptrdiff_t)n);
+    // grid[c] = the first site at or after c << shift; one closing word = n
+    const uint32_t g = e->site_shift;
+    const uint64_t n_cells = (e->genome_bytes >> g) + 1;
+    std::vector<uint32_t> grid((size_t)n_cells + 1);
+    {
+        size_t k = 0;
+        for (uint64_t c = 0; c <= n_cells; c++) {
+            while (k < n && idx[k] < (c << g)) k++;
+            grid[(size_t)c] = (uint32_t)k;
+        }
+    }
+    std::vector<uint32_t> counts(n * ALLELE_WORDS, 0u);
+    for (size_t k = 0, o = 0; k < n && o < old_idx.size(); k++) {   // both ascending
+        while (o < old_idx.size() && old_idx[o] < idx[k]) o++;
+        if (o < old_idx.size() && old_idx[o] == idx[k]) memcpy(&counts[k * ALLELE_WORDS], &old_counts[o * ALLELE_WORDS], ALLELE_WORDS * sizeof(uint32_t));
+    }
+    if (hipMalloc((void **)&e->d_site_idx, idx.size() * sizeof(uint64_t)) != hipSuccess || hipMalloc((void **)&e->d_site_grid, grid.size() * sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc((void **)&e->d_site_counts, counts.size() * sizeof(uint32_t)) != hipSuccess || hipMalloc((void **)&e->d_site_base, n) != hipSuccess) {
+        (void)hipGetLastError();
+        free_sites(e);
+        e->site_idx.clear();
+        e->site_ref.clear();
+        e->site_pos.clear();
+        e->site_slot.clear();
+        return fail(PSSBAM_ENOMEM, "the site table (%llu sites, %llu grid words at shift %u) does not fit the device", (unsigned long long)n,
+                    (unsigned long long)grid.size(), g);
+    }
+    e->site_cells = n_cells;
+    HIP_TRY(hipMemcpy(e->d_site_idx, idx.data(), idx.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_site_grid, grid.data(), grid.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_site_counts, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return PSSBAM_OK;
+}
+
+extern "C" int pssbam_engine_set_sites(pssbam_engine *e, int32_t n_names, const char *const *names, int64_t n_sites, const int32_t *name_of,
+                                       const uint32_t *pos0, uint32_t trim) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (n_names < 0 || n_sites < 0 || n_sites > PSSBAM_MAX_REGIONS) return fail(PSSBAM_EINVAL, "site count outside 0..%d", PSSBAM_MAX_REGIONS);
+    if (trim > PSSBAM_MAX_SITE_TRIM) return fail(PSSBAM_EINVAL, "site trim %u above %d", trim, PSSBAM_MAX_SITE_TRIM);
+    if ((n_names && !names) || (n_sites && (!name_of || !pos0))) return fail(PSSBAM_EINVAL, "null site list");
+    if (n_sites) {
+        if (!(e->cfg.tally_mask & PSSBAM_TALLY_PSS)) return fail(PSSBAM_EINVAL, "the sites count the bases of the reads in the substitution tables: the engine needs PSSBAM_TALLY_PSS");
+        if (e->gapped) return fail(PSSBAM_EINVAL, "sites do not go with gapped reads (pssbam_engine_set_gapped_reads): the offsets of a clipped or gapped read need a CIGAR walk");
+    }
+    if (e->tallied || e->cur_feed >= 0 || !e->deferred.empty())
+        return fail(PSSBAM_ESTATE, "records have been tallied already: set the sites after create or reset, before the first submit");
+    std::unordered_map<std::string, std::vector<uint32_t>> map;
+    for (int64_t i = 0; i < n_sites; i++) {
+        if (name_of[i] < 0 || name_of[i] >= n_names) return fail(PSSBAM_EINVAL, "site %lld: contig index %d outside 0..%d", (long long)i, name_of[i], n_names - 1);
+        if (!names[name_of[i]]) return fail(PSSBAM_EINVAL, "site contig name %d is NULL", name_of[i]);
+        map[names[name_of[i]]].push_back(pos0[i]);
+    }
+    uint64_t given = 0;
+    for (auto &kv : map) {   // sorted, duplicates merged
+        std::vector<uint32_t> &v = kv.second;
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+        given += v.size();
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    e->sites.swap(map);
+    e->has_sites = n_sites > 0;
+    e->site_trim = trim;
+    e->sites_given = given;
+    if (!e->has_sites) {   // switched off: nothing stays allocated, the engine launches what it launches without the call
+        if (e->d_site_idx) HIP_TRY(hipStreamSynchronize(e->stream));
+        free_sites(e);
+        e->site_idx.clear();
+        e->site_ref.clear();
+        e->site_pos.clear();
+        e->site_slot.clear();
+        return PSSBAM_OK;
+    }
+    return e->have_refs ? pack_sites(e) : PSSBAM_OK;   // (otherwise set_references packs the table when it comes)
+}
+
 static int size_per_contig(pssbam_engine *e, int32_t n_ref);
 
 extern "C" int pssbam_engine_set_references(pssbam_engine *e, int32_t n_ref, const char *const *names) {
@@ -970,6 +1127,7 @@ extern "C" int pssbam_engine_set_references(pssbam_engine *e, int32_t n_ref, con
     e->ref_info_host.swap(info);
     coverage_contigs(e);   // depth of coverage: the list its finish kernels find a position's contig in
     if (const int rc = pack_regions(e, replaced)) return rc;   // -T: the region table follows the reference list
+    if (const int rc = pack_sites(e)) return rc;               // the site table too
     return feed_resume(e);   // super-batches inflated ahead of the genome are tallied now
 }
 
@@ -1761,6 +1919,13 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         HIP_TRY(hipGetLastError());
         e->cov_totals_valid = false;
     }
+    // allele counts at the listed sites: behind the tally like the coverage's kernel; nothing is launched while no site is resolved
+    if (e->has_sites && e->d_site_idx) {
+        const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)n_records + 255) / 256, (uint64_t)e->n_cu * 8));
+        hipLaunchKernelGGL(allele_add, dim3(grid), dim3(256), 0, e->stream, P, (const uint64_t *)e->d_site_idx, (uint32_t)e->site_idx.size(),
+                           (const uint32_t *)e->d_site_grid, e->site_cells, e->site_shift, e->site_trim, e->d_site_counts);
+        HIP_TRY(hipGetLastError());
+    }
     // the record sink: the kept records of this block, behind its tally and in front of whatever frees the block's buffers
     if (sink_on(e)) return launch_select(e, P, nbytes);
     return PSSBAM_OK;
@@ -2185,6 +2350,7 @@ extern "C" int pssbam_engine_set_gapped_reads(pssbam_engine *e, int32_t on) {
         if (const int rc = check_exclusive(e, MODE_GAPPED)) return rc;
         if (e->dedup) return fail(PSSBAM_EINVAL, "gapped reads do not go with duplicate flagging (pssbam_engine_set_duplicates): the key of a clipped read is not defined");
         if (e->coverage) return fail(PSSBAM_EINVAL, "gapped reads do not go with coverage (pssbam_engine_set_coverage): the span of a clipped or gapped read is not defined");
+        if (e->has_sites) return fail(PSSBAM_EINVAL, "gapped reads do not go with sites (pssbam_engine_set_sites): the offsets of a clipped or gapped read need a CIGAR walk");
     }
     if (e->tallied) return fail(PSSBAM_ESTATE, "records have been tallied already: set gapped reads after create or reset, before the first tally");
     e->gapped = on != 0;   // (the counter block keeps its size: a caller-bound block stays bound)
@@ -2622,6 +2788,58 @@ extern "C" int pssbam_engine_reset(pssbam_engine *e) {
     if (e->d_cov) {   // coverage: all zero again, at the size it has; the setting stays
         HIP_TRY(hipMemsetAsync(e->d_cov, 0, e->cov_len * sizeof(uint32_t), e->stream));
         e->cov_totals_valid = false;
+    }
+    if (e->d_site_counts)   // allele counts: all zero again; the sites stay
+        HIP_TRY(hipMemsetAsync(e->d_site_counts, 0, e->site_idx.size() * ALLELE_WORDS * sizeof(uint32_t), e->stream));
+    return PSSBAM_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// allele counts at listed sites (allele_kernels.h): the finish
+// --------------------------------------------------------------------------------------
+extern "C" int pssbam_engine_finish_sites(pssbam_engine *e, uint64_t cap, int32_t *ref, uint32_t *pos0, uint8_t *ref_base, uint32_t *counts,
+                                          uint64_t *n_sites, uint64_t totals[4]) {
+    if (!e) return fail(PSSBAM_EINVAL, "null engine");
+    if (!e->has_sites) return fail(PSSBAM_EINVAL, "no sites are set (pssbam_engine_set_sites)");
+    if (const int rc = pssbam_engine_sync(e)) return rc;
+    const size_t n = e->d_site_idx ? e->site_idx.size() : 0;
+    if (n_sites) *n_sites = n;
+    const bool arrays = ref || pos0 || ref_base || counts;
+    if (arrays && cap < n) return fail(PSSBAM_EINVAL, "room for %llu sites, %llu are resolved", (unsigned long long)cap, (unsigned long long)n);
+    if (totals) {
+        totals[0] = e->sites_given;
+        totals[1] = n;
+        totals[2] = totals[3] = 0;
+    }
+    if (!n || (!arrays && !totals)) return PSSBAM_OK;
+    for (size_t j = 0; j < n; j++) {
+        if (ref) ref[j] = e->site_ref[j];
+        if (pos0) pos0[j] = e->site_pos[j];
+    }
+    if (ref_base) {
+        const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t)e->n_cu * 8));
+        hipLaunchKernelGGL(allele_ref_base, dim3(grid), dim3(256), 0, e->stream, (const uint8_t *)e->d_genome, e->genome_bytes, (const uint64_t *)e->d_site_idx,
+                           (uint32_t)n, e->d_site_base);
+        HIP_TRY(hipGetLastError());
+        std::vector<uint8_t> h(n);
+        HIP_TRY(hipMemcpyAsync(h.data(), e->d_site_base, n, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        for (size_t j = 0; j < n; j++) ref_base[j] = h[e->site_slot[j]];
+    }
+    if (counts || totals) {   // the device's rows are in the genome's order, the caller's by refID then position
+        std::vector<uint32_t> h(n * ALLELE_WORDS);
+        HIP_TRY(hipMemcpyAsync(h.data(), e->d_site_counts, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        for (size_t j = 0; j < n; j++) {
+            const uint32_t *row = &h[(size_t)e->site_slot[j] * ALLELE_WORDS];
+            uint64_t sum = 0;
+            for (uint32_t w = 0; w < ALLELE_WORDS; w++) sum += row[w];
+            if (counts) memcpy(counts + j * ALLELE_WORDS, row, ALLELE_WORDS * sizeof(uint32_t));
+            if (totals) {
+                totals[2] += sum != 0;
+                totals[3] += sum;
+            }
+        }
     }
     return PSSBAM_OK;
 }

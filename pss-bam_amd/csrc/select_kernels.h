@@ -27,18 +27,23 @@ static constexpr uint32_t SELECT_GATHER_THREADS = 256, SELECT_GATHER_CHUNKS = 8;
 __device__ __forceinline__ uint32_t select_n_recs(const TallyParams &P) { return P.n_recs_dev ? min(*P.n_recs_dev, P.n_recs) : P.n_recs; }
 
 // Was record r (below the block's count) added to the forward or the reverse main table?  The one statement of "kept" on the
-// device: select_mark and coverage_add (coverage_kernels.h) both ask it.  pl = the record's plan, rec_len = its bytes in the block.
-__device__ __forceinline__ bool select_keep(const TallyParams &P, uint32_t r, GappedPlan &pl, uint32_t &rec_len) {
+// device: select_mark, coverage_add (coverage_kernels.h) and allele_add (allele_kernels.h) all ask it.  pl = the record's plan,
+// rec_len = its bytes in the block, h = its decoded header.
+__device__ __forceinline__ bool select_keep(const TallyParams &P, uint32_t r, GappedPlan &pl, uint32_t &rec_len, RecHdr &h) {
     const uint32_t o0 = P.offs[r], o1 = P.offs[r + 1];
     rec_len = o1 - o0;
     GlobalBytes src{P.recs + o0};
-    const RecHdr h = decode_hdr(src, o1 - o0);
+    h = decode_hdr(src, o1 - o0);
     if (P.gapped) pl = make_plan<true, false, true, true>(P, src, h);
     else static_cast<Plan &>(pl) = make_plan<true, true>(P, src, h);
     bool keep = (P.tally_mask & 1u) != 0 && (pl.pss_fwd || pl.pss_rev);
     if (keep && mism_on(P)) keep = !mism_beyond(P, count_mismatches(src, h, P.genome + pl.gbase, pl.s, pl.L, P.mism_tv != 0u));
     if (keep && P.score_w) keep = !score_below(P, read_score(P, src, h, P.genome + pl.gbase, pl.s, pl.L, pl.rev));
     return keep;
+}
+__device__ __forceinline__ bool select_keep(const TallyParams &P, uint32_t r, GappedPlan &pl, uint32_t &rec_len) {
+    RecHdr h;
+    return select_keep(P, r, pl, rec_len, h);
 }
 
 // len has P.n_recs + 1 entries (the host's bound of the count); the ones from the device's count on are zero

@@ -237,7 +237,8 @@ static int apply_options(pssbam_engine *e)
            (o->out_bam && (o->out_deflate ? pssbam_engine_set_block_sink(e, out_block_sink, NULL) : pssbam_engine_set_record_sink(e, out_sink, NULL))) ||
            (o->out_bam && o->out_mask_mode != PSSBAM_END_MASK_OFF && pssbam_engine_set_end_mask(e, o->out_mask_mode, o->out_mask_n5, o->out_mask_n3)) ||
            (o->duplicates && pssbam_engine_set_duplicates(e, 1, 0)) ||
-           ((o->coverage || o->coverage_bedgraph) && pssbam_engine_set_coverage(e, 1, coverage_positions_hint));
+           ((o->coverage || o->coverage_bedgraph) && pssbam_engine_set_coverage(e, 1, coverage_positions_hint)) ||
+           (o->sites && pssbam_engine_set_sites(e, o->sites->n_names, (const char *const *)o->sites->names, o->sites->n, o->sites->name_of, o->sites->pos0, o->site_trim));
 }
 
 static void *engine_make_main(void *arg)
@@ -526,6 +527,12 @@ void run_result_free(run_result *res)
     free(res->cov_run_start);
     free(res->cov_run_end);
     free(res->cov_run_depth);
+    for (int i = 0; res->allele_names && i < res->allele_n_names; i++) free(res->allele_names[i]);
+    free(res->allele_names);
+    free(res->allele_ref);
+    free(res->allele_pos);
+    free(res->allele_base);
+    free(res->allele_counts);
     free(res->plane_fwd);
     free(res->plane_rev);
     free(res->plane_k5);
@@ -964,6 +971,29 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             }
         }
         res->has_coverage = 1;
+    }
+    if (frontend_opts.sites) { /* -a: the one engine's site counters */
+        const int32_t n_ref = rd ? bam_reader_header(rd)->n_ref : sam_reader_n_ref(sd);
+        const char *const *names = rd ? (const char *const *)bam_reader_header(rd)->ref_name : sam_reader_ref_names(sd);
+        if (pssbam_engine_finish_sites(eng[0], 0, NULL, NULL, NULL, NULL, &res->allele_n, NULL)) {
+            fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+            goto done;
+        }
+        const size_t room = (size_t)res->allele_n + 1;
+        res->allele_n_names = n_ref;
+        res->allele_names = (char **)calloc((size_t)n_ref + 1, sizeof *res->allele_names);
+        res->allele_ref = (int32_t *)malloc(room * sizeof(int32_t));
+        res->allele_pos = (uint32_t *)malloc(room * sizeof(uint32_t));
+        res->allele_base = (uint8_t *)malloc(room);
+        res->allele_counts = (uint32_t *)malloc(room * 10 * sizeof(uint32_t));
+        if (!res->allele_names || !res->allele_ref || !res->allele_pos || !res->allele_base || !res->allele_counts) { fprintf(stderr, "Error: out of memory\n"); goto done; }
+        for (int32_t i = 0; i < n_ref; i++) res->allele_names[i] = strdup(names[i]);
+        if (pssbam_engine_finish_sites(eng[0], res->allele_n, res->allele_ref, res->allele_pos, res->allele_base, res->allele_counts, &res->allele_n,
+                                       res->allele_totals)) {
+            fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+            goto done;
+        }
+        res->has_alleles = 1;
     }
     if (frontend_opts.length_hist > 0 && (cfg->tally_mask & PSSBAM_TALLY_PSS)) { /* -H: summed with the rest of the block */
         res->hist_max = frontend_opts.length_hist;

@@ -7,6 +7,7 @@
 
 #include "fasta-genome-io.h"
 #include "pssbam_hip.h"
+#include "alleles.h"
 #include "coverage.h"
 #include "duplicates.h"
 #include "regions.h"
@@ -69,6 +70,15 @@ typedef struct run_result {
     uint64_t *cov_lengths, *cov_per_contig, cov_hist[PSS_COV_HIST_MAX + 2], cov_n_runs;
     int32_t *cov_run_ref;
     uint32_t *cov_run_start, *cov_run_end, *cov_run_depth;
+    /* -a (frontend_opts.sites; has_alleles: filled): the allele_n_names references of the input, in header order, and what
+     * pssbam_engine_finish_sites gave: the allele_n resolved sites' reference index, 0-based position, reference letter and ten
+     * counters each, and the four totals */
+    int has_alleles, allele_n_names;
+    char **allele_names;
+    uint64_t allele_n, allele_totals[4];
+    int32_t *allele_ref;
+    uint32_t *allele_pos, *allele_counts;
+    uint8_t *allele_base;
 } run_result;
 
 /* -y / -Y: the weight table [4][n_dist][n_qual], the filter (use_filter: only reads with a score of at least min_score are
@@ -157,6 +167,10 @@ typedef struct frontend_options {
      * LN values as its hint) and run_tally() returns the per-contig figures and the histogram, and for -b the runs.  One GPU. */
     int coverage;
     const char *coverage_bedgraph;
+    /* pss-bam -a / -t: the sites of the sites file (alleles.h; NULL: none) and the trim; the run's one engine counts the bases the
+     * reads it adds to a table show there (pssbam_engine_set_sites) and run_tally() returns the counts.  One GPU. */
+    const pss_sites *sites;
+    uint32_t site_trim;
 } frontend_options;
 extern frontend_options frontend_opts;   /* everything off */
 

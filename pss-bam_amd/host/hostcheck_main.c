@@ -8,7 +8,9 @@
  * bam_writer_append_blocks in uneven pieces -- the path of pss-bam -O ... -Z without a GPU (-x trunc / -x chain damage the last
  * piece: the call must fail and leave no file); with -w and -K <all|ds|ss>,<n5>[,<n3>] every record passes through the end mask
  * of pss-bam -K on its way to the writer -- the per-record function the device kernel runs (csrc/end_mask_kernels.h), compiled
- * for the host.  It exists for the sanitizer builds (`make sanitize`: ThreadSanitizer and
+ * for the host; with -s <sites.txt> the sites-file reader of pss-bam -a (alleles.h) runs over the file and, with -S <prefix>, its
+ * report writer over made-up counts for the sites read (a refused file is exit 1 with the reader's message).  It exists for the
+ * sanitizer builds (`make sanitize`: ThreadSanitizer and
  * AddressSanitizer + UBSan; tests/test_sanitizers.py) -- the digests of the instrumented
  * binaries must equal the plain build's, and the sanitizers must stay silent.
  */
@@ -17,6 +19,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "alleles.h"
 #include "bam_reader.h"
 #include "bam_writer.h"
 #include "end_mask.h"
@@ -110,7 +113,7 @@ static int reblock_add(struct reblock *r, bam_writer *wr, const uint8_t *p, size
 
 int main(int argc, char **argv)
 {
-    const char *fa = NULL, *aln = NULL, *out = NULL;
+    const char *fa = NULL, *aln = NULL, *out = NULL, *sites_fn = NULL, *sites_out = NULL;
     int level = 1, wthreads = 0, blocks = 0;
     const char *damage = NULL, *mask_arg = NULL;
     int mask_mode = PSSBAM_EM_OFF;
@@ -128,15 +131,55 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "-b")) blocks = 1;
         else if (!strcmp(argv[i], "-x") && i + 1 < argc) damage = argv[++i];
         else if (!strcmp(argv[i], "-K") && i + 1 < argc) mask_arg = argv[++i];
+        else if (!strcmp(argv[i], "-s") && i + 1 < argc) sites_fn = argv[++i];
+        else if (!strcmp(argv[i], "-S") && i + 1 < argc) sites_out = argv[++i];
     }
     if (mask_arg) {
         char err[200];
         if (pss_parse_end_mask(mask_arg, &mask_mode, &mask_n5, &mask_n3, err, sizeof err)) { fprintf(stderr, "hostcheck: %s\n", err); return 1; }
         if (!out) { fprintf(stderr, "hostcheck: -K masks what -w writes\n"); return 1; }
     }
-    if (!fa && !aln) {
-        fprintf(stderr, "usage: hostcheck [-f genome.fa[.gz]] [-a file.bam|file.sam[.gz] [-w out.bam [-z level] [-t threads] [-b [-x trunc|chain]] [-K mode,n5[,n3]]]]\n");
+    if (!fa && !aln && !sites_fn) {
+        fprintf(stderr, "usage: hostcheck [-f genome.fa[.gz]] [-a file.bam|file.sam[.gz] [-w out.bam [-z level] [-t threads] [-b [-x trunc|chain]] [-K mode,n5[,n3]]]] [-s sites.txt [-S prefix]]\n");
         return 2;
+    }
+    if (sites_fn) {   /* pss-bam -a: the reader, and the writer over counts made up from the site's number */
+        char err[600];
+        pss_sites st;
+        if (pss_read_sites(sites_fn, &st, err, sizeof err)) { fprintf(stderr, "hostcheck: %s\n", err); return 1; }
+        uint64_t h = 1469598103934665603ull;
+        for (int32_t k = 0; k < st.n_names; k++) h = fnv(h, st.names[k], strlen(st.names[k]) + 1);
+        h = fnv(h, st.name_of, (size_t)st.n * sizeof *st.name_of);
+        h = fnv(h, st.pos0, (size_t)st.n * sizeof *st.pos0);
+        printf("sites names=%d sites=%lld digest=%016llx\n", (int)st.n_names, (long long)st.n, (unsigned long long)h);
+        if (sites_out) {   /* arrays of exactly the sites' size: a stray read is one past a heap block */
+            const size_t n = (size_t)st.n;
+            uint8_t *base = (uint8_t *)malloc(n);
+            uint32_t *counts = (uint32_t *)malloc(n * 10 * sizeof *counts);
+            if (!base || !counts) { fprintf(stderr, "hostcheck: out of memory\n"); return 1; }
+            uint64_t totals[4] = {n, n, 0, 0};
+            for (size_t i = 0; i < n; i++) {
+                base[i] = (uint8_t)"ACGTN"[i % 5];
+                uint64_t sum = 0;
+                for (size_t w = 0; w < 10; w++) sum += counts[10 * i + w] = (uint32_t)((i * 7 + w * 3) % 5 == 0 ? i + w : 0);
+                totals[2] += sum != 0;
+                totals[3] += sum;
+            }
+            const int32_t first = st.name_of[0];
+            st.name_of[0] = st.n_names;   /* a reference the list lacks: refused, and no file is left */
+            if (!pss_write_alleles("genome.fa", "reads.bam", sites_fn, 2, sites_out, st.n_names, (const char *const *)st.names, (uint64_t)n, st.name_of, st.pos0, base,
+                                   counts, totals)) {
+                fprintf(stderr, "hostcheck: the writer took a site on a reference it does not have\n");
+                return 1;
+            }
+            st.name_of[0] = first;
+            if (pss_write_alleles("genome.fa", "reads.bam", sites_fn, 2, sites_out, st.n_names, (const char *const *)st.names, (uint64_t)n, st.name_of, st.pos0, base,
+                                  counts, totals))
+                return 1;
+            free(base);
+            free(counts);
+        }
+        pss_free_sites(&st);
     }
     if (fa) {
         Genome *g = init_genome(fa);

@@ -104,6 +104,15 @@
  * name when it is complete and must not name the -B or the -O file.  Either switches the engine's array on (4 bytes per genome
  * position on the device); -b alone writes no summary.  Not with -I (the span of a clipped read needs a definition of its own); SAM
  * text is fine; one GPU (PSSBAM_NGPU unset or 1): the arrays of several engines are not summed.
+ * Added: -a <sites> [-t <n>] counts, in the same pass, the bases the tallied reads show at listed sites, split by strand: the pileup at a
+ * SNP panel.  The sites file holds one site per line, contig and 1-based position in its first two blank- or tab-separated columns
+ * (further columns are ignored: a `samtools mpileup -l` positions file and an ANGSD -sites file both read; '#' lines and empty lines are
+ * skipped).  A read added to a table -- exactly the reads -O writes and -c counts -- shows at every listed site between its first and
+ * last n bases (-t, default 0) its SEQ base there: A, C, G, T or other (N, IUPAC codes, under -Q a base below the minimum quality).
+ * Writes <prefix>.pss.alleles.txt (alleles.h): per site of a contig that both the input's header and the FASTA hold -- depth 0
+ * included, header order, then position -- the reference base and fA fC fG fT fO rA rC rG rT rO.  -K changes nothing.  Not with -I
+ * (the offsets of a clipped or gapped read need a CIGAR walk); SAM text is fine; one GPU (PSSBAM_NGPU unset or 1).  No random or
+ * majority calling and no genotype likelihoods: the counts are what such callers start from.
  * Differences on purpose: missing -F/-B/-o are detected reliably (the reference tests
  * uninitialised pointers), an unreadable FASTA/BAM is a diagnosed exit(1) instead of a
  * crash, and PSSBAM_STATS=1 prints the per-status record tallies to stderr.
@@ -115,6 +124,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include "alleles.h"
 #include "base_quality.h"
 #include "composition.h"
 #include "contig_sets.h"
@@ -156,9 +166,9 @@ int main(int argc, char *argv[])
     const char *out_bam = NULL, *out_level_arg = NULL;
     const char *out_mask_arg = NULL;
     int out_deflate = 0, duplicates = 0, coverage = 0;
-    const char *bedgraph = NULL;
+    const char *bedgraph = NULL, *sites_fn = NULL, *trim_arg = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:P:y:YO:z:ZK:dcb:")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:P:y:YO:z:ZK:dcb:a:t:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -195,6 +205,8 @@ int main(int argc, char *argv[])
         case 'd': duplicates = 1; break;
         case 'c': coverage = 1; break;
         case 'b': bedgraph = optarg; break;
+        case 'a': sites_fn = optarg; break;
+        case 't': trim_arg = optarg; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -241,7 +253,9 @@ int main(int argc, char *argv[])
               "-K <all|ds|ss>,<n5>[,<n3>] <with -O: in that BAM, mask the first n5 bases of the 5' and n3 (default: n5) of the 3' end of each read with N, quality 0: all of them, T at 5' / A at 3' (ds) or T at both (ss)>\n"
               "-d <flag duplicates before the tally: unpaired reads with the contig, position, length, strand (and, where the tables are split by read group, read group) of an earlier read; also write the duplication histogram (one GPU; not with -I)>\n"
               "-c <also write the depth of coverage of the tallied reads: per contig covered bases, breadth, mean and maximum depth, and the depth histogram (one GPU; not with -I)>\n"
-              "-b <out.bedgraph> <also write the intervals the tallied reads cover, with their depth, as a bedGraph (one GPU; not with -I)>\n",
+              "-b <out.bedgraph> <also write the intervals the tallied reads cover, with their depth, as a bedGraph (one GPU; not with -I)>\n"
+              "-a <sites.txt> <also write the bases the tallied reads show at the listed sites (contig and 1-based position per line), split by strand (one GPU; not with -I)>\n"
+              "-t <n> <with -a: leave the first and last n bases of each read out of the counts (0..65535, default: 0)>\n",
               stderr);
         exit(1);
     }
@@ -348,6 +362,29 @@ int main(int argc, char *argv[])
     }
     if ((coverage || bedgraph) && getenv("PSSBAM_NGPU") && atoi(getenv("PSSBAM_NGPU")) > 1) {
         fprintf(stderr, "%s keeps one depth array, on one GPU: not with PSSBAM_NGPU=%s.\n", coverage ? "-c" : "-b", getenv("PSSBAM_NGPU"));
+        exit(1);
+    }
+    /* -a / -t: no row of the table below either (no counter words; they go with every option but -I) */
+    uint32_t site_trim = 0;
+    if (trim_arg) {
+        char *end = NULL;
+        const long v = strtol(trim_arg, &end, 10);
+        if (!sites_fn) {
+            fprintf(stderr, "-t trims the reads of the allele counts: it needs -a <sites>.\n");
+            exit(1);
+        }
+        if (!*trim_arg || *end || v < 0 || v > PSS_SITE_MAX_TRIM) {
+            fprintf(stderr, "-t takes a number of bases in 0..%d, not %s.\n", PSS_SITE_MAX_TRIM, trim_arg);
+            exit(1);
+        }
+        site_trim = (uint32_t)v;
+    }
+    if (sites_fn && gapped) {
+        fprintf(stderr, "-a (allele counts at sites) does not go with %s: the offsets of a clipped or gapped read need a CIGAR walk.\n", L_I);
+        exit(1);
+    }
+    if (sites_fn && getenv("PSSBAM_NGPU") && atoi(getenv("PSSBAM_NGPU")) > 1) {
+        fprintf(stderr, "-a keeps one set of site counters, on one GPU: not with PSSBAM_NGPU=%s.\n", getenv("PSSBAM_NGPU"));
         exit(1);
     }
     if (bedgraph) {
@@ -511,6 +548,15 @@ int main(int argc, char *argv[])
             exit(1);
         }
     }
+    pss_sites sites;
+    memset(&sites, 0, sizeof sites);
+    if (sites_fn) {
+        char err[600];
+        if (pss_read_sites(sites_fn, &sites, err, sizeof err)) {
+            fprintf(stderr, "%s\n", err);
+            exit(1);
+        }
+    }
     frontend_contig_map sets;
     memset(&sets, 0, sizeof sets);
     if (ctg_map) {
@@ -569,6 +615,7 @@ int main(int argc, char *argv[])
     if (duplicates) fprintf(stderr, " -d");
     if (coverage) fprintf(stderr, " -c");
     if (bedgraph) fprintf(stderr, " -b %s", bedgraph);
+    if (sites_fn) fprintf(stderr, " -a %s -t %u", sites_fn, site_trim);
     fputc('\n', stderr);
 
     pssbam_config cfg;
@@ -615,6 +662,8 @@ int main(int argc, char *argv[])
     frontend_opts.duplicates = duplicates;
     frontend_opts.coverage = coverage;
     frontend_opts.coverage_bedgraph = bedgraph;
+    frontend_opts.sites = sites_fn ? &sites : NULL;
+    frontend_opts.site_trim = site_trim;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
     /* HIP start-up, engines and the compressed BAM feed (PCIe, inflate, CRC, record index) overlap the FASTA
      * load; only the tally launches wait for the genome (frontend.c) */
@@ -652,6 +701,10 @@ int main(int argc, char *argv[])
         pss_write_coverage_bedgraph(bedgraph, res.cov_n, (const char *const *)res.cov_names, res.cov_n_runs, res.cov_run_ref, res.cov_run_start, res.cov_run_end,
                                     res.cov_run_depth))
         exit(1);   /* -b */
+    if (res.has_alleles &&
+        pss_write_alleles(fasta_fn, bam_fn, sites_fn, site_trim, out_prefix, res.allele_n_names, (const char *const *)res.allele_names, res.allele_n, res.allele_ref,
+                          res.allele_pos, res.allele_base, res.allele_counts, res.allele_totals))
+        exit(1);   /* -a */
     if (res.site_fwd) {   /* -X: IN as the engine returns it; OUT = T - IN on the position rows, the context rows as T */
         const size_t cells = (size_t)(region_len + 2) * 16;
         unsigned long *out_fwd = (unsigned long *)malloc(cells * sizeof *out_fwd), *out_rev = (unsigned long *)malloc(cells * sizeof *out_rev);
