@@ -1224,41 +1224,69 @@ static int with_planes(PlaneSel sel, F f) {
 
 static int no_kernel() { return fail(PSSBAM_EINVAL, "no tally kernel is built for this combination of options"); }
 
-// -y / -Y: the one row pass of tally_tiled_score (pss-bam -r <= 30: every row in pass 0; the substitution tally alone, one plane), with
-// or without -Q and -T: four instantiations, and the plain reduce_partials behind them
-static int launch_tiled_score(pssbam_engine *e, TallyParams &P, bool maskq, bool regions, uint32_t lds, uint32_t n_tiles) {
-    return with_flags([&](auto MASKQ, auto REGIONS) -> int {
-        return launch_with_reduce(e, tally_tiled_score<MASKQ(), REGIONS()>, reduce_partials<false>, SCRATCH_WORDS, lds, n_tiles, P, std::tuple<>(), 0u);
-    }, maskq, regions);
+// f(std::integral_constant<TallyArm, arm>): and for the arm of a tally_tiled launch
+template <class F>
+static int with_arm(TallyArm arm, F f) {
+    return arm == ARM_HIST       ? f(std::integral_constant<TallyArm, ARM_HIST>{})
+           : arm == ARM_SITE     ? f(std::integral_constant<TallyArm, ARM_SITE>{})
+           : arm == ARM_END      ? f(std::integral_constant<TallyArm, ARM_END>{})
+           : arm == ARM_GAPPED   ? f(std::integral_constant<TallyArm, ARM_GAPPED>{})
+           : arm == ARM_MISM     ? f(std::integral_constant<TallyArm, ARM_MISM>{})
+           : arm == ARM_INTERIOR ? f(std::integral_constant<TallyArm, ARM_INTERIOR>{})
+           : arm == ARM_COMP     ? f(std::integral_constant<TallyArm, ARM_COMP>{})
+           : arm == ARM_SCORE    ? f(std::integral_constant<TallyArm, ARM_SCORE>{})
+                                 : f(std::integral_constant<TallyArm, ARM_NONE>{});
+}
+
+static bool mismatches_on(const pssbam_engine *e) { return e->mism_hist > 0 || e->mism_max >= 0; }   // -n / -N
+static bool interior_on(const pssbam_engine *e) { return e->interior_margin >= 0; }   // -W
+static bool composition_on(const pssbam_engine *e) { return e->composition > 0; }   // -P
+static bool read_score_on(const pssbam_engine *e) { return e->d_score_w != nullptr; }   // -y / -Y
+
+// The exclusive modes: at most one is on in an engine.  Their extra counter words all start at off_groups, and the ones that
+// take a read's fate from the whole read do so in the one 32-row pass.  `arm` is the arm of tally_tiled that computes the mode
+// (the plane modes have kernels of their own).  A new mode is one row here.
+enum Mode { MODE_RG, MODE_LEN, MODE_REF, MODE_HASH, MODE_EACH, MODE_HIST, MODE_SITE, MODE_END, MODE_GAPPED, MODE_MISM, MODE_INTERIOR,
+            MODE_COMPOSITION, MODE_SCORE };
+static const struct { const char *name; bool (*on)(const pssbam_engine *); TallyArm arm; } MODES[] = {
+    {"read groups", [](const pssbam_engine *e) { return e->planes == PLANES_RG; }, ARM_NONE},
+    {"length bins", [](const pssbam_engine *e) { return e->planes == PLANES_LEN; }, ARM_NONE},
+    {"contig sets", [](const pssbam_engine *e) { return e->planes == PLANES_REF; }, ARM_NONE},
+    {"replicates", [](const pssbam_engine *e) { return e->planes == PLANES_HASH; }, ARM_NONE},
+    {"per-contig tables", [](const pssbam_engine *e) { return e->per_contig; }, ARM_NONE},
+    {"the length histogram", [](const pssbam_engine *e) { return e->hist_max > 0; }, ARM_HIST},
+    {"site context", [](const pssbam_engine *e) { return e->site_mode != PSSBAM_SITE_NONE; }, ARM_SITE},
+    {"the end condition", [](const pssbam_engine *e) { return e->end_depth > 0; }, ARM_END},
+    {"gapped reads", [](const pssbam_engine *e) { return e->gapped; }, ARM_GAPPED},
+    {"the mismatch count", mismatches_on, ARM_MISM},
+    {"the interior table", interior_on, ARM_INTERIOR},
+    {"the composition table", composition_on, ARM_COMP},
+    {"the read score", read_score_on, ARM_SCORE},
+};
+
+// The arm of the engine's tally_tiled launches: that of the mode that is on
+static TallyArm tally_arm(const pssbam_engine *e) {
+    for (const auto &m : MODES)
+        if (m.on(e)) return m.arm;
+    return ARM_NONE;
 }
 
 // One row pass of tally_tiled and its reduce_partials: the instantiation for the launch's tallies, the pass (LATER: rows
-// 32.. of a large -r) and its -Q, -T, -H, -X, -E and -I state.  `exists` is the list of instantiations: the k-mer tally (alone or
-// beside the substitution tables) and -H belong to pass 0, -Q -H -X to the substitution tables, -X excludes the other two;
-// -E is the substitution tally of pass 0 alone, with or without -Q and -T; -I is the substitution tally alone in every pass, with or
-// without -Q and -T (eight instantiations); -n / -N is the substitution tally of pass 0 alone, with or without -Q and -T (four), and
-// so is -W (four more; never together with -n / -N), and so is -P (four more; never together with either).  -y / -Y has a kernel of
-// its own, tally_tiled_score (launch_tiled_score).
-// (SITE, END: the larger scratch slot of the -X / -E instantiations and the reduce that walks it)
+// 32.. of a large -r), its -Q and -T state and its arm.  Which instantiations there are says tally_tiled_exists
+// (tally_kernels.h).  (ARM_SITE, ARM_END: the larger scratch slot of the -X / -E instantiations and the reduce that walks it)
 static int launch_tiled(pssbam_engine *e, TallyParams &P, bool do_pss, bool do_kmer, bool kmer_lds, bool later, bool maskq, bool regions,
-                        bool hist, bool site, bool endc, bool gapped, bool mism, bool interior, bool comp, uint32_t lds, uint32_t n_tiles) {
-    return with_flags([&](auto DO_PSS, auto DO_KMER, auto LDS_KMER, auto LATER, auto MASKQ, auto REGIONS, auto HIST, auto SITE, auto END, auto GAPPED, auto MISM,
-                          auto INTERIOR, auto COMP) -> int {
-        constexpr bool exists = (DO_KMER() || !LDS_KMER()) &&
-                                (LATER() ? DO_PSS() && !DO_KMER() && !HIST()
-                                         : (DO_PSS() || DO_KMER()) && (DO_PSS() || !(MASKQ() || HIST() || SITE())) && !(SITE() && (DO_KMER() || HIST()))) &&
-                                (!END() || (DO_PSS() && !DO_KMER() && !LATER() && !HIST() && !SITE())) &&
-                                (!GAPPED() || (DO_PSS() && !DO_KMER() && !LDS_KMER() && !HIST() && !SITE() && !END())) &&
-                                (!MISM() || (DO_PSS() && !DO_KMER() && !LDS_KMER() && !LATER() && !HIST() && !SITE() && !END() && !GAPPED())) &&
-                                (!INTERIOR() || (DO_PSS() && !DO_KMER() && !LDS_KMER() && !LATER() && !HIST() && !SITE() && !END() && !GAPPED() && !MISM())) &&
-                                (!COMP() || (DO_PSS() && !DO_KMER() && !LDS_KMER() && !LATER() && !HIST() && !SITE() && !END() && !GAPPED() && !MISM() && !INTERIOR()));
-        if constexpr (exists)
-            return launch_with_reduce(e, tally_tiled<DO_PSS(), DO_KMER(), LDS_KMER(), LATER(), MASKQ(), REGIONS(), HIST(), SITE(), END(), GAPPED(), MISM(), INTERIOR(), COMP()>,
-                                      reduce_partials<SITE(), END()>, SITE() ? SITE_SCRATCH_WORDS : END() ? END_SCRATCH_WORDS : SCRATCH_WORDS, lds, n_tiles, P,
-                                      std::tuple<>(), (uint32_t)LDS_KMER());
-        else
-            return no_kernel();
-    }, do_pss, do_kmer, kmer_lds, later, maskq, regions, hist, site, endc, gapped, mism, interior, comp);
+                        TallyArm arm, uint32_t lds, uint32_t n_tiles) {
+    return with_arm(arm, [&](auto ARM) -> int {
+        return with_flags([&](auto DO_PSS, auto DO_KMER, auto LDS_KMER, auto LATER, auto MASKQ, auto REGIONS) -> int {
+            if constexpr (tally_tiled_exists(DO_PSS(), DO_KMER(), LDS_KMER(), LATER(), MASKQ(), ARM()))
+                return launch_with_reduce(e, tally_tiled<DO_PSS(), DO_KMER(), LDS_KMER(), LATER(), MASKQ(), REGIONS(), ARM()>,
+                                          reduce_partials<ARM() == ARM_SITE, ARM() == ARM_END>,
+                                          ARM() == ARM_SITE ? SITE_SCRATCH_WORDS : ARM() == ARM_END ? END_SCRATCH_WORDS : SCRATCH_WORDS, lds, n_tiles, P,
+                                          std::tuple<>(), (uint32_t)LDS_KMER());
+            else
+                return no_kernel();
+        }, do_pss, do_kmer, kmer_lds, later, maskq, regions);
+    });
 }
 
 
@@ -1664,40 +1692,32 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
     P.min_bq = do_pss ? e->min_bq : 0u;
     const bool maskq = P.min_bq > 0;   // -Q: the MASKQ instantiations of the tiled kernels; min_bq == 0 launches what it always did
     const bool regions = e->has_regions;   // -T: the REGIONS instantiations; without regions the engine launches what it always did
-    const bool hist = do_pss && e->hist_max > 0;   // -H: the HIST instantiations; without a histogram the engine launches what it always did
-    if (hist) {
+    // -H, -X, -E, -I, -n / -N, -W, -P, -y / -Y: the instantiations with the mode's arm; an engine without a mode launches what it always did
+    const TallyArm arm = tally_arm(e);
+    if (arm == ARM_HIST) {
         P.hist_max = e->hist_max;
         P.off_hist = e->off_groups;
-    }
-    const bool site = do_pss && e->site_mode != PSSBAM_SITE_NONE;   // -X: the SITE instantiations; without it the engine launches what it always did
-    if (site) P.off_site = e->off_groups;
-    const bool endc = do_pss && e->end_depth > 0;   // -E: the END instantiations; without it the engine launches what it always did
-    if (endc) {
+    } else if (arm == ARM_SITE) {
+        P.off_site = e->off_groups;
+    } else if (arm == ARM_END) {
         P.end_depth = e->end_depth;
         P.end_cell5 = e->end_cell5;
         P.end_cell3 = e->end_cell3;
         P.off_end = e->off_groups;
-    }
-    // -n / -N: the MISM instantiations; without the setting the engine launches what it always did
-    const bool mism = do_pss && (e->mism_hist > 0 || e->mism_max >= 0);
-    if (mism) {
+    } else if (arm == ARM_GAPPED) {
+        P.gapped = 1u;
+    } else if (arm == ARM_MISM) {
         P.mism_limit = e->mism_max >= 0 ? (uint32_t)e->mism_max + 1u : 0u;
         P.mism_hist = e->mism_hist;
         P.mism_tv = e->mism_tv ? 1u : 0u;
         P.off_mism = e->mism_hist ? e->off_groups : 0u;
-    }
-    const bool interior = do_pss && e->interior_margin >= 0;   // -W: the INTERIOR instantiations; without it the engine launches what it always did
-    if (interior) {
+    } else if (arm == ARM_INTERIOR) {
         P.interior = (uint32_t)e->interior_margin + 1u;
         P.off_interior = e->off_groups;
-    }
-    const bool comp = do_pss && e->composition > 0;   // -P: the COMP instantiations; without it the engine launches what it always did
-    if (comp) {
+    } else if (arm == ARM_COMP) {
         P.composition = e->composition;
         P.off_composition = e->off_groups;
-    }
-    const bool score = do_pss && e->d_score_w != nullptr;   // -y / -Y: the SCORE instantiations; without it the engine launches what it always did
-    if (score) {
+    } else if (arm == ARM_SCORE) {
         P.score_w = e->d_score_w;
         P.score_nd = e->score_nd;
         P.score_nq = e->score_nq;
@@ -1707,8 +1727,6 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
         P.score_shift = e->score_shift;
         P.off_score = e->score_half ? e->off_groups : 0u;
     }
-    const bool gapped = do_pss && e->gapped;   // -I: the GAPPED instantiations; without it the engine launches what it always did
-    P.gapped = gapped ? 1u : 0u;
     if (regions) {
         P.region_info = e->d_region_info;
         P.region_grid = e->d_region_grid;
@@ -1866,13 +1884,9 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                     });
                 }
             }
-        } else if (score) {
-            // -y / -Y (one pass: -r <= 30; never tally_compact, which has no QUAL path): tally_tiled_score, with [sf | sr] behind the
-            // staging buffer, at most 2 KiB
-            rc = launch_tiled_score(e, P, maskq, regions, lds + 4u * e->score_half * 4u, n_tiles);
-        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions && !hist && !site && !endc && !gapped && !mism && !interior && !comp) {
+        } else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions && arm == ARM_NONE) {
             // -r N <= 16 (2 context rows + 16 positions): the short-window variant, one pass (it stages prefixes only
-            // and has no QUAL path: -R and -Q go to tally_tiled; so do -T, -H, -X, -E, -I, -n / -N, -W and -P, whose arms only tally_tiled carries)
+            // and has no QUAL path: -R and -Q go to tally_tiled; so do -T and every mode with an arm, which only tally_tiled carries)
             if (!do_kmer && getenv("PSSBAM_COMPACT_DECODE_TWICE"))   // diagnostics: what the shared header decode costs
                 rc = launch_with_reduce(e, tally_compact_decode_twice, reduce_partials<false>, SCRATCH_WORDS, lds, n_tiles, P, std::tuple<>(), 0u);
             else
@@ -1884,23 +1898,28 @@ static int launch_tally(pssbam_engine *e, const uint8_t *d_recs, uint64_t nbytes
                         return no_kernel();
                 }, do_kmer, kmer_lds, e->compact_plan_once);
         } else {
-            // tally_tiled, 32 table rows per pass over the block.  Pass 0 has the status counters, the k-mer tally and -H's
-            // histogram, with the LDS part of its two arrays behind the staging buffer (at most HIST_LDS_MAX_BINS bins each:
-            // 8 KiB); rows 32.. of a large -r are further passes, substitution rows only, that count nothing of these again
+            // tally_tiled, 32 table rows per pass over the block.  Pass 0 has the status counters, the k-mer tally and what its
+            // arm keeps in LDS behind the staging buffer; rows 32.. of a large -r are further passes, substitution rows only,
+            // that count nothing of these again.  The arms but -H, -X and -I are one pass: -r <= 30.
             uint32_t lds0 = lds;
-            if (hist) {
+            switch (arm) {
+            case ARM_HIST:   // the LDS part of [hf | hr], at most HIST_LDS_MAX_BINS bins each: 8 KiB
                 P.hist_lds_bins = std::min(e->hist_max + 2u, HIST_LDS_MAX_BINS);
                 if (e->env_hist_lds_bins >= 0) P.hist_lds_bins = std::min(P.hist_lds_bins, (uint32_t)e->env_hist_lds_bins);
                 lds0 += hist_lds_bytes(P.hist_lds_bins);
+                break;
+            case ARM_END: lds0 += end_lds_bytes(e->rows); break;   // the conditional tables and reads[4]
+            case ARM_MISM: lds0 += e->mism_hist ? 2u * (e->mism_hist + 2u) * 4u : 0u; break;   // -N: [mf | mr], at most 2 KiB
+            case ARM_INTERIOR: lds0 += INTERIOR_WORDS * 4u; break;   // [table | reads]
+            case ARM_COMP: lds0 += 20u * e->composition * 4u; break;   // [c5 | c3], at most 2400 bytes
+            case ARM_SCORE: lds0 += 4u * e->score_half * 4u; break;   // -Y: [sf | sr], at most 2 KiB (never tally_compact, which has no QUAL path)
+            default: break;   // (-X: a static object of the kernel; -I: nothing)
             }
-            if (mism && e->mism_hist) lds0 += 2u * (e->mism_hist + 2u) * 4u;   // -N (one pass: -r <= 30): [mf | mr] behind the staging buffer, at most 2 KiB
-            if (interior) lds0 += INTERIOR_WORDS * 4u;   // -W (one pass: -r <= 30): [table | reads] behind the staging buffer
-            if (comp) lds0 += 20u * e->composition * 4u;   // -P (one pass: -r <= 30): [c5 | c3] behind the staging buffer, at most 2400 bytes
-            if (endc) lds0 += end_lds_bytes(e->rows);   // -E (one pass: -r <= 30): the conditional tables and reads[4] behind the staging buffer
+            const TallyArm later_arm = arm == ARM_SITE || arm == ARM_GAPPED ? arm : ARM_NONE;   // the two arms that work on every row
             for (uint32_t pass = 0; pass < n_passes && rc == PSSBAM_OK; pass++) {
                 P.row_base = pass * TILED_ROWS;
-                rc = pass == 0 ? launch_tiled(e, P, do_pss, do_kmer, kmer_lds, false, maskq, regions, hist, site, endc, gapped, mism, interior, comp, lds0, n_tiles)
-                               : launch_tiled(e, P, true, false, false, true, maskq, regions, false, site, false, gapped, false, false, false, lds, n_tiles);
+                rc = pass == 0 ? launch_tiled(e, P, do_pss, do_kmer, kmer_lds, false, maskq, regions, arm, lds0, n_tiles)
+                               : launch_tiled(e, P, true, false, false, true, maskq, regions, later_arm, lds, n_tiles);
             }
         }
         if (rc != PSSBAM_OK) return rc;
@@ -2193,31 +2212,6 @@ extern "C" int pssbam_engine_finish_kmer_groups(pssbam_engine *e, int32_t group,
     if (k3) HIP_TRY(hipMemcpy(k3, e->d_counters + at + e->n_bins, e->n_bins * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return PSSBAM_OK;
 }
-
-static bool mismatches_on(const pssbam_engine *e) { return e->mism_hist > 0 || e->mism_max >= 0; }   // -n / -N
-static bool interior_on(const pssbam_engine *e) { return e->interior_margin >= 0; }   // -W
-static bool composition_on(const pssbam_engine *e) { return e->composition > 0; }   // -P
-static bool read_score_on(const pssbam_engine *e) { return e->d_score_w != nullptr; }   // -y / -Y
-
-// The exclusive modes: at most one is on in an engine.  Their extra counter words all start at off_groups, and the ones that
-// take a read's fate from the whole read do so in the one 32-row pass.  A new mode is one row here.
-enum Mode { MODE_RG, MODE_LEN, MODE_REF, MODE_HASH, MODE_EACH, MODE_HIST, MODE_SITE, MODE_END, MODE_GAPPED, MODE_MISM, MODE_INTERIOR,
-            MODE_COMPOSITION, MODE_SCORE };
-static const struct { const char *name; bool (*on)(const pssbam_engine *); } MODES[] = {
-    {"read groups", [](const pssbam_engine *e) { return e->planes == PLANES_RG; }},
-    {"length bins", [](const pssbam_engine *e) { return e->planes == PLANES_LEN; }},
-    {"contig sets", [](const pssbam_engine *e) { return e->planes == PLANES_REF; }},
-    {"replicates", [](const pssbam_engine *e) { return e->planes == PLANES_HASH; }},
-    {"per-contig tables", [](const pssbam_engine *e) { return e->per_contig; }},
-    {"the length histogram", [](const pssbam_engine *e) { return e->hist_max > 0; }},
-    {"site context", [](const pssbam_engine *e) { return e->site_mode != PSSBAM_SITE_NONE; }},
-    {"the end condition", [](const pssbam_engine *e) { return e->end_depth > 0; }},
-    {"gapped reads", [](const pssbam_engine *e) { return e->gapped; }},
-    {"the mismatch count", mismatches_on},
-    {"the interior table", interior_on},
-    {"the composition table", composition_on},
-    {"the read score", read_score_on},
-};
 
 // What every setter that switches `mine` on asks first: no other mode is on (setting the one that is on again is no conflict)
 static int check_exclusive(const pssbam_engine *e, Mode mine) {

@@ -64,7 +64,7 @@
 //                 the staged prefix (record_decode.h: cigar_anchor), a lane's read stream starts at its end's anchor and
 //                 CODES-B blanks what lies outside the end's matched run; the reference side is the plain kernel's.
 //
-//  SCORE arm of the tiled body (-y / -Y, kernel tally_tiled_score, one pass): a sum of caller-supplied weights over the C and G sites of the
+//  SCORE arm of tally_tiled (-y / -Y, pass 0 of a one-pass launch): a sum of caller-supplied weights over the C and G sites of the
 //                 whole read, by distance from the read's ends and base quality (read_score is the definition, one lane per read;
 //                 read_score_staged the pair's two halves in CODES-A); a read below the minimum stops being a candidate, and the
 //                 histogram of the score lives in LDS behind the staging buffer.
@@ -859,17 +859,32 @@ __device__ __forceinline__ void stage_tile_dma(const uint8_t *recs, uint64_t rec
     }
 }
 
+// The arm of a tally_tiled launch: what it computes beside the tables, for one of the options that exclude each other
+// (-H, -X, -E, -I, -n / -N, -W, -P, -y / -Y; engine.hip: MODES).  At most one, so it is one template argument.
+enum TallyArm { ARM_NONE, ARM_HIST, ARM_SITE, ARM_END, ARM_GAPPED, ARM_MISM, ARM_INTERIOR, ARM_COMP, ARM_SCORE };
+
+// Which tally_tiled<DO_PSS, DO_KMER, LDS_KMER, LATER, MASKQ, REGIONS, ARM> exist (REGIONS is free): the k-mer bins are in LDS only
+// where there is a k-mer tally, base qualities mask the substitution tables only, a later pass (rows 32.. of a large -r) is
+// the substitution tally alone; the length histogram belongs to pass 0 and may sit beside the k-mer tally, site context and
+// anchored ends go with the substitution tally alone in every pass, every other arm with pass 0 of it.
+constexpr bool tally_tiled_exists(bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER, bool MASKQ, TallyArm ARM) {
+    const bool pss_alone = DO_PSS && !DO_KMER;
+    return (DO_PSS || DO_KMER) && (DO_KMER || !LDS_KMER) && (DO_PSS || !MASKQ) && (!LATER || pss_alone) &&
+           (ARM == ARM_NONE || (ARM == ARM_HIST ? DO_PSS && !LATER : ARM == ARM_SITE || ARM == ARM_GAPPED ? pss_alone : pss_alone && !LATER));
+}
+
 // A record too large for the staging window: decoded and tallied straight from global memory
 // by one lane.  Rare (a record of tens of KB); kept out of line so it costs the hot path
 // nothing.  It reads the kernel arguments through a pointer to the kernarg segment (taken in
 // the kernel): a reference to the kernel's by-value copy would force that whole struct into
 // scratch memory.
-template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool MASKQ = false, bool REGIONS = false, bool HIST = false, bool SITE = false,
-          bool END = false, bool GAPPED = false, bool MISM = false, bool INTERIOR = false, bool COMP = false, bool SCORE = false>
+template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool MASKQ = false, bool REGIONS = false, TallyArm ARM = ARM_NONE>
 __device__ __attribute__((noinline)) uint32_t tally_overflow_record(const TallyParams *kernarg, uint32_t o0,
                                                                     uint32_t o1, uint32_t *table, uint32_t *lds_kmer,
                                                                     uint32_t *hist_lds = nullptr, uint32_t *site_lds = nullptr,
                                                                     uint32_t *end_lds = nullptr) {
+    constexpr bool HIST = ARM == ARM_HIST, SITE = ARM == ARM_SITE, END = ARM == ARM_END, GAPPED = ARM == ARM_GAPPED, MISM = ARM == ARM_MISM,
+                   INTERIOR = ARM == ARM_INTERIOR, COMP = ARM == ARM_COMP, SCORE = ARM == ARM_SCORE;
     const TallyParams &P = *kernarg;
     GlobalBytes gsrc{P.recs + o0};
     const RecHdr gh = decode_hdr(gsrc, o1 - o0);
@@ -1113,6 +1128,8 @@ __device__ __forceinline__ void count_interior_staged(const uint32_t *genome4, u
 // Both lanes of a read's pair ask (same addresses: one request to the memory system).  Only the record's fixed fields
 // are read, so prefixes are staged as without it.  The instantiations without REGIONS contain none of it.
 //
+// The arms (ARM: one per instantiation at the most, and which instantiations exist says tally_tiled_exists):
+//
 // HIST (-H, P.hist_max > 0; pass 0, one plane): behind CODES-B, where pss_fwd / pss_rev are decided, the left-end lane
 // of every read that is added to a table counts its length (hist_wave_add); `hist_lds` holds the LDS part of the two
 // arrays and is added to the counter block when the workgroup is done, one 64-bit atomic per non-zero bin.  Nothing is
@@ -1151,7 +1168,7 @@ __device__ __forceinline__ void count_interior_staged(const uint32_t *genome4, u
 // (mism_wave_add) into `hist_lds`, here the 2 * (M + 2) words [mf | mr] behind the staging buffer, which leave LDS once, at
 // kernel end, with one 64-bit atomic per non-zero bin.  The instantiations without MISM contain none of it.
 //
-// INTERIOR (-W, P.interior = d + 1 non-zero; pass 0 of a one-pass launch, one plane, substitution tables only, never with MISM): in
+// INTERIOR (-W, P.interior = d + 1 non-zero; pass 0 of a one-pass launch, one plane, substitution tables only): in
 // CODES-A, where MISM compares, every lane of a candidate's pair walks one half of the read's interior [d, min(L - d, l_seq)) --
 // the halves start at a multiple of 8 bases, d & ~7 and the cut, and the positions below d are masked -- and counts it into 16
 // bins (count_interior_staged; under MASKQ with the staged QUAL bytes of the same positions).  Whether the read is added to a
@@ -1161,7 +1178,7 @@ __device__ __forceinline__ void count_interior_staged(const uint32_t *genome4, u
 // atomic per non-zero word at kernel end, and every 8192 tiles of a workgroup: a tile adds fewer than 128 * 2048 = 2^18 to a
 // word, so a u32 word cannot wrap.  The instantiations without INTERIOR contain none of it.
 //
-// COMP (-P, P.composition = w non-zero; pass 0 of a one-pass launch, one plane, substitution tables only, never with MISM or INTERIOR):
+// COMP (-P, P.composition = w non-zero; pass 0 of a one-pass launch, one plane, substitution tables only):
 // CODES-A gathers, next to the end's window, the 32 reference positions outside the read at this end (s - 32 .. s - 1 on the left,
 // s + L .. s + L + 31 on the right: inside the padding between contigs where they leave the contig) and works out how many of the w
 // outside offsets lie inside the contig; both are first used where the window's registers are, in front of the next tile's DMA.
@@ -1172,7 +1189,7 @@ __device__ __forceinline__ void count_interior_staged(const uint32_t *genome4, u
 // and every 8192 tiles of a workgroup: a tile adds at most 128 to a word, so a u32 word cannot wrap.  The instantiations
 // without COMP contain none of it.
 //
-// SCORE (-y / -Y, P.score_w non-null; pass 0 of a one-pass launch, one plane, substitution tables only, never with MISM, INTERIOR or COMP):
+// SCORE (-y / -Y, P.score_w non-null; pass 0 of a one-pass launch, one plane, substitution tables only):
 // in CODES-A, where MISM compares, every lane of a candidate's pair sums the weights of one half of [0, min(L, l_seq)), cut at a
 // multiple of 8 bases (read_score_staged: SEQ and QUAL from the staged record -- a whole record is staged, as under -Q -- the
 // reference from the 4-bit genome image, the weights from their table in global memory, which every workgroup re-reads and which
@@ -1182,8 +1199,7 @@ __device__ __forceinline__ void count_interior_staged(const uint32_t *genome4, u
 // words [sf | sr] behind the staging buffer, which leave LDS once, at kernel end, with one 64-bit atomic per non-zero word.  The
 // instantiations without SCORE contain none of it.
 template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS, PlaneSel PLANES = PLANES_NONE, bool MASKQ = false,
-          bool REGIONS = false, bool HIST = false, bool SITE = false, bool END = false, bool GAPPED = false, bool MISM = false,
-          bool INTERIOR = false, bool COMP = false, bool SCORE = false>
+          bool REGIONS = false, TallyArm ARM = ARM_NONE>
 __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const TallyParams *kernarg,
                                                  uint8_t *__restrict__ stage, uint8_t *__restrict__ sheet,
                                                  uint32_t *__restrict__ table,
@@ -1193,20 +1209,15 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
                                                  const PlaneParams *gk = nullptr, uint32_t *__restrict__ grp_lds = nullptr,
                                                  uint32_t *__restrict__ hist_lds = nullptr, uint32_t *__restrict__ site_lds = nullptr,
                                                  uint32_t *__restrict__ end_lds = nullptr, uint32_t *__restrict__ each_lds = nullptr) {
+    constexpr bool HIST = ARM == ARM_HIST, SITE = ARM == ARM_SITE, END = ARM == ARM_END, GAPPED = ARM == ARM_GAPPED, MISM = ARM == ARM_MISM,
+                   INTERIOR = ARM == ARM_INTERIOR, COMP = ARM == ARM_COMP, SCORE = ARM == ARM_SCORE;
     constexpr bool GROUPED = PLANES != PLANES_NONE;   // one table plane per read group / length bin
     constexpr bool EACH = PLANES == PLANES_EACH;      // ... per BAM reference, resident in LDS slots
     static_assert(!EACH || (DO_PSS && !DO_KMER), "a plane per reference splits the substitution tables");
-    static_assert(!END || (DO_PSS && !DO_KMER && !LATER_PASS && PLANES == PLANES_NONE && !HIST && !SITE), "the end condition belongs to pass 0 of the one-plane substitution tally without the length histogram and site context");
-    static_assert(!SITE || (DO_PSS && !DO_KMER && PLANES == PLANES_NONE && !HIST), "site context belongs to the one-plane substitution tally without the length histogram");
-    static_assert(!HIST || (DO_PSS && !LATER_PASS && PLANES == PLANES_NONE), "the length histogram belongs to pass 0 of the one-plane substitution tally");
     constexpr bool KPLANES = GROUPED && DO_KMER;      // ... of k-mer bins (tally_tiled_kmer_planes: no sheet, no table)
     static_assert(!KPLANES || !DO_PSS, "planes split either the substitution tables or the k-mer tables");
-    static_assert(!MASKQ || DO_PSS, "base qualities mask the substitution tables only");
-    static_assert(!GAPPED || (DO_PSS && !DO_KMER && PLANES == PLANES_NONE && !HIST && !SITE && !END), "anchored ends belong to the one-plane substitution tally without the length histogram, site context and the end condition");
-    static_assert(!MISM || (DO_PSS && !DO_KMER && !LATER_PASS && PLANES == PLANES_NONE && !HIST && !SITE && !END && !GAPPED), "the mismatch count belongs to pass 0 of the one-plane substitution tally without the length histogram, site context, the end condition and anchored ends");
-    static_assert(!INTERIOR || (DO_PSS && !DO_KMER && !LATER_PASS && PLANES == PLANES_NONE && !HIST && !SITE && !END && !GAPPED && !MISM), "the interior table belongs to pass 0 of the one-plane substitution tally without the length histogram, site context, the end condition, anchored ends and the mismatch count");
-    static_assert(!COMP || (DO_PSS && !DO_KMER && !LATER_PASS && PLANES == PLANES_NONE && !HIST && !SITE && !END && !GAPPED && !MISM && !INTERIOR), "the composition table belongs to pass 0 of the one-plane substitution tally without the length histogram, site context, the end condition, anchored ends, the mismatch count and the interior table");
-    static_assert(!SCORE || (DO_PSS && !DO_KMER && !LATER_PASS && PLANES == PLANES_NONE && !HIST && !SITE && !END && !GAPPED && !MISM && !INTERIOR && !COMP), "the read score belongs to pass 0 of the one-plane substitution tally without the length histogram, site context, the end condition, anchored ends, the mismatch count, the interior table and the composition table");
+    static_assert(tally_tiled_exists(DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, MASKQ, ARM), "no such tally (tally_tiled_exists)");
+    static_assert(ARM == ARM_NONE || PLANES == PLANES_NONE, "an arm belongs to the one-plane tally");
     const uint32_t T = P.reads_per_tile;   // <= TILED_MAX_T
     const uint32_t n_recs = P.n_recs_dev ? *P.n_recs_dev : P.n_recs;   // device-indexed blocks: the count lives in device memory
     const uint32_t pieces = P.prefix_pieces;  // 16-byte pieces staged per record
@@ -1554,7 +1565,7 @@ __device__ __forceinline__ void tally_tiled_body(const TallyParams &P, const Tal
         if (in_tile && !in_stage && e == 0u) {
             if constexpr (KPLANES) ev_over = tally_overflow_record_kmer_planes<PLANES, LDS_KMER, REGIONS>(kernarg, gk, o0, o1, lds_kmer);
             else if constexpr (GROUPED) ev_over = tally_overflow_record_planes<PLANES, MASKQ, REGIONS>(kernarg, gk, o0, o1, table);
-            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS, HIST, SITE, END, GAPPED, MISM, INTERIOR, COMP, SCORE>(kernarg, o0, o1, table, lds_kmer, hist_lds, site_lds, end_lds);
+            else ev_over = tally_overflow_record<DO_PSS, DO_KMER, LDS_KMER, MASKQ, REGIONS, ARM>(kernarg, o0, o1, table, lds_kmer, hist_lds, site_lds, end_lds);
             if (pass0) atomicAdd(&lds_delta[ST_SLOW_PATH], 1);
         }
         // First use of the gathered registers happens HERE, before the next tile's DMA is issued:
@@ -2575,15 +2586,17 @@ __global__ void __launch_bounds__(256) reduce_partials(const TallyParams P, uint
     if (sum) atomicAdd(dst, (unsigned long long)sum);
 }
 
-// HIST: dynamic LDS is the staging buffer and, behind it, the 2 * P.hist_lds_bins words of the length histogram
-// SITE: one more static object, the 2 KiB in-context table
-// END: behind the staging buffer the conditional tables and reads[4], end_lds_bytes(N + 2) (never together with HIST)
+// Dynamic LDS is the staging buffer and, behind it, what the arm keeps there (hist_lds; never two arms at once):
+// HIST: the 2 * P.hist_lds_bins words of the length histogram
+// SITE: nothing there; one more static object, the 2 KiB in-context table
+// END: the conditional tables and reads[4], end_lds_bytes(N + 2)
 // GAPPED: nothing more in LDS (the CIGAR walk reads the staged prefix)
-// MISM: behind the staging buffer the 2 * (P.mism_hist + 2) words of the mismatch histogram, where HIST has its bins (never together)
-// INTERIOR: in the same place the 17 words [table | reads] of the interior table (never together with either)
-// COMP: in the same place the 20 * P.composition words [c5 | c3] of the composition table (never together with any of them)
-template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS = false, bool MASKQ = false, bool REGIONS = false, bool HIST = false,
-          bool SITE = false, bool END = false, bool GAPPED = false, bool MISM = false, bool INTERIOR = false, bool COMP = false>
+// MISM: the 2 * (P.mism_hist + 2) words of the mismatch histogram
+// INTERIOR: the 17 words [table | reads] of the interior table
+// COMP: the 20 * P.composition words [c5 | c3] of the composition table
+// SCORE: the 4 * P.score_half words of the score histogram (whole records are staged, as under -Q).  The weight table stays in
+// global memory (beside the staging buffer it does not in general leave room for two workgroups per CU).
+template <bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER_PASS = false, bool MASKQ = false, bool REGIONS = false, TallyArm ARM = ARM_NONE>
 __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
@@ -2594,38 +2607,19 @@ __global__ void __launch_bounds__(TILED_THREADS) tally_tiled(const TallyParams P
     __shared__ uint4 refs_lds[REF_LDS_ENTRIES + 1];
     // the kernel's single argument, as it lies in the kernarg segment (for the out-of-line path)
     const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
-    uint32_t *hist_lds = (HIST || MISM || INTERIOR || COMP) ? (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces)) : nullptr;
-    if constexpr (SITE) {
+    constexpr bool BEHIND = ARM == ARM_HIST || ARM == ARM_MISM || ARM == ARM_INTERIOR || ARM == ARM_COMP || ARM == ARM_SCORE;
+    uint32_t *hist_lds = BEHIND ? (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces)) : nullptr;
+    if constexpr (ARM == ARM_SITE) {
         __shared__ uint32_t site_lds[SITE_WORDS];
-        tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, true>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
-                                                                                                      lds_delta, refs_lds, nullptr, nullptr, hist_lds, site_lds);
-    } else if constexpr (END) {
+        tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, ARM>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta,
+                                                                                                  refs_lds, nullptr, nullptr, hist_lds, site_lds);
+    } else if constexpr (ARM == ARM_END) {
         uint32_t *end_lds = (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces));
-        tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, false, true>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
-                                                                                                             lds_delta, refs_lds, nullptr, nullptr, hist_lds, nullptr, end_lds);
+        tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, ARM>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta,
+                                                                                                  refs_lds, nullptr, nullptr, hist_lds, nullptr, end_lds);
     } else
-    tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, HIST, false, false, GAPPED, MISM, INTERIOR, COMP>(P, kernarg, stage, sheet, table, toffs, lds_kmer,
-                                                                                                                  lds_delta, refs_lds, nullptr, nullptr, hist_lds);
-}
-
-// -y / -Y: tally_tiled's pass 0 of the one-plane substitution tally with the SCORE arm of the body, a kernel of its own name so that
-// tally_tiled's argument list, and with it the name of every kernel the engine launches without the setting, stays what it is.
-// Dynamic LDS: the staging buffer (whole records, as under -Q) and, behind it, the 4 * P.score_half words of the score histogram,
-// where HIST and MISM have their bins.  The weight table stays in global memory (beside the staging buffer it does not in general leave
-// room for two workgroups per CU).
-template <bool MASKQ, bool REGIONS>
-__global__ void __launch_bounds__(TILED_THREADS) tally_tiled_score(const TallyParams P) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
-    __shared__ __attribute__((aligned(16))) uint8_t sheet[TILED_MAX_T * 64u];
-    __shared__ uint32_t table[TABLE_WORDS];
-    __shared__ uint32_t toffs[2u * (TILED_MAX_T + 4u)];
-    __shared__ uint32_t lds_kmer[1];
-    __shared__ int32_t lds_delta[ST_USED];
-    __shared__ uint4 refs_lds[REF_LDS_ENTRIES + 1];
-    const TallyParams *kernarg = (const TallyParams *)__builtin_amdgcn_kernarg_segment_ptr();
-    uint32_t *hist_lds = (uint32_t *)(stage + tiled_lds_bytes(P.reads_per_tile, P.prefix_pieces));
-    tally_tiled_body<true, false, false, false, PLANES_NONE, MASKQ, REGIONS, false, false, false, false, false, false, false, true>(
-        P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta, refs_lds, nullptr, nullptr, hist_lds);
+    tally_tiled_body<DO_PSS, DO_KMER, LDS_KMER, LATER_PASS, PLANES_NONE, MASKQ, REGIONS, ARM>(P, kernarg, stage, sheet, table, toffs, lds_kmer, lds_delta,
+                                                                                              refs_lds, nullptr, nullptr, hist_lds);
 }
 
 // ---------------------------------------------------------------------------------------

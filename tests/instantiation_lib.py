@@ -2,10 +2,11 @@
 launches each, and the CPU expectation of every configuration.  Shared by test_instantiations_host.py (no GPU) and
 test_gpu_instantiations.py.
 
-launch_tally / launch_tiled (pss-bam_amd/csrc/engine.hip) turn runtime flags into template arguments; every combination
-is a kernel of its own, with its own registers and spills.  `exists` below mirrors the `constexpr bool exists` predicate
-of launch_tiled; EXISTS_SOURCE, LAUNCH_SITES, GUARDS and ROUTING are the statements of engine.hip the mirror and
-`launched` were written from, whitespace-normalised, and source_statements() reads them back from the file: when they
+launch_tally / launch_tiled (pss-bam_amd/csrc/engine.hip) turn runtime flags and the engine's arm (TallyArm: the one of
+the options -H -X -E -I -n/-N -W -P -y/-Y that is on) into template arguments; every combination is a kernel of its own,
+with its own registers and spills.  `exists` below mirrors the predicate tally_tiled_exists of tally_kernels.h;
+EXISTS_SOURCE, LAUNCH_SITES, GUARDS, ROUTING, ARMS and MODE_ARMS are the statements of the two files the mirror and
+`launched` were written from, whitespace-normalised, and source_statements() reads them back from the files: when they
 differ the instantiation table has changed, and the census (the mirror, `launched`, the counts and the configuration
 list) has to follow before the texts are updated.
 
@@ -13,7 +14,7 @@ An instantiation is (kernel name, template arguments); a Config is one engine se
 instantiations its launches go through, config_of(inst) a configuration that launches a given one.  CONFIGS is the list
 test_gpu_instantiations.py runs: 32 pss-only, 16 pss + k-mer, 4 k-mer-only, 20 plane, 12 k-mer-plane configurations and
 the one tally_compact form test_gpu_tile_loop.py does not launch.  The other five compact forms are COMPACT_ELSEWHERE,
-by test id.
+the four tally_tiled forms of the SCORE arm (-y / -Y) SCORE_ELSEWHERE, both by test id.
 
 Expectations are composed the way the arms' own feature tests build them: records -> regions_lib.reduce_recs (-T) ->
 base_quality_lib.mask_recs (-Q 20) -> the feature's expectation (the CPU oracle, or the feature lib's direct count).
@@ -49,41 +50,42 @@ from test_gpu_tile_loop import (CONTIG_SETS, END_COND, HIST_MAX, KMER_EDGES, LEN
                                 assert_every_tile_overflows, direct_hist, region_stats, sam_of, stats_of)
 
 ENGINE_HIP = Path(__file__).resolve().parent.parent / "pss-bam_amd" / "csrc" / "engine.hip"
+KERNELS_H = ENGINE_HIP.parent / "tally_kernels.h"
 
-# ---- the statements of engine.hip this census was written from (the tripwire) -------------------------------------------
+# ---- the statements of engine.hip and tally_kernels.h this census was written from (the tripwire) -----------------------
 
 EXISTS_SOURCE = (
-    "constexpr bool exists = (DO_KMER() || !LDS_KMER()) && "
-    "(LATER() ? DO_PSS() && !DO_KMER() && !HIST() "
-    ": (DO_PSS() || DO_KMER()) && (DO_PSS() || !(MASKQ() || HIST() || SITE())) && !(SITE() && (DO_KMER() || HIST()))) && "
-    "(!END() || (DO_PSS() && !DO_KMER() && !LATER() && !HIST() && !SITE())) && "
-    "(!GAPPED() || (DO_PSS() && !DO_KMER() && !LDS_KMER() && !HIST() && !SITE() && !END())) && "
-    "(!MISM() || (DO_PSS() && !DO_KMER() && !LDS_KMER() && !LATER() && !HIST() && !SITE() && !END() && !GAPPED())) && "
-    "(!INTERIOR() || (DO_PSS() && !DO_KMER() && !LDS_KMER() && !LATER() && !HIST() && !SITE() && !END() && !GAPPED() && !MISM())) && "
-    "(!COMP() || (DO_PSS() && !DO_KMER() && !LDS_KMER() && !LATER() && !HIST() && !SITE() && !END() && !GAPPED() && !MISM() && !INTERIOR()));")
+    "constexpr bool tally_tiled_exists(bool DO_PSS, bool DO_KMER, bool LDS_KMER, bool LATER, bool MASKQ, TallyArm ARM) { "
+    "const bool pss_alone = DO_PSS && !DO_KMER; "
+    "return (DO_PSS || DO_KMER) && (DO_KMER || !LDS_KMER) && (DO_PSS || !MASKQ) && (!LATER || pss_alone) && "
+    "(ARM == ARM_NONE || (ARM == ARM_HIST ? DO_PSS && !LATER : ARM == ARM_SITE || ARM == ARM_GAPPED ? pss_alone : pss_alone && !LATER)); }")
 
 # every `kernel<template arguments>` of the four kernels in engine.hip, in file order
 LAUNCH_SITES = [
-    "tally_tiled<DO_PSS(), DO_KMER(), LDS_KMER(), LATER(), MASKQ(), REGIONS(), HIST(), SITE(), END(), GAPPED(), MISM(), INTERIOR(), COMP()>",
+    "tally_tiled<DO_PSS(), DO_KMER(), LDS_KMER(), LATER(), MASKQ(), REGIONS(), ARM()>",
     "tally_tiled_planes<PLANES_EACH, LATER(), MASKQ(), REGIONS()>",
     "tally_tiled_planes<SEL(), LATER(), MASKQ(), REGIONS()>",
     "tally_tiled_kmer_planes<SEL(), LDS_KMER(), REGIONS()>",
     "tally_compact<DO_KMER(), LDS_KMER(), PLAN_ONCE()>",
 ]
 # every `if constexpr (...)` between launch_tiled and the end of launch_tally, and the selectors with_planes knows
-GUARDS = ["exists", "SEL() == PLANES_HASH", "SEL() == PLANES_HASH", "DO_KMER() || !LDS_KMER()"]
+GUARDS = ["tally_tiled_exists(DO_PSS(), DO_KMER(), LDS_KMER(), LATER(), MASKQ(), ARM())", "SEL() == PLANES_HASH", "SEL() == PLANES_HASH",
+          "DO_KMER() || !LDS_KMER()"]
 PLANE_SELECTORS = ["PLANES_RG", "PLANES_LEN", "PLANES_HASH", "PLANES_REF"]      # (PLANES_EACH has a launch site of its own)
+# the arms with_arm knows, and the arm column of MODES (five plane modes, then -H -X -E -I -n/-N -W -P -y/-Y)
+ARMS = ["ARM_HIST", "ARM_SITE", "ARM_END", "ARM_GAPPED", "ARM_MISM", "ARM_INTERIOR", "ARM_COMP", "ARM_SCORE", "ARM_NONE"]
+MODE_ARMS = ["ARM_NONE"] * 5 + ARMS[:8]
 # the runtime flags behind the template arguments, and which launch a block takes
 ROUTING = [
-    "}, do_pss, do_kmer, kmer_lds, later, maskq, regions, hist, site, endc, gapped, mism, interior, comp);",
+    "}, do_pss, do_kmer, kmer_lds, later, maskq, regions);",
     "}, pass > 0, maskq, regions);",
     "}, pass > 0, maskq, regions);",
     "}, kmer_lds, regions);",
     "}, do_kmer, kmer_lds, e->compact_plan_once);",
-    "} else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions && !hist && !site && !endc && "
-    "!gapped && !mism && !interior && !comp) {",
-    "rc = pass == 0 ? launch_tiled(e, P, do_pss, do_kmer, kmer_lds, false, maskq, regions, hist, site, endc, gapped, mism, interior, comp, lds0, n_tiles) "
-    ": launch_tiled(e, P, true, false, false, true, maskq, regions, false, site, false, gapped, false, false, false, lds, n_tiles);",
+    "} else if (do_pss && e->rows <= COMPACT_MAX_ROWS && e->use_compact && !e->has_rg && !maskq && !regions && arm == ARM_NONE) {",
+    "const TallyArm later_arm = arm == ARM_SITE || arm == ARM_GAPPED ? arm : ARM_NONE;",
+    "rc = pass == 0 ? launch_tiled(e, P, do_pss, do_kmer, kmer_lds, false, maskq, regions, arm, lds0, n_tiles) "
+    ": launch_tiled(e, P, true, false, false, true, maskq, regions, later_arm, lds, n_tiles);",
 ]
 CONSTANTS = {"TILED_ROWS": 32, "KMER_LDS_MAX_K": 4, "COMPACT_MAX_ROWS": 18}      # tally_kernels.h
 
@@ -92,69 +94,67 @@ def _norm(text: str) -> str:
     return " ".join(text.split())
 
 
-def source_statements(path: Path = ENGINE_HIP) -> dict:
-    """the same statements read from engine.hip, whitespace-normalised"""
-    text = path.read_text()
+def source_statements(engine: Path = ENGINE_HIP, kernels: Path = KERNELS_H) -> dict:
+    """the same statements read from engine.hip and tally_kernels.h, whitespace-normalised"""
+    text, ktext = engine.read_text(), kernels.read_text()
     region = text[text.index("static int launch_tiled("):text.index('extern "C" int pssbam_engine_hint_records')]
     planes_fn = text[text.index("static int with_planes("):text.index("static int no_kernel()")]
     routing = [m.group(0) for m in re.finditer(r"^\s*\}, [^\n{}]*\);$", region, re.M)]
     routing += re.findall(r"\} else if \(do_pss && e->rows <= COMPACT_MAX_ROWS[^{]*\{", region)
+    routing += re.findall(r"const TallyArm later_arm = [^;]*;", region)
     routing += re.findall(r"rc = pass == 0 \? launch_tiled\(.*?;\n", region, re.S)
-    kernels = tl_constants()
     return {
-        "exists": [_norm(m) for m in re.findall(r"constexpr bool exists = .*?;", text, re.S)],
+        "exists": [_norm(m) for m in re.findall(r"constexpr bool tally_tiled_exists\(.*?\n\}", ktext, re.S)],
         "launch_sites": [_norm(m.group(0)) for m in re.finditer(r"\b(?:tally_tiled|tally_tiled_planes|tally_tiled_kmer_planes|tally_compact)<[^<>;]*>", text)],
         "guards": [_norm(m) for m in re.findall(r"if constexpr \((.*?)\)(?= return|$)", region, re.M)],
         "plane_selectors": re.findall(r"integral_constant<PlaneSel, (PLANES_\w+)>", planes_fn),
+        "arms": re.findall(r"integral_constant<TallyArm, (ARM_\w+)>", text),
+        "mode_arms": re.findall(r'^\s*\{"[^"]*", .*, (ARM_\w+)\},$', text, re.M),
         "routing": [_norm(s) for s in routing],
-        "constants": kernels,
+        "constants": tl_constants(ktext),
     }
 
 
-def tl_constants() -> dict:
-    text = (ENGINE_HIP.parent / "tally_kernels.h").read_text()
+def tl_constants(text: str) -> dict:
     return {k: int(re.search(rf"constexpr \w+ {k} = (\d+);", text).group(1)) for k in CONSTANTS}
 
 
 def census_statements() -> dict:
-    return {"exists": [EXISTS_SOURCE], "launch_sites": LAUNCH_SITES, "guards": GUARDS, "plane_selectors": PLANE_SELECTORS,
-            "routing": [_norm(s) for s in ROUTING], "constants": CONSTANTS}
+    return {"exists": [EXISTS_SOURCE], "launch_sites": LAUNCH_SITES, "guards": GUARDS, "plane_selectors": PLANE_SELECTORS, "arms": ARMS,
+            "mode_arms": MODE_ARMS, "routing": [_norm(s) for s in ROUTING], "constants": CONSTANTS}
 
 
 # ---- the instantiations ---------------------------------------------------------------------------------------------------
 
-TILED_FLAGS = ("DO_PSS", "DO_KMER", "LDS_KMER", "LATER", "MASKQ", "REGIONS", "HIST", "SITE", "END", "GAPPED", "MISM", "INTERIOR", "COMP")
-OPTION_FLAG = {"H": "HIST", "X": "SITE", "E": "END", "I": "GAPPED", "N": "MISM", "W": "INTERIOR", "P": "COMP"}
+TILED_FLAGS = ("DO_PSS", "DO_KMER", "LDS_KMER", "LATER", "MASKQ", "REGIONS", "ARM")      # six bools and the arm, "NONE" or an OPTION_ARM value
+OPTION_ARM = {"H": "HIST", "X": "SITE", "E": "END", "I": "GAPPED", "N": "MISM", "W": "INTERIOR", "P": "COMP", "Y": "SCORE"}
 PLANES = ("RG", "LEN", "HASH", "REF", "EACH")           # -G, -S, -J, -C, -A
 KMER_PLANES = ("RG", "LEN", "REF")
-COUNTS = {"tally_tiled": 64, "tally_tiled_planes": 40, "tally_tiled_kmer_planes": 12, "tally_compact": 6}
+COUNTS = {"tally_tiled": 68, "tally_tiled_planes": 40, "tally_tiled_kmer_planes": 12, "tally_compact": 6}
 
 
-def exists(DO_PSS, DO_KMER, LDS_KMER, LATER, MASKQ, REGIONS, HIST, SITE, END, GAPPED, MISM, INTERIOR, COMP) -> bool:
-    """launch_tiled's `constexpr bool exists` (EXISTS_SOURCE), clause by clause; REGIONS is free"""
+def exists(DO_PSS, DO_KMER, LDS_KMER, LATER, MASKQ, REGIONS, ARM) -> bool:
+    """tally_tiled_exists (EXISTS_SOURCE), clause by clause; REGIONS is free"""
+    pss_alone = DO_PSS and not DO_KMER
     return bool(
-        (DO_KMER or not LDS_KMER)
-        and ((DO_PSS and not DO_KMER and not HIST) if LATER
-             else ((DO_PSS or DO_KMER) and (DO_PSS or not (MASKQ or HIST or SITE)) and not (SITE and (DO_KMER or HIST))))
-        and (not END or (DO_PSS and not DO_KMER and not LATER and not HIST and not SITE))
-        and (not GAPPED or (DO_PSS and not DO_KMER and not LDS_KMER and not HIST and not SITE and not END))
-        and (not MISM or (DO_PSS and not DO_KMER and not LDS_KMER and not LATER and not HIST and not SITE and not END and not GAPPED))
-        and (not INTERIOR or (DO_PSS and not DO_KMER and not LDS_KMER and not LATER and not HIST and not SITE and not END and not GAPPED
-                              and not MISM))
-        and (not COMP or (DO_PSS and not DO_KMER and not LDS_KMER and not LATER and not HIST and not SITE and not END and not GAPPED
-                          and not MISM and not INTERIOR)))
+        (DO_PSS or DO_KMER) and (DO_KMER or not LDS_KMER) and (DO_PSS or not MASKQ) and (not LATER or pss_alone)
+        and (ARM == "NONE" or ((DO_PSS and not LATER) if ARM == "HIST" else pss_alone if ARM in ("SITE", "GAPPED") else (pss_alone and not LATER))))
 
 
 def tiled(**on) -> tuple:
-    """the tally_tiled instantiation with the named flags on"""
-    assert set(on) <= set(TILED_FLAGS)
-    return ("tally_tiled", tuple(int(bool(on.get(f, 0))) for f in TILED_FLAGS))
+    """the tally_tiled instantiation with the named flags on; an arm is named like a flag, and two arms are refused"""
+    arms = [a for a in OPTION_ARM.values() if on.pop(a, 0)]
+    if len(arms) > 1:
+        raise ValueError(f"one arm per instantiation, not {arms}")
+    assert set(on) <= set(TILED_FLAGS[:6])
+    return ("tally_tiled", tuple(int(bool(on.get(f, 0))) for f in TILED_FLAGS[:6]) + ((arms or ["NONE"])[0],))
 
 
 def enumerate_all() -> dict:
     """{kernel: [instantiation]} of the four families"""
     return {
-        "tally_tiled": [("tally_tiled", bits) for bits in itertools.product((0, 1), repeat=len(TILED_FLAGS)) if exists(*bits)],
+        "tally_tiled": [("tally_tiled", bits + (arm,)) for bits in itertools.product((0, 1), repeat=6) for arm in ["NONE", *OPTION_ARM.values()]
+                        if exists(*bits, arm)],
         "tally_tiled_planes": [("tally_tiled_planes", (sel, later, maskq, regions))
                                for sel in PLANES for later in (0, 1) for maskq in (0, 1) for regions in (0, 1)],
         "tally_tiled_kmer_planes": [("tally_tiled_kmer_planes", (sel, lds, regions)) for sel in KMER_PLANES for lds in (0, 1) for regions in (0, 1)],
@@ -163,10 +163,10 @@ def enumerate_all() -> dict:
 
 
 def describe(inst) -> str:
-    """`tally_tiled<DO_PSS, MASKQ, SITE>` (the flags that are on), `tally_tiled_planes<LEN, LATER=1, MASKQ=0, REGIONS=1>`, ..."""
+    """`tally_tiled<DO_PSS, MASKQ, SITE>` (the flags that are on and the arm), `tally_tiled_planes<LEN, LATER=1, MASKQ=0, REGIONS=1>`, ..."""
     kernel, args = inst
     if kernel == "tally_tiled":
-        return f"tally_tiled<{', '.join(f for f, b in zip(TILED_FLAGS, args) if b)}>"
+        return f"tally_tiled<{', '.join([f for f, b in zip(TILED_FLAGS, args[:6]) if b] + [a for a in args[6:] if a != 'NONE'])}>"
     names = {"tally_tiled_planes": ("", "LATER=", "MASKQ=", "REGIONS="), "tally_tiled_kmer_planes": ("", "LDS_KMER=", "REGIONS="),
              "tally_compact": ("DO_KMER=", "LDS_KMER=", "PLAN_ONCE=")}[kernel]
     return f"{kernel}<{', '.join(f'{n}{a}' for n, a in zip(names, args))}>"
@@ -239,12 +239,12 @@ def launched(c: Config) -> set:
         if do_pss:
             return {("tally_tiled_planes", (c.option, int(p > 0), maskq, regions)) for p in range(n_passes)}
         return {("tally_tiled_kmer_planes", (c.option, kmer_lds, regions))}
-    opt = {flag: int(do_pss and c.option == o) for o, flag in OPTION_FLAG.items()}
-    if do_pss and rows <= CONSTANTS["COMPACT_MAX_ROWS"] and not maskq and not regions and not any(opt.values()):
+    arm = OPTION_ARM.get(c.option) if do_pss else None
+    if do_pss and rows <= CONSTANTS["COMPACT_MAX_ROWS"] and not maskq and not regions and arm is None:
         return {("tally_compact", (int(do_kmer), kmer_lds, int(c.plan_once)))}
-    out = {tiled(DO_PSS=do_pss, DO_KMER=do_kmer, LDS_KMER=kmer_lds, MASKQ=maskq, REGIONS=regions, **opt)}
+    out = {tiled(DO_PSS=do_pss, DO_KMER=do_kmer, LDS_KMER=kmer_lds, MASKQ=maskq, REGIONS=regions, **({arm: 1} if arm else {}))}
     if n_passes > 1:
-        out.add(tiled(DO_PSS=1, LATER=1, MASKQ=maskq, REGIONS=regions, SITE=opt["SITE"], GAPPED=opt["GAPPED"]))
+        out.add(tiled(DO_PSS=1, LATER=1, MASKQ=maskq, REGIONS=regions, **({arm: 1} if arm in ("SITE", "GAPPED") else {})))
     return out
 
 
@@ -261,7 +261,7 @@ def config_of(inst) -> Config:
         do_kmer, lds, once = args
         return Config("compact", "-", 15, (4 if lds else 9) if do_kmer else None, plan_once=bool(once))
     f = dict(zip(TILED_FLAGS, args))
-    option = next((o for o, flag in OPTION_FLAG.items() if f[flag]), "-")
+    option = next((o for o, arm in OPTION_ARM.items() if f["ARM"] == arm), "-")
     klen = (4 if f["LDS_KMER"] else 9) if f["DO_KMER"] else None
     if not f["DO_PSS"]:
         return Config("kmer", "-", None, klen, False, bool(f["REGIONS"]))
@@ -288,6 +288,16 @@ COMPACT_ELSEWHERE = {
     ("tally_compact", (0, 0, 1)): "test_gpu_tile_loop.py::test_compact_walks_several_tiles[plan_once_r15-three_wg]",
     ("tally_compact", (1, 1, 1)): "test_gpu_tile_loop.py::test_compact_walks_several_tiles[plan_once_r15_k4-three_wg]",
 }
+
+
+# the four forms of the SCORE arm (-y / -Y: without and with -Q and -T), by the test of test_gpu_read_score.py that launches each
+SCORE_ELSEWHERE = {
+    tiled(DO_PSS=1, SCORE=1): "test_gpu_read_score.py::test_several_tiles_per_workgroup[three_wg]",
+    tiled(DO_PSS=1, SCORE=1, MASKQ=1): "test_gpu_read_score.py::test_filter_with_min_base_quality[TILED]",
+    tiled(DO_PSS=1, SCORE=1, REGIONS=1): "test_gpu_read_score.py::test_filter_with_regions[TILED]",
+    tiled(DO_PSS=1, SCORE=1, MASKQ=1, REGIONS=1): "test_gpu_read_score.py::test_filter_with_min_base_quality_and_regions[TILED]",
+}
+ELSEWHERE = {**COMPACT_ELSEWHERE, **SCORE_ELSEWHERE}
 
 
 # ---- the expectations (CPU only) ------------------------------------------------------------------------------------------

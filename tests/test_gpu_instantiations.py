@@ -1,6 +1,7 @@
 """Every instantiation of the tiled tally kernels against the oracle.
 
-tally_tiled (64 instantiations), tally_tiled_planes (40), tally_tiled_kmer_planes (12) and tally_compact (6) are one
+tally_tiled (68 instantiations, the four of the SCORE arm run by test_gpu_read_score.py), tally_tiled_planes (40),
+tally_tiled_kmer_planes (12) and tally_compact (6) are one
 kernel per combination of compile-time flags, each with its own register allocation.  The feature tests run every flag;
 this module runs every combination: instantiation_lib's configuration list covers the whole census
 (test_instantiations_host.py shows that without a GPU, and that no comparison below is vacuous), and each configuration

@@ -171,7 +171,7 @@ def test_filter_with_regions(pkg, fuzz, kernel):
 
 @pytest.mark.parametrize("kernel", KERNELS)
 def test_filter_with_min_base_quality_and_regions(pkg, fuzz, kernel):
-    """the fourth instantiation of tally_tiled_score: -Q and -T together"""
+    """the fourth instantiation of tally_tiled's SCORE arm: -Q and -T together"""
     (table, q, t), = [c for c in rs.CUTS if c[1]]
     ivs = rl.fuzz_intervals(7301, fuzz.contigs, fuzz.recs)
     o = tl.PssOpts(region_len=15)

@@ -1,8 +1,9 @@
 """No GPU: the census of the tiled tally family (instantiation_lib) against the launch code, and the expectations
 test_gpu_instantiations.py compares the kernels with.
 
-The counts 64 / 40 / 12 / 6 come from a Python mirror of launch_tiled's `exists` predicate and of the with_flags /
-with_planes launch sites; the tripwire holds the statements of engine.hip the mirror was written from against the file.
+The counts 68 / 40 / 12 / 6 come from a Python mirror of the predicate tally_tiled_exists (tally_kernels.h) and of the
+with_arm / with_flags / with_planes launch sites; the tripwire holds the statements of tally_kernels.h and engine.hip the
+mirror was written from against the files.
 When it trips, the instantiation table has changed: update `exists`, `launched`, COUNTS and CONFIGS in instantiation_lib
 so that every new instantiation has a configuration (and an expectation), then the recorded statements.
 
@@ -19,7 +20,11 @@ import time
 import numpy as np
 import pytest
 
+import inspect
+import re
+
 import instantiation_lib as inl
+import test_gpu_read_score
 from test_gpu_tile_loop import COMPACT
 
 
@@ -35,47 +40,55 @@ def built(oracle, tmp_path_factory):
 
 def test_counts():
     fams = inl.enumerate_all()
-    assert {k: len(v) for k, v in fams.items()} == inl.COUNTS == {"tally_tiled": 64, "tally_tiled_planes": 40, "tally_tiled_kmer_planes": 12, "tally_compact": 6}
+    assert {k: len(v) for k, v in fams.items()} == inl.COUNTS == {"tally_tiled": 68, "tally_tiled_planes": 40, "tally_tiled_kmer_planes": 12, "tally_compact": 6}
     tiled = [dict(zip(inl.TILED_FLAGS, a)) for _, a in fams["tally_tiled"]]
-    assert sum(not f["LATER"] for f in tiled) == 52 and sum(f["LATER"] for f in tiled) == 12
-    options = lambda f: "".join(o for o, flag in inl.OPTION_FLAG.items() if f[flag]) or "-"   # noqa: E731
+    assert sum(not f["LATER"] for f in tiled) == 56 and sum(f["LATER"] for f in tiled) == 12
+    options = lambda f: "".join(o for o, arm in inl.OPTION_ARM.items() if f["ARM"] == arm) or "-"   # noqa: E731
     split = {}
     for f in tiled:
         key = ("kmer" if not f["DO_PSS"] else "pss_kmer" if f["DO_KMER"] else "pss", bool(f["LATER"]), options(f))
         split[key] = split.get(key, 0) + 1
     assert split == {**{("pss", False, o): 4 for o in "-HXEINWP"}, **{("pss", True, o): 4 for o in "-XI"},
-                     ("pss_kmer", False, "-"): 8, ("pss_kmer", False, "H"): 8, ("kmer", False, "-"): 4}
+                     ("pss_kmer", False, "-"): 8, ("pss_kmer", False, "H"): 8, ("kmer", False, "-"): 4, ("pss", False, "Y"): 4}
     assert all(len(set(v)) == len(v) for v in fams.values())
 
 
 def test_tripwire_engine_source_is_what_the_census_was_written_from():
     got, want = inl.source_statements(), inl.census_statements()
     for key in want:
-        assert got[key] == want[key], f"engine.hip's {key} changed: update instantiation_lib's census, then this text"
+        assert got[key] == want[key], f"the launch code's {key} changed: update instantiation_lib's census, then this text"
 
 
 def test_tripwire_trips_on_a_changed_table(tmp_path):
-    """a copy of engine.hip with one clause of `exists` gone, one template argument dropped, one routing flag changed"""
-    text = inl.ENGINE_HIP.read_text()
-    for key, old, new in (("exists", " && !MISM() && !INTERIOR()));", " && !MISM()));"),
-                          ("launch_sites", "tally_tiled_kmer_planes<SEL(), LDS_KMER(), REGIONS()>", "tally_tiled_kmer_planes<SEL(), LDS_KMER()>"),
-                          ("routing", "}, kmer_lds, regions);", "}, kmer_lds, false);"),
-                          ("plane_selectors", "sel == PLANES_HASH ? f(std::integral_constant<PlaneSel, PLANES_HASH>{})", "sel == PLANES_HASH ? f(std::integral_constant<PlaneSel, PLANES_REF>{})")):
-        assert text.count(old) == 1, key
-        (tmp_path / "engine.hip").write_text(text.replace(old, new))
-        got, want = inl.source_statements(tmp_path / "engine.hip"), inl.census_statements()
+    """a copy of the two files with one clause of the predicate gone, one template argument dropped, one routing flag changed, one
+    plane selector, one arm of with_arm and one arm of MODES swapped"""
+    texts = {"engine.hip": inl.ENGINE_HIP.read_text(), "tally_kernels.h": inl.KERNELS_H.read_text()}
+    for key, name, old, new in (
+            ("exists", "tally_kernels.h", " && (DO_PSS || !MASKQ) && (!LATER || pss_alone) &&", " && (!LATER || pss_alone) &&"),
+            ("launch_sites", "engine.hip", "tally_tiled_kmer_planes<SEL(), LDS_KMER(), REGIONS()>", "tally_tiled_kmer_planes<SEL(), LDS_KMER()>"),
+            ("routing", "engine.hip", "}, kmer_lds, regions);", "}, kmer_lds, false);"),
+            ("plane_selectors", "engine.hip", "sel == PLANES_HASH ? f(std::integral_constant<PlaneSel, PLANES_HASH>{})", "sel == PLANES_HASH ? f(std::integral_constant<PlaneSel, PLANES_REF>{})"),
+            ("arms", "engine.hip", "arm == ARM_COMP     ? f(std::integral_constant<TallyArm, ARM_COMP>{})", "arm == ARM_COMP     ? f(std::integral_constant<TallyArm, ARM_MISM>{})"),
+            ("mode_arms", "engine.hip", '{"the interior table", interior_on, ARM_INTERIOR},', '{"the interior table", interior_on, ARM_MISM},')):
+        assert texts[name].count(old) == 1, key
+        for n, text in texts.items():
+            (tmp_path / n).write_text(text.replace(old, new) if n == name else text)
+        got, want = inl.source_statements(tmp_path / "engine.hip", tmp_path / "tally_kernels.h"), inl.census_statements()
         assert [k for k in want if got[k] != want[k]] == [key]
 
 
 def test_exists_mirror_on_a_few_known_combinations():
     on = lambda **f: inl.exists(*inl.tiled(**f)[1])   # noqa: E731
     assert on(DO_PSS=1) and on(DO_KMER=1) and on(DO_KMER=1, LDS_KMER=1) and not on() and not on(LDS_KMER=1, DO_PSS=1)
-    assert on(DO_PSS=1, SITE=1, LATER=1) and not on(DO_PSS=1, HIST=1, LATER=1) and not on(DO_PSS=1, SITE=1, HIST=1)
+    assert on(DO_PSS=1, SITE=1, LATER=1) and not on(DO_PSS=1, HIST=1, LATER=1)
     assert not on(DO_KMER=1, MASKQ=1) and on(DO_KMER=1, REGIONS=1) and not on(DO_PSS=1, DO_KMER=1, SITE=1)
     assert on(DO_PSS=1, GAPPED=1, LATER=1, MASKQ=1, REGIONS=1) and not on(DO_PSS=1, DO_KMER=1, GAPPED=1)
     for one in ("END", "MISM", "INTERIOR", "COMP"):
         assert on(DO_PSS=1, **{one: 1}) and not on(DO_PSS=1, LATER=1, **{one: 1}) and not on(DO_PSS=1, DO_KMER=1, **{one: 1})
-    assert not on(DO_PSS=1, MISM=1, INTERIOR=1) and not on(DO_PSS=1, INTERIOR=1, COMP=1) and not on(DO_PSS=1, MISM=1, COMP=1)
+    assert on(DO_PSS=1, SCORE=1, MASKQ=1, REGIONS=1) and not on(DO_PSS=1, LATER=1, SCORE=1) and not on(DO_PSS=1, DO_KMER=1, SCORE=1)
+    for two in (dict(SITE=1, HIST=1), dict(MISM=1, INTERIOR=1), dict(INTERIOR=1, COMP=1), dict(MISM=1, COMP=1)):      # two options at once: no such instantiation can be written
+        with pytest.raises(ValueError):
+            inl.tiled(DO_PSS=1, **two)
 
 
 # ---- instantiations <-> configurations -------------------------------------------------------------------------------------
@@ -85,7 +98,7 @@ def test_every_instantiation_has_a_configuration_that_launches_it():
         for inst in fam:
             c = inl.config_of(inst)
             assert inst in inl.launched(c), (inl.describe(inst), c.name)
-            if inst not in inl.COMPACT_ELSEWHERE:
+            if inst not in inl.ELSEWHERE:
                 assert c.name in inl.BY_NAME, (inl.describe(inst), c.name)
 
 
@@ -113,9 +126,10 @@ def test_the_configuration_list_covers_every_instantiation():
     assert by_family == {"pss": 32, "pss_kmer": 16, "kmer": 4, "planes": 20, "kmer_planes": 12, "compact": 1}
     covered = set().union(*(inl.launched(c) for c in inl.CONFIGS))
     everything = {i for fam in inl.enumerate_all().values() for i in fam}
-    assert covered | set(inl.COMPACT_ELSEWHERE) == everything and not covered & set(inl.COMPACT_ELSEWHERE)
+    assert covered | set(inl.ELSEWHERE) == everything and not covered & set(inl.ELSEWHERE)
     assert covered - everything == set()
     assert {i for i in everything if i[0] == "tally_compact"} - covered == set(inl.COMPACT_ELSEWHERE)
+    assert {i for i in everything if i[0] == "tally_tiled"} - covered == set(inl.SCORE_ELSEWHERE)
 
 
 def test_the_other_compact_forms_are_launched_where_the_census_says():
@@ -127,6 +141,19 @@ def test_the_other_compact_forms_are_launched_where_the_census_says():
         r = int(next(p for p in parts if p.startswith("r"))[1:])
         k = next((int(p[1:]) for p in parts if p.startswith("k")), None)
         assert inl.launched(inl.Config("compact", "-", r, k, plan_once=arm.startswith("plan_once"))) == {inst}
+
+
+def test_the_score_forms_are_launched_where_the_census_says():
+    """the ids name tests of test_gpu_read_score, and the engine set-up of each (its check_filter call: -r, -Q, -T and the tiled
+    kernel) launches that very instantiation"""
+    assert len(inl.SCORE_ELSEWHERE) == len(set(inl.SCORE_ELSEWHERE.values())) == 4
+    for inst, test_id in inl.SCORE_ELSEWHERE.items():
+        name, param = re.fullmatch(r"test_gpu_read_score\.py::(\w+)\[(\w+)\]", test_id).groups()
+        src = inspect.getsource(getattr(test_gpu_read_score, name))
+        assert (param == "TILED" and "TILED" in test_gpu_read_score.KERNELS) or test_gpu_read_score.SHAPES[param].get("PSSBAM_GRID_WGS")
+        (r,), (call,) = re.findall(r"PssOpts\(region_len=(\d+)\)", src), re.findall(r"check_filter\(pkg, \w+, o, kernel, ([^\n]*)\)\n", src)
+        c = inl.Config("pss", "Y", int(r), None, maskq="q=q" in call, regions="ivs=ivs" in call)
+        assert inl.launched(c) == {inst}, test_id
 
 
 # ---- the expectations -------------------------------------------------------------------------------------------------------
