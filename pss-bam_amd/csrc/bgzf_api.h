@@ -489,8 +489,6 @@ static int grow(T **ptr, size_t *cap, size_t need, size_t elem = sizeof(T)) {
     return PSSBAM_OK;
 }
 
-static constexpr uint64_t FEED_SUB_MAX = (3584ull << 20);   // records per tally launch: below 4 GiB
-
 // Device buffers of the feed can be reserved ahead of the first submit (pssbam_feed_reserve, from a
 // helper thread while the caller still loads its FASTA): allocating ~13 GB takes from a millisecond
 // to a second depending on what the driver has to reclaim.  What no engine took goes back with
@@ -731,8 +729,22 @@ static int feed_flush(pssbam_engine *e) {
         s.blocks_cap = *std::min_element(c, c + 8);
     }
     const uint64_t data_end = s.out_used;   // the blocks sit contiguously in [FEED_GAP, data_end)
-    // (offsets: a block of isize bytes starts at most isize / 36 + 1 records, whatever its bytes are)
-    if ((rc = grow(&s.d_offs, &s.offs_cap, (size_t)(std::max<uint64_t>(data_end, FEED_GAP + e->feed_out_target) / 36ull + std::max<size_t>(nb, s.blocks_cap) + 2ull * s.sub_first.size() + 64ull)))) return rc;
+    // offsets per tally sub-batch: the records STARTING in its blocks, relative to a 16-byte aligned base
+    uint64_t offs_at = 0;
+    std::vector<uint64_t> sub_offs(s.sub_first.size()), sub_base(s.sub_first.size()), sub_len(s.sub_first.size());
+    for (size_t k = 0; k < s.sub_first.size(); k++) {
+        const uint32_t b0 = s.sub_first[k], b1 = k + 1 < s.sub_first.size() ? s.sub_first[k + 1] : (uint32_t)nb;
+        // (sub-batch 0 owns the carried record in the gap; a later one may be entered by the last record of its predecessor)
+        const uint64_t base = k == 0 ? 0ull : (s.blocks[b0].out_off & ~15ull);
+        const uint64_t end = std::min<uint64_t>(data_end, s.blocks[b1 - 1].out_off + s.blocks[b1 - 1].isize + FEED_GAP);
+        sub_offs[k] = offs_at;
+        sub_base[k] = base;
+        sub_len[k] = end - base;
+        offs_at += sub_len[k] / 36ull + (b1 - b0) + 2ull;
+    }
+    // (offsets: a block of isize bytes starts at most isize / 36 + 1 records, whatever its bytes are; every sub-batch's share
+    //  is sized by its span, which reaches FEED_GAP into its successor: many small sub-batches need more than the data's own)
+    if ((rc = grow(&s.d_offs, &s.offs_cap, (size_t)std::max<uint64_t>(offs_at + 64ull, std::max<uint64_t>(data_end, FEED_GAP + e->feed_out_target) / 36ull + std::max<size_t>(nb, s.blocks_cap) + 2ull * s.sub_first.size() + 64ull)))) return rc;
     if ((rc = grow(&s.d_nrecs, &s.nrecs_cap, std::max<size_t>(s.sub_first.size(), 4)))) return rc;
     if (!e->d_carry) HIP_TRY(hipMalloc(&e->d_carry, FEED_GAP));
     // every chunk of this super-batch has been issued on the copy streams: the engine's stream waits for them
@@ -820,25 +832,15 @@ static int feed_flush(pssbam_engine *e) {
                            (const uint64_t *)s.d_last, (const uint64_t *)s.d_nexta, n, data_end, (const uint64_t *)s.d_chain, s.d_counts,
                            s.d_chain + 1, e->d_feed_flags, s.d_chain + 2);
     }
-    // offsets per tally sub-batch: the records STARTING in its blocks, relative to a 16-byte aligned base
-    uint64_t offs_at = 0;
-    std::vector<uint64_t> sub_offs(s.sub_first.size()), sub_base(s.sub_first.size()), sub_len(s.sub_first.size());
     for (size_t k = 0; k < s.sub_first.size(); k++) {
         const uint32_t b0 = s.sub_first[k], b1 = k + 1 < s.sub_first.size() ? s.sub_first[k + 1] : (uint32_t)nb;
-        // (sub-batch 0 owns the carried record in the gap; a later one may be entered by the last record of its predecessor)
-        const uint64_t base = k == 0 ? 0ull : (s.blocks[b0].out_off & ~15ull);
-        const uint64_t end = std::min<uint64_t>(data_end, s.blocks[b1 - 1].out_off + s.blocks[b1 - 1].isize + FEED_GAP);
-        sub_offs[k] = offs_at;
-        sub_base[k] = base;
-        sub_len[k] = end - base;
         const uint32_t n = b1 - b0;
         const uint32_t igrid = std::min<uint32_t>((n + 255u) / 256u, (uint32_t)e->n_cu * 8u);
         hipLaunchKernelGGL(pssbam::bgzf_index_scan, dim3(1), dim3(1024), 0, e->stream, (const uint32_t *)(s.d_counts + b0), n, s.d_base + b0,
                            s.d_nrecs + k);
         hipLaunchKernelGGL(pssbam::bgzf_chain_write, dim3(igrid), dim3(256), 0, e->stream, (const uint8_t *)s.d_out, (const uint64_t *)(s.d_a + b0),
-                           (const uint32_t *)(s.d_counts + b0), (const uint32_t *)(s.d_base + b0), n, base, s.d_offs + offs_at,
+                           (const uint32_t *)(s.d_counts + b0), (const uint32_t *)(s.d_base + b0), n, sub_base[k], s.d_offs + sub_offs[k],
                            (const uint32_t *)(s.d_nrecs + k));
-        offs_at += sub_len[k] / 36ull + n + 2ull;
     }
     // the partial record at the end sets out for the next super-batch (whichever slot that will be)
     hipLaunchKernelGGL(pssbam::bgzf_chain_carry_out, dim3(1), dim3(256), 0, e->stream, (const uint8_t *)s.d_out, (const uint64_t *)(s.d_chain + 1), data_end,
@@ -892,7 +894,7 @@ static int feed_append(pssbam_engine *e, const uint8_t *comp, const pssbam_bgzf_
     if (comp_at + (byte1 - byte0) + 32 > s.comp_cap) return fail(PSSBAM_ESTATE, "compressed bytes of the super-batch exceed their buffer");
     for (uint32_t i = b0; i < b1; i++) {
         pssbam_bgzf_block b = blocks[i];
-        if (s.sub_first.empty() || s.sub_bytes + b.isize > FEED_SUB_MAX) {
+        if (s.sub_first.empty() || s.sub_bytes + b.isize > e->feed_sub_max) {
             s.sub_first.push_back((uint32_t)s.blocks.size());
             s.sub_bytes = 0;
         }
@@ -914,6 +916,8 @@ static int feed_state_init(pssbam_engine *e) {
     if (e->d_feed_flags) return PSSBAM_OK;
     e->feed_t0 = feed_now();
     if (getenv("PSSBAM_FEED_SUPER_BYTES")) e->feed_out_target = std::max<uint64_t>(1ull << 20, strtoull(getenv("PSSBAM_FEED_SUPER_BYTES"), nullptr, 10));
+    // (tests: tally sub-batches of a size a test can reach; never above the constant the u32 offsets and the reserves are sized by)
+    if (getenv("PSSBAM_FEED_SUB_BYTES")) e->feed_sub_max = std::min<uint64_t>(FEED_SUB_MAX, std::max<uint64_t>(65536, strtoull(getenv("PSSBAM_FEED_SUB_BYTES"), nullptr, 10)));
     // the inflate kernel keeps INF_WAVES_PER_CU waves x 64 lanes per CU busy, a block per lane, and blocks take about the
     // same time: a super-batch of a whole number of "rounds" of blocks wastes no partial round
     const uint64_t lanes = (uint64_t)e->n_cu * (uint64_t)pssbam::INF_WAVES_PER_CU * 64ull;

@@ -103,7 +103,8 @@ struct Slot {  // one in-flight host-submitted block
 // launches wait for the genome (pssbam_engine_feed_open) and is three deep otherwise.
 static constexpr uint64_t FEED_OUT_TARGET = 4400ull << 20, FEED_COMP_CAP = 2ull << 30, FEED_OUT_SLACK = 160ull << 20,
                           FEED_OVERSHOOT = 64ull << 20,   // a submit may run this far past the target before the super-batch is cut
-                          FEED_GAP = 16ull << 20;   // room in front of a super-batch's data for the record the previous one ended in
+                          FEED_GAP = 16ull << 20,   // room in front of a super-batch's data for the record the previous one ended in
+                          FEED_SUB_MAX = 3584ull << 20;   // record bytes per tally launch: below 4 GiB
 static constexpr int FEED_SLOTS_READY = 3, FEED_SLOTS_MAX = 40;
 
 struct FeedAcc {  // one super-batch of compressed blocks: assembled chunk by chunk, then inflated in ONE launch
@@ -383,6 +384,7 @@ struct pssbam_engine {
     uint8_t *h_handoff = nullptr;      // page-locked [8 + FEED_GAP]: the partial record ANOTHER engine's run ended with arrives here (feed_handoff)
     hipEvent_t handoff_ev = nullptr;   // recorded on this engine's stream behind the hand-off of its own tail
     uint64_t feed_out_target = FEED_OUT_TARGET, feed_comp_cap = FEED_COMP_CAP;   // per super-batch
+    uint64_t feed_sub_max = FEED_SUB_MAX;   // a new tally sub-batch where the record bytes would pass this ($PSSBAM_FEED_SUB_BYTES: tests)
     double feed_t_alloc = 0, feed_t_wait_busy = 0, feed_t_flush = 0;   // host seconds inside the feed (PSSBAM_STATS)
     double feed_t0 = 0, feed_t_first_flush = -1;                        // host clock of the first submit_bgzf; first flush, seconds after it
     uint64_t feed_slots_allocated = 0, feed_deferred_launches = 0, feed_early_flushes = 0;
