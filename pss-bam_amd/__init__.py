@@ -76,6 +76,9 @@ MAX_END_DEPTH = 8
 END_MASK_OFF, END_MASK_ALL, END_MASK_DS, END_MASK_SS = 0, 1, 2, 3
 END_MASK_MODES = {None: END_MASK_OFF, "off": END_MASK_OFF, "all": END_MASK_ALL, "ds": END_MASK_DS, "ss": END_MASK_SS}
 MAX_END_MASK = 65535
+RESCALE_OFF, RESCALE_DS, RESCALE_SS = 0, 1, 2
+RESCALE_MODES = {None: RESCALE_OFF, "off": RESCALE_OFF, "ds": RESCALE_DS, "ss": RESCALE_SS}
+MAX_RESCALE_ROWS, RESCALE_QUALS = 64, 94
 MAX_DUP_HIST = 65535
 COV_HIST_MAX = 255
 MAX_SITE_TRIM = 65535
@@ -1151,3 +1154,25 @@ class Engine:
         ms, n = C.c_double(), C.c_uint64()
         _chk(self._L.pssbam_engine_kernel_time(self._h, C.byref(ms), C.byref(n), int(reset)))
         return float(ms.value), int(n.value)
+
+
+class _Rescale(C.Structure):   # host/rescale.h pss_rescale
+    _fields_ = [("mode", C.c_int), ("file_rows", C.c_uint32), ("rows", C.c_uint32), ("baseline", C.c_double * 2),
+                ("rate", C.c_double * MAX_RESCALE_ROWS * 2), ("damage", C.c_double * MAX_RESCALE_ROWS * 2),
+                ("table", C.c_uint8 * (2 * MAX_RESCALE_ROWS * RESCALE_QUALS))]
+
+
+def rescale_table(path, mode: str, baseline: float | None = None) -> dict:
+    """The quality-rescale table from the <prefix>.pss.rates.txt of an earlier run (pss_rescale_table, libpssbam_host.so): {"mode",
+    "file_rows", "rows", "baseline" [2], "rate" [2][rows], "damage" [2][rows], "table" uint8 [2][rows][94]}, end 0 the 5' and 1 the
+    3' end.  baseline None: the mean of each end's column over the second half of the file's rows.  PssbamError with the
+    command's own message for a file it refuses."""
+    H = C.CDLL(str(LIB_HOST))
+    H.pss_rescale_table.argtypes = [C.c_char_p, C.c_int, C.c_double, C.POINTER(_Rescale), C.c_char_p, C.c_size_t]
+    r, err = _Rescale(), C.create_string_buffer(700)
+    if H.pss_rescale_table(str(path).encode(), RESCALE_MODES[mode], -1.0 if baseline is None else float(baseline), C.byref(r), err, len(err)):
+        raise PssbamError(err.value.decode())
+    n = int(r.rows)
+    return {"mode": mode, "file_rows": int(r.file_rows), "rows": n, "baseline": [float(v) for v in r.baseline],
+            "rate": np.array([list(r.rate[e])[:n] for e in range(2)]), "damage": np.array([list(r.damage[e])[:n] for e in range(2)]),
+            "table": np.frombuffer(bytes(r.table), dtype=np.uint8)[:2 * n * RESCALE_QUALS].reshape(2, n, RESCALE_QUALS).copy()}

@@ -8,7 +8,10 @@
  * bam_writer_append_blocks in uneven pieces -- the path of pss-bam -O ... -Z without a GPU (-x trunc / -x chain damage the last
  * piece: the call must fail and leave no file); with -w and -K <all|ds|ss>,<n5>[,<n3>] every record passes through the end mask
  * of pss-bam -K on its way to the writer -- the per-record function the device kernel runs (csrc/end_mask_kernels.h), compiled
- * for the host; with -s <sites.txt> the sites-file reader of pss-bam -a (alleles.h) runs over the file and, with -S <prefix>, its
+ * for the host; with -w and -k <ds|ss>,<rates file>[,<baseline>] (and -f, -r <region_len>, -M <min mapq>) every record that pss-bam
+ * -r -q would add to a table passes through the quality rescale first -- the table builder (rescale.h) and the
+ * per-record function of the device kernel (csrc/rescale_kernels.h), the plan restated for the host there -- and the candidate counts
+ * are printed; with -s <sites.txt> the sites-file reader of pss-bam -a (alleles.h) runs over the file and, with -S <prefix>, its
  * report writer over made-up counts for the sites read (a refused file is exit 1 with the reader's message).  It exists for the
  * sanitizer builds (`make sanitize`: ThreadSanitizer and
  * AddressSanitizer + UBSan; tests/test_sanitizers.py) -- the digests of the instrumented
@@ -25,6 +28,8 @@
 #include "end_mask.h"
 #include "end_mask_kernels.h"
 #include "fasta-genome-io.h"
+#include "rescale.h"
+#include "rescale_kernels.h"
 #include "sam_reader.h"
 
 #include <zlib.h>
@@ -120,6 +125,11 @@ int main(int argc, char **argv)
     uint32_t mask_n5 = 0, mask_n3 = 0;
     uint8_t *masked = NULL;   /* -K: the batch on its way to the writer */
     size_t masked_cap = 0;
+    const char *rescale_arg = NULL;   /* -k, with -r and -M */
+    static pss_rescale rescale;
+    uint32_t region_len = 15, min_mq = 0;
+    static uint32_t rs_counts[4 * PSS_RESCALE_MAX_ROWS];
+    static uint64_t rs_total[4 * PSS_RESCALE_MAX_ROWS];
     int quick = 0; /* -q: no digest, just drain the reader and report its inflate seconds (throughput probe) */
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-q")) { quick = 1; continue; }
@@ -131,6 +141,9 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "-b")) blocks = 1;
         else if (!strcmp(argv[i], "-x") && i + 1 < argc) damage = argv[++i];
         else if (!strcmp(argv[i], "-K") && i + 1 < argc) mask_arg = argv[++i];
+        else if (!strcmp(argv[i], "-k") && i + 1 < argc) rescale_arg = argv[++i];
+        else if (!strcmp(argv[i], "-r") && i + 1 < argc) region_len = (uint32_t)atoi(argv[++i]);
+        else if (!strcmp(argv[i], "-M") && i + 1 < argc) min_mq = (uint32_t)atoi(argv[++i]);
         else if (!strcmp(argv[i], "-s") && i + 1 < argc) sites_fn = argv[++i];
         else if (!strcmp(argv[i], "-S") && i + 1 < argc) sites_out = argv[++i];
     }
@@ -139,8 +152,13 @@ int main(int argc, char **argv)
         if (pss_parse_end_mask(mask_arg, &mask_mode, &mask_n5, &mask_n3, err, sizeof err)) { fprintf(stderr, "hostcheck: %s\n", err); return 1; }
         if (!out) { fprintf(stderr, "hostcheck: -K masks what -w writes\n"); return 1; }
     }
+    if (rescale_arg) {
+        char err[700];
+        if (pss_parse_rescale(rescale_arg, &rescale, NULL, err, sizeof err)) { fprintf(stderr, "hostcheck: %s\n", err); return 1; }
+        if (!out || !fa) { fprintf(stderr, "hostcheck: -k rescales what -w writes, against the genome of -f\n"); return 1; }
+    }
     if (!fa && !aln && !sites_fn) {
-        fprintf(stderr, "usage: hostcheck [-f genome.fa[.gz]] [-a file.bam|file.sam[.gz] [-w out.bam [-z level] [-t threads] [-b [-x trunc|chain]] [-K mode,n5[,n3]]]] [-s sites.txt [-S prefix]]\n");
+        fprintf(stderr, "usage: hostcheck [-f genome.fa[.gz]] [-a file.bam|file.sam[.gz] [-w out.bam [-z level] [-t threads] [-b [-x trunc|chain]] [-K mode,n5[,n3]] [-k mode,rates[,baseline] [-r region_len] [-M min_mapq]]]] [-s sites.txt [-S prefix]]\n");
         return 2;
     }
     if (sites_fn) {   /* pss-bam -a: the reader, and the writer over counts made up from the site's number */
@@ -181,6 +199,7 @@ int main(int argc, char **argv)
         }
         pss_free_sites(&st);
     }
+    Genome *genome = NULL;   /* -k: kept for the records */
     if (fa) {
         Genome *g = init_genome(fa);
         if (!g) { fprintf(stderr, "hostcheck: cannot load %s\n", fa); return 1; }
@@ -191,7 +210,8 @@ int main(int argc, char **argv)
             bases += g->seqs[i]->len;
         }
         printf("genome seqs=%zu bases=%llu digest=%016llx\n", (size_t)g->n_seqs, (unsigned long long)bases, (unsigned long long)h);
-        destroy_genome(g);
+        if (rescale_arg) genome = g;
+        else destroy_genome(g);
     }
     if (aln) {
         char err[512];
@@ -205,6 +225,27 @@ int main(int argc, char **argv)
             if (!rd) { fprintf(stderr, "hostcheck: -w takes a BAM input\n"); return 1; }
             wr = bam_writer_open(out, bam_reader_header(rd), level, wthreads);
             if (!wr) { fprintf(stderr, "hostcheck: %s\n", bam_writer_open_error()); return 1; }
+        }
+        /* -k: the BAM's references in the genome's stored form (A C G T = 0 1 2 3 after the upper-case fold, everything else itself) */
+        uint8_t **contigs = NULL;
+        uint32_t *contig_len = NULL;
+        const int32_t n_contigs = rescale_arg && rd ? bam_reader_header(rd)->n_ref : 0;
+        const uint32_t rs_d = rescale.rows < region_len ? rescale.rows : region_len;
+        if (rescale_arg) {
+            contigs = (uint8_t **)calloc((size_t)n_contigs + 1, sizeof *contigs);
+            contig_len = (uint32_t *)calloc((size_t)n_contigs + 1, sizeof *contig_len);
+            if (!contigs || !contig_len) { fprintf(stderr, "hostcheck: out of memory\n"); return 1; }
+            for (int32_t k = 0; k < n_contigs; k++) {
+                const Seq *sq = find_seq(genome, bam_reader_header(rd)->ref_name[k]);
+                if (!sq || sq->len > 0xFFFFFFFFu) continue;
+                contigs[k] = (uint8_t *)malloc(sq->len ? sq->len : 1);
+                if (!contigs[k]) { fprintf(stderr, "hostcheck: out of memory\n"); return 1; }
+                contig_len[k] = (uint32_t)sq->len;
+                for (size_t j = 0; j < sq->len; j++) {
+                    const int c = sq->seq[j] >= 'a' && sq->seq[j] <= 'z' ? sq->seq[j] - 32 : (unsigned char)sq->seq[j];
+                    contigs[k][j] = (uint8_t)(c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : c);
+                }
+            }
         }
         struct reblock rb;
         memset(&rb, 0, sizeof rb);
@@ -224,6 +265,30 @@ int main(int argc, char **argv)
                 if (offs[i + 1] - offs[i] != 4u + bs) { fprintf(stderr, "hostcheck: record %lld mis-indexed\n", (long long)(recs + i)); return 1; }
             }
             if (!quick) h = fnv(h, p, nbytes);
+            if (wr && rescale_arg) {   /* -k in front of -K, as on the device: a buffer of exactly the batch's size here too */
+                if (masked_cap != nbytes) {
+                    free(masked);
+                    masked = (uint8_t *)malloc(nbytes ? nbytes : 1);
+                    masked_cap = nbytes;
+                    if (!masked) { fprintf(stderr, "hostcheck: out of memory\n"); return 1; }
+                }
+                memcpy(masked, p, nbytes);
+                memset(rs_counts, 0, sizeof rs_counts);
+                for (int64_t i = 0; i < n && rs_d; i++) {
+                    const uint8_t *G;
+                    int64_t s;
+                    uint32_t L, rev, in_fwd, in_rev;
+                    const uint32_t len = offs[i + 1] - offs[i];
+                    if (!pssbam_rescale_host_plan(p + offs[i], len, (const uint8_t *const *)contigs, contig_len, n_contigs, region_len, min_mq, &G, &s, &L, &rev, &in_fwd, &in_rev))
+                        continue;
+                    pssbam_rescale_record(p + offs[i], masked + offs[i], len, G, s, L, rev, in_fwd, in_rev, (uint32_t)rescale.mode, rs_d, rescale.rows, 0u,
+                                          rescale.table, rs_counts);
+                }
+                for (size_t k = 0; k < 4 * (size_t)rescale.rows; k++) rs_total[k] += rs_counts[k];
+                if (mask_mode != PSSBAM_EM_OFF)
+                    for (int64_t i = 0; i < n; i++) pssbam_end_mask_record(masked + offs[i], offs[i + 1] - offs[i], (uint32_t)mask_mode, mask_n5, mask_n3);
+                p = masked;
+            } else
             if (wr && mask_mode != PSSBAM_EM_OFF) {   /* a buffer of exactly the batch's size: a stray write is one past a heap block */
                 if (masked_cap != nbytes) {
                     free(masked);
@@ -257,6 +322,13 @@ int main(int argc, char **argv)
             free(rb.blk);
         }
         free(masked);
+        for (int32_t k = 0; k < n_contigs; k++) free(contigs[k]);
+        free(contigs);
+        free(contig_len);
+        if (rescale_arg)
+            for (uint32_t k = 0; k < 2 * rs_d; k++)
+                printf("rescale end=%d row=%u candidates=%llu lowered=%llu\n", k < rs_d ? 5 : 3, k % rs_d, (unsigned long long)rs_total[2 * ((k / rs_d) * rescale.rows + k % rs_d)],
+                       (unsigned long long)rs_total[2 * ((k / rs_d) * rescale.rows + k % rs_d) + 1]);
         if (wr && bam_writer_close(wr, err, sizeof err)) { fprintf(stderr, "hostcheck: %s\n", err); return 1; }
         const int32_t n_ref = rd ? bam_reader_header(rd)->n_ref : sam_reader_n_ref(sd);
         printf("alignments input=%s refs=%d records=%llu bytes=%llu digest=%016llx\n", is_bam ? "bam" : "sam", n_ref,
@@ -266,5 +338,6 @@ int main(int argc, char **argv)
         bam_reader_close(rd);
         sam_reader_close(sd);
     }
+    if (genome) destroy_genome(genome);
     return 0;
 }
