@@ -783,6 +783,23 @@ int pssbam_engine_finish_coverage(pssbam_engine *e, int32_t first_ref, int32_t n
  * tile sums instead of computing them again. */
 int pssbam_engine_finish_coverage_runs(pssbam_engine *e, uint64_t cap, int32_t *ref, uint32_t *start, uint32_t *end, uint32_t *depth,
                                        uint64_t *n_runs);
+/* Fixed windows (pss-bam -w): every reference of the last set_references that the genome holds is cut into the windows
+ * [k * window, min((k + 1) * window, length)), k = 0 .. ceil(length / window) - 1, contig-relative and 0-based; the last window of a
+ * contig may be short, none crosses a contig, and padding belongs to none.  Window i is [start[i], end[i]) of reference ref[i] (-1:
+ * the contig named "*"); acgt[i] = its positions whose FASTA letter, upper-cased, is A, C, G or T; gc[i] = those that are C or G;
+ * covered[i] = its positions at depth > 0; depth_sum[i] = the sum of depth(c, p) over it, depth as defined above.  All exact.  Windows
+ * come by refID, then start; the later one of two references of the same name has none.  *n_windows = the exact count, always;
+ * with all seven arrays NULL that is all the call does.  Any single array may be NULL.  Drains like pssbam_engine_finish_coverage, is
+ * non-destructive and may be called any number of times; it starts from the tile sums of an earlier finish call when nothing was
+ * submitted since, and keeps its own result for the same window until a block is submitted, the references or the genome change,
+ * the engine is reset or coverage is switched off.  The accumulators (20 bytes per window, in up to 64 copies while that stays below 1.3 MB) are allocated by the call and freed by
+ * it: PSSBAM_ENOMEM when they do not fit the device.  PSSBAM_EINVAL for a window outside PSSBAM_COV_WINDOW_MIN ..
+ * PSSBAM_COV_WINDOW_MAX, when the count does not fit 32 bits, when cap, the room of each array, is below the count, and when the
+ * setting is off; PSSBAM_ESTATE without a genome and references.  Nothing is launched or allocated while the call is not used. */
+#define PSSBAM_COV_WINDOW_MIN 16u
+#define PSSBAM_COV_WINDOW_MAX (1u << 30)
+int pssbam_engine_finish_coverage_windows(pssbam_engine *e, uint32_t window, uint64_t cap, int32_t *ref, uint32_t *start, uint32_t *end,
+                                          uint32_t *acgt, uint32_t *gc, uint32_t *covered, uint64_t *depth_sum, uint64_t *n_windows);
 
 /* Strand-split allele counts of the kept records at listed sites (pss-bam -a / -t), from the same pass: the pileup at a SNP panel.
  *   A site is a (contig, 0-based position) pair: site i is pos0[i] on the contig named names[name_of[i]].  Positions may come in any

@@ -53,6 +53,7 @@ HIP_SYMBOLS = [
     "pssbam_engine_set_record_sink", "pssbam_engine_set_block_sink", "pssbam_engine_set_end_mask",
     "pssbam_engine_set_duplicates", "pssbam_engine_finish_duplicates",
     "pssbam_engine_set_coverage", "pssbam_engine_finish_coverage", "pssbam_engine_finish_coverage_runs",
+    "pssbam_engine_finish_coverage_windows",
     "pssbam_engine_set_sites", "pssbam_engine_finish_sites",
     "pssbam_bgzf_deflate_work_bytes", "pssbam_bgzf_deflate_device", "pssbam_bgzf_deflate_host",
 ]
@@ -197,6 +198,8 @@ def hip_lib() -> C.CDLL:
         L.pssbam_engine_set_coverage.argtypes = [C.c_void_p, C.c_int32, C.c_uint64]
         L.pssbam_engine_finish_coverage.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.pssbam_engine_finish_coverage_runs.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "pssbam_engine_finish_coverage_windows"):   # (tools/windows_bench.py also loads the library of the commit before it)
+        L.pssbam_engine_finish_coverage_windows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64] + [C.c_void_p] * 8
     if hasattr(L, "pssbam_engine_set_sites"):   # (tools/allele_bench.py also loads the library of the commit before it)
         L.pssbam_engine_set_sites.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int64, C.c_void_p, C.c_void_p, C.c_uint32]
         L.pssbam_engine_finish_sites.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -868,6 +871,25 @@ class Engine:
                                                         C.addressof(n_runs)))
         n = int(n_runs.value)
         return ref[:n], start[:n], end[:n], depth[:n]
+
+    def finish_coverage_windows(self, window: int, cap: int | None = None, count_only: bool = False):
+        """sync, then the fixed windows of `window` positions (16 .. 2**30) of every reference the genome holds as (ref, start, end,
+        acgt, gc, covered, depth_sum) arrays -- half-open, by refID then start, the last window of a contig possibly short -- or,
+        with count_only, their number.  cap: the room to offer (default: the exact count, asked for first).  Non-destructive."""
+        n_win = C.c_uint64(0)
+        if count_only or cap is None:
+            _chk(self._L.pssbam_engine_finish_coverage_windows(self._h, int(window), 0, None, None, None, None, None, None, None, C.addressof(n_win)))
+            if count_only:
+                return int(n_win.value)
+            cap = int(n_win.value)
+        ref = np.zeros(max(int(cap), 1), dtype=np.int32)
+        start, end, acgt, gc, covered = (np.zeros(max(int(cap), 1), dtype=np.uint32) for _ in range(5))
+        depth_sum = np.zeros(max(int(cap), 1), dtype=np.uint64)
+        _chk(self._L.pssbam_engine_finish_coverage_windows(self._h, int(window), int(cap), ref.ctypes.data, start.ctypes.data, end.ctypes.data,
+                                                           acgt.ctypes.data, gc.ctypes.data, covered.ctypes.data, depth_sum.ctypes.data,
+                                                           C.addressof(n_win)))
+        n = int(n_win.value)
+        return ref[:n], start[:n], end[:n], acgt[:n], gc[:n], covered[:n], depth_sum[:n]
 
     def set_sites(self, names, name_of, pos0, trim: int = 0):
         """Strand-split allele counts of the kept records at listed sites (pssbam_engine_set_sites): site i is the 0-based position

@@ -18,6 +18,9 @@
 //                       per-contig {covered, depth_sum, max_depth} through LDS accumulators that live across the workgroup's
 //                       tiles (one global atomic per workgroup and contig), and the tile's number of runs.
 //   coverage_runs       (bedGraph only) {contig, start, depth} of every run and the end of the run before it, compacted, in order.
+//   coverage_windows    (pss-bam -w only) every tile once more on top of its base, beside the genome's stored bytes: {depth_sum,
+//                       covered, acgt, gc} of every fixed window of every listed contig, through LDS accumulators of the windows a
+//                       tile meets and one no-return atomic per tile, window and non-zero word (at the end of the file).
 //
 // A run starts where the difference is non-zero and the depth is non-zero, and ends at the next non-zero difference: run boundaries
 // are exactly the non-zero entries of cov[], so runs are maximal by construction and -- the depth being 0 in padding -- never cross a
@@ -294,6 +297,149 @@ __global__ void __launch_bounds__(COV_THREADS) coverage_runs(const uint32_t *cov
                 depth[at] = dep.d[k];
                 at++;
             }
+        }
+    }
+}
+
+// ---- fixed windows (pssbam_engine_finish_coverage_windows, pss-bam -w) ----------------------------------------------------------------
+// Every listed contig is cut into windows [k W, min((k + 1) W, length)); the window k of the contig at place c of the list has the
+// global id wbase[c] + k (wbase: the host's prefix of ceil(length / W)), so ids rise with the position and the windows a tile meets
+// are one stretch of ids behind w_first.  The accumulators are four arrays over the ids -- an atomic wave-instruction then adds to
+// consecutive words -- in `shards` copies of n entries each: workgroup b adds to copy b % shards and the host sums the copies.  With
+// few, large windows every workgroup at work adds to the same handful of words, and adds to one address take their turns.
+struct CovWindows {
+    unsigned long long *depth_sum;
+    uint32_t *covered, *acgt, *gc;
+    uint64_t n;                       // ids at and above n are never written
+    uint32_t shards;
+};
+
+// A stretch of n positions of one contig meets at most (n + 14) / 16 + 1 windows of 16 or more, and at most 9 contigs meet a tile.
+static constexpr uint32_t COV_TILE_WINDOWS = (COV_TILE + 9 * 14) / 16 + 1 + 9;
+
+__device__ __forceinline__ void coverage_atomic_add64(unsigned long long *p, unsigned long long v) {
+    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// of the four stored genome bytes in x: how many are A C G T (below 4), and how many of those C or G (1 or 2)
+__device__ __forceinline__ void coverage_count_bases(uint32_t x, uint32_t &n_acgt, uint32_t &n_gc) {
+    const uint32_t t = x & 0xFCFCFCFCu;
+    const uint32_t other = ((((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) >> 7) & 0x01010101u;   // 1 per byte of 4 and above (no carry leaves a byte)
+    n_acgt += 4u - __popc(other);
+    n_gc += __popc((x ^ (x >> 1)) & 0x01010101u & ~other);
+}
+
+// Walks the tiles like coverage_stats and adds {depth_sum, covered, acgt, gc} of every window of W positions to out.  A lane sums
+// in registers while contig and window stay the same; what it has goes to the workgroup's LDS accumulators of the tile's windows, and
+// those -- what is non-zero of them -- to the totals once per tile and window.  genome has genome_len stored bytes, a multiple of 16.
+__global__ void __launch_bounds__(COV_THREADS) coverage_windows(const uint32_t *cov, const uint8_t *genome, uint64_t genome_len, uint64_t n_tiles,
+                                                                const unsigned long long *base, const uint4 *contigs, uint32_t n_contigs,
+                                                                const unsigned long long *wbase, uint32_t W, CovWindows out) {
+    __shared__ uint32_t lds[COV_THREADS / 64];
+    __shared__ unsigned long long w_sum[COV_TILE_WINDOWS];
+    __shared__ uint32_t w_cov[COV_TILE_WINDOWS], w_acgt[COV_TILE_WINDOWS], w_gc[COV_TILE_WINDOWS];
+    for (uint32_t i = threadIdx.x; i < COV_TILE_WINDOWS; i += COV_THREADS) { w_sum[i] = 0ull; w_cov[i] = 0u; w_acgt[i] = 0u; w_gc[i] = 0u; }
+    const uint64_t copy = (uint64_t)(blockIdx.x % out.shards) * out.n;   // the workgroup's copy of the accumulators
+    for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const CovItems diff = coverage_load(cov, t);
+        const uint64_t p_tile = t * COV_TILE, p0 = p_tile + (uint64_t)threadIdx.x * COV_ITEMS;
+        const uint4 g = p0 < genome_len ? *(const uint4 *)(genome + p0) : make_uint4(~0u, ~0u, ~0u, ~0u);   // (behind the genome lies no contig)
+        const uint32_t gw[4] = {g.x, g.y, g.z, g.w};
+        const uint32_t c_lo = coverage_find(contigs, 0u, n_contigs, p_tile);               // the same addresses in every lane
+        const uint32_t c_hi = coverage_find(contigs, c_lo, n_contigs, p_tile + COV_TILE - 1u);
+        uint64_t w_first = 0;                                                              // the id of the tile's first window
+        if (c_lo < n_contigs) {
+            const uint64_t lo0 = coverage_contig_lo(contigs[c_lo]);
+            w_first = wbase[c_lo] + (p_tile > lo0 ? (uint32_t)(p_tile - lo0) / W : 0u);
+        }
+        CovItems dep;
+        const uint32_t before = coverage_depths(dep, diff, (uint32_t)base[t], lds);   // (its barriers also order the zeroing above and below)
+        uint32_t idx = coverage_find(contigs, c_lo, min(c_hi + 1u, n_contigs), p0);
+        uint4 c = idx < n_contigs ? contigs[idx] : make_uint4(0u, 0u, 0u, 0u);
+        // the window at hand: id wid, ends in front of genome position w_end (0: none)
+        uint64_t wid = 0, w_end = 0, d_sum = 0;
+        uint32_t n_cov = 0u, n_acgt = 0u, n_gc = 0u;
+        auto flush = [&]() {
+            if (n_cov | n_acgt) {
+                const uint64_t slot = wid - w_first;
+                if (slot < COV_TILE_WINDOWS) {
+                    if (d_sum) atomicAdd(&w_sum[slot], (unsigned long long)d_sum);
+                    if (n_cov) atomicAdd(&w_cov[slot], n_cov);
+                    if (n_acgt) atomicAdd(&w_acgt[slot], n_acgt);
+                    if (n_gc) atomicAdd(&w_gc[slot], n_gc);
+                } else if (wid < out.n) {   // (more windows in a tile than the stored layout allows: straight to the totals)
+                    if (d_sum) coverage_atomic_add64(out.depth_sum + copy + wid, d_sum);
+                    if (n_cov) coverage_atomic_add(out.covered + copy + wid, n_cov);
+                    if (n_acgt) coverage_atomic_add(out.acgt + copy + wid, n_acgt);
+                    if (n_gc) coverage_atomic_add(out.gc + copy + wid, n_gc);
+                }
+            }
+            n_cov = 0u; n_acgt = 0u; n_gc = 0u; d_sum = 0;
+        };
+        auto enter = [&](uint64_t p) {   // p lies in contig idx and behind the window at hand
+            flush();
+            const uint64_t lo = coverage_contig_lo(c);
+            const uint32_t k = (uint32_t)(p - lo) / W;
+            wid = wbase[idx] + k;
+            w_end = lo + min((uint64_t)(k + 1u) * W, (uint64_t)c.z);
+        };
+        // the common lane: all of its positions inside one window and no difference among them -- one depth, sixteen times, and the
+        // bases counted a word at a time
+        uint32_t any = 0u;
+        for (uint32_t k = 0; k < COV_ITEMS; k++) any |= diff.d[k];
+        bool plain = !any && idx < n_contigs && p0 >= coverage_contig_lo(c) && p0 + COV_ITEMS <= coverage_contig_lo(c) + c.z;
+        if (plain) {
+            enter(p0);
+            plain = p0 + COV_ITEMS <= w_end;
+        }
+        if (plain) {
+            for (uint32_t k = 0; k < 4u; k++) coverage_count_bases(gw[k], n_acgt, n_gc);
+            if (before) { n_cov = COV_ITEMS; d_sum = (uint64_t)before * COV_ITEMS; }
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < COV_ITEMS; k++) {
+            if (plain) break;
+            const uint64_t p = p0 + k;
+            while (idx < n_contigs && p >= coverage_contig_lo(c) + c.z) {
+                flush();
+                w_end = 0;
+                idx++;
+                if (idx < n_contigs) c = contigs[idx];
+            }
+            if (idx >= n_contigs || p < coverage_contig_lo(c)) continue;   // padding
+            if (p >= w_end) enter(p);
+            const uint32_t b = (gw[k >> 2] >> (8u * (k & 3u))) & 0xFFu, d = dep.d[k];
+            n_acgt += b < 4u ? 1u : 0u;
+            n_gc += b == 1u || b == 2u ? 1u : 0u;
+            n_cov += d ? 1u : 0u;
+            d_sum += d;
+        }
+        // what the lane holds at its end: when the whole wave holds the same window -- every wave of a tile inside a large window
+        // -- the wave sums first and one lane adds
+        const uint64_t wid0 = __shfl(wid, 0);
+        if (__all(w_end != 0 && wid == wid0)) {
+            uint32_t bases = n_acgt | (n_gc << 16);   // (at most 1024 each)
+            for (uint32_t m = 1; m < 64u; m <<= 1) {
+                d_sum += __shfl_xor(d_sum, m);
+                n_cov += __shfl_xor(n_cov, m);
+                bases += __shfl_xor(bases, m);
+            }
+            if (threadIdx.x & 63u) { d_sum = 0; n_cov = 0u; bases = 0u; }
+            n_acgt = bases & 0xFFFFu;
+            n_gc = bases >> 16;
+        }
+        flush();
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < COV_TILE_WINDOWS; i += COV_THREADS) {
+            const uint64_t w = w_first + i;
+            if (!(w_cov[i] | w_acgt[i])) continue;
+            if (w < out.n) {
+                if (w_sum[i]) coverage_atomic_add64(out.depth_sum + copy + w, w_sum[i]);
+                if (w_cov[i]) coverage_atomic_add(out.covered + copy + w, w_cov[i]);
+                if (w_acgt[i]) coverage_atomic_add(out.acgt + copy + w, w_acgt[i]);
+                if (w_gc[i]) coverage_atomic_add(out.gc + copy + w, w_gc[i]);
+            }
+            w_sum[i] = 0ull; w_cov[i] = 0u; w_acgt[i] = 0u; w_gc[i] = 0u;
         }
     }
 }

@@ -25,6 +25,7 @@
 #include <atomic>
 #include <memory>
 #include <mutex>
+#include <new>
 #include <vector>
 
 #include "tally_kernels.h"
@@ -417,6 +418,12 @@ struct pssbam_engine {
     size_t scratch_slots = 0;
     uint32_t dev_pieces = 0;       // prefix pieces sampled from a device-resident block
     uint64_t dev_pieces_avg = 0;   // ... and the mean record size it was sampled at
+    // finish_coverage_windows (behind everything a submit touches, whose places stay what they were): cov_epoch counts the times the totals were computed; the windows of size cov_win_size (0: none), in
+    // genome order, stand while cov_win_epoch is the epoch of totals that are still valid
+    uint64_t cov_epoch = 0, cov_win_epoch = 0;
+    uint32_t cov_win_size = 0;
+    std::vector<unsigned long long> cov_win_sum;
+    std::vector<uint32_t> cov_win_cov, cov_win_acgt, cov_win_gc;
 };
 
 static void ctx_mask(const char *set, uint32_t (&m)[8]) {
@@ -2909,6 +2916,11 @@ extern "C" int pssbam_engine_set_coverage(pssbam_engine *e, int32_t on, uint64_t
     } else {
         e->coverage = false;
         e->cov_hint = 0;
+        e->cov_win_size = 0;
+        std::vector<unsigned long long>().swap(e->cov_win_sum);
+        std::vector<uint32_t>().swap(e->cov_win_cov);
+        std::vector<uint32_t>().swap(e->cov_win_acgt);
+        std::vector<uint32_t>().swap(e->cov_win_gc);
         if (e->d_cov || e->d_cov_sums || e->d_cov_out || e->d_cov_contigs || e->d_cov_runs) {   // off: nothing stays allocated
             HIP_TRY(hipStreamSynchronize(e->stream));   // (reset's memset)
             if (e->genome_stream) HIP_TRY(hipStreamSynchronize(e->genome_stream));
@@ -2989,6 +3001,7 @@ static int coverage_totals(pssbam_engine *e) {
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->cov_totals_valid = true;
     e->cov_runs_scanned = false;
+    e->cov_epoch++;
     return PSSBAM_OK;
 }
 
@@ -3088,6 +3101,119 @@ extern "C" int pssbam_engine_finish_coverage_runs(pssbam_engine *e, uint64_t cap
             if (depth) depth[at] = h[3 * total + i];
         }
     if (at != total) return fail(PSSBAM_EHIP, "coverage runs outside the listed contigs: %llu of %llu placed", (unsigned long long)at, (unsigned long long)total);
+    return PSSBAM_OK;
+}
+
+// Fixed windows over the same array (coverage_windows).  The accumulators live for the call; the result stays on the host, in genome
+// order, while cov_epoch says that the totals it was computed beside still stand and the window size is the same.
+extern "C" int pssbam_engine_finish_coverage_windows(pssbam_engine *e, uint32_t window, uint64_t cap, int32_t *ref, uint32_t *start, uint32_t *end,
+                                                     uint32_t *acgt, uint32_t *gc, uint32_t *covered, uint64_t *depth_sum, uint64_t *n_windows) {
+    int rc = coverage_ready(e);
+    if (rc) return rc;
+    if (window < PSSBAM_COV_WINDOW_MIN || window > PSSBAM_COV_WINDOW_MAX)
+        return fail(PSSBAM_EINVAL, "window size %u outside %u..%u", window, PSSBAM_COV_WINDOW_MIN, PSSBAM_COV_WINDOW_MAX);
+    if (!e->d_genome || !e->have_refs || !e->d_cov) return fail(PSSBAM_ESTATE, "windows need the genome and the references (set_genome, set_references)");
+    const size_t n_contigs = e->cov_contigs.size();
+    std::vector<unsigned long long> wbase(n_contigs + 1, 0ull);   // the id of each contig's first window, in genome order
+    for (size_t k = 0; k < n_contigs; k++) wbase[k + 1] = wbase[k] + ((uint64_t)e->cov_contigs[k].z + window - 1) / window;
+    const uint64_t total = wbase[n_contigs];
+    if (total > 0xFFFFFFFFull) return fail(PSSBAM_EINVAL, "%llu windows of %u positions: the count does not fit 32 bits", (unsigned long long)total, window);
+    if (n_windows) *n_windows = total;
+    if (!ref && !start && !end && !acgt && !gc && !covered && !depth_sum) return PSSBAM_OK;
+    if (cap < total) return fail(PSSBAM_EINVAL, "room for %llu windows, the genome has %llu", (unsigned long long)cap, (unsigned long long)total);
+    if (!total) return PSSBAM_OK;
+    if ((rc = coverage_totals(e))) return rc;   // the tiles' bases: those of the last finish call when nothing was added since
+    if (e->cov_win_size != window || e->cov_win_epoch != e->cov_epoch || e->cov_win_sum.size() != total) {
+        e->cov_win_size = 0;
+        // [depth_sum | covered | acgt | gc] over the ids, then the contigs' first ids.  While windows are few the four arrays come in
+        // `shards` copies (at most 1.3 MB): every workgroup at work would add to the same few words otherwise.
+        const uint32_t shards = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(64, (1ull << 16) / total));
+        const size_t cells = (size_t)total * shards;
+        // the host's room first, so that nothing of the device is held when it cannot be had; one copy is read straight into it,
+        // several go through h and are summed
+        std::vector<unsigned long long> h;
+        try {
+            e->cov_win_sum.resize(total);
+            e->cov_win_cov.resize(total);
+            e->cov_win_acgt.resize(total);
+            e->cov_win_gc.resize(total);
+            if (shards > 1) h.resize(cells * (sizeof(unsigned long long) + 3 * sizeof(uint32_t)) / sizeof(unsigned long long) + 1);
+        } catch (const std::bad_alloc &) {
+            return fail(PSSBAM_ENOMEM, "no host memory for %llu windows", (unsigned long long)total);
+        }
+        const size_t acc_bytes = cells * (sizeof(unsigned long long) + 3 * sizeof(uint32_t)), wbase_bytes = std::max<size_t>(n_contigs, 1) * sizeof(unsigned long long);
+        unsigned char *d_acc = nullptr;
+        if (hipMalloc((void **)&d_acc, acc_bytes + wbase_bytes + 16) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(PSSBAM_ENOMEM, "the accumulators of %llu windows (%llu bytes) do not fit the device", (unsigned long long)total, (unsigned long long)acc_bytes);
+        }
+        CovWindows W;
+        W.depth_sum = (unsigned long long *)d_acc;
+        W.covered = (uint32_t *)(W.depth_sum + cells);
+        W.acgt = W.covered + cells;
+        W.gc = W.acgt + cells;
+        W.n = total;
+        W.shards = shards;
+        unsigned long long *const d_wbase = (unsigned long long *)(d_acc + (acc_bytes + 7) / 8 * 8);
+        const uint64_t n_tiles = e->cov_len / COV_TILE;
+        hipError_t err = hipMemsetAsync(d_acc, 0, acc_bytes, e->stream);
+        if (err == hipSuccess && n_contigs) err = hipMemcpyAsync(d_wbase, wbase.data(), n_contigs * sizeof(unsigned long long), hipMemcpyHostToDevice, e->stream);
+        if (err == hipSuccess) {
+            hipLaunchKernelGGL(coverage_windows, dim3(coverage_grid(e, n_tiles)), dim3(COV_THREADS), 0, e->stream, (const uint32_t *)e->d_cov,
+                               (const uint8_t *)e->d_genome, e->genome_bytes, n_tiles, (const unsigned long long *)e->d_cov_sums, (const uint4 *)e->d_cov_contigs,
+                               (uint32_t)n_contigs, (const unsigned long long *)d_wbase, window, W);
+            err = hipGetLastError();
+        }
+        if (shards > 1) {
+            if (err == hipSuccess) err = hipMemcpyAsync(h.data(), d_acc, acc_bytes, hipMemcpyDeviceToHost, e->stream);
+        } else {
+            if (err == hipSuccess) err = hipMemcpyAsync(e->cov_win_sum.data(), W.depth_sum, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream);
+            if (err == hipSuccess) err = hipMemcpyAsync(e->cov_win_cov.data(), W.covered, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
+            if (err == hipSuccess) err = hipMemcpyAsync(e->cov_win_acgt.data(), W.acgt, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
+            if (err == hipSuccess) err = hipMemcpyAsync(e->cov_win_gc.data(), W.gc, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
+        }
+        const hipError_t err_sync = hipStreamSynchronize(e->stream);   // (wbase and the four vectors are read and written until here)
+        (void)hipFree(d_acc);
+        HIP_TRY(err);
+        HIP_TRY(err_sync);
+        if (shards > 1) {
+            const unsigned long long *h_sum = h.data();
+            const uint32_t *h_cov = (const uint32_t *)(h_sum + cells), *h_acgt = h_cov + cells, *h_gc = h_acgt + cells;
+            for (uint64_t w = 0; w < total; w++) {
+                unsigned long long s_sum = 0;
+                uint32_t s_cov = 0, s_acgt = 0, s_gc = 0;
+                for (uint32_t s = 0; s < shards; s++) {
+                    s_sum += h_sum[s * total + w];
+                    s_cov += h_cov[s * total + w];
+                    s_acgt += h_acgt[s * total + w];
+                    s_gc += h_gc[s * total + w];
+                }
+                e->cov_win_sum[w] = s_sum;
+                e->cov_win_cov[w] = s_cov;
+                e->cov_win_acgt[w] = s_acgt;
+                e->cov_win_gc[w] = s_gc;
+            }
+        }
+        e->cov_win_size = window;
+        e->cov_win_epoch = e->cov_epoch;
+    }
+    // the device's order is the genome's (contigs by name); the caller's is by refID
+    std::vector<std::pair<uint32_t, uint32_t>> by_ref;   // {refID, slot}
+    for (size_t k = 0; k < n_contigs; k++) by_ref.emplace_back(e->cov_contigs[k].w, (uint32_t)k);
+    std::sort(by_ref.begin(), by_ref.end());
+    uint64_t at = 0;
+    for (const auto &rs : by_ref) {
+        const uint64_t len = e->cov_contigs[rs.second].z, first = wbase[rs.second], n = wbase[rs.second + 1] - first;
+        for (uint64_t k = 0; k < n; k++, at++) {
+            if (ref) ref[at] = rs.first == (uint32_t)e->n_ref ? -1 : (int32_t)rs.first;
+            if (start) start[at] = (uint32_t)(k * window);
+            if (end) end[at] = (uint32_t)std::min<uint64_t>((k + 1) * window, len);
+            if (acgt) acgt[at] = e->cov_win_acgt[first + k];
+            if (gc) gc[at] = e->cov_win_gc[first + k];
+            if (covered) covered[at] = e->cov_win_cov[first + k];
+            if (depth_sum) depth_sum[at] = e->cov_win_sum[first + k];
+        }
+    }
     return PSSBAM_OK;
 }
 

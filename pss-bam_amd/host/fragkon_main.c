@@ -15,6 +15,7 @@
  * an unpaired candidate of this command's own filters): every table is what this command gives without -d for the input whose
  * duplicates carry FLAG 0x400.  With -o it also writes <prefix>.fragkon.duplicates.txt (duplicates.h).  One GPU.
  * pss-bam's -c / -b (depth of coverage of the tallied reads) are refused: the candidates of the k-mer tables are not the reads of a table.
+ * So is its -w (windowed depth and GC content), which reads the same array.
  * So are its -a / -t (allele counts of the tallied reads at listed sites), for the same reason.
  */
 #include <ctype.h>
@@ -41,7 +42,7 @@ int main(int argc, char *argv[])
     int by_group = 0, duplicates = 0;
     const char *len_edges = NULL, *ctg_map = NULL, *bed_fn = NULL;
 
-    while ((option = getopt(argc, argv, ":F:B:k:l:L:q:mGS:C:o:T:dcb:a:t:")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:k:l:L:q:mGS:C:o:T:dcb:a:t:w:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -58,6 +59,9 @@ int main(int argc, char *argv[])
         case 'c':
         case 'b':   /* pss-bam's depth of coverage is that of the reads in its tables; this command's candidates are not those */
             fprintf(stderr, "-%c (depth of coverage of the tallied reads) is an option of pss-bam: fragkon has none.\n", option);
+            exit(1);
+        case 'w':   /* ... and so is the depth of its windows */
+            fprintf(stderr, "-%c (windowed depth and GC content of the tallied reads) is an option of pss-bam: fragkon has none.\n", option);
             exit(1);
         case 'a':
         case 't':   /* likewise pss-bam's allele counts at listed sites */

@@ -237,7 +237,7 @@ static int apply_options(pssbam_engine *e)
            (o->out_bam && (o->out_deflate ? pssbam_engine_set_block_sink(e, out_block_sink, NULL) : pssbam_engine_set_record_sink(e, out_sink, NULL))) ||
            (o->out_bam && o->out_mask_mode != PSSBAM_END_MASK_OFF && pssbam_engine_set_end_mask(e, o->out_mask_mode, o->out_mask_n5, o->out_mask_n3)) ||
            (o->duplicates && pssbam_engine_set_duplicates(e, 1, 0)) ||
-           ((o->coverage || o->coverage_bedgraph) && pssbam_engine_set_coverage(e, 1, coverage_positions_hint)) ||
+           ((o->coverage || o->coverage_bedgraph || o->coverage_window) && pssbam_engine_set_coverage(e, 1, coverage_positions_hint)) ||
            (o->sites && pssbam_engine_set_sites(e, o->sites->n_names, (const char *const *)o->sites->names, o->sites->n, o->sites->name_of, o->sites->pos0, o->site_trim));
 }
 
@@ -527,6 +527,13 @@ void run_result_free(run_result *res)
     free(res->cov_run_start);
     free(res->cov_run_end);
     free(res->cov_run_depth);
+    free(res->win_ref);
+    free(res->win_start);
+    free(res->win_end);
+    free(res->win_acgt);
+    free(res->win_gc);
+    free(res->win_covered);
+    free(res->win_depth_sum);
     for (int i = 0; res->allele_names && i < res->allele_n_names; i++) free(res->allele_names[i]);
     free(res->allele_names);
     free(res->allele_ref);
@@ -938,7 +945,7 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
         }
         res->has_duplicates = 1;
     }
-    if (frontend_opts.coverage || frontend_opts.coverage_bedgraph) { /* -c / -b: the one engine's array */
+    if (frontend_opts.coverage || frontend_opts.coverage_bedgraph || frontend_opts.coverage_window) { /* -c / -b / -w: the one engine's array */
         const int32_t n_ref = rd ? bam_reader_header(rd)->n_ref : sam_reader_n_ref(sd);
         const char *const *names = rd ? (const char *const *)bam_reader_header(rd)->ref_name : sam_reader_ref_names(sd);
         res->cov_n = n_ref;
@@ -966,6 +973,30 @@ int run_tally(const pssbam_config *cfg, Genome *genome, const char *aln_path, in
             if (!res->cov_run_ref || !res->cov_run_start || !res->cov_run_end || !res->cov_run_depth) { fprintf(stderr, "Error: out of memory\n"); goto done; }
             if (pssbam_engine_finish_coverage_runs(eng[0], res->cov_n_runs, res->cov_run_ref, res->cov_run_start, res->cov_run_end, res->cov_run_depth,
                                                    &res->cov_n_runs)) {
+                fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+                goto done;
+            }
+        }
+        if (frontend_opts.coverage_window) {
+            const uint32_t w = frontend_opts.coverage_window;
+            if (pssbam_engine_finish_coverage_windows(eng[0], w, 0, NULL, NULL, NULL, NULL, NULL, NULL, NULL, &res->win_n)) {
+                fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
+                goto done;
+            }
+            const size_t room = (size_t)res->win_n + 1;
+            res->win_ref = (int32_t *)malloc(room * sizeof(int32_t));
+            res->win_start = (uint32_t *)malloc(room * sizeof(uint32_t));
+            res->win_end = (uint32_t *)malloc(room * sizeof(uint32_t));
+            res->win_acgt = (uint32_t *)malloc(room * sizeof(uint32_t));
+            res->win_gc = (uint32_t *)malloc(room * sizeof(uint32_t));
+            res->win_covered = (uint32_t *)malloc(room * sizeof(uint32_t));
+            res->win_depth_sum = (uint64_t *)malloc(room * sizeof(uint64_t));
+            if (!res->win_ref || !res->win_start || !res->win_end || !res->win_acgt || !res->win_gc || !res->win_covered || !res->win_depth_sum) {
+                fprintf(stderr, "Error: out of memory\n");
+                goto done;
+            }
+            if (pssbam_engine_finish_coverage_windows(eng[0], w, res->win_n, res->win_ref, res->win_start, res->win_end, res->win_acgt, res->win_gc, res->win_covered,
+                                                      res->win_depth_sum, &res->win_n)) {
                 fprintf(stderr, "Error: GPU engine: %s\n", pssbam_last_error());
                 goto done;
             }

@@ -70,6 +70,11 @@ typedef struct run_result {
     uint64_t *cov_lengths, *cov_per_contig, cov_hist[PSS_COV_HIST_MAX + 2], cov_n_runs;
     int32_t *cov_run_ref;
     uint32_t *cov_run_start, *cov_run_end, *cov_run_depth;
+    /* -w (frontend_opts.coverage_window; filled with has_coverage): the win_n windows of pssbam_engine_finish_coverage_windows, by
+     * reference (an index into cov_names) and start */
+    uint64_t win_n, *win_depth_sum;
+    int32_t *win_ref;
+    uint32_t *win_start, *win_end, *win_acgt, *win_gc, *win_covered;
     /* -a (frontend_opts.sites; has_alleles: filled): the allele_n_names references of the input, in header order, and what
      * pssbam_engine_finish_sites gave: the allele_n resolved sites' reference index, 0-based position, reference letter and ten
      * counters each, and the four totals */
@@ -167,6 +172,9 @@ typedef struct frontend_options {
      * LN values as its hint) and run_tally() returns the per-contig figures and the histogram, and for -b the runs.  One GPU. */
     int coverage;
     const char *coverage_bedgraph;
+    /* pss-bam -w: non-zero = the window size; switches the same array on, and run_tally() returns the windows
+     * (pssbam_engine_finish_coverage_windows).  One GPU. */
+    uint32_t coverage_window;
     /* pss-bam -a / -t: the sites of the sites file (alleles.h; NULL: none) and the trim; the run's one engine counts the bases the
      * reads it adds to a table show there (pssbam_engine_set_sites) and run_tally() returns the counts.  One GPU. */
     const pss_sites *sites;

@@ -104,6 +104,13 @@
  * name when it is complete and must not name the -B or the -O file.  Either switches the engine's array on (4 bytes per genome
  * position on the device); -b alone writes no summary.  Not with -I (the span of a clipped read needs a definition of its own); SAM
  * text is fine; one GPU (PSSBAM_NGPU unset or 1): the arrays of several engines are not summed.
+ * Added: -w <size> cuts every reference of the input's header that the FASTA holds into windows of <size> positions (16..2^30; the last one
+ * of a contig may be short) and writes, from the same pass and the same array as -c, <prefix>.pss.windows.txt -- per window the A/C/G/T
+ * letters of the FASTA, those that are C or G, their fraction, the covered positions, the summed and the mean depth of the tallied
+ * reads -- and <prefix>.pss.gcbias.txt: the full-size windows with at least half of their letters A, C, G or T by GC percentage 0..100,
+ * with their mean depth and that depth relative to the mean of all of them (windows.h).  It is what `bedtools makewindows | bedtools
+ * coverage` and `bedtools nuc` give over the -O file, and the curve of a GC-bias plot.  -w alone writes no coverage summary.  Both files
+ * take their names when they are complete.  Goes with every option -c goes with: not with -I, SAM text is fine, one GPU.
  * Added: -a <sites> [-t <n>] counts, in the same pass, the bases the tallied reads show at listed sites, split by strand: the pileup at a
  * SNP panel.  The sites file holds one site per line, contig and 1-based position in its first two blank- or tab-separated columns
  * (further columns are ignored: a `samtools mpileup -l` positions file and an ANGSD -sites file both read; '#' lines and empty lines are
@@ -143,6 +150,7 @@
 #include "replicates.h"
 #include "report.h"
 #include "sam_reader.h"
+#include "windows.h"
 
 /* the options' names in the messages, each spelt once */
 static const char L_G[] = "-G (tables per read group)", L_S[] = "-S (tables per length bin)", L_C[] = "-C (tables per contig set)",
@@ -166,9 +174,10 @@ int main(int argc, char *argv[])
     const char *out_bam = NULL, *out_level_arg = NULL;
     const char *out_mask_arg = NULL;
     int out_deflate = 0, duplicates = 0, coverage = 0;
-    const char *bedgraph = NULL, *sites_fn = NULL, *trim_arg = NULL;
+    const char *bedgraph = NULL, *sites_fn = NULL, *trim_arg = NULL, *window_arg = NULL;
+    uint32_t window = 0;
 
-    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:P:y:YO:z:ZK:dcb:a:t:")) != -1) {
+    while ((option = getopt(argc, argv, ":F:B:o:R:r:l:L:q:U:D:mGS:C:Q:T:H:X:E:IAn:N:VJ:W:P:y:YO:z:ZK:dcb:a:t:w:")) != -1) {
         switch (option) {
         case 'F': fasta_fn = strdup(optarg); break;
         case 'B': bam_fn = strdup(optarg); break;
@@ -207,6 +216,7 @@ int main(int argc, char *argv[])
         case 'b': bedgraph = optarg; break;
         case 'a': sites_fn = optarg; break;
         case 't': trim_arg = optarg; break;
+        case 'w': window_arg = optarg; break;
         case 'R': read_group = strdup(optarg); break;
         case ':':
             fprintf(stderr, "Please enter required argument for option -%c.\n", optopt);
@@ -254,6 +264,7 @@ int main(int argc, char *argv[])
               "-d <flag duplicates before the tally: unpaired reads with the contig, position, length, strand (and, where the tables are split by read group, read group) of an earlier read; also write the duplication histogram (one GPU; not with -I)>\n"
               "-c <also write the depth of coverage of the tallied reads: per contig covered bases, breadth, mean and maximum depth, and the depth histogram (one GPU; not with -I)>\n"
               "-b <out.bedgraph> <also write the intervals the tallied reads cover, with their depth, as a bedGraph (one GPU; not with -I)>\n"
+              "-w <size> <also write, per window of <size> positions (16..1073741824), the GC content of the reference and the covered positions and depth of the tallied reads, and the GC-bias table of those windows (one GPU; not with -I)>\n"
               "-a <sites.txt> <also write the bases the tallied reads show at the listed sites (contig and 1-based position per line), split by strand (one GPU; not with -I)>\n"
               "-t <n> <with -a: leave the first and last n bases of each read out of the counts (0..65535, default: 0)>\n",
               stderr);
@@ -362,6 +373,19 @@ int main(int argc, char *argv[])
     }
     if ((coverage || bedgraph) && getenv("PSSBAM_NGPU") && atoi(getenv("PSSBAM_NGPU")) > 1) {
         fprintf(stderr, "%s keeps one depth array, on one GPU: not with PSSBAM_NGPU=%s.\n", coverage ? "-c" : "-b", getenv("PSSBAM_NGPU"));
+        exit(1);
+    }
+    /* -w: the same array as -c / -b, and their rules */
+    if (window_arg && pss_parse_window(window_arg, &window)) {
+        fprintf(stderr, "-w takes a window size, a whole number in %u..%u, not %s.\n", PSS_WINDOW_MIN, PSS_WINDOW_MAX, window_arg);
+        exit(1);
+    }
+    if (window_arg && gapped) {
+        fprintf(stderr, "-w (windowed depth and GC content) does not go with %s: the span of a clipped or gapped read is not defined.\n", L_I);
+        exit(1);
+    }
+    if (window_arg && getenv("PSSBAM_NGPU") && atoi(getenv("PSSBAM_NGPU")) > 1) {
+        fprintf(stderr, "-w keeps one depth array, on one GPU: not with PSSBAM_NGPU=%s.\n", getenv("PSSBAM_NGPU"));
         exit(1);
     }
     /* -a / -t: no row of the table below either (no counter words; they go with every option but -I) */
@@ -615,6 +639,7 @@ int main(int argc, char *argv[])
     if (duplicates) fprintf(stderr, " -d");
     if (coverage) fprintf(stderr, " -c");
     if (bedgraph) fprintf(stderr, " -b %s", bedgraph);
+    if (window_arg) fprintf(stderr, " -w %u", window);
     if (sites_fn) fprintf(stderr, " -a %s -t %u", sites_fn, site_trim);
     fputc('\n', stderr);
 
@@ -662,6 +687,7 @@ int main(int argc, char *argv[])
     frontend_opts.duplicates = duplicates;
     frontend_opts.coverage = coverage;
     frontend_opts.coverage_bedgraph = bedgraph;
+    frontend_opts.coverage_window = window;
     frontend_opts.sites = sites_fn ? &sites : NULL;
     frontend_opts.site_trim = site_trim;
     fprintf(stderr, "Reading genome sequence from:\n%s\n", fasta_fn);
@@ -701,6 +727,10 @@ int main(int argc, char *argv[])
         pss_write_coverage_bedgraph(bedgraph, res.cov_n, (const char *const *)res.cov_names, res.cov_n_runs, res.cov_run_ref, res.cov_run_start, res.cov_run_end,
                                     res.cov_run_depth))
         exit(1);   /* -b */
+    if (res.has_coverage && window &&
+        pss_write_windows(fasta_fn, bam_fn, out_prefix, window, res.cov_n, (const char *const *)res.cov_names, res.win_n, res.win_ref, res.win_start, res.win_end,
+                          res.win_acgt, res.win_gc, res.win_covered, res.win_depth_sum))
+        exit(1);   /* -w */
     if (res.has_alleles &&
         pss_write_alleles(fasta_fn, bam_fn, sites_fn, site_trim, out_prefix, res.allele_n_names, (const char *const *)res.allele_names, res.allele_n, res.allele_ref,
                           res.allele_pos, res.allele_base, res.allele_counts, res.allele_totals))
